@@ -6,7 +6,12 @@ frame (stream state persists in HBM from step to step).  Workload at N=1 = BASEL
 65,536 synthetic CELT-only fullband stereo streams, 160-byte LCG payloads.
 All packets of all timed steps are resident in HBM before the timed region starts.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps of the selected workload and prints its line.  --full adds everything else
+the bench measures or checks: the PCM check of the last timed step against the CPU oracle, the CPU baseline, the in-order
+step time, the other BASELINE configs (+ RFC mode and the host-buffer path) as `other_configs`, and for mixed_pages_2m the
+overlapped end-to-end run.  --dump-outputs DIR writes what the timed path left after its last step (see dump_outputs()).
 
 N > 1: one process per GPU under torch.distributed.run (RCCL).  When the driver has already started the ranks
 (WORLD_SIZE in the environment) this process is one of them and WORLD_SIZE must equal --gpus; when it has not,
@@ -15,7 +20,7 @@ bench.py ...` as a CHILD process, relays rank 0's JSON line and exits with the c
 
 Prints ONE JSON line on rank 0.  `value` = frames decoded by all ranks / max-over-ranks wall time.
 `roofline` prices the decode kernel against HBM peak using the ALGORITHMIC bytes per frame
-(B_celt = 21,633 B); `cpu_baseline` times the CPU oracle (a bit-identical port of
+(B_celt = 21,633 B); `cpu_baseline` (--full) times the CPU oracle (a bit-identical port of
 the reference path) on a bounded sample of the same workload on this host's cores.
 """
 import argparse
@@ -47,6 +52,7 @@ RFC_WORKLOAD = "rfc_mixed_64k"
 RFC_LOSS = 0.05
 MIX = ((0x0C, 40), (0x7C, 120), (0xFC, 160))  # mode of local stream s = s % 3: SILK-NB, hybrid FB, CELT FB
 PACKETS_PER_PAGE = 10
+OTHER_STEPS, OTHER_WARMUP = 50, 10  # --full: most timed / warm-up steps of the other BASELINE configs (see main)
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8.0 TB/s spec
 
 
@@ -72,6 +78,56 @@ def load_shard():
     sys.modules[name] = mod
     spec.loader.exec_module(mod)
     return mod
+
+
+def lcg_steps(ids, frames, L, seed_base, threads=1):
+    """The payloads of pkg.lcg_payloads(n, frames, L, seed_base)[f][ids], yielded one step f at a time as uint8 [len(ids), L]:
+    the same bytes, made by jumping each stream's generator L states per array operation in cache-sized blocks of streams
+    (`threads` threads), so that setting up many steps stays short and no step's packets outlive its upload."""
+    from concurrent.futures import ThreadPoolExecutor
+    A, C = np.empty(L, dtype=np.uint32), np.empty(L, dtype=np.uint32)
+    a, c = 1, 0
+    for i in range(L):  # state i + 1 after x: A[i] x + C[i] (mod 2^32)
+        a, c = (a * 1664525) & 0xFFFFFFFF, (c * 1664525 + 1013904223) & 0xFFFFFFFF
+        A[i], C[i] = a, c
+    x = np.uint32(seed_base) ^ np.asarray(ids, dtype=np.uint32)
+    n, B = len(x), 2048
+    bufs = [np.empty((B, L), dtype=np.uint32) for _ in range(threads)]
+
+    def block(t, out):
+        for lo in range(t * B, n, threads * B):
+            buf, xs = bufs[t][:min(n, lo + B) - lo], x[lo:lo + B]
+            np.multiply(xs[:, None], A, out=buf)
+            np.add(buf, C, out=buf)
+            xs[:] = buf[:, -1]
+            np.right_shift(buf, np.uint32(24), out=buf)
+            out[lo:lo + B] = buf
+
+    with ThreadPoolExecutor(threads) as ex:
+        for _ in range(frames):
+            out = np.empty((n, L), dtype=np.uint8)
+            list(ex.map(block, range(threads), [out] * threads))
+            yield out
+
+
+DUMP_PCM_BYTES = 48 << 20  # --dump-outputs: the PCM sample's size as float32 (the whole dump stays below 64 MB)
+
+
+def dump_outputs(path, pcm, res, seed=0x5EED):
+    """--dump-outputs: what the timed path left after its last step, by stream id -- pcm int16 [n, samples, 2] and the return
+    codes res [n] -- as .npy files under `path`: result.npy (every stream's return code, float64), pcm_energy.npy (every stream's
+    sum of squared samples, exact in float64), pcm.npy (the PCM of a fixed, seeded sample of streams, float32; all of them when
+    they fit DUMP_PCM_BYTES) and pcm_streams.npy (the ids of that sample, float64)."""
+    os.makedirs(path, exist_ok=True)
+    n = pcm.shape[0]
+    flat = pcm.reshape(n, -1)
+    s = min(n, DUMP_PCM_BYTES // (flat.shape[1] * 4))
+    pick = np.arange(n) if s == n else np.sort(np.random.default_rng(seed).choice(n, s, replace=False))
+    energy = np.concatenate([np.einsum("ij,ij->i", b, b) for b in (flat[lo:lo + 4096].astype(np.float64) for lo in range(0, n, 4096))])
+    np.save(os.path.join(path, "pcm.npy"), pcm[pick].astype(np.float32))
+    np.save(os.path.join(path, "pcm_streams.npy"), pick.astype(np.float64))
+    np.save(os.path.join(path, "pcm_energy.npy"), energy)
+    np.save(os.path.join(path, "result.npy"), np.asarray(res, dtype=np.float64))
 
 
 def cpu_baseline(toc, L, seconds_target=12.0):
@@ -324,9 +380,10 @@ def launch_ranks(args, argv):
     return proc.returncode
 
 
-def check_against_oracle(pkg, ctx, name, n, frames, d_pcm, pay=None, pages_seed=None, slot_stream=None):
+def check_against_oracle(pkg, ctx, name, n, frames, d_pcm, pay_of=None, pages_seed=None, slot_stream=None):
     """After the timed region: the last step's PCM of >= 256 streams spread over the batch against the CPU oracle (which
     decodes those streams' whole history: warm-up + timed steps).  Raises on a mismatch.
+    pay_of(ids): the payloads of those streams' steps, uint8 [frames, len(ids), L] (single-mode workloads).
     slot_stream: stream id of every PCM slot of the last step (step tables grouped by mode are not in stream order)."""
     import zlib
     import oracle_py
@@ -336,10 +393,16 @@ def check_against_oracle(pkg, ctx, name, n, frames, d_pcm, pay=None, pages_seed=
     ctx.d2h(out, d_pcm)
     slot_of = np.arange(n) if slot_stream is None else np.argsort(slot_stream)
     refs = {}
-    if pay is not None:
+    if pay_of is not None:
+        # a few streams per oracle call on the CPUs granted: the oracle keeps every frame's PCM of the streams it decodes
+        from concurrent.futures import ThreadPoolExecutor
         toc = WORKLOADS[name][0]
-        ref, _ = o.batch_decode(2, toc, np.ascontiguousarray(pay[:frames][:, pick]))
-        refs = {int(s): ref[i, frames - 1] for i, s in enumerate(pick)}
+
+        def last_pcm(ids):
+            return o.batch_decode(2, toc, np.ascontiguousarray(pay_of(ids)))[0][:, frames - 1]
+
+        with ThreadPoolExecutor(load_shard().usable_cpus()) as ex:
+            refs = dict(zip(pick.tolist(), (r for ref in ex.map(last_pcm, np.array_split(pick, -(-len(pick) // 4))) for r in ref)))
     else:  # mixed pages: stream s has mode s % 3 and payload row s // 3 of that mode's generator
         for m, (toc, L) in enumerate(MIX):
             sel = pick[pick % 3 == m]
@@ -409,8 +472,9 @@ def kernels_of(name):
     return "k_silk_parse + k_silk_params + k_silk_synth + k_celt_parse + k_celt_recon + k_celt_post" if split_silk else "k_decode_step"
 
 
-def run_workload(name, args, ranks, pkg, ctx, n_override=0, cpu=True):
-    """One workload: W warm-up steps, K timed steps between barriers, PCM check, roofline, CPU baseline.  -> dict (rank 0)."""
+def run_workload(name, args, ranks, pkg, ctx, n_override=0, cpu=True, dump=None):
+    """One workload: W warm-up steps, K timed steps between barriers, roofline; with --full the PCM check and (cpu) the CPU
+    baseline; dump: the directory --dump-outputs names (rank 0 writes it).  -> dict (rank 0)."""
     shard = load_shard()
     rank, world = ranks.rank, ranks.world
     toc, L, bytes_per_frame, default_streams = WORKLOADS[name]
@@ -420,12 +484,16 @@ def run_workload(name, args, ranks, pkg, ctx, n_override=0, cpu=True):
     if mixed:  # stream s has mode s % 3: 262,144 streams per GPU are 87,382 SILK-NB + 87,381 hybrid + 87,381 CELT (8 ranks: 2,097,152 pages)
         bytes_per_frame = sum(len(range(m, n, 3)) * b for m, b in enumerate((5953, 24945, 21633))) / n
     ctx.streams_alloc(n, 2)
-    ingest, pay, e2e = None, None, None
+    ingest, e2e, slot_stream = None, None, None
     frees = []
     d_pcm = ctx.dev_alloc(n * 960 * 2 * 2)
     d_res = ctx.dev_alloc(4 * n)
     frees += [d_pcm, d_res]
     if mixed:
+        step_bytes = sum(len(range(m, n, 3)) * (L_m + 1) for m, (_, L_m) in enumerate(MIX))
+        if (K + W) * step_bytes > 0x7FFFFFFF:  # (opusgpu_pages_demux: one arena per call, 32-bit descriptor offsets)
+            raise SystemExit(f"{name}: {K + W} steps of {n} streams are {(K + W) * step_bytes / 2**30:.1f} GiB of packets; the page demux "
+                             f"takes at most 2 GiB in one call: --steps + --warmup <= {0x7FFFFFFF // step_bytes}")
         # work arrives at rank 0 as Ogg pages and is scattered: the path's one exchange step, before the timed region
         t_in0 = time.perf_counter()
         base, lay, ingest, _keep = prepare_pages_work(pkg, shard, ranks, ctx, n, K + W, args.ingest, args.page_crc)
@@ -445,16 +513,14 @@ def run_workload(name, args, ranks, pkg, ctx, n_override=0, cpu=True):
     else:
         # streams are sharded across ranks with no data-path exchange: each rank owns streams
         # [rank*n, (rank+1)*n) of the global id space (seeds differ per global stream id)
-        pay = pkg.lcg_payloads(n, K + W, L, seed_base=ranks.seed_base())
         d_arena, d_desc = [], []
         # SILK-only / hybrid workloads: every step's table in the order of the frames' LBRR flags (the top bits of their first byte),
         # so that the 32 frames of a parse wave agree on how many extra frames of side information they read past -- framing work,
         # like grouping a page step's table by mode; BENCH_ORDER_BY_HEADER=0: stream order
         by_header = os.environ.get("BENCH_ORDER_BY_HEADER", "1") != "0" and not (toc & 0x80)
-        last_slot_stream = None
-        for f in range(K + W):
-            arena, descs = pkg.build_step(toc, pay[f], order_by_header=by_header)
-            last_slot_stream = descs["stream"].astype(np.int64) if by_header else None
+        for pay_f in lcg_steps(np.arange(n), K + W, L, ranks.seed_base(), threads=min(8, shard.usable_cpus())):
+            arena, descs = pkg.build_step(toc, pay_f, order_by_header=by_header)
+            slot_stream = descs["stream"].astype(np.int64) if by_header else None
             a = ctx.dev_alloc(arena.nbytes + 16)
             d = ctx.dev_alloc(descs.nbytes)
             ctx.h2d(a, arena)
@@ -503,14 +569,24 @@ def run_workload(name, args, ranks, pkg, ctx, n_override=0, cpu=True):
     ctx.d2h(res, d_res)
     if not (res == 960).all():
         raise SystemExit(f"{name}: decode failed for {(res != 960).sum()} frames in the last step")
-    # parity of what was just timed: last step's PCM of >= 256 streams vs the CPU oracle (every rank checks its own)
-    if mixed:
-        r = rank
+    if mixed and (args.full or dump):
         last = np.zeros(n, dtype=pkg.DESC_DTYPE)
         import ctypes
         at = base.value if isinstance(base, ctypes.c_void_p) else int(base)
         ctx.d2h(last, ctypes.c_void_p(at + lay.desc_at[K + W - 1]))
-        parity = check_against_oracle(pkg, ctx, name, n, K + W, d_pcm, slot_stream=last["stream"].astype(np.int64),
+        slot_stream = last["stream"].astype(np.int64)
+    if dump and rank == 0:
+        pcm = np.zeros((n, 960, 2), dtype=np.int16)
+        ctx.d2h(pcm, d_pcm)
+        if slot_stream is not None:  # slot j of the step belongs to stream slot_stream[j]
+            pcm[slot_stream], res[slot_stream] = pcm.copy(), res.copy()
+        dump_outputs(dump, pcm, res)
+        del pcm
+    parity = None
+    # parity of what was just timed: last step's PCM of >= 256 streams vs the CPU oracle (every rank checks its own)
+    if mixed and args.full:
+        r = rank
+        parity = check_against_oracle(pkg, ctx, name, n, K + W, d_pcm, slot_stream=slot_stream,
                                       pages_seed=lambda m: (0x9E3779B9 ^ (r * 0x01000193) ^ (m * 0x5bd1e995)) & 0xFFFFFFFF)
         if RAW_PAGES and os.environ.get("BENCH_E2E", "1") != "0":  # (BENCH_E2E=0: profiling runs count the timed steps' kernels only)
             timed_pcm = np.zeros((n, 960, 2), dtype=np.int16)
@@ -521,8 +597,9 @@ def run_workload(name, args, ranks, pkg, ctx, n_override=0, cpu=True):
             e2e = {"wall_s": ranks.max_over_ranks(e2e_stats["wall_s"]), "pages": ranks.sum_over_ranks(e2e_stats["pages"]),
                    "rank0": e2e_stats}
             del timed_pcm, e2e_pcm
-    else:
-        parity = check_against_oracle(pkg, ctx, name, n, K + W, d_pcm, pay=pay, slot_stream=last_slot_stream)
+    elif args.full:
+        parity = check_against_oracle(pkg, ctx, name, n, K + W, d_pcm, slot_stream=slot_stream,
+                                      pay_of=lambda ids: np.stack(list(lcg_steps(ids, K + W, L, ranks.seed_base()))))
 
     value, dt, total_frames = shard.aggregate_throughput(ranks, n * K, dt)
     for p in frees:
@@ -566,6 +643,8 @@ def run_workload(name, args, ranks, pkg, ctx, n_override=0, cpu=True):
                      "valu_issue": valu_issue_for(name, n, avg_kernel_s * 1e3)},
         "parity_check": parity,
     }
+    if parity is None:  # (--full only)
+        del out["parity_check"]
     if ingest is not None:
         # host page demux + scatter happen before the timed region and are never part of `value`; the end-to-end figure
         # prices them in: all pages of the job / (ingest wall time + the decode steps those pages make)
@@ -616,16 +695,17 @@ def rfc_frame_bytes(toc, L, lost):
     return b
 
 
-def run_rfc_workload(args, ranks, pkg, ctx, n_override=0, cpu=True):
+def run_rfc_workload(args, ranks, pkg, ctx, n_override=0, cpu=True, selected=False, dump=None):
     """RFC mode, one measured line: every TOC configuration, lost packets and forward error correction through the device-resident
-    entry (opusgpu_decode_step_device in OPUSGPU_MODE_RFC: one k_decode_rfc launch per step).  -> dict (rank 0)."""
+    entry (opusgpu_decode_step_device in OPUSGPU_MODE_RFC: one k_decode_rfc launch per step).  selected: the workload --workload
+    names (--steps / --warmup as given; as one of the other configs at most 8 + 2); dump: as run_workload's.  -> dict (rank 0)."""
     import zlib
     import rfc_common
     import oracle_py
     shard = load_shard()
     rank, world = ranks.rank, ranks.world
     n = n_override or 65536
-    K, W = min(args.steps, 8), min(args.warmup, 2)
+    K, W = (args.steps, args.warmup) if selected else (min(args.steps, 8), min(args.warmup, 2))
     F = K + W
     rng = np.random.default_rng(0xC0DEC + rank)
     cfg = np.arange(n) % 32
@@ -711,27 +791,33 @@ def run_rfc_workload(args, ranks, pkg, ctx, n_override=0, cpu=True):
     ctx.d2h(res, d_res)
     if not (res == durs).all():
         raise SystemExit(f"{RFC_WORKLOAD}: {(res != durs).sum()} frames of the last step did not return their TOC's duration")
-    # parity of what was timed: the last step's PCM of 10 streams per configuration against the oracle's RFC mode, which decodes,
-    # conceals and recovers those streams' whole history
-    pick = np.unique(np.concatenate([np.arange(0, n, max(1, n // 320)), np.arange(n - 32, n)])).astype(np.int64)
-    out = np.zeros((n, 2880, 2), dtype=np.int16)
-    ctx.d2h(out, d_pcm)
-    o = oracle_py.load()
-    big = np.concatenate(host_arena)
-    ref, rets = o.batch_decode_rfc(2, big, offs[:, pick], lens[:, pick], ops[:, pick])
-    crc, bad = 0, []
-    for i, s_ in enumerate(pick):
-        D = int(durs[s_])
-        if rets[i, F - 1] != D or not np.array_equal(out[s_, :D], ref[i, :D]):
-            bad.append(int(s_))
-        crc = zlib.crc32(out[s_, :D].tobytes(), crc)
-    if bad:
-        raise SystemExit(f"{RFC_WORKLOAD}: GPU PCM of the last timed step differs from the CPU oracle's RFC mode for streams {bad[:8]} "
-                         f"({len(bad)} of {len(pick)} checked)")
-    parity = {"streams_checked": len(pick), "frames_of_history": F,
-              "lost_or_recovered_in_last_step": int((ops[F - 1, pick] != 0).sum()),
-              "result": "last timed step bit-exact vs the CPU oracle's RFC mode (itself parity-unpinned: DESIGN.md section 11)",
-              "pcm_crc32": f"{crc:08x}"}
+    out, parity = None, None
+    if dump or args.full:
+        out = np.zeros((n, 2880, 2), dtype=np.int16)
+        ctx.d2h(out, d_pcm)
+    if dump and rank == 0:  # a frame's PCM is its first D samples: what lies behind them is no output
+        dump_outputs(dump, np.where((np.arange(2880)[None, :] < durs[:, None])[:, :, None], out, np.int16(0)), res)
+    if args.full:
+        # parity of what was timed: the last step's PCM of 10 streams per configuration against the oracle's RFC mode, which decodes,
+        # conceals and recovers those streams' whole history
+        pick = np.unique(np.concatenate([np.arange(0, n, max(1, n // 320)), np.arange(n - 32, n)])).astype(np.int64)
+        o = oracle_py.load()
+        big = np.concatenate(host_arena)
+        ref, rets = o.batch_decode_rfc(2, big, offs[:, pick], lens[:, pick], ops[:, pick])
+        crc, bad = 0, []
+        for i, s_ in enumerate(pick):
+            D = int(durs[s_])
+            if rets[i, F - 1] != D or not np.array_equal(out[s_, :D], ref[i, :D]):
+                bad.append(int(s_))
+            crc = zlib.crc32(out[s_, :D].tobytes(), crc)
+        if bad:
+            raise SystemExit(f"{RFC_WORKLOAD}: GPU PCM of the last timed step differs from the CPU oracle's RFC mode for streams {bad[:8]} "
+                             f"({len(bad)} of {len(pick)} checked)")
+        parity = {"streams_checked": len(pick), "frames_of_history": F,
+                  "lost_or_recovered_in_last_step": int((ops[F - 1, pick] != 0).sum()),
+                  "result": "last timed step bit-exact vs the CPU oracle's RFC mode (itself parity-unpinned: DESIGN.md section 11)",
+                  "pcm_crc32": f"{crc:08x}"}
+    del out
     timed = ops[W:]
     alg = sum(rfc_frame_bytes(int(toc_of[c]), int(L_of[c]), False) * int(((cfg == c)[None, :] & (timed != 1)).sum()) +
               rfc_frame_bytes(int(toc_of[c]), int(L_of[c]), True) * int(((cfg == c)[None, :] & (timed == 1)).sum()) for c in range(32))
@@ -767,7 +853,11 @@ def run_rfc_workload(args, ranks, pkg, ctx, n_override=0, cpu=True):
                      "avg_launch_ms": avg_kernel_s * 1e3, "algorithmic_bytes_per_frame": alg / K / n, "frames_per_launch": n},
         "parity_check": parity,
     }
+    if parity is None:  # (--full only)
+        del out_line["parity_check"]
     if cpu and not args.no_cpu_baseline:
+        o = oracle_py.load()
+        big = np.concatenate(host_arena)
         cores = shard.usable_cpus()
         ns = min(n, 4096)
         t1 = time.perf_counter()
@@ -822,16 +912,23 @@ def main():
     ap.add_argument("--window", default="on", choices=["on", "off"],
                     help="queue the K timed steps with ONE opusgpu_decode_steps_device call (the library then orders the kernels of "
                          "neighbouring pipelined steps by dependencies); off: one opusgpu_decode_step_device_modes call per step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything the bench measures or checks besides the headline: PCM check against the CPU oracle, CPU baseline, "
+                         "in-order step time, other configs, overlapped end-to-end ingest (default: the selected workload's timed steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path left after its last step to DIR/*.npy (float32 / float64, below 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU work of the headline workload's cpu_baseline sample")
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="start / join the ranks, check the rank count, print a line and stop: no GPU work (the CPU test of "
                          "the launcher path runs this with OPUSGPU_DIST_BACKEND=gloo)")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="only the selected workload (default: the other BASELINE configs follow as other_configs)")
+                    help="--full with the selected workload only (else the other BASELINE configs follow as other_configs)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # not started by a launcher: start the ranks ourselves, as a child job, before anything here touches the GPU
         sys.exit(launch_ranks(args, sys.argv[1:]))
@@ -858,7 +955,7 @@ def main():
     ctx = pkg.Context(local_rank)
     ctx.set_pipeline(args.pipeline == "on")
     if args.workload == RFC_WORKLOAD:  # not a BASELINE config: its own line, same fields
-        o = run_rfc_workload(args, ranks, pkg, ctx, n_override=args.streams)
+        o = run_rfc_workload(args, ranks, pkg, ctx, n_override=args.streams, cpu=args.full, selected=True, dump=args.dump_outputs)
         if rank == 0:
             o.update({"metric": "decoded 48 kHz stereo frames/sec/GPU, RFC mode (x real-time); HBM GB/s vs roofline", "n_gpus": world,
                       "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "data": "synthetic",
@@ -867,8 +964,8 @@ def main():
         ranks.close()
         ctx.close()
         return
-    main_out = run_workload(args.workload, args, ranks, pkg, ctx, n_override=args.streams)
-    if args.pipeline == "on" and not args.no_other_configs:
+    main_out = run_workload(args.workload, args, ranks, pkg, ctx, n_override=args.streams, cpu=args.full, dump=args.dump_outputs)
+    if args.full and args.pipeline == "on" and not args.no_other_configs:
         # the same workload with nothing queued ahead: one in-order step per call (what a caller gets that hands over one step at a
         # time and needs it back before the next -- the headline `value` is the pipelined window, K x 20 ms of audio buffered per stream)
         saved = (args.pipeline, args.steps, args.warmup)
@@ -881,16 +978,20 @@ def main():
             main_out["config"]["in_order_ms_per_step"] = o["ms_per_step"]
             main_out["config"]["workload"] += f"; in order, one step per call: {o['ms_per_step']:.3f} ms per step"
     others = []
-    if not args.no_other_configs and args.workload == "celt_fb_stereo_64k" and not args.streams:
+    if args.full and not args.no_other_configs and args.workload == "celt_fb_stereo_64k" and not args.streams:
         # the other BASELINE configs (3, 4, and one GPU's share of 5), timed the same way in the same run; their CPU
-        # baselines get a smaller sample so that the default run stays within a few minutes
+        # baselines get a smaller sample so that the --full run stays within a few minutes
+        # They are timed over at most OTHER_STEPS + OTHER_WARMUP steps, whatever the headline's --steps: mixed_pages_2m's page demux
+        # takes at most 76 steps of its 262,144 streams in one call, and the rest of the run stays within minutes.
         saved = args.cpu_seconds
         args.cpu_seconds = 5.0
+        args.steps, args.warmup = min(K, OTHER_STEPS), min(W, OTHER_WARMUP)
         for name in ("silk_nb_stereo_64k", "hybrid_fb_stereo_256k", "mixed_pages_2m"):
             o = run_workload(name, args, ranks, pkg, ctx)
             if o is not None:
-                o["name"] = name
+                o.update({"name": name, "steps": args.steps, "warmup": args.warmup})
                 others.append(o)
+        args.steps, args.warmup = K, W
         o = run_rfc_workload(args, ranks, pkg, ctx)
         if o is not None:
             others.append(o)

@@ -7,7 +7,7 @@ mkdir -p gpurun_out/$tag
 for round in 1 2; do
   for wl in $wls; do
     for l in $libs; do
-      OPUSGPU_LIB=$PWD/build_ab/lib_$l.so timeout -k 10 200 python3 bench.py --workload $wl --steps $steps --warmup 3 --no-cpu-baseline --no-other-configs \
+      OPUSGPU_LIB=$PWD/build_ab/lib_$l.so timeout -k 10 200 python3 bench.py --workload $wl --steps $steps --warmup 3 --full --no-cpu-baseline --no-other-configs \
         > gpurun_out/$tag/b_${l}_${wl}_$round.json 2> gpurun_out/$tag/b_${l}_${wl}_$round.err || { echo "FAILED $l $wl"; tail -3 gpurun_out/$tag/b_${l}_${wl}_$round.err; exit 1; }
       python3 - "$l" "$wl" "$round" gpurun_out/$tag/b_${l}_${wl}_$round.json <<'PY'
 import json, sys

@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
-"""Container-only check: every table in the generated rom_tables.h that has a counterpart in the reference
-sources is value-for-value identical to the reference's literal (read as TEXT from /root/reference/src).
-Run by tests/test_rom_tables.py when /root/reference exists; skipped on the GPU box."""
+"""Check that every table in the generated rom_tables.h that has a counterpart in the reference sources is
+value-for-value identical to the reference's literal (read as TEXT from the reference's src/ directory, REF).
+--record PATH writes what the check compares against as value counts and SHA-256 digests
+(tests/golden/rom_reference_tables.json), so that tests/test_rom_tables.py can check the tables without the reference."""
+import hashlib
+import json
 import os
 import re
 import sys
@@ -44,7 +47,45 @@ def parse_arrays(text, macros=None):
     return out
 
 
+def digest(vals):
+    """SHA-256 of a table's values as little-endian int64."""
+    return hashlib.sha256(b"".join(int(v).to_bytes(8, "little", signed=True) for v in vals)).hexdigest()
+
+
+def pvq_u_rows(rows, data):
+    """The reference's ragged PVQ U(n,k) rows (celt.cpp:75-183, row offsets :651): per row n, [n, k0, k1) with the values
+    data[rows[n] + k] for k in [k0, k1)."""
+    out = []
+    for n in range(15):
+        end = (rows[n + 1] + n + 1) if n < 14 else len(data)
+        out.append((n, n, max(n, end - rows[n])))
+    return out
+
+
+def record(path):
+    """The fixture keeps this project's table names and, of the reference's tables, value counts and digests only."""
+    macros = {"OFFSET_VL_Q10": 32, "OFFSET_VH_Q10": 100, "OFFSET_UVL_Q10": 100, "OFFSET_UVH_Q10": 240}
+    ref = parse_arrays(open(os.path.join(REF, "celt.cpp")).read())
+    ref.update(parse_arrays(open(os.path.join(REF, "silk.cpp")).read(), macros))
+    rows, data = ref["row_idx"], ref["CELT_PVQ_U_DATA"]
+    spans = pvq_u_rows(rows, data)
+    out = {
+        "source": "the reference's table literals as tools/check_rom_tables.py parses them, kept as value counts and SHA-256 "
+                  "digests of the values as little-endian int64 (check_rom_tables.digest): per table of PAIRS under our name, "
+                  "the set of all its tables (SILK tables are matched by content), and the PVQ U(n,k) entries of its ragged rows",
+        "pairs": {mine: {"count": len(ref[theirs]), "sha256": digest(ref[theirs])} for mine, theirs in PAIRS.items()},
+        "all_tables_sha256": sorted({digest(v) for v in ref.values()}),
+        "pvq_u": {"rows": spans, "sha256": digest([data[rows[n] + k] for n, k0, k1 in spans for k in range(k0, k1)])},
+    }
+    with open(path, "w") as fh:
+        json.dump(out, fh, indent=1)
+        fh.write("\n")
+
+
 def main():
+    if len(sys.argv) == 3 and sys.argv[1] == "--record":
+        record(sys.argv[2])
+        return 0
     if not os.path.isdir(REF):
         print("reference not present: nothing to check")
         return 0

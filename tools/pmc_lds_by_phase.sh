@@ -2,7 +2,7 @@
 # usage (GPU box): tools/pmc_lds_by_phase.sh lib1.so lib2.so ...   -- LDS counters of k_celt_recon_fb for ablated builds
 # (tools/build_variant.sh <name> -DOG_RABL=n: the kernel returns after stage n -- 1 staging, 2 leaf pass, 3 band loop; "default" =
 # the whole kernel).  The differences between consecutive builds attribute bank conflicts to the phases.  The ablated builds
-# produce wrong PCM on purpose: the bench's parity check fails after the counters are in.
+# produce wrong PCM on purpose: a plain bench run does not check it (with --full its parity check fails after the counters are in).
 export TMPDIR=/tmp
 for lib in "$@"; do
   tag=$(basename $lib .so)
