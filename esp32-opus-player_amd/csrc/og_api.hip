@@ -30,6 +30,15 @@ static_assert(sizeof(opusgpu_frame_desc) == sizeof(FrameDesc), "descriptor layou
 enum { OPUSGPU_COPY_PIECES = 16, OPUSGPU_COPY_THREADS = 8 };
 
 // ---- kernels --------------------------------------------------------------------------------------
+// OPUSGPU_STALL_STREAM / OPUSGPU_STALL_US (og_debug.hpp): one wave that holds its stream for `ticks` of the device wall clock.  It
+// writes no memory, and `max_spins` ends its loop whatever the clock reads.
+#ifndef OG_STALL_MAX_SPINS
+#define OG_STALL_MAX_SPINS (1 << 20) // (each spin sleeps >= 512 cycles: 100 ms, the longest stall asked for, is < 470,000 spins at 2.4 GHz)
+#endif
+__global__ void __launch_bounds__(64) k_stream_stall(long long ticks, int max_spins) {
+    const long long t0 = wall_clock64();
+    for (int i = 0; i < max_spins && wall_clock64() - t0 < ticks; i++) __builtin_amdgcn_s_sleep(8);
+}
 __global__ void __launch_bounds__(64) k_stream_init(StreamState *st, int first, int count, int channels, int full) {
     const int s = first + (int)blockIdx.x;
     if ((int)blockIdx.x >= count) return;
@@ -654,6 +663,7 @@ struct HostPool {
 #ifndef OG_SILK_SETS
 #define OG_SILK_SETS 3 // sets of SILK records and hand-offs that pipelined SILK / hybrid steps rotate through
 #endif
+static_assert(OG_SILK_SETS >= 2, "a pipelined SILK / hybrid step runs next to the step before it");
 struct opusgpu_ctx {
     int device = -1;
     hipStream_t stream = nullptr;
@@ -713,6 +723,7 @@ struct opusgpu_ctx {
     hipEvent_t ev_parsed = nullptr; // step k: its early parse has finished (on parse_stream)
     hipEvent_t ev_recon = nullptr;  // step k: its reconstruction has finished (on recon_stream)
     hipEvent_t ev_post[3] = {};     // by slot: k_celt_post of the last step that used it has finished (on the step's stream)
+    long long stall_ticks = 0;      // OPUSGPU_STALL_US in ticks of the device wall clock (0: no stalls, og_debug.hpp)
     const void *last_recs = nullptr;
     // Steps queued as a window (opusgpu_decode_steps_device): the kernels of neighbouring steps are placed in the order that
     // works -- the next step's parse, then this step's reconstruction, then the de-emphasis of the step before -- by stream
@@ -787,6 +798,15 @@ int opusgpu_ctx_create(int device, opusgpu_ctx **out) {
     ctx->fast_recon = og_debug().fast_recon;
     ctx->parse_groups = og_debug().parse_groups;
     ctx->host_parts = og_debug().host_parts;
+    if (og_debug().stall_us) {
+        int khz = 0;
+        if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device) != hipSuccess || khz <= 0) {
+            (void)hipGetLastError();
+            delete ctx;
+            return OPUSGPU_ERR_HIP;
+        }
+        ctx->stall_ticks = (long long)og_debug().stall_us * khz / 1000;
+    }
     if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) {
         delete ctx;
         return OPUSGPU_ERR_HIP;
@@ -1073,12 +1093,21 @@ static int decode_step_impl(opusgpu_ctx *ctx, int n, const void *d_descs, const 
     if ((uintptr_t)d_arena & 15) return OPUSGPU_BAD_ARG; // (the parse kernels fetch packets as aligned 16-byte pieces, og_range.hpp)
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
     const int pcm_stride = (ctx->mode == OPUSGPU_MODE_RFC ? OPUSGPU_RFC_FRAME_SAMPLES : OPUSGPU_FRAME_SAMPLES) * ctx->channels;
+    // OPUSGPU_STALL_STREAM (og_debug.hpp): in front of every kernel of the step on the named stream, a wave that holds that stream --
+    // it falls behind the others by whole steps, and only the events between the streams keep the kernels in order
+    auto stall = [&](hipStream_t q) {
+        if (!ctx->stall_ticks) return;
+        const int w = og_debug().stall_stream;
+        hipStream_t const t = w == 1 ? s : w == 2 ? ctx->parse_stream : w == 3 ? ctx->recon_stream : ctx->side_stream;
+        if (t && q == t) hipLaunchKernelGGL(k_stream_stall, dim3(1), dim3(64), 0, q, ctx->stall_ticks, (int)OG_STALL_MAX_SPINS);
+    };
     ctx->last_descs = d_descs;
     ctx->last_n = ctx->mode == OPUSGPU_MODE_RFC || !ctx->split_celt ? 0 : n;
     ctx->last_had_silk_recs = ctx->split_celt && ctx->split_hybrid;
     if (ctx->mode == OPUSGPU_MODE_RFC) { // every frame on the one kernel of that mode (og_rfc.hip)
         HIPCHK(ctx, hipSetDevice(ctx->device));
         if (int rc = enter_step_kind(ctx, 0, s)) return rc;
+        stall(s);
         og_launch_decode_rfc(s, d_descs, d_arena, ctx->d_streams, d_pcm, d_result, n, ctx->n_streams, pcm_stride);
         HIPCHK(ctx, hipGetLastError());
         if (ctx->pipeline) { // (a later pipelined step's early parse waits for all of this one)
@@ -1091,6 +1120,7 @@ static int decode_step_impl(opusgpu_ctx *ctx, int n, const void *d_descs, const 
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (!ctx->split_celt) { // OPUSGPU_SPLIT=0 (A/B measurements): every frame through the single kernel, in order
         if (int rc = enter_step_kind(ctx, 0, s)) return rc;
+        stall(s);
         hipLaunchKernelGGL(k_decode_step, dim3(n), dim3(64), 0, s, (const FrameDesc *)d_descs, (const u8 *)d_arena, ctx->d_streams,
                            (i16 *)d_pcm, (i32 *)d_result, n, ctx->n_streams, pcm_stride, 0, nullptr, nullptr, 0);
         HIPCHK(ctx, hipGetLastError());
@@ -1162,6 +1192,7 @@ static int decode_step_impl(opusgpu_ctx *ctx, int n, const void *d_descs, const 
     auto front = [&](hipStream_t q, size_t f0, int cnt, SilkShadow *shadow = nullptr, u32 epoch = 0, hipStream_t pq = nullptr) {
         const FrameDesc *dd = (const FrameDesc *)d_descs + f0;
         if (srecs) {
+            stall(q);
             // (64 frames per wave where the kernel's issue slots are what counts: pipelined steps, large batches; 32 for a small
             // in-order step, whose time is the latency of one wave's serial chain -- same-box: SILK-NB in order 1.36 / 1.41 ms)
             if (shadow || cnt >= OG_SILK_PARSE_WIDE_MIN || og_debug().parse_wide == 2)
@@ -1174,10 +1205,12 @@ static int decode_step_impl(opusgpu_ctx *ctx, int n, const void *d_descs, const 
                 (void)hipEventRecord(ctx->ev_sp, q);
                 (void)hipStreamWaitEvent(pq, ctx->ev_sp, 0);
             }
+            stall(pq ? pq : q);
             hipLaunchKernelGGL(k_silk_params, dim3((cnt + OG_PAR_LANES / 2 - 1) / (OG_PAR_LANES / 2)), dim3(64), 0, pq ? pq : q, dd,
                                (const StreamState *)ctx->d_streams, srecs + f0, cnt, ctx->n_streams, shadow, epoch);
             if (pq && pq != q) (void)hipEventRecord(ctx->ev_spar, pq);
         }
+        if (any_celt) stall(q);
         if (any_celt && ((shadow && og_debug().parse_wide) || og_debug().parse_wide == 2)) { // (a pipelined step: the wide parse, like pipelined CELT-only steps)
             const int fr = og_celt_parse64_frames();
             og_launch_celt_parse64(q, (cnt + fr - 1) / fr, dd, d_arena, ctx->d_streams, recs + f0, cnt, ctx->n_streams,
@@ -1191,7 +1224,9 @@ static int decode_step_impl(opusgpu_ctx *ctx, int n, const void *d_descs, const 
     // `rq` (pipelined SILK / hybrid steps): the stream the CELT reconstruction runs on, NEXT TO the SILK synthesis instead of behind
     // it -- a hybrid frame's two halves share nothing until the de-emphasis adds them (the synthesis takes prev_mode from the record,
     // SilkRec::prev_mode), and the reconstruction of step k touches nothing the de-emphasis of step k - 1 still reads (it appends to
-    // the history ring; k_celt_post reads at the position the reconstruction recorded, as in pipelined CELT-only steps)
+    // the history ring; k_celt_post reads at the position the reconstruction recorded, as in pipelined CELT-only steps).  The ring
+    // holds two frames (2 x 960 of 2,048 samples): the reconstruction of step k waits for the last kernel of step k - 2, whose
+    // de-emphasis reads where it writes -- nothing else orders the two (the parse of step k waits only for step k - OG_SILK_SETS)
     auto back_half = [&](hipStream_t q, size_t f0, int cnt, hipStream_t rq = nullptr) {
         const FrameDesc *dd = (const FrameDesc *)d_descs + f0;
         i16 *pp = (i16 *)d_pcm + f0 * (size_t)pcm_stride;
@@ -1201,18 +1236,27 @@ static int decode_step_impl(opusgpu_ctx *ctx, int n, const void *d_descs, const 
         if (srecs) { // SILK-only frames and the SILK half of hybrid frames
             // (a step that may hold SILK-only frames: the narrowband ones in the kernel whose LDS is sized for them, og_silk_nb.hip)
             const int nb = (modes & 1) && og_debug().silk_nb_kernel;
+            stall(q);
             if (nb) og_launch_silk_synth_nb(q, dd, d_arena, ctx->d_streams, pp, rr, cnt, ctx->n_streams, pcm_stride, handoff + f0, srecs + f0, 1);
+            if (nb) stall(q);
             og_launch_silk_synth(q, dd, d_arena, ctx->d_streams, pp, rr, cnt, ctx->n_streams, pcm_stride, handoff + f0, srecs + f0, nb);
             others = true;
         } else if (any_silk) { // every frame that is not CELT-only (OPUSGPU_SPLIT_HYBRID=0)
+            stall(q);
             hipLaunchKernelGGL(k_decode_step, dim3(cnt), dim3(64), 0, q, dd, (const u8 *)d_arena, ctx->d_streams, pp, rr, cnt, ctx->n_streams,
                                pcm_stride, 1, nullptr, nullptr, 0);
             others = true;
         }
         if (any_celt) {
             hipStream_t const r = rq ? rq : q;
-            if (rq) (void)hipStreamWaitEvent(rq, ctx->ev_sparsed, 0); // (this step's CELT parse)
+            if (rq) {
+                (void)hipStreamWaitEvent(rq, ctx->ev_sparsed, 0); // (this step's CELT parse)
+                const int two_back = (sset + OG_SILK_SETS - 2) % OG_SILK_SETS; // (recorded after this step's kernels: still step k - 2's)
+                if (ctx->sdone_recorded[two_back]) (void)hipStreamWaitEvent(rq, ctx->ev_sdone[two_back], 0);
+            }
+            stall(r);
             if (ctx->fast_recon) og_launch_celt_recon_fb(r, dd, ctx->d_streams, recs + f0, rout + f0, cnt, ctx->n_streams, handoff ? 1 : 0, nullptr);
+            if (ctx->fast_recon) stall(r);
             hipLaunchKernelGGL(k_celt_recon, dim3(ctx->fast_recon ? (cnt + 63) / 64 : cnt), dim3(64), 0, r, dd, ctx->d_streams,
                                (const ParseRec *)(recs + f0), rout + f0, cnt, ctx->n_streams, handoff ? 1 : 0, ctx->fast_recon);
             if (rq) {
@@ -1220,12 +1264,16 @@ static int decode_step_impl(opusgpu_ctx *ctx, int n, const void *d_descs, const 
                 (void)hipStreamWaitEvent(q, ctx->ev_hrecon, 0);
             }
         }
-        if (any_celt || !others || modes != 7)
+        if (any_celt || !others || modes != 7) {
+            stall(q);
             hipLaunchKernelGGL(k_celt_post, dim3((cnt * ctx->channels + 63) / 64), dim3(64), 0, q, dd, ctx->d_streams, (const ParseRec *)(recs + f0),
                                (const ReconOut *)(rout + f0), rr, pp, cnt, ctx->n_streams, ctx->channels, pcm_stride, hh, modes, others ? 1 : 0);
-        if (srecs && (modes & 1)) // the rare hybrid -> SILK-only transition frames (Q4), parked by k_silk_synth, through the full kernel
+        }
+        if (srecs && (modes & 1)) { // the rare hybrid -> SILK-only transition frames (Q4), parked by k_silk_synth, through the full kernel
+            stall(q);
             hipLaunchKernelGGL(k_decode_step, dim3((cnt + 63) / 64), dim3(64), 0, q, dd, (const u8 *)d_arena, ctx->d_streams, pp, rr, cnt,
                                ctx->n_streams, pcm_stride, 1, handoff + f0, (const SilkRec *)(srecs + f0), 1);
+        }
     };
     if (pipe_silk) {
         // PIPELINED SILK / HYBRID STEPS (no CELT-only frames).  k_silk_parse waits on latency (0.9 ms of one lane's serial chain for 0.27 ms of issue time at
@@ -1234,8 +1282,9 @@ static int decode_step_impl(opusgpu_ctx *ctx, int n, const void *d_descs, const 
         // index, the NLSFs, the rate and channel count, prev_mode: all of it entropy-side -- so it keeps a copy of its own
         // (SilkShadow) and runs for step k + 1 on parse_stream while step k's synthesis is under way on the step's stream -- for
         // hybrid frames followed by their CELT parse, which resumes its range decoder and carries the band energies itself as in
-        // pipelined CELT-only steps.  Two sets of records and hand-offs alternate; the parse of step k + 1 waits for the last kernel of step k - 1 (its set's
-        // last reader -- and with it for every write to the state of streams it may have no current copy of).
+        // pipelined CELT-only steps.  OG_SILK_SETS sets of records and hand-offs rotate; the parse of step k waits for the last kernel of step
+        // k - OG_SILK_SETS (its set's last reader -- and with it for every write to the state of streams it may have no current copy of),
+        // the CELT reconstruction beside the synthesis for the last kernel of step k - 2 (back_half: the history ring).
         if (!ctx->ev_sparsed) {
             HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_sparsed, hipEventDisableTiming));
             HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_sp, hipEventDisableTiming));
@@ -1353,6 +1402,7 @@ static int decode_step_impl(opusgpu_ctx *ctx, int n, const void *d_descs, const 
     {
         const int grid = (n + wide * ctx->parse_groups - 1) / (wide * ctx->parse_groups);
         launch_jitter();
+        stall(ctx->parse_stream);
         if (og_debug().parse_wide) // (64 frames per wave: next to the reconstruction the parse costs its issue slots, not its latency)
             og_launch_celt_parse64(ctx->parse_stream, grid, d_descs, d_arena, ctx->d_streams, recs, n, ctx->n_streams, nullptr, (int)PARSE_CELT_ONLY,
                                    ctx->parse_groups, ctx->d_started);
@@ -1374,9 +1424,11 @@ static int decode_step_impl(opusgpu_ctx *ctx, int n, const void *d_descs, const 
     // reconstruct (one frame per wave) ...
     if (ctx->fast_recon) {
         launch_jitter();
+        stall(back);
         og_launch_celt_recon_fb(back, d_descs, ctx->d_streams, recs, rout, n, ctx->n_streams, 0, ctx->d_started + 16);
         ctx->recon_started_total += (u32)og_celt_recon_fb_signals(n);
     }
+    stall(back);
     hipLaunchKernelGGL(k_celt_recon, dim3(ctx->fast_recon ? (n + 63) / 64 : n), dim3(64), 0, back, (const FrameDesc *)d_descs, ctx->d_streams,
                        (const ParseRec *)recs, rout, n, ctx->n_streams, 0, ctx->fast_recon);
     HIPCHK(ctx, hipEventRecord(ctx->ev_recon, back));
@@ -1391,6 +1443,7 @@ static int decode_step_impl(opusgpu_ctx *ctx, int n, const void *d_descs, const 
     }
     // ... -> de-emphasis and PCM (one (frame, channel) per lane); the result codes
     launch_jitter();
+    stall(s);
     hipLaunchKernelGGL(k_celt_post, dim3((n * ctx->channels + 63) / 64), dim3(64), 0, s, (const FrameDesc *)d_descs, ctx->d_streams,
                        (const ParseRec *)recs, (const ReconOut *)rout, (i32 *)d_result, (i16 *)d_pcm, n, ctx->n_streams, ctx->channels,
                        pcm_stride, (const SilkHandoff *)nullptr, modes, 0);

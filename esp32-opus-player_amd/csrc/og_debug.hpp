@@ -1,7 +1,8 @@
 // og_debug.hpp -- every debugging / measurement switch of the library in one place, read from the environment ONCE per process.
 //
 // None of them is needed in production: the defaults are what the measurements in DESIGN.md settled on.  They exist for A/B
-// runs of the same binary (tools/kstats.sh) and for the robustness test of pipelined steps (tools/launch_jitter.py).
+// runs of the same binary (tools/kstats.sh), for the robustness test of pipelined steps (tools/launch_jitter.py) and for the
+// cross-step ordering test (tests/test_gpu_stream_hazards.py).
 //
 //   variable                  field            default  meaning
 //   OPUSGPU_SPLIT             split            1        0: every frame through the single kernel k_decode_step (round 1's design)
@@ -23,12 +24,19 @@
 //   OPUSGPU_PAGES_TIMING      pages_timing     0        1: wall time of the phases of opusgpu_pages_demux on stderr
 //   OPUSGPU_LAUNCH_DELAY_US   launch_delay_us  0        the host sleeps this long before every kernel launch of a decode step
 //                                                       (robustness of the placement of pipelined steps against launch jitter)
+//   OPUSGPU_STALL_STREAM      stall_stream     (none)   step | parse | recon | side: with OPUSGPU_STALL_US, a decode step puts a stall kernel in
+//                                                       front of every kernel it launches on that stream -- the caller's stream, the
+//                                                       early parse's, the reconstruction's, the second half's of in-order steps (when the
+//                                                       context has no reconstruction stream) -- so that one stream falls behind the others
+//                                                       by whole steps and only events keep them in order (tests/test_gpu_stream_hazards.py)
+//   OPUSGPU_STALL_US          stall_us         0        how long each stall holds its stream, in microseconds (at most 100,000)
 #pragma once
 #include <stdlib.h>
+#include <string.h>
 
 struct og_debug_knobs {
     int split = 1, split_hybrid = 1, fast_recon = 1, hybrid_recon_aside = 1, silk_params_aside = 1, silk_nb_kernel = 1, halves = 1, silk_pipeline = 1, hybrid_pipeline = 1, parse_wide = 1, parse_groups = 1, parse_priority = 1, host_parts = 16, host_slices = 1, host_timing = 0,
-        pages_timing = 0, launch_delay_us = 0;
+        pages_timing = 0, launch_delay_us = 0, stall_stream = 0, stall_us = 0; // stall_stream: 0 none, 1 step, 2 parse, 3 recon, 4 side
 };
 inline const og_debug_knobs &og_debug() {
     static const og_debug_knobs k = [] {
@@ -62,6 +70,16 @@ inline const og_debug_knobs &og_debug() {
         if (const char *e = getenv("OPUSGPU_HOST_TIMING")) v.host_timing = atoi(e) == 2 ? 2 : 1;
         v.pages_timing = getenv("OPUSGPU_PAGES_TIMING") != nullptr;
         number("OPUSGPU_LAUNCH_DELAY_US", v.launch_delay_us, 0, 100000);
+        if (const char *e = getenv("OPUSGPU_STALL_STREAM")) {
+            const char *names[] = {"step", "parse", "recon", "side"};
+            for (int i = 0; i < 4; i++)
+                if (!strcmp(e, names[i])) v.stall_stream = i + 1;
+        }
+        if (const char *e = getenv("OPUSGPU_STALL_US")) {
+            const int x = atoi(e);
+            v.stall_us = x < 0 ? 0 : x > 100000 ? 100000 : x;
+        }
+        if (!v.stall_stream || !v.stall_us) v.stall_stream = v.stall_us = 0;
         return v;
     }();
     return k;

@@ -26,6 +26,7 @@ BUDGET = {
     "k_celt_parse": (256, 64),
     "k_celt_post": (128, 0),
     "k_decode_rfc": (256, 1024),   # two waves per SIMD (launch bound; it spills)
+    "k_stream_stall": (8, 0),      # OPUSGPU_STALL_STREAM (og_debug.hpp): a clock loop that writes no memory -- no scratch, no LDS either
 }
 
 
@@ -63,7 +64,7 @@ def test_kernels_keep_their_register_budgets():
     seen = {}
     for mangled, (vgpr, scratch, lds) in meta.items():
         for k in BUDGET:
-            if re.search(r"\d+" + k + r"(P|E|v|$)", mangled) or mangled == k:
+            if re.search(r"\d+" + k + r"(P|E|v|x|$)", mangled) or mangled == k:
                 seen[k] = (vgpr, scratch, lds)
     missing = [k for k in BUDGET if k not in seen]
     assert not missing, f"kernels not found in the library's code objects: {missing} (have {sorted(meta)[:6]}...)"
@@ -72,4 +73,5 @@ def test_kernels_keep_their_register_budgets():
     # LDS steps the occupancy figures in DESIGN.md rest on (granules of 1,280 bytes per workgroup)
     assert seen["k_silk_synth"][2] <= 8960 and seen["k_silk_synth_nb"][2] <= 6400 and seen["k_celt_recon_fb"][2] <= 6400
     assert seen["k_silk_parse"][2] <= 8192 and seen["k_silk_params"][2] <= 12800  # (7.8 KB: the table blob and the pulse decoder's block rows, 64 columns)
+    assert seen["k_stream_stall"][2] == 0
     assert seen["k_celt_parse"][2] <= 11520  # the in-order parse kernel: nine granules (its 64-frame twin sizes its LDS at the launch)
