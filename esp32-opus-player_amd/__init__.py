@@ -29,7 +29,24 @@ EXPORTS = [
     "opusgpu_page_batch_free", "opusgpu_pages_crc_device", "opusgpu_output_stage_device",
     "opusgpu_set_mode", "opusgpu_get_mode", "opusgpu_set_pipeline", "opusgpu_get_pipeline", "opusgpu_packet_to_frames_mode",
     "opusgpu_empty_packet_to_frames",
+    "opusgpu_ms_create", "opusgpu_ms_destroy", "opusgpu_ms_last_error", "opusgpu_ms_set_mode", "opusgpu_ms_reset",
+    "opusgpu_ms_packet_to_frames", "opusgpu_ms_decode_packets", "opusgpu_ms_decode_step_device", "opusgpu_ms_synchronize",
 ]
+
+
+class MsLayout(C.Structure):
+    """opusgpu_ms_layout (include/opusgpu.h, MULTISTREAM)."""
+    _fields_ = [("channels", C.c_int32), ("streams", C.c_int32), ("coupled", C.c_int32), ("mapping", C.c_uint8 * 256)]
+
+
+def ms_layout(channels, streams, coupled, mapping=None):
+    """An MsLayout; mapping defaults to the identity (output channel c <- decoded channel c)."""
+    lay = MsLayout()
+    lay.channels, lay.streams, lay.coupled = channels, streams, coupled
+    m = list(range(channels)) if mapping is None else list(mapping)
+    for c in range(256):
+        lay.mapping[c] = m[c] if c < len(m) else 255
+    return lay
 
 
 class OutputCfg(C.Structure):
@@ -148,6 +165,17 @@ def load_lib():
     lib.opusgpu_pages_crc_device.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
     lib.opusgpu_output_stage_device.argtypes = [vp, C.c_int, C.c_int, vp, C.c_longlong, vp, C.c_int, vp, OutputCfg, vp,
                                                 C.c_longlong, vp]
+    lib.opusgpu_ms_create.argtypes = [C.c_int, C.POINTER(MsLayout), C.c_int, C.POINTER(vp)]
+    lib.opusgpu_ms_destroy.argtypes = [vp]
+    lib.opusgpu_ms_destroy.restype = None
+    lib.opusgpu_ms_last_error.argtypes = [vp]
+    lib.opusgpu_ms_last_error.restype = C.c_char_p
+    lib.opusgpu_ms_set_mode.argtypes = [vp, C.c_int]
+    lib.opusgpu_ms_reset.argtypes = [vp, C.c_int, C.c_int, C.c_int]
+    lib.opusgpu_ms_packet_to_frames.argtypes = [C.POINTER(MsLayout), C.c_char_p, C.c_int32, C.c_int32, C.c_int, C.POINTER(FrameDesc), vp]
+    lib.opusgpu_ms_decode_packets.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_int, vp]
+    lib.opusgpu_ms_decode_step_device.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
+    lib.opusgpu_ms_synchronize.argtypes = [vp]
     _lib = lib
     return lib
 
@@ -181,6 +209,19 @@ def empty_packet_to_frames(last_flags, decoder_channels, frame_size, stream: int
     if n < 0:
         return n
     return [(d[i].offset, d[i].len, d[i].flags) for i in range(n)]
+
+
+def ms_packet_to_frames(layout, packet: bytes, decoder: int = 0, rfc=False):
+    """Host-only: one multistream packet -> (duration in samples, [per elementary stream: list of (offset, len, flags)]), or a
+    negative code (opusgpu_ms_packet_to_frames).  `layout`: an MsLayout (ms_layout())."""
+    lib = load_lib()
+    S = max(int(layout.streams), 1)
+    d = (FrameDesc * (48 * S))()
+    counts = np.zeros(S, dtype=np.int32)
+    r = lib.opusgpu_ms_packet_to_frames(C.byref(layout), packet, len(packet), decoder, 1 if rfc else 0, d, counts.ctypes.data)
+    if r < 0:
+        return r
+    return r, [[(d[s * 48 + k].offset, d[s * 48 + k].len, d[s * 48 + k].flags) for k in range(counts[s])] for s in range(S)]
 
 
 class PageBatch:
@@ -516,6 +557,78 @@ class Context:
 
 
 # ---- synthetic workloads ---------------------------------------------------
+class MultistreamContext:
+    """n_decoders multistream decoders of one layout (include/opusgpu.h, MULTISTREAM): `streams` elementary streams, the first
+    `coupled` of them stereo, output channel c <- decoded channel mapping[c] (255: silent)."""
+
+    def __init__(self, device, n_decoders, channels, streams, coupled, mapping=None):
+        self.lib = load_lib()
+        self.layout = ms_layout(channels, streams, coupled, mapping)
+        h = C.c_void_p()
+        rc = self.lib.opusgpu_ms_create(device, C.byref(self.layout), n_decoders, C.byref(h))
+        if rc != 0:
+            e = OpusGpuError(f"opusgpu_ms_create failed with {rc}")
+            e.code = rc
+            raise e
+        self.h = h
+        self.n_decoders, self.channels, self.streams, self.coupled = n_decoders, channels, streams, coupled
+        self.rfc = False
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.opusgpu_ms_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _chk(self, rc, what):
+        if rc != 0:
+            e = OpusGpuError(f"{what} failed: {rc} ({self.lib.opusgpu_ms_last_error(self.h).decode()})")
+            e.code = rc
+            raise e
+
+    def set_mode(self, rfc):
+        self._chk(self.lib.opusgpu_ms_set_mode(self.h, 1 if rfc else 0), "opusgpu_ms_set_mode")
+        self.rfc = bool(rfc)
+
+    def reset(self, first=0, count=None, full=True):
+        count = self.n_decoders - first if count is None else count
+        self._chk(self.lib.opusgpu_ms_reset(self.h, first, count, 1 if full else 0), "opusgpu_ms_reset")
+
+    def decode_packets(self, decoder_ids, packets, frame_capacity=1, pcm=None):
+        """Batched opus_multistream_decode: -> (pcm [n, cap*960, channels] int16, result [n] int32).  `pcm`: an array to decode
+        into (blocks of failed packets keep what they held)."""
+        packets = [b"" if p is None else bytes(p) for p in packets]
+        n = len(packets)
+        ids = np.ascontiguousarray(decoder_ids, dtype=np.int32)
+        lens = np.array([len(p) for p in packets], dtype=np.int32)
+        blob = np.frombuffer(b"".join(packets) + b"\0", dtype=np.uint8)
+        offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.uint64) if n else np.zeros(0, np.uint64)
+        ptrs = (np.uint64(blob.ctypes.data) + offs).astype(np.uint64)
+        shape = (n, frame_capacity * FRAME, self.channels)
+        if pcm is None:
+            pcm = np.zeros(shape, dtype=np.int16)
+        elif pcm.shape != shape or pcm.dtype != np.int16 or not pcm.flags.c_contiguous:
+            raise ValueError(f"pcm must be a C-contiguous int16 array of shape {shape}")
+        res = np.zeros(n, dtype=np.int32)
+        self._chk(self.lib.opusgpu_ms_decode_packets(self.h, n, ids.ctypes.data, ptrs.ctypes.data, lens.ctypes.data, pcm.ctypes.data,
+                                                     frame_capacity, res.ctypes.data), "opusgpu_ms_decode_packets")
+        return pcm, res
+
+    def decode_step_device(self, n, d_descs, d_arena, d_pcm, d_result, stream=None):
+        """n rows of `streams` descriptors (DESC_DTYPE, stream field = decoder) in device memory -> d_pcm [n][960 * channels]
+        (RFC mode: 2880 * channels), d_result [n]."""
+        self._chk(self.lib.opusgpu_ms_decode_step_device(self.h, n, d_descs, d_arena, d_pcm, d_result, stream),
+                  "opusgpu_ms_decode_step_device")
+
+    def synchronize(self):
+        self._chk(self.lib.opusgpu_ms_synchronize(self.h), "opusgpu_ms_synchronize")
+
+
 TOC_CELT_FB_STEREO = 0xFC
 TOC_SILK_NB_STEREO = 0x0C
 TOC_HYBRID_FB_STEREO = 0x7C

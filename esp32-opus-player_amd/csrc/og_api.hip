@@ -2272,3 +2272,6 @@ int opusgpu_decode_packets_fec(opusgpu_ctx *ctx, int n, const int32_t *stream_id
 }
 
 } // extern "C"
+
+// multistream decoding (include/opusgpu.h, MULTISTREAM): drives the contexts above
+#include "og_ms.hpp"

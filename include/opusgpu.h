@@ -404,6 +404,85 @@ int opusgpu_output_stage_device(opusgpu_ctx *ctx, int n_blocks, int block_sample
                                 const void *d_valid, int valid_all, const void *d_cfgs, opusgpu_output_cfg cfg, void *d_i2s,
                                 long long i2s_stride, void *hip_stream);
 
+/* ---- MULTISTREAM: surround, family-255 and other multi-stream Opus ----------------------------------------
+ * A multistream packet carries `streams` elementary Opus packets, one per elementary stream, each in self-delimited framing
+ * (RFC 6716 Appendix B) except the last one, which is in standard framing (opus_multistream_packet_validate,
+ * src/opus_decoder.cpp:803-823).  The first `coupled` streams are stereo and are decoded by 2-channel decoders, the rest are mono
+ * and are decoded by 1-channel decoders, with everything that implies: a mono decoder downmixes a stereo packet, a stereo decoder
+ * duplicates a mono packet (Q3 mixing of mono SILK-only frames included).  Each elementary stream is exactly what a context of
+ * that channel count would make of its packets.  The decoded channels -- 2s and 2s + 1 the left and right of coupled stream s,
+ * coupled + s mono stream s (s >= coupled) -- go to output channel c from decoded channel mapping[c] (get_left_channel /
+ * get_right_channel / get_mono_channel, :700-727); one decoded channel may feed several outputs, mapping[c] == 255 is silence.
+ * The reference defines these semantics but cannot run them for more than one stream (its decoders share one codec state); here
+ * every elementary stream has its own state record.
+ * The opus_multistream_* entry points of include/opus_decoder.h keep answering OPUS_UNIMPLEMENTED for streams != 1, as the
+ * reference build does; this section is the way to decode such streams.
+ * An opusgpu_ms holds n_decoders multistream decoders of ONE layout (one object per layout) on two contexts of its own
+ * (n_decoders * coupled stereo streams, n_decoders * (streams - coupled) mono streams).  Steps run in order (no pipelining).
+ * Layout checks (opus_multistream_decoder_init :742-770 and validate_layout :688-697): 1 <= channels <= 255, streams >= 1,
+ * 0 <= coupled <= streams, streams + coupled <= 255, every mapping[c] (c < channels) < streams + coupled or 255; otherwise
+ * OPUSGPU_BAD_ARG. */
+typedef struct opusgpu_ms_layout {
+    int32_t channels;     /* 1..255 output channels */
+    int32_t streams;      /* 1..255 elementary streams */
+    int32_t coupled;      /* the first `coupled` streams are stereo, the rest mono */
+    uint8_t mapping[256]; /* output channel c <- decoded channel mapping[c]; 255 = silent; entries >= channels are ignored */
+} opusgpu_ms_layout;
+typedef struct opusgpu_ms opusgpu_ms;
+
+int opusgpu_ms_create(int device, const opusgpu_ms_layout *layout, int n_decoders, opusgpu_ms **out);
+void opusgpu_ms_destroy(opusgpu_ms *ms);
+const char *opusgpu_ms_last_error(const opusgpu_ms *ms);
+/* OPUSGPU_MODE_REFERENCE / OPUSGPU_MODE_RFC for both contexts (RFC mode: see opusgpu_set_mode; forward error correction is not
+ * offered here). */
+int opusgpu_ms_set_mode(opusgpu_ms *ms, int mode);
+/* Decoders [first, first + count): every elementary stream as opusgpu_streams_reset does it. */
+int opusgpu_ms_reset(opusgpu_ms *ms, int first, int count, int full);
+/* Host framing of one multistream packet: descs[s * 48 + k] = frame k of elementary stream s (stream field = `decoder`, offsets
+ * relative to the packet start, flags as opusgpu_packet_to_frames_mode makes them for `mode`), counts[s] = its frame count.
+ * Returns the packet's duration in samples at 48 kHz (every stream has it) or: OPUSGPU_INVALID_PACKET for len == 0 or
+ * len < 2 * streams - 1 (:855), a missing stream, streams of different durations, a stream longer than 120 ms (:803-823); what
+ * the frame split returns for a malformed stream; OPUSGPU_BAD_ARG for a bad layout or argument.  Reference mode only: streams
+ * with equal durations but different frame counts are OPUSGPU_INVALID_PACKET -- the reference decodes every frame as 960
+ * samples (Q6), so such streams would give different sample counts and its loop (:866-909) would overrun its buffer.  Refusing
+ * the packet is a deliberate difference. */
+int opusgpu_ms_packet_to_frames(const opusgpu_ms_layout *layout, const uint8_t *packet, int32_t len, int32_t decoder, int mode,
+                                opusgpu_frame_desc *descs, int32_t *counts);
+/* The batched opus_multistream_decode (src/opus_decoder.cpp:826-914): packets[i] (lens[i] bytes) for decoder decoder_ids[i],
+ * i < n; a decoder may appear at most once per call.  pcm receives n blocks of frame_capacity * 960 * channels interleaved int16
+ * (frame_capacity 1..48); result[i] = samples per channel (the common count of the elementary streams) or a negative code.
+ * Checked on the host before anything is decoded: the framing above (OPUSGPU_INVALID_PACKET), the duration against frame_size =
+ * min(frame_capacity * 960, 5760) (OPUSGPU_BUFFER_TOO_SMALL, :845-847), and in reference mode, like opusgpu_decode_packets, more
+ * frames than frame_capacity (OPUSGPU_BUFFER_TOO_SMALL).  Also reference mode: with more than one stream, frames longer than 20 ms
+ * are OPUSGPU_BUFFER_TOO_SMALL -- the reference checks every stream after the first against the first one's result (:880,
+ * frame_size = ret), which counts 960 samples per frame, and fails the second stream after decoding the first; here nothing is
+ * decoded.  Decode-time refusals (e.g. OPUSGPU_CELT_BAD_ARG for a CELT or hybrid frame of at most one byte) are reported as the
+ * first negative elementary result in stream order, AFTER the other elementary streams of the packet have been decoded: the
+ * reference stops at the failing stream (:876-878), here every stream goes on (a deliberate difference; an elementary stream
+ * itself still stops at its first failing frame, as opus_decode_native does).  Nothing is written to the PCM block of a packet
+ * whose result is negative, and a block is written only as far as its result reaches.
+ * Empty packets (packets[i] == NULL or lens[i] == 0): reference mode runs the empty-packet branch (EMPTY PACKETS above) on every
+ * elementary stream, frame_size / 960 passes each (:851-874 with do_plc); RFC mode conceals a lost packet on every elementary
+ * stream, as opusgpu_decode_packets does for one stream.  RFC mode: elementary streams may differ in frame count and frame
+ * duration (their durations are equal), result[i] is the packet's duration. */
+int opusgpu_ms_decode_packets(opusgpu_ms *ms, int n, const int32_t *decoder_ids, const uint8_t *const *packets,
+                              const int32_t *lens, int16_t *pcm, int frame_capacity, int32_t *result);
+/* One device step of n multistream frames: d_descs holds n rows of `streams` descriptors (row r = one multistream frame, its
+ * elementary frames in stream order; every descriptor's `stream` field names the DECODER, 0 .. n_decoders - 1), payload bytes in
+ * d_arena (16-byte aligned, as for opusgpu_decode_step_device); d_pcm (16-byte aligned) receives [n][960 * channels] int16
+ * (RFC mode: [n][OPUSGPU_RFC_FRAME_SAMPLES * channels], d_result[r] the row's sample count), d_result[n] int32 the row's common
+ * sample count or its first negative elementary result in stream order.  Asynchronous on `hip_stream` (NULL: the object's own
+ * stream); consecutive steps on different streams are ordered by a drain.  A row decodes one frame of each elementary stream of
+ * its decoder, so a decoder appears at most once per step.  Checked on the device, per row: a row whose descriptors name
+ * different decoders, a decoder out of range, a mode value of 3, another mode than the object's (the RFC bit), the FEC bit, or
+ * (RFC mode) frames of different durations gets OPUSGPU_BAD_ARG and none of its elementary frames is decoded.  Empty packets
+ * take one row per pass (reference mode) or per concealed frame (RFC mode), with the descriptors opusgpu_empty_packet_to_frames
+ * makes (decoder channel count 2 for coupled streams, 1 for mono ones).  Rows with a negative result get no PCM. */
+int opusgpu_ms_decode_step_device(opusgpu_ms *ms, int n, const void *d_descs, const void *d_arena, void *d_pcm, void *d_result,
+                                  void *hip_stream);
+/* The host waits for everything the object has queued. */
+int opusgpu_ms_synchronize(opusgpu_ms *ms);
+
 #ifdef __cplusplus
 }
 #endif
