@@ -27,7 +27,6 @@
 using namespace og;
 
 static_assert(sizeof(opusgpu_frame_desc) == sizeof(FrameDesc), "descriptor layout");
-enum { OPUSGPU_COPY_PIECES = 16, OPUSGPU_COPY_THREADS = 8 };
 
 // ---- kernels --------------------------------------------------------------------------------------
 // OPUSGPU_STALL_STREAM / OPUSGPU_STALL_US (og_debug.hpp): one wave that holds its stream for `ticks` of the device wall clock.  It
@@ -600,163 +599,93 @@ __global__ void __launch_bounds__(64) k_celt_post(const FrameDesc *__restrict__ 
     ss->celt.deemph[c] = m;
 }
 
-// ---- context ----------------------------------------------------------------------------------------
-// Worker threads of the host-buffer path, started once per context: a large opusgpu_decode_packets call hands them ranges of its
-// packets four times (scan, place per part, delivery); starting 16 threads each time cost 0.6 ms per hand-over at 65,536 packets.
-struct HostPool {
-    std::vector<std::thread> th;
-    std::mutex m;
-    std::condition_variable wake, done;
-    std::function<void(int)> job;
-    int generation = 0, want = 0, pending = 0;
-    bool quit = false;
-    ~HostPool() {
-        {
-            std::lock_guard<std::mutex> l(m);
-            quit = true;
-        }
-        wake.notify_all();
-        for (auto &t : th) t.join();
-    }
-    void worker(int id) {
-        int seen = 0;
-        for (;;) {
-            std::function<void(int)> f;
-            {
-                std::unique_lock<std::mutex> l(m);
-                wake.wait(l, [&] { return quit || (generation != seen && id < want); });
-                if (quit) return;
-                seen = generation;
-                f = job;
-            }
-            f(id);
-            {
-                std::lock_guard<std::mutex> l(m);
-                if (--pending == 0) done.notify_all();
-            }
-        }
-    }
-    // f(t) for t = 0 .. count - 1, t = 0 on the calling thread; returns when all are through
-    void run(int count, const std::function<void(int)> &f) {
-        if (count <= 1) {
-            f(0);
-            return;
-        }
-        while ((int)th.size() < count - 1) {
-            const int id = (int)th.size();
-            th.emplace_back([this, id] { worker(id); });
-        }
-        {
-            std::lock_guard<std::mutex> l(m);
-            job = [&f](int id) { f(id + 1); };
-            want = count - 1;
-            pending = count - 1;
-            generation++;
-        }
-        wake.notify_all();
-        f(0);
-        std::unique_lock<std::mutex> l(m);
-        done.wait(l, [&] { return pending == 0; });
-    }
-};
+#include "og_step.hpp"
 
-#ifndef OG_SILK_SETS
-#define OG_SILK_SETS 3 // sets of SILK records and hand-offs that pipelined SILK / hybrid steps rotate through
-#endif
-static_assert(OG_SILK_SETS >= 2, "a pipelined SILK / hybrid step runs next to the step before it");
-struct opusgpu_ctx {
-    int device = -1;
-    hipStream_t stream = nullptr;
-    StreamState *d_streams = nullptr;
-    int n_streams = 0, channels = 0;
-    // staging for the host-buffer path
-    void *d_descs = nullptr, *d_arena = nullptr, *d_pcm = nullptr, *d_result = nullptr;
-    size_t cap_descs = 0, cap_arena = 0, cap_pcm = 0, cap_result = 0;
-    // pinned host landing zone of the host-buffer path's PCM and result codes (DMA at full PCIe rate, no zero-filling of
-    // a fresh temporary per call); the caller's pageable buffer is filled from it by a few host threads
-    void *h_pcm = nullptr, *h_res = nullptr;
-    size_t cap_h_pcm = 0, cap_h_res = 0;
-    // ... and of the way in: the call's packet bytes and step table are gathered in page-locked memory that lives as long as the
-    // context (a fresh 10 MB allocation per call is 2,600 page faults in front of the first upload, and a copy from pageable
-    // memory holds the calling thread until the runtime has staged it)
-    void *h_arena = nullptr, *h_descs = nullptr;
-    size_t cap_h_arena = 0, cap_h_descs = 0;
-    HostPool pool;
-    u32 *d_crc_tables = nullptr; // 8 x 256 words, made on first use (opusgpu_pages_crc_device)
-    hipEvent_t ev_piece[OPUSGPU_COPY_PIECES] = {}; // one per piece of the PCM's way back to the host (opusgpu_decode_packets)
-    // large batches on the host-buffer path run in parts: a part's PCM travels back (on a stream of its own) while the next
-    // part's kernels run
-    hipStream_t copy_stream = nullptr;
-    std::mutex registered_mutex;
-    std::vector<std::pair<uintptr_t, size_t>> registered; // host ranges page-locked through opusgpu_host_register
-    hipEvent_t ev_part[OPUSGPU_COPY_PIECES] = {};
-    int host_parts = 8; // OPUSGPU_HOST_PARTS=1: one batch, copy after the kernels (A/B measurements); 2, 4, 8, 16
-    // parse records of the split CELT path (one per frame of a step), grown on demand
-    // (five sets: pipelined CELT-only steps rotate through 0 - 2 -- in-order steps use 0 --, pipelined SILK-only / hybrid steps
-    // alternate 3 and 4: steps of the two kinds may be in flight together, OPUSGPU_STEP_KEEPS_MODE)
-    void *d_recs[6] = {}, *d_rout[6] = {}; // (sets 0 - 2: pipelined CELT-only steps and everything in order; 3 - 5: pipelined SILK / hybrid steps)
-    size_t cap_recs[6] = {}, cap_rout[6] = {};
-    // (OG_SILK_SETS sets: pipelined SILK / hybrid steps rotate; everything else uses set 0.  Three since round 5: with two the parse
-    // of step k + 1 had to wait for the synthesis of step k - 1 to let go of its set, and the chain parse -> parameters of a small
-    // step -- 0.58 + 0.45 ms at 65,536 SILK-NB frames -- was then longer than the synthesis it should have hidden under)
-    void *d_handoff[OG_SILK_SETS] = {}, *d_srecs[OG_SILK_SETS] = {};
-    size_t cap_handoff[OG_SILK_SETS] = {}, cap_srecs[OG_SILK_SETS] = {};
-    const void *last_srecs = nullptr; // the SILK records of the last step (opusgpu_debug_stage_taps)
-    // Pipelined SILK-only steps (a step the caller declares SILK-only): the parse kernel keeps what its next run needs of the past
-    // in d_shadow (SilkShadow per stream, og_silk_parse.hpp) and runs for step k + 1 on parse_stream next to step k's synthesis.
-    void *d_shadow = nullptr;
-    unsigned shadow_epoch = 1; // advanced by everything else that may change a stream's SILK state: stale copies are ignored
-    int silk_slot = 0, sdone_recorded[OG_SILK_SETS] = {}, last_silk_mask = 0, last_kind = 0; // last_kind: 0 in order, 1 pipelined CELT-only, 2 pipelined SILK-only
-    bool last_kind2_celt = false; // the last step of kind 2 held CELT-only frames too (enter_step_kind)
-    hipEvent_t ev_sparsed = nullptr, ev_sdone[OG_SILK_SETS] = {}, ev_sp = nullptr, ev_spar = nullptr, ev_hrecon = nullptr; // ev_sp: a step's SILK parse is done; ev_spar: its parameter half; ev_hrecon: its CELT reconstruction
-    int split_celt = 1;   // OPUSGPU_SPLIT=0 forces the single-kernel path for every mode (A/B measurements)
-    int split_hybrid = 1; // OPUSGPU_SPLIT_HYBRID=0 keeps SILK-only and hybrid frames entirely on the single-kernel path
-    int fast_recon = 1;   // OPUSGPU_FAST_RECON=0: every CELT frame through the general reconstruction kernel (A/B measurements)
-    int mode = OPUSGPU_MODE_REFERENCE; // opusgpu_set_mode
-    // opusgpu_set_pipeline: the parse of step k + 1's CELT-only frames runs on parse_stream, next to step k's reconstruction
-    // and its reconstruction on recon_stream; parse records and the reconstruction's per-frame output (d_recs, d_rout) rotate
-    int pipeline = 0, slot = 0, front_recorded = 0, post_recorded[3] = {};
-    hipStream_t parse_stream = nullptr, recon_stream = nullptr, last_step_stream = nullptr;
-    hipStream_t side_stream = nullptr;                // in-order steps with SILK frames: the second half's chain (decode_step_impl)
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    hipEvent_t ev_front = nullptr;  // step k: its front kernels have finished (on the step's stream)
-    hipEvent_t ev_parsed = nullptr; // step k: its early parse has finished (on parse_stream)
-    hipEvent_t ev_recon = nullptr;  // step k: its reconstruction has finished (on recon_stream)
-    hipEvent_t ev_post[3] = {};     // by slot: k_celt_post of the last step that used it has finished (on the step's stream)
-    long long stall_ticks = 0;      // OPUSGPU_STALL_US in ticks of the device wall clock (0: no stalls, og_debug.hpp)
-    const void *last_recs = nullptr;
-    // Steps queued as a window (opusgpu_decode_steps_device): the kernels of neighbouring steps are placed in the order that
-    // works -- the next step's parse, then this step's reconstruction, then the de-emphasis of the step before -- by stream
-    // memory waits on two counters the parse / reconstruction workgroups bump when they start (device words, 64 bytes apart;
-    // the host keeps the totals they will reach).  Round 2 got that order from a spin-wait kernel watching the wall clock.
-    u32 *d_started = nullptr; // [0] early-parse workgroups started, [16] every 64th reconstruction workgroup started
-    u32 parse_started_total = 0, recon_started_total = 0;
-    u32 window_parse_target = 0, window_recon_target = 0; // the counts the last queued step of an unfinished window waits for (0: none)
-    // (OPUSGPU_PARSE_GROUPS) groups of frames per workgroup of the early parse, one after the other.  Round 2 measured two as the
-    // best (half as many parse workgroups resident for twice as long: 2.545 / 2.50 / 2.52 / 2.97 ms per step at 1 / 2 / 3 / 4).  Round 4:
-    // a group takes a parse wave 0.85 ms, so two groups are a chain of 1.7 ms -- which had become the step (a reconstruction doing
-    // 40 % of its work: still 1.69 ms).  With one group the parse is done after 1.0 ms of the step and what counts is how many of the
-    // reconstruction's waves fit a CU next to it: the parse kernel's LDS went from 46 KB to 36 KB per 128 frames for that
-    // (og_celt_split.hpp: ParseLds), 1.83 -> 1.74 ms.
-    int parse_groups = 1;
-    // the last decode step's tables, for opusgpu_debug_stage_taps
-    const void *last_descs = nullptr;
-    int last_n = 0, last_had_silk_recs = 0;
-    // RFC mode, host side of the loss path: per stream, the frame count and descriptor flags of the last packet framed by
-    // opusgpu_decode_packets -- what a lost packet of that stream is concealed as (0 frames: nothing framed yet)
-    std::vector<int32_t> last_count, last_flags;
-    char err[256] = {0};
+// ---- the launches of the scheduler (og_step.hpp): frames [f0, f0 + cnt) of step `st` on stream q ---------------------
+const size_t og_parse_rec_bytes = sizeof(ParseRec), og_recon_out_bytes = sizeof(ReconOut), og_silk_handoff_bytes = sizeof(SilkHandoff),
+             og_silk_rec_bytes = sizeof(SilkRec);
+namespace {
+struct StepRange { // the step's tables at frame f0 (hand-off and SILK records: null when the step has none)
+    const FrameDesc *dd;
+    i16 *pp;
+    i32 *rr;
+    ParseRec *recs;
+    ReconOut *rout;
+    SilkHandoff *hh;
+    SilkRec *srecs;
+    StepRange(const Step &st, size_t f0)
+        : dd((const FrameDesc *)st.descs + f0), pp((i16 *)st.pcm + f0 * (size_t)st.pcm_stride), rr((i32 *)st.result + f0),
+          recs((ParseRec *)st.recs + f0), rout((ReconOut *)st.rout + f0), hh(st.handoff ? (SilkHandoff *)st.handoff + f0 : nullptr),
+          srecs(st.srecs ? (SilkRec *)st.srecs + f0 : nullptr) {}
 };
-
-static int fail(opusgpu_ctx *ctx, int code, const char *what, hipError_t e) {
-    if (ctx) snprintf(ctx->err, sizeof(ctx->err), "%s: %s", what, hipGetErrorString(e));
-    return code;
+} // namespace
+void launch_stream_stall(opusgpu_ctx *ctx, hipStream_t q) {
+    hipLaunchKernelGGL(k_stream_stall, dim3(1), dim3(64), 0, q, ctx->stall_ticks, (int)OG_STALL_MAX_SPINS);
 }
-#define HIPCHK(ctx, call)                                                \
-    do {                                                                 \
-        hipError_t e_ = (call);                                          \
-        if (e_ != hipSuccess) return fail(ctx, OPUSGPU_ERR_HIP, #call, e_); \
-    } while (0)
+void launch_decode_rfc(opusgpu_ctx *ctx, hipStream_t q, const Step &st) {
+    og_launch_decode_rfc(q, st.descs, st.arena, ctx->d_streams, st.pcm, st.result, st.n, ctx->n_streams, st.pcm_stride);
+}
+void launch_decode_step(opusgpu_ctx *ctx, hipStream_t q, const Step &st, size_t f0, int cnt, int pass) {
+    const StepRange r(st, f0);
+    hipLaunchKernelGGL(k_decode_step, dim3(pass == 2 ? (cnt + 63) / 64 : cnt), dim3(64), 0, q, r.dd, (const u8 *)st.arena, ctx->d_streams, r.pp,
+                       r.rr, cnt, ctx->n_streams, st.pcm_stride, pass ? 1 : 0, pass == 2 ? r.hh : nullptr,
+                       (const SilkRec *)(pass == 2 ? r.srecs : nullptr), pass == 2 ? 1 : 0);
+}
+void launch_silk_parse(opusgpu_ctx *ctx, hipStream_t q, const Step &st, size_t f0, int cnt, void *shadow, uint32_t epoch) {
+    const StepRange r(st, f0);
+    hipLaunchKernelGGL(k_silk_parse, dim3((cnt + 31) / 32), dim3(64), 0, q, r.dd, (const u8 *)st.arena, (const StreamState *)ctx->d_streams,
+                       r.srecs, r.hh, cnt, ctx->n_streams, (SilkShadow *)shadow, epoch);
+}
+void launch_silk_parse64(opusgpu_ctx *ctx, hipStream_t q, const Step &st, size_t f0, int cnt, void *shadow, uint32_t epoch) {
+    const StepRange r(st, f0);
+    hipLaunchKernelGGL(k_silk_parse64, dim3((cnt + 63) / 64), dim3(64), 0, q, r.dd, (const u8 *)st.arena, (const StreamState *)ctx->d_streams,
+                       r.srecs, r.hh, cnt, ctx->n_streams, (SilkShadow *)shadow, epoch);
+}
+void launch_silk_params(opusgpu_ctx *ctx, hipStream_t q, const Step &st, size_t f0, int cnt, void *shadow, uint32_t epoch) {
+    const StepRange r(st, f0);
+    hipLaunchKernelGGL(k_silk_params, dim3((cnt + OG_PAR_LANES / 2 - 1) / (OG_PAR_LANES / 2)), dim3(64), 0, q, r.dd,
+                       (const StreamState *)ctx->d_streams, r.srecs, cnt, ctx->n_streams, (SilkShadow *)shadow, epoch);
+}
+int celt_parse_early_grid(const opusgpu_ctx *ctx, int cnt, bool wide) {
+    const int per = (wide ? og_celt_parse64_frames() : OG_PL_FRAMES) * ctx->parse_groups;
+    return (cnt + per - 1) / per;
+}
+void launch_celt_parse(opusgpu_ctx *ctx, hipStream_t q, const Step &st, size_t f0, int cnt, bool wide, bool early) {
+    const StepRange r(st, f0);
+    const int which = early ? (int)PARSE_CELT_ONLY : (int)PARSE_ALL, groups = early ? ctx->parse_groups : 1;
+    const int per = wide ? og_celt_parse64_frames() : OG_PL_FRAMES;
+    const int grid = early ? celt_parse_early_grid(ctx, cnt, wide) : (cnt + per - 1) / per;
+    u32 *const started = early ? ctx->sp.d_started : nullptr;
+    if (wide)
+        og_launch_celt_parse64(q, grid, r.dd, st.arena, ctx->d_streams, r.recs, cnt, ctx->n_streams, r.hh, which, groups, started);
+    else
+        hipLaunchKernelGGL(k_celt_parse, dim3(grid), dim3(64 * OG_PL_WAVES), 0, q, r.dd, (const u8 *)st.arena, ctx->d_streams, r.recs, cnt,
+                           ctx->n_streams, (const SilkHandoff *)r.hh, which, groups, started);
+}
+void launch_celt_recon_fb(opusgpu_ctx *ctx, hipStream_t q, const Step &st, size_t f0, int cnt, bool counts_in) {
+    const StepRange r(st, f0);
+    og_launch_celt_recon_fb(q, r.dd, ctx->d_streams, r.recs, r.rout, cnt, ctx->n_streams, r.hh ? 1 : 0, counts_in ? ctx->sp.d_started + 16 : nullptr);
+}
+void launch_celt_recon(opusgpu_ctx *ctx, hipStream_t q, const Step &st, size_t f0, int cnt) {
+    const StepRange r(st, f0);
+    hipLaunchKernelGGL(k_celt_recon, dim3(ctx->fast_recon ? (cnt + 63) / 64 : cnt), dim3(64), 0, q, r.dd, ctx->d_streams, (const ParseRec *)r.recs,
+                       r.rout, cnt, ctx->n_streams, r.hh ? 1 : 0, ctx->fast_recon);
+}
+void launch_celt_post(opusgpu_ctx *ctx, hipStream_t q, const Step &st, size_t f0, int cnt, bool others) {
+    const StepRange r(st, f0);
+    hipLaunchKernelGGL(k_celt_post, dim3((cnt * ctx->channels + 63) / 64), dim3(64), 0, q, r.dd, ctx->d_streams, (const ParseRec *)r.recs,
+                       (const ReconOut *)r.rout, r.rr, r.pp, cnt, ctx->n_streams, ctx->channels, st.pcm_stride, (const SilkHandoff *)r.hh, st.modes,
+                       others ? 1 : 0);
+}
+void launch_silk_synth(opusgpu_ctx *ctx, hipStream_t q, const Step &st, size_t f0, int cnt, int nb_done) {
+    const StepRange r(st, f0);
+    og_launch_silk_synth(q, r.dd, st.arena, ctx->d_streams, r.pp, r.rr, cnt, ctx->n_streams, st.pcm_stride, r.hh, r.srecs, nb_done);
+}
+void launch_silk_synth_nb(opusgpu_ctx *ctx, hipStream_t q, const Step &st, size_t f0, int cnt) {
+    const StepRange r(st, f0);
+    og_launch_silk_synth_nb(q, r.dd, st.arena, ctx->d_streams, r.pp, r.rr, cnt, ctx->n_streams, st.pcm_stride, r.hh, r.srecs, 1);
+}
+
 
 // OPUSGPU_HOST_TIMING=1: wall time of the phases of opusgpu_decode_packets on stderr (adds a stream synchronise after the
 // kernels so that decode and copy-back can be told apart; for tuning only)
@@ -774,7 +703,6 @@ struct HostPhaseTimer {
 
 extern "C" {
 
-static int grow(opusgpu_ctx *ctx, void **p, size_t *cap, size_t need);
 
 int opusgpu_version(void) { return 100; }
 
@@ -824,47 +752,26 @@ void opusgpu_ctx_destroy(opusgpu_ctx *ctx) {
     (void)hipFree(ctx->d_arena);
     (void)hipFree(ctx->d_pcm);
     (void)hipFree(ctx->d_result);
-    if (ctx->parse_stream) (void)hipStreamSynchronize(ctx->parse_stream);
-    if (ctx->recon_stream) (void)hipStreamSynchronize(ctx->recon_stream);
+    pipeline_destroy(ctx);
     for (int i = 0; i < 6; i++) {
         (void)hipFree(ctx->d_recs[i]);
         (void)hipFree(ctx->d_rout[i]);
-        if (i < 3 && ctx->ev_post[i]) (void)hipEventDestroy(ctx->ev_post[i]);
     }
     for (int i = 0; i < OG_SILK_SETS; i++) {
         (void)hipFree(ctx->d_handoff[i]);
         (void)hipFree(ctx->d_srecs[i]);
-        if (ctx->ev_sdone[i]) (void)hipEventDestroy(ctx->ev_sdone[i]);
     }
-    if (ctx->ev_sparsed) (void)hipEventDestroy(ctx->ev_sparsed);
-    if (ctx->ev_sp) (void)hipEventDestroy(ctx->ev_sp);
-    if (ctx->ev_spar) (void)hipEventDestroy(ctx->ev_spar);
-    if (ctx->ev_hrecon) (void)hipEventDestroy(ctx->ev_hrecon);
     (void)hipFree(ctx->d_shadow);
     (void)hipHostFree(ctx->h_pcm);
     (void)hipHostFree(ctx->h_res);
     (void)hipHostFree(ctx->h_arena);
     (void)hipHostFree(ctx->h_descs);
     (void)hipFree(ctx->d_crc_tables);
-    (void)hipFree(ctx->d_started);
     for (hipEvent_t e : ctx->ev_piece)
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : ctx->ev_part)
         if (e) (void)hipEventDestroy(e);
-    if (ctx->side_stream) {
-        (void)hipStreamSynchronize(ctx->side_stream);
-        (void)hipStreamDestroy(ctx->side_stream);
-    }
-    if (ctx->ev_fork) {
-        (void)hipEventDestroy(ctx->ev_fork);
-        (void)hipEventDestroy(ctx->ev_join);
-    }
     if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
-    if (ctx->parse_stream) (void)hipStreamDestroy(ctx->parse_stream);
-    if (ctx->recon_stream) (void)hipStreamDestroy(ctx->recon_stream);
-    if (ctx->ev_front) (void)hipEventDestroy(ctx->ev_front);
-    if (ctx->ev_parsed) (void)hipEventDestroy(ctx->ev_parsed);
-    if (ctx->ev_recon) (void)hipEventDestroy(ctx->ev_recon);
     (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }
@@ -879,27 +786,13 @@ int opusgpu_get_mode(const opusgpu_ctx *ctx) { return ctx ? ctx->mode : OPUSGPU_
 int opusgpu_set_pipeline(opusgpu_ctx *ctx, int on) {
     if (!ctx) return OPUSGPU_BAD_ARG;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (on && !ctx->parse_stream) {
-        // the early parse is a single round of long-running workgroups: it is placed first (highest priority), the
-        // reconstruction it runs next to fills the slots around it
-        int least = 0, greatest = 0;
-        HIPCHK(ctx, hipDeviceGetStreamPriorityRange(&least, &greatest));
-        if (!og_debug().parse_priority) greatest = least;
-        HIPCHK(ctx, hipStreamCreateWithPriority(&ctx->parse_stream, hipStreamNonBlocking, greatest));
-        HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->recon_stream, hipStreamNonBlocking));
-        HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_front, hipEventDisableTiming));
-        HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_parsed, hipEventDisableTiming));
-        HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_recon, hipEventDisableTiming));
-        for (int i = 0; i < 3; i++) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_post[i], hipEventDisableTiming));
-        HIPCHK(ctx, hipMalloc((void **)&ctx->d_started, 128));
-        HIPCHK(ctx, hipMemset(ctx->d_started, 0, 128));
-    }
+    if (on)
+        if (int rc = pipeline_create(ctx)) return rc;
     if ((on != 0) != (ctx->pipeline != 0)) { // switching: from an idle device (steps of either kind may be queued on any stream)
         HIPCHK(ctx, hipDeviceSynchronize());
-        ctx->front_recorded = ctx->post_recorded[0] = ctx->post_recorded[1] = ctx->post_recorded[2] = 0;
-        for (int i = 0; i < OG_SILK_SETS; i++) ctx->sdone_recorded[i] = 0;
-        ctx->last_kind = 0;
-        ctx->shadow_epoch++;
+        ctx->sp.drained();
+        ctx->sp.last_kind = 0;
+        ctx->sp.shadow_epoch++;
     }
     ctx->pipeline = on ? 1 : 0;
     return OPUSGPU_OK;
@@ -913,14 +806,9 @@ int opusgpu_streams_reset(opusgpu_ctx *ctx, int first, int count, int full) {
     if (!ctx || first < 0 || count < 0 || first + count > ctx->n_streams) return OPUSGPU_BAD_ARG;
     if (count == 0) return OPUSGPU_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (ctx->parse_stream) { // whatever pipelined steps still have in flight works on the state this resets
-        HIPCHK(ctx, hipStreamSynchronize(ctx->parse_stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->recon_stream));
-        if (ctx->last_step_stream) HIPCHK(ctx, hipStreamSynchronize(ctx->last_step_stream));
-    }
-    ctx->front_recorded = ctx->post_recorded[0] = ctx->post_recorded[1] = ctx->post_recorded[2] = 0; // (the reset below is synchronous)
-    for (int i = 0; i < OG_SILK_SETS; i++) ctx->sdone_recorded[i] = 0;
-    ctx->shadow_epoch++; // (the parse kernel's copies of these streams' past are stale now)
+    if (int rc = sync_in_flight(ctx)) return rc; // whatever pipelined steps still have in flight works on the state this resets
+    ctx->sp.drained();                           // (the reset below, on the context's stream, is synchronous)
+    ctx->sp.shadow_epoch++; // (the parse kernel's copies of these streams' past are stale now)
     hipLaunchKernelGGL(k_stream_init, dim3(count), dim3(64), 0, ctx->stream, ctx->d_streams, first, count, ctx->channels,
                        full ? 1 : 0);
     HIPCHK(ctx, hipGetLastError());
@@ -935,11 +823,7 @@ int opusgpu_streams_alloc(opusgpu_ctx *ctx, int n_streams, int channels) {
     if (!ctx || n_streams <= 0 || (channels != 1 && channels != 2)) return OPUSGPU_BAD_ARG;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->parse_stream) { // pipelined steps still in flight work on the state that is about to be freed
-        HIPCHK(ctx, hipStreamSynchronize(ctx->parse_stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->recon_stream));
-        if (ctx->last_step_stream) HIPCHK(ctx, hipStreamSynchronize(ctx->last_step_stream));
-    }
+    if (int rc = sync_in_flight(ctx)) return rc; // pipelined steps still in flight work on the state that is about to be freed
     if (ctx->d_streams) {
         HIPCHK(ctx, hipFree(ctx->d_streams));
         ctx->d_streams = nullptr;
@@ -952,7 +836,7 @@ int opusgpu_streams_alloc(opusgpu_ctx *ctx, int n_streams, int channels) {
     e = hipMalloc(&ctx->d_shadow, sizeof(SilkShadow) * (size_t)n_streams);
     if (e != hipSuccess) return fail(ctx, OPUSGPU_ALLOC_FAIL, "hipMalloc(shadow)", e);
     HIPCHK(ctx, hipMemset(ctx->d_shadow, 0, sizeof(SilkShadow) * (size_t)n_streams)); // (epoch 0: never current)
-    ctx->shadow_epoch++;
+    ctx->sp.shadow_epoch++;
     ctx->n_streams = n_streams;
     ctx->channels = channels;
     ctx->last_count.assign((size_t)n_streams, 0);
@@ -982,17 +866,6 @@ int opusgpu_memcpy_h2d(opusgpu_ctx *ctx, void *dst, const void *src, size_t byte
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return OPUSGPU_OK;
 }
-// Whatever pipelined steps still have in flight -- the last step's reconstruction on recon_stream, an early parse, the step's
-// own stream when the caller supplied one -- works on state, records and ReconOut: a read-back waits for all of it, not only
-// for the context's stream.
-static int sync_in_flight(opusgpu_ctx *ctx) {
-    if (ctx->parse_stream) {
-        HIPCHK(ctx, hipStreamSynchronize(ctx->parse_stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->recon_stream));
-    }
-    if (ctx->last_step_stream && ctx->last_step_stream != ctx->stream) HIPCHK(ctx, hipStreamSynchronize(ctx->last_step_stream));
-    return OPUSGPU_OK;
-}
 int opusgpu_memcpy_d2h(opusgpu_ctx *ctx, void *dst, const void *src, size_t bytes) {
     if (!ctx) return OPUSGPU_BAD_ARG;
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -1002,456 +875,6 @@ int opusgpu_memcpy_d2h(opusgpu_ctx *ctx, void *dst, const void *src, size_t byte
     return OPUSGPU_OK;
 }
 
-// `tables_resident`: the step's descriptors and payload bytes are complete in device memory now (the public entry's contract
-// when pipelining is on); false when this call's own uploads are still queued on the step's stream (opusgpu_decode_packets):
-// such a step does not run ahead of anything.
-// OPUSGPU_LAUNCH_DELAY_US (og_debug.hpp): the host dawdles before the launches of a decode step -- what a loaded host, a slow
-// event hop or another thread's launches would do -- so that tools/launch_jitter.py can show the step time does not depend on it
-#ifndef OG_SILK_PARSE_WIDE_MIN
-#define OG_SILK_PARSE_WIDE_MIN 98304 // frames of an in-order launch from which the SILK parse runs with 64 frames per wave
-#endif
-#ifndef OG_HALVES_MIN
-#define OG_HALVES_MIN 4096 // frames per half below which an in-order step is not cut in two
-#endif
-static void launch_jitter() {
-    if (const int us = og_debug().launch_delay_us) std::this_thread::sleep_for(std::chrono::microseconds(us));
-}
-// `next_n` (steps queued as a window, opusgpu_decode_steps_device): the number of frames of the step that the same call queues
-// right behind this one with the same mode mask, 0 when there is none or it is not known.
-// `slices` (opusgpu_decode_packets: PCM that leaves in pieces): the step's entropy kernels run once over all n frames -- they wait
-// on latency, a fraction of the frames takes them as long as all -- and the arithmetic kernels slice by slice, frames
-// [bounds[i], bounds[i + 1]); after_slice(i) is called behind slice i's last launch (to queue that slice's copies).
-// A step is of one of three kinds: in order (0), pipelined CELT-only (1), pipelined SILK-only (2).  Going into or out of a run of
-// pipelined SILK-only steps happens from an idle device (their parse reads the stream state when it has no current copy of its
-// own, and whatever follows them reads what their last kernels write); every step of another kind ends the epoch of the parse
-// kernel's copies (it may write SILK state, or prev_mode, behind that kernel's back).
-// keeps_kind (OPUSGPU_STEP_KEEPS_MODE): the caller's word that no stream of this step has decoded a frame of another mode (SILK-only,
-// hybrid, CELT-only) since its last reset.  Such a step shares no stream with anything of the other kind that is still in flight,
-// so going from one pipelined kind to the other needs no drain, and a CELT-only step leaves the SILK parse kernel's copies (of
-// other streams) as current as they were.
-// ... as long as the two kinds really are about different streams: a kind-2 step that carries CELT-only frames along (any mix under
-// OPUSGPU_STEP_KEEPS_MODE, `celt_frames`) reconstructs them on ITS stream, ordered only against other kind-2 steps, while a kind-1
-// step's reconstruction runs on recon_stream and waits only for kind-1 steps.  Next to each other the two would work on the same
-// CELT-only streams' state with nothing in between: that change of kind drains like an undeclared one.
-static int enter_step_kind(opusgpu_ctx *ctx, int kind, hipStream_t s, bool keeps_kind = false, bool celt_frames = false) {
-    const bool shares_celt = (kind == 1 && ctx->last_kind == 2 && ctx->last_kind2_celt) || (kind == 2 && celt_frames && ctx->last_kind == 1);
-    const bool disjoint = keeps_kind && kind != 0 && ctx->last_kind != 0 && !shares_celt;
-    if ((kind == 2) != (ctx->last_kind == 2) && !disjoint) {
-        if (int rc = sync_in_flight(ctx)) return rc;
-        HIPCHK(ctx, hipStreamSynchronize(s));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        ctx->front_recorded = ctx->post_recorded[0] = ctx->post_recorded[1] = ctx->post_recorded[2] = 0;
-        for (int i = 0; i < OG_SILK_SETS; i++) ctx->sdone_recorded[i] = 0;
-        ctx->last_silk_mask = 0;
-    }
-    if (kind != 2 && !(keeps_kind && kind == 1)) ctx->shadow_epoch++;
-    ctx->last_kind = kind;
-    if (kind == 2) ctx->last_kind2_celt = celt_frames;
-    return OPUSGPU_OK;
-}
-
-// Records and reconstruction output of slot `par` for a step of `need` frames.
-static int grow_step_slot(opusgpu_ctx *ctx, int par, size_t need) {
-    int rc;
-    if (ctx->cap_recs[par] < sizeof(ParseRec) * need && (rc = grow(ctx, &ctx->d_recs[par], &ctx->cap_recs[par], sizeof(ParseRec) * need)))
-        return rc;
-    if (ctx->cap_rout[par] < sizeof(ReconOut) * need && (rc = grow(ctx, &ctx->d_rout[par], &ctx->cap_rout[par], sizeof(ReconOut) * need)))
-        return rc;
-    return OPUSGPU_OK;
-}
-
-// A window that ends early (a HIP error between two of its steps): the placement waits of the last step queued -- for workgroups
-// of a step that will not come -- are let go by writing the counts they wait for; the waits are placement only (events carry the
-// data dependencies), so whatever is queued completes.  Then the device drains and the counters restart from zero.
-static void release_window_waits(opusgpu_ctx *ctx) {
-    if (!ctx->d_started || (!ctx->window_parse_target && !ctx->window_recon_target)) return;
-    hipStream_t q = nullptr;
-    if (hipStreamCreateWithFlags(&q, hipStreamNonBlocking) == hipSuccess) {
-        if (ctx->window_parse_target) (void)hipStreamWriteValue32(q, ctx->d_started, ctx->window_parse_target, 0);
-        if (ctx->window_recon_target) (void)hipStreamWriteValue32(q, ctx->d_started + 16, ctx->window_recon_target, 0);
-        (void)hipStreamSynchronize(q);
-        (void)hipStreamDestroy(q);
-    }
-    (void)sync_in_flight(ctx);
-    (void)hipStreamSynchronize(ctx->stream);
-    (void)hipMemset(ctx->d_started, 0, 128);
-    ctx->parse_started_total = ctx->recon_started_total = 0;
-    ctx->window_parse_target = ctx->window_recon_target = 0;
-    (void)hipGetLastError();
-}
-
-struct StepSlices {
-    int count = 0;
-    const size_t *bounds = nullptr;
-    std::function<int(int)> after_slice;
-};
-static int decode_step_impl(opusgpu_ctx *ctx, int n, const void *d_descs, const void *d_arena, void *d_pcm, void *d_result,
-                            void *hip_stream, bool tables_resident, int modes = 7, int next_n = 0, const StepSlices *slices = nullptr) {
-    if (!ctx || n < 0 || !ctx->d_streams) return OPUSGPU_BAD_ARG;
-    if (n == 0) return OPUSGPU_OK;
-    if (!d_descs || !d_arena || !d_pcm || !d_result) return OPUSGPU_BAD_ARG;
-    if ((uintptr_t)d_arena & 15) return OPUSGPU_BAD_ARG; // (the parse kernels fetch packets as aligned 16-byte pieces, og_range.hpp)
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
-    const int pcm_stride = (ctx->mode == OPUSGPU_MODE_RFC ? OPUSGPU_RFC_FRAME_SAMPLES : OPUSGPU_FRAME_SAMPLES) * ctx->channels;
-    // OPUSGPU_STALL_STREAM (og_debug.hpp): in front of every kernel of the step on the named stream, a wave that holds that stream --
-    // it falls behind the others by whole steps, and only the events between the streams keep the kernels in order
-    auto stall = [&](hipStream_t q) {
-        if (!ctx->stall_ticks) return;
-        const int w = og_debug().stall_stream;
-        hipStream_t const t = w == 1 ? s : w == 2 ? ctx->parse_stream : w == 3 ? ctx->recon_stream : ctx->side_stream;
-        if (t && q == t) hipLaunchKernelGGL(k_stream_stall, dim3(1), dim3(64), 0, q, ctx->stall_ticks, (int)OG_STALL_MAX_SPINS);
-    };
-    ctx->last_descs = d_descs;
-    ctx->last_n = ctx->mode == OPUSGPU_MODE_RFC || !ctx->split_celt ? 0 : n;
-    ctx->last_had_silk_recs = ctx->split_celt && ctx->split_hybrid;
-    if (ctx->mode == OPUSGPU_MODE_RFC) { // every frame on the one kernel of that mode (og_rfc.hip)
-        HIPCHK(ctx, hipSetDevice(ctx->device));
-        if (int rc = enter_step_kind(ctx, 0, s)) return rc;
-        stall(s);
-        og_launch_decode_rfc(s, d_descs, d_arena, ctx->d_streams, d_pcm, d_result, n, ctx->n_streams, pcm_stride);
-        HIPCHK(ctx, hipGetLastError());
-        if (ctx->pipeline) { // (a later pipelined step's early parse waits for all of this one)
-            HIPCHK(ctx, hipEventRecord(ctx->ev_front, s));
-            ctx->front_recorded = 1;
-        }
-        ctx->last_step_stream = s;
-        return OPUSGPU_OK;
-    }
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (!ctx->split_celt) { // OPUSGPU_SPLIT=0 (A/B measurements): every frame through the single kernel, in order
-        if (int rc = enter_step_kind(ctx, 0, s)) return rc;
-        stall(s);
-        hipLaunchKernelGGL(k_decode_step, dim3(n), dim3(64), 0, s, (const FrameDesc *)d_descs, (const u8 *)d_arena, ctx->d_streams,
-                           (i16 *)d_pcm, (i32 *)d_result, n, ctx->n_streams, pcm_stride, 0, nullptr, nullptr, 0);
-        HIPCHK(ctx, hipGetLastError());
-        ctx->last_step_stream = s;
-        if (slices) // (one kernel for the whole step: every slice's PCM is there behind it)
-            for (int i = 0; i < slices->count; i++)
-                if (int rc = slices->after_slice(i)) return rc;
-        return OPUSGPU_OK;
-    }
-    // `modes` (bit 0 SILK-only, 1 hybrid, 2 CELT-only frames may be present; 7 = not known): the kernels of modes the caller
-    // rules out are not launched; k_celt_post reports a frame of such a mode as OPUSGPU_BAD_ARG
-    const bool keeps_kind = (modes & OPUSGPU_STEP_KEEPS_MODE) != 0;
-    modes &= 7;
-    if (!modes) modes = 7;
-    const bool any_silk = (modes & 3) != 0, any_celt = (modes & 6) != 0;
-    // Only a step the caller declares CELT-only runs ahead of the step before it.  (Round 2 also ran the CELT-only part of a
-    // mixed step's parse ahead: 4 % on the mixed-pages workload.  Cutting such a step into two halves -- below -- gains 6 %, and
-    // the two do not combine: a mixed or undeclared step takes the halves.)
-    const bool pipe = ctx->pipeline && tables_resident && modes == 4;
-    const bool window = pipe && next_n > 0; // the next step is queued by this very call: see PLACEMENT
-    // ... and a step declared free of CELT-only frames runs its parse kernels ahead (PIPELINED SILK / HYBRID STEPS below)
-    // -- or, with the caller's word that no stream of the step ever changes its mode (OPUSGPU_STEP_KEEPS_MODE), a step of ANY mix with
-    // SILK-only / hybrid frames in it: its CELT-only frames' parse carries the band energies like a pipelined CELT-only step's, and a
-    // CELT-only frame cannot make another stream's SILK copy stale
-    const bool pipe_silk = ctx->pipeline && tables_resident && ((modes & 4) == 0 || keeps_kind) && (modes & 3) != 0 && ctx->split_hybrid && !slices &&
-                           (modes == 1 ? og_debug().silk_pipeline : og_debug().hybrid_pipeline);
-    if (int rc = enter_step_kind(ctx, pipe ? 1 : pipe_silk ? 2 : 0, s, keeps_kind, (modes & 4) != 0)) return rc;
-    if (ctx->pipeline && ctx->last_step_stream && ctx->last_step_stream != s) {
-        // consecutive steps on different streams: nothing orders them but the caller, so nothing may run ahead either
-        HIPCHK(ctx, hipStreamSynchronize(ctx->last_step_stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->parse_stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->recon_stream));
-        ctx->front_recorded = ctx->post_recorded[0] = ctx->post_recorded[1] = ctx->post_recorded[2] = 0;
-    }
-    ctx->last_step_stream = s;
-    // The records, the reconstruction's per-frame output and the hand-off buffers only grow; growing frees the old one, which
-    // waits for the device to go idle.  Records and reconstruction output exist twice: pipelined steps alternate.
-    if (pipe) ctx->slot = (ctx->slot + 1) % 3;
-    if (pipe_silk) ctx->silk_slot = (ctx->silk_slot + 1) % OG_SILK_SETS;
-    const int sset = pipe_silk ? ctx->silk_slot : 0; // the set of SILK records and hand-offs this step uses (and of CELT records with them)
-    const int par = pipe ? ctx->slot : pipe_silk ? 3 + sset : 0, par2 = (par + 1) % 3; // this step's slot; (pipelined CELT-only steps:) the slot of the step two before it
-    if (int rc = grow_step_slot(ctx, par, (size_t)n)) return rc; // (a window's slots were sized before its first launch)
-    if (ctx->split_hybrid && any_silk) {
-        int rc;
-        if (ctx->cap_handoff[sset] < sizeof(SilkHandoff) * (size_t)n || ctx->cap_srecs[sset] < sizeof(SilkRec) * (size_t)n) {
-            if (pipe_silk) { // (growing frees: not under kernels of the other set that are still in flight)
-                if ((rc = sync_in_flight(ctx))) return rc;
-                HIPCHK(ctx, hipStreamSynchronize(s));
-            }
-            if (ctx->cap_handoff[sset] < sizeof(SilkHandoff) * (size_t)n &&
-                (rc = grow(ctx, &ctx->d_handoff[sset], &ctx->cap_handoff[sset], sizeof(SilkHandoff) * (size_t)n)))
-                return rc;
-            if (ctx->cap_srecs[sset] < sizeof(SilkRec) * (size_t)n &&
-                (rc = grow(ctx, &ctx->d_srecs[sset], &ctx->cap_srecs[sset], sizeof(SilkRec) * (size_t)n)))
-                return rc;
-        }
-    }
-    ParseRec *const recs = (ParseRec *)ctx->d_recs[par];
-    ReconOut *const rout = (ReconOut *)ctx->d_rout[par];
-    SilkHandoff *const handoff = ctx->split_hybrid && any_silk ? (SilkHandoff *)ctx->d_handoff[sset] : nullptr;
-    SilkRec *const srecs = ctx->split_hybrid && any_silk ? (SilkRec *)ctx->d_srecs[sset] : nullptr;
-    ctx->last_recs = recs;
-    ctx->last_srecs = srecs;
-    ctx->last_had_silk_recs = srecs != nullptr;
-    const dim3 parse_block(64 * OG_PL_WAVES);
-    // The in-order chain of frames [f0, f0 + cnt) of the step, in two halves: the ENTROPY kernels (one frame per lane) ...
-    // `pq` (pipelined SILK / hybrid steps): the stream the parameter half runs on -- behind this step's SILK parse and the parameter
-    // half of the step before, but off the entropy chain: the parse of the next step does not wait for it (SilkShadow's two sides)
-    auto front = [&](hipStream_t q, size_t f0, int cnt, SilkShadow *shadow = nullptr, u32 epoch = 0, hipStream_t pq = nullptr) {
-        const FrameDesc *dd = (const FrameDesc *)d_descs + f0;
-        if (srecs) {
-            stall(q);
-            // (64 frames per wave where the kernel's issue slots are what counts: pipelined steps, large batches; 32 for a small
-            // in-order step, whose time is the latency of one wave's serial chain -- same-box: SILK-NB in order 1.36 / 1.41 ms)
-            if (shadow || cnt >= OG_SILK_PARSE_WIDE_MIN || og_debug().parse_wide == 2)
-                hipLaunchKernelGGL(k_silk_parse64, dim3((cnt + 63) / 64), dim3(64), 0, q, dd, (const u8 *)d_arena,
-                                   (const StreamState *)ctx->d_streams, srecs + f0, handoff + f0, cnt, ctx->n_streams, shadow, epoch);
-            else
-                hipLaunchKernelGGL(k_silk_parse, dim3((cnt + 31) / 32), dim3(64), 0, q, dd, (const u8 *)d_arena,
-                                   (const StreamState *)ctx->d_streams, srecs + f0, handoff + f0, cnt, ctx->n_streams, shadow, epoch);
-            if (pq && pq != q) {
-                (void)hipEventRecord(ctx->ev_sp, q);
-                (void)hipStreamWaitEvent(pq, ctx->ev_sp, 0);
-            }
-            stall(pq ? pq : q);
-            hipLaunchKernelGGL(k_silk_params, dim3((cnt + OG_PAR_LANES / 2 - 1) / (OG_PAR_LANES / 2)), dim3(64), 0, pq ? pq : q, dd,
-                               (const StreamState *)ctx->d_streams, srecs + f0, cnt, ctx->n_streams, shadow, epoch);
-            if (pq && pq != q) (void)hipEventRecord(ctx->ev_spar, pq);
-        }
-        if (any_celt) stall(q);
-        if (any_celt && ((shadow && og_debug().parse_wide) || og_debug().parse_wide == 2)) { // (a pipelined step: the wide parse, like pipelined CELT-only steps)
-            const int fr = og_celt_parse64_frames();
-            og_launch_celt_parse64(q, (cnt + fr - 1) / fr, dd, d_arena, ctx->d_streams, recs + f0, cnt, ctx->n_streams,
-                                   handoff ? handoff + f0 : nullptr, (int)PARSE_ALL, 1, nullptr);
-        } else if (any_celt)
-            hipLaunchKernelGGL(k_celt_parse, dim3((cnt + OG_PL_FRAMES - 1) / OG_PL_FRAMES), parse_block, 0, q, dd, (const u8 *)d_arena,
-                               ctx->d_streams, recs + f0, cnt, ctx->n_streams, (const SilkHandoff *)(handoff ? handoff + f0 : nullptr),
-                               (int)PARSE_ALL, 1, (u32 *)nullptr);
-    };
-    // ... and the ARITHMETIC ones (one frame per wave), which also write the PCM and the result codes
-    // `rq` (pipelined SILK / hybrid steps): the stream the CELT reconstruction runs on, NEXT TO the SILK synthesis instead of behind
-    // it -- a hybrid frame's two halves share nothing until the de-emphasis adds them (the synthesis takes prev_mode from the record,
-    // SilkRec::prev_mode), and the reconstruction of step k touches nothing the de-emphasis of step k - 1 still reads (it appends to
-    // the history ring; k_celt_post reads at the position the reconstruction recorded, as in pipelined CELT-only steps).  The ring
-    // holds two frames (2 x 960 of 2,048 samples): the reconstruction of step k waits for the last kernel of step k - 2, whose
-    // de-emphasis reads where it writes -- nothing else orders the two (the parse of step k waits only for step k - OG_SILK_SETS)
-    auto back_half = [&](hipStream_t q, size_t f0, int cnt, hipStream_t rq = nullptr) {
-        const FrameDesc *dd = (const FrameDesc *)d_descs + f0;
-        i16 *pp = (i16 *)d_pcm + f0 * (size_t)pcm_stride;
-        i32 *rr = (i32 *)d_result + f0;
-        const SilkHandoff *hh = handoff ? handoff + f0 : nullptr;
-        bool others = false; // (the kernels that report stream-index errors for every mode)
-        if (srecs) { // SILK-only frames and the SILK half of hybrid frames
-            // (a step that may hold SILK-only frames: the narrowband ones in the kernel whose LDS is sized for them, og_silk_nb.hip)
-            const int nb = (modes & 1) && og_debug().silk_nb_kernel;
-            stall(q);
-            if (nb) og_launch_silk_synth_nb(q, dd, d_arena, ctx->d_streams, pp, rr, cnt, ctx->n_streams, pcm_stride, handoff + f0, srecs + f0, 1);
-            if (nb) stall(q);
-            og_launch_silk_synth(q, dd, d_arena, ctx->d_streams, pp, rr, cnt, ctx->n_streams, pcm_stride, handoff + f0, srecs + f0, nb);
-            others = true;
-        } else if (any_silk) { // every frame that is not CELT-only (OPUSGPU_SPLIT_HYBRID=0)
-            stall(q);
-            hipLaunchKernelGGL(k_decode_step, dim3(cnt), dim3(64), 0, q, dd, (const u8 *)d_arena, ctx->d_streams, pp, rr, cnt, ctx->n_streams,
-                               pcm_stride, 1, nullptr, nullptr, 0);
-            others = true;
-        }
-        if (any_celt) {
-            hipStream_t const r = rq ? rq : q;
-            if (rq) {
-                (void)hipStreamWaitEvent(rq, ctx->ev_sparsed, 0); // (this step's CELT parse)
-                const int two_back = (sset + OG_SILK_SETS - 2) % OG_SILK_SETS; // (recorded after this step's kernels: still step k - 2's)
-                if (ctx->sdone_recorded[two_back]) (void)hipStreamWaitEvent(rq, ctx->ev_sdone[two_back], 0);
-            }
-            stall(r);
-            if (ctx->fast_recon) og_launch_celt_recon_fb(r, dd, ctx->d_streams, recs + f0, rout + f0, cnt, ctx->n_streams, handoff ? 1 : 0, nullptr);
-            if (ctx->fast_recon) stall(r);
-            hipLaunchKernelGGL(k_celt_recon, dim3(ctx->fast_recon ? (cnt + 63) / 64 : cnt), dim3(64), 0, r, dd, ctx->d_streams,
-                               (const ParseRec *)(recs + f0), rout + f0, cnt, ctx->n_streams, handoff ? 1 : 0, ctx->fast_recon);
-            if (rq) {
-                (void)hipEventRecord(ctx->ev_hrecon, rq);
-                (void)hipStreamWaitEvent(q, ctx->ev_hrecon, 0);
-            }
-        }
-        if (any_celt || !others || modes != 7) {
-            stall(q);
-            hipLaunchKernelGGL(k_celt_post, dim3((cnt * ctx->channels + 63) / 64), dim3(64), 0, q, dd, ctx->d_streams, (const ParseRec *)(recs + f0),
-                               (const ReconOut *)(rout + f0), rr, pp, cnt, ctx->n_streams, ctx->channels, pcm_stride, hh, modes, others ? 1 : 0);
-        }
-        if (srecs && (modes & 1)) { // the rare hybrid -> SILK-only transition frames (Q4), parked by k_silk_synth, through the full kernel
-            stall(q);
-            hipLaunchKernelGGL(k_decode_step, dim3((cnt + 63) / 64), dim3(64), 0, q, dd, (const u8 *)d_arena, ctx->d_streams, pp, rr, cnt,
-                               ctx->n_streams, pcm_stride, 1, handoff + f0, (const SilkRec *)(srecs + f0), 1);
-        }
-    };
-    if (pipe_silk) {
-        // PIPELINED SILK / HYBRID STEPS (no CELT-only frames).  k_silk_parse waits on latency (0.9 ms of one lane's serial chain for 0.27 ms of issue time at
-        // 65,536 frames), k_silk_synth is bound by issue: they fit next to each other, but within a step the second needs the
-        // first.  Across steps the parse needs of step k only what step k's parse already knows -- the indices' history, the gain
-        // index, the NLSFs, the rate and channel count, prev_mode: all of it entropy-side -- so it keeps a copy of its own
-        // (SilkShadow) and runs for step k + 1 on parse_stream while step k's synthesis is under way on the step's stream -- for
-        // hybrid frames followed by their CELT parse, which resumes its range decoder and carries the band energies itself as in
-        // pipelined CELT-only steps.  OG_SILK_SETS sets of records and hand-offs rotate; the parse of step k waits for the last kernel of step
-        // k - OG_SILK_SETS (its set's last reader -- and with it for every write to the state of streams it may have no current copy of),
-        // the CELT reconstruction beside the synthesis for the last kernel of step k - 2 (back_half: the history ring).
-        if (!ctx->ev_sparsed) {
-            HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_sparsed, hipEventDisableTiming));
-            HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_sp, hipEventDisableTiming));
-            HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_spar, hipEventDisableTiming));
-            HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_hrecon, hipEventDisableTiming));
-            for (int i = 0; i < OG_SILK_SETS; i++) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_sdone[i], hipEventDisableTiming));
-        }
-        if (ctx->sdone_recorded[sset]) HIPCHK(ctx, hipStreamWaitEvent(ctx->parse_stream, ctx->ev_sdone[sset], 0));
-        // One thing of the step before is not entropy-side: a SILK-only frame right behind a hybrid one (Q4) decodes a 2.5 ms CELT
-        // frame in the step's LAST kernel (the full kernel's second pass), which writes the band energies a hybrid frame's CELT parse
-        // predicts from.  So a step that may hold hybrid frames does not run ahead of a step that may have held SILK-only ones.
-        // (a stream that keeps its mode has no such frame: OPUSGPU_STEP_KEEPS_MODE)
-        const int prev_set = (sset + OG_SILK_SETS - 1) % OG_SILK_SETS; // (the step before this one)
-        if (!keeps_kind && (modes & 2) && (ctx->last_silk_mask & 1) && ctx->sdone_recorded[prev_set])
-            HIPCHK(ctx, hipStreamWaitEvent(ctx->parse_stream, ctx->ev_sdone[prev_set], 0));
-        ctx->last_silk_mask = modes;
-        // (Tried: the step's frames in chunks, the CELT parse of chunk c on the reconstruction's idle stream next to the SILK parse of
-        // chunk c + 1, so that the two entropy kernels do not run one after the other: hybrid-256k 12.7 -> 13.1 / 13.3 / 18.7 ms with
-        // 2 / 4 / 8 chunks.  The step is bound by what all its kernels issue together, not by the length of the entropy chain.)
-        front(ctx->parse_stream, 0, n, (SilkShadow *)ctx->d_shadow, (u32)ctx->shadow_epoch, og_debug().silk_params_aside ? ctx->recon_stream : nullptr);
-        HIPCHK(ctx, hipEventRecord(ctx->ev_sparsed, ctx->parse_stream));
-        HIPCHK(ctx, hipStreamWaitEvent(s, ctx->ev_sparsed, 0));
-        if (og_debug().silk_params_aside) HIPCHK(ctx, hipStreamWaitEvent(s, ctx->ev_spar, 0));
-        // (for steps without CELT-only frames: hybrid-256k 9.50 -> 9.35 ms; with them -- a mixed step's reconstruction is three times
-        // the work -- next to the synthesis it loses: mixed pages 7.02 -> 7.22 ms)
-        back_half(s, 0, n, (og_debug().hybrid_recon_aside == 2 || (og_debug().hybrid_recon_aside && (modes & 6) == 2)) ? ctx->recon_stream : nullptr);
-        HIPCHK(ctx, hipEventRecord(ctx->ev_sdone[sset], s));
-        ctx->sdone_recorded[sset] = 1;
-        HIPCHK(ctx, hipGetLastError());
-        return OPUSGPU_OK;
-    }
-    if (!pipe) {
-        if (!slices && n >= 2 * OG_HALVES_MIN && og_debug().halves) {
-            // TWO HALVES.  A step with SILK-only / hybrid frames runs in order -- k_silk_parse reads state the step's later kernels
-            // write, so nothing of the next step can start early -- and its kernels are of two kinds: the lane-per-frame parse
-            // kernels wait on latency with 13 % of their lanes active (k_silk_parse: 3.97 of a 15.4 ms step of 262,144 hybrid
-            // frames), the wave-per-frame ones are bound by vector-instruction issue.  The frames of a step belong to different
-            // streams and share nothing, so the step is cut in two and the halves' chains run on two streams: while one half's
-            // synthesis fills the SIMDs the other half parses in its gaps.  No state changes hands: each half is the in-order chain
-            // of its own frames over its own part of the records; the caller's stream forks the second one and joins it.
-            // (CELT-only steps too since round 5: 2.155 -> 2.07 ms per step of 65,536 -- the floor of an in-order step is one lane's
-            // parse, 0.85 ms whatever the batch, plus the reconstruction; only steps queued ahead hide the parse, opusgpu_set_pipeline)
-            if (!ctx->ev_fork) {
-                HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
-                HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
-            }
-            // (the second chain's stream: the one pipelined steps reconstruct on when there is one -- it is idle here, the caller's
-            // stream has waited for everything on it -- rather than one more: measured with a fourth stream of the context, the two
-            // chains no longer overlapped at all, 2.14 instead of 1.89 ms per SILK-NB step; the hardware queues are few)
-            if (!ctx->recon_stream && !ctx->side_stream) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->side_stream, hipStreamNonBlocking));
-            hipStream_t const side = ctx->recon_stream ? ctx->recon_stream : ctx->side_stream;
-            // (Both chains start together.  Staggered -- the second one behind the first one's parse kernels, so that one half parses
-            // while the other synthesises from the start -- was measured SLOWER, 14.9 against 14.5 ms per step of 262,144 hybrid
-            // frames and 2.44 against 1.90 ms per SILK-NB step: half a batch's parse takes as long as a whole batch's.)
-            HIPCHK(ctx, hipEventRecord(ctx->ev_fork, s));
-            HIPCHK(ctx, hipStreamWaitEvent(side, ctx->ev_fork, 0));
-            const int h = (n / 2 + 63) / 64 * 64; // (a multiple of the parse kernels' frames per workgroup)
-            front(s, 0, h);
-            back_half(s, 0, h);
-            front(side, (size_t)h, n - h);
-            back_half(side, (size_t)h, n - h);
-            HIPCHK(ctx, hipEventRecord(ctx->ev_join, side));
-            HIPCHK(ctx, hipStreamWaitEvent(s, ctx->ev_join, 0));
-        } else if (slices && slices->count > 1) {
-            front(s, 0, n);
-            for (int i = 0; i < slices->count; i++) {
-                const size_t lo = slices->bounds[i], hi = slices->bounds[i + 1];
-                if (hi > lo) back_half(s, lo, (int)(hi - lo));
-                if (int rc = slices->after_slice(i)) return rc;
-            }
-        } else {
-            front(s, 0, n);
-            back_half(s, 0, n);
-        }
-        HIPCHK(ctx, hipGetLastError());
-        if (ctx->pipeline) { // (a step that ran in order: whatever a later pipelined step runs ahead waits for all of it)
-            HIPCHK(ctx, hipEventRecord(ctx->ev_front, s));
-            ctx->front_recorded = 1;
-        }
-        return OPUSGPU_OK;
-    }
-    // The kernels of a step and what orders them:
-    //   FRONT   k_silk_parse  k_celt_parse  k_silk_synth (or the full kernel)  k_decode_step[Q4]
-    //   BACK    k_celt_recon_fb  k_celt_recon  ->  k_celt_post
-    // In order (the default): all on the step's stream.  After k_silk_parse the SILK synthesis and the CELT parse +
-    // reconstruction are independent (SilkRec::prev_mode, og_silk_parse.hpp); running them on two streams was measured
-    // (DESIGN.md section 6): next to k_celt_recon the synthesis gains nothing; next to k_celt_parse it gains 5 % on mixed-mode
-    // steps but costs 13 % on CELT-only steps.
-    // Pipelined (opusgpu_set_pipeline, a step the caller declares CELT-only; the tables are resident, so nothing here waits for
-    // the caller's earlier work):
-    //   parse_stream   [the last in-order step, post of step k-3]  k_celt_parse
-    //   recon_stream   [the parse, post of step k-2; in a window: every workgroup of the parse of step k+1]  k_celt_recon_fb  k_celt_recon
-    //   step's stream  [reconstruction of step k; in a window: the first round of the reconstruction of step k+1]  k_celt_post
-    // The entropy half reads one thing of the stream's state, the band energies, and writes them itself (celt_parse_lane): the
-    // parse of step k+1 depends on the parse of step k only.  The reconstruction touches neither the caller's buffers (its result
-    // codes go through ReconOut) nor anything k_celt_post reads of the step BEFORE (the history ring is written 960 samples
-    // further on; the ring position travels in ReconOut), so the reconstruction of step k+1 starts while k_celt_post of step k
-    // runs; two steps on, it waits for it (the ring holds two frames; records and ReconOut rotate through three sets).
-    // A step that is not declared CELT-only runs in order (ev_front: a later pipelined step's parse waits for all of it).
-    // PLACEMENT.  The three kernels compete for LDS: the parse is one round of 14 KB workgroups that live ~1 ms, the
-    // reconstruction 65,536 workgroups of 7.5 KB that live ~0.15 ms, the de-emphasis 10 KB ones that nothing waits for.  A parse
-    // workgroup that arrives when the CUs are full of reconstruction workgroups finds no hole that fits it (3.1 ms per step
-    // instead of 2.3), so the order that works is: parse of step k+1, THEN reconstruction of step k, THEN de-emphasis of step
-    // k-1.  Events cannot say "that kernel's workgroups have started"; round 2 approximated it with a wave that watched the wall
-    // clock.  When the caller queues a window of steps (opusgpu_decode_steps_device) the next step is known, and the order is a
-    // real dependency: the parse and reconstruction workgroups count themselves in when they start, and the stream that
-    // launches the dependent kernel waits on that count (hipStreamWaitValue32) -- placement does not depend on how long a launch
-    // or an event takes to arrive.  A single step (opusgpu_decode_step_device) cannot know whether another follows: its kernels
-    // are released by their data dependencies alone.
-    // (from here on: a pipelined step -- CELT-only frames, no SILK records, no hand-off)
-    // the early parse: behind the front of the step before and its own slot's last user (three steps back)
-    if (ctx->front_recorded) HIPCHK(ctx, hipStreamWaitEvent(ctx->parse_stream, ctx->ev_front, 0));
-    if (ctx->post_recorded[par]) HIPCHK(ctx, hipStreamWaitEvent(ctx->parse_stream, ctx->ev_post[par], 0));
-    const int wide = og_debug().parse_wide ? og_celt_parse64_frames() : OG_PL_FRAMES; // frames per group of the early parse
-    {
-        const int grid = (n + wide * ctx->parse_groups - 1) / (wide * ctx->parse_groups);
-        launch_jitter();
-        stall(ctx->parse_stream);
-        if (og_debug().parse_wide) // (64 frames per wave: next to the reconstruction the parse costs its issue slots, not its latency)
-            og_launch_celt_parse64(ctx->parse_stream, grid, d_descs, d_arena, ctx->d_streams, recs, n, ctx->n_streams, nullptr, (int)PARSE_CELT_ONLY,
-                                   ctx->parse_groups, ctx->d_started);
-        else
-            hipLaunchKernelGGL(k_celt_parse, dim3(grid), parse_block, 0, ctx->parse_stream, (const FrameDesc *)d_descs, (const u8 *)d_arena,
-                               ctx->d_streams, recs, n, ctx->n_streams, (const SilkHandoff *)nullptr, (int)PARSE_CELT_ONLY, ctx->parse_groups,
-                               ctx->d_started);
-        ctx->parse_started_total += (u32)grid;
-    }
-    HIPCHK(ctx, hipEventRecord(ctx->ev_parsed, ctx->parse_stream));
-    hipStream_t const back = ctx->recon_stream;
-    HIPCHK(ctx, hipStreamWaitEvent(back, ctx->ev_parsed, 0));
-    if (ctx->post_recorded[par2]) HIPCHK(ctx, hipStreamWaitEvent(back, ctx->ev_post[par2], 0)); // (the ring: 2 x 960 of 2048)
-    if (window) { // ... and every workgroup of the next step's parse has its place
-        const int next_grid = (next_n + wide * ctx->parse_groups - 1) / (wide * ctx->parse_groups);
-        ctx->window_parse_target = ctx->parse_started_total + (u32)next_grid;
-        HIPCHK(ctx, hipStreamWaitValue32(back, ctx->d_started, ctx->window_parse_target, hipStreamWaitValueGte, 0xffffffffu));
-    }
-    // reconstruct (one frame per wave) ...
-    if (ctx->fast_recon) {
-        launch_jitter();
-        stall(back);
-        og_launch_celt_recon_fb(back, d_descs, ctx->d_streams, recs, rout, n, ctx->n_streams, 0, ctx->d_started + 16);
-        ctx->recon_started_total += (u32)og_celt_recon_fb_signals(n);
-    }
-    stall(back);
-    hipLaunchKernelGGL(k_celt_recon, dim3(ctx->fast_recon ? (n + 63) / 64 : n), dim3(64), 0, back, (const FrameDesc *)d_descs, ctx->d_streams,
-                       (const ParseRec *)recs, rout, n, ctx->n_streams, 0, ctx->fast_recon);
-    HIPCHK(ctx, hipEventRecord(ctx->ev_recon, back));
-    HIPCHK(ctx, hipStreamWaitEvent(s, ctx->ev_recon, 0));
-    // Nothing waits for the de-emphasis for two steps, and placed before the next step's reconstruction its 10 KB workgroups
-    // take room that kernel -- the critical one -- would use: in a window it is held until the first round of that
-    // reconstruction has started (its count of started workgroups, one in 64 counted)
-    if (window && ctx->fast_recon) {
-        const int first_round = OG_MIN(og_celt_recon_fb_signals(next_n), 32);
-        ctx->window_recon_target = ctx->recon_started_total + (u32)first_round;
-        HIPCHK(ctx, hipStreamWaitValue32(s, ctx->d_started + 16, ctx->window_recon_target, hipStreamWaitValueGte, 0xffffffffu));
-    }
-    // ... -> de-emphasis and PCM (one (frame, channel) per lane); the result codes
-    launch_jitter();
-    stall(s);
-    hipLaunchKernelGGL(k_celt_post, dim3((n * ctx->channels + 63) / 64), dim3(64), 0, s, (const FrameDesc *)d_descs, ctx->d_streams,
-                       (const ParseRec *)recs, (const ReconOut *)rout, (i32 *)d_result, (i16 *)d_pcm, n, ctx->n_streams, ctx->channels,
-                       pcm_stride, (const SilkHandoff *)nullptr, modes, 0);
-    HIPCHK(ctx, hipEventRecord(ctx->ev_post[par], s));
-    ctx->post_recorded[par] = 1;
-    HIPCHK(ctx, hipGetLastError());
-    return OPUSGPU_OK;
-}
 
 int opusgpu_decode_step_device(opusgpu_ctx *ctx, int n, const void *d_descs, const void *d_arena, void *d_pcm,
                                void *d_result, void *hip_stream) {
@@ -1467,14 +890,6 @@ int opusgpu_decode_steps_device(opusgpu_ctx *ctx, int n_steps, const int32_t *n,
     if (!ctx || n_steps < 0 || modes < 0 || modes > 7) return OPUSGPU_BAD_ARG;
     if (n_steps == 0) return OPUSGPU_OK;
     if (!n || !d_descs || !d_arena || !d_pcm || !d_result) return OPUSGPU_BAD_ARG;
-    if (ctx->d_started && (ctx->parse_started_total > 0x70000000u || ctx->recon_started_total > 0x70000000u)) {
-        // the start counters only grow: long before they could wrap they restart from zero, on an idle device
-        HIPCHK(ctx, hipSetDevice(ctx->device));
-        if (int rc = sync_in_flight(ctx)) return rc;
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        HIPCHK(ctx, hipMemset(ctx->d_started, 0, 128));
-        ctx->parse_started_total = ctx->recon_started_total = 0;
-    }
     // Everything that can refuse a step is looked at BEFORE the first launch: step k of a window holds its reconstruction and its
     // de-emphasis until workgroups of step k + 1 have started (hipStreamWaitValue32 below), so a call that stopped between the two
     // would leave waits nothing satisfies.
@@ -1486,25 +901,7 @@ int opusgpu_decode_steps_device(opusgpu_ctx *ctx, int n_steps, const int32_t *n,
         max_n = OG_MAX(max_n, n[k]);
     }
     if (max_n == 0) return OPUSGPU_OK;
-    const int m = modes ? modes : 7;
-    if (ctx->pipeline && m == 4 && ctx->split_celt && ctx->mode != OPUSGPU_MODE_RFC) {
-        // ... and so is every allocation: the record slots only grow, growing frees the old buffer, and hipFree waits for ALL
-        // streams of the device -- among them the one whose head is such a wait for a parse that this thread has yet to launch.
-        // All three slots take the window's largest step now, while nothing of the window is queued.
-        HIPCHK(ctx, hipSetDevice(ctx->device));
-        for (int par = 0; par < 3; par++)
-            if (int rc = grow_step_slot(ctx, par, (size_t)max_n)) return rc;
-    }
-    for (int k = 0; k < n_steps; k++) {
-        const int next_n = k + 1 < n_steps ? n[k + 1] : 0;
-        const int rc = decode_step_impl(ctx, n[k], d_descs[k], d_arena[k], d_pcm[k], d_result[k], hip_stream, true, m, next_n > 0 ? next_n : 0);
-        if (rc) { // (a HIP error in the middle of a window: let go of what the steps before it wait for, then report it)
-            release_window_waits(ctx);
-            return rc;
-        }
-    }
-    ctx->window_parse_target = ctx->window_recon_target = 0; // (every wait of this window has its kernel queued behind it)
-    return OPUSGPU_OK;
+    return decode_window(ctx, n_steps, n, max_n, d_descs, d_arena, d_pcm, d_result, hip_stream, modes ? modes : 7);
 }
 
 #ifdef OG_PROF
@@ -1643,9 +1040,9 @@ int opusgpu_stream_wait_event(opusgpu_ctx *ctx, void *event, void *hip_stream) {
     HIPCHK(ctx, hipStreamWaitEvent(hip_stream ? (hipStream_t)hip_stream : ctx->stream, (hipEvent_t)event, 0));
     // the context's own stream: the streams pipelined steps run ahead on wait too -- what is behind the event (an upload of step
     // tables, opusgpu_upload_fence) is then as good as resident for every kernel of the steps queued after this call
-    if ((!hip_stream || (hipStream_t)hip_stream == ctx->stream) && ctx->parse_stream) {
-        HIPCHK(ctx, hipStreamWaitEvent(ctx->parse_stream, (hipEvent_t)event, 0));
-        HIPCHK(ctx, hipStreamWaitEvent(ctx->recon_stream, (hipEvent_t)event, 0));
+    if ((!hip_stream || (hipStream_t)hip_stream == ctx->stream) && ctx->sp.parse_stream) {
+        HIPCHK(ctx, hipStreamWaitEvent(ctx->sp.parse_stream, (hipEvent_t)event, 0));
+        HIPCHK(ctx, hipStreamWaitEvent(ctx->sp.recon_stream, (hipEvent_t)event, 0));
     }
     return OPUSGPU_OK;
 }

@@ -2,7 +2,8 @@
 //
 // None of them is needed in production: the defaults are what the measurements in DESIGN.md settled on.  They exist for A/B
 // runs of the same binary (tools/kstats.sh), for the robustness test of pipelined steps (tools/launch_jitter.py) and for the
-// cross-step ordering test (tests/test_gpu_stream_hazards.py).
+// cross-step ordering tests (tests/test_gpu_stream_hazards.py; tests/test_step_order.py on the CPU).  The scheduler that reads most
+// of them is og_step.hpp.
 //
 //   variable                  field            default  meaning
 //   OPUSGPU_SPLIT             split            1        0: every frame through the single kernel k_decode_step (round 1's design)

@@ -1,5 +1,5 @@
-// og_ms.hpp -- multistream decoding (include/opusgpu.h, MULTISTREAM): included at the end of og_api.hip, whose contexts and
-// decode_step_impl it drives.
+// og_ms.hpp -- multistream decoding (include/opusgpu.h, MULTISTREAM): included at the end of og_api.hip, whose contexts (og_ctx.hpp) and
+// decode_step_impl (og_step.hpp) it drives.
 //
 // An opusgpu_ms owns two ordinary contexts: a 2-channel one with n_decoders * coupled streams and a 1-channel one with
 // n_decoders * (streams - coupled) streams (either may be absent).  Decoder d's coupled stream s is stream d * coupled + s of the

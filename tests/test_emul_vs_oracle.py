@@ -67,7 +67,7 @@ def test_emulated_kernels_match_oracle(emu, oracle, seed, modes, switch):
 
 @pytest.mark.parametrize("seed,modes", [(11, [0]), (12, [0, 1]), (13, [0, 1, 2])])
 def test_entropy_half_past_kept_by_the_parse_matches_the_state(emu, oracle, seed, modes):
-    """Pipelined SILK-only steps (og_api.hip): the parse kernel keeps its own copy of what the entropy half needs of the frames
+    """Pipelined SILK-only steps (og_step.hpp: step_pipelined_silk): the parse kernel keeps its own copy of what the entropy half needs of the frames
     before (SilkShadow) and computes what the synthesis WILL write to the state.  Here, frame by frame in emulation: random walks
     over SILK NB / MB / WB and hybrid configurations, mono and stereo packets in mono and stereo decoders, empty-ish and error
     frames -- after every frame that decoded, the copy must equal the state field by field, and PCM and return codes the oracle's.

@@ -22,7 +22,7 @@ steps = int(os.environ.get("PROF_STEPS", "4"))  # steps of the traced run (bench
 for f in sorted(glob.glob(root + "/trace/**/*kernel_stats.csv", recursive=True)):
     with open(f) as fh:
         for row in csv.DictReader(fh):
-            # per STEP: a step with SILK frames launches its kernels twice (two halves on two streams, og_api.hip)
+            # per STEP: a step with SILK frames launches its kernels twice (two halves on two streams, og_step.hpp)
             durations[row["Name"].split("(")[0]] = float(row["TotalDurationNs"]) / steps / 1e6
 for kern in kernels:
     acc = defaultdict(list)
