@@ -153,7 +153,7 @@ struct ParseLds { // [element][lane]: lanes of a wave touch consecutive addresse
             // off the CUs the parse kernel runs on.
             u32 bw[NBANDS][OG_PL_LANES];
         } al;
-        i32 stack[5][6][OG_PL_LANES]; // split frames of the partition walk: [depth][word][lane]
+        i32 stack[4][5][OG_PL_LANES]; // split frames of the partition walk: [depth][word][lane] (every split takes one off LM = 3: four deep at most)
     } u;
 #ifdef OG_PL_PAD /* occupancy experiments only */
     u8 pad_experiment[OG_PL_PAD];
@@ -312,6 +312,76 @@ struct RecWriter {
     }
 };
 
+// isqrt32 (celt.cpp:3086) for arguments below 2^24, which a float holds exactly: the hardware's root is within one of the integer
+// root, and two comparisons settle it.  (The reference's bit-by-bit loop runs as long as the wave's largest argument needs.)
+// The root is below 4,096 there and a float's spacing at 4,096 is 2^-11, so any root good to a few units in the last place -- the
+// correctly rounded one the compiler emits by default as much as a bare v_sqrt_f32 -- truncates to the integer root or to one
+// beside it.  The CPU test walks all of 2^24 with the host's root; the only caller passes at most 8 x 129^2 + 1 = 133,129.
+OG_DEV u32 isqrt24(u32 val) {
+    u32 g = (u32)__builtin_sqrtf((float)val);
+    g -= g * g > val;
+    g += (g + 1) * (g + 1) <= val;
+    return g;
+}
+
+// compute_theta (celt.cpp:1241) as the partition walk calls it -- mono, no fill mask -- for a lane of its own.  The angle has one
+// of two models, uniform (ec_dec_uint) where the node still spans several short blocks and triangular where it does not, and a
+// parse wave holds frames of both kinds at nearly every split: compute_theta's three decode / update pairs then run one after the
+// other with a part of the lanes each.  Here a lane's model only chooses the total it decodes against and how the decoded value
+// maps to (itheta, fl, fs): ONE division pair, one update and one renormalisation for the whole wave.
+OG_DEV void split_theta_lane(RcLane &rc, int band, Split &sc, int N, i32 &b, int B0, int LM) {
+    int itheta = 0;
+    const int pulse_cap = RomLds::logn(band) + LM * (1 << BITRES);
+    const int offset = (pulse_cap >> 1) - 4;
+    const int qn = compute_qn(N, b, offset, pulse_cap, 0);
+    const u32 tell = rc_tell_frac(rc);
+    if (qn != 1) {
+        const bool uni = B0 > 1;
+        const int h = qn >> 1;
+        const int ftb = uni ? OG_MAX(ilog((u32)qn) - 8, 0) : 0; // ec_dec_uint(qn + 1): raw bits below the eight range-coded ones
+        const u32 ft = uni ? (u32)(qn >> ftb) + 1 : (u32)((h + 1) * (h + 1));
+        const u32 fm = rc_decode(rc, ft);
+        // the triangular model (celt.cpp:1290-1305): rising below the middle, falling above it.  (Lanes of the uniform model run
+        // this arithmetic too and drop the result: with fm < ft <= 257 there every value stays small and every shift defined.)
+        const bool low = fm < (u32)(h * (h + 1) >> 1);
+        const u32 root = isqrt24(8 * (low ? fm : ft - fm - 1) + 1);
+        const int it = low ? (int)((root - 1) >> 1) : (int)((2u * (u32)(qn + 1) - root) >> 1);
+        const int fs_t = low ? it + 1 : qn + 1 - it;
+        const u32 fl_t = low ? (u32)(it * (it + 1) >> 1) : ft - (u32)(fs_t * (fs_t + 1) >> 1);
+        const u32 fl = uni ? fm : fl_t, fs = uni ? 1u : (u32)fs_t;
+        rc_update(rc, fl, fl + fs, ft);
+        itheta = uni ? (int)fm : it;
+        if (ftb) {
+            const u32 t = fm << ftb | rc_bits(rc, (unsigned)ftb);
+            if (t > (u32)qn) rc.error = 1;
+            itheta = (int)OG_MIN(t, (u32)qn);
+        }
+        itheta = (int)udiv((u32)(itheta * 16384), (u32)qn);
+    }
+    const int qalloc = (int)(rc_tell_frac(rc) - tell);
+    b -= qalloc;
+    int imid, iside, delta;
+    if (itheta == 0) {
+        imid = 32767;
+        iside = 0;
+        delta = -16384;
+    } else if (itheta == 16384) {
+        imid = 0;
+        iside = 32767;
+        delta = 16384;
+    } else {
+        imid = bitexact_cos(itheta);
+        iside = bitexact_cos(16384 - itheta);
+        delta = frac_mul16((N - 1) << 7, bitexact_log2tan(iside, imid));
+    }
+    sc.inv = 0;
+    sc.imid = imid;
+    sc.iside = iside;
+    sc.delta = delta;
+    sc.itheta = itheta;
+    sc.qalloc = qalloc;
+}
+
 // quant_partition celt.cpp:1382, range-decoder half: split decisions, angles, pulse counts and PVQ indices.  The
 // partition tree itself does not reach the record: the reconstruction only needs its LEAVES in decode order, each with
 // what the tree implies for it -- position, size, gain, and how the band's fill / collapse masks map onto the leaf:
@@ -334,11 +404,10 @@ OG_DEV int parse_tree(RcLane &rc, RecWriter &out, int band, i32 &remaining_bits,
             if (!(LM != -1 && b > pulse_cache_max<RomLds>(band, LM) + 12 && N > 2)) break;
             const int B0 = B;
             Split sc;
-            i32 fill = 0;
             N >>= 1;
             LM -= 1;
             B = (B + 1) >> 1;
-            compute_theta<RomLds>(rc, band, 0, 0, remaining_bits, sc, N, b, B, B0, LM, 0, fill);
+            split_theta_lane(rc, band, sc, N, b, B0, LM);
             i32 delta = sc.delta;
             const int itheta = sc.itheta;
             if (B0 > 1 && (itheta & 0x3fff)) {
@@ -352,15 +421,25 @@ OG_DEV int parse_tree(RcLane &rc, RecWriter &out, int band, i32 &remaining_bits,
             remaining_bits -= sc.qalloc;
             const int mid_first = mbits >= sbits;
             const int off_side = off + (B0 >> 1), silent_mid = silent | (itheta == 16384), silent_side = silent | (itheta == 0);
-            i32 *F = &PL.u.stack[depth][0][OG_PCOL];
-            F[0 * OG_PL_LANES] = x | N << 11 | (LM + 1) << 19 | B << 22 | mid_first << 27 | 1 << 28;
-            F[1 * OG_PL_LANES] = mbits;
-            F[2 * OG_PL_LANES] = sbits;
-            F[3 * OG_PL_LANES] = remaining_bits;
-            // what the second child needs: its mask offset and whether it is silent
-            F[4 * OG_PL_LANES] = itheta | (mid_first ? off_side : off) << 16 | (mid_first ? silent_side : silent_mid) << 24;
             const i32 gain_mid = tr16(mul16_p15(gain, sc.imid)), gain_side = tr16(mul16_p15(gain, sc.iside));
-            F[5 * OG_PL_LANES] = (gain_mid & 0xffff) | gain_side << 16;
+            // The frame holds the SECOND child as it will start (celt.cpp:1440-1461): where it lies, its mask offset, whether it is
+            // silent, its gain, both children's bits and the budget as of now (for the rebalancing) -- and nothing of the split
+            // itself: once the second child has started nothing is left to do here, so it takes the frame with it and the way
+            // back from a leaf is ONE pop.  (The frames stayed until both children were done: a loop over the finished ones that
+            // the wave ran as often as its deepest lane needed, every lane's LDS reads depending on the word before.)
+            // Word 0 has no bit to spare: position < 2^11 (two channels of 960), half size N <= 88 of 8 bits, LM + 1 <= 3 of 3, blocks
+            // B <= 16 of 5, mask offset <= 15 of 4 (it sums B0 >> 1 = 8 + 4 + 2 + 1 at most), silence.
+#ifdef OG_HOST_EMUL
+            if (x + N >= 2048 || N > 255 || LM + 1 > 7 || B > 31 || off_side > 15) __builtin_trap();
+#endif
+            i32 *F = &PL.u.stack[depth][0][OG_PCOL];
+            F[0 * OG_PL_LANES] = (i32)((u32)(mid_first ? x + N : x) | (u32)N << 11 | (u32)(LM + 1) << 19 | (u32)B << 22 |
+                                       (u32)(mid_first ? off_side : off) << 27 | (u32)(mid_first ? silent_side : silent_mid) << 31);
+            F[1 * OG_PL_LANES] = mid_first ? mbits : sbits;
+            F[2 * OG_PL_LANES] = mid_first ? sbits : mbits;
+            F[3 * OG_PL_LANES] = remaining_bits;
+            // (the side gets nothing back when the angle is 0, the mid nothing when it is 16384)
+            F[4 * OG_PL_LANES] = ((mid_first ? gain_side : gain_mid) & 0xffff) | (itheta != (mid_first ? 0 : 16384)) << 16;
             depth++;
             if (mid_first) {
                 b = mbits;
@@ -395,40 +474,27 @@ OG_DEV int parse_tree(RcLane &rc, RecWriter &out, int band, i32 &remaining_bits,
             }
         }
         OG_MARK(44);
-        for (;;) { // back to the parents
-            if (depth == 0) {
-                OG_MARK(40);
-                const int need_low = has_low && n_fill > 0;
-                out.patch(jpos, (u32)n_fill | (u32)(out.nl - first_pvq) << JW_NPVQ_SHIFT | (u32)first_pvq << JW_FIRST_SHIFT |
-                                    (need_low ? JW_NEED_LOW : 0));
-                return need_low;
-            }
-            i32 *F = &PL.u.stack[depth - 1][0][OG_PCOL];
-            const i32 w0 = F[0];
-            const int mid_first = (w0 >> 27) & 1, stage = (w0 >> 28) & 3;
-            if (stage == 1) {
-                i32 mbits = F[1 * OG_PL_LANES], sbits = F[2 * OG_PL_LANES];
-                const int itheta = F[4 * OG_PL_LANES] & 0x7fff;
-                const i32 rebalance = (mid_first ? mbits : sbits) - (F[3 * OG_PL_LANES] - remaining_bits);
-                if (mid_first) {
-                    if (rebalance > 3 << BITRES && itheta != 0) sbits += rebalance - (3 << BITRES);
-                } else {
-                    if (rebalance > 3 << BITRES && itheta != 16384) mbits += rebalance - (3 << BITRES);
-                }
-                F[0] = (w0 & ~(3 << 28)) | 2 << 28;
-                N = (w0 >> 11) & 255;
-                LM = ((w0 >> 19) & 7) - 1;
-                B = (w0 >> 22) & 31;
-                x = (w0 & 2047) + (mid_first ? N : 0);
-                b = mid_first ? sbits : mbits;
-                gain = mid_first ? F[5 * OG_PL_LANES] >> 16 : (i32)(i16)F[5 * OG_PL_LANES];
-                off = (F[4 * OG_PL_LANES] >> 16) & 15;
-                silent = (F[4 * OG_PL_LANES] >> 24) & 1;
-                break;
-            }
+        if (depth == 0) break;
+        { // on to the innermost split's second child, with what the first one left of its bits (celt.cpp:1446-1461)
             depth--;
+            const i32 *F = &PL.u.stack[depth][0][OG_PCOL];
+            const u32 w0 = (u32)F[0];
+            const i32 w4 = F[4 * OG_PL_LANES];
+            const i32 rebalance = F[1 * OG_PL_LANES] - (F[3 * OG_PL_LANES] - remaining_bits);
+            b = F[2 * OG_PL_LANES] + ((rebalance > 3 << BITRES && (w4 >> 16)) ? rebalance - (3 << BITRES) : 0);
+            x = (int)(w0 & 2047);
+            N = (int)(w0 >> 11) & 255;
+            LM = (int)((w0 >> 19) & 7) - 1;
+            B = (int)(w0 >> 22) & 31;
+            off = (int)(w0 >> 27) & 15;
+            silent = (int)(w0 >> 31);
+            gain = (i32)(i16)w4;
         }
     }
+    OG_MARK(40);
+    const int need_low = has_low && n_fill > 0;
+    out.patch(jpos, (u32)n_fill | (u32)(out.nl - first_pvq) << JW_NPVQ_SHIFT | (u32)first_pvq << JW_FIRST_SHIFT | (need_low ? JW_NEED_LOW : 0));
+    return need_low;
 }
 
 // quant_all_bands celt.cpp:1754: the range-decoder half, plus everything else about a band that is known without the

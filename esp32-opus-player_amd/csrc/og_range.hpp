@@ -258,6 +258,27 @@ OG_DEV u32 rc_uint(R &rc, u32 ft_in) { // ec_dec_uint :2747
     return s;
 }
 
+// Lane-private flavour: as a non-template overload it takes EVERY rc_uint call on an RcLane -- the partition walk's codeword
+// indices, compute_theta's uniform angle, the intensity band, the post-filter octave, in both CELT parse kernels (the SILK lane
+// parse has no ec_dec_uint) -- and the template stays for the
+// wave-uniform Rc (rc_uint<RcLane>(...) still names the template's body: tests/emul/og_parse_kat.cpp compares the two that way).
+// The template above has a decode / update pair on either side of `ftb > 8`, and the lanes of a parse wave
+// (64 frames, 64 codebook sizes) nearly always disagree about it: the wave then runs both pairs -- four divisions and two
+// renormalisation loops -- with part of its lanes each.  Here the two sizes differ in the total they decode against and in the
+// raw bits that follow; decode, update and renormalisation are one instruction stream for all lanes.
+OG_DEV u32 rc_uint(RcLane &rc, u32 ft_in) { // ec_dec_uint :2747
+    ft_in--;
+    const int ftb = OG_MAX(ilog(ft_in) - 8, 0); // raw bits below the eight range-coded ones
+    const u32 ft = (ft_in >> ftb) + 1;
+    const u32 s = rc_decode(rc, ft);
+    rc_update(rc, s, s + 1, ft);
+    if (ftb == 0) return s;
+    const u32 t = s << ftb | rc_bits(rc, (unsigned)ftb);
+    if (t <= ft_in) return t;
+    rc.error = 1;
+    return ft_in;
+}
+
 template <class R>
 OG_DEV int rc_laplace(R &rc, u32 fs, int decay) { // ec_laplace_decode :3047
     int val = 0;
