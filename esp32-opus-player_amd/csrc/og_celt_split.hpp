@@ -995,6 +995,18 @@ OG_DEV u32 pvq_u3(u32 h) { // h < 2^11
 }
 OG_DEV int pvq_isqrt_near(u32 tq) { return (int)__builtin_amdgcn_sqrtf((float)tq); }
 #endif
+// Which of a leaf's blocks (of `blen` coefficients each) coefficient j lies in, without a division per pulse: j / blen is
+// (j * M) >> 16 for M = floor(65536 / blen) + 1 -- or that plus one -- whenever j < 176 and blen <= 176 (the error j (M - 65536 /
+// blen) / 65536 stays below 1 / blen; tests/test_pvq_walk_sites.py walks every j, blen and both M).  On the GPU M comes from the
+// reciprocal instruction: one ulp, and 65536 / blen is an integer (exactly represented, blen a power of two) or at least
+// 1 / blen away from one, which is 80 times the error of the product -- so the truncation is the floor.
+#ifdef OG_HOST_EMUL
+OG_DEV u32 pvq_block_mul(int blen) { return blen > 0 ? 65536u / (u32)blen + 1u : 0u; }
+OG_DEV int pvq_block_of(int j, u32 mul) { return (int)(((u32)j * mul) >> 16); }
+#else
+OG_DEV u32 pvq_block_mul(int blen) { return (u32)(65536.0f * __builtin_amdgcn_rcpf((float)blen)) + 1u; }
+OG_DEV int pvq_block_of(int j, u32 mul) { return (int)(__umul24((u32)j, mul) >> 16); } // (175 * 65537 < 2^24)
+#endif
 OG_DEV int pvq_row_base(const PvqLds &T, int r) { return (int)T.rb[r < 4 ? 4 : (r > 14 ? 14 : r)]; } // (rows outside 4..14 are not table rows)
 
 #ifndef OG_SKIP_RATIO
@@ -1013,6 +1025,10 @@ OG_DEV u32 pvq_leaf_lane(i16 *xv, const PvqLds &T, int n, int k, u32 i, int pos,
     const int N = n, K = k, x = pos;
     const int logB = ilog2(B), blen = N >> logB; // B is a power of two
     i32 yy = 0;
+    // The collapse mask -- which of the B blocks hold a pulse -- is gathered where the pulses are stored: the walk stores every
+    // non-zero itself, so the spectrum need not be read back for it.
+    const u32 bmul = pvq_block_mul(blen);
+    u32 cm = 0;
     // cwrsi celt.cpp:2545.  The reference has two code paths (k >= n: "lots of pulses", k < n: "lots of dimensions")
     // that differ only in how they walk its triangular table; with U(a, b) available for any pair both are
     //   s = (i >= U(n, k+1));  i -= s ? U(n, k+1) : 0;  k' = max { k' <= k : U(n, k') <= i };  value = +-(k - k');  i -= U(n, k')
@@ -1098,53 +1114,43 @@ OG_DEV u32 pvq_leaf_lane(i16 *xv, const PvqLds &T, int n, int k, u32 i, int pos,
         if (p0 <= i && s == 0) {
             i -= p0;
         } else { // a pulse: the largest k' < k with U(n, k') <= i (U(n, 0) = 0 <= i; U(n, k) > i here)
+            // ONE bisection for every lane of the wave (a wave of unrelated leaves has takers for each form of this search at
+            // nearly every step, and runs one loop after the other, each to its own deepest lane: DESIGN 6g).  A lane with n <= k
+            // searches along row n, columns 0 .. k - 1.  A lane with n > k searches the rows at column n, and only the table
+            // rows 4 .. k - 1 (rows from k on are not looked at: a row ends where its entries leave 32 bits, and only U(k, n) and
+            // the entries below it are known to exist): "3" stands for "no table row passes", and then the closed forms of rows
+            // 1 .. 3 are compared at once below the loop.  What differs between the two kinds is a probe's address.
             u32 plo = 0;
-            int kk = 0;
-            if (sparse) { // rows k' < k < n at column n
-                if (k <= 8) {
-                    // all candidates at once (rows 1..3 computed, rows 4..7 at fixed bases); U(., n) grows with the row: the last one
-                    // that passes is k' (rows from k on are not looked at: a row ends where its entries leave 32 bits, and only
-                    // U(k, n) and the entries below it are known to exist)
-                    const u32 c4 = T.at(ROM_PVQ_RB4 + n), c5 = T.at(ROM_PVQ_RB5 + n), c6 = T.at(ROM_PVQ_RB6 + n), c7 = T.at(ROM_PVQ_RB7 + n);
-                    const u32 cand[7] = {1u, v2, v3, c4, c5, c6, c7};
+            const bool tabp = sparse || tab; // the probes read the table (not so: row 3 in closed form)
+            const int off = sparse ? n : bn;
+            int lo = sparse ? OG_MIN(3, k - 1) : 0, hi = k - 1;
+            while (lo < hi) {
+                const int mid = (lo + hi + 1) >> 1; // >= 1 (n > k: >= 4)
+                const int rbm = pvq_row_base(T, mid);
+                const u32 tm = T.at(tabp ? (sparse ? rbm : mid) + off : 0);
+                const u32 pm = tabp ? tm : pvq_u3((u32)mid);
+                if (pm <= i) {
+                    lo = mid;
+                    plo = pm;
+                } else
+                    hi = mid - 1;
+            }
+            int kk = lo;
+            if (sparse && lo <= 3) { // U(., n) grows with the row: the last of rows 1 .. 3 (below k) that passes, or none
+                const u32 cand[3] = {1u, v2, v3};
+                kk = 0;
 #pragma unroll
-                    for (int r = 1; r <= 7; r++) {
-                        const bool ok = r < k && cand[r - 1] <= i;
-                        kk = ok ? r : kk;
-                        plo = ok ? cand[r - 1] : plo;
-                    }
-                } else {
-                    int lo = 0, hi = k - 1;
-                    while (lo < hi) {
-                        const int mid = (lo + hi + 1) >> 1;
-                        const u32 tm = T.at(mid >= 4 ? pvq_row_base(T, mid) + n : 0);
-                        const u32 pm = mid >= 4 ? tm : pvq_row_sel(mid, v2, v3);
-                        if (pm <= i) {
-                            lo = mid;
-                            plo = pm;
-                        } else
-                            hi = mid - 1;
-                    }
-                    kk = lo;
+                for (int r = 1; r <= 3; r++) {
+                    const bool ok = r < k && cand[r - 1] <= i;
+                    kk = ok ? r : kk;
+                    plo = ok ? cand[r - 1] : plo;
                 }
-            } else { // along row n
-                int lo = 0, hi = k - 1;
-                while (lo < hi) {
-                    const int mid = (lo + hi + 1) >> 1; // >= 1
-                    const u32 tm = T.at(tab ? bn + mid : 0);
-                    const u32 pm = tab ? tm : pvq_u3((u32)mid);
-                    if (pm <= i) {
-                        lo = mid;
-                        plo = pm;
-                    } else
-                        hi = mid - 1;
-                }
-                kk = lo;
             }
             const int val = (k - kk + s) ^ s;
             k = kk;
             i -= plo;
-            xv[pos] = (i16)val;
+            xv[pos] = (i16)val; // (never zero: k' < k)
+            cm |= 1u << pvq_block_of(pos - x, bmul);
             yy += val * val;
             b0 = pvq_row_base(T, k); // (rows k and k + 1, for the steps with more dimensions than pulses)
             b1 = pvq_row_base(T, k + 1);
@@ -1160,24 +1166,22 @@ OG_DEV u32 pvq_leaf_lane(i16 *xv, const PvqLds &T, int n, int k, u32 i, int pos,
         k = (int)((i + 1) >> 1);
         if (k) i -= 2 * (u32)k - 1;
         int val = (k0 - k + s) ^ s;
-        xv[pos++] = (i16)val;
+        xv[pos] = (i16)val;
+        cm |= (u32)(val != 0) << pvq_block_of(pos - x, bmul);
+        pos++;
         yy += val * val;
         s = -(int)i;
         val = (k + s) ^ s;
         xv[pos] = (i16)val;
+        cm |= (u32)(val != 0) << pvq_block_of(pos - x, bmul);
         yy += val * val;
     }
-    // collapse mask from the pulses
+#ifdef OG_PVQ_WALK_TAP // (host emulation, tests/emul/og_pvq_walk_kat.cpp: the pulses and their energy, before they are scaled)
+    OG_PVQ_WALK_TAP(xv + x, N, yy);
+#endif
+    // collapse mask: the blocks seen above (coefficients past B * blen, if any, belong to no block)
     OG_MARK(57);
-    u32 cm = 1;
-    if (B > 1) {
-        cm = 0;
-        for (int b = 0, j = 0; b < B; b++) {
-            u32 any = 0;
-            for (int e = 0; e < blen; e++, j++) any |= (u32)(u16)xv[x + j];
-            cm |= (u32)(any != 0) << b;
-        }
-    }
+    cm = B > 1 ? cm & ((1u << B) - 1u) : 1u;
     // scale the pulses in place
     OG_MARK(58);
     const int kk = ilog2(yy) >> 1;
