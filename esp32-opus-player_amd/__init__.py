@@ -31,6 +31,9 @@ EXPORTS = [
     "opusgpu_empty_packet_to_frames",
     "opusgpu_ms_create", "opusgpu_ms_destroy", "opusgpu_ms_last_error", "opusgpu_ms_set_mode", "opusgpu_ms_reset",
     "opusgpu_ms_packet_to_frames", "opusgpu_ms_decode_packets", "opusgpu_ms_decode_step_device", "opusgpu_ms_synchronize",
+    "opusgpu_files_plan", "opusgpu_file_batch_steps", "opusgpu_file_batch_step", "opusgpu_file_batch_segments", "opusgpu_file_batch_arena",
+    "opusgpu_file_batch_track_samples", "opusgpu_file_batch_packet_start", "opusgpu_file_batch_free", "opusgpu_tracks_assemble_device",
+    "opusgpu_files_decode",
 ]
 
 
@@ -96,6 +99,15 @@ PAGE_INFO_DTYPE = np.dtype([("status", "<i4"), ("packets", "<i4"), ("first_step"
                             ("serial", "<u4"), ("seqno", "<u4"), ("granulepos", "<i8")])
 PAGE_BAD_CAPTURE, PAGE_BAD_CRC, PAGE_SPANS, PAGE_BAD_PACKET, PAGE_BAD_STREAM = -200, -201, -202, -203, -204
 PAGES_VERIFY_CRC, PAGES_GROUP_BY_MODE, PAGES_ORDER_BY_HEADER = 1, 2, 4
+
+# opusgpu_track_seg / opusgpu_track_state / opusgpu_file_info (include/opusgpu.h, WHOLE FILES)
+TRACK_SEG_DTYPE = np.dtype([("slot", "<i4"), ("src_first", "<i4"), ("count", "<i4"), ("track", "<i4"), ("dst_first", "<i8"),
+                            ("packet_seq", "<i4"), ("reserved", "<i4")])
+TRACK_STATE_DTYPE = np.dtype([("first_bad", "<i4"), ("code", "<i4")])
+FILE_INFO_DTYPE = np.dtype([("status", "<i4"), ("channels", "<i4"), ("pre_skip", "<i4"), ("output_gain", "<i4"), ("mapping_family", "<i4"),
+                            ("packets", "<i4"), ("frames", "<i4"), ("holes", "<i4"), ("track_samples", "<i8"), ("track_offset", "<i8")])
+OPUSGPU_BAD_ARG, OPUSGPU_UNIMPLEMENTED, OPUSGPU_CELT_BAD_ARG = -1, -5, -18
+RFC_FRAME = 2880
 
 _lib = None
 
@@ -176,6 +188,20 @@ def load_lib():
     lib.opusgpu_ms_decode_packets.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_int, vp]
     lib.opusgpu_ms_decode_step_device.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
     lib.opusgpu_ms_synchronize.argtypes = [vp]
+    lib.opusgpu_files_plan.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.POINTER(vp)]
+    lib.opusgpu_file_batch_steps.argtypes = [vp]
+    lib.opusgpu_file_batch_step.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int)]
+    lib.opusgpu_file_batch_segments.argtypes = [vp, C.c_int, C.POINTER(vp)]
+    lib.opusgpu_file_batch_arena.argtypes = [vp, C.POINTER(C.c_size_t)]
+    lib.opusgpu_file_batch_arena.restype = vp
+    lib.opusgpu_file_batch_track_samples.argtypes = [vp]
+    lib.opusgpu_file_batch_track_samples.restype = C.c_int64
+    lib.opusgpu_file_batch_packet_start.argtypes = [vp, C.c_int, C.c_int]
+    lib.opusgpu_file_batch_packet_start.restype = C.c_int64
+    lib.opusgpu_file_batch_free.argtypes = [vp]
+    lib.opusgpu_file_batch_free.restype = None
+    lib.opusgpu_tracks_assemble_device.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp]
+    lib.opusgpu_files_decode.argtypes = [vp, vp, vp, vp, vp]
     _lib = lib
     return lib
 
@@ -315,6 +341,65 @@ class PageBatch:
     def close(self):
         if self.h:
             self.lib.opusgpu_page_batch_free(self.h)
+            self.h = None
+            self.arena = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class FileBatch:
+    """Decode steps, packet arena and track segments planned from whole Ogg Opus files by opusgpu_files_plan (host only,
+    include/opusgpu.h WHOLE FILES).  files: a list of bytes-like objects, file i = decoder stream i.  info: one FILE_INFO_DTYPE
+    record per file (status, OpusHead fields, packets, frames, holes, planned track length and offset)."""
+
+    def __init__(self, files, channels=2, rfc=False, flags=0, threads=1):
+        lib = load_lib()
+        self._files = [np.frombuffer(bytes(f) + b"\0", dtype=np.uint8) for f in files]  # (kept alive; + 1: never an empty buffer)
+        n = len(self._files)
+        ptrs = np.array([a.ctypes.data for a in self._files], dtype=np.uint64)
+        lens = np.array([a.size - 1 for a in self._files], dtype=np.int64)
+        self.info = np.zeros(n, dtype=FILE_INFO_DTYPE)
+        h = C.c_void_p()
+        r = lib.opusgpu_files_plan(n, ptrs.ctypes.data, lens.ctypes.data, channels, 1 if rfc else 0, flags, threads, self.info.ctypes.data,
+                                   C.byref(h))
+        if r != 0:
+            e = OpusGpuError(f"opusgpu_files_plan failed: {r}")
+            e.code = r
+            raise e
+        self.lib, self.h = lib, h
+        self.n_files, self.channels, self.rfc = n, channels, bool(rfc)
+        self.row_samples = RFC_FRAME if rfc else FRAME
+        self.n_steps = lib.opusgpu_file_batch_steps(h)
+        self.track_samples = lib.opusgpu_file_batch_track_samples(h)
+        nbytes = C.c_size_t()
+        a = lib.opusgpu_file_batch_arena(h, C.byref(nbytes))
+        self.arena = np.ctypeslib.as_array((C.c_uint8 * nbytes.value).from_address(a)) if nbytes.value else np.zeros(0, np.uint8)
+
+    def step(self, k):
+        """-> (descriptors [DESC_DTYPE], file of every slot [int32], segments [TRACK_SEG_DTYPE], modes); views, valid until close()."""
+        d, sf, sg, modes = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int()
+        n = self.lib.opusgpu_file_batch_step(self.h, k, C.byref(d), C.byref(sf), C.byref(modes))
+        if n < 0:
+            raise IndexError(k)
+        if n == 0:
+            return np.zeros(0, DESC_DTYPE), np.zeros(0, np.int32), np.zeros(0, TRACK_SEG_DTYPE), modes.value
+        self.lib.opusgpu_file_batch_segments(self.h, k, C.byref(sg))
+        descs = np.frombuffer((C.c_uint8 * (16 * n)).from_address(d.value), dtype=DESC_DTYPE)
+        files = np.frombuffer((C.c_uint8 * (4 * n)).from_address(sf.value), dtype=np.int32)
+        segs = np.frombuffer((C.c_uint8 * (32 * n)).from_address(sg.value), dtype=TRACK_SEG_DTYPE)
+        return descs, files, segs, modes.value
+
+    def packet_start(self, file, packet_seq):
+        """Planned start (track-relative sample) of a file's packet; packet_seq == its packet count: the planned length."""
+        return self.lib.opusgpu_file_batch_packet_start(self.h, file, packet_seq)
+
+    def close(self):
+        if self.h:
+            self.lib.opusgpu_file_batch_free(self.h)
             self.h = None
             self.arena = None
 
@@ -481,6 +566,48 @@ class Context:
         cfg = OutputCfg(volume, 1 if force_mono else 0, bits, channels)
         self._chk(self.lib.opusgpu_output_stage_device(self.h, n_blocks, block_samples, d_pcm, pcm_stride, d_valid, valid_all,
                                                        d_cfgs, cfg, d_i2s, i2s_stride, stream), "opusgpu_output_stage_device")
+
+    def tracks_assemble_device(self, n_segs, d_segs, d_pcm, row_samples, d_result, d_tracks, d_track_state, stream=None):
+        """k_tracks_assemble (include/opusgpu.h WHOLE FILES): segments [TRACK_SEG_DTYPE] of a step's PCM rows -> the packed tracks."""
+        self._chk(self.lib.opusgpu_tracks_assemble_device(self.h, n_segs, d_segs, d_pcm, row_samples, d_result, d_tracks, d_track_state,
+                                                          stream), "opusgpu_tracks_assemble_device")
+
+    def decode_files(self, files, rfc=False, flags=PAGES_GROUP_BY_MODE, threads=1, batch=None):
+        """Whole Ogg Opus files -> (list of int16 arrays [samples, channels], one trimmed track per file, info).  The context's
+        streams 0 .. len(files) - 1 are (re)allocated when there are too few and get fresh state; its mode is set to `rfc`.
+        info: FILE_INFO_DTYPE records with two more fields: `final_status` (the first failed frame's code, else the plan's status)
+        and `bad_packet` (that frame's packet, or -1); `track_samples` is the FINAL length.  batch: a FileBatch made beforehand
+        from the same files (its channels and mode must be the context's)."""
+        own = batch is None
+        channels = self.channels or 2
+        if own:
+            batch = FileBatch(files, channels=channels, rfc=rfc, flags=flags, threads=threads)
+        try:
+            n = batch.n_files
+            if self.n_streams < n or self.channels != batch.channels:
+                self.streams_alloc(max(n, 1), batch.channels)
+            self.set_mode(batch.rfc)
+            total = max(int(batch.track_samples), 1) * batch.channels
+            d_tracks = self.dev_alloc(2 * total)
+            try:
+                lengths = np.zeros(n, dtype=np.int64)
+                status = np.zeros((n, 2), dtype=np.int32)
+                self._chk(self.lib.opusgpu_files_decode(self.h, batch.h, d_tracks, lengths.ctypes.data, status.ctypes.data),
+                          "opusgpu_files_decode")
+                packed = np.zeros(total, dtype=np.int16)
+                self.d2h(packed, d_tracks)
+            finally:
+                self.dev_free(d_tracks)
+            packed = packed.reshape(-1, batch.channels)
+            info = np.zeros(n, dtype=np.dtype(FILE_INFO_DTYPE.descr + [("final_status", "<i4"), ("bad_packet", "<i4")]))
+            for name in FILE_INFO_DTYPE.names:
+                info[name] = batch.info[name]
+            info["track_samples"], info["final_status"], info["bad_packet"] = lengths, status[:, 0], status[:, 1]
+            tracks = [packed[o:o + ln] for o, ln in zip(batch.info["track_offset"], lengths)]
+            return tracks, info
+        finally:
+            if own:
+                batch.close()
 
     def decode_step_by_kind(self, n_silk, n_hybrid, n_celt, d_descs, d_arena, d_pcm, d_result, keeps_kind=False, stream=None):
         """One step whose table is grouped by mode (OPUSGPU_PAGES_GROUP_BY_MODE: SILK-only, hybrid, CELT-only frames in that

@@ -1672,3 +1672,4 @@ int opusgpu_decode_packets_fec(opusgpu_ctx *ctx, int n, const int32_t *stream_id
 
 // multistream decoding (include/opusgpu.h, MULTISTREAM): drives the contexts above
 #include "og_ms.hpp"
+#include "og_tracks.hpp"

@@ -151,6 +151,9 @@ struct Packet {
 class OpusFile {
   public:
     OpusFile(read_fn rd, decode_fn dec, void *user) : rd_(rd), dec_(dec), user_(user) {}
+    // A complete file in memory, read in the same OP_READ_SIZE pieces; its end is a clean end of data.  No decode callback: such a
+    // reader is driven through next_planned() / commit() (csrc/og_files.cpp), never through read_stereo().
+    OpusFile(const uint8_t *data, size_t len) : rd_(nullptr), dec_(nullptr), user_(nullptr), mem_(data), mem_len_(len) {}
     const Head &head() const { return head_; }
     bool ready() const { return ready_; }
 
@@ -197,7 +200,7 @@ class OpusFile {
 
     // op_read_stereo opusfile.cpp:1293 (with op_read_native :1171 inlined for _buf_size == 0)
     int read_stereo(int16_t *pcm, int buf_size) {
-        if (!ready_) return OP_EINVAL;
+        if (!ready_ || !dec_) return OP_EINVAL;
         int ret = fill();
         if (ret < 0) return ret;
         int avail = od_size_ - od_pos_;
@@ -213,10 +216,47 @@ class OpusFile {
         return n;
     }
 
+    // What op_read_native decides about the next audio packet BEFORE it decodes it (opusfile.cpp:1207-1260): the packet, the
+    // duration its TOC names, how many of its samples end trimming leaves (`trimmed`) and how many of those the pre-skip -- or the
+    // 80 ms after a hole -- still discards (`skip`): samples [skip, trimmed) of the packet's PCM are the caller's.
+    struct Planned {
+        const Packet *pkt = nullptr; // valid until the next call
+        int duration = 0, skip = 0, trimmed = 0;
+    };
+    // 1: `pl` is the next packet; 0: end of the stream; < 0: what fetch_page reports (OP_HOLE: the caller may go on).
+    int next_planned(Planned &pl) {
+        if (!ready_) return OP_EINVAL;
+        for (;;) {
+            if (op_pos_ < op_.size()) {
+                const Packet &pop = op_[op_pos_++];
+                const int duration = packet_duration(pop.data.data(), (int32_t)pop.data.size());
+                int trimmed = duration;
+                if (pop.e_o_s) { // end trimming (opusfile.cpp:1220-1227)
+                    int64_t diff;
+                    if (gp_cmp(pop.granulepos, prev_packet_gp_) <= 0) trimmed = 0;
+                    else if (gp_diff(&diff, pop.granulepos, prev_packet_gp_) && diff < trimmed) trimmed = (int)diff;
+                }
+                prev_packet_gp_ = pop.granulepos;
+                pl.pkt = &pop;
+                pl.duration = duration;
+                pl.trimmed = trimmed;
+                pl.skip = trimmed < cur_discard_ ? trimmed : cur_discard_;
+                return 1;
+            }
+            int ret = fetch_page();
+            if (ret == OP_EOF) return 0;
+            if (ret < 0) return ret;
+        }
+    }
+    // the packet of the last next_planned() has been decoded: its skipped samples count against the discard
+    void commit(const Planned &pl) { cur_discard_ -= pl.skip; }
+
   private:
     read_fn rd_;
     decode_fn dec_;
     void *user_;
+    const uint8_t *mem_ = nullptr;
+    size_t mem_len_ = 0, mem_pos_ = 0;
     Head head_;
     bool ready_ = false;
     // sync layer
@@ -292,7 +332,14 @@ class OpusFile {
                 const int chunk = 2048; // OP_READ_SIZE
                 size_t old = buf_.size();
                 buf_.resize(old + chunk);
-                int n = rd_ ? rd_(buf_.data() + old, chunk) : -1;
+                int n = -1;
+                if (mem_) {
+                    const size_t left = mem_len_ - mem_pos_;
+                    n = left < (size_t)chunk ? (int)left : chunk;
+                    memcpy(buf_.data() + old, mem_ + mem_pos_, (size_t)n);
+                    mem_pos_ += (size_t)n;
+                } else if (rd_)
+                    n = rd_(buf_.data() + old, chunk);
                 if (n < 0) {
                     buf_.resize(old);
                     return OP_EREAD;
@@ -492,29 +539,16 @@ class OpusFile {
     int fill() {
         for (;;) {
             if (od_size_ - od_pos_ > 0) return 0;
-            if (op_pos_ < op_.size()) {
-                const Packet &pop = op_[op_pos_++];
-                const int nch = head_.channel_count;
-                const int duration = packet_duration(pop.data.data(), (int32_t)pop.data.size());
-                int trimmed = duration;
-                if (pop.e_o_s) { // end trimming (opusfile.cpp:1220-1227)
-                    int64_t diff;
-                    if (gp_cmp(pop.granulepos, prev_packet_gp_) <= 0) trimmed = 0;
-                    else if (gp_diff(&diff, pop.granulepos, prev_packet_gp_) && diff < trimmed) trimmed = (int)diff;
-                }
-                prev_packet_gp_ = pop.granulepos;
-                if (od_.size() < (size_t)nch * 5760) od_.resize((size_t)nch * 5760); // 120 ms at 48 kHz
-                int ret = dec_(user_, pop.data.data(), (int32_t)pop.data.size(), od_.data(), duration);
-                if (ret < 0) return OP_EBADPACKET;
-                int skip = trimmed < cur_discard_ ? trimmed : cur_discard_;
-                cur_discard_ -= skip;
-                od_pos_ = skip;
-                od_size_ = trimmed;
-                continue;
-            }
-            int ret = fetch_page();
-            if (ret == OP_EOF) return 0;
-            if (ret < 0) return ret;
+            Planned pl;
+            int ret = next_planned(pl);
+            if (ret <= 0) return ret;
+            const int nch = head_.channel_count;
+            if (od_.size() < (size_t)nch * 5760) od_.resize((size_t)nch * 5760); // 120 ms at 48 kHz
+            ret = dec_(user_, pl.pkt->data.data(), (int32_t)pl.pkt->data.size(), od_.data(), pl.duration);
+            if (ret < 0) return OP_EBADPACKET;
+            commit(pl);
+            od_pos_ = pl.skip;
+            od_size_ = pl.trimmed;
         }
     }
 };

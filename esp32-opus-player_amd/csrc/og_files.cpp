@@ -1,0 +1,304 @@
+// og_files.cpp -- the file planner (include/opusgpu.h, "WHOLE FILES"): N complete Ogg Opus files -> decode steps, a packet
+// arena and, per step, the segments that place every decoded frame's kept samples in its file's track.  Host only.
+//
+// The container bookkeeping is the single-file reader's own (og_container.hpp): every file is opened and drained through
+// OpusFile::next_planned / commit, which is fill() without the decode.  Three passes: (1) per file, in parallel: run the reader,
+// split every packet into frames, keep the frames' bytes and placements in a per-file plan; (2) sequential and cheap: track
+// offsets, arena offsets, per-step (and per-key) slot numbering in file order; (3) per file, in parallel: copy the bytes into the
+// arena and write descriptors and segments into their slots.
+#include <stdint.h>
+#include <stdlib.h>
+#include <string.h>
+#include <atomic>
+#include <new>
+#include <thread>
+#include <vector>
+#include "og_container.hpp"
+#include "og_packet.hpp"
+#include "../../include/opusgpu.h"
+
+namespace {
+
+struct FramePlan {
+    int32_t offset, len, flags; // offset: into the file's own bytes (FilePlan::bytes)
+    int32_t src_first, count, packet_seq;
+    int64_t dst_rel; // position in the track
+    uint8_t key;     // sort key within a step (0 without grouping)
+    uint8_t kept;    // the file has decoded frames of this frame's mode only, up to and including it
+};
+
+struct FilePlan {
+    std::vector<FramePlan> frames;
+    std::vector<uint8_t> bytes;
+    std::vector<int64_t> packet_start; // packets + 1 entries: the last one is the track length
+};
+
+template <class F>
+void parallel_for(int n, int threads, F f) { // f(begin, end)
+    threads = threads < 1 ? 1 : threads;
+    if (threads > n / 16 + 1) threads = n / 16 + 1;
+    if (threads <= 1) {
+        f(0, n);
+        return;
+    }
+    std::vector<std::thread> th;
+    for (int t = 0; t < threads; t++) {
+        const int b = (int)((int64_t)n * t / threads), e = (int)((int64_t)n * (t + 1) / threads);
+        th.emplace_back([=] { f(b, e); });
+    }
+    for (auto &x : th) x.join();
+}
+
+// One file through the reader.  Returns the status; `fp` holds whatever was planned before a failure.
+int plan_file(const uint8_t *data, size_t len, int channels, int mode, int flags, opusgpu_file_info &fi, FilePlan &fp) {
+    ogc::OpusFile of(data, len);
+    const int r = of.open();
+    const ogc::Head &h = of.head();
+    fi.channels = h.channel_count, fi.pre_skip = (int32_t)h.pre_skip, fi.output_gain = h.output_gain, fi.mapping_family = h.mapping_family;
+    fp.packet_start.assign(1, 0);
+    if (r < 0) return r == ogc::OP_EIMPL ? OPUSGPU_UNIMPLEMENTED : r;
+    if (h.mapping_family != 0) return OPUSGPU_UNIMPLEMENTED;
+    if (h.channel_count != channels) return OPUSGPU_BAD_ARG;
+    const bool rfc = mode == OPUSGPU_MODE_RFC;
+    const bool by_header = (flags & OPUSGPU_PAGES_ORDER_BY_HEADER) != 0;
+    const bool group = by_header || (flags & OPUSGPU_PAGES_GROUP_BY_MODE) != 0;
+    int64_t pos = 0; // samples of the track so far
+    int first_mode = -1;
+    bool kept = true;
+    int status = 0;
+    for (;;) {
+        ogc::OpusFile::Planned pl;
+        const int ret = of.next_planned(pl);
+        if (ret == 0) break;
+        if (ret == ogc::OP_HOLE) {
+            fi.holes++;
+            continue;
+        }
+        if (ret < 0) {
+            status = ret;
+            break;
+        }
+        const std::vector<uint8_t> &pk = pl.pkt->data;
+        int16_t size[48];
+        uint8_t toc;
+        int off = 0;
+        const int count = ogh::parse_packet(pk.data(), (int32_t)pk.size(), 0, &toc, size, &off, nullptr);
+        if (count < 0) { // (the reader's decode callback fails here)
+            status = ogc::OP_EBADPACKET;
+            break;
+        }
+        const int spf = ogh::toc_samples_per_frame(toc, 48000);
+        if (!rfc && spf != OPUSGPU_FRAME_SAMPLES) { // reference mode decodes every frame as 960 samples (Q6): refused, see the header
+            fp = FilePlan();
+            fp.packet_start.assign(1, 0);
+            fi.packets = fi.frames = 0;
+            return OPUSGPU_UNIMPLEMENTED;
+        }
+        const int32_t fl = rfc ? ogh::toc_flags_rfc(toc) : ogh::toc_flags(toc);
+        const int m = fl & 3;
+        if (first_mode < 0) first_mode = m;
+        if (m != first_mode) kept = false;
+        const int32_t base = (int32_t)fp.bytes.size();
+        fp.bytes.insert(fp.bytes.end(), pk.begin(), pk.end());
+        for (int k = 0; k < count; k++) { // the packet's PCM is its frames' back to back; samples [skip, trimmed) are kept
+            const int lo = k * spf, hi = lo + spf;
+            const int a = lo > pl.skip ? lo : pl.skip, b = hi < pl.trimmed ? hi : pl.trimmed;
+            FramePlan f;
+            f.offset = base + off, f.len = size[k], f.flags = fl;
+            f.count = b > a ? b - a : 0;
+            f.src_first = f.count ? a - lo : 0;
+            f.dst_rel = pos + (f.count ? a - pl.skip : 0);
+            f.packet_seq = fi.packets;
+            f.kept = kept;
+            int key = 0;
+            if (by_header) { // og_pages.cpp: SILK 0..3 and hybrid 4..7 by the LBRR flags, CELT 8
+                key = m == 2 ? 8 : 4 * m;
+                if (m != 2 && size[k] > 0) {
+                    const uint8_t b0 = pk[(size_t)off];
+                    key += (int)((b0 >> 6) & 1) | ((fl & 32) ? (int)((b0 >> 4) & 1) << 1 : 0);
+                }
+            } else if (group)
+                key = m;
+            f.key = (uint8_t)key;
+            fp.frames.push_back(f);
+            off += size[k];
+        }
+        of.commit(pl);
+        pos += pl.trimmed > pl.skip ? pl.trimmed - pl.skip : 0;
+        fp.packet_start.push_back(pos);
+        fi.packets++;
+        if (fp.bytes.size() > 0x7fffffffu || fp.frames.size() > 0x3fffffffu) { // (one file: 32-bit offsets)
+            status = OPUSGPU_ALLOC_FAIL;
+            break;
+        }
+    }
+    fi.frames = (int32_t)fp.frames.size();
+    return status;
+}
+
+} // namespace
+
+struct opusgpu_file_batch {
+    int n_files = 0, channels = 0, mode = 0;
+    std::vector<opusgpu_frame_desc> descs; // all steps, step after step
+    std::vector<opusgpu_track_seg> segs;   // parallel to descs
+    std::vector<int32_t> slot_files;       // parallel to descs
+    std::vector<size_t> step_begin;        // n_steps + 1
+    std::vector<int32_t> step_modes;
+    std::vector<uint8_t> arena;
+    std::vector<opusgpu_file_info> info;
+    std::vector<int64_t> packet_start; // all files, file after file
+    std::vector<size_t> packet_begin;  // n_files + 1
+    int64_t track_samples = 0;
+};
+
+extern "C" {
+
+int opusgpu_files_plan(int n_files, const uint8_t *const *files, const int64_t *file_lens, int channels, int mode, int flags,
+                       int threads, opusgpu_file_info *info, opusgpu_file_batch **out) {
+    if (!out) return OPUSGPU_BAD_ARG;
+    *out = nullptr;
+    if (n_files < 0 || (n_files > 0 && (!files || !file_lens)) || (channels != 1 && channels != 2) ||
+        (mode != OPUSGPU_MODE_REFERENCE && mode != OPUSGPU_MODE_RFC) ||
+        (flags & ~(OPUSGPU_PAGES_GROUP_BY_MODE | OPUSGPU_PAGES_ORDER_BY_HEADER)))
+        return OPUSGPU_BAD_ARG;
+    for (int i = 0; i < n_files; i++)
+        if (file_lens[i] < 0 || (file_lens[i] > 0 && !files[i])) return OPUSGPU_BAD_ARG;
+    opusgpu_file_batch *b = nullptr;
+    try {
+        b = new opusgpu_file_batch;
+        b->n_files = n_files, b->channels = channels, b->mode = mode;
+        b->info.assign((size_t)n_files, opusgpu_file_info{});
+        std::vector<FilePlan> plans((size_t)n_files);
+        std::atomic<bool> oom{false};
+        // pass 1: the reader over every file
+        parallel_for(n_files, threads, [&](int lo, int hi) {
+            try {
+                for (int i = lo; i < hi; i++)
+                    b->info[i].status = plan_file(files[i], (size_t)file_lens[i], channels, mode, flags, b->info[i], plans[i]);
+            } catch (const std::bad_alloc &) {
+                oom = true;
+            }
+        });
+        if (oom) throw std::bad_alloc();
+        // pass 2: tracks, arena, steps
+        const bool by_header = (flags & OPUSGPU_PAGES_ORDER_BY_HEADER) != 0;
+        const int G = by_header ? 9 : (flags & OPUSGPU_PAGES_GROUP_BY_MODE) ? 3 : 1;
+        std::vector<size_t> arena_at((size_t)n_files + 1, 0);
+        b->packet_begin.assign((size_t)n_files + 1, 0);
+        size_t n_steps = 0, total = 0;
+        int64_t at = 0;
+        for (int i = 0; i < n_files; i++) {
+            opusgpu_file_info &fi = b->info[i];
+            fi.track_samples = plans[i].packet_start.back();
+            fi.track_offset = at;
+            at = (at + fi.track_samples + 63) / 64 * 64; // every track begins on a 128-byte boundary (mono: 64 samples)
+            arena_at[i + 1] = arena_at[i] + plans[i].bytes.size();
+            b->packet_begin[i + 1] = b->packet_begin[i] + plans[i].packet_start.size();
+            if (plans[i].frames.size() > n_steps) n_steps = plans[i].frames.size();
+            total += plans[i].frames.size();
+        }
+        b->track_samples = at;
+        if (arena_at[n_files] > 0x7fffffffu || total > 0x7fffffffu) { // descriptor offsets and slots are 32-bit: split the call
+            delete b;
+            return OPUSGPU_BAD_ARG;
+        }
+        // a counting sort of the frames by (step, key), stable in file order
+        std::vector<size_t> cur(n_steps * G + 1, 0);
+        for (int i = 0; i < n_files; i++)
+            for (size_t k = 0; k < plans[i].frames.size(); k++) cur[k * G + plans[i].frames[k].key + 1]++;
+        for (size_t j = 1; j < cur.size(); j++) cur[j] += cur[j - 1];
+        b->step_begin.resize(n_steps + 1);
+        for (size_t s = 0; s <= n_steps; s++) b->step_begin[s] = cur[s * G];
+        std::vector<std::vector<uint32_t>> slot_of((size_t)n_files);
+        b->step_modes.assign(n_steps, 0);
+        std::vector<uint8_t> step_broken(n_steps, 0);
+        for (int i = 0; i < n_files; i++) {
+            slot_of[i].resize(plans[i].frames.size());
+            for (size_t k = 0; k < plans[i].frames.size(); k++) {
+                const FramePlan &f = plans[i].frames[k];
+                slot_of[i][k] = (uint32_t)cur[k * G + f.key]++;
+                b->step_modes[k] |= 1 << (f.flags & 3);
+                if (!f.kept) step_broken[k] = 1;
+            }
+        }
+        for (size_t s = 0; s < n_steps; s++)
+            if (!step_broken[s]) b->step_modes[s] |= OPUSGPU_STEP_KEEPS_MODE;
+        // pass 3: bytes, descriptors, segments
+        b->descs.resize(total);
+        b->segs.resize(total);
+        b->slot_files.resize(total);
+        b->arena.assign(arena_at[n_files] + 16, 0); // the kernels fetch packets as aligned 16-byte pieces: keep a tail
+        b->packet_start.resize(b->packet_begin[n_files]);
+        parallel_for(n_files, threads, [&](int lo, int hi) {
+            for (int i = lo; i < hi; i++) {
+                const FilePlan &fp = plans[i];
+                if (!fp.bytes.empty()) memcpy(b->arena.data() + arena_at[i], fp.bytes.data(), fp.bytes.size());
+                memcpy(b->packet_start.data() + b->packet_begin[i], fp.packet_start.data(), fp.packet_start.size() * sizeof(int64_t));
+                for (size_t k = 0; k < fp.frames.size(); k++) {
+                    const FramePlan &f = fp.frames[k];
+                    const size_t slot = slot_of[i][k];
+                    b->descs[slot] = opusgpu_frame_desc{i, (int32_t)(arena_at[i] + (size_t)f.offset), f.len, f.flags};
+                    opusgpu_track_seg &sg = b->segs[slot];
+                    sg.slot = (int32_t)(slot - b->step_begin[k]);
+                    sg.src_first = f.src_first, sg.count = f.count, sg.track = i;
+                    sg.dst_first = b->info[i].track_offset + f.dst_rel;
+                    sg.packet_seq = f.packet_seq, sg.reserved = 0;
+                    b->slot_files[slot] = i;
+                }
+            }
+        });
+        if (info && n_files) memcpy(info, b->info.data(), sizeof(opusgpu_file_info) * (size_t)n_files);
+        *out = b;
+        return OPUSGPU_OK;
+    } catch (const std::bad_alloc &) {
+        delete b;
+        return OPUSGPU_ALLOC_FAIL;
+    }
+}
+
+int opusgpu_file_batch_steps(const opusgpu_file_batch *b) { return b ? (int)b->step_begin.size() - 1 : OPUSGPU_BAD_ARG; }
+
+int opusgpu_file_batch_step(const opusgpu_file_batch *b, int step, const opusgpu_frame_desc **descs, const int32_t **slot_files,
+                            int *modes) {
+    if (!b || step < 0 || step + 1 >= (int)b->step_begin.size()) return OPUSGPU_BAD_ARG;
+    const size_t at = b->step_begin[step];
+    if (descs) *descs = b->descs.data() + at;
+    if (slot_files) *slot_files = b->slot_files.data() + at;
+    if (modes) *modes = b->step_modes[step];
+    return (int)(b->step_begin[step + 1] - at);
+}
+
+int opusgpu_file_batch_segments(const opusgpu_file_batch *b, int step, const opusgpu_track_seg **segs) {
+    if (!b || step < 0 || step + 1 >= (int)b->step_begin.size()) return OPUSGPU_BAD_ARG;
+    const size_t at = b->step_begin[step];
+    if (segs) *segs = b->segs.data() + at;
+    return (int)(b->step_begin[step + 1] - at);
+}
+
+const uint8_t *opusgpu_file_batch_arena(const opusgpu_file_batch *b, size_t *bytes) {
+    if (!b) return nullptr;
+    if (bytes) *bytes = b->arena.size();
+    return b->arena.data();
+}
+
+int64_t opusgpu_file_batch_track_samples(const opusgpu_file_batch *b) { return b ? b->track_samples : -1; }
+
+int64_t opusgpu_file_batch_packet_start(const opusgpu_file_batch *b, int file, int packet_seq) {
+    if (!b || file < 0 || file >= b->n_files || packet_seq < 0) return -1;
+    const size_t lo = b->packet_begin[file], hi = b->packet_begin[file + 1];
+    if ((size_t)packet_seq >= hi - lo) return -1;
+    return b->packet_start[lo + (size_t)packet_seq];
+}
+
+void opusgpu_file_batch_free(opusgpu_file_batch *b) { delete b; }
+
+// (for opusgpu_files_decode, which lives with the kernels: csrc/og_tracks.hpp)
+int og_file_batch_shape(const opusgpu_file_batch *b, int *n_files, int *channels, int *mode) {
+    if (!b) return OPUSGPU_BAD_ARG;
+    *n_files = b->n_files, *channels = b->channels, *mode = b->mode;
+    return OPUSGPU_OK;
+}
+const opusgpu_file_info *og_file_batch_info(const opusgpu_file_batch *b) { return b ? b->info.data() : nullptr; }
+
+} // extern "C"

@@ -483,6 +483,109 @@ int opusgpu_ms_decode_step_device(opusgpu_ms *ms, int n, const void *d_descs, co
 /* The host waits for everything the object has queued. */
 int opusgpu_ms_synchronize(opusgpu_ms *ms);
 
+/* ---- WHOLE FILES: N Ogg Opus files in, N trimmed PCM tracks in HBM out ------------------------------------------------------
+ * The page path above ends at per-step PCM blocks and leaves pre-skip, end trimming, holes and spanning packets to the caller; the
+ * file surface (include/opusfile.h) handles all of those, one stream per process.  This section joins the two: a host planner
+ * that runs the single-file reader's own bookkeeping (csrc/og_container.hpp: op_find_initial_pcm_offset, op_fetch_and_process_page
+ * and the deciding half of op_read_native, src/opusfile.cpp:486-632, :835-1133, :1207-1260) over every file without decoding, and
+ * a kernel that copies every decoded frame's kept samples to their place in the file's track.
+ * File i is decoder stream i.  The k-th frame of a file goes in step k (a stream at most once per step); step tables and arena
+ * are in the device layout of the page batch (16-byte arena tail; OPUSGPU_PAGES_GROUP_BY_MODE / _ORDER_BY_HEADER order a step's
+ * table the same way).  In RFC mode the descriptors carry duration and RFC bit as opusgpu_packet_to_frames_mode makes them.
+ * On OP_HOLE (-3) the planner does what a caller does who notes it and reads on (holes are counted); any other negative reader
+ * code ends the file's plan there and is reported in status -- what was planned before it is decoded.  Chained links are not
+ * followed (the reader stops at a new link).  The OpusHead output gain is reported, not applied (the reference does not apply it).
+ * Refusals, per file, never a failed call (a refused file contributes no frame and a track of 0 samples):
+ *   OpusHead channel count != `channels`  -> OPUSGPU_BAD_ARG (a mono file on a stereo context is not the same decoder, Q3);
+ *   mapping family != 0                   -> OPUSGPU_UNIMPLEMENTED;
+ *   reference mode, an audio packet whose TOC names another frame duration than 20 ms -> OPUSGPU_UNIMPLEMENTED.  What the
+ *     single-file reader makes of such a packet: the decoder writes 960 samples per frame whatever the TOC says (Q6) and the reader
+ *     hands out the TOC's duration from its scratch buffer -- the head of a frame decoded at the wrong length (2.5 / 5 / 10 ms), or
+ *     960 fresh samples followed by whatever an earlier packet left there (40 / 60 ms).  Nobody wants that: such files are RFC mode's.
+ *   A packet with a valid duration that fails the frame split ends the plan with OP_EBADPACKET (-136), where the reader's decode
+ *   callback would have failed.
+ * SEGMENTS.  One per descriptor of a step, in slot order (32 bytes, little-endian, this layout is part of the ABI):
+ *   "copy `count` samples per channel of PCM row `slot` of this step, starting at sample `src_first` of the row, to sample
+ *   `dst_first` of the packed track buffer" -- dst_first counts samples per channel from the start of the buffer, i.e. the track's
+ *   offset (opusgpu_file_info.track_offset) plus the position in the track.  A frame cut by pre-skip or end trimming has a
+ *   shortened segment; a frame that is skipped or trimmed entirely keeps a segment of count 0, which copies nothing: its result
+ *   code still counts (the reader decodes such packets too and fails on them).
+ * FAILED FRAMES.  A segment whose frame's result is negative writes nothing and lowers first_bad of its track's state record to
+ * its packet_seq (atomic minimum), recording the code; a segment whose packet_seq is >= its track's first_bad writes nothing.  A
+ * track's final length is the planned start of packet first_bad -- where the single-file reader would have returned
+ * OP_EBADPACKET.  Samples at or past the final length are unspecified (earlier frames of the failing packet may have landed
+ * there).  Later frames of such a stream are still decoded; only their output is dropped. */
+typedef struct opusgpu_track_seg { /* 32 bytes */
+    int32_t slot;       /* PCM row (and result entry) of the step */
+    int32_t src_first;  /* first sample per channel taken from the row */
+    int32_t count;      /* samples per channel; 0: nothing to copy */
+    int32_t track;      /* file index = state record */
+    int64_t dst_first;  /* sample per channel in the packed track buffer */
+    int32_t packet_seq; /* index of the audio packet in its file, 0-based, counted over the packets the reader hands to the decoder */
+    int32_t reserved;   /* 0 */
+} opusgpu_track_seg;
+typedef struct opusgpu_track_state { /* 8 bytes, one per track; before the first step: { INT32_MAX, 0 } */
+    int32_t first_bad; /* lowest packet_seq with a failed frame */
+    int32_t code;      /* that frame's result */
+} opusgpu_track_state;
+typedef struct opusgpu_file_info { /* 48 bytes */
+    int32_t status;         /* 0, a refusal (above), or the reader's code: e.g. -132 OP_ENOTFORMAT, -133 OP_EBADHEADER, -136 OP_EBADPACKET, -139 OP_EBADTIMESTAMP */
+    int32_t channels;       /* OpusHead: channel count, pre-skip, output gain (Q7.8 dB), mapping family; 0 when no header was found */
+    int32_t pre_skip;
+    int32_t output_gain;
+    int32_t mapping_family;
+    int32_t packets;        /* audio packets planned */
+    int32_t frames;         /* frames planned = steps the file takes part in */
+    int32_t holes;
+    int64_t track_samples;  /* planned track length, samples per channel */
+    int64_t track_offset;   /* where the track begins in the packed buffer, samples per channel; a multiple of 64: every track
+                               begins on a 128-byte boundary */
+} opusgpu_file_info;
+typedef struct opusgpu_file_batch opusgpu_file_batch;
+
+/* files[i]: file_lens[i] bytes, a complete Ogg Opus file in memory.  channels 1 or 2; mode OPUSGPU_MODE_REFERENCE or _RFC; flags
+ * OPUSGPU_PAGES_GROUP_BY_MODE / OPUSGPU_PAGES_ORDER_BY_HEADER or 0; threads <= 0: one.  info (n_files entries) may be NULL.
+ * Returns OPUSGPU_OK, OPUSGPU_BAD_ARG or OPUSGPU_ALLOC_FAIL.  Host only: no GPU involved. */
+int opusgpu_files_plan(int n_files, const uint8_t *const *files, const int64_t *file_lens, int channels, int mode, int flags,
+                       int threads, opusgpu_file_info *info, opusgpu_file_batch **out);
+int opusgpu_file_batch_steps(const opusgpu_file_batch *b);
+/* Step `step`: returns its descriptor count; *descs its table, *slot_files (may be NULL) the file of every slot, *modes (may be
+ * NULL) what the step may be declared as: OPUSGPU_HAS_* of the modes that occur, plus OPUSGPU_STEP_KEEPS_MODE when no file with
+ * a frame in the step has changed its mode up to and including that frame. */
+int opusgpu_file_batch_step(const opusgpu_file_batch *b, int step, const opusgpu_frame_desc **descs, const int32_t **slot_files,
+                            int *modes);
+/* The step's segment list (one per descriptor, slot order); returns the count. */
+int opusgpu_file_batch_segments(const opusgpu_file_batch *b, int step, const opusgpu_track_seg **segs);
+const uint8_t *opusgpu_file_batch_arena(const opusgpu_file_batch *b, size_t *bytes);
+/* Samples per channel of the packed track buffer (the last track's offset + length, rounded up to 64): allocate 2 * channels
+ * bytes for each. */
+int64_t opusgpu_file_batch_track_samples(const opusgpu_file_batch *b);
+/* The planned start (sample per channel, track-relative) of packet `packet_seq` of file `file`; packet_seq == the file's packet
+ * count gives the planned track length.  -1 for bad arguments. */
+int64_t opusgpu_file_batch_packet_start(const opusgpu_file_batch *b, int file, int packet_seq);
+void opusgpu_file_batch_free(opusgpu_file_batch *b);
+
+/* k_tracks_assemble: applies n_segs segments (device array of opusgpu_track_seg) to d_pcm [rows][row_samples * channels] int16
+ * (16-byte aligned; row_samples 960, or OPUSGPU_RFC_FRAME_SAMPLES in RFC mode) with the step's results d_result, into the packed
+ * track buffer d_tracks (128-byte aligned) with the state records d_track_state.  The caller guarantees that every segment lies
+ * inside its row (0 <= src_first, src_first + count <= row_samples) and inside the track buffer, and that segments of one call
+ * do not overlap in the buffer.  Asynchronous on the context's stream (or `hip_stream`): queued behind a decode step on the same
+ * stream it needs no other ordering. */
+int opusgpu_tracks_assemble_device(opusgpu_ctx *ctx, int n_segs, const void *d_segs, const void *d_pcm, int row_samples,
+                                   const void *d_result, void *d_tracks, void *d_track_state, void *hip_stream);
+/* Everything at once: uploads the batch, gives streams 0 .. n_files - 1 of the context fresh state, runs the steps with the
+ * assembly behind each on the context's stream and waits.  The context must have at least n_files streams of the batch's channel
+ * count and be in the batch's mode (OPUSGPU_BAD_ARG otherwise).  With opusgpu_set_pipeline on, every step is declared with the
+ * modes the planner found (see opusgpu_file_batch_step), so steps run ahead of each other exactly as declared steps do; otherwise
+ * they run in order.  The assembly adds no drain: it is queued on the steps' stream, and every kernel of step k + 1 that writes
+ * PCM or result codes runs on that stream (or one forked from it) -- ONE step PCM buffer is all the pipeline depth needs, since only
+ * parse and reconstruction kernels, which never touch it, run ahead.
+ * d_tracks: opusgpu_file_batch_track_samples x channels int16 in HBM, 128-byte aligned.  track_lengths_out[i] (may be NULL): the
+ * final length of track i in samples per channel.  status_out (may be NULL) gets two entries per file: [2 * i] = the first
+ * failed frame's code (e.g. OPUSGPU_CELT_BAD_ARG), else the plan's status; [2 * i + 1] = the failing packet's packet_seq, or -1. */
+int opusgpu_files_decode(opusgpu_ctx *ctx, const opusgpu_file_batch *batch, void *d_tracks, int64_t *track_lengths_out,
+                         int32_t *status_out);
+
 #ifdef __cplusplus
 }
 #endif

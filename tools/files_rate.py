@@ -1,0 +1,131 @@
+#!/usr/bin/env python3
+"""Whole-file path rate (include/opusgpu.h, WHOLE FILES): N stereo files of one page of 10 CELT-FB packets of 160 bytes, random
+pre-skips and end trims, planned once and decoded device-resident.  Per batch of 10 steps, mean and spread over --reps repeats:
+(a) the steps alone (the path without this feature), (b) the steps with k_tracks_assemble behind each on the same stream,
+(d) a device-to-device hipMemcpyAsync of the bytes the assembly moves, in the same process -- in order and with pipelined steps.
+(c), the kernel's own time, comes from a kernel trace: run this script under `rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o files --`
+and then `python3 tools/files_rate.py --stats DIR` reads DIR's kernel_stats.csv (bytes read + written per launch: 2 x the step's
+kept samples x 4).  Also: the planner's files/s on --threads threads next to opusgpu_pages_demux's pages/s on the same pages.
+usage (GPU box): python3 tools/files_rate.py [--n N] [--reps R] | python3 tools/files_rate.py --stats DIR [--n N]"""
+import argparse
+import ctypes as C
+import glob
+import importlib.util
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+here = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.join(here, "..", "tests"))
+ap = argparse.ArgumentParser()
+ap.add_argument("--n", type=int, default=65536)
+ap.add_argument("--reps", type=int, default=10)
+ap.add_argument("--threads", type=int, default=16)
+ap.add_argument("--stats", default=None)
+args = ap.parse_args()
+n = args.n
+
+spec = importlib.util.spec_from_file_location("esp32_opus_player_amd", os.path.join(here, "..", "esp32-opus-player_amd", "__init__.py"))
+pkg = importlib.util.module_from_spec(spec)
+spec.loader.exec_module(pkg)
+import files_util as fu  # noqa: E402
+
+files, pre, trim = fu.bulk_files(pkg, n, pkg.TOC_CELT_FB_STEREO, 160, pages=1, per_page=10)
+kept = int((9600 - pre - trim).sum())          # samples per channel of all tracks
+MOVED = 2 * kept * 4                           # bytes the assembly reads + writes per batch
+
+if args.stats:
+    import csv
+    rows = []
+    for f in glob.glob(os.path.join(args.stats, "**", "*kernel_stats.csv"), recursive=True):
+        rows += [r for r in csv.DictReader(open(f)) if "k_tracks_assemble" in r["Name"]]
+    assert rows, "no k_tracks_assemble in the kernel statistics"
+    r = rows[0]
+    avg_ms = float(r["AverageNs"]) / 1e6
+    print(json.dumps({"kernel": "k_tracks_assemble", "calls": int(r["Calls"]), "avg_ms_per_launch": round(avg_ms, 4),
+                      "min_ms": round(float(r["MinNs"]) / 1e6, 4), "ms_per_batch_of_10": round(avg_ms * 10, 3),
+                      "bytes_per_batch": MOVED, "tb_per_s": round(MOVED / 10 / (avg_ms / 1e3) / 1e12, 2)}))
+    raise SystemExit(0)
+
+# ---- planner and page demux rates ----------------------------------------------------------------------
+blobs = [r.tobytes() for r in files]
+t0 = time.perf_counter()
+b = pkg.FileBatch(blobs, channels=2, flags=pkg.PAGES_GROUP_BY_MODE, threads=args.threads)
+plan_s = time.perf_counter() - t0
+assert (b.info["status"] == 0).all() and b.n_steps == 10
+hdr = files.shape[1] - (27 + 10 + 10 * 161)  # the audio page is the file's tail
+pages = np.ascontiguousarray(files[:, hdr:])
+t0 = time.perf_counter()
+pb = pkg.PageBatch(pages.reshape(-1), np.arange(n, dtype=np.int64) * pages.shape[1], np.full(n, pages.shape[1], np.int32), np.arange(n),
+                   threads=args.threads)
+demux_s = time.perf_counter() - t0
+pb.close()
+
+# ---- device-resident steps -------------------------------------------------------------------------------
+ctx = pkg.Context(0)
+ctx.streams_alloc(n, 2)
+steps = [b.step(k) for k in range(10)]
+descs = np.concatenate([s[0] for s in steps])
+segs = np.concatenate([s[2] for s in steps])
+d_descs, d_segs, d_arena = ctx.dev_alloc(descs.nbytes), ctx.dev_alloc(segs.nbytes), ctx.dev_alloc(b.arena.nbytes)
+d_pcm, d_res = ctx.dev_alloc(n * 960 * 4), ctx.dev_alloc(4 * n)
+d_tracks, d_copy = ctx.dev_alloc(int(b.track_samples) * 4), ctx.dev_alloc(int(b.track_samples) * 4)
+state = np.zeros(n, dtype=pkg.TRACK_STATE_DTYPE)
+state["first_bad"] = 2**31 - 1
+d_state = ctx.dev_alloc(state.nbytes)
+for d, a in ((d_descs, descs), (d_segs, segs), (d_arena, b.arena), (d_state, state)):
+    ctx.h2d(d, a)
+hip = C.CDLL("libamdhip64.so")
+hip.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+hip.hipDeviceSynchronize.argtypes = []
+
+
+def batch(assemble):
+    at = 0
+    for k in range(10):
+        m = len(steps[k][0])
+        ctx.decode_step_device(m, C.c_void_p(d_descs.value + 16 * at), d_arena, d_pcm, d_res, modes=steps[k][3])
+        if assemble:
+            ctx.tracks_assemble_device(m, C.c_void_p(d_segs.value + 32 * at), d_pcm, 960, d_res, d_tracks, d_state)
+        at += m
+
+
+def timed(fn, sync):
+    fn()
+    sync()
+    out = []
+    for _ in range(args.reps):
+        t0 = time.perf_counter()
+        fn()
+        sync()
+        out.append((time.perf_counter() - t0) * 1e3)
+    return out
+
+
+def copy():
+    assert hip.hipMemcpyAsync(d_copy, d_tracks, MOVED // 2, 3, None) == 0  # hipMemcpyDeviceToDevice: reads and writes MOVED / 2 each
+
+
+out = {"files": n, "bytes_moved_per_batch": MOVED, "plan_files_per_s": round(n / plan_s), "plan_threads": args.threads,
+       "demux_pages_per_s": round(n / demux_s)}
+for name, pipe in (("in_order", 0), ("pipelined", 1)):
+    ctx.set_pipeline(pipe)
+    a, w = [], []
+    for _ in range(3):  # (a) and (b) interleaved, three rounds each: drift shows up as spread, not as a difference
+        a += timed(lambda: batch(False), ctx.synchronize)
+        w += timed(lambda: batch(True), ctx.synchronize)
+    out[name] = {"a_steps_ms": round(float(np.mean(a)), 3), "a_min_max_ms": [round(min(a), 3), round(max(a), 3)], "a_std_ms": round(float(np.std(a)), 3),
+                 "b_steps_assembly_ms": round(float(np.mean(w)), 3), "b_min_max_ms": [round(min(w), 3), round(max(w), 3)],
+                 "b_minus_a_ms": round(float(np.mean(w) - np.mean(a)), 3)}
+ctx.set_pipeline(0)
+c = timed(copy, hip.hipDeviceSynchronize)
+out["d_memcpy_d2d_ms"] = round(float(np.mean(c)), 3)
+out["d_memcpy_tb_per_s"] = round(MOVED / (float(np.mean(c)) / 1e3) / 1e12, 2)
+got = np.zeros(n, dtype=pkg.TRACK_STATE_DTYPE)
+ctx.d2h(got, d_state)
+assert (got["first_bad"] == 2**31 - 1).all()
+print(json.dumps(out))
+ctx.close()
