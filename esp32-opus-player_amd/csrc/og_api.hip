@@ -9,9 +9,6 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <sched.h>
-#include <atomic>
-#include <chrono>
 #include <condition_variable>
 #include <functional>
 #include <memory>
@@ -20,7 +17,7 @@
 #include <thread>
 #include <vector>
 #include "og_decode.hpp"
-#include "og_packet.hpp"
+#include "og_host_framing.hpp"
 #include "og_output.hpp"
 #include "og_debug.hpp"
 
@@ -687,20 +684,6 @@ void launch_silk_synth_nb(opusgpu_ctx *ctx, hipStream_t q, const Step &st, size_
 }
 
 
-// OPUSGPU_HOST_TIMING=1: wall time of the phases of opusgpu_decode_packets on stderr (adds a stream synchronise after the
-// kernels so that decode and copy-back can be told apart; for tuning only)
-struct HostPhaseTimer {
-    bool on, light; // on: OPUSGPU_HOST_TIMING=1, the one-batch flow with a wait after the kernels; light (=2): the flow as it is
-    std::chrono::steady_clock::time_point t;
-    HostPhaseTimer() : on(og_debug().host_timing == 1), light(og_debug().host_timing == 2), t(std::chrono::steady_clock::now()) {}
-    void mark(const char *what) {
-        if (!on && !light) return;
-        const auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "[opusgpu_decode_packets] %-34s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t).count());
-        t = now;
-    }
-};
-
 extern "C" {
 
 
@@ -1180,40 +1163,16 @@ int opusgpu_packet_to_frames(const uint8_t *packet, int32_t len, int32_t stream,
 int opusgpu_packet_to_frames_mode(const uint8_t *packet, int32_t len, int32_t stream, int mode, opusgpu_frame_desc descs[48]) {
     if (!packet || !descs) return OPUSGPU_BAD_ARG;
     if (len <= 0) return len == 0 ? OPUSGPU_INVALID_PACKET : OPUSGPU_BAD_ARG;
-    int16_t size[48];
-    uint8_t toc;
-    int offset = 0;
-    const int count = ogh::parse_packet(packet, len, 0, &toc, size, &offset, nullptr);
-    if (count < 0) return count;
-    const int32_t flags = mode == OPUSGPU_MODE_RFC ? ogh::toc_flags_rfc(toc) : ogh::toc_flags(toc);
-    for (int i = 0; i < count; i++) {
-        descs[i].stream = stream;
-        descs[i].offset = offset;
-        descs[i].len = size[i];
-        descs[i].flags = flags;
-        offset += size[i];
-    }
-    return count;
+    return ogh::packet_to_frames_mode(packet, len, stream, mode, descs);
 }
 
 int opusgpu_empty_packet_to_frames(int32_t stream, int32_t last_flags, int decoder_channels, int frame_size, opusgpu_frame_desc descs[48]) {
     if (!descs || frame_size <= 0 || frame_size % 120 || (decoder_channels != 1 && decoder_channels != 2)) return OPUSGPU_BAD_ARG;
     const int count = (frame_size + OPUSGPU_FRAME_SAMPLES - 1) / OPUSGPU_FRAME_SAMPLES;
     if (count > 48) return OPUSGPU_BAD_ARG;
-    const int32_t flags = last_flags >= 0 ? (last_flags & 63) : ogh::empty_flags_no_packet_yet(decoder_channels);
+    const int32_t flags = ogh::empty_flags(last_flags, decoder_channels);
     for (int i = 0; i < count; i++) descs[i] = opusgpu_frame_desc{stream, 0, 0, flags};
     return count;
-}
-
-static int grow_pinned(opusgpu_ctx *ctx, void **p, size_t *cap, size_t need) {
-    if (*cap >= need) return OPUSGPU_OK;
-    if (*p) HIPCHK(ctx, hipHostFree(*p));
-    *p = nullptr;
-    *cap = 0;
-    const size_t want = need + need / 4;
-    if (hipHostMalloc(p, want, hipHostMallocDefault) != hipSuccess) return OPUSGPU_ALLOC_FAIL;
-    *cap = want;
-    return OPUSGPU_OK;
 }
 
 static int grow(opusgpu_ctx *ctx, void **p, size_t *cap, size_t need) {
@@ -1228,447 +1187,10 @@ static int grow(opusgpu_ctx *ctx, void **p, size_t *cap, size_t need) {
     return OPUSGPU_OK;
 }
 
-// How a concealment of `total` samples is cut into device frames (valid duration codes): a frame of the last packet's size at a
-// time like opus_decode(NULL) (src/opus_decoder.cpp:294-308 has the loop), what is left over (30 / 50 ms) as 20 / 40 ms + 10 ms.
-static int conceal_pieces(int total, int last_fs, int32_t base_flags, int32_t out_flags[48]) {
-    static const int kDur[6] = {2880, 1920, 960, 480, 240, 120}, kCode[6] = {5, 4, 0, 3, 2, 1};
-    int n = 0;
-    while (total > 0) {
-        int w = total < last_fs ? total : last_fs;
-        total -= w;
-        while (w > 0) {
-            int j = 0;
-            while (kDur[j] > w) j++;
-            if (n == 48) return -1;
-            out_flags[n++] = (base_flags & ~(7 << 6) & ~(1 << 10)) | kCode[j] << 6 | 1 << 9;
-            w -= kDur[j];
-        }
-    }
-    return n;
-}
-
-// CPUs this process may run on (its affinity mask: a container's share, not the machine's), at most `most`.
-static int host_cpus(int most) {
-    cpu_set_t set;
-    int c = 8;
-    if (sched_getaffinity(0, sizeof set, &set) == 0) c = CPU_COUNT(&set);
-    return c < 1 ? 1 : (c > most ? most : c);
-}
-
-// Is [p, p + bytes) page-locked host memory the device can write?  ONE page-locked range must cover all of it: either one the
-// caller registered through opusgpu_host_register (the context keeps the list), or one allocation / registration the runtime knows
-// (its start and size are asked for: two ends that are each page-locked may have pageable memory between them).
-static bool host_range_is_pinned(opusgpu_ctx *ctx, const void *p, size_t bytes) {
-    if (!p || !bytes) return false;
-    const uintptr_t lo = (uintptr_t)p, hi = lo + bytes;
-    {
-        std::lock_guard<std::mutex> lock(ctx->registered_mutex);
-        for (const auto &r : ctx->registered)
-            if (lo >= r.first && hi <= r.first + r.second) return true;
-    }
-    hipPointerAttribute_t a{};
-    if (hipPointerGetAttributes(&a, p) != hipSuccess || a.type != hipMemoryTypeHost) {
-        (void)hipGetLastError(); // (pageable memory is reported as an error: not one of ours)
-        return false;
-    }
-    void *start = nullptr;
-    size_t size = 0;
-    if (hipPointerGetAttribute(&start, HIP_POINTER_ATTRIBUTE_RANGE_START_ADDR, (hipDeviceptr_t)p) != hipSuccess ||
-        hipPointerGetAttribute(&size, HIP_POINTER_ATTRIBUTE_RANGE_SIZE, (hipDeviceptr_t)p) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return lo >= (uintptr_t)start && hi <= (uintptr_t)start + size;
-}
-
-static int decode_packets_impl(opusgpu_ctx *ctx, int n, const int32_t *stream_ids, const uint8_t *const *packets,
-                               const int32_t *lens, int16_t *pcm, int frame_capacity, int32_t *result, const bool fec) {
-    if (!ctx || n < 0 || !ctx->d_streams) return OPUSGPU_BAD_ARG;
-    if (n == 0) return OPUSGPU_OK;
-    if (!stream_ids || !packets || !lens || !pcm || !result || frame_capacity <= 0) return OPUSGPU_BAD_ARG;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (ctx->pipeline) // (pipelined device-resident steps may still be in flight on the library's streams, which the parts below use)
-        if (int rc0 = sync_in_flight(ctx)) return rc0;
-    const int CC = ctx->channels;
-    const bool rfc = ctx->mode == OPUSGPU_MODE_RFC;
-    if (fec && !rfc) return OPUSGPU_BAD_ARG;
-    // one frame's block in the device PCM buffer: 20 ms, or room for a 60 ms frame in RFC mode
-    const size_t frame_pcm = (size_t)(rfc ? OPUSGPU_RFC_FRAME_SAMPLES : OPUSGPU_FRAME_SAMPLES) * CC;
-    const size_t cap_pcm = (size_t)frame_capacity * OPUSGPU_FRAME_SAMPLES * CC; // the caller's block per packet
-    // 1. frame the packets on the host (opus_decode_native, src/opus_decoder.cpp:280-348).  Large batches by ranges of
-    //    packets on a few threads, in two passes: frame counts and sizes, then (after the prefix sums that place every
-    //    packet) descriptors and packet bytes.
-    HostPhaseTimer timer;
-    const int host_threads = n >= 4096 ? host_cpus(16) : 1;
-    auto on_subranges = [&](int from, int to, auto &&f) { // f(lo, hi) over [from, to), on the host threads
-        if (host_threads == 1 || to - from < 1024) {
-            f(from, to);
-            return;
-        }
-        const int64_t w = to - from;
-        ctx->pool.run(host_threads, [&](int t) { f(from + (int)(w * t / host_threads), from + (int)(w * (t + 1) / host_threads)); });
-    };
-    auto on_ranges = [&](auto &&f) { on_subranges(0, n, f); };
-    std::vector<int> first(n + 1, 0), nframes(n, 0);
-    std::vector<uint8_t> is_lost(n, 0);
-    // The common large call is REGULAR: every packet holds one frame (frame-count code 0) of a stream that exists, of a size and
-    // duration the call has room for.  One look at the TOC bytes settles that, and then nothing of the first framing pass is
-    // needed: packet i is frame i of the one step, its bytes lie at the running sum of the lengths, and the (only) framing pass
-    // runs part by part next to the device (0.63 + 0.17 ms of host work less in front of the first kernel at 65,536 packets).
-    bool regular = !rfc && !fec && n >= 4096 && ctx->host_parts > 1 && !timer.on;
-    if (regular) {
-        std::atomic<int> irregular{0};
-        on_ranges([&](int lo, int hi) {
-            for (int i = lo; i < hi; i++) {
-                const uint8_t *p = packets[i];
-                if (stream_ids[i] < 0 || stream_ids[i] >= ctx->n_streams || !p || lens[i] < 1 || lens[i] > 1276 || (p[0] & 3) != 0 ||
-                    ogh::toc_samples_per_frame(p[0], 48000) > frame_capacity * OPUSGPU_FRAME_SAMPLES) {
-                    irregular.store(1, std::memory_order_relaxed);
-                    return;
-                }
-                result[i] = 0;
-                nframes[i] = 1;
-                ctx->last_count[stream_ids[i]] = 1; // (what an empty packet of this stream will be decoded as: below)
-                ctx->last_flags[stream_ids[i]] = ogh::toc_flags(p[0]);
-            }
-        });
-        regular = irregular.load() == 0;
-        if (!regular) std::fill(nframes.begin(), nframes.end(), 0);
-    }
-    if (!regular) on_ranges([&](int lo, int hi) {
-        for (int i = lo; i < hi; i++) {
-            result[i] = 0;
-            if (stream_ids[i] < 0 || stream_ids[i] >= ctx->n_streams || lens[i] < 0) {
-                result[i] = OPUSGPU_BAD_ARG;
-                continue;
-            }
-            if (!packets[i] || lens[i] == 0) {
-                if (!rfc) {
-                    // The reference has no concealment, but opus_decode_native's empty-packet branch is live (src/opus_decoder.cpp:
-                    // 290-308): opus_decode_frame(st, NULL, 0) -- a frame of no bytes in the stream's LAST mode / bandwidth / channel
-                    // count, 960 samples per pass -- until frame_size (here frame_capacity x 960, a multiple of 120) is filled or a
-                    // pass fails: SILK-only decodes (the coder reads zeros), hybrid runs its SILK half and ends in CELT's -18
-                    // (src/celt.cpp:2225), CELT-only in -18; a stream without a packet since its reset is in mode 0 (descriptor bit 11)
-                    nframes[i] = frame_capacity;
-                    is_lost[i] = 1;
-                    continue;
-                }
-                // RFC mode: a lost packet is concealed as long as the stream's last packet was (one 20 ms frame if there was none)
-                const int count = ctx->last_count[stream_ids[i]] ? ctx->last_count[stream_ids[i]] : 1;
-                const int fs = ogh::flags_frame_size(ctx->last_flags[stream_ids[i]]);
-                if ((int64_t)count * fs > (int64_t)frame_capacity * OPUSGPU_FRAME_SAMPLES) {
-                    result[i] = OPUSGPU_BUFFER_TOO_SMALL;
-                    continue;
-                }
-                nframes[i] = count;
-                is_lost[i] = 1;
-                continue;
-            }
-            opusgpu_frame_desc d[48];
-            const int count = opusgpu_packet_to_frames_mode(packets[i], lens[i], stream_ids[i], ctx->mode, d);
-            if (count < 0) {
-                result[i] = count;
-                continue;
-            }
-            if (fec) { // the packet BEFORE this one was lost (opus_decode with decode_fec = 1): its duration is concealed, the last
-                       // frame's worth of it from this packet's first frame where SILK data is there to carry LBRR frames
-                const int sid = stream_ids[i], lc = ctx->last_count[sid];
-                const int last_fs = lc ? ogh::flags_frame_size(ctx->last_flags[sid]) : 120;
-                const int lost_dur = lc ? lc * last_fs : OPUSGPU_FRAME_SAMPLES;
-                const int pfs = ogh::toc_samples_per_frame(packets[i][0], 48000);
-                const bool celt = (d[0].flags & 3) == 2 || (lc && (ctx->last_flags[sid] & 3) == 2);
-                if (lost_dur > frame_capacity * OPUSGPU_FRAME_SAMPLES) {
-                    result[i] = OPUSGPU_BUFFER_TOO_SMALL;
-                    continue;
-                }
-                int32_t fl[48];
-                const bool use = !(lost_dur < pfs || celt);
-                const int np = conceal_pieces(use ? lost_dur - pfs : lost_dur, last_fs, lc ? ctx->last_flags[sid] : d[0].flags, fl);
-                if (np < 0 || np + (use ? 1 : 0) > 48) {
-                    result[i] = OPUSGPU_BAD_ARG;
-                    continue;
-                }
-                nframes[i] = np + (use ? 1 : 0);
-                is_lost[i] = use ? 2 : 3; // 2: concealment + the FEC frame, 3: concealment only
-                continue;
-            }
-            // count * packet_frame_size > frame_size -> OPUS_BUFFER_TOO_SMALL (src/opus_decoder.cpp:323)
-            const int pfs = ogh::toc_samples_per_frame(packets[i][0], 48000);
-            // (RFC mode decodes the durations the check is about: no second condition)
-            if ((int64_t)count * pfs > (int64_t)frame_capacity * OPUSGPU_FRAME_SAMPLES || (!rfc && count > frame_capacity)) {
-                result[i] = OPUSGPU_BUFFER_TOO_SMALL;
-                continue;
-            }
-            nframes[i] = count;
-            // what a later empty packet of the stream decodes / conceals as: st->mode, bandwidth, stream_channels (src/opus_decoder.cpp:
-            // 327-331: set once the packet has passed the checks above, whatever its frames return).  (A stream appears at most once
-            // per call: no two threads write the same entry.)
-            ctx->last_count[stream_ids[i]] = count;
-            ctx->last_flags[stream_ids[i]] = d[0].flags;
-        }
-    });
-    timer.mark("framing pass 1 (counts)");
-    std::vector<size_t> base(n + 1, 0); // where packet i lies in the arena
-    int max_frames = 0;
-    for (int i = 0; i < n; i++) {
-        first[i + 1] = first[i] + nframes[i];
-        base[i + 1] = base[i] + (nframes[i] && !(is_lost[i] == 1 || is_lost[i] == 3) ? (size_t)lens[i] : 0);
-        if (nframes[i] > max_frames) max_frames = nframes[i];
-    }
-    timer.mark("prefix sums");
-    if (first[n] == 0) return OPUSGPU_OK;
-    if (base[n] > 0x7fffffffu) return OPUSGPU_BAD_ARG; // descriptor offsets are 32-bit: split the call
-    if (int rc0 = grow_pinned(ctx, &ctx->h_descs, &ctx->cap_h_descs, sizeof(opusgpu_frame_desc) * (size_t)first[n])) return rc0;
-    if (int rc0 = grow_pinned(ctx, &ctx->h_arena, &ctx->cap_h_arena, base[n] + 1)) return rc0;
-    opusgpu_frame_desc *const all = (opusgpu_frame_desc *)ctx->h_descs; // frames in (packet, frame) order
-    uint8_t *const arena = (uint8_t *)ctx->h_arena;
-    timer.mark("staging");
-    auto place = [&](int lo, int hi) { // framing pass 2: descriptors and packet bytes of packets [lo, hi) to their places
-        for (int i = lo; i < hi; i++) {
-            if (!nframes[i]) continue;
-            if (is_lost[i] == 1) { // nothing to read: len 0, the flags of the stream's last packet (RFC mode: RFC bit and duration included)
-                const int32_t fresh = rfc ? (int32_t)((ogh::MODE_CELT - ogh::MODE_SILK) | 4 << 2 | (CC == 2 ? 32 : 0) | 1 << 9)
-                                          : ogh::empty_flags_no_packet_yet(CC);
-                const int32_t fl = ctx->last_count[stream_ids[i]] ? ctx->last_flags[stream_ids[i]] : fresh;
-                for (int k = 0; k < nframes[i]; k++) all[first[i] + k] = opusgpu_frame_desc{stream_ids[i], 0, 0, fl};
-                continue;
-            }
-            if (rfc && is_lost[i] >= 2) { // decode_fec: the concealment frames, then (2) the packet's first frame with the FEC bit
-                const int sid = stream_ids[i], lc = ctx->last_count[sid];
-                opusgpu_frame_desc d0[48];
-                (void)opusgpu_packet_to_frames_mode(packets[i], lens[i], sid, ctx->mode, d0);
-                int32_t fl[48];
-                const int np = nframes[i] - (is_lost[i] == 2 ? 1 : 0);
-                const int last_fs = lc ? ogh::flags_frame_size(ctx->last_flags[sid]) : 120;
-                const int lost_dur = lc ? lc * last_fs : OPUSGPU_FRAME_SAMPLES;
-                (void)conceal_pieces(is_lost[i] == 2 ? lost_dur - ogh::flags_frame_size(d0[0].flags) : lost_dur, last_fs,
-                                     lc ? ctx->last_flags[sid] : d0[0].flags, fl);
-                for (int k = 0; k < np; k++) all[first[i] + k] = opusgpu_frame_desc{sid, 0, 0, fl[k]};
-                if (is_lost[i] == 2) {
-                    memcpy(arena + base[i], packets[i], (size_t)lens[i]);
-                    d0[0].offset += (int32_t)base[i];
-                    d0[0].flags |= 1 << 10;
-                    all[first[i] + np] = d0[0];
-                }
-                continue;
-            }
-            opusgpu_frame_desc d[48];
-            (void)opusgpu_packet_to_frames_mode(packets[i], lens[i], stream_ids[i], ctx->mode, d);
-            memcpy(arena + base[i], packets[i], (size_t)lens[i]);
-            for (int k = 0; k < nframes[i]; k++) {
-                d[k].offset += (int32_t)base[i];
-                all[first[i] + k] = d[k];
-            }
-        }
-    };
-    // The common large call -- one frame per packet -- is pipelined: the frames in packet order ARE the step table, so the call
-    // goes in parts of packets, each placed (pass 2), uploaded and launched while the device works on the part before it and that
-    // part's PCM travels back.  Anything else: everything placed and uploaded first, then one step per frame index.
-    const bool pipelined = max_frames == 1 && first[n] >= 4096 && ctx->host_parts > 1 && !timer.on;
-    int rc = grow(ctx, &ctx->d_arena, &ctx->cap_arena, base[n] + 16);
-    if (rc) return rc;
-    if (!pipelined) {
-        on_ranges(place);
-        timer.mark("prefix + framing pass 2 (place)");
-        // 2. upload the arena once; run one step per frame index (frames of one packet are sequential)
-        HIPCHK(ctx, hipMemcpyAsync(ctx->d_arena, arena, base[n], hipMemcpyHostToDevice, ctx->stream));
-        timer.mark("arena upload (enqueue)");
-    }
-    std::vector<opusgpu_frame_desc> step;
-    std::vector<int> owner;
-    std::vector<int32_t> placed(rfc ? n : 0, 0); // RFC mode: samples of packet i delivered so far (frames may differ in duration)
-    for (int k = 0; k < max_frames; k++) {
-        step.clear();
-        owner.clear();
-        if (regular) {
-            // (frame j belongs to packet j)
-        } else if (pipelined) {
-            owner.reserve(first[n]);
-            for (int i = 0; i < n; i++)
-                if (nframes[i]) owner.push_back(i);
-        } else
-            for (int i = 0; i < n; i++)
-                if (nframes[i] > k && result[i] >= 0) {
-                    step.push_back(all[first[i] + k]);
-                    owner.push_back(i);
-                }
-        const int m = regular ? n : (int)owner.size();
-        if (m == 0) break;
-        timer.mark("step table");
-        if ((rc = grow(ctx, &ctx->d_descs, &ctx->cap_descs, sizeof(opusgpu_frame_desc) * m))) return rc;
-        if ((rc = grow(ctx, &ctx->d_pcm, &ctx->cap_pcm, frame_pcm * 2 * m))) return rc;
-        if ((rc = grow(ctx, &ctx->d_result, &ctx->cap_result, sizeof(int32_t) * m))) return rc;
-        if (!pipelined)
-            HIPCHK(ctx, hipMemcpyAsync(ctx->d_descs, step.data(), sizeof(opusgpu_frame_desc) * m, hipMemcpyHostToDevice,
-                                       ctx->stream));
-        if ((rc = grow_pinned(ctx, &ctx->h_pcm, &ctx->cap_h_pcm, frame_pcm * 2 * m))) return rc;
-        if ((rc = grow_pinned(ctx, &ctx->h_res, &ctx->cap_h_res, sizeof(int32_t) * m))) return rc;
-        const int16_t *h_pcm = (const int16_t *)ctx->h_pcm;
-        const int32_t *h_res = (const int32_t *)ctx->h_res;
-        // 3. kernels, then results and PCM back to the host.  The PCM comes in pieces, each followed by an event: every packet
-        //    owns its own block of the caller's buffer, and the threads that fill the blocks start on a piece as soon as it has
-        //    landed, while the later pieces are still on their way.  A large batch goes in parts: a part's pieces travel (on the
-        //    copy stream) while the next part's kernels run.  More parts start the copy earlier but pay the parse kernels' fixed
-        //    latency once per part: two is the measured optimum at 65,536 frames (9.5 ms; one 11.8, four 10.7, eight 13.2).
-        // the modes a range of this step's frames contains (the kernels of the others are not launched).  The range indexes the
-        // table that is uploaded: `all` itself in the pipelined flow (single-frame packets in packet order ARE the step table),
-        // `step` otherwise -- step[j] = all[first[owner[j]] + k], a different set of frames than all[lo .. hi) as soon as one packet
-        // of the call has more than one frame.
-        auto modes_of = [&](size_t lo, size_t hi) {
-            const opusgpu_frame_desc *table = pipelined ? all : step.data();
-            int mask = 0;
-            for (size_t f = lo; f < hi && mask != 7; f++) mask |= 1 << (table[f].flags & 3);
-            return mask & 7;
-        };
-        const int pieces = m >= 4096 ? OPUSGPU_COPY_PIECES : 1;
-        // (slices cost one more launch of the arithmetic kernels each; parts that are steps of their own pay the entropy kernels'
-        // latency each: two of those at most)
-        const bool sliced = pipelined && og_debug().host_slices;
-        const int parts = !(pieces > 1 && !timer.on) ? 1 : (sliced ? ctx->host_parts : OG_MIN(ctx->host_parts, 2));
-        for (int t = 0; t < pieces; t++)
-            if (!ctx->ev_piece[t]) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_piece[t], hipEventDisableTiming));
-        // frames [bound[t], bound[t + 1]) make piece t; a part is pieces / parts consecutive pieces.  Pipelined: a part is a range
-        // of PACKETS (its frames: first[] of the range's ends), cut evenly into its pieces.
-        size_t bound[OPUSGPU_COPY_PIECES + 1];
-        for (int h = 0; h < parts; h++) {
-            const int t0 = h * pieces / parts, t1 = (h + 1) * pieces / parts;
-            const size_t flo = pipelined ? (size_t)first[(int64_t)n * h / parts] : (size_t)((int64_t)m * t0 / pieces);
-            const size_t fhi = pipelined ? (size_t)first[(int64_t)n * (h + 1) / parts] : (size_t)((int64_t)m * t1 / pieces);
-            for (int t = t0; t <= t1; t++) bound[t] = flo + (size_t)((int64_t)(fhi - flo) * (t - t0) / (t1 - t0));
-        }
-        auto piece_lo = [&](int t) { return bound[t]; };
-        // DIRECT: the caller's PCM buffer is page-locked (opusgpu_host_register, hipHostMalloc, hipHostRegister) and the step table is
-        // the packets in order, one 20 ms block each: the pieces travel straight into it -- no landing zone, no host copy behind it.
-        const bool direct = pipelined && m == n && frame_capacity == 1 && !rfc && host_range_is_pinned(ctx, pcm, (size_t)n * cap_pcm * 2);
-        auto copy_pieces = [&](hipStream_t cs, int t0, int t1) -> int { // results of the pieces' frames first, then the pieces
-            const size_t flo = piece_lo(t0), fhi = piece_lo(t1);
-            HIPCHK(ctx, hipMemcpyAsync((int32_t *)ctx->h_res + flo, (const int32_t *)ctx->d_result + flo, sizeof(int32_t) * (fhi - flo),
-                                       hipMemcpyDeviceToHost, cs));
-            for (int t = t0; t < t1; t++) {
-                const size_t lo = piece_lo(t), hi = piece_lo(t + 1);
-                HIPCHK(ctx, hipMemcpyAsync((direct ? (uint8_t *)pcm : (uint8_t *)ctx->h_pcm) + lo * frame_pcm * 2,
-                                           (const uint8_t *)ctx->d_pcm + lo * frame_pcm * 2, (hi - lo) * frame_pcm * 2, hipMemcpyDeviceToHost, cs));
-                HIPCHK(ctx, hipEventRecord(ctx->ev_piece[t], cs));
-            }
-            return OPUSGPU_OK;
-        };
-        if (parts > 1) {
-            hipStream_t made;
-            if (int rc = copy_stream_of(ctx, &made)) return rc; // (opusgpu_upload_async makes it too, from another thread)
-            for (int h = 0; h < parts; h++)
-                if (!ctx->ev_part[h]) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_part[h], hipEventDisableTiming));
-        }
-        if (parts > 1 && sliced) {
-            // SLICES: everything placed and uploaded at once (0.2 ms of host work at 65,536 packets), the entropy kernels once over
-            // the whole table, the arithmetic kernels slice by slice with the slice's PCM leaving behind them
-            on_ranges(place);
-            timer.mark("  all packets placed");
-            HIPCHK(ctx, hipMemcpyAsync(ctx->d_arena, arena, base[n], hipMemcpyHostToDevice, ctx->stream));
-            HIPCHK(ctx, hipMemcpyAsync(ctx->d_descs, all, sizeof(opusgpu_frame_desc) * m, hipMemcpyHostToDevice, ctx->stream));
-            size_t cut[OPUSGPU_COPY_PIECES + 1];
-            for (int h = 0; h <= parts; h++) cut[h] = piece_lo(h * pieces / parts);
-            StepSlices sl;
-            sl.count = parts;
-            sl.bounds = cut;
-            sl.after_slice = [&](int h) -> int {
-                HIPCHK(ctx, hipEventRecord(ctx->ev_part[h], ctx->stream));
-                HIPCHK(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->ev_part[h], 0));
-                return copy_pieces(ctx->copy_stream, h * pieces / parts, (h + 1) * pieces / parts);
-            };
-            rc = decode_step_impl(ctx, m, ctx->d_descs, ctx->d_arena, ctx->d_pcm, ctx->d_result, nullptr, false, modes_of(0, m), 0, &sl);
-            if (rc) return rc;
-            timer.mark("  uploaded, launched, copies queued");
-        } else if (parts > 1) {
-            // (A/B flow, OPUSGPU_HOST_SLICES=0: every part its own in-order step -- the entropy kernels' latency is paid per part.
-            //  Measured also: the parts' chains alternating between two streams, 6.8 - 7.0 ms per 65,536 packets like the slices.)
-            for (int h = 0; h < parts; h++) {
-                const int t0 = h * pieces / parts, t1 = (h + 1) * pieces / parts;
-                const size_t flo = piece_lo(t0), fhi = piece_lo(t1);
-                hipStream_t const q = ctx->stream;
-                if (pipelined) { // this part's packets: place, upload
-                    const int plo = (int)((int64_t)n * h / parts), phi = (int)((int64_t)n * (h + 1) / parts);
-                    on_subranges(plo, phi, place);
-                    timer.mark("  part placed");
-                    if (base[phi] > base[plo])
-                        HIPCHK(ctx, hipMemcpyAsync((uint8_t *)ctx->d_arena + base[plo], arena + base[plo], base[phi] - base[plo],
-                                                   hipMemcpyHostToDevice, q));
-                    if (fhi > flo)
-                        HIPCHK(ctx, hipMemcpyAsync((opusgpu_frame_desc *)ctx->d_descs + flo, all + flo,
-                                                   sizeof(opusgpu_frame_desc) * (fhi - flo), hipMemcpyHostToDevice, q));
-                }
-                rc = decode_step_impl(ctx, (int)(fhi - flo), (const opusgpu_frame_desc *)ctx->d_descs + flo, ctx->d_arena,
-                                      (uint8_t *)ctx->d_pcm + flo * frame_pcm * 2, (int32_t *)ctx->d_result + flo, nullptr, false, modes_of(flo, fhi));
-                if (rc) return rc; // (an empty part launches nothing; its pieces' events are still recorded below)
-                HIPCHK(ctx, hipEventRecord(ctx->ev_part[h], q));
-                HIPCHK(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->ev_part[h], 0));
-                if ((rc = copy_pieces(ctx->copy_stream, t0, t1))) return rc;
-                timer.mark("  part uploaded, launched, copies queued");
-            }
-
-            timer.mark("table upload + kernels + copy-back in parts (enqueue)");
-        } else {
-            rc = decode_step_impl(ctx, m, ctx->d_descs, ctx->d_arena, ctx->d_pcm, ctx->d_result, nullptr, false, modes_of(0, m));
-            if (rc) return rc;
-            timer.mark("table upload + kernels (enqueue)");
-            if (timer.on) {
-                HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-                timer.mark("kernels (wait)");
-            }
-            if ((rc = copy_pieces(ctx->stream, 0, pieces))) return rc;
-        }
-        timer.mark("copy-back (enqueue)");
-        // every thread takes its share of every piece: the work left when the last piece lands is 1 / pieces of the PCM,
-        // spread over all threads
-        const int threads = pieces == 1 ? 1 : OPUSGPU_COPY_THREADS;
-        hipError_t thread_err[OPUSGPU_COPY_THREADS];
-        auto deliver = [&](int t) {
-            thread_err[t] = hipSuccess;
-            for (int p = 0; p < pieces; p++) {
-                if ((thread_err[t] = hipEventSynchronize(ctx->ev_piece[p])) != hipSuccess) return;
-                const int64_t plo = (int64_t)bound[p], phi = (int64_t)bound[p + 1];
-                const int lo = (int)(plo + (phi - plo) * t / threads), hi = (int)(plo + (phi - plo) * (t + 1) / threads);
-                for (int j = lo; j < hi; j++) {
-                    const int i = regular ? j : owner[j];
-                    if (h_res[j] < 0) {
-                        result[i] = h_res[j];
-                        if (direct) memset(pcm + (size_t)i * cap_pcm, 0, frame_pcm * 2); // (whatever the device buffer held: not the caller's)
-                        continue;
-                    }
-                    if (direct) { // the PCM is in place already
-                        result[i] += h_res[j];
-                        continue;
-                    }
-                    if (rfc) { // a packet appears once per step: nobody else touches placed[i]
-                        memcpy(pcm + (size_t)i * cap_pcm + (size_t)placed[i] * CC, &h_pcm[(size_t)j * frame_pcm], (size_t)h_res[j] * CC * 2);
-                        placed[i] += h_res[j];
-                    } else
-                        memcpy(pcm + (size_t)i * cap_pcm + (size_t)k * frame_pcm, &h_pcm[(size_t)j * frame_pcm], frame_pcm * 2);
-                    result[i] += h_res[j];
-                }
-            }
-        };
-        if (threads == 1)
-            deliver(0);
-        else {
-            ctx->pool.run(threads, deliver);
-        }
-        for (int t = 0; t < threads; t++)
-            if (thread_err[t] != hipSuccess) return fail(ctx, OPUSGPU_ERR_HIP, "hipEventSynchronize (PCM piece)", thread_err[t]);
-        timer.mark("copy-back + delivery (wait)");
-    }
-    return OPUSGPU_OK;
-}
-
-int opusgpu_decode_packets(opusgpu_ctx *ctx, int n, const int32_t *stream_ids, const uint8_t *const *packets,
-                           const int32_t *lens, int16_t *pcm, int frame_capacity, int32_t *result) {
-    return decode_packets_impl(ctx, n, stream_ids, packets, lens, pcm, frame_capacity, result, false);
-}
-int opusgpu_decode_packets_fec(opusgpu_ctx *ctx, int n, const int32_t *stream_ids, const uint8_t *const *packets,
-                               const int32_t *lens, int16_t *pcm, int frame_capacity, int32_t *result) {
-    return decode_packets_impl(ctx, n, stream_ids, packets, lens, pcm, frame_capacity, result, true);
-}
-
 } // extern "C"
+
+// the host-buffer path (opusgpu_decode_packets, opusgpu_decode_packets_fec): queues the steps above
+#include "og_host_path.hpp"
 
 // multistream decoding (include/opusgpu.h, MULTISTREAM): drives the contexts above
 #include "og_ms.hpp"

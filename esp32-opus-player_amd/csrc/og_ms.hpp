@@ -457,23 +457,14 @@ int opusgpu_ms_decode_packets(opusgpu_ms *ms, int n, const int32_t *decoder_ids,
         if (d < 0 || d >= ms->n_dec || lens[i] < 0)
             code = OPUSGPU_BAD_ARG;
         else if (empty) {
-            for (int st = 0; st < S; st++) { // every elementary stream, as do_plc does (:851-874)
+            for (int st = 0; st < S; st++) { // every elementary stream, as do_plc does (:851-874): the empty-packet branch, frame_size /
+                                             // 960 passes (include/opusgpu.h EMPTY PACKETS); RFC mode: a lost packet, concealed
                 opusgpu_ctx *c = ctx_of(st);
                 const int e = sub_index(d, st);
-                const int ch = st < C2 ? 2 : 1;
-                const int32_t last = c->last_count[e] ? c->last_flags[e] : -1;
-                if (!rfc) { // the empty-packet branch, frame_size / 960 passes (include/opusgpu.h EMPTY PACKETS)
-                    const int32_t fl = last >= 0 ? (last & 63) : ogh::empty_flags_no_packet_yet(ch);
-                    for (int k = 0; k < frame_size / OPUSGPU_FRAME_SAMPLES; k++) tmp[st * 48 + k] = opusgpu_frame_desc{e, 0, 0, fl};
-                    tcnt[st] = frame_size / OPUSGPU_FRAME_SAMPLES;
-                } else { // a lost packet: concealed as long as the stream's last packet was
-                    const int count = c->last_count[e] ? c->last_count[e] : 1;
-                    const int fs = ogh::flags_frame_size(c->last_flags[e]);
-                    if ((int64_t)count * fs > acc_samples) code = OPUSGPU_BUFFER_TOO_SMALL;
-                    const int32_t fl = last >= 0 ? last : (int32_t)((ogh::MODE_CELT - ogh::MODE_SILK) | 4 << 2 | (ch == 2 ? 32 : 0) | 1 << 9);
-                    for (int k = 0; k < count && k < 48; k++) tmp[st * 48 + k] = opusgpu_frame_desc{e, 0, 0, fl};
-                    tcnt[st] = count;
-                }
+                const ogh::PacketPlan p = ogh::plan_packet(nullptr, 0, e, c->n_streams, ms->mode, false, st < C2 ? 2 : 1,
+                                                           rfc ? frame_capacity : frame_size / OPUSGPU_FRAME_SAMPLES, c->last_count[e], c->last_flags[e], nullptr);
+                if (p.code) code = p.code;
+                tcnt[st] = ogh::plan_descs(p, nullptr, 0, e, ms->mode, 0, nullptr, &tmp[st * 48]);
             }
         } else {
             const int samples = opusgpu_ms_packet_to_frames(&L, packets[i], lens[i], d, ms->mode, tmp.data(), tcnt.data());
@@ -490,8 +481,7 @@ int opusgpu_ms_decode_packets(opusgpu_ms *ms, int n, const int32_t *decoder_ids,
                 for (int st = 0; st < S; st++) { // the TOC an empty packet of this stream decodes as (:327-331)
                     opusgpu_ctx *c = ctx_of(st);
                     const int e = sub_index(d, st);
-                    c->last_count[e] = tcnt[st];
-                    c->last_flags[e] = tmp[st * 48].flags;
+                    ogh::remember_packet(ogh::decoded_plan(tcnt[st], tmp[st * 48].flags), &c->last_count[e], &c->last_flags[e]);
                     for (int k = 0; k < tcnt[st]; k++) {
                         tmp[st * 48 + k].stream = e;
                         tmp[st * 48 + k].offset += (int32_t)base[i];
