@@ -28,9 +28,7 @@ static_assert(sizeof(opusgpu_frame_desc) == sizeof(FrameDesc), "descriptor layou
 // ---- kernels --------------------------------------------------------------------------------------
 // OPUSGPU_STALL_STREAM / OPUSGPU_STALL_US (og_debug.hpp): one wave that holds its stream for `ticks` of the device wall clock.  It
 // writes no memory, and `max_spins` ends its loop whatever the clock reads.
-#ifndef OG_STALL_MAX_SPINS
 #define OG_STALL_MAX_SPINS (1 << 20) // (each spin sleeps >= 512 cycles: 100 ms, the longest stall asked for, is < 470,000 spins at 2.4 GHz)
-#endif
 __global__ void __launch_bounds__(64) k_stream_stall(long long ticks, int max_spins) {
     const long long t0 = wall_clock64();
     for (int i = 0; i < max_spins && wall_clock64() - t0 < ticks; i++) __builtin_amdgcn_s_sleep(8);
@@ -251,12 +249,8 @@ __global__ void __launch_bounds__(256) k_output_stage(const i16 *__restrict__ pc
 #ifndef OG_WAVES_PER_SIMD
 #define OG_WAVES_PER_SIMD 1
 #endif
-#ifndef OG_RECON_WAVES
 #define OG_RECON_WAVES 2
-#endif
-#ifndef OG_SILK_WAVES
 #define OG_SILK_WAVES 2
-#endif
 __global__ void __launch_bounds__(64, OG_WAVES_PER_SIMD) k_decode_step(const FrameDesc *__restrict__ descs, const u8 *__restrict__ arena,
                                                    StreamState *st, i16 *pcm, i32 *result, int n, int n_streams,
                                                    int pcm_stride, int skip_celt, SilkHandoff *handoff, const SilkRec *srecs,
@@ -317,9 +311,7 @@ extern "C" void og_launch_silk_synth_nb(hipStream_t s, const void *descs, const 
 // information and pulses of frame LANES g + l into srecs[frame] and leaves the coder state in handoff[frame].  Twice, like the CELT
 // parse: k_silk_parse with 32 frames per wave (the upper lanes idle) for small in-order steps, k_silk_parse64 with 64 for pipelined
 // steps and large batches (og_silk_parse.hpp, OG_SP_LANES).
-#ifndef OG_SPARSE_WAVES
 #define OG_SPARSE_WAVES 4
-#endif
 // `shadow` (null in in-order steps): the per-stream copies of what the entropy half needs of the past, kept by this kernel for
 // pipelined SILK / hybrid steps (SilkShadow, og_silk_parse.hpp); `epoch`: the context's current one.
 template <int LANES>
@@ -357,9 +349,7 @@ __global__ void __launch_bounds__(64, OG_SPARSE_WAVES) k_silk_parse64(const Fram
 // ... and their parameter half (silk_decode_parameters), ONE (FRAME, CHANNEL) PER LANE: lane l of workgroup g takes channel l / 32
 // of frame 32 g + l % 32 -- the record's indices in, the dequantised parameters out, and for pipelined steps the entropy half's
 // past of the stream's next frame (`shadow`).  Behind k_silk_parse on the same stream.
-#ifndef OG_SPARAMS_WAVES
 #define OG_SPARAMS_WAVES 4
-#endif
 __global__ void __launch_bounds__(64, OG_SPARAMS_WAVES) k_silk_params(const FrameDesc *__restrict__ descs, const StreamState *st, SilkRec *srecs,
                                                                        int n, int n_streams, SilkShadow *shadow, u32 epoch) {
     constexpr int FR = OG_PAR_LANES / 2;

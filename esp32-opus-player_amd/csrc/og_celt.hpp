@@ -1173,7 +1173,7 @@ struct CeltSynth {
     int lost;          // a concealed frame (celt_decode_lost): the energy histories, the post-filter and its state stay as they are
     int energies_kept_by_parse = 0; // split path: CeltState::bandE is written by the parse kernel (celt_parse_lane), not here
     // the stream's post-filter state and ring head, when the caller has them in registers already (the reconstruction kernel
-    // fetches every scalar it needs of the stream in one batch at its start, og_celt_split.hpp ReconHdr); else read here
+    // fetches every scalar it needs of the stream in one batch at its start, og_celt_recon.hpp ReconHdr); else read here
     int have_state = 0;
     int st_pf_period, st_pf_period_old, st_pf_tapset, st_pf_tapset_old, st_ring_pos;
     i32 st_pf_gain, st_pf_gain_old;

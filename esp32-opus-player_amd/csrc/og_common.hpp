@@ -43,14 +43,7 @@ extern "C" void og_emul_tap(int id); // stage taps for parity tests (host emulat
 #define OG_DEV static __device__ __forceinline__
 #define OG_DEVN static __device__ __noinline__
 #define OG_MEMBER __device__ __forceinline__
-// A workgroup is one wave, except in the translation units that say otherwise before including this header (og_recon.hip:
-// several frames per workgroup, one per wave): there OG_LANE is the lane within the wave and OG_WAVE the wave's index.
-#ifndef OG_LANE
-#define OG_LANE ((int)threadIdx.x)
-#endif
-#ifndef OG_WAVE
-#define OG_WAVE 0
-#endif
+#define OG_LANE ((int)threadIdx.x) // (a workgroup of the wave-per-frame kernels is one wave)
 #define OG_NLANES 64
 #define OG_FULL_SYNC() __syncthreads()
 // LDS-only ordering between lanes of ONE wave: the LDS unit serves a wave's instructions in order, so only the

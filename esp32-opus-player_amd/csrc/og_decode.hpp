@@ -5,10 +5,8 @@
 #pragma once
 #include "og_celt.hpp"
 #include "og_celt_split.hpp"
-#ifndef OG_NO_SILK
 #include "og_silk.hpp"
 #include "og_plc.hpp"
-#endif
 
 namespace og {
 
@@ -21,9 +19,7 @@ OG_DEV void stream_init(StreamState *st, int channels) {
     OG_SYNC();
     OG_FOR_LANES(i, 2 * NBANDS) st->celt.logE1[i] = st->celt.logE2[i] = (i16)(-28 * 1024);
     if (OG_LANE == 0) st->channels = channels;
-#ifndef OG_NO_SILK
     silk_init_state(&st->silk);
-#endif
     OG_SYNC();
 }
 
@@ -34,9 +30,7 @@ OG_DEV void stream_reset(StreamState *st) {
         st->prev_mode = 0;
         st->range_final = 0;
     }
-#ifndef OG_NO_SILK
     silk_init_state(&st->silk);
-#endif
     OG_SYNC();
 }
 
@@ -90,7 +84,6 @@ OG_DEV int decode_frame_wave(StreamState *st, const u8 *payload, int len, int mo
         return INTERNAL_ERROR; // the synthesis kernel only exists behind the parse kernel
     int celt_ret = 0;
 
-#ifndef OG_NO_SILK
     if (mode != MODE_CELT && !q4_resume) {
         if (prev_mode == MODE_CELT) silk_init_state(&st->silk);
         int internal_hz = 16000;
@@ -98,16 +91,12 @@ OG_DEV int decode_frame_wave(StreamState *st, const u8 *payload, int len, int mo
         int ret = silk_decode_20ms<!WITH_CELT>(&st->silk, rc, ch, internal_hz, srec); // fills g_pcm_silk (48 kHz, interleaved)
         if (ret) return INTERNAL_ERROR;
     }
-#else
-    if (mode != MODE_CELT) return INTERNAL_ERROR;
-#endif
     int start_band = 0;
     if (!srec && mode != MODE_CELT && rc_tell(rc) + 17 + 20 * (mode == MODE_HYBRID) <= 8 * len) {
         if (mode == MODE_HYBRID) (void)rc_bit_logp(rc, 12); // redundancy flag read and ignored (Q2)
     }
     if (mode != MODE_CELT) start_band = 17;
     const int disable_inv = CC == 1;
-#ifndef OG_NO_SILK
     if (handoff && mode == MODE_HYBRID) {
         OG_SYNC();
         {
@@ -143,7 +132,6 @@ OG_DEV int decode_frame_wave(StreamState *st, const u8 *payload, int len, int mo
         OG_SYNC();
         return audiosize;
     }
-#endif
 
     if constexpr (WITH_CELT) {
     // One CELT call site (the whole CELT decoder is inlined into it): the regular frame, or -- Q4 -- the 2.5 ms
@@ -180,7 +168,6 @@ OG_DEV int decode_frame_wave(StreamState *st, const u8 *payload, int len, int mo
             OG_SYNC();
         }
     }
-#ifndef OG_NO_SILK
     if (mode != MODE_CELT) { // SAT16(outbuf + pcm_silk) over audiosize*stream_channels entries (Q3)
         OG_SYNC();
         OG_FOR_LANES(i, audiosize * ch) { // i indexes the interleaved PCM; sample j of channel c lives in plane c
@@ -189,7 +176,6 @@ OG_DEV int decode_frame_wave(StreamState *st, const u8 *payload, int len, int mo
         }
         OG_SYNC();
     }
-#endif
     if (OG_LANE == 0) {
         st->prev_mode = mode_after;
         st->frames_decoded += 1;
@@ -230,7 +216,6 @@ OG_DEV int conceal_chunk_rfc(StreamState *st, int ch, i16 *pcm, int audiosize, i
         return audiosize;
     }
     const int nmix = audiosize * (ch < CC ? ch : CC);
-#ifndef OG_NO_SILK
     if (mode != MODE_CELT) {
         Rc none;
         rc_init(none, 0u);
@@ -247,13 +232,9 @@ OG_DEV int conceal_chunk_rfc(StreamState *st, int ch, i16 *pcm, int audiosize, i
             OG_SYNC();
         }
     }
-#else
-    if (mode != MODE_CELT) return INTERNAL_ERROR;
-#endif
     int celt_ret = 0;
     if (mode != MODE_SILK) {
         celt_ret = celt_conceal(&st->celt, &st->loss, audiosize, CC, mode == MODE_CELT ? 0 : 17, st->loss.celt_end_band);
-#ifndef OG_NO_SILK
         if (mode == MODE_HYBRID && celt_ret >= 0) {
             OG_SYNC();
             OG_FOR_LANES(i, nmix) {
@@ -262,7 +243,6 @@ OG_DEV int conceal_chunk_rfc(StreamState *st, int ch, i16 *pcm, int audiosize, i
             }
             OG_SYNC();
         }
-#endif
         if (celt_ret >= 0) {
             OG_SYNC();
             if (hold)
@@ -327,16 +307,13 @@ OG_DEV int decode_frame_rfc(StreamState *st, const u8 *payload, int len, int mod
     // concealment from the OLD mode (as much as the frame is long, for a 2.5 ms frame), cross-faded into the new frame at the
     // end.  The SILK modes' concealment runs before anything of the new frame is decoded, CELT's behind the frame's SILK layer.
     // It waits in the SILK up-sampler's buffers (dead whenever it is needed; a frame with a redundant frame has no transition).
-    int transition = 0;
-#ifndef OG_NO_SILK
-    transition = prev_mode > 0 && ((mode == MODE_CELT && prev_mode != MODE_CELT && !prev_redundancy) || (mode != MODE_CELT && prev_mode == MODE_CELT));
+    int transition = prev_mode > 0 && ((mode == MODE_CELT && prev_mode != MODE_CELT && !prev_redundancy) || (mode != MODE_CELT && prev_mode == MODE_CELT));
     i16 *const tr_hold = &SL().u.out.up[0][0];
     const int tr_size = OG_MIN(240, audiosize);
     if (transition && mode == MODE_CELT) {
         const int r = conceal_chunk_rfc(st, ch, nullptr, tr_size, tr_hold);
         if (r < 0) return r;
     }
-#endif
     OG_SYNC();
     OG_FOR_LANES(i, len) S.pkt[i] = payload[i];
     OG_SYNC();
@@ -344,7 +321,6 @@ OG_DEV int decode_frame_rfc(StreamState *st, const u8 *payload, int len, int mod
     rc_init(rc, (u32)len);
     int celt_ret = 0, redundancy = 0, celt_to_silk = 0, redundancy_bytes = 0, celt_lost = 0, main_len = len;
     u32 redundant_rng = 0;
-#ifndef OG_NO_SILK
     if (mode != MODE_CELT) {
         if (prev_mode == MODE_CELT) silk_init_state(&st->silk, &st->loss);
         silk_wave_tab_load(); // (og_rfc.hip: the entropy decoder's tables into LDS, over rows that nothing uses until the CELT layer)
@@ -390,10 +366,6 @@ OG_DEV int decode_frame_rfc(StreamState *st, const u8 *payload, int len, int mod
             OG_SYNC();
         }
     }
-#else
-    if (mode != MODE_CELT) return INTERNAL_ERROR;
-    i16 *const red_hold = nullptr;
-#endif
     if (OG_LANE == 0) st->loss.celt_end_band = end_band; // (what a later concealment's last band is)
     // the redundant frame: its bytes to the front of the packet buffer, a range decoder of its own, 5 ms from band 0
     auto decode_redundant = [&]() {
@@ -430,7 +402,6 @@ OG_DEV int decode_frame_rfc(StreamState *st, const u8 *payload, int len, int mod
             celt_ret = celt_conceal(&st->celt, &st->loss, audiosize, CC, mode == MODE_CELT ? 0 : 17, end_band);
         else
             celt_ret = celt_decode_frame(&st->celt, rc, audiosize, ch, CC, mode == MODE_CELT ? 0 : 17, disable_inv, end_band, &st->loss);
-#ifndef OG_NO_SILK
         if (mode == MODE_HYBRID && celt_ret >= 0) {
             OG_SYNC();
             OG_FOR_LANES(i, nmix) { // i indexes the interleaved PCM; sample j of channel c lives in plane c
@@ -439,14 +410,12 @@ OG_DEV int decode_frame_rfc(StreamState *st, const u8 *payload, int len, int mod
             }
             OG_SYNC();
         }
-#endif
         if (celt_ret >= 0) {
             OG_SYNC();
             pcm_store(pcm, audiosize, Cp, CC);
             OG_SYNC();
         }
     }
-#ifndef OG_NO_SILK
     else if (prev_mode == MODE_HYBRID && !(redundancy && celt_to_silk && prev_redundancy)) {
         // RFC 6716 section 4.5.2: the MDCT fades out through a silence frame of 2.5 ms from band 0 (its return value is not looked
         // at); its 120 samples per channel are added to the SILK PCM already in HBM
@@ -487,7 +456,6 @@ OG_DEV int decode_frame_rfc(StreamState *st, const u8 *payload, int len, int mod
         OG_FOR_LANES(i, head * CC) pcm[i] = tr_hold[i];
         rfc_smooth_fade(pcm, CC * head, tr_hold, CC * head, CC, false);
     }
-#endif
     OG_SYNC();
     if (OG_LANE == 0) {
         st->prev_mode = mode;

@@ -2,9 +2,9 @@
 // steps, where the kernel's latency is what the step pays) and as k_celt_parse64 with 64 (og_parse64.hip: pipelined steps, where the
 // kernel runs next to the arithmetic kernels and its ISSUE SLOTS are what the step pays -- a wave's instruction stream is nearly the
 // same for 64 frames as for 32: 3.45 k -> 2.0 k vector instructions per frame, 20 % -> 33 % of the lanes active).
-// Define OG_PARSE_KERNEL_NAME (and OG_PL_LANES, before og_celt_split.hpp) before including this.
+// Define OG_PARSE_KERNEL_NAME (and OG_PL_LANES, OG_PL_WAVES, OG_PARSE_DYN_LDS: og_celt_parse.hpp) before including this.
 #pragma once
-#include "og_celt_split.hpp"
+#include "og_celt_parse.hpp"
 
 using namespace og;
 

@@ -4,7 +4,7 @@
 // A translation unit of its own because the working set is ONE __shared__ object (FrameLds, og_state.hpp) whose layout
 // is chosen at compile time: here OG_RECON_TIGHT selects the layout without the folding-history rows, the packet buffer and
 // the entropy-decoding arrays, with the synthesis buffer starting inside X.  Only the phase-major band loop and the
-// synthesis run from this layout; frames it does not take (recon_fast_eligible, og_celt_split.hpp) are left to the general
+// synthesis run from this layout; frames it does not take (recon_fast_eligible, og_celt_recon.hpp) are left to the general
 // kernel k_celt_recon in og_api.hip, which is launched right behind this one and skips the frames done here.
 // Why: measured on the 10 KB layout, k_celt_recon's time goes with 1 / (waves per SIMD) -- 2.69 ms at three, 2.09 ms at four; and
 // in pipelined steps the kernel shares its CUs' LDS with the parse kernel's workgroups (og_state.hpp).
@@ -13,13 +13,11 @@
 // leaves of two / four frames pooled in one workgroup and dealt out by cost, and a kernel of its own for the leaves: DESIGN.md 6c.)
 #define OG_RECON_TIGHT 1
 #include <hip/hip_runtime.h>
-#include "og_celt_split.hpp"
+#include "og_celt_recon.hpp"
 
 using namespace og;
 
-#ifndef OG_FAST_WAVES
 #define OG_FAST_WAVES 6 // (80 registers; the working set is five LDS granules: og_state.hpp)
-#endif
 
 
 // `hybrid`: the step's hybrid frames come through the split path too (their SILK half by k_silk_parse / k_silk_synth): this

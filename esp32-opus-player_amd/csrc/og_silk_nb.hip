@@ -17,7 +17,5 @@
 #define OG_SSYNTH_NB_ONLY 1
 // Five waves per SIMD, not the six its 75 registers would allow: the step's entropy kernels (82 and 100 registers a wave) need room
 // on the same SIMDs, and the step is as long as their chain -- measured (SILK-NB step, pipelined): 0.94 ms at six, 0.84 at five, 0.90 at four
-#ifndef OG_SSYNTH_MAX_WAVES
 #define OG_SSYNTH_MAX_WAVES 5
-#endif
 #include "og_silk_synth_kernel.hpp"

@@ -12,7 +12,8 @@
 // Reference behaviour: silk_Decode's entropy half (src/silk.cpp:1481-1700), silk_decode_indices (:708),
 // silk_decode_pulses (:898) with silk_shell_decoder (:1162) and silk_decode_signs (:1436), silk_stereo_decode_pred (:592).
 #pragma once
-#include "og_celt_split.hpp"
+#include "og_range.hpp"
+#include "og_celt_rec.hpp"
 
 namespace og {
 
@@ -220,9 +221,7 @@ OG_DEV void shell_split_tab(RcLane &rc, int &c1, int &c2, int p, int table) {
 // is nearly the same for 64 frames as for 32) -- k_silk_parse uses the first 32 columns: 32 frames per wave for small in-order
 // steps, where the latency of a wave's serial chain is what the step pays and more, shorter-lived waves hide it better.  (Round 4
 // measured 64 frames per wave as a wash; with the parameter half gone -- 77 registers, 7.8 KB of LDS -- it wins: DESIGN.md 6e.)
-#ifndef OG_SP_LANES
 #define OG_SP_LANES (OG_NLANES >= 64 ? 64 : OG_NLANES)
-#endif
 // Lane-private scratch, [element][lane]: a lane's walk along its column and the wave's access to a row fall on different banks.
 // k_silk_parse keeps only the pulse decoder's block bookkeeping here (2.5 KB per 32 frames; with the table blob 5.4 KB per workgroup):
 //   blk      sum_pulses | nLshifts << 5 per 16-sample block;

@@ -10,9 +10,7 @@
 
 using namespace og;
 
-#ifndef OG_SILK_WAVES
 #define OG_SILK_WAVES 2
-#endif
 #ifdef OG_SSYNTH_MAX_WAVES // at most this many of the kernel's waves per SIMD (the register allocation is raised to the count that says so)
 #define OG_SSYNTH_OCC __attribute__((amdgpu_waves_per_eu(2, OG_SSYNTH_MAX_WAVES)))
 #else

@@ -12,9 +12,7 @@
 #include <functional>
 #include <thread>
 
-#ifndef OG_SILK_SETS
 #define OG_SILK_SETS 3 // sets of SILK records and hand-offs that pipelined SILK / hybrid steps rotate through
-#endif
 static_assert(OG_SILK_SETS >= 2, "a pipelined SILK / hybrid step runs next to the step before it");
 
 // The library's streams, the events between them and what the host remembers of the steps it has queued.
@@ -136,12 +134,8 @@ static void pipeline_destroy(opusgpu_ctx *ctx) {
 // such a step does not run ahead of anything.
 // OPUSGPU_LAUNCH_DELAY_US (og_debug.hpp): the host dawdles before the launches of a decode step -- what a loaded host, a slow
 // event hop or another thread's launches would do -- so that tools/launch_jitter.py can show the step time does not depend on it
-#ifndef OG_SILK_PARSE_WIDE_MIN
 #define OG_SILK_PARSE_WIDE_MIN 98304 // frames of an in-order launch from which the SILK parse runs with 64 frames per wave
-#endif
-#ifndef OG_HALVES_MIN
 #define OG_HALVES_MIN 4096 // frames per half below which an in-order step is not cut in two
-#endif
 static void launch_jitter() {
     if (const int us = og_debug().launch_delay_us) std::this_thread::sleep_for(std::chrono::microseconds(us));
 }

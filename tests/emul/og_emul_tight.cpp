@@ -3,7 +3,8 @@
 // the general one come back as -999.  Same entry points as og_emul.cpp so that tools/fuzz_emul_celt.py can drive either.
 #define OG_HOST_EMUL 1
 #define OG_RECON_TIGHT 1
-#include "og_celt_split.hpp"
+#include "og_celt_parse.hpp"
+#include "og_celt_recon.hpp"
 
 extern "C" {
 int emu_state_size(void) { return (int)sizeof(og::StreamState); }

@@ -1,4 +1,4 @@
-// TEST-ONLY driver for tests/test_pvq_walk_sites.py: the reconstruction kernel's PVQ index walk (pvq_leaf_lane, og_celt_split.hpp) in
+// TEST-ONLY driver for tests/test_pvq_walk_sites.py: the reconstruction kernel's PVQ index walk (pvq_leaf_lane, og_celt_recon.hpp) in
 // host emulation, in the LDS layout of k_celt_recon_fb, against the oracle's step-by-step cwrsi -- the pulses and their energy
 // BEFORE the scaling (tapped), the scaled coefficients and the collapse mask; and the block-of-position arithmetic of the mask.
 #define OG_HOST_EMUL 1
@@ -11,7 +11,7 @@ static int32_t tap_yy;
         for (int q_ = 0; q_ < (n); q_++) tap_y[q_] = (p)[q_]; \
         tap_yy = (e);                                  \
     } while (0)
-#include "og_celt_split.hpp"
+#include "og_celt_recon.hpp"
 
 extern "C" void og_emul_tap(int) {}
 extern "C" {
@@ -51,7 +51,7 @@ long kat_walk(int n, int k, const uint32_t *idx, int nidx, uint32_t *where, long
 }
 
 // (j * M) >> 16 == j / blen and j * M < 2^24 for every j < 176, blen <= 176 and M = floor(65536 / blen) + 1 or + 2 (the GPU takes M
-// from a reciprocal of one ulp: og_celt_split.hpp); and the emulation's own M is the first of the two.  Returns the failures.
+// from a reciprocal of one ulp: og_celt_recon.hpp); and the emulation's own M is the first of the two.  Returns the failures.
 long kat_block_of(long *cases) {
     long bad = 0;
     for (int blen = 1; blen <= 176; blen++) {

@@ -85,7 +85,7 @@ def test_pvq_leaf_over_all_reachable_n_k(oracle):
 
 
 def test_pvq_sparse_leaves_many_indices(oracle):
-    """The leaf walk skips runs of zeros in sparse leaves by bisection (og_celt_split.hpp, pvq_leaf_lane): every reachable
+    """The leaf walk skips runs of zeros in sparse leaves by bisection (og_celt_recon.hpp, pvq_leaf_lane): every reachable
     (N, K) with more than one dimension per pulse, many indices each -- random ones, the first and last, and the ones around
     every U(N, j) boundary, where a run ends or a sign flips."""
     emu = C.CDLL(os.path.join(ROOT, "tests", "emul", "libog_emul.so"))

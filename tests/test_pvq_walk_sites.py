@@ -1,4 +1,4 @@
-"""The reconstruction kernel's PVQ index walk (pvq_leaf_lane, og_celt_split.hpp: one bisection per pulse for all lanes, the
+"""The reconstruction kernel's PVQ index walk (pvq_leaf_lane, og_celt_recon.hpp: one bisection per pulse for all lanes, the
 collapse mask gathered from the pulses as they are stored) in host emulation, in the LDS layout of k_celt_recon_fb, against the
 oracle's step-by-step cwrsi (oracle/oc_celt_math.c) -- driver tests/emul/og_pvq_walk_kat.cpp, built here with g++; no GPU:
 

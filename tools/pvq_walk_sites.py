@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Which code regions ("sites") of the PVQ index walk (og_celt_split.hpp, pvq_leaf_lane) a WAVE passes per trip of its loop on the
+"""Which code regions ("sites") of the PVQ index walk (og_celt_recon.hpp, pvq_leaf_lane) a WAVE passes per trip of its loop on the
 headline payloads, and what candidate schedules of the walk would cost (CPU, host emulation for the leaves).  A wave
 holds the leaves of one frame, one per lane, and runs every region that has at least one taker, loops to their deepest lane.
 The walk is restated here per lane with the kernel's own schedule (tools/pvq_zero_run.py has the arithmetic); the cost of a region

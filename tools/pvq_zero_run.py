@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The identity behind the zero-run skip of the PVQ leaf walk (og_celt_split.hpp, pvq_leaf_lane), checked in exact integers against
+"""The identity behind the zero-run skip of the PVQ leaf walk (og_celt_recon.hpp, pvq_leaf_lane), checked in exact integers against
 the step-by-step walk (cwrsi, src/celt.cpp:2545): with V(a) = U(a,k) + U(a,k+1) the dimensions n .. a+1 all decode to zero exactly
 when V(n) - V(a) <= 2 i < V(n) + V(a), and skipping them subtracts (V(n) - V(a)) / 2 from the index.   python3 tools/pvq_zero_run.py"""
 import random, functools, sys
