@@ -34,6 +34,9 @@ EXPORTS = [
     "opusgpu_files_plan", "opusgpu_file_batch_steps", "opusgpu_file_batch_step", "opusgpu_file_batch_segments", "opusgpu_file_batch_arena",
     "opusgpu_file_batch_track_samples", "opusgpu_file_batch_packet_start", "opusgpu_file_batch_free", "opusgpu_tracks_assemble_device",
     "opusgpu_files_decode",
+    "opusgpu_file_layout", "opusgpu_ms_files_plan", "opusgpu_ms_file_batch_steps", "opusgpu_ms_file_batch_step", "opusgpu_ms_file_batch_segments",
+    "opusgpu_ms_file_batch_arena", "opusgpu_ms_file_batch_track_samples", "opusgpu_ms_file_batch_packet_start", "opusgpu_ms_file_batch_free",
+    "opusgpu_ms_tracks_assemble_device", "opusgpu_ms_files_decode", "opusgpu_ms_files_last_steps_ms",
 ]
 
 
@@ -202,6 +205,22 @@ def load_lib():
     lib.opusgpu_file_batch_free.restype = None
     lib.opusgpu_tracks_assemble_device.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp]
     lib.opusgpu_files_decode.argtypes = [vp, vp, vp, vp, vp]
+    lib.opusgpu_file_layout.argtypes = [vp, C.c_int64, C.POINTER(MsLayout), vp]
+    lib.opusgpu_ms_files_plan.argtypes = [C.c_int, vp, vp, C.POINTER(MsLayout), C.c_int, C.c_int, vp, C.POINTER(vp)]
+    lib.opusgpu_ms_file_batch_steps.argtypes = [vp]
+    lib.opusgpu_ms_file_batch_step.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp)]
+    lib.opusgpu_ms_file_batch_segments.argtypes = [vp, C.c_int, C.POINTER(vp)]
+    lib.opusgpu_ms_file_batch_arena.argtypes = [vp, C.POINTER(C.c_size_t)]
+    lib.opusgpu_ms_file_batch_arena.restype = vp
+    lib.opusgpu_ms_file_batch_track_samples.argtypes = [vp]
+    lib.opusgpu_ms_file_batch_track_samples.restype = C.c_int64
+    lib.opusgpu_ms_file_batch_packet_start.argtypes = [vp, C.c_int, C.c_int]
+    lib.opusgpu_ms_file_batch_packet_start.restype = C.c_int64
+    lib.opusgpu_ms_file_batch_free.argtypes = [vp]
+    lib.opusgpu_ms_file_batch_free.restype = None
+    lib.opusgpu_ms_tracks_assemble_device.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp]
+    lib.opusgpu_ms_files_decode.argtypes = [vp, vp, vp, vp, vp]
+    lib.opusgpu_ms_files_last_steps_ms.restype = C.c_float
     _lib = lib
     return lib
 
@@ -400,6 +419,84 @@ class FileBatch:
     def close(self):
         if self.h:
             self.lib.opusgpu_file_batch_free(self.h)
+            self.h = None
+            self.arena = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def file_layout(data):
+    """Host-only: the layout of one Ogg Opus file, read from its OpusHead (opusgpu_file_layout) -> ((channels, streams, coupled,
+    mapping list), info [FILE_INFO_DTYPE record]).  Family 0 gives one stream and the identity mapping.  Raises OpusGpuError with
+    the reader's code (or OPUSGPU_UNIMPLEMENTED for mapping family 255) when the file has no usable header."""
+    lib = load_lib()
+    buf = np.frombuffer(bytes(data) + b"\0", dtype=np.uint8)
+    lay = MsLayout()
+    info = np.zeros(1, dtype=FILE_INFO_DTYPE)
+    r = lib.opusgpu_file_layout(buf.ctypes.data, buf.size - 1, C.byref(lay), info.ctypes.data)
+    if r != 0:
+        e = OpusGpuError(f"opusgpu_file_layout failed: {r}")
+        e.code = r
+        raise e
+    return (lay.channels, lay.streams, lay.coupled, [lay.mapping[c] for c in range(lay.channels)]), info[0]
+
+
+class MsFileBatch:
+    """Decode steps, packet arena and track segments planned from whole Ogg Opus files of ONE multistream layout by
+    opusgpu_ms_files_plan (host only, include/opusgpu.h WHOLE FILES / MULTISTREAM).  files: a list of bytes-like objects, file i =
+    decoder i; layout: (channels, streams, coupled, mapping) or an MsLayout.  A step is rows of `streams` descriptors, one row and
+    one segment per file that has a frame in it."""
+
+    def __init__(self, files, layout, rfc=False, threads=1):
+        lib = load_lib()
+        self.layout = layout if isinstance(layout, MsLayout) else ms_layout(*layout)
+        self._files = [np.frombuffer(bytes(f) + b"\0", dtype=np.uint8) for f in files]  # (kept alive; + 1: never an empty buffer)
+        n = len(self._files)
+        ptrs = np.array([a.ctypes.data for a in self._files], dtype=np.uint64)
+        lens = np.array([a.size - 1 for a in self._files], dtype=np.int64)
+        self.info = np.zeros(n, dtype=FILE_INFO_DTYPE)
+        h = C.c_void_p()
+        r = lib.opusgpu_ms_files_plan(n, ptrs.ctypes.data, lens.ctypes.data, C.byref(self.layout), 1 if rfc else 0, threads,
+                                      self.info.ctypes.data, C.byref(h))
+        if r != 0:
+            e = OpusGpuError(f"opusgpu_ms_files_plan failed: {r}")
+            e.code = r
+            raise e
+        self.lib, self.h = lib, h
+        self.n_files, self.channels, self.streams, self.rfc = n, int(self.layout.channels), int(self.layout.streams), bool(rfc)
+        self.row_samples = RFC_FRAME if rfc else FRAME
+        self.n_steps = lib.opusgpu_ms_file_batch_steps(h)
+        self.track_samples = lib.opusgpu_ms_file_batch_track_samples(h)
+        nbytes = C.c_size_t()
+        a = lib.opusgpu_ms_file_batch_arena(h, C.byref(nbytes))
+        self.arena = np.ctypeslib.as_array((C.c_uint8 * nbytes.value).from_address(a)) if nbytes.value else np.zeros(0, np.uint8)
+
+    def step(self, k):
+        """-> (descriptors [rows, streams] of DESC_DTYPE, file of every row [int32], segments [TRACK_SEG_DTYPE]); views, valid
+        until close()."""
+        d, sf, sg = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        n = self.lib.opusgpu_ms_file_batch_step(self.h, k, C.byref(d), C.byref(sf))
+        if n < 0:
+            raise IndexError(k)
+        if n == 0:
+            return np.zeros((0, self.streams), DESC_DTYPE), np.zeros(0, np.int32), np.zeros(0, TRACK_SEG_DTYPE)
+        self.lib.opusgpu_ms_file_batch_segments(self.h, k, C.byref(sg))
+        descs = np.frombuffer((C.c_uint8 * (16 * n * self.streams)).from_address(d.value), dtype=DESC_DTYPE).reshape(n, self.streams)
+        files = np.frombuffer((C.c_uint8 * (4 * n)).from_address(sf.value), dtype=np.int32)
+        segs = np.frombuffer((C.c_uint8 * (32 * n)).from_address(sg.value), dtype=TRACK_SEG_DTYPE)
+        return descs, files, segs
+
+    def packet_start(self, file, packet_seq):
+        """Planned start (track-relative sample) of a file's packet; packet_seq == its packet count: the planned length."""
+        return self.lib.opusgpu_ms_file_batch_packet_start(self.h, file, packet_seq)
+
+    def close(self):
+        if self.h:
+            self.lib.opusgpu_ms_file_batch_free(self.h)
             self.h = None
             self.arena = None
 
@@ -698,6 +795,7 @@ class MultistreamContext:
             e.code = rc
             raise e
         self.h = h
+        self.device = device
         self.n_decoders, self.channels, self.streams, self.coupled = n_decoders, channels, streams, coupled
         self.rfc = False
 
@@ -754,6 +852,49 @@ class MultistreamContext:
 
     def synchronize(self):
         self._chk(self.lib.opusgpu_ms_synchronize(self.h), "opusgpu_ms_synchronize")
+
+    def tracks_assemble_device(self, n_segs, d_segs, d_pcm_coupled, d_pcm_mono, row_samples, d_res_coupled, d_res_mono, d_tracks,
+                               d_track_state, stream=None):
+        """k_ms_tracks_assemble (include/opusgpu.h WHOLE FILES / MULTISTREAM): segments [TRACK_SEG_DTYPE] of a step's ELEMENTARY PCM
+        rows (coupled [rows * coupled, row_samples, 2], mono [rows * mono, row_samples]) -> the packed interleaved tracks."""
+        self._chk(self.lib.opusgpu_ms_tracks_assemble_device(self.h, n_segs, d_segs, d_pcm_coupled, d_pcm_mono, row_samples, d_res_coupled,
+                                                             d_res_mono, d_tracks, d_track_state, stream),
+                  "opusgpu_ms_tracks_assemble_device")
+
+    def decode_files(self, files, rfc=False, threads=1, batch=None):
+        """Whole Ogg Opus files of this object's layout -> (list of int16 arrays [samples, channels], one trimmed track per file,
+        info), as Context.decode_files returns them: FILE_INFO_DTYPE records plus `final_status` and `bad_packet`, `track_samples`
+        the FINAL length.  Decoders 0 .. len(files) - 1 get fresh state; the object's mode is set to the batch's.  batch: an
+        MsFileBatch made beforehand from the same files (of this layout; `rfc` is then the batch's)."""
+        own = batch is None
+        if own:
+            batch = MsFileBatch(files, self.layout, rfc=rfc, threads=threads)
+        mem = Context(self.device)  # (device memory and copies are a plain context's calls)
+        try:
+            n = batch.n_files
+            self.set_mode(batch.rfc)
+            total = max(int(batch.track_samples), 1) * batch.channels
+            d_tracks = mem.dev_alloc(2 * total)
+            try:
+                lengths = np.zeros(n, dtype=np.int64)
+                status = np.zeros((n, 2), dtype=np.int32)
+                self._chk(self.lib.opusgpu_ms_files_decode(self.h, batch.h, d_tracks, lengths.ctypes.data, status.ctypes.data),
+                          "opusgpu_ms_files_decode")
+                packed = np.zeros(total, dtype=np.int16)
+                mem.d2h(packed, d_tracks)
+            finally:
+                mem.dev_free(d_tracks)
+            packed = packed.reshape(-1, batch.channels)
+            info = np.zeros(n, dtype=np.dtype(FILE_INFO_DTYPE.descr + [("final_status", "<i4"), ("bad_packet", "<i4")]))
+            for name in FILE_INFO_DTYPE.names:
+                info[name] = batch.info[name]
+            info["track_samples"], info["final_status"], info["bad_packet"] = lengths, status[:, 0], status[:, 1]
+            tracks = [packed[o:o + ln] for o, ln in zip(batch.info["track_offset"], lengths)]
+            return tracks, info
+        finally:
+            mem.close()
+            if own:
+                batch.close()
 
 
 TOC_CELT_FB_STEREO = 0xFC

@@ -6,6 +6,8 @@
 // split every packet into frames, keep the frames' bytes and placements in a per-file plan; (2) sequential and cheap: track
 // offsets, arena offsets, per-step (and per-key) slot numbering in file order; (3) per file, in parallel: copy the bytes into the
 // arena and write descriptors and segments into their slots.
+// opusgpu_ms_files_plan (WHOLE FILES / MULTISTREAM) is the same three passes and the same reader loop; its frames are rows of
+// `streams` descriptors, framed by opusgpu_ms_packet_to_frames.
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
@@ -20,7 +22,7 @@
 namespace {
 
 struct FramePlan {
-    int32_t offset, len, flags; // offset: into the file's own bytes (FilePlan::bytes)
+    int32_t flags; // of the frame's first descriptor
     int32_t src_first, count, packet_seq;
     int64_t dst_rel; // position in the track
     uint8_t key;     // sort key within a step (0 without grouping)
@@ -29,6 +31,7 @@ struct FramePlan {
 
 struct FilePlan {
     std::vector<FramePlan> frames;
+    std::vector<opusgpu_frame_desc> descs; // `width` per frame (1, or the layout's streams); offsets into the file's own bytes
     std::vector<uint8_t> bytes;
     std::vector<int64_t> packet_start; // packets + 1 entries: the last one is the track length
 };
@@ -49,22 +52,28 @@ void parallel_for(int n, int threads, F f) { // f(begin, end)
     for (auto &x : th) x.join();
 }
 
-// One file through the reader.  Returns the status; `fp` holds whatever was planned before a failure.
-int plan_file(const uint8_t *data, size_t len, int channels, int mode, int flags, opusgpu_file_info &fi, FilePlan &fp) {
-    ogc::OpusFile of(data, len);
+// Opens the file and reports its OpusHead.  Returns the reader's code (OP_EIMPL as OPUSGPU_UNIMPLEMENTED).
+int open_file(ogc::OpusFile &of, opusgpu_file_info &fi) {
     const int r = of.open();
     const ogc::Head &h = of.head();
     fi.channels = h.channel_count, fi.pre_skip = (int32_t)h.pre_skip, fi.output_gain = h.output_gain, fi.mapping_family = h.mapping_family;
+    return r == ogc::OP_EIMPL ? OPUSGPU_UNIMPLEMENTED : r;
+}
+
+int refuse(opusgpu_file_info &fi, FilePlan &fp, int code) {
+    fp = FilePlan();
     fp.packet_start.assign(1, 0);
-    if (r < 0) return r == ogc::OP_EIMPL ? OPUSGPU_UNIMPLEMENTED : r;
-    if (h.mapping_family != 0) return OPUSGPU_UNIMPLEMENTED;
-    if (h.channel_count != channels) return OPUSGPU_BAD_ARG;
-    const bool rfc = mode == OPUSGPU_MODE_RFC;
-    const bool by_header = (flags & OPUSGPU_PAGES_ORDER_BY_HEADER) != 0;
-    const bool group = by_header || (flags & OPUSGPU_PAGES_GROUP_BY_MODE) != 0;
+    fi.packets = fi.frames = 0;
+    return code;
+}
+
+// An open file through the reader, the loop both planners share.  split(packet, base, fr, &spf) frames one packet whose bytes will
+// lie at `base` of fp.bytes: it appends the descriptors of the packet's frames to fp.descs, frame after frame, fills flags, key
+// and kept of fr[0 .. count) and returns the frame count and the frames' duration -- or OPUSGPU_UNIMPLEMENTED, which refuses the
+// file, or another negative code, which ends the plan there.  Returns the status; `fp` holds whatever was planned before a failure.
+template <class Split>
+int plan_packets(ogc::OpusFile &of, bool rfc, opusgpu_file_info &fi, FilePlan &fp, Split split) {
     int64_t pos = 0; // samples of the track so far
-    int first_mode = -1;
-    bool kept = true;
     int status = 0;
     for (;;) {
         ogc::OpusFile::Planned pl;
@@ -79,37 +88,67 @@ int plan_file(const uint8_t *data, size_t len, int channels, int mode, int flags
             break;
         }
         const std::vector<uint8_t> &pk = pl.pkt->data;
-        int16_t size[48];
-        uint8_t toc;
-        int off = 0;
-        const int count = ogh::parse_packet(pk.data(), (int32_t)pk.size(), 0, &toc, size, &off, nullptr);
-        if (count < 0) { // (the reader's decode callback fails here)
-            status = ogc::OP_EBADPACKET;
+        FramePlan fr[48];
+        int spf = 0;
+        const size_t n_descs = fp.descs.size();
+        const int count = split(pk, (int32_t)fp.bytes.size(), fr, &spf);
+        if (count < 0 && count != OPUSGPU_UNIMPLEMENTED) { // (the reader's decode callback fails here)
+            fp.descs.resize(n_descs);
+            status = count;
             break;
         }
-        const int spf = ogh::toc_samples_per_frame(toc, 48000);
-        if (!rfc && spf != OPUSGPU_FRAME_SAMPLES) { // reference mode decodes every frame as 960 samples (Q6): refused, see the header
-            fp = FilePlan();
-            fp.packet_start.assign(1, 0);
-            fi.packets = fi.frames = 0;
-            return OPUSGPU_UNIMPLEMENTED;
-        }
-        const int32_t fl = rfc ? ogh::toc_flags_rfc(toc) : ogh::toc_flags(toc);
-        const int m = fl & 3;
-        if (first_mode < 0) first_mode = m;
-        if (m != first_mode) kept = false;
-        const int32_t base = (int32_t)fp.bytes.size();
+        // reference mode decodes every frame as 960 samples (Q6): refused, see the header
+        if (count < 0 || (!rfc && spf != OPUSGPU_FRAME_SAMPLES)) return refuse(fi, fp, OPUSGPU_UNIMPLEMENTED);
         fp.bytes.insert(fp.bytes.end(), pk.begin(), pk.end());
         for (int k = 0; k < count; k++) { // the packet's PCM is its frames' back to back; samples [skip, trimmed) are kept
             const int lo = k * spf, hi = lo + spf;
             const int a = lo > pl.skip ? lo : pl.skip, b = hi < pl.trimmed ? hi : pl.trimmed;
-            FramePlan f;
-            f.offset = base + off, f.len = size[k], f.flags = fl;
+            FramePlan &f = fr[k];
             f.count = b > a ? b - a : 0;
             f.src_first = f.count ? a - lo : 0;
             f.dst_rel = pos + (f.count ? a - pl.skip : 0);
             f.packet_seq = fi.packets;
-            f.kept = kept;
+            fp.frames.push_back(f);
+        }
+        of.commit(pl);
+        pos += pl.trimmed > pl.skip ? pl.trimmed - pl.skip : 0;
+        fp.packet_start.push_back(pos);
+        fi.packets++;
+        if (fp.bytes.size() > 0x7fffffffu || fp.descs.size() > 0x3fffffffu) { // (one file: 32-bit offsets)
+            status = OPUSGPU_ALLOC_FAIL;
+            break;
+        }
+    }
+    fi.frames = (int32_t)fp.frames.size();
+    return status;
+}
+
+// One stereo or mono file (opusgpu_files_plan).
+int plan_file(const uint8_t *data, size_t len, int channels, int mode, int flags, opusgpu_file_info &fi, FilePlan &fp) {
+    ogc::OpusFile of(data, len);
+    fp.packet_start.assign(1, 0);
+    const int r = open_file(of, fi);
+    if (r < 0) return r;
+    if (fi.mapping_family != 0) return OPUSGPU_UNIMPLEMENTED;
+    if (fi.channels != channels) return OPUSGPU_BAD_ARG;
+    const bool rfc = mode == OPUSGPU_MODE_RFC;
+    const bool by_header = (flags & OPUSGPU_PAGES_ORDER_BY_HEADER) != 0;
+    const bool group = by_header || (flags & OPUSGPU_PAGES_GROUP_BY_MODE) != 0;
+    int first_mode = -1;
+    bool kept = true;
+    return plan_packets(of, rfc, fi, fp, [&](const std::vector<uint8_t> &pk, int32_t base, FramePlan *fr, int *spf) {
+        int16_t size[48];
+        uint8_t toc;
+        int off = 0;
+        const int count = ogh::parse_packet(pk.data(), (int32_t)pk.size(), 0, &toc, size, &off, nullptr);
+        if (count < 0) return (int)ogc::OP_EBADPACKET;
+        *spf = ogh::toc_samples_per_frame(toc, 48000);
+        const int32_t fl = rfc ? ogh::toc_flags_rfc(toc) : ogh::toc_flags(toc);
+        const int m = fl & 3;
+        if (first_mode < 0) first_mode = m;
+        if (m != first_mode) kept = false;
+        for (int k = 0; k < count; k++) {
+            fp.descs.push_back(opusgpu_frame_desc{0, base + off, size[k], fl});
             int key = 0;
             if (by_header) { // og_pages.cpp: SILK 0..3 and hybrid 4..7 by the LBRR flags, CELT 8
                 key = m == 2 ? 8 : 4 * m;
@@ -119,31 +158,57 @@ int plan_file(const uint8_t *data, size_t len, int channels, int mode, int flags
                 }
             } else if (group)
                 key = m;
-            f.key = (uint8_t)key;
-            fp.frames.push_back(f);
+            fr[k].flags = fl, fr[k].key = (uint8_t)key, fr[k].kept = kept;
             off += size[k];
         }
-        of.commit(pl);
-        pos += pl.trimmed > pl.skip ? pl.trimmed - pl.skip : 0;
-        fp.packet_start.push_back(pos);
-        fi.packets++;
-        if (fp.bytes.size() > 0x7fffffffu || fp.frames.size() > 0x3fffffffu) { // (one file: 32-bit offsets)
-            status = OPUSGPU_ALLOC_FAIL;
-            break;
+        return count;
+    });
+}
+
+bool same_layout(const ogc::Head &h, const opusgpu_ms_layout &l) {
+    return h.channel_count == l.channels && h.stream_count == l.streams && h.coupled_count == l.coupled &&
+           memcmp(h.mapping, l.mapping, (size_t)h.channel_count) == 0;
+}
+
+// One file of the batch's layout (opusgpu_ms_files_plan): a frame is a row of `streams` descriptors.
+int plan_ms_file(const uint8_t *data, size_t len, const opusgpu_ms_layout &lay, int mode, opusgpu_file_info &fi, FilePlan &fp) {
+    ogc::OpusFile of(data, len);
+    fp.packet_start.assign(1, 0);
+    const int r = open_file(of, fi);
+    if (r < 0) return r;
+    if (!same_layout(of.head(), lay)) return OPUSGPU_BAD_ARG;
+    const bool rfc = mode == OPUSGPU_MODE_RFC;
+    const int S = lay.streams;
+    std::vector<opusgpu_frame_desc> el((size_t)S * 48);
+    std::vector<int32_t> cnt((size_t)S);
+    return plan_packets(of, rfc, fi, fp, [&](const std::vector<uint8_t> &pk, int32_t base, FramePlan *fr, int *spf) {
+        if (opusgpu_ms_packet_to_frames(&lay, pk.data(), (int32_t)pk.size(), 0, mode, el.data(), cnt.data()) < 0)
+            return (int)ogc::OP_EBADPACKET;
+        *spf = ogh::toc_samples_per_frame(pk[0], 48000); // the reader's own view of the packet: elementary stream 0's TOC
+        // the device step takes rows of one duration (RFC mode; reference mode's framing has refused unequal counts already)
+        for (int s = 1; s < S; s++)
+            if (cnt[s] != cnt[0] || ((el[(size_t)s * 48].flags ^ el[0].flags) & (7 << 6))) return OPUSGPU_UNIMPLEMENTED;
+        for (int k = 0; k < cnt[0]; k++) {
+            for (int s = 0; s < S; s++) {
+                opusgpu_frame_desc d = el[(size_t)s * 48 + k];
+                d.offset += base;
+                fp.descs.push_back(d);
+            }
+            fr[k].flags = el[k].flags, fr[k].key = 0, fr[k].kept = 1;
         }
-    }
-    fi.frames = (int32_t)fp.frames.size();
-    return status;
+        return (int)cnt[0];
+    });
 }
 
 } // namespace
 
-struct opusgpu_file_batch {
-    int n_files = 0, channels = 0, mode = 0;
-    std::vector<opusgpu_frame_desc> descs; // all steps, step after step
-    std::vector<opusgpu_track_seg> segs;   // parallel to descs
-    std::vector<int32_t> slot_files;       // parallel to descs
-    std::vector<size_t> step_begin;        // n_steps + 1
+// What both kinds of batch hold.  A slot is one frame of one file: `width` descriptors and one segment.
+struct og_batch {
+    int n_files = 0, channels = 0, mode = 0, width = 1;
+    std::vector<opusgpu_frame_desc> descs; // all steps, step after step, `width` per slot
+    std::vector<opusgpu_track_seg> segs;   // one per slot
+    std::vector<int32_t> slot_files;       // one per slot
+    std::vector<size_t> step_begin;        // n_steps + 1, in slots
     std::vector<int32_t> step_modes;
     std::vector<uint8_t> arena;
     std::vector<opusgpu_file_info> info;
@@ -151,39 +216,33 @@ struct opusgpu_file_batch {
     std::vector<size_t> packet_begin;  // n_files + 1
     int64_t track_samples = 0;
 };
+struct opusgpu_file_batch : og_batch {};
+struct opusgpu_ms_file_batch : og_batch {
+    opusgpu_ms_layout layout{};
+};
 
-extern "C" {
+namespace {
 
-int opusgpu_files_plan(int n_files, const uint8_t *const *files, const int64_t *file_lens, int channels, int mode, int flags,
-                       int threads, opusgpu_file_info *info, opusgpu_file_batch **out) {
-    if (!out) return OPUSGPU_BAD_ARG;
-    *out = nullptr;
-    if (n_files < 0 || (n_files > 0 && (!files || !file_lens)) || (channels != 1 && channels != 2) ||
-        (mode != OPUSGPU_MODE_REFERENCE && mode != OPUSGPU_MODE_RFC) ||
-        (flags & ~(OPUSGPU_PAGES_GROUP_BY_MODE | OPUSGPU_PAGES_ORDER_BY_HEADER)))
-        return OPUSGPU_BAD_ARG;
-    for (int i = 0; i < n_files; i++)
-        if (file_lens[i] < 0 || (file_lens[i] > 0 && !files[i])) return OPUSGPU_BAD_ARG;
-    opusgpu_file_batch *b = nullptr;
+// Passes 1 to 3 over a new batch `b` (n_files, width and mode set): plan(i, info, file plan) is pass 1 for file i; G sort keys.
+// Returns OPUSGPU_OK, OPUSGPU_BAD_ARG (32-bit offsets exceeded) or OPUSGPU_ALLOC_FAIL.
+template <class Plan>
+int build_batch(og_batch *b, int threads, int G, opusgpu_file_info *info, Plan plan) {
+    const int n_files = b->n_files;
+    const size_t W = (size_t)b->width;
     try {
-        b = new opusgpu_file_batch;
-        b->n_files = n_files, b->channels = channels, b->mode = mode;
         b->info.assign((size_t)n_files, opusgpu_file_info{});
         std::vector<FilePlan> plans((size_t)n_files);
         std::atomic<bool> oom{false};
         // pass 1: the reader over every file
         parallel_for(n_files, threads, [&](int lo, int hi) {
             try {
-                for (int i = lo; i < hi; i++)
-                    b->info[i].status = plan_file(files[i], (size_t)file_lens[i], channels, mode, flags, b->info[i], plans[i]);
+                for (int i = lo; i < hi; i++) b->info[i].status = plan(i, b->info[i], plans[i]);
             } catch (const std::bad_alloc &) {
                 oom = true;
             }
         });
         if (oom) throw std::bad_alloc();
         // pass 2: tracks, arena, steps
-        const bool by_header = (flags & OPUSGPU_PAGES_ORDER_BY_HEADER) != 0;
-        const int G = by_header ? 9 : (flags & OPUSGPU_PAGES_GROUP_BY_MODE) ? 3 : 1;
         std::vector<size_t> arena_at((size_t)n_files + 1, 0);
         b->packet_begin.assign((size_t)n_files + 1, 0);
         size_t n_steps = 0, total = 0;
@@ -199,10 +258,7 @@ int opusgpu_files_plan(int n_files, const uint8_t *const *files, const int64_t *
             total += plans[i].frames.size();
         }
         b->track_samples = at;
-        if (arena_at[n_files] > 0x7fffffffu || total > 0x7fffffffu) { // descriptor offsets and slots are 32-bit: split the call
-            delete b;
-            return OPUSGPU_BAD_ARG;
-        }
+        if (arena_at[n_files] > 0x7fffffffu || total * W > 0x7fffffffu) return OPUSGPU_BAD_ARG; // descriptor offsets and slots are 32-bit: split the call
         // a counting sort of the frames by (step, key), stable in file order
         std::vector<size_t> cur(n_steps * G + 1, 0);
         for (int i = 0; i < n_files; i++)
@@ -225,7 +281,7 @@ int opusgpu_files_plan(int n_files, const uint8_t *const *files, const int64_t *
         for (size_t s = 0; s < n_steps; s++)
             if (!step_broken[s]) b->step_modes[s] |= OPUSGPU_STEP_KEEPS_MODE;
         // pass 3: bytes, descriptors, segments
-        b->descs.resize(total);
+        b->descs.resize(total * W);
         b->segs.resize(total);
         b->slot_files.resize(total);
         b->arena.assign(arena_at[n_files] + 16, 0); // the kernels fetch packets as aligned 16-byte pieces: keep a tail
@@ -238,7 +294,10 @@ int opusgpu_files_plan(int n_files, const uint8_t *const *files, const int64_t *
                 for (size_t k = 0; k < fp.frames.size(); k++) {
                     const FramePlan &f = fp.frames[k];
                     const size_t slot = slot_of[i][k];
-                    b->descs[slot] = opusgpu_frame_desc{i, (int32_t)(arena_at[i] + (size_t)f.offset), f.len, f.flags};
+                    for (size_t w = 0; w < W; w++) {
+                        const opusgpu_frame_desc &d = fp.descs[k * W + w];
+                        b->descs[slot * W + w] = opusgpu_frame_desc{i, (int32_t)(arena_at[i] + (size_t)d.offset), d.len, d.flags};
+                    }
                     opusgpu_track_seg &sg = b->segs[slot];
                     sg.slot = (int32_t)(slot - b->step_begin[k]);
                     sg.src_first = f.src_first, sg.count = f.count, sg.track = i;
@@ -249,48 +308,88 @@ int opusgpu_files_plan(int n_files, const uint8_t *const *files, const int64_t *
             }
         });
         if (info && n_files) memcpy(info, b->info.data(), sizeof(opusgpu_file_info) * (size_t)n_files);
-        *out = b;
         return OPUSGPU_OK;
     } catch (const std::bad_alloc &) {
-        delete b;
         return OPUSGPU_ALLOC_FAIL;
     }
 }
 
-int opusgpu_file_batch_steps(const opusgpu_file_batch *b) { return b ? (int)b->step_begin.size() - 1 : OPUSGPU_BAD_ARG; }
+bool files_ok(int n_files, const uint8_t *const *files, const int64_t *file_lens) {
+    if (n_files < 0 || (n_files > 0 && (!files || !file_lens))) return false;
+    for (int i = 0; i < n_files; i++)
+        if (file_lens[i] < 0 || (file_lens[i] > 0 && !files[i])) return false;
+    return true;
+}
 
-int opusgpu_file_batch_step(const opusgpu_file_batch *b, int step, const opusgpu_frame_desc **descs, const int32_t **slot_files,
-                            int *modes) {
+int batch_step(const og_batch *b, int step, const opusgpu_frame_desc **descs, const int32_t **slot_files, int *modes) {
     if (!b || step < 0 || step + 1 >= (int)b->step_begin.size()) return OPUSGPU_BAD_ARG;
     const size_t at = b->step_begin[step];
-    if (descs) *descs = b->descs.data() + at;
+    if (descs) *descs = b->descs.data() + at * (size_t)b->width;
     if (slot_files) *slot_files = b->slot_files.data() + at;
     if (modes) *modes = b->step_modes[step];
     return (int)(b->step_begin[step + 1] - at);
 }
 
-int opusgpu_file_batch_segments(const opusgpu_file_batch *b, int step, const opusgpu_track_seg **segs) {
+int batch_segments(const og_batch *b, int step, const opusgpu_track_seg **segs) {
     if (!b || step < 0 || step + 1 >= (int)b->step_begin.size()) return OPUSGPU_BAD_ARG;
     const size_t at = b->step_begin[step];
     if (segs) *segs = b->segs.data() + at;
     return (int)(b->step_begin[step + 1] - at);
 }
 
-const uint8_t *opusgpu_file_batch_arena(const opusgpu_file_batch *b, size_t *bytes) {
+const uint8_t *batch_arena(const og_batch *b, size_t *bytes) {
     if (!b) return nullptr;
     if (bytes) *bytes = b->arena.size();
     return b->arena.data();
 }
 
-int64_t opusgpu_file_batch_track_samples(const opusgpu_file_batch *b) { return b ? b->track_samples : -1; }
-
-int64_t opusgpu_file_batch_packet_start(const opusgpu_file_batch *b, int file, int packet_seq) {
+int64_t batch_packet_start(const og_batch *b, int file, int packet_seq) {
     if (!b || file < 0 || file >= b->n_files || packet_seq < 0) return -1;
     const size_t lo = b->packet_begin[file], hi = b->packet_begin[file + 1];
     if ((size_t)packet_seq >= hi - lo) return -1;
     return b->packet_start[lo + (size_t)packet_seq];
 }
 
+} // namespace
+
+extern "C" {
+
+int opusgpu_files_plan(int n_files, const uint8_t *const *files, const int64_t *file_lens, int channels, int mode, int flags,
+                       int threads, opusgpu_file_info *info, opusgpu_file_batch **out) {
+    if (!out) return OPUSGPU_BAD_ARG;
+    *out = nullptr;
+    if (!files_ok(n_files, files, file_lens) || (channels != 1 && channels != 2) ||
+        (mode != OPUSGPU_MODE_REFERENCE && mode != OPUSGPU_MODE_RFC) ||
+        (flags & ~(OPUSGPU_PAGES_GROUP_BY_MODE | OPUSGPU_PAGES_ORDER_BY_HEADER)))
+        return OPUSGPU_BAD_ARG;
+    opusgpu_file_batch *b = new (std::nothrow) opusgpu_file_batch;
+    if (!b) return OPUSGPU_ALLOC_FAIL;
+    b->n_files = n_files, b->channels = channels, b->mode = mode;
+    const int G = (flags & OPUSGPU_PAGES_ORDER_BY_HEADER) ? 9 : (flags & OPUSGPU_PAGES_GROUP_BY_MODE) ? 3 : 1;
+    const int rc = build_batch(b, threads, G, info, [&](int i, opusgpu_file_info &fi, FilePlan &fp) {
+        return plan_file(files[i], (size_t)file_lens[i], channels, mode, flags, fi, fp);
+    });
+    if (rc) {
+        delete b;
+        return rc;
+    }
+    *out = b;
+    return OPUSGPU_OK;
+}
+
+int opusgpu_file_batch_steps(const opusgpu_file_batch *b) { return b ? (int)b->step_begin.size() - 1 : OPUSGPU_BAD_ARG; }
+int opusgpu_file_batch_step(const opusgpu_file_batch *b, int step, const opusgpu_frame_desc **descs, const int32_t **slot_files,
+                            int *modes) {
+    return batch_step(b, step, descs, slot_files, modes);
+}
+int opusgpu_file_batch_segments(const opusgpu_file_batch *b, int step, const opusgpu_track_seg **segs) {
+    return batch_segments(b, step, segs);
+}
+const uint8_t *opusgpu_file_batch_arena(const opusgpu_file_batch *b, size_t *bytes) { return batch_arena(b, bytes); }
+int64_t opusgpu_file_batch_track_samples(const opusgpu_file_batch *b) { return b ? b->track_samples : -1; }
+int64_t opusgpu_file_batch_packet_start(const opusgpu_file_batch *b, int file, int packet_seq) {
+    return batch_packet_start(b, file, packet_seq);
+}
 void opusgpu_file_batch_free(opusgpu_file_batch *b) { delete b; }
 
 // (for opusgpu_files_decode, which lives with the kernels: csrc/og_tracks.hpp)
@@ -300,5 +399,76 @@ int og_file_batch_shape(const opusgpu_file_batch *b, int *n_files, int *channels
     return OPUSGPU_OK;
 }
 const opusgpu_file_info *og_file_batch_info(const opusgpu_file_batch *b) { return b ? b->info.data() : nullptr; }
+
+// ---- multistream files (include/opusgpu.h, WHOLE FILES / MULTISTREAM) ------------------------------------------------------
+int opusgpu_file_layout(const uint8_t *file, int64_t len, opusgpu_ms_layout *layout, opusgpu_file_info *info) {
+    if (!layout || len < 0 || (len > 0 && !file)) return OPUSGPU_BAD_ARG;
+    opusgpu_file_info fi{};
+    int r = OPUSGPU_ALLOC_FAIL;
+    try {
+        ogc::OpusFile of(file, (size_t)len);
+        r = open_file(of, fi);
+        if (r >= 0) {
+            const ogc::Head &h = of.head();
+            r = OPUSGPU_OK;
+            layout->channels = h.channel_count, layout->streams = h.stream_count, layout->coupled = h.coupled_count;
+            memset(layout->mapping, 255, sizeof layout->mapping);
+            memcpy(layout->mapping, h.mapping, (size_t)h.channel_count);
+        }
+    } catch (const std::bad_alloc &) {
+    }
+    fi.status = r;
+    if (info) *info = fi;
+    return r;
+}
+
+int opusgpu_ms_files_plan(int n_files, const uint8_t *const *files, const int64_t *file_lens, const opusgpu_ms_layout *layout,
+                          int mode, int threads, opusgpu_file_info *info, opusgpu_ms_file_batch **out) {
+    if (!out) return OPUSGPU_BAD_ARG;
+    *out = nullptr;
+    if (!files_ok(n_files, files, file_lens) || !layout || (mode != OPUSGPU_MODE_REFERENCE && mode != OPUSGPU_MODE_RFC))
+        return OPUSGPU_BAD_ARG;
+    // the layout checks are the multistream decoder's own: its framing answers OPUSGPU_BAD_ARG for a layout it would not take
+    // (and OPUSGPU_INVALID_PACKET for this packet of no bytes otherwise)
+    opusgpu_frame_desc none;
+    int32_t count;
+    if (opusgpu_ms_packet_to_frames(layout, (const uint8_t *)"", 0, 0, mode, &none, &count) == OPUSGPU_BAD_ARG) return OPUSGPU_BAD_ARG;
+    opusgpu_ms_file_batch *b = new (std::nothrow) opusgpu_ms_file_batch;
+    if (!b) return OPUSGPU_ALLOC_FAIL;
+    b->n_files = n_files, b->channels = layout->channels, b->mode = mode, b->width = layout->streams;
+    b->layout = *layout;
+    for (int c = layout->channels; c < 256; c++) b->layout.mapping[c] = 255;
+    const int rc = build_batch(b, threads, 1, info, [&](int i, opusgpu_file_info &fi, FilePlan &fp) {
+        return plan_ms_file(files[i], (size_t)file_lens[i], b->layout, mode, fi, fp);
+    });
+    if (rc) {
+        delete b;
+        return rc;
+    }
+    *out = b;
+    return OPUSGPU_OK;
+}
+
+int opusgpu_ms_file_batch_steps(const opusgpu_ms_file_batch *b) { return b ? (int)b->step_begin.size() - 1 : OPUSGPU_BAD_ARG; }
+int opusgpu_ms_file_batch_step(const opusgpu_ms_file_batch *b, int step, const opusgpu_frame_desc **descs, const int32_t **slot_files) {
+    return batch_step(b, step, descs, slot_files, nullptr);
+}
+int opusgpu_ms_file_batch_segments(const opusgpu_ms_file_batch *b, int step, const opusgpu_track_seg **segs) {
+    return batch_segments(b, step, segs);
+}
+const uint8_t *opusgpu_ms_file_batch_arena(const opusgpu_ms_file_batch *b, size_t *bytes) { return batch_arena(b, bytes); }
+int64_t opusgpu_ms_file_batch_track_samples(const opusgpu_ms_file_batch *b) { return b ? b->track_samples : -1; }
+int64_t opusgpu_ms_file_batch_packet_start(const opusgpu_ms_file_batch *b, int file, int packet_seq) {
+    return batch_packet_start(b, file, packet_seq);
+}
+void opusgpu_ms_file_batch_free(opusgpu_ms_file_batch *b) { delete b; }
+
+// (for opusgpu_ms_files_decode: csrc/og_ms_tracks.hpp)
+int og_ms_file_batch_shape(const opusgpu_ms_file_batch *b, int *n_files, const opusgpu_ms_layout **layout, int *mode) {
+    if (!b) return OPUSGPU_BAD_ARG;
+    *n_files = b->n_files, *layout = &b->layout, *mode = b->mode;
+    return OPUSGPU_OK;
+}
+const opusgpu_file_info *og_ms_file_batch_info(const opusgpu_ms_file_batch *b) { return b ? b->info.data() : nullptr; }
 
 } // extern "C"

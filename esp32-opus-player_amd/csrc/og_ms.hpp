@@ -360,8 +360,10 @@ int opusgpu_ms_reset(opusgpu_ms *ms, int first, int count, int full) {
 }
 
 // One device step of n rows (include/opusgpu.h).  Stereo half on the step's stream, mono half on the mono context's stream next to
-// it, the mapping behind both on the step's stream.
-static int ms_step_impl(opusgpu_ms *ms, int n, const void *d_descs, const void *d_arena, void *d_pcm, void *d_result, hipStream_t s) {
+// it, the mapping behind both on the step's stream.  map == false: the step ends behind both halves, with the elementary PCM and
+// results in d_pc / d_pm / d_rc / d_rm for whoever is queued on `s` next (og_ms_tracks.hpp); d_pcm and d_result are not used.
+static int ms_step_impl(opusgpu_ms *ms, int n, const void *d_descs, const void *d_arena, void *d_pcm, void *d_result, hipStream_t s,
+                        bool map) {
     const opusgpu_ms_layout &L = ms->lay;
     const int C2 = L.coupled, M = ms->mono;
     const bool rfc = ms->mode == OPUSGPU_MODE_RFC;
@@ -390,6 +392,7 @@ static int ms_step_impl(opusgpu_ms *ms, int n, const void *d_descs, const void *
         MSCHK(ms, hipEventRecord(ms->ev_mono, ms->cm->stream));
         MSCHK(ms, hipStreamWaitEvent(s, ms->ev_mono, 0));
     }
+    if (!map) return OPUSGPU_OK;
     return ms_launch_map(ms, s, n, ms->d_pc, fr * 2, ms->d_pm, fr, ms->d_rc, ms->d_rm, fr, d_pcm, (long long)fr * L.channels, d_result);
 }
 
@@ -410,7 +413,7 @@ int opusgpu_ms_decode_step_device(opusgpu_ms *ms, int n, const void *d_descs, co
     if ((long long)n * ms->lay.streams > 0x7fffffff) return OPUSGPU_BAD_ARG;
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ms->stream;
     if (int rc = ms_enter(ms, s)) return rc;
-    return ms_step_impl(ms, n, d_descs, d_arena, d_pcm, d_result, s);
+    return ms_step_impl(ms, n, d_descs, d_arena, d_pcm, d_result, s, true);
 }
 
 int opusgpu_ms_synchronize(opusgpu_ms *ms) {

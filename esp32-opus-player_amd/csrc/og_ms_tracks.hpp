@@ -1,0 +1,308 @@
+// og_ms_tracks.hpp -- whole multistream files (include/opusgpu.h, WHOLE FILES / MULTISTREAM): the kernel that maps channels and
+// assembles tracks in one pass, and the call that drives a planned batch (og_files.cpp) through the ms steps.  Included at the end
+// of og_api.hip behind og_ms.hpp (opusgpu_ms, ms_step_impl) and og_tracks.hpp (TrackSeg, TrackState).
+#pragma once
+
+// ---- kernel -------------------------------------------------------------------------------------------
+// k_ms_tracks_assemble: k_ms_map and k_tracks_assemble in one, one workgroup per segment.  An ms step that ends in k_ms_map writes
+// [rows][row_samples * channels] interleaved PCM which k_tracks_assemble would read back only to copy most of it once more; here
+// the samples go from the two contexts' PCM -- stereo [rows * coupled][row_samples * 2], mono [rows * mono][row_samples] -- to
+// their place in the track directly.
+// The work is split by DESTINATION, as in k_tracks_assemble: lane q owns the q-th aligned 16-byte piece of the track buffer that
+// the segment touches -- 8 consecutive int16 of the interleaved track -- composes it and stores it whole; only the segment's first
+// and last piece, where it covers them in part, go out as 16-bit stores.  The sources come into LDS first, as in k_ms_map: of every
+// elementary stream the mapping uses, the aligned 16-byte pieces that hold a sample the tile needs (stereo streams as they are, L/R
+// interleaved; mono streams after them); the tile's first LDS sample is the source sample `A`, src_first rounded down to 8, so
+// that every stream's pieces are aligned in HBM and in LDS alike.  A tile is PT destination pieces and the (at most TS) source
+// samples they take; a 20 ms row of 8 channels is one tile, a 2,880-sample row of 8 channels three.
+// lut[c] = LDS index of output channel c's sample A, times 2, plus 1 for a mono source (step 1 instead of 2); -1: muted.
+struct MsTrackArgs {
+    int n_stereo, n_mono; // the elementary streams that are staged: those the mapping uses, stereo ones first
+    unsigned long long row_of; // byte j: which of its decoder's coupled (j < n_stereo) or mono streams staged stream j is -- packed, so
+                               // that a lane gets at it with a shift: a table lookup would be a load in front of every PCM load
+    int lut[8];           // output channel c: -1 muted, else (decoded channels staged before its stream) << 2 | right << 1 | mono
+};
+template <int CH>
+__global__ void __launch_bounds__(256) k_ms_tracks_assemble(const TrackSeg *__restrict__ segs, const i16 *__restrict__ pc,
+                                                             const i16 *__restrict__ pm, int row_samples, const i32 *__restrict__ rc,
+                                                             const i32 *__restrict__ rm, int streams, int coupled, MsTrackArgs a, int TS,
+                                                             i16 *__restrict__ tracks, TrackState *__restrict__ state) {
+    extern __shared__ __align__(16) i16 lds[]; // [TS * staged decoded channels] samples, then the channel table
+    const TrackSeg sg = segs[blockIdx.x];
+    const int tid = (int)threadIdx.x;
+    const int mono = streams - coupled;
+    // the row's result as k_ms_map forms it: the first negative elementary result in stream order, else the common count
+    i32 res = 0;
+    for (int s = 0; s < streams; s++) {
+        const i32 v = s < coupled ? rc[(size_t)sg.slot * coupled + s] : rm[(size_t)sg.slot * mono + (s - coupled)];
+        if (s == 0 || v < 0) res = v;
+        if (v < 0) break;
+        if (v != res) {
+            res = OPUSGPU_INTERNAL_ERROR;
+            break;
+        }
+    }
+    if (res < 0) { // a failed row: nothing is written, the track ends at its packet (k_tracks_assemble's protocol)
+        if (tid == 0) {
+            const i32 old = atomicMin(&state[sg.track].first_bad, sg.packet_seq);
+            if (sg.packet_seq < old) state[sg.track].code = res;
+        }
+        return;
+    }
+    if (sg.packet_seq >= state[sg.track].first_bad) return;
+    if (sg.count <= 0 || sg.src_first < 0 || sg.src_first + sg.count > row_samples) return;
+    const int D = 2 * a.n_stereo + a.n_mono;
+    int *lut = reinterpret_cast<int *>(lds + (size_t)TS * D);
+    if (tid < CH) {
+        const int m = a.lut[tid];
+        lut[tid] = m < 0 ? -1 : (((m >> 2) * TS + ((m >> 1) & 1)) << 1) | (m & 1);
+    }
+    // the segment in the track buffer, in int16 elements: pieces of 8
+    const long long E0 = sg.dst_first * CH;
+    const int EN = sg.count * CH;
+    const long long c0 = E0 >> 3;
+    const int lead = (int)(E0 - (c0 << 3)); // elements of the first piece that lie in front of the segment
+    const int pieces = (lead + EN + 7) >> 3;
+    const int PT = (TS - 8) * CH / 8; // pieces per tile: they take at most TS - 8 source samples, and up to 7 lie between A and the first
+    const int cnt1 = sg.count - 1;
+    for (int p0 = 0; p0 < pieces; p0 += PT) {
+        const int p1 = p0 + PT < pieces ? p0 + PT : pieces;
+        // the samples of the segment that pieces [p0, p1) hold
+        const int j_lo = (p0 * 8 > lead ? p0 * 8 - lead : 0) / CH;
+        const int j_end = (p1 * 8 - lead - 1) / CH;
+        const int j_hi = j_end < cnt1 ? j_end : cnt1;
+        const int lo = sg.src_first + j_lo;
+        const int A = lo & ~7;
+        const int n = sg.src_first + j_hi + 1 - A; // source samples [A, A + n), n <= TS
+        // 1. sources of the tile -> LDS, 16 bytes per lane and load; no piece without a sample of [lo, A + n) is fetched
+        const int pc_pieces = (n + 3) >> 2, pm_pieces = (n + 7) >> 3; // per stereo / mono stream
+        const int pc_skip = (lo - A) >> 2;
+        const int all = a.n_stereo * pc_pieces + a.n_mono * pm_pieces;
+        for (int q = tid; q < all; q += 256) {
+            uint4 v;
+            int at;
+            if (q < a.n_stereo * pc_pieces) {
+                const int j = q / pc_pieces, w = q - j * pc_pieces;
+                if (w < pc_skip) continue;
+                v = reinterpret_cast<const uint4 *>(pc + ((size_t)sg.slot * coupled + ((a.row_of >> (8 * j)) & 255)) * row_samples * 2 + (size_t)A * 2)[w];
+                at = j * 2 * TS + w * 8;
+            } else {
+                const int q2 = q - a.n_stereo * pc_pieces;
+                const int j = q2 / pm_pieces, w = q2 - j * pm_pieces;
+                v = reinterpret_cast<const uint4 *>(pm + ((size_t)sg.slot * mono + ((a.row_of >> (8 * (a.n_stereo + j))) & 255)) * row_samples + A)[w];
+                at = (2 * a.n_stereo + j) * TS + w * 8;
+            }
+            *reinterpret_cast<uint4 *>(lds + at) = v;
+        }
+        __syncthreads();
+        // 2. LDS -> the track, 8 interleaved int16 (16 bytes) per lane and store
+        const int off = sg.src_first - A;
+        for (int q = p0 + tid; q < p1; q += 256) {
+            const int r0 = q * 8 - lead;           // the piece's first element, counted from the segment's (-7 .. -1: in front of it)
+            int j = (r0 + 8 * CH) / CH - 8;        // its sample (floor) and channel
+            int c = r0 - j * CH;
+            int t = off + (j < 0 ? 0 : j > cnt1 ? cnt1 : j); // elements outside the segment read a sample of it: they are not stored
+            u32 w[4];
+#pragma unroll
+            for (int k = 0; k < 8; k += 2) {
+                u32 v2[2];
+#pragma unroll
+                for (int h = 0; h < 2; h++) {
+                    const int l = lut[c];
+                    v2[h] = l < 0 ? 0 : (uint16_t)lds[(l >> 1) + t * (l & 1 ? 1 : 2)];
+                    if (++c == CH) {
+                        c = 0;
+                        j++;
+                        t = off + (j < 0 ? 0 : j > cnt1 ? cnt1 : j);
+                    }
+                }
+                w[k / 2] = v2[0] | v2[1] << 16;
+            }
+            i16 *d = tracks + ((c0 + q) << 3);
+            if (r0 >= 0 && r0 + 8 <= EN) {
+                *reinterpret_cast<uint4 *>(d) = make_uint4(w[0], w[1], w[2], w[3]);
+            } else {
+#pragma unroll
+                for (int h = 0; h < 8; h++)
+                    if (r0 + h >= 0 && r0 + h < EN) d[h] = (i16)(w[h >> 1] >> (16 * (h & 1)));
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// ---- host side ----------------------------------------------------------------------------------------
+extern "C" int og_ms_file_batch_shape(const opusgpu_ms_file_batch *b, int *n_files, const opusgpu_ms_layout **layout, int *mode);
+extern "C" const opusgpu_file_info *og_ms_file_batch_info(const opusgpu_ms_file_batch *b);
+
+static int ms_tracks_launch(opusgpu_ms *ms, hipStream_t s, int n_segs, const void *d_segs, const void *pc, const void *pm, int row_samples,
+                            const void *rc, const void *rm, void *d_tracks, void *d_track_state) {
+    const opusgpu_ms_layout &L = ms->lay;
+    // the streams the mapping uses, stereo ones first (stream order has them first), and where each lies in the staged tile
+    MsTrackArgs a{};
+    int staged_at[256];
+    bool used[256] = {};
+    for (int c = 0; c < L.channels; c++)
+        if (L.mapping[c] != 255) used[L.mapping[c] < 2 * L.coupled ? L.mapping[c] >> 1 : L.mapping[c] - L.coupled] = true;
+    int n = 0;
+    for (int st = 0; st < L.streams; st++) {
+        if (!used[st]) continue;
+        staged_at[st] = st < L.coupled ? 2 * n : 2 * a.n_stereo + (n - a.n_stereo);
+        a.row_of |= (unsigned long long)(st < L.coupled ? st : st - L.coupled) << (8 * n++);
+        (st < L.coupled ? a.n_stereo : a.n_mono)++;
+    }
+    for (int c = 0; c < 8; c++) {
+        const int m = c < L.channels ? L.mapping[c] : 255;
+        if (m == 255)
+            a.lut[c] = -1;
+        else if (m < 2 * L.coupled)
+            a.lut[c] = staged_at[m >> 1] << 2 | (m & 1) << 1;
+        else
+            a.lut[c] = staged_at[m - L.coupled] << 2 | 1;
+    }
+    // LDS tile (samples): a whole row and its alignment slack where 16 KB hold them, 8-sample multiples always
+    const int D = 2 * a.n_stereo + a.n_mono;
+    int ts = 16384 / (2 * (D ? D : 1)) / 8 * 8;
+    if (ts > row_samples + 16) ts = row_samples + 16;
+    const size_t lds = (size_t)ts * D * 2 + (size_t)L.channels * 4;
+    auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3((unsigned)n_segs), dim3(256), lds, s, (const TrackSeg *)d_segs, (const i16 *)pc, (const i16 *)pm,
+                           row_samples, (const i32 *)rc, (const i32 *)rm, L.streams, L.coupled, a, ts, (i16 *)d_tracks,
+                           (TrackState *)d_track_state);
+    };
+    switch (L.channels) { // files carry 1 - 8 channels: no general instance
+        case 1: go(k_ms_tracks_assemble<1>); break;
+        case 2: go(k_ms_tracks_assemble<2>); break;
+        case 3: go(k_ms_tracks_assemble<3>); break;
+        case 4: go(k_ms_tracks_assemble<4>); break;
+        case 5: go(k_ms_tracks_assemble<5>); break;
+        case 6: go(k_ms_tracks_assemble<6>); break;
+        case 7: go(k_ms_tracks_assemble<7>); break;
+        case 8: go(k_ms_tracks_assemble<8>); break;
+        default: return OPUSGPU_BAD_ARG;
+    }
+    MSCHK(ms, hipGetLastError());
+    return OPUSGPU_OK;
+}
+
+// Device time of the step loop of the last opusgpu_ms_files_decode (events on the steps' stream around it; -1: none yet), so that
+// tools/ms_files_rate.py can set the steps against opusgpu_ms_decode_step_device without the upload in front of them.
+static float g_ms_files_steps_ms = -1.f;
+struct MsStepTimer {
+    hipStream_t s;
+    hipEvent_t a = nullptr, b = nullptr;
+    explicit MsStepTimer(hipStream_t stream) : s(stream) {
+        if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess || hipEventRecord(a, s) != hipSuccess) a = nullptr;
+    }
+    void stop() {
+        if (a && hipEventRecord(b, s) != hipSuccess) a = nullptr;
+    }
+    float elapsed_ms() const { // after the stream has been drained
+        float ms = -1.f;
+        return a && hipEventElapsedTime(&ms, a, b) == hipSuccess ? ms : -1.f;
+    }
+    ~MsStepTimer() {
+        if (a) (void)hipEventDestroy(a);
+        if (b) (void)hipEventDestroy(b);
+    }
+};
+
+extern "C" {
+
+float opusgpu_ms_files_last_steps_ms(void) { return g_ms_files_steps_ms; }
+
+int opusgpu_ms_tracks_assemble_device(opusgpu_ms *ms, int n_segs, const void *d_segs, const void *d_pcm_coupled, const void *d_pcm_mono,
+                                      int row_samples, const void *d_res_coupled, const void *d_res_mono, void *d_tracks,
+                                      void *d_track_state, void *hip_stream) {
+    if (!ms || n_segs < 0 || ms->lay.channels > 8) return OPUSGPU_BAD_ARG;
+    if (n_segs == 0) return OPUSGPU_OK;
+    if (!d_segs || !d_tracks || !d_track_state || row_samples <= 0 || row_samples % 8 || ((uintptr_t)d_tracks & 127) ||
+        ((uintptr_t)d_segs & 7) || ((uintptr_t)d_pcm_coupled & 15) || ((uintptr_t)d_pcm_mono & 15) ||
+        (ms->lay.coupled && (!d_pcm_coupled || !d_res_coupled)) || (ms->mono && (!d_pcm_mono || !d_res_mono)))
+        return OPUSGPU_BAD_ARG;
+    MSCHK(ms, hipSetDevice(ms->device));
+    return ms_tracks_launch(ms, hip_stream ? (hipStream_t)hip_stream : ms->stream, n_segs, d_segs, d_pcm_coupled, d_pcm_mono, row_samples,
+                            d_res_coupled, d_res_mono, d_tracks, d_track_state);
+}
+
+int opusgpu_ms_files_decode(opusgpu_ms *ms, const opusgpu_ms_file_batch *batch, void *d_tracks, int64_t *track_lengths_out,
+                            int32_t *status_out) {
+    int n_files = 0, mode = 0;
+    const opusgpu_ms_layout *lay = nullptr;
+    if (!ms || og_ms_file_batch_shape(batch, &n_files, &lay, &mode)) return OPUSGPU_BAD_ARG;
+    if (ms->n_dec < n_files || ms->mode != mode || ms->lay.channels > 8 || ms->lay.channels != lay->channels ||
+        ms->lay.streams != lay->streams || ms->lay.coupled != lay->coupled || memcmp(ms->lay.mapping, lay->mapping, sizeof lay->mapping))
+        return OPUSGPU_BAD_ARG;
+    const opusgpu_file_info *info = og_ms_file_batch_info(batch);
+    const int n_steps = opusgpu_ms_file_batch_steps(batch);
+    const int row = mode == OPUSGPU_MODE_RFC ? OPUSGPU_RFC_FRAME_SAMPLES : OPUSGPU_FRAME_SAMPLES;
+    const size_t S = (size_t)lay->streams;
+    size_t total = 0;
+    for (int k = 0; k < n_steps; k++) total += (size_t)opusgpu_ms_file_batch_step(batch, k, nullptr, nullptr);
+    std::vector<TrackState> st((size_t)n_files, TrackState{INT32_MAX, 0});
+    if (total > 0) {
+        if (!d_tracks || ((uintptr_t)d_tracks & 127)) return OPUSGPU_BAD_ARG;
+        hipStream_t s = ms->stream;
+        int rc = ms_enter(ms, s);
+        if (rc) return rc;
+        // device copies of the batch; the tables of every step lie step after step behind step 0's (og_files.cpp)
+        struct Bufs {
+            void *p[4] = {};
+            ~Bufs() {
+                for (void *q : p)
+                    if (q) (void)hipFree(q);
+            }
+        } d;
+        void *&d_descs = d.p[0], *&d_segs = d.p[1], *&d_arena = d.p[2], *&d_state = d.p[3];
+        const opusgpu_frame_desc *descs = nullptr;
+        const opusgpu_track_seg *segs = nullptr;
+        size_t arena_bytes = 0;
+        const uint8_t *arena = opusgpu_ms_file_batch_arena(batch, &arena_bytes);
+        (void)opusgpu_ms_file_batch_step(batch, 0, &descs, nullptr);
+        (void)opusgpu_ms_file_batch_segments(batch, 0, &segs);
+        const size_t sizes[4] = {total * S * sizeof(opusgpu_frame_desc), total * sizeof(opusgpu_track_seg), arena_bytes,
+                                 (size_t)n_files * sizeof(TrackState)};
+        for (int i = 0; i < 4; i++) {
+            const hipError_t e = hipMalloc(&d.p[i], sizes[i] + 16);
+            if (e != hipSuccess) return ms_fail(ms, OPUSGPU_ALLOC_FAIL, "hipMalloc(files)", e);
+        }
+        MSCHK(ms, hipMemcpy(d_descs, descs, sizes[0], hipMemcpyHostToDevice));
+        MSCHK(ms, hipMemcpy(d_segs, segs, sizes[1], hipMemcpyHostToDevice));
+        MSCHK(ms, hipMemcpy(d_arena, arena, arena_bytes, hipMemcpyHostToDevice));
+        MSCHK(ms, hipMemcpy(d_state, st.data(), sizes[3], hipMemcpyHostToDevice));
+        if ((rc = opusgpu_ms_reset(ms, 0, n_files, 1))) return rc;
+        // The steps, each ending behind its two halves instead of in k_ms_map, the fused assembly behind it on the same stream.
+        // One set of elementary PCM and result buffers (the object's own) serves every step: step k + 1's stereo half is queued on
+        // `s` behind step k's assembly, and its mono half, on the mono context's stream, waits for ev_split, which step k + 1
+        // records on `s` -- behind step k's assembly too.  Step 0 is the largest, so the buffers do not move after it.
+        MsStepTimer timer(s);
+        size_t at = 0;
+        for (int k = 0; k < n_steps && !rc; k++) {
+            const int n = opusgpu_ms_file_batch_step(batch, k, nullptr, nullptr);
+            if (n <= 0) continue;
+            rc = ms_step_impl(ms, n, (const char *)d_descs + at * S * sizeof(opusgpu_frame_desc), d_arena, nullptr, nullptr, s, false);
+            if (!rc)
+                rc = ms_tracks_launch(ms, s, n, (const char *)d_segs + at * sizeof(opusgpu_track_seg), ms->d_pc, ms->d_pm, row, ms->d_rc,
+                                      ms->d_rm, d_tracks, d_state);
+            at += (size_t)n;
+        }
+        timer.stop();
+        const int rs = opusgpu_ms_synchronize(ms);
+        if (!rc) rc = rs;
+        if (!rc) g_ms_files_steps_ms = timer.elapsed_ms();
+        if (!rc) MSCHK(ms, hipMemcpy(st.data(), d_state, sizes[3], hipMemcpyDeviceToHost));
+        if (rc) return rc;
+    }
+    for (int i = 0; i < n_files; i++) {
+        const bool bad = st[i].first_bad != INT32_MAX;
+        if (track_lengths_out)
+            track_lengths_out[i] = bad ? opusgpu_ms_file_batch_packet_start(batch, i, st[i].first_bad) : info[i].track_samples;
+        if (status_out) {
+            status_out[2 * i] = bad ? st[i].code : info[i].status;
+            status_out[2 * i + 1] = bad ? st[i].first_bad : -1;
+        }
+    }
+    return OPUSGPU_OK;
+}
+
+} // extern "C"

@@ -497,7 +497,7 @@ int opusgpu_ms_synchronize(opusgpu_ms *ms);
  * followed (the reader stops at a new link).  The OpusHead output gain is reported, not applied (the reference does not apply it).
  * Refusals, per file, never a failed call (a refused file contributes no frame and a track of 0 samples):
  *   OpusHead channel count != `channels`  -> OPUSGPU_BAD_ARG (a mono file on a stereo context is not the same decoder, Q3);
- *   mapping family != 0                   -> OPUSGPU_UNIMPLEMENTED;
+ *   mapping family != 0                   -> OPUSGPU_UNIMPLEMENTED (family 1: WHOLE FILES / MULTISTREAM below);
  *   reference mode, an audio packet whose TOC names another frame duration than 20 ms -> OPUSGPU_UNIMPLEMENTED.  What the
  *     single-file reader makes of such a packet: the decoder writes 960 samples per frame whatever the TOC says (Q6) and the reader
  *     hands out the TOC's duration from its scratch buffer -- the head of a frame decoded at the wrong length (2.5 / 5 / 10 ms), or
@@ -585,6 +585,75 @@ int opusgpu_tracks_assemble_device(opusgpu_ctx *ctx, int n_segs, const void *d_s
  * failed frame's code (e.g. OPUSGPU_CELT_BAD_ARG), else the plan's status; [2 * i + 1] = the failing packet's packet_seq, or -1. */
 int opusgpu_files_decode(opusgpu_ctx *ctx, const opusgpu_file_batch *batch, void *d_tracks, int64_t *track_lengths_out,
                          int32_t *status_out);
+
+/* ---- WHOLE FILES / MULTISTREAM: N surround Ogg Opus files in, N trimmed interleaved tracks in HBM out -----------------------------
+ * The two sections above joined: files whose OpusHead carries channel mapping family 1 (1 - 8 channels, `streams` elementary
+ * streams) are planned by the same reader-driven loop as stereo files and decoded by an opusgpu_ms of their layout.  The reader's
+ * bookkeeping looks only at a packet's first TOC byte -- elementary stream 0's, and every elementary stream of a packet has the
+ * same duration -- and at the granule positions, so pre-skip, end trimming, holes, the 80 ms discard after a hole, spanning packets
+ * and CRC resync are exactly what they are for a stereo file with the same pages (tests/test_ms_files_plan.py pins that).
+ * File i is DECODER i.  Step k holds one row of `streams` descriptors (the layout opusgpu_ms_decode_step_device documents: row r =
+ * descriptors [r * streams, (r + 1) * streams), stream field = the decoder, offsets into the batch's arena) for every file that
+ * has a k-th frame, rows in file order, and one opusgpu_track_seg per row: `slot` is the row.  A segment counts samples per
+ * channel, as above; a track holds `channels` interleaved int16 per sample and begins at a multiple of 64 samples.
+ * Refusals, per file, never a failed call (a refused file contributes no row and a track of 0 samples):
+ *   the OpusHead's layout differs from `layout` in channel, stream or coupled count or in a mapping entry -> OPUSGPU_BAD_ARG
+ *     (family 0 heads are the layouts {1, 1, 0, {0}} and {2, 1, 1, {0, 1}});
+ *   mapping family 255 -> OPUSGPU_UNIMPLEMENTED (the reader's OP_EIMPL);
+ *   reference mode, an audio packet whose TOC names another frame duration than 20 ms -> OPUSGPU_UNIMPLEMENTED, as above;
+ *   RFC mode, a packet whose elementary streams differ in frame count or in frame duration -> OPUSGPU_UNIMPLEMENTED: the device
+ *     step takes rows of one duration (opusgpu_ms_decode_packets takes such packets one call at a time).
+ *   A packet with a valid duration that opusgpu_ms_packet_to_frames rejects -- too short for its streams, a malformed elementary
+ *   packet, streams of different durations, reference mode: of different frame counts -- ends the plan with OP_EBADPACKET (-136);
+ *   what was planned before it is decoded.
+ * A failed elementary frame fails its row (the first negative elementary result in stream order), and a failed row ends its track
+ * as a failed frame does above (FAILED FRAMES). */
+typedef struct opusgpu_ms_file_batch opusgpu_ms_file_batch;
+
+/* The layout of one file, read from its OpusHead by the single-file reader's open (headers and the first audio page): family 0 gives
+ * streams 1, coupled channels - 1 and the identity mapping, family 1 what the header says; mapping entries >= channels are 255.
+ * A caller with a mixed corpus groups its files by this, one opusgpu_ms per layout.  info (may be NULL) receives status and the
+ * OpusHead fields.  Returns OPUSGPU_OK, OPUSGPU_BAD_ARG, or what the reader says, e.g. -132 OP_ENOTFORMAT, -133 OP_EBADHEADER;
+ * family 255 is OPUSGPU_UNIMPLEMENTED.  *layout is written only on success.  Host only. */
+int opusgpu_file_layout(const uint8_t *file, int64_t len, opusgpu_ms_layout *layout, opusgpu_file_info *info);
+/* opusgpu_files_plan for files of ONE layout.  There is no `flags`: the grouping flags order single frames by mode, and a row
+ * mixes the modes of its elementary streams.  Returns OPUSGPU_OK, OPUSGPU_BAD_ARG (a layout opusgpu_ms_create would refuse
+ * included) or OPUSGPU_ALLOC_FAIL.  Host only. */
+int opusgpu_ms_files_plan(int n_files, const uint8_t *const *files, const int64_t *file_lens, const opusgpu_ms_layout *layout,
+                          int mode, int threads, opusgpu_file_info *info, opusgpu_ms_file_batch **out);
+int opusgpu_ms_file_batch_steps(const opusgpu_ms_file_batch *b);
+/* Step `step`: returns its ROW count; *descs its table (rows x streams descriptors), *slot_files (may be NULL) the file of every row. */
+int opusgpu_ms_file_batch_step(const opusgpu_ms_file_batch *b, int step, const opusgpu_frame_desc **descs, const int32_t **slot_files);
+int opusgpu_ms_file_batch_segments(const opusgpu_ms_file_batch *b, int step, const opusgpu_track_seg **segs); /* one per row */
+const uint8_t *opusgpu_ms_file_batch_arena(const opusgpu_ms_file_batch *b, size_t *bytes);
+/* Samples per channel of the packed track buffer: allocate 2 * channels bytes for each. */
+int64_t opusgpu_ms_file_batch_track_samples(const opusgpu_ms_file_batch *b);
+int64_t opusgpu_ms_file_batch_packet_start(const opusgpu_ms_file_batch *b, int file, int packet_seq);
+void opusgpu_ms_file_batch_free(opusgpu_ms_file_batch *b);
+
+/* k_ms_tracks_assemble: the channel mapping and the track assembly in one pass.  Applies n_segs segments to the ELEMENTARY PCM of
+ * one ms step -- d_pcm_coupled [rows * coupled][row_samples * 2] and d_pcm_mono [rows * (streams - coupled)][row_samples] int16,
+ * with the elementary results d_res_coupled [rows * coupled] and d_res_mono [rows * (streams - coupled)], the layout in which the
+ * object's two contexts leave a step -- and writes output channel c of every kept sample from decoded channel mapping[c] (255:
+ * zero) into the packed track buffer d_tracks (`channels` interleaved int16 per sample, 128-byte aligned).  A row's result is its
+ * first negative elementary result in stream order, else the common sample count (streams that disagree: OPUSGPU_INTERNAL_ERROR);
+ * a negative one is a failed frame (FAILED FRAMES above).  Layouts of 1 - 8 channels (OPUSGPU_BAD_ARG otherwise); row_samples a
+ * multiple of 8; PCM pointers 16-byte aligned; a pointer of a kind of stream the layout does not have may be NULL.  The caller
+ * guarantees what opusgpu_tracks_assemble_device asks for.  Asynchronous on `hip_stream` (NULL: the object's own stream). */
+int opusgpu_ms_tracks_assemble_device(opusgpu_ms *ms, int n_segs, const void *d_segs, const void *d_pcm_coupled,
+                                      const void *d_pcm_mono, int row_samples, const void *d_res_coupled, const void *d_res_mono,
+                                      void *d_tracks, void *d_track_state, void *hip_stream);
+/* opusgpu_files_decode for a multistream batch: uploads it, gives decoders 0 .. n_files - 1 fresh state, and per step runs the row
+ * split, the stereo step, the mono step and k_ms_tracks_assemble on the object's stream; the interleaved [rows][960 * channels]
+ * PCM of opusgpu_ms_decode_step_device is never made.  Steps run in order.  The object must hold at least n_files decoders of the
+ * batch's layout and be in the batch's mode (OPUSGPU_BAD_ARG otherwise).  d_tracks: opusgpu_ms_file_batch_track_samples x
+ * channels int16 in HBM, 128-byte aligned; track_lengths_out and status_out as for opusgpu_files_decode. */
+int opusgpu_ms_files_decode(opusgpu_ms *ms, const opusgpu_ms_file_batch *batch, void *d_tracks, int64_t *track_lengths_out,
+                            int32_t *status_out);
+/* Measurement aid (tools/ms_files_rate.py): the device time in ms of the step loop of this process's last successful
+ * opusgpu_ms_files_decode -- split, both halves and the assembly of every step, without the upload and the reset in front of them
+ * (events on the object's stream around the loop); -1 before the first call. */
+float opusgpu_ms_files_last_steps_ms(void);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,170 @@
+#!/usr/bin/env python3
+"""Whole multistream files rate (include/opusgpu.h, WHOLE FILES / MULTISTREAM): N 5.1 files (6 channels, 4 streams, 2 coupled) of one
+page of 10 packets, CELT-FB 20 ms frames of 160 bytes on every elementary stream, random pre-skips and end trims of 0 - 2,000
+samples, planned once and decoded device-resident.  Per batch of 10 steps, mean and spread over --reps repeats, the two variants
+interleaved:
+(A) the batch's 10 steps through opusgpu_ms_decode_step_device: split, both halves, k_ms_map into [rows][960 * 6]; no trimming.
+    Host clock around the 10 calls and a synchronise.
+(B) the same 10 steps inside opusgpu_ms_files_decode, k_ms_tracks_assemble behind each instead of the map.  The call uploads the
+    batch first, so its steps are timed by the library itself, with events around the step loop (opusgpu_ms_files_last_steps_ms).
+The kernels' own times come from a kernel trace: run this script under `rocprofv3 --kernel-trace --stats --output-format csv -d DIR
+-o msfiles --` and then `python3 tools/ms_files_rate.py --stats DIR` reads DIR's kernel_stats.csv (k_ms_tracks_assemble: per batch
+it reads and writes the kept samples x 6 channels x 2 bytes each; k_ms_map: ms_rate.py's count per step).
+usage (GPU box): python3 tools/ms_files_rate.py [--n N] [--reps R] | python3 tools/ms_files_rate.py --stats DIR [--n N]"""
+import argparse
+import ctypes as C
+import glob
+import importlib.util
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+here = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.join(here, "..", "tests"))
+ap = argparse.ArgumentParser()
+ap.add_argument("--n", type=int, default=65536)
+ap.add_argument("--reps", type=int, default=30)
+ap.add_argument("--threads", type=int, default=16)
+ap.add_argument("--stats", default=None)
+args = ap.parse_args()
+n = args.n
+
+spec = importlib.util.spec_from_file_location("esp32_opus_player_amd", os.path.join(here, "..", "esp32-opus-player_amd", "__init__.py"))
+pkg = importlib.util.module_from_spec(spec)
+spec.loader.exec_module(pkg)
+import files_util as fu  # noqa: E402
+import ms_files_util as mf  # noqa: E402
+import ogg_util  # noqa: E402
+
+LAYOUT = (6, 4, 2, [0, 4, 1, 2, 3, 5])
+CH, S, CP, L, PACKETS = 6, 4, 2, 160, 10
+rng = np.random.default_rng(3)
+pre = rng.integers(0, 2001, n)
+trim = rng.integers(0, 2001, n)
+kept = int((PACKETS * 960 - pre - trim).sum())  # samples per channel of all tracks
+MOVED = 2 * kept * CH * 2                       # bytes the fused assembly reads + writes per batch
+MAP_BYTES = n * (2 * 960 * 2 * 2 + 2 * 960 * 2) + n * 960 * 6 * 2  # k_ms_map, per full step
+
+if args.stats:
+    import csv
+    rows = []
+    for f in glob.glob(os.path.join(args.stats, "**", "*kernel_stats.csv"), recursive=True):
+        rows += list(csv.DictReader(open(f)))
+    out = []
+    for key, per_launch in (("k_ms_tracks_assemble", MOVED / PACKETS), ("k_ms_map", MAP_BYTES), ("k_tracks_assemble", None)):
+        for r in rows:
+            if r["Name"].startswith(key) or ("void " + key) in r["Name"]:
+                avg_ms = float(r["AverageNs"]) / 1e6
+                o = {"kernel": r["Name"].split("(")[0], "calls": int(r["Calls"]), "avg_ms_per_launch": round(avg_ms, 4),
+                     "min_ms": round(float(r["MinNs"]) / 1e6, 4), "max_ms": round(float(r["MaxNs"]) / 1e6, 4)}
+                if per_launch:
+                    o["bytes_per_launch"] = int(per_launch)
+                    o["tb_per_s"] = round(per_launch / (avg_ms / 1e3) / 1e12, 2)
+                out.append(o)
+    assert out, "neither kernel in the kernel statistics"
+    print(json.dumps(out))
+    raise SystemExit(0)
+
+
+def crc_fill(rows):
+    rows[:, 22:26] = 0
+    rows[:, 22:26] = pkg.ogg_crc_rows(rows).astype("<u4").reshape(-1, 1).view(np.uint8)
+
+
+# ---- the files, numpy all the way --------------------------------------------------------------------------------------------
+serial = np.arange(n, dtype=np.uint32) + 1000
+head = np.frombuffer(ogg_util.page(0, 0, 0, [mf.head(LAYOUT, 0)], bos=True), dtype=np.uint8)
+tags = np.frombuffer(ogg_util.page(0, 1, 0, [ogg_util.opus_tags()]), dtype=np.uint8)
+H, T = np.tile(head, (n, 1)), np.tile(tags, (n, 1))
+for rows in (H, T):
+    rows[:, 14:18] = serial.astype("<u4").reshape(n, 1).view(np.uint8)
+H[:, 28 + 10:28 + 12] = pre.astype("<u2").reshape(n, 1).view(np.uint8)  # 27 + 1 lacing value, then OpusHead: pre-skip at 10
+crc_fill(H)
+crc_fill(T)
+# a multistream packet: [TOC, 160, payload] for streams 0 - 2 (self-delimited), [TOC, payload] for stream 3
+PK = (S - 1) * (L + 2) + (L + 1)
+lacing = fu.raw_page(0, 2, 0, mf.lace(PK) * PACKETS, b"")  # the page header with the segment table, no body yet
+hdr = len(lacing)
+page = np.zeros((n, hdr + PACKETS * PK), dtype=np.uint8)
+page[:, :hdr] = np.frombuffer(lacing, dtype=np.uint8)
+page[:, 5] = 4  # end of stream
+page[:, 6:14] = (PACKETS * 960 - trim).astype("<i8").reshape(n, 1).view(np.uint8)
+page[:, 14:18] = serial.astype("<u4").reshape(n, 1).view(np.uint8)
+pay = pkg.lcg_payloads(n, PACKETS * S, L, seed_base=3 * 7919 + 1)  # [PACKETS * S, n, L]
+body = page[:, hdr:].reshape(n, PACKETS, PK)
+at = 0
+for s in range(S):
+    body[:, :, at] = 0xFC if s < CP else 0xF8  # CELT FB 20 ms, stereo / mono
+    at += 1
+    if s != S - 1:
+        body[:, :, at] = L
+        at += 1
+    body[:, :, at:at + L] = pay[s::S].transpose(1, 0, 2)
+    at += L
+crc_fill(page)
+files = np.concatenate([H, T, page], axis=1)
+blobs = [r.tobytes() for r in files]
+del files, page, pay
+
+t0 = time.perf_counter()
+b = pkg.MsFileBatch(blobs, LAYOUT, threads=args.threads)
+plan_s = time.perf_counter() - t0
+assert (b.info["status"] == 0).all() and b.n_steps == PACKETS, (np.unique(b.info["status"]), b.n_steps)
+assert (b.info["track_samples"] == PACKETS * 960 - pre - trim).all()
+
+# ---- (A) and (B), interleaved --------------------------------------------------------------------------------------------------
+ctx = pkg.Context(0)
+ms = pkg.MultistreamContext(0, n, *LAYOUT)
+steps = [b.step(k) for k in range(PACKETS)]
+descs = np.concatenate([s[0].reshape(-1) for s in steps])
+d_descs, d_arena = ctx.dev_alloc(descs.nbytes), ctx.dev_alloc(b.arena.nbytes)
+d_pcm, d_res = ctx.dev_alloc(n * 960 * CH * 2), ctx.dev_alloc(4 * n)
+d_tracks = ctx.dev_alloc(max(int(b.track_samples), 1) * CH * 2)
+ctx.h2d(d_descs, descs)
+ctx.h2d(d_arena, b.arena)
+lengths = np.zeros(n, dtype=np.int64)
+status = np.zeros((n, 2), dtype=np.int32)
+
+
+def run_a():
+    ms.reset()
+    at = 0
+    t0 = time.perf_counter()
+    for k in range(PACKETS):
+        m = len(steps[k][1])
+        ms.decode_step_device(m, C.c_void_p(d_descs.value + 16 * S * at), d_arena, d_pcm, d_res)
+        at += m
+    ms.synchronize()
+    return (time.perf_counter() - t0) * 1e3
+
+
+def run_b():
+    t0 = time.perf_counter()
+    ms._chk(ms.lib.opusgpu_ms_files_decode(ms.h, b.h, d_tracks, lengths.ctypes.data, status.ctypes.data), "opusgpu_ms_files_decode")
+    return ms.lib.opusgpu_ms_files_last_steps_ms(), (time.perf_counter() - t0) * 1e3
+
+
+run_a()
+run_b()
+a, w, call = [], [], []
+for _ in range(args.reps):
+    a.append(run_a())
+    x, y = run_b()
+    w.append(x)
+    call.append(y)
+assert (status[:, 0] == 0).all() and (lengths == b.info["track_samples"]).all()
+res = np.zeros(n, np.int32)
+ctx.d2h(res, d_res)
+assert (res == 960).all(), np.unique(res)[:8]
+spread = max(a) - min(a)
+print(json.dumps({"layout": "5.1", "files": n, "reps": args.reps, "bytes_moved_by_assembly_per_batch": MOVED, "map_bytes_per_step": MAP_BYTES,
+                  "plan_files_per_s": round(n / plan_s), "plan_threads": args.threads,
+                  "a_ms_steps_ms": round(float(np.mean(a)), 3), "a_min_max_ms": [round(min(a), 3), round(max(a), 3)], "a_spread_ms": round(spread, 3),
+                  "b_files_steps_ms": round(float(np.mean(w)), 3), "b_min_max_ms": [round(min(w), 3), round(max(w), 3)],
+                  "b_minus_a_ms": round(float(np.mean(w) - np.mean(a)), 3), "condition_b_le_a_plus_spread": bool(np.mean(w) <= np.mean(a) + spread),
+                  "b_whole_call_ms": round(float(np.mean(call)), 3)}))
+ms.close()
+ctx.close()
