@@ -192,32 +192,24 @@ def load_lib():
     lib.opusgpu_ms_decode_step_device.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
     lib.opusgpu_ms_synchronize.argtypes = [vp]
     lib.opusgpu_files_plan.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.POINTER(vp)]
-    lib.opusgpu_file_batch_steps.argtypes = [vp]
-    lib.opusgpu_file_batch_step.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int)]
-    lib.opusgpu_file_batch_segments.argtypes = [vp, C.c_int, C.POINTER(vp)]
-    lib.opusgpu_file_batch_arena.argtypes = [vp, C.POINTER(C.c_size_t)]
-    lib.opusgpu_file_batch_arena.restype = vp
-    lib.opusgpu_file_batch_track_samples.argtypes = [vp]
-    lib.opusgpu_file_batch_track_samples.restype = C.c_int64
-    lib.opusgpu_file_batch_packet_start.argtypes = [vp, C.c_int, C.c_int]
-    lib.opusgpu_file_batch_packet_start.restype = C.c_int64
-    lib.opusgpu_file_batch_free.argtypes = [vp]
-    lib.opusgpu_file_batch_free.restype = None
     lib.opusgpu_tracks_assemble_device.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp]
     lib.opusgpu_files_decode.argtypes = [vp, vp, vp, vp, vp]
     lib.opusgpu_file_layout.argtypes = [vp, C.c_int64, C.POINTER(MsLayout), vp]
     lib.opusgpu_ms_files_plan.argtypes = [C.c_int, vp, vp, C.POINTER(MsLayout), C.c_int, C.c_int, vp, C.POINTER(vp)]
-    lib.opusgpu_ms_file_batch_steps.argtypes = [vp]
-    lib.opusgpu_ms_file_batch_step.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp)]
-    lib.opusgpu_ms_file_batch_segments.argtypes = [vp, C.c_int, C.POINTER(vp)]
-    lib.opusgpu_ms_file_batch_arena.argtypes = [vp, C.POINTER(C.c_size_t)]
-    lib.opusgpu_ms_file_batch_arena.restype = vp
-    lib.opusgpu_ms_file_batch_track_samples.argtypes = [vp]
-    lib.opusgpu_ms_file_batch_track_samples.restype = C.c_int64
-    lib.opusgpu_ms_file_batch_packet_start.argtypes = [vp, C.c_int, C.c_int]
-    lib.opusgpu_ms_file_batch_packet_start.restype = C.c_int64
-    lib.opusgpu_ms_file_batch_free.argtypes = [vp]
-    lib.opusgpu_ms_file_batch_free.restype = None
+    for prefix, step_more in (("opusgpu_file_batch", [C.POINTER(C.c_int)]), ("opusgpu_ms_file_batch", [])):
+        def f(name):
+            return getattr(lib, f"{prefix}_{name}")
+        f("steps").argtypes = [vp]
+        f("step").argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp)] + step_more
+        f("segments").argtypes = [vp, C.c_int, C.POINTER(vp)]
+        f("arena").argtypes = [vp, C.POINTER(C.c_size_t)]
+        f("arena").restype = vp
+        f("track_samples").argtypes = [vp]
+        f("track_samples").restype = C.c_int64
+        f("packet_start").argtypes = [vp, C.c_int, C.c_int]
+        f("packet_start").restype = C.c_int64
+        f("free").argtypes = [vp]
+        f("free").restype = None
     lib.opusgpu_ms_tracks_assemble_device.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp]
     lib.opusgpu_ms_files_decode.argtypes = [vp, vp, vp, vp, vp]
     lib.opusgpu_ms_files_last_steps_ms.restype = C.c_float
@@ -370,55 +362,59 @@ class PageBatch:
             pass
 
 
-class FileBatch:
-    """Decode steps, packet arena and track segments planned from whole Ogg Opus files by opusgpu_files_plan (host only,
-    include/opusgpu.h WHOLE FILES).  files: a list of bytes-like objects, file i = decoder stream i.  info: one FILE_INFO_DTYPE
-    record per file (status, OpusHead fields, packets, frames, holes, planned track length and offset)."""
+class _PlannedFiles:
+    """What FileBatch and MsFileBatch share: the plan call, the batch's accessors (the C family `_prefix`: opusgpu_file_batch /
+    opusgpu_ms_file_batch) and its lifetime.  A slot of a step has `_width` descriptors."""
+    _prefix, _width = None, 1
 
-    def __init__(self, files, channels=2, rfc=False, flags=0, threads=1):
-        lib = load_lib()
+    def _plan(self, files, rfc, name, call):
+        """call(n, file pointers, lengths, info, out handle) -> the code of the plan function `name`."""
+        self.lib = load_lib()
         self._files = [np.frombuffer(bytes(f) + b"\0", dtype=np.uint8) for f in files]  # (kept alive; + 1: never an empty buffer)
         n = len(self._files)
         ptrs = np.array([a.ctypes.data for a in self._files], dtype=np.uint64)
         lens = np.array([a.size - 1 for a in self._files], dtype=np.int64)
         self.info = np.zeros(n, dtype=FILE_INFO_DTYPE)
         h = C.c_void_p()
-        r = lib.opusgpu_files_plan(n, ptrs.ctypes.data, lens.ctypes.data, channels, 1 if rfc else 0, flags, threads, self.info.ctypes.data,
-                                   C.byref(h))
+        r = call(n, ptrs.ctypes.data, lens.ctypes.data, self.info.ctypes.data, C.byref(h))
         if r != 0:
-            e = OpusGpuError(f"opusgpu_files_plan failed: {r}")
+            e = OpusGpuError(f"{name} failed: {r}")
             e.code = r
             raise e
-        self.lib, self.h = lib, h
-        self.n_files, self.channels, self.rfc = n, channels, bool(rfc)
+        self.h = h
+        self.n_files, self.rfc = n, bool(rfc)
         self.row_samples = RFC_FRAME if rfc else FRAME
-        self.n_steps = lib.opusgpu_file_batch_steps(h)
-        self.track_samples = lib.opusgpu_file_batch_track_samples(h)
+        self.n_steps = self._c("steps")(h)
+        self.track_samples = self._c("track_samples")(h)
         nbytes = C.c_size_t()
-        a = lib.opusgpu_file_batch_arena(h, C.byref(nbytes))
+        a = self._c("arena")(h, C.byref(nbytes))
         self.arena = np.ctypeslib.as_array((C.c_uint8 * nbytes.value).from_address(a)) if nbytes.value else np.zeros(0, np.uint8)
 
-    def step(self, k):
-        """-> (descriptors [DESC_DTYPE], file of every slot [int32], segments [TRACK_SEG_DTYPE], modes); views, valid until close()."""
-        d, sf, sg, modes = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int()
-        n = self.lib.opusgpu_file_batch_step(self.h, k, C.byref(d), C.byref(sf), C.byref(modes))
+    def _c(self, name):
+        return getattr(self.lib, f"{self._prefix}_{name}")
+
+    def _step_tables(self, k, *more):
+        """-> (descriptors, flat; file of every slot; segments): views, valid until close().  more: what the step call takes
+        behind slot_files."""
+        d, sf, sg = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        n = self._c("step")(self.h, k, C.byref(d), C.byref(sf), *more)
         if n < 0:
             raise IndexError(k)
         if n == 0:
-            return np.zeros(0, DESC_DTYPE), np.zeros(0, np.int32), np.zeros(0, TRACK_SEG_DTYPE), modes.value
-        self.lib.opusgpu_file_batch_segments(self.h, k, C.byref(sg))
-        descs = np.frombuffer((C.c_uint8 * (16 * n)).from_address(d.value), dtype=DESC_DTYPE)
+            return np.zeros(0, DESC_DTYPE), np.zeros(0, np.int32), np.zeros(0, TRACK_SEG_DTYPE)
+        self._c("segments")(self.h, k, C.byref(sg))
+        descs = np.frombuffer((C.c_uint8 * (16 * n * self._width)).from_address(d.value), dtype=DESC_DTYPE)
         files = np.frombuffer((C.c_uint8 * (4 * n)).from_address(sf.value), dtype=np.int32)
         segs = np.frombuffer((C.c_uint8 * (32 * n)).from_address(sg.value), dtype=TRACK_SEG_DTYPE)
-        return descs, files, segs, modes.value
+        return descs, files, segs
 
     def packet_start(self, file, packet_seq):
         """Planned start (track-relative sample) of a file's packet; packet_seq == its packet count: the planned length."""
-        return self.lib.opusgpu_file_batch_packet_start(self.h, file, packet_seq)
+        return self._c("packet_start")(self.h, file, packet_seq)
 
     def close(self):
         if self.h:
-            self.lib.opusgpu_file_batch_free(self.h)
+            self._c("free")(self.h)
             self.h = None
             self.arena = None
 
@@ -427,6 +423,23 @@ class FileBatch:
             self.close()
         except Exception:
             pass
+
+
+class FileBatch(_PlannedFiles):
+    """Decode steps, packet arena and track segments planned from whole Ogg Opus files by opusgpu_files_plan (host only,
+    include/opusgpu.h WHOLE FILES).  files: a list of bytes-like objects, file i = decoder stream i.  info: one FILE_INFO_DTYPE
+    record per file (status, OpusHead fields, packets, frames, holes, planned track length and offset)."""
+    _prefix = "opusgpu_file_batch"
+
+    def __init__(self, files, channels=2, rfc=False, flags=0, threads=1):
+        self.channels = channels
+        self._plan(files, rfc, "opusgpu_files_plan", lambda n, ptrs, lens, info, out: load_lib().opusgpu_files_plan(
+            n, ptrs, lens, channels, 1 if rfc else 0, flags, threads, info, out))
+
+    def step(self, k):
+        """-> (descriptors [DESC_DTYPE], file of every slot [int32], segments [TRACK_SEG_DTYPE], modes); views, valid until close()."""
+        modes = C.c_int()
+        return self._step_tables(k, C.byref(modes)) + (modes.value,)
 
 
 def file_layout(data):
@@ -445,66 +458,48 @@ def file_layout(data):
     return (lay.channels, lay.streams, lay.coupled, [lay.mapping[c] for c in range(lay.channels)]), info[0]
 
 
-class MsFileBatch:
+class MsFileBatch(_PlannedFiles):
     """Decode steps, packet arena and track segments planned from whole Ogg Opus files of ONE multistream layout by
     opusgpu_ms_files_plan (host only, include/opusgpu.h WHOLE FILES / MULTISTREAM).  files: a list of bytes-like objects, file i =
     decoder i; layout: (channels, streams, coupled, mapping) or an MsLayout.  A step is rows of `streams` descriptors, one row and
     one segment per file that has a frame in it."""
+    _prefix = "opusgpu_ms_file_batch"
 
     def __init__(self, files, layout, rfc=False, threads=1):
-        lib = load_lib()
         self.layout = layout if isinstance(layout, MsLayout) else ms_layout(*layout)
-        self._files = [np.frombuffer(bytes(f) + b"\0", dtype=np.uint8) for f in files]  # (kept alive; + 1: never an empty buffer)
-        n = len(self._files)
-        ptrs = np.array([a.ctypes.data for a in self._files], dtype=np.uint64)
-        lens = np.array([a.size - 1 for a in self._files], dtype=np.int64)
-        self.info = np.zeros(n, dtype=FILE_INFO_DTYPE)
-        h = C.c_void_p()
-        r = lib.opusgpu_ms_files_plan(n, ptrs.ctypes.data, lens.ctypes.data, C.byref(self.layout), 1 if rfc else 0, threads,
-                                      self.info.ctypes.data, C.byref(h))
-        if r != 0:
-            e = OpusGpuError(f"opusgpu_ms_files_plan failed: {r}")
-            e.code = r
-            raise e
-        self.lib, self.h = lib, h
-        self.n_files, self.channels, self.streams, self.rfc = n, int(self.layout.channels), int(self.layout.streams), bool(rfc)
-        self.row_samples = RFC_FRAME if rfc else FRAME
-        self.n_steps = lib.opusgpu_ms_file_batch_steps(h)
-        self.track_samples = lib.opusgpu_ms_file_batch_track_samples(h)
-        nbytes = C.c_size_t()
-        a = lib.opusgpu_ms_file_batch_arena(h, C.byref(nbytes))
-        self.arena = np.ctypeslib.as_array((C.c_uint8 * nbytes.value).from_address(a)) if nbytes.value else np.zeros(0, np.uint8)
+        self.channels, self.streams = int(self.layout.channels), int(self.layout.streams)
+        self._width = self.streams
+        self._plan(files, rfc, "opusgpu_ms_files_plan", lambda n, ptrs, lens, info, out: load_lib().opusgpu_ms_files_plan(
+            n, ptrs, lens, C.byref(self.layout), 1 if rfc else 0, threads, info, out))
 
     def step(self, k):
         """-> (descriptors [rows, streams] of DESC_DTYPE, file of every row [int32], segments [TRACK_SEG_DTYPE]); views, valid
         until close()."""
-        d, sf, sg = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        n = self.lib.opusgpu_ms_file_batch_step(self.h, k, C.byref(d), C.byref(sf))
-        if n < 0:
-            raise IndexError(k)
-        if n == 0:
-            return np.zeros((0, self.streams), DESC_DTYPE), np.zeros(0, np.int32), np.zeros(0, TRACK_SEG_DTYPE)
-        self.lib.opusgpu_ms_file_batch_segments(self.h, k, C.byref(sg))
-        descs = np.frombuffer((C.c_uint8 * (16 * n * self.streams)).from_address(d.value), dtype=DESC_DTYPE).reshape(n, self.streams)
-        files = np.frombuffer((C.c_uint8 * (4 * n)).from_address(sf.value), dtype=np.int32)
-        segs = np.frombuffer((C.c_uint8 * (32 * n)).from_address(sg.value), dtype=TRACK_SEG_DTYPE)
-        return descs, files, segs
+        descs, files, segs = self._step_tables(k)
+        return descs.reshape(-1, self.streams), files, segs
 
-    def packet_start(self, file, packet_seq):
-        """Planned start (track-relative sample) of a file's packet; packet_seq == its packet count: the planned length."""
-        return self.lib.opusgpu_ms_file_batch_packet_start(self.h, file, packet_seq)
 
-    def close(self):
-        if self.h:
-            self.lib.opusgpu_ms_file_batch_free(self.h)
-            self.h = None
-            self.arena = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+def _decode_planned(lib, chk, name, handle, batch, mem):
+    """The shared body of the two decode_files: runs the decode call `name` of `lib` for the decoder `handle` over `batch` into a
+    track buffer from `mem` (a Context: dev_alloc, d2h, dev_free); chk(code, what) raises.  -> (tracks, info)."""
+    n = batch.n_files
+    total = max(int(batch.track_samples), 1) * batch.channels
+    d_tracks = mem.dev_alloc(2 * total)
+    try:
+        lengths = np.zeros(n, dtype=np.int64)
+        status = np.zeros((n, 2), dtype=np.int32)
+        chk(getattr(lib, name)(handle, batch.h, d_tracks, lengths.ctypes.data, status.ctypes.data), name)
+        packed = np.zeros(total, dtype=np.int16)
+        mem.d2h(packed, d_tracks)
+    finally:
+        mem.dev_free(d_tracks)
+    packed = packed.reshape(-1, batch.channels)
+    info = np.zeros(n, dtype=np.dtype(FILE_INFO_DTYPE.descr + [("final_status", "<i4"), ("bad_packet", "<i4")]))
+    for field in FILE_INFO_DTYPE.names:
+        info[field] = batch.info[field]
+    info["track_samples"], info["final_status"], info["bad_packet"] = lengths, status[:, 0], status[:, 1]
+    tracks = [packed[o:o + ln] for o, ln in zip(batch.info["track_offset"], lengths)]
+    return tracks, info
 
 
 class Context:
@@ -680,28 +675,10 @@ class Context:
         if own:
             batch = FileBatch(files, channels=channels, rfc=rfc, flags=flags, threads=threads)
         try:
-            n = batch.n_files
-            if self.n_streams < n or self.channels != batch.channels:
-                self.streams_alloc(max(n, 1), batch.channels)
+            if self.n_streams < batch.n_files or self.channels != batch.channels:
+                self.streams_alloc(max(batch.n_files, 1), batch.channels)
             self.set_mode(batch.rfc)
-            total = max(int(batch.track_samples), 1) * batch.channels
-            d_tracks = self.dev_alloc(2 * total)
-            try:
-                lengths = np.zeros(n, dtype=np.int64)
-                status = np.zeros((n, 2), dtype=np.int32)
-                self._chk(self.lib.opusgpu_files_decode(self.h, batch.h, d_tracks, lengths.ctypes.data, status.ctypes.data),
-                          "opusgpu_files_decode")
-                packed = np.zeros(total, dtype=np.int16)
-                self.d2h(packed, d_tracks)
-            finally:
-                self.dev_free(d_tracks)
-            packed = packed.reshape(-1, batch.channels)
-            info = np.zeros(n, dtype=np.dtype(FILE_INFO_DTYPE.descr + [("final_status", "<i4"), ("bad_packet", "<i4")]))
-            for name in FILE_INFO_DTYPE.names:
-                info[name] = batch.info[name]
-            info["track_samples"], info["final_status"], info["bad_packet"] = lengths, status[:, 0], status[:, 1]
-            tracks = [packed[o:o + ln] for o, ln in zip(batch.info["track_offset"], lengths)]
-            return tracks, info
+            return _decode_planned(self.lib, self._chk, "opusgpu_files_decode", self.h, batch, self)
         finally:
             if own:
                 batch.close()
@@ -871,26 +848,8 @@ class MultistreamContext:
             batch = MsFileBatch(files, self.layout, rfc=rfc, threads=threads)
         mem = Context(self.device)  # (device memory and copies are a plain context's calls)
         try:
-            n = batch.n_files
             self.set_mode(batch.rfc)
-            total = max(int(batch.track_samples), 1) * batch.channels
-            d_tracks = mem.dev_alloc(2 * total)
-            try:
-                lengths = np.zeros(n, dtype=np.int64)
-                status = np.zeros((n, 2), dtype=np.int32)
-                self._chk(self.lib.opusgpu_ms_files_decode(self.h, batch.h, d_tracks, lengths.ctypes.data, status.ctypes.data),
-                          "opusgpu_ms_files_decode")
-                packed = np.zeros(total, dtype=np.int16)
-                mem.d2h(packed, d_tracks)
-            finally:
-                mem.dev_free(d_tracks)
-            packed = packed.reshape(-1, batch.channels)
-            info = np.zeros(n, dtype=np.dtype(FILE_INFO_DTYPE.descr + [("final_status", "<i4"), ("bad_packet", "<i4")]))
-            for name in FILE_INFO_DTYPE.names:
-                info[name] = batch.info[name]
-            info["track_samples"], info["final_status"], info["bad_packet"] = lengths, status[:, 0], status[:, 1]
-            tracks = [packed[o:o + ln] for o, ln in zip(batch.info["track_offset"], lengths)]
-            return tracks, info
+            return _decode_planned(self.lib, self._chk, "opusgpu_ms_files_decode", self.h, batch, mem)
         finally:
             mem.close()
             if own:

@@ -1184,5 +1184,6 @@ static int grow(opusgpu_ctx *ctx, void **p, size_t *cap, size_t need) {
 
 // multistream decoding (include/opusgpu.h, MULTISTREAM): drives the contexts above
 #include "og_ms.hpp"
+#include "og_files_run.hpp"
 #include "og_tracks.hpp"
 #include "og_ms_tracks.hpp"

@@ -15,6 +15,7 @@
 #include <new>
 #include <thread>
 #include <vector>
+#include "og_batch.hpp"
 #include "og_container.hpp"
 #include "og_packet.hpp"
 #include "../../include/opusgpu.h"
@@ -149,15 +150,7 @@ int plan_file(const uint8_t *data, size_t len, int channels, int mode, int flags
         if (m != first_mode) kept = false;
         for (int k = 0; k < count; k++) {
             fp.descs.push_back(opusgpu_frame_desc{0, base + off, size[k], fl});
-            int key = 0;
-            if (by_header) { // og_pages.cpp: SILK 0..3 and hybrid 4..7 by the LBRR flags, CELT 8
-                key = m == 2 ? 8 : 4 * m;
-                if (m != 2 && size[k] > 0) {
-                    const uint8_t b0 = pk[(size_t)off];
-                    key += (int)((b0 >> 6) & 1) | ((fl & 32) ? (int)((b0 >> 4) & 1) << 1 : 0);
-                }
-            } else if (group)
-                key = m;
+            const int key = by_header ? ogh::header_order_key(fl, size[k] > 0 ? pk[(size_t)off] : 0, size[k]) : group ? m : 0;
             fr[k].flags = fl, fr[k].key = (uint8_t)key, fr[k].kept = kept;
             off += size[k];
         }
@@ -201,25 +194,6 @@ int plan_ms_file(const uint8_t *data, size_t len, const opusgpu_ms_layout &lay, 
 }
 
 } // namespace
-
-// What both kinds of batch hold.  A slot is one frame of one file: `width` descriptors and one segment.
-struct og_batch {
-    int n_files = 0, channels = 0, mode = 0, width = 1;
-    std::vector<opusgpu_frame_desc> descs; // all steps, step after step, `width` per slot
-    std::vector<opusgpu_track_seg> segs;   // one per slot
-    std::vector<int32_t> slot_files;       // one per slot
-    std::vector<size_t> step_begin;        // n_steps + 1, in slots
-    std::vector<int32_t> step_modes;
-    std::vector<uint8_t> arena;
-    std::vector<opusgpu_file_info> info;
-    std::vector<int64_t> packet_start; // all files, file after file
-    std::vector<size_t> packet_begin;  // n_files + 1
-    int64_t track_samples = 0;
-};
-struct opusgpu_file_batch : og_batch {};
-struct opusgpu_ms_file_batch : og_batch {
-    opusgpu_ms_layout layout{};
-};
 
 namespace {
 
@@ -343,13 +317,6 @@ const uint8_t *batch_arena(const og_batch *b, size_t *bytes) {
     return b->arena.data();
 }
 
-int64_t batch_packet_start(const og_batch *b, int file, int packet_seq) {
-    if (!b || file < 0 || file >= b->n_files || packet_seq < 0) return -1;
-    const size_t lo = b->packet_begin[file], hi = b->packet_begin[file + 1];
-    if ((size_t)packet_seq >= hi - lo) return -1;
-    return b->packet_start[lo + (size_t)packet_seq];
-}
-
 } // namespace
 
 extern "C" {
@@ -388,17 +355,9 @@ int opusgpu_file_batch_segments(const opusgpu_file_batch *b, int step, const opu
 const uint8_t *opusgpu_file_batch_arena(const opusgpu_file_batch *b, size_t *bytes) { return batch_arena(b, bytes); }
 int64_t opusgpu_file_batch_track_samples(const opusgpu_file_batch *b) { return b ? b->track_samples : -1; }
 int64_t opusgpu_file_batch_packet_start(const opusgpu_file_batch *b, int file, int packet_seq) {
-    return batch_packet_start(b, file, packet_seq);
+    return b ? b->packet_start_of(file, packet_seq) : -1;
 }
 void opusgpu_file_batch_free(opusgpu_file_batch *b) { delete b; }
-
-// (for opusgpu_files_decode, which lives with the kernels: csrc/og_tracks.hpp)
-int og_file_batch_shape(const opusgpu_file_batch *b, int *n_files, int *channels, int *mode) {
-    if (!b) return OPUSGPU_BAD_ARG;
-    *n_files = b->n_files, *channels = b->channels, *mode = b->mode;
-    return OPUSGPU_OK;
-}
-const opusgpu_file_info *og_file_batch_info(const opusgpu_file_batch *b) { return b ? b->info.data() : nullptr; }
 
 // ---- multistream files (include/opusgpu.h, WHOLE FILES / MULTISTREAM) ------------------------------------------------------
 int opusgpu_file_layout(const uint8_t *file, int64_t len, opusgpu_ms_layout *layout, opusgpu_file_info *info) {
@@ -459,16 +418,8 @@ int opusgpu_ms_file_batch_segments(const opusgpu_ms_file_batch *b, int step, con
 const uint8_t *opusgpu_ms_file_batch_arena(const opusgpu_ms_file_batch *b, size_t *bytes) { return batch_arena(b, bytes); }
 int64_t opusgpu_ms_file_batch_track_samples(const opusgpu_ms_file_batch *b) { return b ? b->track_samples : -1; }
 int64_t opusgpu_ms_file_batch_packet_start(const opusgpu_ms_file_batch *b, int file, int packet_seq) {
-    return batch_packet_start(b, file, packet_seq);
+    return b ? b->packet_start_of(file, packet_seq) : -1;
 }
 void opusgpu_ms_file_batch_free(opusgpu_ms_file_batch *b) { delete b; }
-
-// (for opusgpu_ms_files_decode: csrc/og_ms_tracks.hpp)
-int og_ms_file_batch_shape(const opusgpu_ms_file_batch *b, int *n_files, const opusgpu_ms_layout **layout, int *mode) {
-    if (!b) return OPUSGPU_BAD_ARG;
-    *n_files = b->n_files, *layout = &b->layout, *mode = b->mode;
-    return OPUSGPU_OK;
-}
-const opusgpu_file_info *og_ms_file_batch_info(const opusgpu_ms_file_batch *b) { return b ? b->info.data() : nullptr; }
 
 } // extern "C"

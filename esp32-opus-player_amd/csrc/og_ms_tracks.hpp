@@ -1,6 +1,6 @@
 // og_ms_tracks.hpp -- whole multistream files (include/opusgpu.h, WHOLE FILES / MULTISTREAM): the kernel that maps channels and
-// assembles tracks in one pass, and the call that drives a planned batch (og_files.cpp) through the ms steps.  Included at the end
-// of og_api.hip behind og_ms.hpp (opusgpu_ms, ms_step_impl) and og_tracks.hpp (TrackSeg, TrackState).
+// assembles tracks in one pass, and what the driver of a planned batch (og_files_run.hpp) needs of an opusgpu_ms.  Included at the
+// end of og_api.hip behind og_ms.hpp (opusgpu_ms, ms_step_impl) and og_tracks.hpp (TrackSeg, TrackState).
 #pragma once
 
 // ---- kernel -------------------------------------------------------------------------------------------
@@ -132,9 +132,6 @@ __global__ void __launch_bounds__(256) k_ms_tracks_assemble(const TrackSeg *__re
 }
 
 // ---- host side ----------------------------------------------------------------------------------------
-extern "C" int og_ms_file_batch_shape(const opusgpu_ms_file_batch *b, int *n_files, const opusgpu_ms_layout **layout, int *mode);
-extern "C" const opusgpu_file_info *og_ms_file_batch_info(const opusgpu_ms_file_batch *b);
-
 static int ms_tracks_launch(opusgpu_ms *ms, hipStream_t s, int n_segs, const void *d_segs, const void *pc, const void *pm, int row_samples,
                             const void *rc, const void *rm, void *d_tracks, void *d_track_state) {
     const opusgpu_ms_layout &L = ms->lay;
@@ -227,82 +224,36 @@ int opusgpu_ms_tracks_assemble_device(opusgpu_ms *ms, int n_segs, const void *d_
 
 int opusgpu_ms_files_decode(opusgpu_ms *ms, const opusgpu_ms_file_batch *batch, void *d_tracks, int64_t *track_lengths_out,
                             int32_t *status_out) {
-    int n_files = 0, mode = 0;
-    const opusgpu_ms_layout *lay = nullptr;
-    if (!ms || og_ms_file_batch_shape(batch, &n_files, &lay, &mode)) return OPUSGPU_BAD_ARG;
-    if (ms->n_dec < n_files || ms->mode != mode || ms->lay.channels > 8 || ms->lay.channels != lay->channels ||
-        ms->lay.streams != lay->streams || ms->lay.coupled != lay->coupled || memcmp(ms->lay.mapping, lay->mapping, sizeof lay->mapping))
+    if (!ms || !batch) return OPUSGPU_BAD_ARG;
+    const opusgpu_ms_layout &lay = batch->layout;
+    if (ms->n_dec < batch->n_files || ms->mode != batch->mode || ms->lay.channels > 8 || ms->lay.channels != lay.channels ||
+        ms->lay.streams != lay.streams || ms->lay.coupled != lay.coupled || memcmp(ms->lay.mapping, lay.mapping, sizeof lay.mapping))
         return OPUSGPU_BAD_ARG;
-    const opusgpu_file_info *info = og_ms_file_batch_info(batch);
-    const int n_steps = opusgpu_ms_file_batch_steps(batch);
-    const int row = mode == OPUSGPU_MODE_RFC ? OPUSGPU_RFC_FRAME_SAMPLES : OPUSGPU_FRAME_SAMPLES;
-    const size_t S = (size_t)lay->streams;
-    size_t total = 0;
-    for (int k = 0; k < n_steps; k++) total += (size_t)opusgpu_ms_file_batch_step(batch, k, nullptr, nullptr);
-    std::vector<TrackState> st((size_t)n_files, TrackState{INT32_MAX, 0});
-    if (total > 0) {
-        if (!d_tracks || ((uintptr_t)d_tracks & 127)) return OPUSGPU_BAD_ARG;
-        hipStream_t s = ms->stream;
-        int rc = ms_enter(ms, s);
-        if (rc) return rc;
-        // device copies of the batch; the tables of every step lie step after step behind step 0's (og_files.cpp)
-        struct Bufs {
-            void *p[4] = {};
-            ~Bufs() {
-                for (void *q : p)
-                    if (q) (void)hipFree(q);
-            }
-        } d;
-        void *&d_descs = d.p[0], *&d_segs = d.p[1], *&d_arena = d.p[2], *&d_state = d.p[3];
-        const opusgpu_frame_desc *descs = nullptr;
-        const opusgpu_track_seg *segs = nullptr;
-        size_t arena_bytes = 0;
-        const uint8_t *arena = opusgpu_ms_file_batch_arena(batch, &arena_bytes);
-        (void)opusgpu_ms_file_batch_step(batch, 0, &descs, nullptr);
-        (void)opusgpu_ms_file_batch_segments(batch, 0, &segs);
-        const size_t sizes[4] = {total * S * sizeof(opusgpu_frame_desc), total * sizeof(opusgpu_track_seg), arena_bytes,
-                                 (size_t)n_files * sizeof(TrackState)};
-        for (int i = 0; i < 4; i++) {
-            const hipError_t e = hipMalloc(&d.p[i], sizes[i] + 16);
-            if (e != hipSuccess) return ms_fail(ms, OPUSGPU_ALLOC_FAIL, "hipMalloc(files)", e);
-        }
-        MSCHK(ms, hipMemcpy(d_descs, descs, sizes[0], hipMemcpyHostToDevice));
-        MSCHK(ms, hipMemcpy(d_segs, segs, sizes[1], hipMemcpyHostToDevice));
-        MSCHK(ms, hipMemcpy(d_arena, arena, arena_bytes, hipMemcpyHostToDevice));
-        MSCHK(ms, hipMemcpy(d_state, st.data(), sizes[3], hipMemcpyHostToDevice));
-        if ((rc = opusgpu_ms_reset(ms, 0, n_files, 1))) return rc;
-        // The steps, each ending behind its two halves instead of in k_ms_map, the fused assembly behind it on the same stream.
-        // One set of elementary PCM and result buffers (the object's own) serves every step: step k + 1's stereo half is queued on
-        // `s` behind step k's assembly, and its mono half, on the mono context's stream, waits for ev_split, which step k + 1
-        // records on `s` -- behind step k's assembly too.  Step 0 is the largest, so the buffers do not move after it.
-        MsStepTimer timer(s);
-        size_t at = 0;
-        for (int k = 0; k < n_steps && !rc; k++) {
-            const int n = opusgpu_ms_file_batch_step(batch, k, nullptr, nullptr);
-            if (n <= 0) continue;
-            rc = ms_step_impl(ms, n, (const char *)d_descs + at * S * sizeof(opusgpu_frame_desc), d_arena, nullptr, nullptr, s, false);
-            if (!rc)
-                rc = ms_tracks_launch(ms, s, n, (const char *)d_segs + at * sizeof(opusgpu_track_seg), ms->d_pc, ms->d_pm, row, ms->d_rc,
-                                      ms->d_rm, d_tracks, d_state);
-            at += (size_t)n;
-        }
-        timer.stop();
-        const int rs = opusgpu_ms_synchronize(ms);
-        if (!rc) rc = rs;
-        if (!rc) g_ms_files_steps_ms = timer.elapsed_ms();
-        if (!rc) MSCHK(ms, hipMemcpy(st.data(), d_state, sizes[3], hipMemcpyDeviceToHost));
-        if (rc) return rc;
-    }
-    for (int i = 0; i < n_files; i++) {
-        const bool bad = st[i].first_bad != INT32_MAX;
-        if (track_lengths_out)
-            track_lengths_out[i] = bad ? opusgpu_ms_file_batch_packet_start(batch, i, st[i].first_bad) : info[i].track_samples;
-        if (status_out) {
-            status_out[2 * i] = bad ? st[i].code : info[i].status;
-            status_out[2 * i + 1] = bad ? st[i].first_bad : -1;
-        }
-    }
-    return OPUSGPU_OK;
+    const int row = batch->mode == OPUSGPU_MODE_RFC ? OPUSGPU_RFC_FRAME_SAMPLES : OPUSGPU_FRAME_SAMPLES;
+    hipStream_t s = ms->stream;
+    if (!batch->segs.empty())
+        if (int rc = ms_enter(ms, s)) return rc;
+    std::unique_ptr<MsStepTimer> timer;
+    FilesRunOps ops;
+    ops.device = ms->device;
+    ops.reset = [&](int n_files) { return opusgpu_ms_reset(ms, 0, n_files, 1); };
+    // Each step ends behind its two halves instead of in k_ms_map, the fused assembly behind it on the same stream.  One set of
+    // elementary PCM and result buffers (the object's own) serves every step: step k + 1's stereo half is queued on `s` behind step
+    // k's assembly, and its mono half, on the mono context's stream, waits for ev_split, which step k + 1 records on `s` -- behind
+    // step k's assembly too.  Step 0 is the largest, so the buffers do not move after it.
+    ops.step = [&](int, int n, const void *d_descs, const void *d_arena, int, void *const *) {
+        return ms_step_impl(ms, n, d_descs, d_arena, nullptr, nullptr, s, false);
+    };
+    ops.assemble = [&](int, int n, const void *d_segs, void *const *, void *d_state) {
+        return ms_tracks_launch(ms, s, n, d_segs, ms->d_pc, ms->d_pm, row, ms->d_rc, ms->d_rm, d_tracks, d_state);
+    };
+    ops.drain = [&] { return opusgpu_ms_synchronize(ms); };
+    ops.hip_failed = [&](int code, const char *what, hipError_t e) { return ms_fail(ms, code, what, e); };
+    ops.loop_begin = [&] { timer.reset(new MsStepTimer(s)); };
+    ops.loop_end = [&] { timer->stop(); };
+    const int rc = files_run(*batch, ops, d_tracks, track_lengths_out, status_out);
+    if (!rc && timer) g_ms_files_steps_ms = timer->elapsed_ms();
+    return rc;
 }
 
 } // extern "C"

@@ -53,6 +53,23 @@ inline int flags_frame_size(int32_t f) {
     return d == 1 ? 120 : d == 2 ? 240 : d == 3 ? 480 : d == 4 ? 1920 : d == 5 ? 2880 : 960;
 }
 
+// OPUSGPU_PAGES_ORDER_BY_HEADER: the sort key of a frame within its step, from its descriptor flags, its first byte and its length
+// (a frame of no bytes has no first byte: pass anything).  Within a step's SILK-only group and its hybrid group, frames go in the
+// order of their LBRR flags -- the range coder's second and fourth symbol, each of probability 1/2, i.e. bits 6 and 4 of the
+// frame's first byte (reference src/silk.cpp:1568-1573; a mono frame has only the first) -- stable otherwise.  An LBRR frame is a
+// whole extra frame of side information and pulses to read past (:1590-1616): 32 frames that agree on it make a parse wave that
+// skips those passes together.  The flags are four sub-keys of the callers' counting sorts (SILK 0..3, hybrid 4..7, CELT 8), not a
+// pass of their own.
+// (Bits 6 and 4 are where a frame DECODED AS 20 ms has them: one VAD bit, then the LBRR flag, per channel.  Reference mode decodes
+// every frame so, whatever duration its TOC names (Q6), and these steps exist in reference mode only; a 40 / 60 ms frame decoded at
+// its true duration would have two / three VAD bits in front of the flag.  The order never changes a result.)
+inline int header_order_key(int32_t flags, uint8_t first_byte, int32_t len) {
+    const int mode = flags & 3;
+    if (mode == 2) return 8;
+    if (len <= 0) return 4 * mode;
+    return 4 * mode + (int)((first_byte >> 6) & 1) + ((flags & 32) ? (int)((first_byte >> 4) & 1) << 1 : 0);
+}
+
 inline int read_size(const uint8_t *d, int32_t len, int16_t *size) {
     if (len < 1) { *size = -1; return -1; }
     if (d[0] < 252) { *size = d[0]; return 1; }

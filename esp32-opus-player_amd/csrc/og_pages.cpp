@@ -300,14 +300,7 @@ static int pages_demux_impl(int n_pages, const uint8_t *const *pages, const int3
         timer.mark("pass 2: chain streams");
         // slots: per step, pages in input order -- or grouped by mode first (three stable groups)
         const bool group = (flags & (OPUSGPU_PAGES_GROUP_BY_MODE | OPUSGPU_PAGES_ORDER_BY_HEADER)) != 0;
-        // ORDER_BY_HEADER: within a step's SILK-only group and its hybrid group, frames in the order of their LBRR flags -- the range
-        // coder's second and fourth symbol, each of probability 1/2, i.e. bits 6 and 4 of the frame's first byte (reference
-        // src/silk.cpp:1568-1573; a mono frame has only the first) -- stable otherwise.  An LBRR frame is a whole extra frame of side
-        // information and pulses to read past (:1590-1616): 32 frames that agree on it make a parse wave that skips those passes
-        // together.  The flags are four sub-keys of the counting sort below (SILK 0..3, hybrid 4..7, CELT 8), not a pass of their own.
-        // (Bits 6 and 4 are where a frame DECODED AS 20 ms has them: one VAD bit, then the LBRR flag, per channel.  Reference mode
-        // decodes every frame so, whatever duration its TOC names (Q6), and these steps exist in reference mode only; a 40 / 60 ms frame
-        // decoded at its true duration would have two / three VAD bits in front of the flag.  The order never changes a result.)
+        // ORDER_BY_HEADER: nine keys instead of three (ogh::header_order_key, og_packet.hpp)
         const bool by_header = (flags & OPUSGPU_PAGES_ORDER_BY_HEADER) != 0;
         const int G = group ? (by_header ? 9 : 3) : 1;
         RawBuf<uint8_t> mode_of; // sort key within a step (mode 0..2, or the nine keys above) per frame of every page, only when grouping
@@ -328,13 +321,7 @@ static int pages_demux_impl(int n_pages, const uint8_t *const *pages, const int3
                     if (by_header) { // the key needs every frame's first byte: the lacing walk again (no checksum this time)
                         const uint8_t *body = pages[i] + scan[i].header_len;
                         scan_page(pages[i], page_lens[i], 0, nullptr, [&](int k, int32_t off, int32_t len, int32_t fl) {
-                            const int mode = fl & 3;
-                            int key = mode == 2 ? 8 : 4 * mode;
-                            if (mode != 2 && len > 0) {
-                                const uint8_t b0 = body[off];
-                                key += (int)((b0 >> 6) & 1) | ((fl & 32) ? (int)((b0 >> 4) & 1) << 1 : 0);
-                            }
-                            mode_of[frame_at[i] + k] = (uint8_t)key;
+                            mode_of[frame_at[i] + k] = (uint8_t)ogh::header_order_key(fl, len > 0 ? body[off] : 0, len);
                         });
                         continue;
                     }

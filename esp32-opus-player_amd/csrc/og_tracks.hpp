@@ -1,6 +1,6 @@
-// og_tracks.hpp -- whole files (include/opusgpu.h, WHOLE FILES): the track assembly kernel and the call that drives a planned
-// batch (og_files.cpp) through the decode steps.  Included at the end of og_api.hip, whose contexts (og_ctx.hpp) and
-// decode_step_impl (og_step.hpp) it uses.
+// og_tracks.hpp -- whole files (include/opusgpu.h, WHOLE FILES): the track assembly kernel and what the driver of a planned batch
+// (og_files_run.hpp) needs of a context.  Included at the end of og_api.hip, whose contexts (og_ctx.hpp) and decode_step_impl
+// (og_step.hpp) it uses.
 #pragma once
 
 // ---- kernel -------------------------------------------------------------------------------------------
@@ -73,9 +73,6 @@ __global__ void __launch_bounds__(256) k_tracks_assemble(const TrackSeg *__restr
 }
 
 // ---- host side ----------------------------------------------------------------------------------------
-extern "C" int og_file_batch_shape(const opusgpu_file_batch *b, int *n_files, int *channels, int *mode);
-extern "C" const opusgpu_file_info *og_file_batch_info(const opusgpu_file_batch *b);
-
 static int tracks_assemble_launch(opusgpu_ctx *ctx, hipStream_t s, int n_segs, const void *d_segs, const void *d_pcm, int row_samples,
                                   const void *d_result, void *d_tracks, void *d_track_state) {
     hipLaunchKernelGGL(k_tracks_assemble, dim3((unsigned)n_segs), dim3(256), 0, s, (const TrackSeg *)d_segs, (const i16 *)d_pcm, row_samples,
@@ -100,79 +97,27 @@ int opusgpu_tracks_assemble_device(opusgpu_ctx *ctx, int n_segs, const void *d_s
 
 int opusgpu_files_decode(opusgpu_ctx *ctx, const opusgpu_file_batch *batch, void *d_tracks, int64_t *track_lengths_out,
                          int32_t *status_out) {
-    int n_files = 0, channels = 0, mode = 0;
-    if (!ctx || og_file_batch_shape(batch, &n_files, &channels, &mode)) return OPUSGPU_BAD_ARG;
-    if (!ctx->d_streams || ctx->n_streams < n_files || ctx->channels != channels || ctx->mode != mode) return OPUSGPU_BAD_ARG;
-    const opusgpu_file_info *info = og_file_batch_info(batch);
-    const int n_steps = opusgpu_file_batch_steps(batch);
-    const int row = mode == OPUSGPU_MODE_RFC ? OPUSGPU_RFC_FRAME_SAMPLES : OPUSGPU_FRAME_SAMPLES;
-    size_t total = 0, max_n = 0;
-    for (int k = 0; k < n_steps; k++) {
-        const size_t n = (size_t)opusgpu_file_batch_step(batch, k, nullptr, nullptr, nullptr);
-        total += n;
-        if (n > max_n) max_n = n;
-    }
-    std::vector<TrackState> st((size_t)n_files, TrackState{INT32_MAX, 0});
-    int rc = OPUSGPU_OK;
-    if (total > 0) {
-        if (!d_tracks || ((uintptr_t)d_tracks & 127)) return OPUSGPU_BAD_ARG;
-        HIPCHK(ctx, hipSetDevice(ctx->device));
-        // device copies of the batch; the tables of every step lie step after step behind step 0's (og_files.cpp)
-        struct Bufs {
-            void *p[6] = {};
-            ~Bufs() {
-                for (void *q : p)
-                    if (q) (void)hipFree(q);
-            }
-        } d;
-        void *&d_descs = d.p[0], *&d_segs = d.p[1], *&d_arena = d.p[2], *&d_pcm = d.p[3], *&d_res = d.p[4], *&d_state = d.p[5];
-        const opusgpu_frame_desc *descs = nullptr;
-        const opusgpu_track_seg *segs = nullptr;
-        size_t arena_bytes = 0;
-        const uint8_t *arena = opusgpu_file_batch_arena(batch, &arena_bytes);
-        (void)opusgpu_file_batch_step(batch, 0, &descs, nullptr, nullptr);
-        (void)opusgpu_file_batch_segments(batch, 0, &segs);
-        const size_t sizes[6] = {total * sizeof(opusgpu_frame_desc), total * sizeof(opusgpu_track_seg), arena_bytes,
-                                 max_n * (size_t)row * channels * 2, max_n * sizeof(int32_t), (size_t)n_files * sizeof(TrackState)};
-        for (int i = 0; i < 6; i++) {
-            const hipError_t e = hipMalloc(&d.p[i], sizes[i] + 16);
-            if (e != hipSuccess) return fail(ctx, OPUSGPU_ALLOC_FAIL, "hipMalloc(files)", e);
-        }
-        // complete in device memory before the first step: what pipelined steps ask of their tables
-        HIPCHK(ctx, hipMemcpy(d_descs, descs, sizes[0], hipMemcpyHostToDevice));
-        HIPCHK(ctx, hipMemcpy(d_segs, segs, sizes[1], hipMemcpyHostToDevice));
-        HIPCHK(ctx, hipMemcpy(d_arena, arena, arena_bytes, hipMemcpyHostToDevice));
-        HIPCHK(ctx, hipMemcpy(d_state, st.data(), sizes[5], hipMemcpyHostToDevice));
-        if ((rc = opusgpu_streams_reset(ctx, 0, n_files, 1))) return rc;
-        // The steps, the assembly of step k behind step k on the same stream.  One PCM buffer and one result buffer: whatever of
-        // step k + 1 runs ahead of step k (parse, reconstruction) touches neither, and the kernels that write them are queued on
-        // this stream -- or on one that forks from it -- behind the assembly that reads them.
-        size_t at = 0;
-        for (int k = 0; k < n_steps && !rc; k++) {
-            int modes = 0;
-            const int n = opusgpu_file_batch_step(batch, k, nullptr, nullptr, &modes);
-            if (n <= 0) continue;
-            rc = decode_step_impl(ctx, n, (const char *)d_descs + at * sizeof(opusgpu_frame_desc), d_arena, d_pcm, d_res, nullptr, true, modes);
-            if (!rc)
-                rc = tracks_assemble_launch(ctx, ctx->stream, n, (const char *)d_segs + at * sizeof(opusgpu_track_seg), d_pcm, row, d_res,
-                                            d_tracks, d_state);
-            at += (size_t)n;
-        }
+    if (!ctx || !batch) return OPUSGPU_BAD_ARG;
+    if (!ctx->d_streams || ctx->n_streams < batch->n_files || ctx->channels != batch->channels || ctx->mode != batch->mode)
+        return OPUSGPU_BAD_ARG;
+    const int row = batch->mode == OPUSGPU_MODE_RFC ? OPUSGPU_RFC_FRAME_SAMPLES : OPUSGPU_FRAME_SAMPLES;
+    FilesRunOps ops;
+    ops.device = ctx->device;
+    ops.extra_slot_bytes[0] = (size_t)row * batch->channels * 2, ops.extra_slot_bytes[1] = sizeof(int32_t); // PCM rows, result codes
+    ops.reset = [&](int n_files) { return opusgpu_streams_reset(ctx, 0, n_files, 1); };
+    ops.step = [&](int, int n, const void *d_descs, const void *d_arena, int modes, void *const *x) {
+        return decode_step_impl(ctx, n, d_descs, d_arena, x[0], x[1], nullptr, true, modes);
+    };
+    ops.assemble = [&](int, int n, const void *d_segs, void *const *x, void *d_state) {
+        return tracks_assemble_launch(ctx, ctx->stream, n, d_segs, x[0], row, x[1], d_tracks, d_state);
+    };
+    ops.drain = [&] {
         (void)sync_in_flight(ctx);
         const hipError_t e = hipStreamSynchronize(ctx->stream);
-        if (!rc && e != hipSuccess) rc = fail(ctx, OPUSGPU_ERR_HIP, "hipStreamSynchronize(files)", e);
-        if (!rc) HIPCHK(ctx, hipMemcpy(st.data(), d_state, sizes[5], hipMemcpyDeviceToHost));
-        if (rc) return rc;
-    }
-    for (int i = 0; i < n_files; i++) {
-        const bool bad = st[i].first_bad != INT32_MAX;
-        if (track_lengths_out) track_lengths_out[i] = bad ? opusgpu_file_batch_packet_start(batch, i, st[i].first_bad) : info[i].track_samples;
-        if (status_out) {
-            status_out[2 * i] = bad ? st[i].code : info[i].status;
-            status_out[2 * i + 1] = bad ? st[i].first_bad : -1;
-        }
-    }
-    return OPUSGPU_OK;
+        return e == hipSuccess ? (int)OPUSGPU_OK : fail(ctx, OPUSGPU_ERR_HIP, "hipStreamSynchronize(files)", e);
+    };
+    ops.hip_failed = [&](int code, const char *what, hipError_t e) { return fail(ctx, code, what, e); };
+    return files_run(*batch, ops, d_tracks, track_lengths_out, status_out);
 }
 
 } // extern "C"

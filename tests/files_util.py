@@ -248,32 +248,20 @@ def frame_toc(flags):
     return toc | (4 if stereo else 0)
 
 
-def model_decode(pkg, oracle, batch):
-    """What opusgpu_files_decode computes, on the oracle: every step's frames decoded one by one (a frame = a code-0 packet of
-    its descriptor's configuration, which is what the device decodes), the step's segments applied with the failure rules of
-    k_tracks_assemble.  -> (tracks [int16 [final length, channels]], final lengths, status [n, 2], planned frames seen)."""
+def model_apply(batch, step_tables, decode_slot):
+    """The part of the model both kinds of batch share: per step, every slot decoded -- decode_slot(k, slot, descriptors of the
+    slot, its file) -> (PCM rows or None, result) -- and the step's segments applied with the failure rules of the assembly
+    kernels; then the fold into lengths and status.  step_tables(k) -> (descriptors per slot, file per slot, segments).
+    -> (tracks [int16 [final length, channels]], final lengths, status [n, 2])."""
     ch, n = batch.channels, batch.n_files
     packed = np.zeros((max(int(batch.track_samples), 1), ch), dtype=np.int16)
     first_bad = np.full(n, INT32_MAX, dtype=np.int64)
     code = np.zeros(n, dtype=np.int32)
-    dec = {}
-    frames = []
     for k in range(batch.n_steps):
-        descs, files, segs, _ = batch.step(k)
+        descs, files, segs = step_tables(k)
         rows, res = {}, {}
         for slot, (d, f) in enumerate(zip(descs, files)):
-            assert d["stream"] == f
-            if f not in dec:
-                dec[f] = oracle.decoder(ch)
-                dec[f].init()
-                dec[f].set_rfc(batch.rfc)
-            toc = frame_toc(int(d["flags"]))
-            assert pkg.packet_to_frames(bytes([toc, 0, 0]))[0][2] == (int(d["flags"]) & 63), hex(toc)
-            body = bytes(batch.arena[d["offset"]:d["offset"] + d["len"]])
-            frames.append((int(f), k, body, int(d["flags"])))
-            buf, r = dec[f].decode(bytes([toc]) + body)
-            res[slot] = r
-            rows[slot] = buf[:max(r, 0)].copy()
+            rows[slot], res[slot] = decode_slot(k, slot, d, int(f))
         for sg in segs:
             t, slot = int(sg["track"]), int(sg["slot"])
             if res[slot] < 0:
@@ -288,8 +276,30 @@ def model_decode(pkg, oracle, batch):
                         for i in range(n)], dtype=np.int64)
     status = np.array([[code[i], first_bad[i]] if first_bad[i] != INT32_MAX else [batch.info["status"][i], -1] for i in range(n)],
                       dtype=np.int64).reshape(n, 2)
-    tracks = [packed[o:o + ln] for o, ln in zip(batch.info["track_offset"], lengths)]
-    return tracks, lengths, status, frames
+    return [packed[o:o + ln] for o, ln in zip(batch.info["track_offset"], lengths)], lengths, status
+
+
+def model_decode(pkg, oracle, batch):
+    """What opusgpu_files_decode computes, on the oracle: every step's frames decoded one by one (a frame = a code-0 packet of
+    its descriptor's configuration, which is what the device decodes), the step's segments applied with the failure rules of
+    k_tracks_assemble.  -> (tracks [int16 [final length, channels]], final lengths, status [n, 2], planned frames seen)."""
+    dec = {}
+    frames = []
+
+    def decode_slot(k, slot, d, f):
+        assert d["stream"] == f
+        if f not in dec:
+            dec[f] = oracle.decoder(batch.channels)
+            dec[f].init()
+            dec[f].set_rfc(batch.rfc)
+        toc = frame_toc(int(d["flags"]))
+        assert pkg.packet_to_frames(bytes([toc, 0, 0]))[0][2] == (int(d["flags"]) & 63), hex(toc)
+        body = bytes(batch.arena[d["offset"]:d["offset"] + d["len"]])
+        frames.append((f, k, body, int(d["flags"])))
+        buf, r = dec[f].decode(bytes([toc]) + body)
+        return buf[:max(r, 0)].copy(), r
+
+    return model_apply(batch, lambda k: batch.step(k)[:3], decode_slot) + (frames,)
 
 
 # ---- large batches (numpy all the way: the pure-Python page builder is too slow for them) ----------------------------------

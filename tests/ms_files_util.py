@@ -10,7 +10,6 @@ import files_util as fu
 import ms_util
 import ogg_util
 
-INT32_MAX = 2**31 - 1
 # 20 ms TOCs an elementary stream keeps for its whole file: SILK NB, hybrid FB, CELT FB, each mono and stereo (the stereo bit
 # disagrees with the decoder's channel count for half of them); TOC - 8 is the same configuration at 10 ms
 TOCS = [0x08, 0x0C, 0x78, 0x7C, 0xF8, 0xFC]
@@ -90,34 +89,15 @@ def model_decode(pkg, oracle, batch, layout):
     """What opusgpu_ms_files_decode computes, on the oracle: every row's elementary frames decoded one by one (a frame = a code-0
     packet of its descriptor's configuration) by an OracleMs, the step's segments applied with the failure rules of the assembly
     kernels.  -> (tracks [int16 [final length, channels]], final lengths, status [n, 2])."""
-    ch, n = batch.channels, batch.n_files
-    packed = np.zeros((max(int(batch.track_samples), 1), ch), dtype=np.int16)
-    first_bad = np.full(n, INT32_MAX, dtype=np.int64)
-    code = np.zeros(n, dtype=np.int32)
-    orc = ms_util.OracleMs(oracle, layout, n, rfc=batch.rfc)
-    for k in range(batch.n_steps):
-        descs, files, segs = batch.step(k)
-        rows, res = {}, {}
-        for r, (row, f) in enumerate(zip(descs, files)):
-            assert (row["stream"] == f).all()
-            el = [bytes([fu.frame_toc(int(d["flags"]))]) + bytes(batch.arena[d["offset"]:d["offset"] + d["len"]]) for d in row]
-            pcm, res[r] = orc.decode(int(f), el, 6)
-            rows[r] = None if pcm is None else pcm.copy()
-        for sg in segs:
-            t, r = int(sg["track"]), int(sg["slot"])
-            if res[r] < 0:
-                if sg["packet_seq"] < first_bad[t]:
-                    first_bad[t], code[t] = sg["packet_seq"], res[r]
-                continue
-            if sg["packet_seq"] >= first_bad[t] or sg["count"] <= 0:
-                continue
-            assert sg["src_first"] + sg["count"] <= res[r], (t, k, sg, res[r])
-            packed[sg["dst_first"]:sg["dst_first"] + sg["count"]] = rows[r][sg["src_first"]:sg["src_first"] + sg["count"]]
-    lengths = np.array([batch.packet_start(i, int(first_bad[i])) if first_bad[i] != INT32_MAX else batch.info["track_samples"][i]
-                        for i in range(n)], dtype=np.int64)
-    status = np.array([[code[i], first_bad[i]] if first_bad[i] != INT32_MAX else [batch.info["status"][i], -1] for i in range(n)],
-                      dtype=np.int64).reshape(n, 2)
-    return [packed[o:o + ln] for o, ln in zip(batch.info["track_offset"], lengths)], lengths, status
+    orc = ms_util.OracleMs(oracle, layout, batch.n_files, rfc=batch.rfc)
+
+    def decode_row(k, r, row, f):
+        assert (row["stream"] == f).all()
+        el = [bytes([fu.frame_toc(int(d["flags"]))]) + bytes(batch.arena[d["offset"]:d["offset"] + d["len"]]) for d in row]
+        pcm, res = orc.decode(f, el, 6)
+        return (None if pcm is None else pcm.copy()), res
+
+    return fu.model_apply(batch, batch.step, decode_row)
 
 
 def corpus(pkg, rng, layout, n_files, n_packets, rfc=False, per_page=4):
