@@ -1,8 +1,9 @@
 // og_host_framing.hpp -- what one packet of a host-buffer call becomes, decided ONCE (host code only: nothing of HIP is needed,
 // tests/emul/og_framing_test.cpp compiles it with a plain C++ compiler and tests/test_host_framing.py checks it on the CPU).
 //
-// opusgpu_decode_packets / _fec (og_host_path.hpp) and opusgpu_ms_decode_packets (og_ms.hpp) frame in two passes with the prefix
-// sums that place every packet between them: plan_packet is the first pass -- every result code, every count, the kind of the
+// opusgpu_decode_packets / _fec (og_host_path.hpp) and opusgpu_ms_decode_packets (through og_ms_framing.hpp's ms_plan_call: plan_packet
+// and plan_descs for its empty packets, remember_packet for its decoded ones) frame in two passes with the prefix sums that
+// place every packet between them: plan_packet is the first pass -- every result code, every count, the kind of the
 // packet --, plan_descs the second: it writes what the plan says and decides nothing.  The flags of a stream that has had no
 // packet yet and the stream memory an empty / lost packet is decoded from (last_count, last_flags) are spelled here and nowhere else.
 #pragma once

@@ -132,8 +132,8 @@ __global__ void __launch_bounds__(256) k_ms_tracks_assemble(const TrackSeg *__re
 }
 
 // ---- host side ----------------------------------------------------------------------------------------
-static int ms_tracks_launch(opusgpu_ms *ms, hipStream_t s, int n_segs, const void *d_segs, const void *pc, const void *pm, int row_samples,
-                            const void *rc, const void *rm, void *d_tracks, void *d_track_state) {
+static int ms_tracks_launch(opusgpu_ms *ms, hipStream_t s, int n_segs, const void *d_segs, const MsSrc src[2], int row_samples, void *d_tracks,
+                            void *d_track_state) {
     const opusgpu_ms_layout &L = ms->lay;
     // the streams the mapping uses, stereo ones first (stream order has them first), and where each lies in the staged tile
     MsTrackArgs a{};
@@ -163,9 +163,9 @@ static int ms_tracks_launch(opusgpu_ms *ms, hipStream_t s, int n_segs, const voi
     if (ts > row_samples + 16) ts = row_samples + 16;
     const size_t lds = (size_t)ts * D * 2 + (size_t)L.channels * 4;
     auto go = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3((unsigned)n_segs), dim3(256), lds, s, (const TrackSeg *)d_segs, (const i16 *)pc, (const i16 *)pm,
-                           row_samples, (const i32 *)rc, (const i32 *)rm, L.streams, L.coupled, a, ts, (i16 *)d_tracks,
-                           (TrackState *)d_track_state);
+        hipLaunchKernelGGL(kern, dim3((unsigned)n_segs), dim3(256), lds, s, (const TrackSeg *)d_segs, (const i16 *)src[0].pcm,
+                           (const i16 *)src[1].pcm, row_samples, (const i32 *)src[0].res, (const i32 *)src[1].res, L.streams, L.coupled, a, ts,
+                           (i16 *)d_tracks, (TrackState *)d_track_state);
     };
     switch (L.channels) { // files carry 1 - 8 channels: no general instance
         case 1: go(k_ms_tracks_assemble<1>); break;
@@ -213,13 +213,13 @@ int opusgpu_ms_tracks_assemble_device(opusgpu_ms *ms, int n_segs, const void *d_
                                       void *d_track_state, void *hip_stream) {
     if (!ms || n_segs < 0 || ms->lay.channels > 8) return OPUSGPU_BAD_ARG;
     if (n_segs == 0) return OPUSGPU_OK;
-    if (!d_segs || !d_tracks || !d_track_state || row_samples <= 0 || row_samples % 8 || ((uintptr_t)d_tracks & 127) ||
-        ((uintptr_t)d_segs & 7) || ((uintptr_t)d_pcm_coupled & 15) || ((uintptr_t)d_pcm_mono & 15) ||
-        (ms->lay.coupled && (!d_pcm_coupled || !d_res_coupled)) || (ms->mono && (!d_pcm_mono || !d_res_mono)))
+    if (!d_segs || !d_tracks || !d_track_state || row_samples <= 0 || row_samples % 8 || ((uintptr_t)d_tracks & 127) || ((uintptr_t)d_segs & 7))
         return OPUSGPU_BAD_ARG;
+    const MsSrc src[2] = {{d_pcm_coupled, row_samples * 2, d_res_coupled}, {d_pcm_mono, row_samples, d_res_mono}};
+    for (int h = 0; h < 2; h++)
+        if (((uintptr_t)src[h].pcm & 15) || (ms->half[h].streams && (!src[h].pcm || !src[h].res))) return OPUSGPU_BAD_ARG;
     MSCHK(ms, hipSetDevice(ms->device));
-    return ms_tracks_launch(ms, hip_stream ? (hipStream_t)hip_stream : ms->stream, n_segs, d_segs, d_pcm_coupled, d_pcm_mono, row_samples,
-                            d_res_coupled, d_res_mono, d_tracks, d_track_state);
+    return ms_tracks_launch(ms, hip_stream ? (hipStream_t)hip_stream : ms->stream, n_segs, d_segs, src, row_samples, d_tracks, d_track_state);
 }
 
 int opusgpu_ms_files_decode(opusgpu_ms *ms, const opusgpu_ms_file_batch *batch, void *d_tracks, int64_t *track_lengths_out,
@@ -238,14 +238,16 @@ int opusgpu_ms_files_decode(opusgpu_ms *ms, const opusgpu_ms_file_batch *batch, 
     ops.device = ms->device;
     ops.reset = [&](int n_files) { return opusgpu_ms_reset(ms, 0, n_files, 1); };
     // Each step ends behind its two halves instead of in k_ms_map, the fused assembly behind it on the same stream.  One set of
-    // elementary PCM and result buffers (the object's own) serves every step: step k + 1's stereo half is queued on `s` behind step
+    // elementary PCM and result buffers (the halves' own) serves every step: step k + 1's stereo half is queued on `s` behind step
     // k's assembly, and its mono half, on the mono context's stream, waits for ev_split, which step k + 1 records on `s` -- behind
     // step k's assembly too.  Step 0 is the largest, so the buffers do not move after it.
     ops.step = [&](int, int n, const void *d_descs, const void *d_arena, int, void *const *) {
         return ms_step_impl(ms, n, d_descs, d_arena, nullptr, nullptr, s, false);
     };
     ops.assemble = [&](int, int n, const void *d_segs, void *const *, void *d_state) {
-        return ms_tracks_launch(ms, s, n, d_segs, ms->d_pc, ms->d_pm, row, ms->d_rc, ms->d_rm, d_tracks, d_state);
+        MsSrc src[2];
+        ms_step_src(ms, row, src);
+        return ms_tracks_launch(ms, s, n, d_segs, src, row, d_tracks, d_state);
     };
     ops.drain = [&] { return opusgpu_ms_synchronize(ms); };
     ops.hip_failed = [&](int code, const char *what, hipError_t e) { return ms_fail(ms, code, what, e); };

@@ -52,9 +52,10 @@ def test_ms_host_path_matches_oracle(pkg, oracle, name):
     ms = pkg.MultistreamContext(0, n, ch, S, cp, mp)
     orc = OracleMs(oracle, layout, n)
     tocs = _stream_tocs(rng, layout, n)
-    # 20 ms steps, a step of two-frame packets, error rows, empty packets, a partial reset
+    # 20 ms steps, a step of two-frame packets, error rows, empty packets, a partial reset, two-frame packets with an error row (a
+    # failing first frame ends its stream's packet)
     plan = [(1, 1, ()), (1, 1, (2,)), (2, 2, ()), (1, 1, ()), ("empty", 2, ()), (1, 1, (0, 5)), ("reset", 0, ()), (1, 1, ()),
-            ("empty", 1, ())]
+            ("empty", 1, ()), (2, 2, (4,))]
     for k, (frames, cap, bad) in enumerate(plan):
         if frames == "reset":
             ms.reset(1, 2)

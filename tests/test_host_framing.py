@@ -1,5 +1,5 @@
 """The framing of the host-buffer path (csrc/og_host_framing.hpp) on the CPU: what opusgpu_decode_packets / _fec and
-opusgpu_ms_decode_packets decide about one packet -- plan_packet: result code, frame count, kind --, the descriptors plan_descs
+opusgpu_ms_decode_packets (through csrc/og_ms_framing.hpp, tests/test_ms_host_plan.py) decide about one packet -- plan_packet: result code, frame count, kind --, the descriptors plan_descs
 writes from that decision, the stream memory (last_count / last_flags) and conceal_pieces.  tests/emul/og_framing_test.cpp puts the
 header behind a C interface; nothing of the GPU or its runtime is needed.
 
