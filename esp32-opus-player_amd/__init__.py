@@ -33,10 +33,11 @@ EXPORTS = [
     "opusgpu_ms_packet_to_frames", "opusgpu_ms_decode_packets", "opusgpu_ms_decode_step_device", "opusgpu_ms_synchronize",
     "opusgpu_files_plan", "opusgpu_file_batch_steps", "opusgpu_file_batch_step", "opusgpu_file_batch_segments", "opusgpu_file_batch_arena",
     "opusgpu_file_batch_track_samples", "opusgpu_file_batch_packet_start", "opusgpu_file_batch_free", "opusgpu_tracks_assemble_device",
-    "opusgpu_files_decode",
+    "opusgpu_files_decode", "opusgpu_head_gain_scale", "opusgpu_tracks_assemble_device_as", "opusgpu_files_decode_as",
     "opusgpu_file_layout", "opusgpu_ms_files_plan", "opusgpu_ms_file_batch_steps", "opusgpu_ms_file_batch_step", "opusgpu_ms_file_batch_segments",
     "opusgpu_ms_file_batch_arena", "opusgpu_ms_file_batch_track_samples", "opusgpu_ms_file_batch_packet_start", "opusgpu_ms_file_batch_free",
     "opusgpu_ms_tracks_assemble_device", "opusgpu_ms_files_decode", "opusgpu_ms_files_last_steps_ms",
+    "opusgpu_ms_tracks_assemble_device_as", "opusgpu_ms_files_decode_as",
 ]
 
 
@@ -109,6 +110,10 @@ TRACK_SEG_DTYPE = np.dtype([("slot", "<i4"), ("src_first", "<i4"), ("count", "<i
 TRACK_STATE_DTYPE = np.dtype([("first_bad", "<i4"), ("code", "<i4")])
 FILE_INFO_DTYPE = np.dtype([("status", "<i4"), ("channels", "<i4"), ("pre_skip", "<i4"), ("output_gain", "<i4"), ("mapping_family", "<i4"),
                             ("packets", "<i4"), ("frames", "<i4"), ("holes", "<i4"), ("track_samples", "<i8"), ("track_offset", "<i8")])
+# opusgpu_track_place and the OPUSGPU_TRACKS_* formats (include/opusgpu.h, TRACK FORMATS)
+TRACK_PLACE_DTYPE = np.dtype([("track_offset", "<i8"), ("plane_samples", "<i8"), ("scale", "<f4"), ("reserved", "<i4")])
+TRACKS_S16, TRACKS_F32, TRACKS_F32_PLANAR = 0, 1, 2
+TRACK_FORMATS = {"s16": TRACKS_S16, "f32": TRACKS_F32, "f32_planar": TRACKS_F32_PLANAR}
 OPUSGPU_BAD_ARG, OPUSGPU_UNIMPLEMENTED, OPUSGPU_CELT_BAD_ARG = -1, -5, -18
 RFC_FRAME = 2880
 
@@ -194,6 +199,10 @@ def load_lib():
     lib.opusgpu_files_plan.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.POINTER(vp)]
     lib.opusgpu_tracks_assemble_device.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp]
     lib.opusgpu_files_decode.argtypes = [vp, vp, vp, vp, vp]
+    lib.opusgpu_head_gain_scale.argtypes = [C.c_int32]
+    lib.opusgpu_head_gain_scale.restype = C.c_float
+    lib.opusgpu_tracks_assemble_device_as.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp]
+    lib.opusgpu_files_decode_as.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp]
     lib.opusgpu_file_layout.argtypes = [vp, C.c_int64, C.POINTER(MsLayout), vp]
     lib.opusgpu_ms_files_plan.argtypes = [C.c_int, vp, vp, C.POINTER(MsLayout), C.c_int, C.c_int, vp, C.POINTER(vp)]
     for prefix, step_more in (("opusgpu_file_batch", [C.POINTER(C.c_int)]), ("opusgpu_ms_file_batch", [])):
@@ -212,6 +221,8 @@ def load_lib():
         f("free").restype = None
     lib.opusgpu_ms_tracks_assemble_device.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp]
     lib.opusgpu_ms_files_decode.argtypes = [vp, vp, vp, vp, vp]
+    lib.opusgpu_ms_tracks_assemble_device_as.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp]
+    lib.opusgpu_ms_files_decode_as.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp]
     lib.opusgpu_ms_files_last_steps_ms.restype = C.c_float
     _lib = lib
     return lib
@@ -479,26 +490,87 @@ class MsFileBatch(_PlannedFiles):
         return descs.reshape(-1, self.streams), files, segs
 
 
-def _decode_planned(lib, chk, name, handle, batch, mem):
-    """The shared body of the two decode_files: runs the decode call `name` of `lib` for the decoder `handle` over `batch` into a
-    track buffer from `mem` (a Context: dev_alloc, d2h, dev_free); chk(code, what) raises.  -> (tracks, info)."""
-    n = batch.n_files
-    total = max(int(batch.track_samples), 1) * batch.channels
-    d_tracks = mem.dev_alloc(2 * total)
-    try:
-        lengths = np.zeros(n, dtype=np.int64)
-        status = np.zeros((n, 2), dtype=np.int32)
-        chk(getattr(lib, name)(handle, batch.h, d_tracks, lengths.ctypes.data, status.ctypes.data), name)
-        packed = np.zeros(total, dtype=np.int16)
-        mem.d2h(packed, d_tracks)
-    finally:
-        mem.dev_free(d_tracks)
-    packed = packed.reshape(-1, batch.channels)
+def head_gain_scale(output_gain_q8):
+    """opusgpu_head_gain_scale: an OpusHead output gain (Q7.8 dB) as the linear factor of the float track formats, 1 / 32768 folded in."""
+    return np.float32(load_lib().opusgpu_head_gain_scale(int(output_gain_q8)))
+
+
+def track_format_args(batch, format="s16", scale=None, out=None, device=0):
+    """What decode_files makes of its format=, scale= and out= for a planned batch, before any device work: -> (OPUSGPU_TRACKS_*
+    value, float32 scale array or None, out flattened or None).  Raises ValueError for a format that does not exist, a scale with
+    "s16" or of the wrong length or not finite, and an `out` that is not a contiguous torch tensor on GPU `device`, of the format's
+    dtype, 128-byte aligned, with at least track_samples * channels elements."""
+    if format not in TRACK_FORMATS:
+        raise ValueError(f"format must be one of {sorted(TRACK_FORMATS)}, not {format!r}")
+    fmt = TRACK_FORMATS[format]
+    if scale is not None:
+        if fmt == TRACKS_S16:
+            raise ValueError("scale needs a float format: int16 tracks are not scaled")
+        if isinstance(scale, str):
+            if scale != "head_gain":
+                raise ValueError(f"scale must be None, 'head_gain' or an array, not {scale!r}")
+            scale = [head_gain_scale(g) for g in batch.info["output_gain"]]
+        scale = np.ascontiguousarray(scale, dtype=np.float32)
+        if scale.shape != (batch.n_files,):
+            raise ValueError(f"scale must have one entry per file ({batch.n_files}), not shape {scale.shape}")
+        if not np.isfinite(scale).all():
+            raise ValueError("scale entries must be finite")
+    if out is not None:
+        need, dtype = max(int(batch.track_samples), 1) * batch.channels, "torch.int16" if fmt == TRACKS_S16 else "torch.float32"
+        if not hasattr(out, "data_ptr") or not hasattr(out, "is_cuda"):
+            raise ValueError("out must be a torch tensor")
+        if not out.is_cuda or out.device.index != device:
+            raise ValueError(f"out must be on GPU {device}, not on {out.device}")
+        if str(out.dtype) != dtype:
+            raise ValueError(f"out must be of dtype {dtype} for format {format!r}, not {out.dtype}")
+        if not out.is_contiguous():
+            raise ValueError("out must be contiguous")
+        if out.numel() < need:
+            raise ValueError(f"out is too small: {out.numel()} elements, {need} needed")
+        if out.data_ptr() % 128:
+            raise ValueError("out must be 128-byte aligned")
+        out = out.view(-1)
+    return fmt, scale, out
+
+
+def _decode_planned(lib, chk, name, handle, batch, mem, args):
+    """The shared body of the two decode_files: runs the decode call `name` of `lib` (`name`_as for a float format) for the decoder
+    `handle` over `batch` into `out` (a torch tensor on the device: nothing comes to the host) or into a track buffer from `mem` (a
+    Context: dev_alloc, d2h, dev_free); args: what track_format_args returned; chk(code, what) raises.  -> (tracks, info)."""
+    fmt, scale, out = args
+    n, ch = batch.n_files, batch.channels
+    total = max(int(batch.track_samples), 1) * ch
+    lengths = np.zeros(n, dtype=np.int64)
+    status = np.zeros((n, 2), dtype=np.int32)
+
+    def run(d_tracks):
+        if fmt == TRACKS_S16:
+            chk(getattr(lib, name)(handle, batch.h, d_tracks, lengths.ctypes.data, status.ctypes.data), name)
+        else:
+            chk(getattr(lib, name + "_as")(handle, batch.h, fmt, None if scale is None else scale.ctypes.data, d_tracks,
+                                           lengths.ctypes.data, status.ctypes.data), name + "_as")
+    if out is not None:
+        import torch
+        torch.cuda.current_stream(out.device).synchronize()  # whatever filled `out` has finished; the call itself waits for its own work
+        run(out.data_ptr())
+        packed = out
+    else:
+        packed = np.zeros(total, dtype=np.int16 if fmt == TRACKS_S16 else np.float32)
+        d_tracks = mem.dev_alloc(packed.nbytes)
+        try:
+            run(d_tracks)
+            mem.d2h(packed, d_tracks)
+        finally:
+            mem.dev_free(d_tracks)
     info = np.zeros(n, dtype=np.dtype(FILE_INFO_DTYPE.descr + [("final_status", "<i4"), ("bad_packet", "<i4")]))
     for field in FILE_INFO_DTYPE.names:
         info[field] = batch.info[field]
     info["track_samples"], info["final_status"], info["bad_packet"] = lengths, status[:, 0], status[:, 1]
-    tracks = [packed[o:o + ln] for o, ln in zip(batch.info["track_offset"], lengths)]
+    if fmt == TRACKS_F32_PLANAR:  # track t: `ch` planes of its planned length rounded up to 64, where its interleaved form would lie
+        planes = (batch.info["track_samples"] + 63) // 64 * 64
+        tracks = [packed[ch * o:ch * (o + p)].reshape(ch, p)[:, :ln] for o, p, ln in zip(batch.info["track_offset"], planes, lengths)]
+    else:
+        tracks = [packed[ch * o:ch * (o + ln)].reshape(ln, ch) for o, ln in zip(batch.info["track_offset"], lengths)]
     return tracks, info
 
 
@@ -513,6 +585,7 @@ class Context:
             raise OpusGpuError(f"opusgpu_ctx_create(device={device}) failed with {rc}"
                                + (" (no usable HIP device; no CPU fallback exists)" if rc == OPUSGPU_ERR_NO_DEVICE else ""))
         self.h = h
+        self.device = device
         self.channels = 0
         self.n_streams = 0
 
@@ -664,21 +737,32 @@ class Context:
         self._chk(self.lib.opusgpu_tracks_assemble_device(self.h, n_segs, d_segs, d_pcm, row_samples, d_result, d_tracks, d_track_state,
                                                           stream), "opusgpu_tracks_assemble_device")
 
-    def decode_files(self, files, rfc=False, flags=PAGES_GROUP_BY_MODE, threads=1, batch=None):
+    def tracks_assemble_device_as(self, n_segs, d_segs, d_pcm, row_samples, d_result, format, d_place, d_tracks, d_track_state, stream=None):
+        """opusgpu_tracks_assemble_device_as: the same into tracks of `format` (TRACKS_*), d_place a device array of TRACK_PLACE_DTYPE."""
+        self._chk(self.lib.opusgpu_tracks_assemble_device_as(self.h, n_segs, d_segs, d_pcm, row_samples, d_result, format, d_place, d_tracks,
+                                                             d_track_state, stream), "opusgpu_tracks_assemble_device_as")
+
+    def decode_files(self, files, rfc=False, flags=PAGES_GROUP_BY_MODE, threads=1, batch=None, format="s16", scale=None, out=None):
         """Whole Ogg Opus files -> (list of int16 arrays [samples, channels], one trimmed track per file, info).  The context's
         streams 0 .. len(files) - 1 are (re)allocated when there are too few and get fresh state; its mode is set to `rfc`.
         info: FILE_INFO_DTYPE records with two more fields: `final_status` (the first failed frame's code, else the plan's status)
         and `bad_packet` (that frame's packet, or -1); `track_samples` is the FINAL length.  batch: a FileBatch made beforehand
-        from the same files (its channels and mode must be the context's)."""
+        from the same files (its channels and mode must be the context's).
+        format: "s16", or "f32" (float32 [samples, channels]) or "f32_planar" (float32 [channels, samples]), every sample the
+        int16 one times scale (include/opusgpu.h TRACK FORMATS).  scale: None (1 / 32768), "head_gain" (each file's OpusHead output
+        gain applied as well) or one float per file.  out: a contiguous torch tensor on this context's GPU, of the format's dtype,
+        128-byte aligned, with at least track_samples * channels elements: the tracks are decoded straight into it, nothing is
+        copied to the host, and the tracks returned are views of it (ValueError before any device work if it does not fit)."""
         own = batch is None
         channels = self.channels or 2
         if own:
             batch = FileBatch(files, channels=channels, rfc=rfc, flags=flags, threads=threads)
         try:
+            args = track_format_args(batch, format, scale, out, self.device)
             if self.n_streams < batch.n_files or self.channels != batch.channels:
                 self.streams_alloc(max(batch.n_files, 1), batch.channels)
             self.set_mode(batch.rfc)
-            return _decode_planned(self.lib, self._chk, "opusgpu_files_decode", self.h, batch, self)
+            return _decode_planned(self.lib, self._chk, "opusgpu_files_decode", self.h, batch, self, args)
         finally:
             if own:
                 batch.close()
@@ -838,20 +922,31 @@ class MultistreamContext:
                                                              d_res_mono, d_tracks, d_track_state, stream),
                   "opusgpu_ms_tracks_assemble_device")
 
-    def decode_files(self, files, rfc=False, threads=1, batch=None):
+    def tracks_assemble_device_as(self, n_segs, d_segs, d_pcm_coupled, d_pcm_mono, row_samples, d_res_coupled, d_res_mono, format, d_place,
+                                  d_tracks, d_track_state, stream=None):
+        """opusgpu_ms_tracks_assemble_device_as: the same into tracks of `format` (TRACKS_*), d_place a device array of TRACK_PLACE_DTYPE."""
+        self._chk(self.lib.opusgpu_ms_tracks_assemble_device_as(self.h, n_segs, d_segs, d_pcm_coupled, d_pcm_mono, row_samples, d_res_coupled,
+                                                                d_res_mono, format, d_place, d_tracks, d_track_state, stream),
+                  "opusgpu_ms_tracks_assemble_device_as")
+
+    def decode_files(self, files, rfc=False, threads=1, batch=None, format="s16", scale=None, out=None):
         """Whole Ogg Opus files of this object's layout -> (list of int16 arrays [samples, channels], one trimmed track per file,
         info), as Context.decode_files returns them: FILE_INFO_DTYPE records plus `final_status` and `bad_packet`, `track_samples`
         the FINAL length.  Decoders 0 .. len(files) - 1 get fresh state; the object's mode is set to the batch's.  batch: an
-        MsFileBatch made beforehand from the same files (of this layout; `rfc` is then the batch's)."""
+        MsFileBatch made beforehand from the same files (of this layout; `rfc` is then the batch's).  format, scale, out: as for
+        Context.decode_files."""
         own = batch is None
         if own:
             batch = MsFileBatch(files, self.layout, rfc=rfc, threads=threads)
-        mem = Context(self.device)  # (device memory and copies are a plain context's calls)
+        mem = None
         try:
+            args = track_format_args(batch, format, scale, out, self.device)
+            mem = Context(self.device)  # (device memory and copies are a plain context's calls)
             self.set_mode(batch.rfc)
-            return _decode_planned(self.lib, self._chk, "opusgpu_ms_files_decode", self.h, batch, mem)
+            return _decode_planned(self.lib, self._chk, "opusgpu_ms_files_decode", self.h, batch, mem, args)
         finally:
-            mem.close()
+            if mem is not None:
+                mem.close()
             if own:
                 batch.close()
 

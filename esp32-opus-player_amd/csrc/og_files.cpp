@@ -8,6 +8,7 @@
 // arena and write descriptors and segments into their slots.
 // opusgpu_ms_files_plan (WHOLE FILES / MULTISTREAM) is the same three passes and the same reader loop; its frames are rows of
 // `streams` descriptors, framed by opusgpu_ms_packet_to_frames.
+#include <math.h>
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
@@ -354,6 +355,7 @@ int opusgpu_file_batch_segments(const opusgpu_file_batch *b, int step, const opu
 }
 const uint8_t *opusgpu_file_batch_arena(const opusgpu_file_batch *b, size_t *bytes) { return batch_arena(b, bytes); }
 int64_t opusgpu_file_batch_track_samples(const opusgpu_file_batch *b) { return b ? b->track_samples : -1; }
+float opusgpu_head_gain_scale(int32_t output_gain_q8) { return (float)(pow(10.0, output_gain_q8 / 5120.0) / 32768.0); }
 int64_t opusgpu_file_batch_packet_start(const opusgpu_file_batch *b, int file, int packet_seq) {
     return b ? b->packet_start_of(file, packet_seq) : -1;
 }

@@ -586,6 +586,50 @@ int opusgpu_tracks_assemble_device(opusgpu_ctx *ctx, int n_segs, const void *d_s
 int opusgpu_files_decode(opusgpu_ctx *ctx, const opusgpu_file_batch *batch, void *d_tracks, int64_t *track_lengths_out,
                          int32_t *status_out);
 
+/* TRACK FORMATS.  opusgpu_files_decode ends at interleaved int16, what parity with the reference is judged on.  The calls below
+ * write the tracks in the form a consumer converts them to anyway, in the same pass:
+ *   VALUE.  Every float sample is (float)s * scale[track]: s the int16 sample the S16 path writes at that place (multistream: after
+ *   the channel mapping, a muted channel is 0), one IEEE single-precision multiply, nothing fused or contracted -- the float tracks
+ *   are a pure function of the S16 tracks, bit for bit.  The default scale is 1.0f / 32768, which is exact.
+ *   LAYOUT.  The packed buffer has opusgpu_file_batch_track_samples x channels elements whatever the format, of 4 bytes for the float
+ *   formats.  OPUSGPU_TRACKS_F32: the element index is the S16 element index.  OPUSGPU_TRACKS_F32_PLANAR: sample n of channel c of
+ *   track t is element  channels * track_offset[t] + c * plane[t] + n,  plane[t] = the track's PLANNED track_samples rounded up to
+ *   64.  The planner packs tracks at multiples of 64 samples and begins the next track at the rounded-up end of this one
+ *   (opusgpu_file_info.track_offset), so the planes of track t fill exactly the elements its interleaved form would, and every
+ *   plane begins on a 256-byte boundary.  A track cut short by a failed frame keeps its planned plane stride; only its reported
+ *   length shrinks.
+ *   FAILED FRAMES are what they are above: a failed frame writes nothing and lowers first_bad, segments at or behind first_bad
+ *   write nothing, the final length is the planned start of the failing packet, elements past it are unspecified.  Padding between
+ *   tracks and between planes is never written. */
+#define OPUSGPU_TRACKS_S16 0        /* interleaved int16: what opusgpu_files_decode writes */
+#define OPUSGPU_TRACKS_F32 1        /* interleaved float32, same sample positions */
+#define OPUSGPU_TRACKS_F32_PLANAR 2 /* float32, one contiguous plane per channel and track */
+typedef struct opusgpu_track_place { /* 24 bytes, one per track, read by the float kernels through opusgpu_track_seg.track (ABI) */
+    int64_t track_offset;  /* where the track begins in the packed buffer, samples per channel; a multiple of 64 */
+    int64_t plane_samples; /* planar: distance between the track's planes in samples, a multiple of 64; interleaved: not read */
+    float scale;
+    int32_t reserved;      /* 0 */
+} opusgpu_track_place;
+/* The OpusHead output gain (Q7.8 dB, RFC 7845 section 5.1; opusgpu_file_info.output_gain) as a linear factor, folded with the
+ * 1 / 32768 of the float formats: (float)(pow(10, q8 / 5120.0) / 32768).  Host only. */
+float opusgpu_head_gain_scale(int32_t output_gain_q8);
+/* opusgpu_tracks_assemble_device for any format.  OPUSGPU_TRACKS_S16 with d_place NULL is that call; S16 with a d_place, or an
+ * unknown format, is OPUSGPU_BAD_ARG.  For the float formats d_tracks holds floats (128-byte aligned, as above) and d_place is a
+ * device array of opusgpu_track_place, 8-byte aligned, with a record for every `track` the segments name.  Planar: the caller
+ * guarantees track_offset <= dst_first of the track's segments, both multiples as the record says, and that the planes lie inside
+ * the buffer.  The other alignment rules and guarantees are those of opusgpu_tracks_assemble_device. */
+int opusgpu_tracks_assemble_device_as(opusgpu_ctx *ctx, int n_segs, const void *d_segs, const void *d_pcm, int row_samples,
+                                      const void *d_result, int format, const void *d_place, void *d_tracks, void *d_track_state,
+                                      void *hip_stream);
+/* opusgpu_files_decode into tracks of `format`.  scale: host array of n_files floats, or NULL for 1 / 32768 each.  With
+ * OPUSGPU_TRACKS_S16 and scale NULL this is opusgpu_files_decode; S16 with a scale is OPUSGPU_BAD_ARG (integer gain has rounding
+ * rules of its own and is not offered), as are an unknown format and a scale entry that is not finite.  d_tracks:
+ * opusgpu_file_batch_track_samples x channels elements of the format, 128-byte aligned.  The place table is built from the batch,
+ * uploaded before the first step and freed before the call returns, also when it fails; steps, buffers and ordering are those of
+ * opusgpu_files_decode -- none of them depends on the format. */
+int opusgpu_files_decode_as(opusgpu_ctx *ctx, const opusgpu_file_batch *batch, int format, const float *scale, void *d_tracks,
+                            int64_t *track_lengths_out, int32_t *status_out);
+
 /* ---- WHOLE FILES / MULTISTREAM: N surround Ogg Opus files in, N trimmed interleaved tracks in HBM out -----------------------------
  * The two sections above joined: files whose OpusHead carries channel mapping family 1 (1 - 8 channels, `streams` elementary
  * streams) are planned by the same reader-driven loop as stereo files and decoded by an opusgpu_ms of their layout.  The reader's
@@ -654,6 +698,14 @@ int opusgpu_ms_files_decode(opusgpu_ms *ms, const opusgpu_ms_file_batch *batch, 
  * opusgpu_ms_files_decode -- split, both halves and the assembly of every step, without the upload and the reset in front of them
  * (events on the object's stream around the loop); -1 before the first call. */
 float opusgpu_ms_files_last_steps_ms(void);
+/* The two calls above for any track format (TRACK FORMATS in WHOLE FILES: value, layout, scale and the place record are the same,
+ * `channels` the layout's; planar: output channel c's plane is decoded channel mapping[c] scaled, or zeros for 255).  Arguments,
+ * refusals and alignment as opusgpu_tracks_assemble_device_as / opusgpu_files_decode_as say. */
+int opusgpu_ms_tracks_assemble_device_as(opusgpu_ms *ms, int n_segs, const void *d_segs, const void *d_pcm_coupled,
+                                         const void *d_pcm_mono, int row_samples, const void *d_res_coupled, const void *d_res_mono,
+                                         int format, const void *d_place, void *d_tracks, void *d_track_state, void *hip_stream);
+int opusgpu_ms_files_decode_as(opusgpu_ms *ms, const opusgpu_ms_file_batch *batch, int format, const float *scale, void *d_tracks,
+                               int64_t *track_lengths_out, int32_t *status_out);
 
 #ifdef __cplusplus
 }

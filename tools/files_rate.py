@@ -6,7 +6,9 @@ pre-skips and end trims, planned once and decoded device-resident.  Per batch of
 (c), the kernel's own time, comes from a kernel trace: run this script under `rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o files --`
 and then `python3 tools/files_rate.py --stats DIR` reads DIR's kernel_stats.csv (bytes read + written per launch: 2 x the step's
 kept samples x 4).  Also: the planner's files/s on --threads threads next to opusgpu_pages_demux's pages/s on the same pages.
-usage (GPU box): python3 tools/files_rate.py [--n N] [--reps R] | python3 tools/files_rate.py --stats DIR [--n N]"""
+--format f32 | f32_planar: the whole call per track format instead (tools/format_rate.py), in order and pipelined; --stats then
+reads the float kernels' rows too (6 bytes moved per sample and channel instead of 4).
+usage (GPU box): python3 tools/files_rate.py [--n N] [--reps R] [--format F] | python3 tools/files_rate.py --stats DIR [--n N]"""
 import argparse
 import ctypes as C
 import glob
@@ -20,13 +22,18 @@ import numpy as np
 
 here = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(here, "..", "tests"))
+sys.path.insert(0, here)
 ap = argparse.ArgumentParser()
 ap.add_argument("--n", type=int, default=65536)
 ap.add_argument("--reps", type=int, default=10)
 ap.add_argument("--threads", type=int, default=16)
 ap.add_argument("--stats", default=None)
+ap.add_argument("--format", choices=["f32", "f32_planar"], default=None,
+                help="compare the whole decode call: int16 tracks, int16 + conversion in torch, the fused float format (tools/format_rate.py)")
 args = ap.parse_args()
 n = args.n
+if args.format:
+    import torch  # before the library: one HIP runtime for both
 
 spec = importlib.util.spec_from_file_location("esp32_opus_player_amd", os.path.join(here, "..", "esp32-opus-player_amd", "__init__.py"))
 pkg = importlib.util.module_from_spec(spec)
@@ -43,11 +50,24 @@ if args.stats:
     for f in glob.glob(os.path.join(args.stats, "**", "*kernel_stats.csv"), recursive=True):
         rows += [r for r in csv.DictReader(open(f)) if "k_tracks_assemble" in r["Name"]]
     assert rows, "no k_tracks_assemble in the kernel statistics"
-    r = rows[0]
-    avg_ms = float(r["AverageNs"]) / 1e6
-    print(json.dumps({"kernel": "k_tracks_assemble", "calls": int(r["Calls"]), "avg_ms_per_launch": round(avg_ms, 4),
-                      "min_ms": round(float(r["MinNs"]) / 1e6, 4), "ms_per_batch_of_10": round(avg_ms * 10, 3),
-                      "bytes_per_batch": MOVED, "tb_per_s": round(MOVED / 10 / (avg_ms / 1e3) / 1e12, 2)}))
+    for r in rows:
+        avg_ms = float(r["AverageNs"]) / 1e6
+        moved = MOVED * 3 // 2 if "_f32" in r["Name"] else MOVED  # float tracks: 2 bytes in, 4 bytes out
+        print(json.dumps({"kernel": r["Name"].split("(")[0], "calls": int(r["Calls"]), "avg_ms_per_launch": round(avg_ms, 4),
+                          "min_ms": round(float(r["MinNs"]) / 1e6, 4), "ms_per_batch_of_10": round(avg_ms * 10, 3),
+                          "bytes_per_batch": moved, "tb_per_s": round(moved / 10 / (avg_ms / 1e3) / 1e12, 2)}))
+    raise SystemExit(0)
+
+if args.format:
+    import format_rate
+    b = pkg.FileBatch([r.tobytes() for r in files], channels=2, flags=pkg.PAGES_GROUP_BY_MODE, threads=args.threads)
+    assert (b.info["status"] == 0).all() and b.n_steps == 10
+    ctx = pkg.Context(0)
+    ctx.streams_alloc(n, 2)
+    for name, pipe in (("in_order", 0), ("pipelined", 1)):
+        ctx.set_pipeline(pipe)
+        print(json.dumps(format_rate.compare(torch, pkg, ctx.lib.opusgpu_files_decode_as, ctx.h, ctx._chk, b, args.format, args.reps, name)))
+    ctx.close()
     raise SystemExit(0)
 
 # ---- planner and page demux rates ----------------------------------------------------------------------

@@ -9,8 +9,10 @@ interleaved:
     batch first, so its steps are timed by the library itself, with events around the step loop (opusgpu_ms_files_last_steps_ms).
 The kernels' own times come from a kernel trace: run this script under `rocprofv3 --kernel-trace --stats --output-format csv -d DIR
 -o msfiles --` and then `python3 tools/ms_files_rate.py --stats DIR` reads DIR's kernel_stats.csv (k_ms_tracks_assemble: per batch
-it reads and writes the kept samples x 6 channels x 2 bytes each; k_ms_map: ms_rate.py's count per step).
-usage (GPU box): python3 tools/ms_files_rate.py [--n N] [--reps R] | python3 tools/ms_files_rate.py --stats DIR [--n N]"""
+it reads and writes the kept samples x 6 channels x 2 bytes each, k_ms_tracks_assemble_f32 reads 2 bytes and writes 4; k_ms_map:
+ms_rate.py's count per step).
+--format f32 | f32_planar: the whole call per track format instead (tools/format_rate.py).
+usage (GPU box): python3 tools/ms_files_rate.py [--n N] [--reps R] [--format F] | python3 tools/ms_files_rate.py --stats DIR [--n N]"""
 import argparse
 import ctypes as C
 import glob
@@ -29,7 +31,11 @@ ap.add_argument("--n", type=int, default=65536)
 ap.add_argument("--reps", type=int, default=30)
 ap.add_argument("--threads", type=int, default=16)
 ap.add_argument("--stats", default=None)
+ap.add_argument("--format", choices=["f32", "f32_planar"], default=None,
+                help="compare the whole decode call: int16 tracks, int16 + conversion in torch, the fused float format (tools/format_rate.py)")
 args = ap.parse_args()
+if args.format:
+    import torch  # before the library is loaded: one HIP runtime for both
 n = args.n
 
 spec = importlib.util.spec_from_file_location("esp32_opus_player_amd", os.path.join(here, "..", "esp32-opus-player_amd", "__init__.py"))
@@ -57,6 +63,10 @@ if args.stats:
     for key, per_launch in (("k_ms_tracks_assemble", MOVED / PACKETS), ("k_ms_map", MAP_BYTES), ("k_tracks_assemble", None)):
         for r in rows:
             if r["Name"].startswith(key) or ("void " + key) in r["Name"]:
+                if key == "k_ms_tracks_assemble" and "_f32" in r["Name"]:
+                    per_launch = MOVED * 3 / 2 / PACKETS  # float tracks: 2 bytes in, 4 bytes out
+                elif key == "k_ms_tracks_assemble":
+                    per_launch = MOVED / PACKETS
                 avg_ms = float(r["AverageNs"]) / 1e6
                 o = {"kernel": r["Name"].split("(")[0], "calls": int(r["Calls"]), "avg_ms_per_launch": round(avg_ms, 4),
                      "min_ms": round(float(r["MinNs"]) / 1e6, 4), "max_ms": round(float(r["MaxNs"]) / 1e6, 4)}
@@ -114,6 +124,14 @@ b = pkg.MsFileBatch(blobs, LAYOUT, threads=args.threads)
 plan_s = time.perf_counter() - t0
 assert (b.info["status"] == 0).all() and b.n_steps == PACKETS, (np.unique(b.info["status"]), b.n_steps)
 assert (b.info["track_samples"] == PACKETS * 960 - pre - trim).all()
+
+if args.format:
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import format_rate
+    ms = pkg.MultistreamContext(0, n, *LAYOUT)
+    print(json.dumps(format_rate.compare(torch, pkg, ms.lib.opusgpu_ms_files_decode_as, ms.h, ms._chk, b, args.format, args.reps, "in_order")))
+    ms.close()
+    raise SystemExit(0)
 
 # ---- (A) and (B), interleaved --------------------------------------------------------------------------------------------------
 ctx = pkg.Context(0)
