@@ -38,6 +38,8 @@ EXPORTS = [
     "opusgpu_ms_file_batch_arena", "opusgpu_ms_file_batch_track_samples", "opusgpu_ms_file_batch_packet_start", "opusgpu_ms_file_batch_free",
     "opusgpu_ms_tracks_assemble_device", "opusgpu_ms_files_decode", "opusgpu_ms_files_last_steps_ms",
     "opusgpu_ms_tracks_assemble_device_as", "opusgpu_ms_files_decode_as",
+    "opusgpu_resample_taps", "opusgpu_resample_layout", "opusgpu_tracks_resample_device", "opusgpu_files_decode_resampled",
+    "opusgpu_ms_files_decode_resampled",
 ]
 
 
@@ -114,6 +116,10 @@ FILE_INFO_DTYPE = np.dtype([("status", "<i4"), ("channels", "<i4"), ("pre_skip",
 TRACK_PLACE_DTYPE = np.dtype([("track_offset", "<i8"), ("plane_samples", "<i8"), ("scale", "<f4"), ("reserved", "<i4")])
 TRACKS_S16, TRACKS_F32, TRACKS_F32_PLANAR = 0, 1, 2
 TRACK_FORMATS = {"s16": TRACKS_S16, "f32": TRACKS_F32, "f32_planar": TRACKS_F32_PLANAR}
+# opusgpu_resample_span and the rates of the resampled tracks (include/opusgpu.h, TRACK RATES): rate -> D = 48000 / rate
+RESAMPLE_SPAN_DTYPE = np.dtype([("in_offset", "<i8"), ("in_samples", "<i8"), ("out_offset", "<i8"), ("out_plane", "<i8"), ("scale", "<f4"),
+                                ("reserved", "<i4")])
+TRACK_RATES = {48000: 1, 24000: 2, 16000: 3, 12000: 4, 8000: 6}
 OPUSGPU_BAD_ARG, OPUSGPU_UNIMPLEMENTED, OPUSGPU_CELT_BAD_ARG = -1, -5, -18
 RFC_FRAME = 2880
 
@@ -224,6 +230,12 @@ def load_lib():
     lib.opusgpu_ms_tracks_assemble_device_as.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp]
     lib.opusgpu_ms_files_decode_as.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp]
     lib.opusgpu_ms_files_last_steps_ms.restype = C.c_float
+    lib.opusgpu_resample_taps.argtypes = [C.c_int, C.POINTER(vp)]
+    lib.opusgpu_resample_layout.argtypes = [C.c_int, vp, C.c_int, vp]
+    lib.opusgpu_resample_layout.restype = C.c_int64
+    lib.opusgpu_tracks_resample_device.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
+    lib.opusgpu_files_decode_resampled.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
+    lib.opusgpu_ms_files_decode_resampled.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
     _lib = lib
     return lib
 
@@ -516,21 +528,67 @@ def track_format_args(batch, format="s16", scale=None, out=None, device=0):
         if not np.isfinite(scale).all():
             raise ValueError("scale entries must be finite")
     if out is not None:
-        need, dtype = max(int(batch.track_samples), 1) * batch.channels, "torch.int16" if fmt == TRACKS_S16 else "torch.float32"
-        if not hasattr(out, "data_ptr") or not hasattr(out, "is_cuda"):
-            raise ValueError("out must be a torch tensor")
-        if not out.is_cuda or out.device.index != device:
-            raise ValueError(f"out must be on GPU {device}, not on {out.device}")
-        if str(out.dtype) != dtype:
-            raise ValueError(f"out must be of dtype {dtype} for format {format!r}, not {out.dtype}")
-        if not out.is_contiguous():
-            raise ValueError("out must be contiguous")
-        if out.numel() < need:
-            raise ValueError(f"out is too small: {out.numel()} elements, {need} needed")
-        if out.data_ptr() % 128:
-            raise ValueError("out must be 128-byte aligned")
-        out = out.view(-1)
+        out = _out_flat(out, max(int(batch.track_samples), 1) * batch.channels, format, device)
     return fmt, scale, out
+
+
+def _out_flat(out, need, format, device):
+    """decode_files' `out` for tracks of `format` that take `need` elements, flattened; ValueError if it does not fit."""
+    dtype = "torch.int16" if TRACK_FORMATS[format] == TRACKS_S16 else "torch.float32"
+    if not hasattr(out, "data_ptr") or not hasattr(out, "is_cuda"):
+        raise ValueError("out must be a torch tensor")
+    if not out.is_cuda or out.device.index != device:
+        raise ValueError(f"out must be on GPU {device}, not on {out.device}")
+    if str(out.dtype) != dtype:
+        raise ValueError(f"out must be of dtype {dtype} for format {format!r}, not {out.dtype}")
+    if not out.is_contiguous():
+        raise ValueError("out must be contiguous")
+    if out.numel() < need:
+        raise ValueError(f"out is too small: {out.numel()} elements, {need} needed")
+    if out.data_ptr() % 128:
+        raise ValueError("out must be 128-byte aligned")
+    return out.view(-1)
+
+
+def resample_taps(rate):
+    """opusgpu_resample_taps: the Q15 decimation taps of `rate` (24000, 16000, 12000, 8000) as an int16 array of 24 D + 1."""
+    p = C.c_void_p()
+    n = load_lib().opusgpu_resample_taps(int(rate), C.byref(p))
+    if n < 0:
+        raise ValueError(f"no taps for rate {rate!r}")
+    return np.ctypeslib.as_array((C.c_int16 * n).from_address(p.value)).copy()
+
+
+def resample_layout(planned_samples, rate):
+    """opusgpu_resample_layout: the grid of the resampled tracks -> (out_offsets [int64], total samples per channel)."""
+    planned = np.ascontiguousarray(planned_samples, dtype=np.int64)
+    offsets = np.zeros(planned.size, dtype=np.int64)
+    total = load_lib().opusgpu_resample_layout(planned.size, planned.ctypes.data, int(rate), offsets.ctypes.data)
+    if total < 0:
+        raise ValueError(f"opusgpu_resample_layout refused rate {rate!r} or a negative length")
+    return offsets, int(total)
+
+
+def track_rate_args(batch, rate=48000, mono=False, format="s16", out=None, device=0, allow_mono=True):
+    """What decode_files makes of its rate= and mono= for a planned batch, before any device work: None for the defaults (today's
+    path), else (D, output channels, out_offsets, total samples per channel, out flattened or None).  Raises ValueError for a rate
+    that does not exist, 48000 without mono, mono with more than 2 channels (or where there is no mono: allow_mono False), and an
+    `out` that does not fit the RESAMPLED tracks: total * output channels elements, otherwise as track_format_args says."""
+    if mono and not allow_mono:
+        raise ValueError("there is no mono downmix of multistream tracks")
+    if rate == 48000 and not mono:
+        return None
+    if rate not in TRACK_RATES:
+        raise ValueError(f"rate must be one of {sorted(TRACK_RATES)}, not {rate!r}")
+    if mono and batch.channels > 2:
+        raise ValueError(f"mono needs 1 or 2 channels, not {batch.channels}")
+    if format not in TRACK_FORMATS:
+        raise ValueError(f"format must be one of {sorted(TRACK_FORMATS)}, not {format!r}")
+    ch_out = 1 if mono else batch.channels
+    offsets, total = resample_layout(batch.info["track_samples"], rate)
+    if out is not None:
+        out = _out_flat(out, max(total, 1) * ch_out, format, device)
+    return TRACK_RATES[rate], ch_out, offsets, total, out
 
 
 def _decode_planned(lib, chk, name, handle, batch, mem, args):
@@ -571,6 +629,47 @@ def _decode_planned(lib, chk, name, handle, batch, mem, args):
         tracks = [packed[ch * o:ch * (o + p)].reshape(ch, p)[:, :ln] for o, p, ln in zip(batch.info["track_offset"], planes, lengths)]
     else:
         tracks = [packed[ch * o:ch * (o + ln)].reshape(ln, ch) for o, ln in zip(batch.info["track_offset"], lengths)]
+    return tracks, info
+
+
+def _decode_planned_resampled(chk, name, call, batch, mem, args, rargs):
+    """_decode_planned for resampled tracks: call(fmt, scale pointer, d_out, four array pointers) runs the decode call `name`;
+    args: what track_format_args returned for out=None, rargs: what track_rate_args returned.  -> (tracks, info): tracks of
+    [ceil(len / D), output channels] (planar: [output channels, ceil(len / D)]), info with `out_samples` and `out_offset` more."""
+    fmt, scale, _ = args
+    D, ch, offsets, total, out = rargs
+    n = batch.n_files
+    out_offsets, out_lengths, lengths = (np.zeros(n, dtype=np.int64) for _ in range(3))
+    status = np.zeros((n, 2), dtype=np.int32)
+
+    def run(d_out):
+        chk(call(fmt, None if scale is None else scale.ctypes.data, d_out, out_offsets.ctypes.data, out_lengths.ctypes.data,
+                 lengths.ctypes.data, status.ctypes.data), name)
+    if out is not None:
+        import torch
+        torch.cuda.current_stream(out.device).synchronize()  # as in _decode_planned
+        run(out.data_ptr())
+        packed = out
+    else:
+        packed = np.zeros(max(total, 1) * ch, dtype=np.int16 if fmt == TRACKS_S16 else np.float32)
+        d_out = mem.dev_alloc(packed.nbytes)
+        try:
+            run(d_out)
+            mem.d2h(packed, d_out)
+        finally:
+            mem.dev_free(d_out)
+    assert (out_offsets == offsets).all()
+    info = np.zeros(n, dtype=np.dtype(FILE_INFO_DTYPE.descr + [("final_status", "<i4"), ("bad_packet", "<i4"), ("out_samples", "<i8"),
+                                                               ("out_offset", "<i8")]))
+    for field in FILE_INFO_DTYPE.names:
+        info[field] = batch.info[field]
+    info["track_samples"], info["final_status"], info["bad_packet"] = lengths, status[:, 0], status[:, 1]
+    info["out_samples"], info["out_offset"] = out_lengths, out_offsets
+    if fmt == TRACKS_F32_PLANAR:
+        planes = ((batch.info["track_samples"] + D - 1) // D + 63) // 64 * 64
+        tracks = [packed[ch * o:ch * (o + p)].reshape(ch, p)[:, :ln] for o, p, ln in zip(out_offsets, planes, out_lengths)]
+    else:
+        tracks = [packed[ch * o:ch * (o + ln)].reshape(ln, ch) for o, ln in zip(out_offsets, out_lengths)]
     return tracks, info
 
 
@@ -742,7 +841,15 @@ class Context:
         self._chk(self.lib.opusgpu_tracks_assemble_device_as(self.h, n_segs, d_segs, d_pcm, row_samples, d_result, format, d_place, d_tracks,
                                                              d_track_state, stream), "opusgpu_tracks_assemble_device_as")
 
-    def decode_files(self, files, rfc=False, flags=PAGES_GROUP_BY_MODE, threads=1, batch=None, format="s16", scale=None, out=None):
+    def tracks_resample_device(self, spans, d_in, channels, rate, mono, format, d_out, stream=None):
+        """k_tracks_resample alone (include/opusgpu.h TRACK RATES): spans a HOST array of RESAMPLE_SPAN_DTYPE, d_in packed int16
+        tracks, d_out the resampled ones in `format` (TRACKS_*).  Waits for the kernel."""
+        spans = np.ascontiguousarray(spans, dtype=RESAMPLE_SPAN_DTYPE)
+        self._chk(self.lib.opusgpu_tracks_resample_device(self.h, spans.size, spans.ctypes.data, d_in, channels, int(rate), 1 if mono else 0,
+                                                          format, d_out, stream), "opusgpu_tracks_resample_device")
+
+    def decode_files(self, files, rfc=False, flags=PAGES_GROUP_BY_MODE, threads=1, batch=None, format="s16", scale=None, out=None,
+                     rate=48000, mono=False):
         """Whole Ogg Opus files -> (list of int16 arrays [samples, channels], one trimmed track per file, info).  The context's
         streams 0 .. len(files) - 1 are (re)allocated when there are too few and get fresh state; its mode is set to `rfc`.
         info: FILE_INFO_DTYPE records with two more fields: `final_status` (the first failed frame's code, else the plan's status)
@@ -752,16 +859,25 @@ class Context:
         int16 one times scale (include/opusgpu.h TRACK FORMATS).  scale: None (1 / 32768), "head_gain" (each file's OpusHead output
         gain applied as well) or one float per file.  out: a contiguous torch tensor on this context's GPU, of the format's dtype,
         128-byte aligned, with at least track_samples * channels elements: the tracks are decoded straight into it, nothing is
-        copied to the host, and the tracks returned are views of it (ValueError before any device work if it does not fit)."""
+        copied to the host, and the tracks returned are views of it (ValueError before any device work if it does not fit).
+        rate: 48000, or 24000 / 16000 / 12000 / 8000 for tracks decimated by D = 48000 / rate on the GPU (include/opusgpu.h TRACK
+        RATES: an integer FIR over the int16 track, bit-exact); mono: one channel, (l + r + 1) >> 1 of a stereo track, at any rate.
+        The tracks are then [ceil(len / D), 1 or channels] (planar: transposed), `out` is sized for them (track_rate_args), and
+        info has `out_samples` and `out_offset` more; `track_samples` stays the final length at 48 kHz."""
         own = batch is None
         channels = self.channels or 2
         if own:
             batch = FileBatch(files, channels=channels, rfc=rfc, flags=flags, threads=threads)
         try:
-            args = track_format_args(batch, format, scale, out, self.device)
+            rargs = track_rate_args(batch, rate, mono, format, out, self.device)
+            args = track_format_args(batch, format, scale, out if rargs is None else None, self.device)
             if self.n_streams < batch.n_files or self.channels != batch.channels:
                 self.streams_alloc(max(batch.n_files, 1), batch.channels)
             self.set_mode(batch.rfc)
+            if rargs is not None:
+                def call(fmt, scale_p, d_out, *arrays):
+                    return self.lib.opusgpu_files_decode_resampled(self.h, batch.h, int(rate), 1 if mono else 0, fmt, scale_p, d_out, *arrays)
+                return _decode_planned_resampled(self._chk, "opusgpu_files_decode_resampled", call, batch, self, args, rargs)
             return _decode_planned(self.lib, self._chk, "opusgpu_files_decode", self.h, batch, self, args)
         finally:
             if own:
@@ -929,20 +1045,25 @@ class MultistreamContext:
                                                                 d_res_mono, format, d_place, d_tracks, d_track_state, stream),
                   "opusgpu_ms_tracks_assemble_device_as")
 
-    def decode_files(self, files, rfc=False, threads=1, batch=None, format="s16", scale=None, out=None):
+    def decode_files(self, files, rfc=False, threads=1, batch=None, format="s16", scale=None, out=None, rate=48000):
         """Whole Ogg Opus files of this object's layout -> (list of int16 arrays [samples, channels], one trimmed track per file,
         info), as Context.decode_files returns them: FILE_INFO_DTYPE records plus `final_status` and `bad_packet`, `track_samples`
         the FINAL length.  Decoders 0 .. len(files) - 1 get fresh state; the object's mode is set to the batch's.  batch: an
-        MsFileBatch made beforehand from the same files (of this layout; `rfc` is then the batch's).  format, scale, out: as for
-        Context.decode_files."""
+        MsFileBatch made beforehand from the same files (of this layout; `rfc` is then the batch's).  format, scale, out, rate: as
+        for Context.decode_files, all channels at `rate` (there is no mono downmix of a surround layout)."""
         own = batch is None
         if own:
             batch = MsFileBatch(files, self.layout, rfc=rfc, threads=threads)
         mem = None
         try:
-            args = track_format_args(batch, format, scale, out, self.device)
+            rargs = track_rate_args(batch, rate, False, format, out, self.device, allow_mono=False)
+            args = track_format_args(batch, format, scale, out if rargs is None else None, self.device)
             mem = Context(self.device)  # (device memory and copies are a plain context's calls)
             self.set_mode(batch.rfc)
+            if rargs is not None:
+                def call(fmt, scale_p, d_out, *arrays):
+                    return self.lib.opusgpu_ms_files_decode_resampled(self.h, batch.h, int(rate), fmt, scale_p, d_out, *arrays)
+                return _decode_planned_resampled(self._chk, "opusgpu_ms_files_decode_resampled", call, batch, mem, args, rargs)
             return _decode_planned(self.lib, self._chk, "opusgpu_ms_files_decode", self.h, batch, mem, args)
         finally:
             if mem is not None:

@@ -1,6 +1,6 @@
 // og_ms_tracks.hpp -- whole multistream files (include/opusgpu.h, WHOLE FILES / MULTISTREAM): the kernel that maps channels and
 // assembles tracks in one pass, and what the driver of a planned batch (og_files_run.hpp) needs of an opusgpu_ms.  Included at the
-// end of og_api.hip behind og_ms.hpp (opusgpu_ms, ms_step_impl) and og_tracks.hpp (TrackSeg, TrackState).
+// end of og_api.hip behind og_ms.hpp (opusgpu_ms, ms_step_impl), og_tracks.hpp (TrackSeg, TrackState) and og_tracks_resample.hpp.
 #pragma once
 
 // ---- kernel -------------------------------------------------------------------------------------------
@@ -449,6 +449,19 @@ int opusgpu_ms_files_decode_as(opusgpu_ms *ms, const opusgpu_ms_file_batch *batc
     std::vector<TrackPlace> places;
     if (int rc = track_places(*batch, format, scale, places)) return rc;
     return ms_files_decode_run(ms, batch, format, format == OPUSGPU_TRACKS_S16 ? nullptr : &places, d_tracks, track_lengths_out, status_out);
+}
+
+// opusgpu_files_decode_resampled behind opusgpu_ms_files_decode (og_tracks_resample.hpp): all channels, no downmix.
+int opusgpu_ms_files_decode_resampled(opusgpu_ms *ms, const opusgpu_ms_file_batch *batch, int rate, int format, const float *scale,
+                                      void *d_out, int64_t *out_offsets, int64_t *out_lengths, int64_t *track_lengths_out,
+                                      int32_t *status_out) {
+    if (!ms || !batch) return OPUSGPU_BAD_ARG;
+    return files_resampled_run(
+        *batch, ms->device, ms->stream, rate, 0, format, scale, d_out, out_offsets, out_lengths, track_lengths_out, status_out,
+        [&](void *d_s16, int64_t *lengths, int32_t *status) {
+            return ms_files_decode_run(ms, batch, OPUSGPU_TRACKS_S16, nullptr, d_s16, lengths, status);
+        },
+        [&](int code, const char *what, hipError_t e) { return ms_fail(ms, code, what, e); });
 }
 
 } // extern "C"

@@ -1,0 +1,376 @@
+// og_tracks_resample.hpp -- tracks at 8 / 12 / 16 / 24 kHz and the mono downmix (include/opusgpu.h, TRACK RATES): the kernel that
+// turns packed int16 tracks into decimated ones, its host side, and the whole-file call that ends in it.  Included at the end of
+// og_api.hip behind og_tracks.hpp (files_decode_run, track_f32, track_store4) and in front of og_ms_tracks.hpp.
+#pragma once
+#include <cmath>
+#define OG_RS_PAIRS_ROM static __device__ const
+#include "og_resample_taps.hpp"
+
+// ---- kernel -------------------------------------------------------------------------------------------
+// k_tracks_resample<D>: one workgroup per entry of a tile table built on the host, a tile being `tile` consecutive output samples
+// of every output channel of one track (a 1-D grid: a long track among short ones costs its own tiles and nothing else).
+//   1. STAGE.  The tile's input window -- (tile + 24) D samples of every channel, 12 D of them in front of the first output's own
+//      sample -- comes into LDS through aligned 16-byte loads of the interleaved track, one piece per lane.  Samples outside
+//      [0, in_samples) are zeros (pieces without a sample inside are not fetched: nothing is read behind the 16-byte piece that
+//      holds a track's last sample), a stereo pair becomes (l + r + 1) >> 1 here when `mono`.  In LDS the window is de-interleaved
+//      twice: one plane per channel and PHASE, sample n0 + D q + p of channel c at place q of plane (c, p).  Tap k = D a + p of
+//      output j then meets place j + a of plane p: lanes that step through a plane side by side read consecutive words, whatever D.
+//      A last tile that is not full stages n_out + 24 places of a plane, and its last group of four outputs reads up to three
+//      places more: words nobody wrote.  They meet only tap pairs that are zero (place j + 24 of an output j that is stored has
+//      the one tap of phase 0, and the pair's other half and the places behind it belong to taps that do not exist) or feed
+//      outputs at j >= n_out, which are never stored, as are the unwritten results behind them that a partial last piece reads
+//      in step 3.  The arithmetic is integer: there is no NaN to spread, and no value to trap on.
+//   2. MAC.  A lane owns four consecutive outputs of one channel.  Per phase it reads the 14 words (28 places) they need once and
+//      feeds them to v_dot2_i32_i16, two neighbouring places against two taps D apart per instruction: 13 per output and phase,
+//      for 24 + 1 / D taps.  The tap pairs are literals of the instruction (og_resample_taps.hpp, generated; the loops are
+//      unrolled), so they are wave-uniform by construction.  Outputs at odd places take the same words against pairs shifted by
+//      one tap.  The sum starts at 16384 and is exact in int32 (sum |h| <= 65535); >> 15 and the clamp make the int16 result,
+//      which goes to a second LDS area in the order of the destination.
+//   3. STORE.  A lane owns an aligned 16-byte piece of the destination -- 8 int16 or 4 floats ((float)y * scale, track_f32) of the
+//      interleaved track, or 4 floats of one plane -- and stores it whole (track_store4 for floats); tracks begin at multiples
+//      of 64 samples and tiles at multiples of `tile`, so only a track's last piece can be partial: it goes out as element stores.
+// D = 1 (rate 48000, mono only) has no filter: the staged downmix is the result.
+struct ResampleSpan {
+    long long in_offset, in_samples, out_offset, out_plane;
+    float scale;
+    i32 reserved;
+};
+struct ResampleTile {
+    i32 track, reserved;
+    long long first; // the tile's first output sample, a multiple of the tile length
+};
+static_assert(sizeof(opusgpu_resample_span) == sizeof(ResampleSpan) && sizeof(ResampleSpan) == 40, "resample span layout");
+
+// Places behind a plane's `tile`: a group of four outputs at place 4 i reads places [4 i, 4 i + 28), of which a partial last tile
+// has written those below n_out + 24 (the rest is harmless, see STAGE above); 40 keeps planes 16-byte aligned and 20 banks apart.
+constexpr int RS_PLANE_PAD = 40;
+
+template <int D>
+__device__ __forceinline__ const u32 *rs_pairs() {
+    if constexpr (D == 2) return og_rs_pairs_2;
+    if constexpr (D == 3) return og_rs_pairs_3;
+    if constexpr (D == 4) return og_rs_pairs_4;
+    if constexpr (D == 6) return og_rs_pairs_6;
+    return nullptr;
+}
+typedef short og_i16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ i32 rs_dot2(u32 x, u32 taps, i32 acc) { // acc + x.lo * taps.lo + x.hi * taps.hi (v_dot2_i32_i16)
+    return __builtin_amdgcn_sdot2(__builtin_bit_cast(og_i16x2, x), __builtin_bit_cast(og_i16x2, taps), acc, false);
+}
+
+template <int D>
+__global__ void __launch_bounds__(256) k_tracks_resample(const ResampleTile *__restrict__ tiles, const ResampleSpan *__restrict__ spans,
+                                                          const i16 *__restrict__ in, int C, int mono, int format, int tile_shift,
+                                                          void *__restrict__ out) {
+    extern __shared__ __align__(16) i16 lds[]; // [CO * D] planes of Q places, then the tile's results [CO * tile]
+    const int tid = (int)threadIdx.x;
+    const ResampleTile tl = tiles[blockIdx.x];
+    const ResampleSpan sp = spans[tl.track];
+    const int tile = 1 << tile_shift, Q = tile + RS_PLANE_PAD;
+    const int CO = mono ? 1 : C;
+    constexpr int LEAD = D == 1 ? 0 : 12; // places of a plane in front of an output's own: (L - 1) / 2 = 12 D samples
+    const long long out_len = (sp.in_samples + D - 1) / D;
+    const long long left = out_len - tl.first;
+    const int n_out = left < tile ? (int)left : tile;
+    if (n_out <= 0) return;
+    i16 *const yo = D == 1 ? lds : lds + CO * D * Q;
+    const bool planar = format == OPUSGPU_TRACKS_F32_PLANAR;
+
+    // 1. the window -> LDS
+    {
+        const long long n0 = (tl.first - LEAD) * D;           // the window's first input sample; negative at a track's head
+        const int W = (n_out + 2 * LEAD) * D * C;             // its elements, all input channels
+        const long long G0 = (sp.in_offset + n0) * C;         // its first element in the buffer
+        const int mis = (int)(G0 & 7);                        // elements between the aligned piece's first and it
+        const long long V0 = sp.in_offset * C, V1 = (sp.in_offset + sp.in_samples) * C; // the track's elements; V0 is a multiple of 8
+        const int pieces = (W + mis + 7) >> 3;
+        const bool mix = mono && C == 2;
+        for (int k = tid; k < pieces; k += 256) {
+            const long long g = G0 - mis + 8LL * k;
+            uint4 v = make_uint4(0, 0, 0, 0);
+            if (g >= V0 && g < V1) v = *reinterpret_cast<const uint4 *>(in + g);
+            const u32 w32[4] = {v.x, v.y, v.z, v.w};
+            const int w = 8 * k - mis;        // the piece's first window element (-7 .. -1 possible in piece 0)
+            int rel = (w + 8 * C) / C - 8;    // its sample in the window (floor) and channel
+            int ch = w - rel * C;
+            if (mix) { // pairs never straddle pieces: G0 is even
+#pragma unroll
+                for (int h = 0; h < 8; h += 2) {
+                    if (w + h >= 0 && w + h < W) {
+                        const int r = rel + (h >> 1);
+                        const long long n = n0 + r;
+                        const u32 lr = w32[h >> 1];
+                        const int m = n >= 0 && n < sp.in_samples ? ((int)(i16)lr + (int)(i16)(lr >> 16) + 1) >> 1 : 0;
+                        lds[(r % D) * Q + r / D] = (i16)m;
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int h = 0; h < 8; h++) {
+                    if (w + h >= 0 && w + h < W) {
+                        const long long n = n0 + rel;
+                        const i16 s = n >= 0 && n < sp.in_samples ? (i16)(w32[h >> 1] >> (16 * (h & 1))) : (i16)0;
+                        lds[(ch * D + rel % D) * Q + rel / D] = s;
+                    }
+                    if (++ch == C) ch = 0, rel++;
+                }
+            }
+        }
+    }
+    __syncthreads();
+
+    // 2. four outputs per lane
+    if constexpr (D > 1) {
+        const u32 *const pairs = rs_pairs<D>();
+        const int items = CO << (tile_shift - 2);
+        for (int x = tid; x < items; x += 256) {
+            const int c = x >> (tile_shift - 2), i = x & ((tile >> 2) - 1);
+            if (4 * i >= n_out) continue;
+            i32 acc[4] = {16384, 16384, 16384, 16384};
+#pragma unroll
+            for (int p = 0; p < D; p++) {
+                const uint2 *src = reinterpret_cast<const uint2 *>(lds + (c * D + p) * Q + 4 * i); // 8-byte aligned
+                u32 X[14];
+#pragma unroll
+                for (int w = 0; w < 7; w++) {
+                    const uint2 t = src[w];
+                    X[2 * w] = t.x, X[2 * w + 1] = t.y;
+                }
+#pragma unroll
+                for (int w = 0; w < OG_RS_PAIRS; w++) {
+                    const u32 te = pairs[(2 * p) * OG_RS_PAIRS + w], to = pairs[(2 * p + 1) * OG_RS_PAIRS + w];
+                    acc[0] = rs_dot2(X[w], te, acc[0]);
+                    acc[1] = rs_dot2(X[w], to, acc[1]);
+                    acc[2] = rs_dot2(X[w + 1], te, acc[2]);
+                    acc[3] = rs_dot2(X[w + 1], to, acc[3]);
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const i32 y = acc[r] >> 15;
+                const int j = 4 * i + r;
+                yo[planar ? c * tile + j : j * CO + c] = (i16)(y < -32768 ? -32768 : y > 32767 ? 32767 : y);
+            }
+        }
+        __syncthreads();
+    }
+
+    // 3. LDS -> the track, 16 bytes per lane and store
+    const float k = sp.scale;
+    if (format == OPUSGPU_TRACKS_S16) {
+        i16 *const dst = static_cast<i16 *>(out) + (sp.out_offset + tl.first) * CO;
+        const int EN = n_out * CO;
+        for (int q = tid; q < (EN + 7) >> 3; q += 256) {
+            const uint4 v = *reinterpret_cast<const uint4 *>(yo + 8 * q);
+            if (8 * q + 8 <= EN) {
+                *reinterpret_cast<uint4 *>(dst + 8 * q) = v;
+            } else {
+                const u32 w32[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                for (int h = 0; h < 8; h++)
+                    if (8 * q + h < EN) dst[8 * q + h] = (i16)(w32[h >> 1] >> (16 * (h & 1)));
+            }
+        }
+    } else {
+        // interleaved: one run of n_out * CO elements; planar: CO runs of n_out, one per plane (a mono track is its plane)
+        const int runs = planar ? CO : 1, EN = planar ? n_out : n_out * CO;
+        const int pp = (EN + 3) >> 2; // pieces per run
+        float *const base = static_cast<float *>(out) + (planar ? sp.out_offset * CO + tl.first : (sp.out_offset + tl.first) * CO);
+        for (int x = tid; x < runs * pp; x += 256) {
+            const int c = planar ? x / pp : 0, q = x - c * pp;
+            const uint2 v = *reinterpret_cast<const uint2 *>(yo + c * tile + 4 * q);
+            const float f[4] = {track_f32(v.x, k), track_f32(v.x >> 16, k), track_f32(v.y, k), track_f32(v.y >> 16, k)};
+            float *const d = base + c * sp.out_plane + 4 * q;
+            if (4 * q + 4 <= EN) {
+                track_store4(d, f);
+            } else {
+#pragma unroll
+                for (int h = 0; h < 4; h++)
+                    if (4 * q + h < EN) d[h] = f[h];
+            }
+        }
+    }
+}
+
+// ---- host side ----------------------------------------------------------------------------------------
+// 48000 / rate for the rates there are, else 0
+static int rs_factor(int rate) {
+    switch (rate) {
+        case 48000: return 1;
+        case 24000: return 2;
+        case 16000: return 3;
+        case 12000: return 4;
+        case 8000: return 6;
+    }
+    return 0;
+}
+static int64_t rs_round64(int64_t v) { return (v + 63) / 64 * 64; }
+
+// What every resampling call refuses before any device work: -> the factor D, or 0.
+static int rs_args_factor(int channels, int rate, int mono, int format) {
+    const int D = rs_factor(rate);
+    if (!D || channels < 1 || channels > 8 || (D == 1 && !mono) || (mono && channels > 2)) return 0;
+    if (format != OPUSGPU_TRACKS_S16 && format != OPUSGPU_TRACKS_F32 && format != OPUSGPU_TRACKS_F32_PLANAR) return 0;
+    return D;
+}
+// A files call's scale: none with S16, finite entries otherwise (track_places' rule).
+static bool rs_scale_ok(int format, const float *scale, int n) {
+    if (format == OPUSGPU_TRACKS_S16) return !scale;
+    for (int i = 0; scale && i < n; i++)
+        if (!std::isfinite(scale[i])) return false;
+    return true;
+}
+
+// A device buffer for the length of one call: freed on every way out.
+struct RsDevBuf {
+    void *p = nullptr;
+    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes + 16); }
+    hipError_t upload(const void *src, size_t bytes) {
+        const hipError_t e = alloc(bytes);
+        return e != hipSuccess || !bytes ? e : hipMemcpy(p, src, bytes, hipMemcpyHostToDevice);
+    }
+    ~RsDevBuf() {
+        if (p) (void)hipFree(p);
+    }
+};
+
+// The kernel over n tracks: checks the spans, builds the tile table, uploads both, launches on `s` and waits.
+// hip_failed(code, what, e) keeps the message of the object the call belongs to and returns `code`.
+template <class Fail>
+static int tracks_resample_run(int device, hipStream_t s, int n_tracks, const opusgpu_resample_span *spans, const void *d_in, int channels,
+                               int rate, int mono, int format, void *d_out, Fail hip_failed) {
+    const int D = rs_args_factor(channels, rate, mono, format);
+    if (!D || n_tracks < 0 || (n_tracks && !spans)) return OPUSGPU_BAD_ARG;
+    const int CO = mono ? 1 : channels;
+    const int tile_shift = CO == 1 ? 10 : CO == 2 ? 9 : 8; // 1,024 outputs of one channel .. 256 of eight: four per lane
+    const int64_t tile = (int64_t)1 << tile_shift;
+    std::vector<ResampleTile> tiles;
+    for (int t = 0; t < n_tracks; t++) {
+        const opusgpu_resample_span &sp = spans[t];
+        if (sp.in_offset < 0 || sp.in_offset % 8 || sp.in_samples < 0 || sp.out_offset < 0 || sp.out_offset % 64) return OPUSGPU_BAD_ARG;
+        const int64_t out_len = (sp.in_samples + D - 1) / D;
+        if (format == OPUSGPU_TRACKS_F32_PLANAR && (sp.out_plane % 64 || sp.out_plane < out_len)) return OPUSGPU_BAD_ARG;
+        if (format != OPUSGPU_TRACKS_S16 && !std::isfinite(sp.scale)) return OPUSGPU_BAD_ARG;
+        if ((out_len + tile - 1) / tile + (int64_t)tiles.size() > 0x7fffffff) return OPUSGPU_BAD_ARG;
+        for (int64_t m = 0; m < out_len; m += tile) tiles.push_back(ResampleTile{t, 0, m});
+    }
+    if (tiles.empty()) return OPUSGPU_OK;
+    if (!d_in || !d_out || ((uintptr_t)d_in & 15) || ((uintptr_t)d_out & 127)) return OPUSGPU_BAD_ARG;
+#define RS_CHK(call)                                                              \
+    do {                                                                          \
+        const hipError_t e_ = (call);                                             \
+        if (e_ != hipSuccess) return hip_failed(OPUSGPU_ERR_HIP, #call, e_);      \
+    } while (0)
+    RS_CHK(hipSetDevice(device));
+    RsDevBuf d_spans, d_tiles;
+    RS_CHK(d_spans.upload(spans, (size_t)n_tracks * sizeof(ResampleSpan)));
+    RS_CHK(d_tiles.upload(tiles.data(), tiles.size() * sizeof(ResampleTile)));
+    const size_t lds = ((size_t)CO * D * (tile + RS_PLANE_PAD) + (size_t)CO * tile) * 2;
+    auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3((unsigned)tiles.size()), dim3(256), lds, s, (const ResampleTile *)d_tiles.p, (const ResampleSpan *)d_spans.p,
+                           (const i16 *)d_in, channels, mono ? 1 : 0, format, tile_shift, d_out);
+    };
+    switch (D) {
+        case 1: go(k_tracks_resample<1>); break;
+        case 2: go(k_tracks_resample<2>); break;
+        case 3: go(k_tracks_resample<3>); break;
+        case 4: go(k_tracks_resample<4>); break;
+        default: go(k_tracks_resample<6>); break;
+    }
+    RS_CHK(hipGetLastError());
+    RS_CHK(hipStreamSynchronize(s));
+#undef RS_CHK
+    return OPUSGPU_OK;
+}
+
+// The spans of a planned batch whose S16 tracks have been decoded: final lengths in, the resampled grid out.
+static void rs_batch_spans(const og_batch &b, int D, const int64_t *final_lengths, const float *scale, std::vector<int64_t> &out_offsets,
+                           std::vector<opusgpu_resample_span> &spans) {
+    const size_t n = (size_t)b.n_files;
+    out_offsets.resize(n);
+    spans.resize(n);
+    int64_t at = 0;
+    for (size_t i = 0; i < n; i++) {
+        const int64_t plane = rs_round64((b.info[i].track_samples + D - 1) / D);
+        out_offsets[i] = at;
+        spans[i] = opusgpu_resample_span{b.info[i].track_offset, final_lengths[i], at, plane, scale ? scale[i] : 1.0f / 32768, 0};
+        at += plane;
+    }
+}
+
+// What both whole-file calls do around their decoder: `decode(d_s16, lengths, status)` runs the batch into the scratch S16 tracks.
+template <class Decode, class Fail>
+static int files_resampled_run(const og_batch &b, int device, hipStream_t s, int rate, int mono, int format, const float *scale, void *d_out,
+                               int64_t *out_offsets, int64_t *out_lengths, int64_t *track_lengths_out, int32_t *status_out, Decode decode,
+                               Fail hip_failed) {
+    const int D = rs_args_factor(b.channels, rate, mono, format);
+    if (!D || !rs_scale_ok(format, scale, b.n_files)) return OPUSGPU_BAD_ARG;
+    const size_t n = (size_t)b.n_files;
+    std::vector<int64_t> lengths(n, 0), offsets;
+    std::vector<int32_t> status(2 * n, 0);
+    std::vector<opusgpu_resample_span> spans;
+    RsDevBuf s16; // the int16 tracks: track_samples x channels, for the length of this call
+    if (!b.segs.empty()) {
+        hipError_t e = hipSetDevice(device);
+        if (e == hipSuccess) e = s16.alloc((size_t)b.track_samples * b.channels * 2);
+        if (e != hipSuccess) return hip_failed(OPUSGPU_ALLOC_FAIL, "hipMalloc(resample scratch)", e);
+    }
+    if (int rc = decode(s16.p, lengths.data(), status.data())) return rc;
+    rs_batch_spans(b, D, lengths.data(), scale, offsets, spans);
+    if (int rc = tracks_resample_run(device, s, b.n_files, spans.data(), s16.p, b.channels, rate, mono, format, d_out, hip_failed)) return rc;
+    for (size_t i = 0; i < n; i++) {
+        if (out_offsets) out_offsets[i] = offsets[i];
+        if (out_lengths) out_lengths[i] = (lengths[i] + D - 1) / D;
+        if (track_lengths_out) track_lengths_out[i] = lengths[i];
+    }
+    if (status_out) std::copy(status.begin(), status.end(), status_out);
+    return OPUSGPU_OK;
+}
+
+extern "C" {
+
+int opusgpu_resample_taps(int rate, const int16_t **taps) {
+    const int16_t *h = nullptr;
+    switch (rate) {
+        case 24000: h = og_rs_taps_2; break;
+        case 16000: h = og_rs_taps_3; break;
+        case 12000: h = og_rs_taps_4; break;
+        case 8000: h = og_rs_taps_6; break;
+        default: return OPUSGPU_BAD_ARG; // 48000 included: the downmix has no table (its one tap, 32768, is no int16)
+    }
+    if (taps) *taps = h;
+    return 24 * rs_factor(rate) + 1;
+}
+
+int64_t opusgpu_resample_layout(int n, const int64_t *planned_samples, int rate, int64_t *out_offsets) {
+    const int D = rs_factor(rate);
+    if (!D || n < 0 || (n && !planned_samples)) return OPUSGPU_BAD_ARG;
+    int64_t at = 0;
+    for (int i = 0; i < n; i++) {
+        if (planned_samples[i] < 0) return OPUSGPU_BAD_ARG;
+        if (out_offsets) out_offsets[i] = at;
+        at += rs_round64((planned_samples[i] + D - 1) / D);
+    }
+    return at;
+}
+
+int opusgpu_tracks_resample_device(opusgpu_ctx *ctx, int n_tracks, const opusgpu_resample_span *spans, const void *d_in, int channels, int rate,
+                                   int mono, int format, void *d_out, void *hip_stream) {
+    if (!ctx) return OPUSGPU_BAD_ARG;
+    return tracks_resample_run(ctx->device, hip_stream ? (hipStream_t)hip_stream : ctx->stream, n_tracks, spans, d_in, channels, rate, mono,
+                               format, d_out, [&](int code, const char *what, hipError_t e) { return fail(ctx, code, what, e); });
+}
+
+int opusgpu_files_decode_resampled(opusgpu_ctx *ctx, const opusgpu_file_batch *batch, int rate, int mono, int format, const float *scale,
+                                   void *d_out, int64_t *out_offsets, int64_t *out_lengths, int64_t *track_lengths_out,
+                                   int32_t *status_out) {
+    if (!ctx || !batch) return OPUSGPU_BAD_ARG;
+    return files_resampled_run(
+        *batch, ctx->device, ctx->stream, rate, mono, format, scale, d_out, out_offsets, out_lengths, track_lengths_out, status_out,
+        [&](void *d_s16, int64_t *lengths, int32_t *status) {
+            return files_decode_run(ctx, batch, OPUSGPU_TRACKS_S16, nullptr, d_s16, lengths, status);
+        },
+        [&](int code, const char *what, hipError_t e) { return fail(ctx, code, what, e); });
+}
+
+} // extern "C"

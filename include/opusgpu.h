@@ -630,6 +630,60 @@ int opusgpu_tracks_assemble_device_as(opusgpu_ctx *ctx, int n_segs, const void *
 int opusgpu_files_decode_as(opusgpu_ctx *ctx, const opusgpu_file_batch *batch, int format, const float *scale, void *d_tracks,
                             int64_t *track_lengths_out, int32_t *status_out);
 
+/* TRACK RATES.  Tracks at 48000 / D Hz, D in {2, 3, 4, 6} (rates 24000, 16000, 12000, 8000), and a mono downmix of mono or stereo
+ * tracks; rate 48000 is allowed only together with `mono`.  Like the float formats the new tracks are a pure function of the S16
+ * track, bit for bit:
+ *   VALUE.  For track t let x[n] be the int16 sample of the S16 track, and x[n] = 0 for n < 0 and for n >= the track's FINAL length
+ *   (samples at or past the final length are unspecified in the buffer and are never read as signal).  With `mono` (1 or 2
+ *   channels only) x is first replaced by (l + r + 1) >> 1 for stereo and is unchanged for mono, and there is one output channel.
+ *   Output sample m of each channel, for m in [0, ceil(len / D)), len the final length, is
+ *       y[m] = sat16((sum_k h_D[k] * x[m * D + k - (L - 1) / 2] + 16384) >> 15),     k in [0, L), L = 24 D + 1,
+ *   >> arithmetic, the accumulation exact in int32 (sum |h_D| <= 65535, asserted where the taps are made), sat16 a clamp to
+ *   [-32768, 32767].  With rate 48000 the downmix is the whole operation (h = {32768}: y = x).  The float formats follow TRACK
+ *   FORMATS: (float)y * scale[track], one IEEE multiply.
+ *   TAPS.  h_D is one symmetric Q15 table of int16: scipy.signal.firwin(L, 0.92 / D, window=("kaiser", 8.0)) rounded to Q15, the
+ *   centre tap corrected so that the sum is exactly 32768 (tools/gen_resample_taps.py writes them to csrc/og_resample_taps.hpp).
+ *   LAYOUT.  Resampled tracks are packed on a grid of their own: out_offset[t] is the running sum of roundup64(ceil(planned[u] / D))
+ *   over the earlier tracks u, planned the PLANNED track_samples -- always a multiple of 64.  Interleaved formats: sample m of
+ *   channel c of track t is element out_channels * (out_offset[t] + m) + c.  OPUSGPU_TRACKS_F32_PLANAR: element out_channels *
+ *   out_offset[t] + c * plane[t] + m, plane[t] = roundup64(ceil(planned[t] / D)).  out_channels is 1 with `mono`, else the channel
+ *   count.  Padding is never written. */
+/* The taps of `rate`: returns L and sets *taps (may be NULL) to the table, or OPUSGPU_BAD_ARG for a rate without a table -- 48000
+ * included, whose single tap 32768 is no int16.  Host only. */
+int opusgpu_resample_taps(int rate, const int16_t **taps);
+/* The grid above for n tracks of planned_samples[i] samples: writes out_offsets[i] (may be NULL) and returns the total in samples
+ * per channel -- allocate out_channels elements of the format for each.  Serves both kinds of batch.  OPUSGPU_BAD_ARG for an unknown
+ * rate (48000 is known: D = 1) or a negative length.  Host only. */
+int64_t opusgpu_resample_layout(int n, const int64_t *planned_samples, int rate, int64_t *out_offsets);
+typedef struct opusgpu_resample_span { /* 40 bytes, one per track (ABI) */
+    int64_t in_offset;  /* where the S16 track begins in d_in, samples per channel; a multiple of 8 */
+    int64_t in_samples; /* its FINAL length */
+    int64_t out_offset; /* where the resampled track begins in d_out, samples per channel; a multiple of 64 */
+    int64_t out_plane;  /* planar: distance between the track's planes, a multiple of 64 and >= ceil(in_samples / D); else not read */
+    float scale;        /* float formats; not read for OPUSGPU_TRACKS_S16 */
+    int32_t reserved;   /* 0 */
+} opusgpu_resample_span;
+/* k_tracks_resample alone: d_in holds packed interleaved int16 tracks of `channels` (1 - 8) channels, 16-byte aligned; `spans` is a
+ * HOST array of n_tracks records.  Writes the tracks of TRACK RATES into d_out (128-byte aligned) in `format`.  The kernel reads
+ * d_in in aligned 16-byte pieces: the buffer must reach to the end of the piece that holds a track's last sample (a buffer of
+ * opusgpu_file_batch_track_samples does).  The caller guarantees that the spans lie inside both buffers and do not overlap in
+ * d_out.  Uploads the records and its tile table, launches on the context's stream (or `hip_stream`), waits, and frees both on
+ * every way out.  OPUSGPU_BAD_ARG before any device work: an unknown rate or format, 48000 without `mono`, `mono` with more than 2
+ * channels, a span that breaks the rules above, a scale that is not finite with a float format. */
+int opusgpu_tracks_resample_device(opusgpu_ctx *ctx, int n_tracks, const opusgpu_resample_span *spans, const void *d_in, int channels,
+                                   int rate, int mono, int format, void *d_out, void *hip_stream);
+/* opusgpu_files_decode into resampled tracks: allocates a scratch S16 track buffer (opusgpu_file_batch_track_samples x channels x 2
+ * bytes), runs opusgpu_files_decode into it -- steps, assembly and ordering unchanged --, takes the final lengths from its
+ * outcome, runs k_tracks_resample into d_out and frees the scratch on every way out.  d_out: opusgpu_resample_layout's total x
+ * out_channels elements of `format`, 128-byte aligned.  scale as for opusgpu_files_decode_as.  out_offsets[i] and out_lengths[i]
+ * (either may be NULL): where resampled track i begins and its length ceil(final / D); track_lengths_out and status_out as for
+ * opusgpu_files_decode (the lengths at 48 kHz).  OPUSGPU_BAD_ARG before any device work: an unknown rate or format, 48000 without
+ * `mono`, `mono` with more than 2 channels, a scale with OPUSGPU_TRACKS_S16, a scale entry that is not finite.  On a failure the
+ * caller's arrays are left as they were. */
+int opusgpu_files_decode_resampled(opusgpu_ctx *ctx, const opusgpu_file_batch *batch, int rate, int mono, int format, const float *scale,
+                                   void *d_out, int64_t *out_offsets, int64_t *out_lengths, int64_t *track_lengths_out,
+                                   int32_t *status_out);
+
 /* ---- WHOLE FILES / MULTISTREAM: N surround Ogg Opus files in, N trimmed interleaved tracks in HBM out -----------------------------
  * The two sections above joined: files whose OpusHead carries channel mapping family 1 (1 - 8 channels, `streams` elementary
  * streams) are planned by the same reader-driven loop as stereo files and decoded by an opusgpu_ms of their layout.  The reader's
@@ -706,6 +760,11 @@ int opusgpu_ms_tracks_assemble_device_as(opusgpu_ms *ms, int n_segs, const void 
                                          int format, const void *d_place, void *d_tracks, void *d_track_state, void *hip_stream);
 int opusgpu_ms_files_decode_as(opusgpu_ms *ms, const opusgpu_ms_file_batch *batch, int format, const float *scale, void *d_tracks,
                                int64_t *track_lengths_out, int32_t *status_out);
+/* opusgpu_files_decode_resampled behind opusgpu_ms_files_decode (TRACK RATES in WHOLE FILES): all of the layout's channels; there is no
+ * `mono` -- a surround downmix needs a matrix and is not offered -- so rate 48000 is OPUSGPU_BAD_ARG here. */
+int opusgpu_ms_files_decode_resampled(opusgpu_ms *ms, const opusgpu_ms_file_batch *batch, int rate, int format, const float *scale,
+                                      void *d_out, int64_t *out_offsets, int64_t *out_lengths, int64_t *track_lengths_out,
+                                      int32_t *status_out);
 
 #ifdef __cplusplus
 }

@@ -8,7 +8,9 @@ and then `python3 tools/files_rate.py --stats DIR` reads DIR's kernel_stats.csv 
 kept samples x 4).  Also: the planner's files/s on --threads threads next to opusgpu_pages_demux's pages/s on the same pages.
 --format f32 | f32_planar: the whole call per track format instead (tools/format_rate.py), in order and pipelined; --stats then
 reads the float kernels' rows too (6 bytes moved per sample and channel instead of 4).
-usage (GPU box): python3 tools/files_rate.py [--n N] [--reps R] [--format F] | python3 tools/files_rate.py --stats DIR [--n N]"""
+--rate R [--mono]: the whole call at a track rate instead (tools/resample_rate.py), in order and pipelined; --stats then prints
+k_tracks_resample's row as well.
+usage (GPU box): python3 tools/files_rate.py [--n N] [--reps R] [--format F | --rate R [--mono]] | python3 tools/files_rate.py --stats DIR [--n N]"""
 import argparse
 import ctypes as C
 import glob
@@ -30,9 +32,12 @@ ap.add_argument("--threads", type=int, default=16)
 ap.add_argument("--stats", default=None)
 ap.add_argument("--format", choices=["f32", "f32_planar"], default=None,
                 help="compare the whole decode call: int16 tracks, int16 + conversion in torch, the fused float format (tools/format_rate.py)")
+ap.add_argument("--rate", type=int, choices=[48000, 24000, 16000, 12000, 8000], default=None,
+                help="compare the whole decode call: int16 tracks, int16 + resampling in torch, the resampled tracks (tools/resample_rate.py)")
+ap.add_argument("--mono", action="store_true")
 args = ap.parse_args()
 n = args.n
-if args.format:
+if args.format or args.rate:
     import torch  # before the library: one HIP runtime for both
 
 spec = importlib.util.spec_from_file_location("esp32_opus_player_amd", os.path.join(here, "..", "esp32-opus-player_amd", "__init__.py"))
@@ -48,9 +53,13 @@ if args.stats:
     import csv
     rows = []
     for f in glob.glob(os.path.join(args.stats, "**", "*kernel_stats.csv"), recursive=True):
-        rows += [r for r in csv.DictReader(open(f)) if "k_tracks_assemble" in r["Name"]]
+        rows += [r for r in csv.DictReader(open(f)) if "k_tracks_assemble" in r["Name"] or "k_tracks_resample" in r["Name"]]
     assert rows, "no k_tracks_assemble in the kernel statistics"
     for r in rows:
+        if "k_tracks_resample" in r["Name"]:  # one launch per batch; its bytes depend on rate and format: time only
+            print(json.dumps({"kernel": r["Name"].split("(")[0], "calls": int(r["Calls"]), "avg_ms_per_launch": round(float(r["AverageNs"]) / 1e6, 4),
+                              "min_ms": round(float(r["MinNs"]) / 1e6, 4), "s16_bytes_read_per_batch": MOVED // 2}))
+            continue
         avg_ms = float(r["AverageNs"]) / 1e6
         moved = MOVED * 3 // 2 if "_f32" in r["Name"] else MOVED  # float tracks: 2 bytes in, 4 bytes out
         print(json.dumps({"kernel": r["Name"].split("(")[0], "calls": int(r["Calls"]), "avg_ms_per_launch": round(avg_ms, 4),
@@ -67,6 +76,22 @@ if args.format:
     for name, pipe in (("in_order", 0), ("pipelined", 1)):
         ctx.set_pipeline(pipe)
         print(json.dumps(format_rate.compare(torch, pkg, ctx.lib.opusgpu_files_decode_as, ctx.h, ctx._chk, b, args.format, args.reps, name)))
+    ctx.close()
+    raise SystemExit(0)
+
+if args.rate:
+    import resample_rate
+    b = pkg.FileBatch([r.tobytes() for r in files], channels=2, flags=pkg.PAGES_GROUP_BY_MODE, threads=args.threads)
+    assert (b.info["status"] == 0).all() and b.n_steps == 10
+    ctx = pkg.Context(0)
+    ctx.streams_alloc(n, 2)
+    for name, pipe in (("in_order", 0), ("pipelined", 1)):
+        ctx.set_pipeline(pipe)
+        print(json.dumps(resample_rate.compare(
+            torch, pkg, lambda d, ln, st: ctx._chk(ctx.lib.opusgpu_files_decode(ctx.h, b.h, d, ln, st), "opusgpu_files_decode"),
+            lambda fmt, d, oo, ol, ln, st: ctx._chk(ctx.lib.opusgpu_files_decode_resampled(ctx.h, b.h, args.rate, int(args.mono), fmt, None, d, oo,
+                                                                                          ol, ln, st), "opusgpu_files_decode_resampled"),
+            b, args.rate, args.mono, args.reps, name)))
     ctx.close()
     raise SystemExit(0)
 

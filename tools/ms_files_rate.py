@@ -12,7 +12,8 @@ The kernels' own times come from a kernel trace: run this script under `rocprofv
 it reads and writes the kept samples x 6 channels x 2 bytes each, k_ms_tracks_assemble_f32 reads 2 bytes and writes 4; k_ms_map:
 ms_rate.py's count per step).
 --format f32 | f32_planar: the whole call per track format instead (tools/format_rate.py).
-usage (GPU box): python3 tools/ms_files_rate.py [--n N] [--reps R] [--format F] | python3 tools/ms_files_rate.py --stats DIR [--n N]"""
+--rate R: the whole call at a track rate instead (tools/resample_rate.py).
+usage (GPU box): python3 tools/ms_files_rate.py [--n N] [--reps R] [--format F | --rate R] | python3 tools/ms_files_rate.py --stats DIR [--n N]"""
 import argparse
 import ctypes as C
 import glob
@@ -33,8 +34,10 @@ ap.add_argument("--threads", type=int, default=16)
 ap.add_argument("--stats", default=None)
 ap.add_argument("--format", choices=["f32", "f32_planar"], default=None,
                 help="compare the whole decode call: int16 tracks, int16 + conversion in torch, the fused float format (tools/format_rate.py)")
+ap.add_argument("--rate", type=int, choices=[24000, 16000, 12000, 8000], default=None,
+                help="compare the whole decode call: int16 tracks, int16 + resampling in torch, the resampled tracks (tools/resample_rate.py)")
 args = ap.parse_args()
-if args.format:
+if args.format or args.rate:
     import torch  # before the library is loaded: one HIP runtime for both
 n = args.n
 
@@ -130,6 +133,18 @@ if args.format:
     import format_rate
     ms = pkg.MultistreamContext(0, n, *LAYOUT)
     print(json.dumps(format_rate.compare(torch, pkg, ms.lib.opusgpu_ms_files_decode_as, ms.h, ms._chk, b, args.format, args.reps, "in_order")))
+    ms.close()
+    raise SystemExit(0)
+
+if args.rate:
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import resample_rate
+    ms = pkg.MultistreamContext(0, n, *LAYOUT)
+    print(json.dumps(resample_rate.compare(
+        torch, pkg, lambda d, ln, st: ms._chk(ms.lib.opusgpu_ms_files_decode(ms.h, b.h, d, ln, st), "opusgpu_ms_files_decode"),
+        lambda fmt, d, oo, ol, ln, st: ms._chk(ms.lib.opusgpu_ms_files_decode_resampled(ms.h, b.h, args.rate, fmt, None, d, oo, ol, ln, st),
+                                               "opusgpu_ms_files_decode_resampled"),
+        b, args.rate, False, args.reps, "in_order")))
     ms.close()
     raise SystemExit(0)
 
