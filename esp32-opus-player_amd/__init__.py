@@ -40,6 +40,7 @@ EXPORTS = [
     "opusgpu_ms_tracks_assemble_device_as", "opusgpu_ms_files_decode_as",
     "opusgpu_resample_taps", "opusgpu_resample_layout", "opusgpu_tracks_resample_device", "opusgpu_files_decode_resampled",
     "opusgpu_ms_files_decode_resampled",
+    "opusgpu_downmix_matrix", "opusgpu_tracks_resample_mixed_device", "opusgpu_files_decode_mixed", "opusgpu_ms_files_decode_mixed",
 ]
 
 
@@ -120,6 +121,8 @@ TRACK_FORMATS = {"s16": TRACKS_S16, "f32": TRACKS_F32, "f32_planar": TRACKS_F32_
 RESAMPLE_SPAN_DTYPE = np.dtype([("in_offset", "<i8"), ("in_samples", "<i8"), ("out_offset", "<i8"), ("out_plane", "<i8"), ("scale", "<f4"),
                                 ("reserved", "<i4")])
 TRACK_RATES = {48000: 1, 24000: 2, 16000: 3, 12000: 4, 8000: 6}
+# opusgpu_mix_matrix (include/opusgpu.h, CHANNEL MIX): m[o][c] in Q14
+MIX_MATRIX_DTYPE = np.dtype([("out_channels", "<i4"), ("in_channels", "<i4"), ("m", "<i2", (8, 8))])
 OPUSGPU_BAD_ARG, OPUSGPU_UNIMPLEMENTED, OPUSGPU_CELT_BAD_ARG = -1, -5, -18
 RFC_FRAME = 2880
 
@@ -236,6 +239,10 @@ def load_lib():
     lib.opusgpu_tracks_resample_device.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
     lib.opusgpu_files_decode_resampled.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
     lib.opusgpu_ms_files_decode_resampled.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
+    lib.opusgpu_downmix_matrix.argtypes = [C.c_int, C.c_int, vp]
+    lib.opusgpu_tracks_resample_mixed_device.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp]
+    lib.opusgpu_files_decode_mixed.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp]
+    lib.opusgpu_ms_files_decode_mixed.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp]
     _lib = lib
     return lib
 
@@ -591,6 +598,62 @@ def track_rate_args(batch, rate=48000, mono=False, format="s16", out=None, devic
     return TRACK_RATES[rate], ch_out, offsets, total, out
 
 
+def downmix_matrix(channels, out_channels):
+    """opusgpu_downmix_matrix: the default table that takes `channels` (1 - 8, Vorbis order) to 2 or 1 -> int16 [out, in], Q14."""
+    rec = np.zeros(1, dtype=MIX_MATRIX_DTYPE)
+    if load_lib().opusgpu_downmix_matrix(int(channels), int(out_channels), rec.ctypes.data) != 0:
+        raise ValueError(f"there is no default downmix of {channels!r} channels to {out_channels!r}")
+    return rec["m"][0, :out_channels, :channels].copy()
+
+
+def mix_matrix(mix, channels):
+    """A `mix` argument for tracks of `channels` channels as its opusgpu_mix_matrix record (a MIX_MATRIX_DTYPE array of one).
+    mix: "mono" or "stereo" (the default table), an integer array [out, in] taken as Q14, or a float array converted by
+    np.rint(a * 16384).  Raises ValueError for what CHANNEL MIX refuses and for a float array that leaves int16."""
+    if isinstance(mix, str):
+        if mix not in ("mono", "stereo"):
+            raise ValueError(f"mix must be 'mono', 'stereo' or a matrix, not {mix!r}")
+        m = downmix_matrix(channels, 1 if mix == "mono" else 2)
+    else:
+        m = np.asarray(mix)
+        if m.ndim != 2 or m.dtype.kind not in "iuf":
+            raise ValueError(f"mix must be a matrix [out_channels, in_channels] of numbers, not shape {m.shape} of {m.dtype}")
+        if m.dtype.kind == "f":
+            if not np.isfinite(m).all():
+                raise ValueError("mix entries must be finite")
+            m = np.rint(m.astype(np.float64) * 16384)
+        if m.size and (m.min() < -32768 or m.max() > 32767):
+            raise ValueError("mix entries must fit int16 in Q14: [-2, 2)")
+        m = m.astype(np.int16)
+    co, ci = m.shape
+    if not 1 <= co <= 8 or not 1 <= ci <= 8:
+        raise ValueError(f"mix must have 1 - 8 rows and columns, not {m.shape}")
+    if ci != channels:
+        raise ValueError(f"mix has {ci} columns for tracks of {channels} channels")
+    if np.abs(m.astype(np.int64)).sum(axis=1).max() > 65535:
+        raise ValueError("a row of mix has sum |M| > 65535 in Q14: the int32 sum would not be exact")
+    rec = np.zeros(1, dtype=MIX_MATRIX_DTYPE)
+    rec["out_channels"], rec["in_channels"] = co, ci
+    rec["m"][0, :co, :ci] = m
+    return rec
+
+
+def track_mix_args(batch, mix, rate=48000, format="s16", out=None, device=0):
+    """What decode_files makes of its mix= (and rate=) for a planned batch, before any device work: (D, output channels, out_offsets,
+    total samples per channel, out flattened or None, the matrix record).  Raises ValueError for what mix_matrix refuses, a rate or
+    format that does not exist, and an `out` that does not fit the MIXED tracks: total * out_channels elements."""
+    rec = mix_matrix(mix, batch.channels)
+    if rate not in TRACK_RATES:
+        raise ValueError(f"rate must be one of {sorted(TRACK_RATES)}, not {rate!r}")
+    if format not in TRACK_FORMATS:
+        raise ValueError(f"format must be one of {sorted(TRACK_FORMATS)}, not {format!r}")
+    ch_out = int(rec["out_channels"][0])
+    offsets, total = resample_layout(batch.info["track_samples"], rate)
+    if out is not None:
+        out = _out_flat(out, max(total, 1) * ch_out, format, device)
+    return TRACK_RATES[rate], ch_out, offsets, total, out, rec
+
+
 def _decode_planned(lib, chk, name, handle, batch, mem, args):
     """The shared body of the two decode_files: runs the decode call `name` of `lib` (`name`_as for a float format) for the decoder
     `handle` over `batch` into `out` (a torch tensor on the device: nothing comes to the host) or into a track buffer from `mem` (a
@@ -848,8 +911,17 @@ class Context:
         self._chk(self.lib.opusgpu_tracks_resample_device(self.h, spans.size, spans.ctypes.data, d_in, channels, int(rate), 1 if mono else 0,
                                                           format, d_out, stream), "opusgpu_tracks_resample_device")
 
+    def tracks_resample_mixed_device(self, spans, d_in, channels, rate, mix, format, d_out, stream=None):
+        """k_tracks_resample_mix alone (include/opusgpu.h CHANNEL MIX): as tracks_resample_device, with `mix` an int16 Q14 matrix
+        [out, in] or a MIX_MATRIX_DTYPE record in place of mono; d_out holds the matrix's rows as channels."""
+        spans = np.ascontiguousarray(spans, dtype=RESAMPLE_SPAN_DTYPE)
+        rec = mix if getattr(mix, "dtype", None) == MIX_MATRIX_DTYPE else mix_matrix(mix, channels)
+        rec = np.ascontiguousarray(rec)
+        self._chk(self.lib.opusgpu_tracks_resample_mixed_device(self.h, spans.size, spans.ctypes.data, d_in, channels, int(rate),
+                                                                rec.ctypes.data, format, d_out, stream), "opusgpu_tracks_resample_mixed_device")
+
     def decode_files(self, files, rfc=False, flags=PAGES_GROUP_BY_MODE, threads=1, batch=None, format="s16", scale=None, out=None,
-                     rate=48000, mono=False):
+                     rate=48000, mono=False, mix=None):
         """Whole Ogg Opus files -> (list of int16 arrays [samples, channels], one trimmed track per file, info).  The context's
         streams 0 .. len(files) - 1 are (re)allocated when there are too few and get fresh state; its mode is set to `rfc`.
         info: FILE_INFO_DTYPE records with two more fields: `final_status` (the first failed frame's code, else the plan's status)
@@ -863,17 +935,27 @@ class Context:
         rate: 48000, or 24000 / 16000 / 12000 / 8000 for tracks decimated by D = 48000 / rate on the GPU (include/opusgpu.h TRACK
         RATES: an integer FIR over the int16 track, bit-exact); mono: one channel, (l + r + 1) >> 1 of a stereo track, at any rate.
         The tracks are then [ceil(len / D), 1 or channels] (planar: transposed), `out` is sized for them (track_rate_args), and
-        info has `out_samples` and `out_offset` more; `track_samples` stays the final length at 48 kHz."""
+        info has `out_samples` and `out_offset` more; `track_samples` stays the final length at 48 kHz.
+        mix: None, or a channel mix in front of the rate (include/opusgpu.h CHANNEL MIX; mix_matrix says what it may be: "mono",
+        "stereo", a Q14 integer matrix [out, in] or a float one), at any rate, 48000 included; not together with mono=True.  The
+        tracks are then [ceil(len / D), out] (planar: transposed), `out` is sized for them (track_mix_args)."""
+        if mix is not None and mono:
+            raise ValueError("mix and mono=True exclude each other: the row {8192, 8192} is mono")
         own = batch is None
         channels = self.channels or 2
         if own:
             batch = FileBatch(files, channels=channels, rfc=rfc, flags=flags, threads=threads)
         try:
-            rargs = track_rate_args(batch, rate, mono, format, out, self.device)
+            margs = None if mix is None else track_mix_args(batch, mix, rate, format, out, self.device)
+            rargs = track_rate_args(batch, rate, mono, format, out, self.device) if mix is None else margs[:5]
             args = track_format_args(batch, format, scale, out if rargs is None else None, self.device)
             if self.n_streams < batch.n_files or self.channels != batch.channels:
                 self.streams_alloc(max(batch.n_files, 1), batch.channels)
             self.set_mode(batch.rfc)
+            if margs is not None:
+                def call(fmt, scale_p, d_out, *arrays):
+                    return self.lib.opusgpu_files_decode_mixed(self.h, batch.h, int(rate), margs[5].ctypes.data, fmt, scale_p, d_out, *arrays)
+                return _decode_planned_resampled(self._chk, "opusgpu_files_decode_mixed", call, batch, self, args, rargs)
             if rargs is not None:
                 def call(fmt, scale_p, d_out, *arrays):
                     return self.lib.opusgpu_files_decode_resampled(self.h, batch.h, int(rate), 1 if mono else 0, fmt, scale_p, d_out, *arrays)
@@ -1045,21 +1127,27 @@ class MultistreamContext:
                                                                 d_res_mono, format, d_place, d_tracks, d_track_state, stream),
                   "opusgpu_ms_tracks_assemble_device_as")
 
-    def decode_files(self, files, rfc=False, threads=1, batch=None, format="s16", scale=None, out=None, rate=48000):
+    def decode_files(self, files, rfc=False, threads=1, batch=None, format="s16", scale=None, out=None, rate=48000, mix=None):
         """Whole Ogg Opus files of this object's layout -> (list of int16 arrays [samples, channels], one trimmed track per file,
         info), as Context.decode_files returns them: FILE_INFO_DTYPE records plus `final_status` and `bad_packet`, `track_samples`
         the FINAL length.  Decoders 0 .. len(files) - 1 get fresh state; the object's mode is set to the batch's.  batch: an
         MsFileBatch made beforehand from the same files (of this layout; `rfc` is then the batch's).  format, scale, out, rate: as
-        for Context.decode_files, all channels at `rate` (there is no mono downmix of a surround layout)."""
+        for Context.decode_files, all channels at `rate`.  mix: as for Context.decode_files -- "mono" and "stereo" are the default
+        downmix tables of the layout's channel count; there is no `mono` argument here."""
         own = batch is None
         if own:
             batch = MsFileBatch(files, self.layout, rfc=rfc, threads=threads)
         mem = None
         try:
-            rargs = track_rate_args(batch, rate, False, format, out, self.device, allow_mono=False)
+            margs = None if mix is None else track_mix_args(batch, mix, rate, format, out, self.device)
+            rargs = track_rate_args(batch, rate, False, format, out, self.device, allow_mono=False) if mix is None else margs[:5]
             args = track_format_args(batch, format, scale, out if rargs is None else None, self.device)
             mem = Context(self.device)  # (device memory and copies are a plain context's calls)
             self.set_mode(batch.rfc)
+            if margs is not None:
+                def call(fmt, scale_p, d_out, *arrays):
+                    return self.lib.opusgpu_ms_files_decode_mixed(self.h, batch.h, int(rate), margs[5].ctypes.data, fmt, scale_p, d_out, *arrays)
+                return _decode_planned_resampled(self._chk, "opusgpu_ms_files_decode_mixed", call, batch, mem, args, rargs)
             if rargs is not None:
                 def call(fmt, scale_p, d_out, *arrays):
                     return self.lib.opusgpu_ms_files_decode_resampled(self.h, batch.h, int(rate), fmt, scale_p, d_out, *arrays)

@@ -464,4 +464,17 @@ int opusgpu_ms_files_decode_resampled(opusgpu_ms *ms, const opusgpu_ms_file_batc
         [&](int code, const char *what, hipError_t e) { return ms_fail(ms, code, what, e); });
 }
 
+// opusgpu_files_decode_mixed behind opusgpu_ms_files_decode: the surround tracks mixed down (or about) on their way to `rate`.
+int opusgpu_ms_files_decode_mixed(opusgpu_ms *ms, const opusgpu_ms_file_batch *batch, int rate, const opusgpu_mix_matrix *mix, int format,
+                                  const float *scale, void *d_out, int64_t *out_offsets, int64_t *out_lengths, int64_t *track_lengths_out,
+                                  int32_t *status_out) {
+    if (!ms || !batch || !mix) return OPUSGPU_BAD_ARG;
+    return files_resampled_run(
+        *batch, ms->device, ms->stream, rate, 0, format, scale, d_out, out_offsets, out_lengths, track_lengths_out, status_out,
+        [&](void *d_s16, int64_t *lengths, int32_t *status) {
+            return ms_files_decode_run(ms, batch, OPUSGPU_TRACKS_S16, nullptr, d_s16, lengths, status);
+        },
+        [&](int code, const char *what, hipError_t e) { return ms_fail(ms, code, what, e); }, mix);
+}
+
 } // extern "C"

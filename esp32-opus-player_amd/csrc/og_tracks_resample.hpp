@@ -1,10 +1,12 @@
-// og_tracks_resample.hpp -- tracks at 8 / 12 / 16 / 24 kHz and the mono downmix (include/opusgpu.h, TRACK RATES): the kernel that
-// turns packed int16 tracks into decimated ones, its host side, and the whole-file call that ends in it.  Included at the end of
+// og_tracks_resample.hpp -- tracks at 8 / 12 / 16 / 24 kHz, the mono downmix and the channel mix (include/opusgpu.h, TRACK RATES and
+// CHANNEL MIX): the kernels that turn packed int16 tracks into decimated ones, their host side, and the whole-file calls that end in them.  Included at the end of
 // og_api.hip behind og_tracks.hpp (files_decode_run, track_f32, track_store4) and in front of og_ms_tracks.hpp.
 #pragma once
 #include <cmath>
+#include <cstdlib>
 #define OG_RS_PAIRS_ROM static __device__ const
 #include "og_resample_taps.hpp"
+#include "og_downmix_tables.hpp"
 
 // ---- kernel -------------------------------------------------------------------------------------------
 // k_tracks_resample<D>: one workgroup per entry of a tile table built on the host, a tile being `tile` consecutive output samples
@@ -30,6 +32,7 @@
 //      interleaved track, or 4 floats of one plane -- and stores it whole (track_store4 for floats); tracks begin at multiples
 //      of 64 samples and tiles at multiples of `tile`, so only a track's last piece can be partial: it goes out as element stores.
 // D = 1 (rate 48000, mono only) has no filter: the staged downmix is the result.
+// Steps 2 and 3 are functions (rs_mac, rs_store) that k_tracks_resample_mix<D>, the kernel with a channel mix in step 1, shares.
 struct ResampleSpan {
     long long in_offset, in_samples, out_offset, out_plane;
     float scale;
@@ -56,6 +59,85 @@ __device__ __forceinline__ const u32 *rs_pairs() {
 typedef short og_i16x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ i32 rs_dot2(u32 x, u32 taps, i32 acc) { // acc + x.lo * taps.lo + x.hi * taps.hi (v_dot2_i32_i16)
     return __builtin_amdgcn_sdot2(__builtin_bit_cast(og_i16x2, x), __builtin_bit_cast(og_i16x2, taps), acc, false);
+}
+
+// Step 2 of k_tracks_resample<D> and k_tracks_resample_mix<D>: the planes of CO channels -> the tile's results in `yo`.
+template <int D>
+__device__ __forceinline__ void rs_mac(const i16 *lds, i16 *yo, int CO, int tile_shift, int n_out, bool planar, int tid) {
+    if constexpr (D > 1) { // four outputs per lane
+        const int tile = 1 << tile_shift, Q = tile + RS_PLANE_PAD;
+        const u32 *const pairs = rs_pairs<D>();
+        const int items = CO << (tile_shift - 2);
+        for (int x = tid; x < items; x += 256) {
+            const int c = x >> (tile_shift - 2), i = x & ((tile >> 2) - 1);
+            if (4 * i >= n_out) continue;
+            i32 acc[4] = {16384, 16384, 16384, 16384};
+#pragma unroll
+            for (int p = 0; p < D; p++) {
+                const uint2 *src = reinterpret_cast<const uint2 *>(lds + (c * D + p) * Q + 4 * i); // 8-byte aligned
+                u32 X[14];
+#pragma unroll
+                for (int w = 0; w < 7; w++) {
+                    const uint2 t = src[w];
+                    X[2 * w] = t.x, X[2 * w + 1] = t.y;
+                }
+#pragma unroll
+                for (int w = 0; w < OG_RS_PAIRS; w++) {
+                    const u32 te = pairs[(2 * p) * OG_RS_PAIRS + w], to = pairs[(2 * p + 1) * OG_RS_PAIRS + w];
+                    acc[0] = rs_dot2(X[w], te, acc[0]);
+                    acc[1] = rs_dot2(X[w], to, acc[1]);
+                    acc[2] = rs_dot2(X[w + 1], te, acc[2]);
+                    acc[3] = rs_dot2(X[w + 1], to, acc[3]);
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const i32 y = acc[r] >> 15;
+                const int j = 4 * i + r;
+                yo[planar ? c * tile + j : j * CO + c] = (i16)(y < -32768 ? -32768 : y > 32767 ? 32767 : y);
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// Step 3 of both kernels: the tile's n_out results of CO channels -> the track, 16 bytes per lane and store.
+__device__ __forceinline__ void rs_store(const i16 *yo, const ResampleSpan &sp, const ResampleTile &tl, int CO, int n_out, int tile, int format,
+                                         bool planar, void *__restrict__ out, int tid) {
+    const float k = sp.scale;
+    if (format == OPUSGPU_TRACKS_S16) {
+        i16 *const dst = static_cast<i16 *>(out) + (sp.out_offset + tl.first) * CO;
+        const int EN = n_out * CO;
+        for (int q = tid; q < (EN + 7) >> 3; q += 256) {
+            const uint4 v = *reinterpret_cast<const uint4 *>(yo + 8 * q);
+            if (8 * q + 8 <= EN) {
+                *reinterpret_cast<uint4 *>(dst + 8 * q) = v;
+            } else {
+                const u32 w32[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                for (int h = 0; h < 8; h++)
+                    if (8 * q + h < EN) dst[8 * q + h] = (i16)(w32[h >> 1] >> (16 * (h & 1)));
+            }
+        }
+    } else {
+        // interleaved: one run of n_out * CO elements; planar: CO runs of n_out, one per plane (a mono track is its plane)
+        const int runs = planar ? CO : 1, EN = planar ? n_out : n_out * CO;
+        const int pp = (EN + 3) >> 2; // pieces per run
+        float *const base = static_cast<float *>(out) + (planar ? sp.out_offset * CO + tl.first : (sp.out_offset + tl.first) * CO);
+        for (int x = tid; x < runs * pp; x += 256) {
+            const int c = planar ? x / pp : 0, q = x - c * pp;
+            const uint2 v = *reinterpret_cast<const uint2 *>(yo + c * tile + 4 * q);
+            const float f[4] = {track_f32(v.x, k), track_f32(v.x >> 16, k), track_f32(v.y, k), track_f32(v.y >> 16, k)};
+            float *const d = base + c * sp.out_plane + 4 * q;
+            if (4 * q + 4 <= EN) {
+                track_store4(d, f);
+            } else {
+#pragma unroll
+                for (int h = 0; h < 4; h++)
+                    if (4 * q + h < EN) d[h] = f[h];
+            }
+        }
+    }
 }
 
 template <int D>
@@ -119,77 +201,100 @@ __global__ void __launch_bounds__(256) k_tracks_resample(const ResampleTile *__r
     }
     __syncthreads();
 
-    // 2. four outputs per lane
-    if constexpr (D > 1) {
-        const u32 *const pairs = rs_pairs<D>();
-        const int items = CO << (tile_shift - 2);
-        for (int x = tid; x < items; x += 256) {
-            const int c = x >> (tile_shift - 2), i = x & ((tile >> 2) - 1);
-            if (4 * i >= n_out) continue;
-            i32 acc[4] = {16384, 16384, 16384, 16384};
-#pragma unroll
-            for (int p = 0; p < D; p++) {
-                const uint2 *src = reinterpret_cast<const uint2 *>(lds + (c * D + p) * Q + 4 * i); // 8-byte aligned
-                u32 X[14];
-#pragma unroll
-                for (int w = 0; w < 7; w++) {
-                    const uint2 t = src[w];
-                    X[2 * w] = t.x, X[2 * w + 1] = t.y;
-                }
-#pragma unroll
-                for (int w = 0; w < OG_RS_PAIRS; w++) {
-                    const u32 te = pairs[(2 * p) * OG_RS_PAIRS + w], to = pairs[(2 * p + 1) * OG_RS_PAIRS + w];
-                    acc[0] = rs_dot2(X[w], te, acc[0]);
-                    acc[1] = rs_dot2(X[w], to, acc[1]);
-                    acc[2] = rs_dot2(X[w + 1], te, acc[2]);
-                    acc[3] = rs_dot2(X[w + 1], to, acc[3]);
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                const i32 y = acc[r] >> 15;
-                const int j = 4 * i + r;
-                yo[planar ? c * tile + j : j * CO + c] = (i16)(y < -32768 ? -32768 : y > 32767 ? 32767 : y);
-            }
-        }
-        __syncthreads();
-    }
+    rs_mac<D>(lds, yo, CO, tile_shift, n_out, planar, tid);          // 2. four outputs per lane
+    rs_store(yo, sp, tl, CO, n_out, tile, format, planar, out, tid); // 3. LDS -> the track
+}
 
-    // 3. LDS -> the track, 16 bytes per lane and store
-    const float k = sp.scale;
-    if (format == OPUSGPU_TRACKS_S16) {
-        i16 *const dst = static_cast<i16 *>(out) + (sp.out_offset + tl.first) * CO;
-        const int EN = n_out * CO;
-        for (int q = tid; q < (EN + 7) >> 3; q += 256) {
-            const uint4 v = *reinterpret_cast<const uint4 *>(yo + 8 * q);
-            if (8 * q + 8 <= EN) {
-                *reinterpret_cast<uint4 *>(dst + 8 * q) = v;
-            } else {
-                const u32 w32[4] = {v.x, v.y, v.z, v.w};
+// k_tracks_resample_mix<D>: the same kernel with a channel mix in step 1 (include/opusgpu.h, CHANNEL MIX); steps 2 and 3 then run
+// for CO = the matrix's rows.  A mix needs all C channels of a sample in one lane, so the window is cut by SAMPLE here: a lane owns
+// 8 consecutive samples of the track, aligned to 8 from the track's start (in_offset is a multiple of 8: they are exactly C aligned
+// 16-byte pieces), and loads them as C uint4 -- a piece whose first element lies outside the track is not fetched, as above.  C is
+// a template parameter of the staging body (a wave-uniform switch in the kernel picks it), so that every element position is a
+// literal and the 4 C words stay in registers.  For each output channel o (a wave-uniform loop) and each of the 8 samples the sum
+// runs word by word through v_dot2_i32_i16: the word that holds channels (c, c + 1) of the sample against the pair
+// (M[o][c], M[o][c + 1]).  Where a sample begins or ends in the middle of a word (odd C) the pair's other half is a coefficient
+// that does not exist -- M[o][-1] or M[o][C], both 0 in the table -- and meets the neighbouring sample's element.  The table comes
+// by value with the kernel's arguments, pair[o][c + 1] = (M[o][c], M[o][c + 1]) for c = -1 .. 7, and is indexed by o and literals:
+// scalar loads, scalar operands.  The sum starts at 8192 and is exact in int32 (a row's sum |M| <= 65535); >> 14 and the clamp make
+// x_o, 0 for a sample outside [0, in_samples), which goes to place r / D of plane (o, r % D) -- for D = 1 straight to the result
+// area in the order of the destination.
+struct RsMixArgs {
+    i32 co;
+    u32 pair[8][9];
+};
+
+template <int D, int C>
+__device__ __forceinline__ void rs_stage_mix(i16 *lds, const i16 *__restrict__ in, const ResampleSpan &sp, const RsMixArgs &mx, long long n0,
+                                             int Wn, int Q, int tile, bool planar, int tid) {
+    const int CO = mx.co;
+    const long long a0 = n0 & ~7LL;  // the group of 8 that holds the window's first sample (floor, also in front of the track)
+    const int lead = (int)(n0 - a0); // samples of it in front of the window
+    const int groups = (lead + Wn + 7) >> 3;
+    const long long V0 = sp.in_offset * C, V1 = (sp.in_offset + sp.in_samples) * C; // the track's elements; V0 is a multiple of 8
+    for (int k = tid; k < groups; k += 256) {
+        const long long nb = a0 + 8LL * k;           // the lane's first sample, counted from the track's
+        const long long g = (sp.in_offset + nb) * C; // its first element in the buffer, a multiple of 8
+        u32 w[4 * C];
 #pragma unroll
-                for (int h = 0; h < 8; h++)
-                    if (8 * q + h < EN) dst[8 * q + h] = (i16)(w32[h >> 1] >> (16 * (h & 1)));
-            }
+        for (int j = 0; j < C; j++) {
+            uint4 v = make_uint4(0, 0, 0, 0);
+            if (g + 8 * j >= V0 && g + 8 * j < V1) v = *reinterpret_cast<const uint4 *>(in + g + 8 * j);
+            w[4 * j] = v.x, w[4 * j + 1] = v.y, w[4 * j + 2] = v.z, w[4 * j + 3] = v.w;
         }
-    } else {
-        // interleaved: one run of n_out * CO elements; planar: CO runs of n_out, one per plane (a mono track is its plane)
-        const int runs = planar ? CO : 1, EN = planar ? n_out : n_out * CO;
-        const int pp = (EN + 3) >> 2; // pieces per run
-        float *const base = static_cast<float *>(out) + (planar ? sp.out_offset * CO + tl.first : (sp.out_offset + tl.first) * CO);
-        for (int x = tid; x < runs * pp; x += 256) {
-            const int c = planar ? x / pp : 0, q = x - c * pp;
-            const uint2 v = *reinterpret_cast<const uint2 *>(yo + c * tile + 4 * q);
-            const float f[4] = {track_f32(v.x, k), track_f32(v.x >> 16, k), track_f32(v.y, k), track_f32(v.y >> 16, k)};
-            float *const d = base + c * sp.out_plane + 4 * q;
-            if (4 * q + 4 <= EN) {
-                track_store4(d, f);
-            } else {
+        const int r0 = 8 * k - lead; // the lane's first sample in the window (-7 .. -1 possible in group 0)
+        int at[8];                   // where sample s goes in the planes of channel 0, -1: outside the window
 #pragma unroll
-                for (int h = 0; h < 4; h++)
-                    if (4 * q + h < EN) d[h] = f[h];
+        for (int s = 0; s < 8; s++) {
+            const int r = r0 + s;
+            at[s] = r < 0 || r >= Wn ? -1 : D == 1 ? r : (r % D) * Q + r / D;
+        }
+        for (int o = 0; o < CO; o++) {
+#pragma unroll
+            for (int s = 0; s < 8; s++) {
+                i32 acc = 8192;
+#pragma unroll
+                for (int wi = (s * C) >> 1; wi <= (s * C + C - 1) >> 1; wi++) acc = rs_dot2(w[wi], mx.pair[o][2 * wi - s * C + 1], acc);
+                acc >>= 14;
+                const long long n = nb + s;
+                const i16 x = n >= 0 && n < sp.in_samples ? (i16)(acc < -32768 ? -32768 : acc > 32767 ? 32767 : acc) : (i16)0;
+                if (at[s] >= 0) lds[D == 1 ? (planar ? o * tile + at[s] : at[s] * CO + o) : o * D * Q + at[s]] = x;
             }
         }
     }
+}
+
+template <int D>
+__global__ void __launch_bounds__(256) k_tracks_resample_mix(const ResampleTile *__restrict__ tiles, const ResampleSpan *__restrict__ spans,
+                                                              const i16 *__restrict__ in, int C, RsMixArgs mx, int format, int tile_shift,
+                                                              void *__restrict__ out) {
+    extern __shared__ __align__(16) i16 lds[]; // as above, CO the matrix's rows
+    const int tid = (int)threadIdx.x;
+    const ResampleTile tl = tiles[blockIdx.x];
+    const ResampleSpan sp = spans[tl.track];
+    const int tile = 1 << tile_shift, Q = tile + RS_PLANE_PAD;
+    const int CO = mx.co;
+    constexpr int LEAD = D == 1 ? 0 : 12;
+    const long long out_len = (sp.in_samples + D - 1) / D;
+    const long long left = out_len - tl.first;
+    const int n_out = left < tile ? (int)left : tile;
+    if (n_out <= 0) return;
+    i16 *const yo = D == 1 ? lds : lds + CO * D * Q;
+    const bool planar = format == OPUSGPU_TRACKS_F32_PLANAR;
+    const long long n0 = (tl.first - LEAD) * D; // the window's first input sample; negative at a track's head
+    const int Wn = (n_out + 2 * LEAD) * D;      // its samples
+    switch (C) {                                // 1. the window, mixed -> LDS
+        case 1: rs_stage_mix<D, 1>(lds, in, sp, mx, n0, Wn, Q, tile, planar, tid); break;
+        case 2: rs_stage_mix<D, 2>(lds, in, sp, mx, n0, Wn, Q, tile, planar, tid); break;
+        case 3: rs_stage_mix<D, 3>(lds, in, sp, mx, n0, Wn, Q, tile, planar, tid); break;
+        case 4: rs_stage_mix<D, 4>(lds, in, sp, mx, n0, Wn, Q, tile, planar, tid); break;
+        case 5: rs_stage_mix<D, 5>(lds, in, sp, mx, n0, Wn, Q, tile, planar, tid); break;
+        case 6: rs_stage_mix<D, 6>(lds, in, sp, mx, n0, Wn, Q, tile, planar, tid); break;
+        case 7: rs_stage_mix<D, 7>(lds, in, sp, mx, n0, Wn, Q, tile, planar, tid); break;
+        default: rs_stage_mix<D, 8>(lds, in, sp, mx, n0, Wn, Q, tile, planar, tid); break;
+    }
+    __syncthreads();
+    rs_mac<D>(lds, yo, CO, tile_shift, n_out, planar, tid);          // 2. and 3. as in k_tracks_resample
+    rs_store(yo, sp, tl, CO, n_out, tile, format, planar, out, tid);
 }
 
 // ---- host side ----------------------------------------------------------------------------------------
@@ -206,10 +311,34 @@ static int rs_factor(int rate) {
 }
 static int64_t rs_round64(int64_t v) { return (v + 63) / 64 * 64; }
 
-// What every resampling call refuses before any device work: -> the factor D, or 0.
-static int rs_args_factor(int channels, int rate, int mono, int format) {
+// CHANNEL MIX: what a matrix for tracks of `channels` channels must keep.
+static bool rs_mix_ok(const opusgpu_mix_matrix &m, int channels) {
+    if (m.out_channels < 1 || m.out_channels > 8 || m.in_channels < 1 || m.in_channels > 8 || m.in_channels != channels) return false;
+    for (int o = 0; o < m.out_channels; o++) {
+        int sum = 0;
+        for (int c = 0; c < m.in_channels; c++) sum += std::abs((int)m.m[o][c]);
+        if (sum > 65535) return false;
+    }
+    return true;
+}
+// The matrix as the kernel takes it: pair[o][k] = (M[o][k - 1], M[o][k]), entries outside the matrix 0 whatever the record holds.
+static RsMixArgs rs_mix_args(const opusgpu_mix_matrix &m) {
+    RsMixArgs a{};
+    a.co = m.out_channels;
+    for (int o = 0; o < m.out_channels; o++)
+        for (int k = 0; k <= 8; k++) {
+            const u32 lo = k >= 1 && k - 1 < m.in_channels ? (uint16_t)m.m[o][k - 1] : 0, hi = k < m.in_channels ? (uint16_t)m.m[o][k] : 0;
+            a.pair[o][k] = lo | hi << 16;
+        }
+    return a;
+}
+
+// What every resampling call refuses before any device work: -> the factor D, or 0.  With a matrix there is no `mono`, and 48000
+// is the mix alone.
+static int rs_args_factor(int channels, int rate, int mono, int format, const opusgpu_mix_matrix *mix = nullptr) {
     const int D = rs_factor(rate);
-    if (!D || channels < 1 || channels > 8 || (D == 1 && !mono) || (mono && channels > 2)) return 0;
+    if (!D || channels < 1 || channels > 8) return 0;
+    if (mix ? mono || !rs_mix_ok(*mix, channels) : (D == 1 && !mono) || (mono && channels > 2)) return 0;
     if (format != OPUSGPU_TRACKS_S16 && format != OPUSGPU_TRACKS_F32 && format != OPUSGPU_TRACKS_F32_PLANAR) return 0;
     return D;
 }
@@ -238,10 +367,10 @@ struct RsDevBuf {
 // hip_failed(code, what, e) keeps the message of the object the call belongs to and returns `code`.
 template <class Fail>
 static int tracks_resample_run(int device, hipStream_t s, int n_tracks, const opusgpu_resample_span *spans, const void *d_in, int channels,
-                               int rate, int mono, int format, void *d_out, Fail hip_failed) {
-    const int D = rs_args_factor(channels, rate, mono, format);
+                               int rate, int mono, int format, void *d_out, Fail hip_failed, const opusgpu_mix_matrix *mix = nullptr) {
+    const int D = rs_args_factor(channels, rate, mono, format, mix);
     if (!D || n_tracks < 0 || (n_tracks && !spans)) return OPUSGPU_BAD_ARG;
-    const int CO = mono ? 1 : channels;
+    const int CO = mix ? mix->out_channels : mono ? 1 : channels;
     const int tile_shift = CO == 1 ? 10 : CO == 2 ? 9 : 8; // 1,024 outputs of one channel .. 256 of eight: four per lane
     const int64_t tile = (int64_t)1 << tile_shift;
     std::vector<ResampleTile> tiles;
@@ -270,12 +399,22 @@ static int tracks_resample_run(int device, hipStream_t s, int n_tracks, const op
         hipLaunchKernelGGL(kern, dim3((unsigned)tiles.size()), dim3(256), lds, s, (const ResampleTile *)d_tiles.p, (const ResampleSpan *)d_spans.p,
                            (const i16 *)d_in, channels, mono ? 1 : 0, format, tile_shift, d_out);
     };
-    switch (D) {
+    const RsMixArgs mx = mix ? rs_mix_args(*mix) : RsMixArgs{};
+    auto go_mix = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3((unsigned)tiles.size()), dim3(256), lds, s, (const ResampleTile *)d_tiles.p, (const ResampleSpan *)d_spans.p,
+                           (const i16 *)d_in, channels, mx, format, tile_shift, d_out);
+    };
+    switch (mix ? -D : D) {
         case 1: go(k_tracks_resample<1>); break;
         case 2: go(k_tracks_resample<2>); break;
         case 3: go(k_tracks_resample<3>); break;
         case 4: go(k_tracks_resample<4>); break;
-        default: go(k_tracks_resample<6>); break;
+        case 6: go(k_tracks_resample<6>); break;
+        case -1: go_mix(k_tracks_resample_mix<1>); break;
+        case -2: go_mix(k_tracks_resample_mix<2>); break;
+        case -3: go_mix(k_tracks_resample_mix<3>); break;
+        case -4: go_mix(k_tracks_resample_mix<4>); break;
+        default: go_mix(k_tracks_resample_mix<6>); break;
     }
     RS_CHK(hipGetLastError());
     RS_CHK(hipStreamSynchronize(s));
@@ -302,8 +441,8 @@ static void rs_batch_spans(const og_batch &b, int D, const int64_t *final_length
 template <class Decode, class Fail>
 static int files_resampled_run(const og_batch &b, int device, hipStream_t s, int rate, int mono, int format, const float *scale, void *d_out,
                                int64_t *out_offsets, int64_t *out_lengths, int64_t *track_lengths_out, int32_t *status_out, Decode decode,
-                               Fail hip_failed) {
-    const int D = rs_args_factor(b.channels, rate, mono, format);
+                               Fail hip_failed, const opusgpu_mix_matrix *mix = nullptr) {
+    const int D = rs_args_factor(b.channels, rate, mono, format, mix);
     if (!D || !rs_scale_ok(format, scale, b.n_files)) return OPUSGPU_BAD_ARG;
     const size_t n = (size_t)b.n_files;
     std::vector<int64_t> lengths(n, 0), offsets;
@@ -317,7 +456,8 @@ static int files_resampled_run(const og_batch &b, int device, hipStream_t s, int
     }
     if (int rc = decode(s16.p, lengths.data(), status.data())) return rc;
     rs_batch_spans(b, D, lengths.data(), scale, offsets, spans);
-    if (int rc = tracks_resample_run(device, s, b.n_files, spans.data(), s16.p, b.channels, rate, mono, format, d_out, hip_failed)) return rc;
+    if (int rc = tracks_resample_run(device, s, b.n_files, spans.data(), s16.p, b.channels, rate, mono, format, d_out, hip_failed, mix))
+        return rc;
     for (size_t i = 0; i < n; i++) {
         if (out_offsets) out_offsets[i] = offsets[i];
         if (out_lengths) out_lengths[i] = (lengths[i] + D - 1) / D;
@@ -371,6 +511,34 @@ int opusgpu_files_decode_resampled(opusgpu_ctx *ctx, const opusgpu_file_batch *b
             return files_decode_run(ctx, batch, OPUSGPU_TRACKS_S16, nullptr, d_s16, lengths, status);
         },
         [&](int code, const char *what, hipError_t e) { return fail(ctx, code, what, e); });
+}
+
+int opusgpu_downmix_matrix(int channels, int out_channels, opusgpu_mix_matrix *m) {
+    if (channels < 1 || channels > 8 || out_channels < 1 || out_channels > 2 || !m) return OPUSGPU_BAD_ARG;
+    *m = opusgpu_mix_matrix{};
+    m->out_channels = out_channels, m->in_channels = channels;
+    for (int o = 0; o < out_channels; o++)
+        for (int c = 0; c < channels; c++) m->m[o][c] = out_channels == 1 ? og_downmix_mono[channels - 1][c] : og_downmix_stereo[channels - 1][o][c];
+    return OPUSGPU_OK;
+}
+
+int opusgpu_tracks_resample_mixed_device(opusgpu_ctx *ctx, int n_tracks, const opusgpu_resample_span *spans, const void *d_in, int channels,
+                                         int rate, const opusgpu_mix_matrix *mix, int format, void *d_out, void *hip_stream) {
+    if (!ctx || !mix) return OPUSGPU_BAD_ARG;
+    return tracks_resample_run(ctx->device, hip_stream ? (hipStream_t)hip_stream : ctx->stream, n_tracks, spans, d_in, channels, rate, 0, format,
+                               d_out, [&](int code, const char *what, hipError_t e) { return fail(ctx, code, what, e); }, mix);
+}
+
+int opusgpu_files_decode_mixed(opusgpu_ctx *ctx, const opusgpu_file_batch *batch, int rate, const opusgpu_mix_matrix *mix, int format,
+                               const float *scale, void *d_out, int64_t *out_offsets, int64_t *out_lengths, int64_t *track_lengths_out,
+                               int32_t *status_out) {
+    if (!ctx || !batch || !mix) return OPUSGPU_BAD_ARG;
+    return files_resampled_run(
+        *batch, ctx->device, ctx->stream, rate, 0, format, scale, d_out, out_offsets, out_lengths, track_lengths_out, status_out,
+        [&](void *d_s16, int64_t *lengths, int32_t *status) {
+            return files_decode_run(ctx, batch, OPUSGPU_TRACKS_S16, nullptr, d_s16, lengths, status);
+        },
+        [&](int code, const char *what, hipError_t e) { return fail(ctx, code, what, e); }, mix);
 }
 
 } // extern "C"

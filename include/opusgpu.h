@@ -684,6 +684,43 @@ int opusgpu_files_decode_resampled(opusgpu_ctx *ctx, const opusgpu_file_batch *b
                                    void *d_out, int64_t *out_offsets, int64_t *out_lengths, int64_t *track_lengths_out,
                                    int32_t *status_out);
 
+/* CHANNEL MIX.  A matrix in front of TRACK RATES: surround to stereo or mono, one channel of a pair, a swap, mid / side, any
+ * weighting.  A mix is out_channels (1 - 8) rows of in_channels (1 - 8) int16 coefficients in Q14, M[o][c].
+ *   VALUE.  For a track with int16 samples s_c[n], zero in front of the track and at or behind its FINAL length as in TRACK RATES,
+ *       x_o[n] = sat16((sum_c M[o][c] * s_c[n] + 8192) >> 14),
+ *   >> arithmetic, the sum exact in int32.  Then TRACK RATES applies to x as if it were the S16 track of out_channels channels: the
+ *   FIR and its sat16((sum + 16384) >> 15), the float formats, the LAYOUT with out_channels as its channel count.  Rate 48000 is
+ *   allowed with a mix and is the mix alone.  There is no `mono` next to a matrix.
+ *   REFUSED before any device work (OPUSGPU_BAD_ARG): out_channels or in_channels outside 1 - 8; in_channels other than the tracks'
+ *   channel count; a row with sum_c |M[o][c]| > 65535 (up to there 65535 * 32768 + 8192 < 2^31: the argument the taps use).
+ *   Entries of m[][] outside the matrix are not read.
+ *   The row {8192, 8192} is exactly `mono`'s (l + r + 1) >> 1; 16384 on the diagonal is exactly x = s.
+ *   DEFAULT TABLES.  opusgpu_downmix_matrix fills the matrix that takes `channels` (1 - 8) channels in the Vorbis order of channel
+ *   mapping family 1 to stereo or mono.  The tables are defined here, not taken from a codec.  Speaker order: 1: M; 2: FL FR; 3: FL C FR;
+ *   4: FL FR RL RR; 5: FL C FR RL RR; 6: FL C FR RL RR LFE; 7: FL C FR SL SR RC LFE; 8: FL C FR SL SR RL RR LFE.  Stereo weights
+ *   (left, right) before normalisation: FL (1, 0), FR (0, 1), C and M (1/sqrt 2, 1/sqrt 2), SL and RL (1/sqrt 2, 0), SR and RR
+ *   (0, 1/sqrt 2), RC (1/2, 1/2), LFE (0, 0); the mono row's weights are left + right.  Each row is rint(16384 w / sum(w)), and its
+ *   largest entry (the first of them when tied) is then corrected so that the row sums to exactly 16384: entries are >= 0, so a
+ *   default mix never clamps (tools/gen_downmix_tables.py writes them to csrc/og_downmix_tables.hpp). */
+typedef struct opusgpu_mix_matrix { /* 136 bytes (ABI) */
+    int32_t out_channels, in_channels;
+    int16_t m[8][8]; /* m[o][c], Q14; unused entries 0 */
+} opusgpu_mix_matrix;
+/* The default table for `channels` (1 - 8) and out_channels 1 or 2 into *m, unused entries 0; anything else, or m NULL, is
+ * OPUSGPU_BAD_ARG.  Host only. */
+int opusgpu_downmix_matrix(int channels, int out_channels, opusgpu_mix_matrix *m);
+/* k_tracks_resample_mix alone: opusgpu_tracks_resample_device's contract and refusals with *mix in place of `mono`, plus REFUSED
+ * above and a NULL mix; every rate of TRACK RATES, 48000 included.  d_out holds mix->out_channels channels. */
+int opusgpu_tracks_resample_mixed_device(opusgpu_ctx *ctx, int n_tracks, const opusgpu_resample_span *spans, const void *d_in, int channels,
+                                         int rate, const opusgpu_mix_matrix *mix, int format, void *d_out, void *hip_stream);
+/* opusgpu_files_decode_resampled with *mix in place of `mono`: the same scratch S16 buffer, the same decode, the same grid with
+ * mix->out_channels as out_channels.  OPUSGPU_BAD_ARG before any device work: an unknown rate or format, a matrix that REFUSED
+ * names (or NULL), a scale with OPUSGPU_TRACKS_S16, a scale entry that is not finite.  On a failure the caller's arrays are left as
+ * they were. */
+int opusgpu_files_decode_mixed(opusgpu_ctx *ctx, const opusgpu_file_batch *batch, int rate, const opusgpu_mix_matrix *mix, int format,
+                               const float *scale, void *d_out, int64_t *out_offsets, int64_t *out_lengths, int64_t *track_lengths_out,
+                               int32_t *status_out);
+
 /* ---- WHOLE FILES / MULTISTREAM: N surround Ogg Opus files in, N trimmed interleaved tracks in HBM out -----------------------------
  * The two sections above joined: files whose OpusHead carries channel mapping family 1 (1 - 8 channels, `streams` elementary
  * streams) are planned by the same reader-driven loop as stereo files and decoded by an opusgpu_ms of their layout.  The reader's
@@ -765,6 +802,11 @@ int opusgpu_ms_files_decode_as(opusgpu_ms *ms, const opusgpu_ms_file_batch *batc
 int opusgpu_ms_files_decode_resampled(opusgpu_ms *ms, const opusgpu_ms_file_batch *batch, int rate, int format, const float *scale,
                                       void *d_out, int64_t *out_offsets, int64_t *out_lengths, int64_t *track_lengths_out,
                                       int32_t *status_out);
+/* opusgpu_files_decode_mixed behind opusgpu_ms_files_decode (CHANNEL MIX): the layout's channels through *mix, at any rate of TRACK
+ * RATES -- the surround downmix that opusgpu_ms_files_decode_resampled does not have. */
+int opusgpu_ms_files_decode_mixed(opusgpu_ms *ms, const opusgpu_ms_file_batch *batch, int rate, const opusgpu_mix_matrix *mix, int format,
+                                  const float *scale, void *d_out, int64_t *out_offsets, int64_t *out_lengths, int64_t *track_lengths_out,
+                                  int32_t *status_out);
 
 #ifdef __cplusplus
 }

@@ -10,7 +10,9 @@ kept samples x 4).  Also: the planner's files/s on --threads threads next to opu
 reads the float kernels' rows too (6 bytes moved per sample and channel instead of 4).
 --rate R [--mono]: the whole call at a track rate instead (tools/resample_rate.py), in order and pipelined; --stats then prints
 k_tracks_resample's row as well.
-usage (GPU box): python3 tools/files_rate.py [--n N] [--reps R] [--format F | --rate R [--mono]] | python3 tools/files_rate.py --stats DIR [--n N]"""
+--rate R --mix mono | stereo: the same with the default downmix table as a channel mix (opusgpu_files_decode_mixed) in place of
+--mono; `--mix mono` and `--mono` produce the same tracks, so their times show what the general staging costs.
+usage (GPU box): python3 tools/files_rate.py [--n N] [--reps R] [--format F | --rate R [--mono | --mix M]] | python3 tools/files_rate.py --stats DIR [--n N]"""
 import argparse
 import ctypes as C
 import glob
@@ -35,7 +37,10 @@ ap.add_argument("--format", choices=["f32", "f32_planar"], default=None,
 ap.add_argument("--rate", type=int, choices=[48000, 24000, 16000, 12000, 8000], default=None,
                 help="compare the whole decode call: int16 tracks, int16 + resampling in torch, the resampled tracks (tools/resample_rate.py)")
 ap.add_argument("--mono", action="store_true")
+ap.add_argument("--mix", choices=["mono", "stereo"], default=None, help="with --rate: the default downmix table as a channel mix")
 args = ap.parse_args()
+if args.mix and (args.mono or not args.rate):
+    ap.error("--mix goes with --rate and without --mono")
 n = args.n
 if args.format or args.rate:
     import torch  # before the library: one HIP runtime for both
@@ -85,13 +90,19 @@ if args.rate:
     assert (b.info["status"] == 0).all() and b.n_steps == 10
     ctx = pkg.Context(0)
     ctx.streams_alloc(n, 2)
+    rec = pkg.mix_matrix(args.mix, 2) if args.mix else None
+
+    def resampled(fmt, d, oo, ol, ln, st):
+        if rec is not None:
+            return ctx._chk(ctx.lib.opusgpu_files_decode_mixed(ctx.h, b.h, args.rate, rec.ctypes.data, fmt, None, d, oo, ol, ln, st),
+                            "opusgpu_files_decode_mixed")
+        return ctx._chk(ctx.lib.opusgpu_files_decode_resampled(ctx.h, b.h, args.rate, int(args.mono), fmt, None, d, oo, ol, ln, st),
+                        "opusgpu_files_decode_resampled")
     for name, pipe in (("in_order", 0), ("pipelined", 1)):
         ctx.set_pipeline(pipe)
         print(json.dumps(resample_rate.compare(
-            torch, pkg, lambda d, ln, st: ctx._chk(ctx.lib.opusgpu_files_decode(ctx.h, b.h, d, ln, st), "opusgpu_files_decode"),
-            lambda fmt, d, oo, ol, ln, st: ctx._chk(ctx.lib.opusgpu_files_decode_resampled(ctx.h, b.h, args.rate, int(args.mono), fmt, None, d, oo,
-                                                                                          ol, ln, st), "opusgpu_files_decode_resampled"),
-            b, args.rate, args.mono, args.reps, name)))
+            torch, pkg, lambda d, ln, st: ctx._chk(ctx.lib.opusgpu_files_decode(ctx.h, b.h, d, ln, st), "opusgpu_files_decode"), resampled,
+            b, args.rate, args.mono, args.reps, name, mix=pkg.downmix_matrix(2, 1 if args.mix == "mono" else 2) if args.mix else None)))
     ctx.close()
     raise SystemExit(0)
 

@@ -13,7 +13,8 @@ it reads and writes the kept samples x 6 channels x 2 bytes each, k_ms_tracks_as
 ms_rate.py's count per step).
 --format f32 | f32_planar: the whole call per track format instead (tools/format_rate.py).
 --rate R: the whole call at a track rate instead (tools/resample_rate.py).
-usage (GPU box): python3 tools/ms_files_rate.py [--n N] [--reps R] [--format F | --rate R] | python3 tools/ms_files_rate.py --stats DIR [--n N]"""
+--rate R --mix mono | stereo: the same through the 5.1 default downmix table (opusgpu_ms_files_decode_mixed).
+usage (GPU box): python3 tools/ms_files_rate.py [--n N] [--reps R] [--format F | --rate R [--mix M]] | python3 tools/ms_files_rate.py --stats DIR [--n N]"""
 import argparse
 import ctypes as C
 import glob
@@ -36,7 +37,10 @@ ap.add_argument("--format", choices=["f32", "f32_planar"], default=None,
                 help="compare the whole decode call: int16 tracks, int16 + conversion in torch, the fused float format (tools/format_rate.py)")
 ap.add_argument("--rate", type=int, choices=[24000, 16000, 12000, 8000], default=None,
                 help="compare the whole decode call: int16 tracks, int16 + resampling in torch, the resampled tracks (tools/resample_rate.py)")
+ap.add_argument("--mix", choices=["mono", "stereo"], default=None, help="with --rate: the 5.1 default downmix table as a channel mix")
 args = ap.parse_args()
+if args.mix and not args.rate:
+    ap.error("--mix goes with --rate")
 if args.format or args.rate:
     import torch  # before the library is loaded: one HIP runtime for both
 n = args.n
@@ -140,11 +144,17 @@ if args.rate:
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     import resample_rate
     ms = pkg.MultistreamContext(0, n, *LAYOUT)
+    rec = pkg.mix_matrix(args.mix, CH) if args.mix else None
+
+    def resampled(fmt, d, oo, ol, ln, st):
+        if rec is not None:
+            return ms._chk(ms.lib.opusgpu_ms_files_decode_mixed(ms.h, b.h, args.rate, rec.ctypes.data, fmt, None, d, oo, ol, ln, st),
+                           "opusgpu_ms_files_decode_mixed")
+        return ms._chk(ms.lib.opusgpu_ms_files_decode_resampled(ms.h, b.h, args.rate, fmt, None, d, oo, ol, ln, st),
+                       "opusgpu_ms_files_decode_resampled")
     print(json.dumps(resample_rate.compare(
-        torch, pkg, lambda d, ln, st: ms._chk(ms.lib.opusgpu_ms_files_decode(ms.h, b.h, d, ln, st), "opusgpu_ms_files_decode"),
-        lambda fmt, d, oo, ol, ln, st: ms._chk(ms.lib.opusgpu_ms_files_decode_resampled(ms.h, b.h, args.rate, fmt, None, d, oo, ol, ln, st),
-                                               "opusgpu_ms_files_decode_resampled"),
-        b, args.rate, False, args.reps, "in_order")))
+        torch, pkg, lambda d, ln, st: ms._chk(ms.lib.opusgpu_ms_files_decode(ms.h, b.h, d, ln, st), "opusgpu_ms_files_decode"), resampled,
+        b, args.rate, False, args.reps, "in_order", mix=pkg.downmix_matrix(CH, 1 if args.mix == "mono" else 2) if args.mix else None)))
     ms.close()
     raise SystemExit(0)
 

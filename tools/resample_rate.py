@@ -4,18 +4,21 @@ variants interleaved per repeat (include/opusgpu.h TRACK RATES):
 the downmix when --mono, and a float conv1d with stride D over the packed buffer with the same taps (ONE convolution over all
 tracks: cheaper than the per-track ones a consumer needs to keep tracks apart, so (b) is a lower bound); (c) the new call, float32
 tracks at the rate.  Means, medians, min / max; the condition is mean(c) <= mean(b) with (a)'s spread (max - min) as the margin.
+With --mix (include/opusgpu.h CHANNEL MIX) the consumer's work in (b) is to float, `@ M.T`, the strided conv1d, and (c) is the
+mixed call: decode_resampled then runs opusgpu_files_decode_mixed or opusgpu_ms_files_decode_mixed.
 torch must be imported before the library is loaded: they then share one HIP runtime."""
 import time
 
 import numpy as np
 
 
-def compare(torch, pkg, decode_s16, decode_resampled, batch, rate, mono, reps, note=""):
+def compare(torch, pkg, decode_s16, decode_resampled, batch, rate, mono, reps, note="", mix=None):
     """decode_s16(d_tracks, lengths, status) and decode_resampled(fmt, d_out, out_offsets, out_lengths, lengths, status) run the
-    library's calls for the batch and return their codes' check.  -> a dict for the JSON line."""
+    library's calls for the batch and return their codes' check.  mix: None or the int16 Q14 matrix [out, in] that
+    decode_resampled applies.  -> a dict for the JSON line."""
     n, ch = batch.n_files, batch.channels
     D = pkg.TRACK_RATES[rate]
-    ch_out = 1 if mono else ch
+    ch_out = len(mix) if mix is not None else 1 if mono else ch
     total = max(int(batch.track_samples), 1)
     offs, out_total = pkg.resample_layout(batch.info["track_samples"], rate)
     s16 = torch.empty(total * ch, dtype=torch.int16, device="cuda:0")
@@ -25,12 +28,18 @@ def compare(torch, pkg, decode_s16, decode_resampled, batch, rate, mono, reps, n
     if D > 1:
         h = torch.tensor(pkg.resample_taps(rate).astype(np.float32) / 32768, device="cuda:0").view(1, 1, -1)
 
+    if mix is not None:
+        m_t = torch.tensor(np.asarray(mix, dtype=np.float32).T / 16384, device="cuda:0")  # [in, out]
+
     def a():
         decode_s16(s16.data_ptr(), lengths.ctypes.data, status.ctypes.data)
 
     def b():
         a()
-        x = s16.view(-1, ch).t().to(torch.float32) * (1.0 / 32768)  # [ch, samples]
+        if mix is not None:
+            x = ((s16.view(-1, ch).to(torch.float32) * (1.0 / 32768)) @ m_t).t()  # [out, samples]
+        else:
+            x = s16.view(-1, ch).t().to(torch.float32) * (1.0 / 32768)  # [ch, samples]
         if mono:
             x = x.mean(0, keepdim=True)
         if D > 1:
@@ -62,8 +71,8 @@ def compare(torch, pkg, decode_s16, decode_resampled, batch, rate, mono, reps, n
         want = x[:, o // D:o // D + on].t()
         inner = slice(13, on - 13)  # away from the track's ends, where (b) sees the neighbouring tracks
         worst = float((got[inner] - want[inner]).abs().max()) * 32768
-        assert worst < 2.0, worst
-    out = {"rate": rate, "mono": bool(mono), "files": n, "reps": reps, "note": note, "scratch_s16_bytes": total * ch * 2,
+        assert worst < (3.0 if mix is not None else 2.0), worst  # the mix rounds to int16 once more, in front of the filter
+    out = {"rate": rate, "mono": bool(mono), "mix": None if mix is None else np.asarray(mix).tolist(), "files": n, "reps": reps, "note": note, "scratch_s16_bytes": total * ch * 2,
            "out_bytes": int(res.numel()) * 4, "worst_lsb_vs_float_conv": worst if fits else "not checked: no track on the grid of (b)"}
     for k, label in (("a", "a_s16"), ("b", "b_s16_then_torch"), ("c", "c_resampled")):
         v = np.array(times[k])
