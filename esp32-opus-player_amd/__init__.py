@@ -41,6 +41,8 @@ EXPORTS = [
     "opusgpu_resample_taps", "opusgpu_resample_layout", "opusgpu_tracks_resample_device", "opusgpu_files_decode_resampled",
     "opusgpu_ms_files_decode_resampled",
     "opusgpu_downmix_matrix", "opusgpu_tracks_resample_mixed_device", "opusgpu_files_decode_mixed", "opusgpu_ms_files_decode_mixed",
+    "opusgpu_mel_basis", "opusgpu_mel_filterbank", "opusgpu_mel_layout", "opusgpu_tracks_mel_device", "opusgpu_files_decode_mel",
+    "opusgpu_ms_files_decode_mel",
 ]
 
 
@@ -123,6 +125,13 @@ RESAMPLE_SPAN_DTYPE = np.dtype([("in_offset", "<i8"), ("in_samples", "<i8"), ("o
 TRACK_RATES = {48000: 1, 24000: 2, 16000: 3, 12000: 4, 8000: 6}
 # opusgpu_mix_matrix (include/opusgpu.h, CHANNEL MIX): m[o][c] in Q14
 MIX_MATRIX_DTYPE = np.dtype([("out_channels", "<i4"), ("in_channels", "<i4"), ("m", "<i2", (8, 8))])
+# opusgpu_mel_params / opusgpu_mel_span and the constants of the log-mel features (include/opusgpu.h, TRACK FEATURES)
+MEL_PARAMS_DTYPE = np.dtype([("n_mels", "<i4"), ("layout", "<i4"), ("reserved", "<i4", (6,))])
+MEL_SPAN_DTYPE = np.dtype([("in_offset", "<i8"), ("in_samples", "<i8"), ("out_offset", "<i8"), ("plane", "<i8"), ("scale", "<f4"),
+                           ("reserved", "<i4")])
+MEL_NFFT, MEL_HOP, MEL_SR, MEL_BINS = 400, 160, 16000, 201
+MEL_BANDS_MAJOR, MEL_FRAMES_MAJOR = 0, 1
+MEL_LAYOUTS = {"bands": MEL_BANDS_MAJOR, "frames": MEL_FRAMES_MAJOR}
 OPUSGPU_BAD_ARG, OPUSGPU_UNIMPLEMENTED, OPUSGPU_CELT_BAD_ARG = -1, -5, -18
 RFC_FRAME = 2880
 
@@ -243,6 +252,13 @@ def load_lib():
     lib.opusgpu_tracks_resample_mixed_device.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp]
     lib.opusgpu_files_decode_mixed.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp]
     lib.opusgpu_ms_files_decode_mixed.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp]
+    lib.opusgpu_mel_basis.argtypes = [C.POINTER(vp), C.POINTER(vp)]
+    lib.opusgpu_mel_filterbank.argtypes = [C.c_int, C.POINTER(vp)]
+    lib.opusgpu_mel_layout.argtypes = [C.c_int, vp, vp, vp]
+    lib.opusgpu_mel_layout.restype = C.c_int64
+    lib.opusgpu_tracks_mel_device.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
+    lib.opusgpu_files_decode_mel.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.opusgpu_ms_files_decode_mel.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     _lib = lib
     return lib
 
@@ -654,6 +670,123 @@ def track_mix_args(batch, mix, rate=48000, format="s16", out=None, device=0):
     return TRACK_RATES[rate], ch_out, offsets, total, out, rec
 
 
+def mel_params(n_mels=80, feature_layout="bands"):
+    """An opusgpu_mel_params record (a MEL_PARAMS_DTYPE array of one).  feature_layout: "bands" ([n_mels, frames]) or "frames"
+    ([frames, n_mels]), or the OPUSGPU_MEL_* value.  Raises ValueError for an n_mels other than 80 or 128 and an unknown layout."""
+    if n_mels not in (80, 128):
+        raise ValueError(f"n_mels must be 80 or 128, not {n_mels!r}")
+    lay = MEL_LAYOUTS.get(feature_layout, feature_layout) if isinstance(feature_layout, str) else feature_layout
+    if lay not in (MEL_BANDS_MAJOR, MEL_FRAMES_MAJOR) or isinstance(lay, bool):
+        raise ValueError(f"feature_layout must be one of {sorted(MEL_LAYOUTS)}, not {feature_layout!r}")
+    rec = np.zeros(1, dtype=MEL_PARAMS_DTYPE)
+    rec["n_mels"], rec["layout"] = n_mels, lay
+    return rec
+
+
+def mel_basis():
+    """opusgpu_mel_basis: the windowed DFT basis the kernel multiplies -> (Wc, Ws), float32 [400, 201] each."""
+    wc, ws = C.c_void_p(), C.c_void_p()
+    n = load_lib().opusgpu_mel_basis(C.byref(wc), C.byref(ws))
+    return tuple(np.ctypeslib.as_array((C.c_float * n).from_address(p.value)).reshape(MEL_NFFT, MEL_BINS).copy() for p in (wc, ws))
+
+
+def mel_filterbank(n_mels):
+    """opusgpu_mel_filterbank: the Slaney filterbank of 80 or 128 bands -> float32 [n_mels, 201]."""
+    p = C.c_void_p()
+    n = load_lib().opusgpu_mel_filterbank(int(n_mels), C.byref(p))
+    if n < 0:
+        raise ValueError(f"n_mels must be 80 or 128, not {n_mels!r}")
+    return np.ctypeslib.as_array((C.c_float * n).from_address(p.value)).reshape(int(n_mels), MEL_BINS).copy()
+
+
+def mel_layout(planned_48k_samples, n_mels=80, feature_layout="bands"):
+    """opusgpu_mel_layout: the grid of the feature tracks -> (feat_offsets [int64], planes [int64], total floats)."""
+    rec = mel_params(n_mels, feature_layout)
+    planned = np.ascontiguousarray(planned_48k_samples, dtype=np.int64)
+    offsets = np.zeros(planned.size, dtype=np.int64)
+    total = load_lib().opusgpu_mel_layout(planned.size, planned.ctypes.data, rec.ctypes.data, offsets.ctypes.data)
+    if total < 0:
+        raise ValueError("opusgpu_mel_layout refused a negative length")
+    planes = ((planned + 2) // 3 // MEL_HOP + 63) // 64 * 64
+    return offsets, planes, int(total)
+
+
+def track_feature_args(batch, features=None, n_mels=80, feature_layout="bands", rate=None, mono=False, mix=None, format=None, scale=None,
+                       out=None, device=0, allow_mono=True):
+    """What decode_files makes of its features= for a planned batch, before any device work: None for features=None (today's
+    paths), else (params record, mix record or None, float32 scale array or None, feat_offsets, planes, total floats, out flattened
+    or None).  Raises ValueError for a feature other than "logmel", what mel_params refuses, a rate other than 16000 (or None), a
+    format other than "f32" (or None), a result of more than one channel -- neither mono=True nor a mix, both, a mix of more than
+    one row, mono on more than 2 channels or where there is none (allow_mono False) --, a scale of the wrong length or not finite,
+    and an `out` that does not fit the feature tracks: total floats, otherwise as track_format_args says."""
+    if features is None:
+        return None
+    if features != "logmel":
+        raise ValueError(f"features must be None or 'logmel', not {features!r}")
+    rec = mel_params(n_mels, feature_layout)
+    if rate not in (None, MEL_SR):
+        raise ValueError(f"features are made of the track at {MEL_SR} Hz: rate must be absent or {MEL_SR}, not {rate!r}")
+    if format not in (None, "f32"):
+        raise ValueError(f"features are float32: format must be absent or 'f32', not {format!r}")
+    if mono and not allow_mono:
+        raise ValueError("there is no mono downmix of multistream tracks: use mix='mono'")
+    if mix is not None and mono:
+        raise ValueError("mix and mono=True exclude each other: the row {8192, 8192} is mono")
+    if mix is None and not mono:
+        raise ValueError("features are made of ONE channel: pass mono=True or a mix of one row (mix='mono')")
+    mrec = None
+    if mix is not None:
+        mrec = mix_matrix(mix, batch.channels)
+        if int(mrec["out_channels"][0]) != 1:
+            raise ValueError(f"features are made of ONE channel: the mix has {int(mrec['out_channels'][0])} rows")
+    elif batch.channels > 2:
+        raise ValueError(f"mono needs 1 or 2 channels, not {batch.channels}")
+    _, scale, _ = track_format_args(batch, "f32", scale, None, device)
+    offsets, planes, total = mel_layout(batch.info["track_samples"], n_mels, feature_layout)
+    if out is not None:
+        out = _out_flat(out, max(total, 1), "f32", device)
+    return rec, mrec, scale, offsets, planes, total, out
+
+
+def _decode_planned_mel(chk, name, call, batch, mem, fargs):
+    """_decode_planned for feature tracks: call(scale pointer, d_out, four array pointers) runs the decode call `name`; fargs: what
+    track_feature_args returned.  -> (features, info): float32 arrays [n_mels, F] or [F, n_mels]; info has `feat_offset` more, and
+    its `frames` is F, the track's feature frames, as `track_samples` is its final length (the plan's count of Opus frames is
+    batch.info["frames"])."""
+    rec, _, scale, offsets, planes, total, out = fargs
+    n, n_mels, frames_major = batch.n_files, int(rec["n_mels"][0]), int(rec["layout"][0]) == MEL_FRAMES_MAJOR
+    feat_offsets, frames, lengths = (np.zeros(n, dtype=np.int64) for _ in range(3))
+    status = np.zeros((n, 2), dtype=np.int32)
+
+    def run(d_out):
+        chk(call(None if scale is None else scale.ctypes.data, d_out, feat_offsets.ctypes.data, frames.ctypes.data, lengths.ctypes.data,
+                 status.ctypes.data), name)
+    if out is not None:
+        import torch
+        torch.cuda.current_stream(out.device).synchronize()  # as in _decode_planned
+        run(out.data_ptr())
+        packed = out
+    else:
+        packed = np.zeros(max(total, 1), dtype=np.float32)
+        d_out = mem.dev_alloc(packed.nbytes)
+        try:
+            run(d_out)
+            mem.d2h(packed, d_out)
+        finally:
+            mem.dev_free(d_out)
+    assert (feat_offsets == offsets).all()
+    info = np.zeros(n, dtype=np.dtype(FILE_INFO_DTYPE.descr + [("final_status", "<i4"), ("bad_packet", "<i4"), ("feat_offset", "<i8")]))
+    for field in FILE_INFO_DTYPE.names:
+        info[field] = batch.info[field]
+    info["track_samples"], info["final_status"], info["bad_packet"] = lengths, status[:, 0], status[:, 1]
+    info["frames"], info["feat_offset"] = frames, feat_offsets
+    if frames_major:
+        feats = [packed[o:o + F * n_mels].reshape(F, n_mels) for o, F in zip(feat_offsets, frames)]
+    else:
+        feats = [packed[o:o + n_mels * p].reshape(n_mels, p)[:, :F] for o, p, F in zip(feat_offsets, planes, frames)]
+    return feats, info
+
+
 def _decode_planned(lib, chk, name, handle, batch, mem, args):
     """The shared body of the two decode_files: runs the decode call `name` of `lib` (`name`_as for a float format) for the decoder
     `handle` over `batch` into `out` (a torch tensor on the device: nothing comes to the host) or into a track buffer from `mem` (a
@@ -920,8 +1053,17 @@ class Context:
         self._chk(self.lib.opusgpu_tracks_resample_mixed_device(self.h, spans.size, spans.ctypes.data, d_in, channels, int(rate),
                                                                 rec.ctypes.data, format, d_out, stream), "opusgpu_tracks_resample_mixed_device")
 
-    def decode_files(self, files, rfc=False, flags=PAGES_GROUP_BY_MODE, threads=1, batch=None, format="s16", scale=None, out=None,
-                     rate=48000, mono=False, mix=None):
+    def tracks_mel_device(self, spans, d_in, n_mels, feature_layout, d_out, stream=None):
+        """k_tracks_mel alone (include/opusgpu.h TRACK FEATURES): spans a HOST array of MEL_SPAN_DTYPE, d_in packed int16 mono tracks
+        at 16 kHz, d_out the float32 feature tracks; feature_layout "bands" or "frames" (or a MEL_PARAMS_DTYPE record in place of
+        n_mels).  Waits for the kernel."""
+        spans = np.ascontiguousarray(spans, dtype=MEL_SPAN_DTYPE)
+        rec = np.ascontiguousarray(n_mels) if getattr(n_mels, "dtype", None) == MEL_PARAMS_DTYPE else mel_params(n_mels, feature_layout)
+        self._chk(self.lib.opusgpu_tracks_mel_device(self.h, spans.size, spans.ctypes.data, d_in, rec.ctypes.data, d_out, stream),
+                  "opusgpu_tracks_mel_device")
+
+    def decode_files(self, files, rfc=False, flags=PAGES_GROUP_BY_MODE, threads=1, batch=None, format=None, scale=None, out=None,
+                     rate=None, mono=False, mix=None, features=None, n_mels=80, feature_layout="bands"):
         """Whole Ogg Opus files -> (list of int16 arrays [samples, channels], one trimmed track per file, info).  The context's
         streams 0 .. len(files) - 1 are (re)allocated when there are too few and get fresh state; its mode is set to `rfc`.
         info: FILE_INFO_DTYPE records with two more fields: `final_status` (the first failed frame's code, else the plan's status)
@@ -938,7 +1080,15 @@ class Context:
         info has `out_samples` and `out_offset` more; `track_samples` stays the final length at 48 kHz.
         mix: None, or a channel mix in front of the rate (include/opusgpu.h CHANNEL MIX; mix_matrix says what it may be: "mono",
         "stereo", a Q14 integer matrix [out, in] or a float one), at any rate, 48000 included; not together with mono=True.  The
-        tracks are then [ceil(len / D), out] (planar: transposed), `out` is sized for them (track_mix_args)."""
+        tracks are then [ceil(len / D), out] (planar: transposed), `out` is sized for them (track_mix_args).
+        format and rate left out are "s16" and 48000.
+        features: None, or "logmel" for log-mel features of the mono track at 16 kHz in place of the samples (include/opusgpu.h
+        TRACK FEATURES: 400-sample Hann window, hop 160, n_mels = 80 or 128 Slaney bands, log10(max(mel, 1e-10))), made on the GPU
+        in the same call.  It needs ONE channel -- mono=True or a mix of one row --, takes scale=, and refuses any rate but 16000 and
+        any format but "f32" (track_feature_args).  The result is a list of float32 arrays [n_mels, F] (feature_layout "bands") or
+        [F, n_mels] ("frames"), F = ceil(len / 3) // 160, or views of `out` (mel_layout's total floats); info has `feat_offset` more
+        and its `frames` is F (the plan's count of Opus frames stays in batch.info["frames"]).  Whisper's clip-wide max - 8 clamp
+        and (x + 4) / 4 are not applied: they are two torch operations on the result."""
         if mix is not None and mono:
             raise ValueError("mix and mono=True exclude each other: the row {8192, 8192} is mono")
         own = batch is None
@@ -946,6 +1096,17 @@ class Context:
         if own:
             batch = FileBatch(files, channels=channels, rfc=rfc, flags=flags, threads=threads)
         try:
+            fargs = track_feature_args(batch, features, n_mels, feature_layout, rate, mono, mix, format, scale, out, self.device)
+            rate, format = 48000 if rate is None else rate, "s16" if format is None else format
+            if fargs is not None:
+                if self.n_streams < batch.n_files or self.channels != batch.channels:
+                    self.streams_alloc(max(batch.n_files, 1), batch.channels)
+                self.set_mode(batch.rfc)
+
+                def call(scale_p, d_out, *arrays):
+                    return self.lib.opusgpu_files_decode_mel(self.h, batch.h, 1 if mono else 0, None if fargs[1] is None else fargs[1].ctypes.data,
+                                                             fargs[0].ctypes.data, scale_p, d_out, *arrays)
+                return _decode_planned_mel(self._chk, "opusgpu_files_decode_mel", call, batch, self, fargs)
             margs = None if mix is None else track_mix_args(batch, mix, rate, format, out, self.device)
             rargs = track_rate_args(batch, rate, mono, format, out, self.device) if mix is None else margs[:5]
             args = track_format_args(batch, format, scale, out if rargs is None else None, self.device)
@@ -1127,18 +1288,29 @@ class MultistreamContext:
                                                                 d_res_mono, format, d_place, d_tracks, d_track_state, stream),
                   "opusgpu_ms_tracks_assemble_device_as")
 
-    def decode_files(self, files, rfc=False, threads=1, batch=None, format="s16", scale=None, out=None, rate=48000, mix=None):
+    def decode_files(self, files, rfc=False, threads=1, batch=None, format=None, scale=None, out=None, rate=None, mix=None, features=None,
+                     n_mels=80, feature_layout="bands"):
         """Whole Ogg Opus files of this object's layout -> (list of int16 arrays [samples, channels], one trimmed track per file,
         info), as Context.decode_files returns them: FILE_INFO_DTYPE records plus `final_status` and `bad_packet`, `track_samples`
         the FINAL length.  Decoders 0 .. len(files) - 1 get fresh state; the object's mode is set to the batch's.  batch: an
         MsFileBatch made beforehand from the same files (of this layout; `rfc` is then the batch's).  format, scale, out, rate: as
         for Context.decode_files, all channels at `rate`.  mix: as for Context.decode_files -- "mono" and "stereo" are the default
-        downmix tables of the layout's channel count; there is no `mono` argument here."""
+        downmix tables of the layout's channel count; there is no `mono` argument here.
+        features, n_mels, feature_layout: as for Context.decode_files, with mix="mono" or a matrix of one row."""
         own = batch is None
         if own:
             batch = MsFileBatch(files, self.layout, rfc=rfc, threads=threads)
         mem = None
         try:
+            fargs = track_feature_args(batch, features, n_mels, feature_layout, rate, False, mix, format, scale, out, self.device, allow_mono=False)
+            rate, format = 48000 if rate is None else rate, "s16" if format is None else format
+            if fargs is not None:
+                mem = Context(self.device)
+                self.set_mode(batch.rfc)
+
+                def call(scale_p, d_out, *arrays):
+                    return self.lib.opusgpu_ms_files_decode_mel(self.h, batch.h, fargs[1].ctypes.data, fargs[0].ctypes.data, scale_p, d_out, *arrays)
+                return _decode_planned_mel(self._chk, "opusgpu_ms_files_decode_mel", call, batch, mem, fargs)
             margs = None if mix is None else track_mix_args(batch, mix, rate, format, out, self.device)
             rargs = track_rate_args(batch, rate, False, format, out, self.device, allow_mono=False) if mix is None else margs[:5]
             args = track_format_args(batch, format, scale, out if rargs is None else None, self.device)

@@ -721,6 +721,89 @@ int opusgpu_files_decode_mixed(opusgpu_ctx *ctx, const opusgpu_file_batch *batch
                                const float *scale, void *d_out, int64_t *out_offsets, int64_t *out_lengths, int64_t *track_lengths_out,
                                int32_t *status_out);
 
+/* TRACK FEATURES.  Log-mel features of the mono track at 16 kHz, the front end of Whisper-style speech models, in the same call
+ * that decodes the files.  Like the float formats, the rates and the mix, the features are a function of an array that is pinned
+ * bit for bit; they are themselves float sums, pinned to a tolerance and to two exact properties (below).
+ *   INPUT.  The int16 mono track at 16 kHz exactly as TRACK RATES / CHANNEL MIX define it -- `mono` on a 1- or 2-channel context, or
+ *   a mix with out_channels == 1 on either kind of context --: y[m], m in [0, n), n = ceil(final_48k / 3).
+ *   CONSTANTS of this version (not fields): n_fft 400, hop 160, sr 16000, fmin 0, fmax 8000, 201 power bins.
+ *   FRAMES.  F = n / 160 (floor): torch.stft(center=True) without its last frame, as Whisper does.
+ *   WINDOW INDEX.  Frame f, tap i in [0, 400) reads index q = 160 f - 200 + i, reflected ONCE: q < 0 becomes -q, q >= n becomes
+ *   2 (n - 1) - q; if q is still outside [0, n) the sample is 0 (that happens only for n < 201).
+ *   SAMPLE.  x_i = (float)y[q] * scale[track], one IEEE multiply; the default scale is 1 / 32768 (the scale rule of TRACK FORMATS).
+ *   POWER.  P[k] = (sum_i Wc[i][k] x_i)^2 + (sum_i Ws[i][k] x_i)^2, k in [0, 201).
+ *   MEL.  mel[j] = sum_k B[j][k] P[k], j in [0, n_mels).
+ *   OUTPUT.  log10f(max(mel[j], 1e-10f)), float32.  Whisper's clip-wide max - 8 clamp and (x + 4) / 4 are two element-wise
+ *   operations on the result and are left to the caller.
+ *   TABLES.  float32, each entry computed in double and rounded once, at first use (once per process):
+ *       w[i] = 0.5 - 0.5 cos(2 pi i / 400)                       the periodic Hann window
+ *       Wc[i][k] = w[i] cos(a), Ws[i][k] = w[i] sin(a),           a = 2 pi ((i k) mod 400) / 400: 2 pi i k / 400 reduced in integers
+ *       B: Slaney's scale, Slaney's normalisation, the formula librosa.filters.mel(sr=16000, n_fft=400, n_mels=n_mels) implements:
+ *         hz(m) = 200 / 3 * m for m < 15, else 1000 exp((ln 6.4 / 27) (m - 15));   mmax = 15 + ln(8) / (ln 6.4 / 27)   (8000 Hz)
+ *         p[j] = hz(j * (mmax / (n_mels + 1))) for j in [0, n_mels], p[n_mels + 1] = hz(mmax)      n_mels + 2 points over [0, 8000] Hz
+ *         B[j][k] = max(0, min((40 k - p[j]) / (p[j + 1] - p[j]), (p[j + 2] - 40 k) / (p[j + 2] - p[j + 1]))) * (2 / (p[j + 2] - p[j]))
+ *     opusgpu_mel_basis and opusgpu_mel_filterbank hand them out: a test or a user computes against exactly the numbers the kernel
+ *     multiplies.
+ *   SUMMATION ORDER is not part of the contract (the kernel folds the window's symmetry: x_i +- x_{400 - i} against half the basis).
+ *   What is: the same call on the same input returns the same bits -- no float atomics, no sum that depends on the launch order --,
+ *   and an all-zero track gives one bit-identical value in every cell.  tests/test_gpu_tracks_mel.py holds the kernel to a
+ *   float64 reference within 8 x the error of a float32 restatement.
+ *   LAYOUT.  Feature tracks lie on a grid of their own, in floats: plane[t] = roundup64(ceil(planned[t] / 3) / 160), planned the
+ *   PLANNED track_samples at 48 kHz; feat_offset[t] is the running sum of n_mels * plane[u] over the earlier tracks u, a multiple
+ *   of 64 floats, in BOTH layouts.  OPUSGPU_MEL_BANDS_MAJOR: band j of frame f is element feat_offset[t] + j * plane[t] + f ([n_mels]
+ *   [frames], what Whisper takes).  OPUSGPU_MEL_FRAMES_MAJOR: element feat_offset[t] + f * n_mels + j.  Padding is never written.  A
+ *   track cut short by a failed frame keeps its planned plane and reports its shorter F. */
+#define OPUSGPU_MEL_NFFT 400
+#define OPUSGPU_MEL_HOP 160
+#define OPUSGPU_MEL_SR 16000
+#define OPUSGPU_MEL_FMIN 0
+#define OPUSGPU_MEL_FMAX 8000
+#define OPUSGPU_MEL_BINS 201
+#define OPUSGPU_MEL_BANDS_MAJOR 0  /* [n_mels][frames], the band's row plane[t] floats long */
+#define OPUSGPU_MEL_FRAMES_MAJOR 1 /* [frames][n_mels] */
+typedef struct opusgpu_mel_params { /* 32 bytes (ABI) */
+    int32_t n_mels;      /* 80 or 128 */
+    int32_t layout;      /* OPUSGPU_MEL_BANDS_MAJOR or OPUSGPU_MEL_FRAMES_MAJOR */
+    int32_t reserved[6]; /* 0 */
+} opusgpu_mel_params;
+/* The DFT basis: sets *wc and *ws (either may be NULL) to Wc and Ws, [400][201] floats each, and returns 400 * 201.  Host only. */
+int opusgpu_mel_basis(const float **wc, const float **ws);
+/* The filterbank of n_mels (80 or 128) bands: sets *b (may be NULL) to B, [n_mels][201] floats, and returns n_mels * 201;
+ * OPUSGPU_BAD_ARG for any other n_mels.  Host only. */
+int opusgpu_mel_filterbank(int n_mels, const float **b);
+/* The grid above for n tracks of planned_48k_samples[i] samples at 48 kHz: writes feat_offsets[i] (may be NULL) and returns the total
+ * in floats.  Serves both kinds of batch.  OPUSGPU_BAD_ARG: params NULL, n_mels not 80 or 128, an unknown layout, a reserved word
+ * that is not 0, a negative length.  Host only. */
+int64_t opusgpu_mel_layout(int n, const int64_t *planned_48k_samples, const opusgpu_mel_params *params, int64_t *feat_offsets);
+typedef struct opusgpu_mel_span { /* 40 bytes, one per track (ABI) */
+    int64_t in_offset;  /* where the int16 mono track begins in d_in16k_mono, in samples; a multiple of 8 */
+    int64_t in_samples; /* n, its length at 16 kHz */
+    int64_t out_offset; /* where the feature track begins in d_out, in floats; a multiple of 64 */
+    int64_t plane;      /* a multiple of 64 and >= n / 160; bands-major: the distance between two bands' rows; frames-major: not read */
+    float scale;
+    int32_t reserved;   /* 0 */
+} opusgpu_mel_span;
+/* k_tracks_mel alone: d_in16k_mono holds packed int16 mono tracks at 16 kHz, 16-byte aligned; `spans` is a HOST array of n_tracks
+ * records.  Writes the features of TRACK FEATURES into d_out (floats, 128-byte aligned).  The kernel reads d_in16k_mono in aligned
+ * 16-byte pieces: the buffer must reach to the end of the piece that holds a track's last sample.  The caller guarantees that the
+ * spans lie inside both buffers and do not overlap in d_out.  A track with n < 160 has no frame and writes nothing.  Uploads the
+ * records, its tile table and the tables, launches on the context's stream (or `hip_stream`), waits, and frees all of them on every
+ * way out.  OPUSGPU_BAD_ARG before any device work: what opusgpu_mel_layout refuses of params, a span that breaks the rules above,
+ * a scale that is not finite. */
+int opusgpu_tracks_mel_device(opusgpu_ctx *ctx, int n_tracks, const opusgpu_mel_span *spans, const void *d_in16k_mono,
+                              const opusgpu_mel_params *params, void *d_out, void *hip_stream);
+/* opusgpu_files_decode into features: runs opusgpu_files_decode_resampled (mix NULL, `mono` 1) or opusgpu_files_decode_mixed (`mono`
+ * 0, *mix with out_channels == 1) at rate 16000 into a scratch buffer of int16 mono tracks, then k_tracks_mel from there into
+ * d_out; both scratch buffers are freed on every way out.  d_out: opusgpu_mel_layout's total in floats, 128-byte aligned.  scale:
+ * host array of n_files floats, or NULL for 1 / 32768 each.  feat_offsets[i] and frames_out[i] (either may be NULL): where feature
+ * track i begins and its F = ceil(final / 3) / 160; track_lengths_out and status_out as for opusgpu_files_decode (the lengths at 48
+ * kHz).  OPUSGPU_BAD_ARG before any device work: what opusgpu_mel_layout refuses of params, neither `mono` nor a mix or both, a mix
+ * with out_channels != 1 or one that CHANNEL MIX refuses, `mono` on more than 2 channels, a scale entry that is not finite, a
+ * d_out that is not 128-byte aligned.  On a failure the caller's arrays are left as they were. */
+int opusgpu_files_decode_mel(opusgpu_ctx *ctx, const opusgpu_file_batch *batch, int mono, const opusgpu_mix_matrix *mix,
+                             const opusgpu_mel_params *params, const float *scale, void *d_out, int64_t *feat_offsets, int64_t *frames_out,
+                             int64_t *track_lengths_out, int32_t *status_out);
+
 /* ---- WHOLE FILES / MULTISTREAM: N surround Ogg Opus files in, N trimmed interleaved tracks in HBM out -----------------------------
  * The two sections above joined: files whose OpusHead carries channel mapping family 1 (1 - 8 channels, `streams` elementary
  * streams) are planned by the same reader-driven loop as stereo files and decoded by an opusgpu_ms of their layout.  The reader's
@@ -807,6 +890,11 @@ int opusgpu_ms_files_decode_resampled(opusgpu_ms *ms, const opusgpu_ms_file_batc
 int opusgpu_ms_files_decode_mixed(opusgpu_ms *ms, const opusgpu_ms_file_batch *batch, int rate, const opusgpu_mix_matrix *mix, int format,
                                   const float *scale, void *d_out, int64_t *out_offsets, int64_t *out_lengths, int64_t *track_lengths_out,
                                   int32_t *status_out);
+/* opusgpu_files_decode_mel behind opusgpu_ms_files_decode (TRACK FEATURES): the layout's channels through *mix, which must have
+ * out_channels == 1; there is no `mono` here.  Refusals as there, plus a NULL mix. */
+int opusgpu_ms_files_decode_mel(opusgpu_ms *ms, const opusgpu_ms_file_batch *batch, const opusgpu_mix_matrix *mix,
+                                const opusgpu_mel_params *params, const float *scale, void *d_out, int64_t *feat_offsets, int64_t *frames_out,
+                                int64_t *track_lengths_out, int32_t *status_out);
 
 #ifdef __cplusplus
 }

@@ -12,7 +12,9 @@ reads the float kernels' rows too (6 bytes moved per sample and channel instead 
 k_tracks_resample's row as well.
 --rate R --mix mono | stereo: the same with the default downmix table as a channel mix (opusgpu_files_decode_mixed) in place of
 --mono; `--mix mono` and `--mono` produce the same tracks, so their times show what the general staging costs.
-usage (GPU box): python3 tools/files_rate.py [--n N] [--reps R] [--format F | --rate R [--mono | --mix M]] | python3 tools/files_rate.py --stats DIR [--n N]"""
+--mel [--n-mels N]: the fused log-mel call (opusgpu_files_decode_mel, mono) next to float32 16 kHz mono tracks followed by
+torch.stft, the filterbank matmul and log10, and k_tracks_mel's share of the call (tools/mel_rate.py).
+usage (GPU box): python3 tools/files_rate.py [--n N] [--reps R] [--format F | --rate R [--mono | --mix M] | --mel [--n-mels N]] | python3 tools/files_rate.py --stats DIR [--n N]"""
 import argparse
 import ctypes as C
 import glob
@@ -38,11 +40,15 @@ ap.add_argument("--rate", type=int, choices=[48000, 24000, 16000, 12000, 8000], 
                 help="compare the whole decode call: int16 tracks, int16 + resampling in torch, the resampled tracks (tools/resample_rate.py)")
 ap.add_argument("--mono", action="store_true")
 ap.add_argument("--mix", choices=["mono", "stereo"], default=None, help="with --rate: the default downmix table as a channel mix")
+ap.add_argument("--mel", action="store_true", help="compare the fused log-mel call with 16 kHz mono float tracks + torch.stft (tools/mel_rate.py)")
+ap.add_argument("--n-mels", type=int, choices=[80, 128], default=80)
 args = ap.parse_args()
 if args.mix and (args.mono or not args.rate):
     ap.error("--mix goes with --rate and without --mono")
+if args.mel and (args.rate or args.format):
+    ap.error("--mel goes without --rate and --format")
 n = args.n
-if args.format or args.rate:
+if args.format or args.rate or args.mel:
     import torch  # before the library: one HIP runtime for both
 
 spec = importlib.util.spec_from_file_location("esp32_opus_player_amd", os.path.join(here, "..", "esp32-opus-player_amd", "__init__.py"))
@@ -103,6 +109,24 @@ if args.rate:
         print(json.dumps(resample_rate.compare(
             torch, pkg, lambda d, ln, st: ctx._chk(ctx.lib.opusgpu_files_decode(ctx.h, b.h, d, ln, st), "opusgpu_files_decode"), resampled,
             b, args.rate, args.mono, args.reps, name, mix=pkg.downmix_matrix(2, 1 if args.mix == "mono" else 2) if args.mix else None)))
+    ctx.close()
+    raise SystemExit(0)
+
+if args.mel:
+    import mel_rate
+    b = pkg.FileBatch([r.tobytes() for r in files], channels=2, flags=pkg.PAGES_GROUP_BY_MODE, threads=args.threads)
+    assert (b.info["status"] == 0).all() and b.n_steps == 10
+    ctx = pkg.Context(0)
+    ctx.streams_alloc(n, 2)
+    for name, pipe in (("in_order", 0), ("pipelined", 1)):
+        ctx.set_pipeline(pipe)
+        print(json.dumps(mel_rate.compare(
+            torch, pkg,
+            lambda fmt, d, oo, ol, ln, st: ctx._chk(ctx.lib.opusgpu_files_decode_resampled(ctx.h, b.h, 16000, 1, fmt, None, d, oo, ol, ln, st),
+                                                    "opusgpu_files_decode_resampled"),
+            lambda p, d, fo, fr, ln, st: ctx._chk(ctx.lib.opusgpu_files_decode_mel(ctx.h, b.h, 1, None, p, None, d, fo, fr, ln, st),
+                                                  "opusgpu_files_decode_mel"),
+            lambda spans, d_in, rec, d_out: ctx.tracks_mel_device(spans, d_in, rec, None, d_out), b, args.n_mels, args.reps, name)))
     ctx.close()
     raise SystemExit(0)
 

@@ -1,0 +1,89 @@
+"""What tools/files_rate.py and tools/ms_files_rate.py run for --mel: the whole decode call of a planned batch into torch tensors,
+variants interleaved per repeat (include/opusgpu.h TRACK FEATURES):
+(a) float32 mono tracks at 16 kHz, the call as it was (decode_files(rate=16000, mono=True, format="f32", out=...)); (b) (a)
+followed by the front end a consumer runs on them in torch -- the ragged tracks gathered into a zero-padded [files, longest]
+batch (the gather index is made once, outside the timing), torch.stft(400, 160, periodic Hann, center=True) without its last
+frame, |.|^2, the filterbank matmul, log10(clamp(1e-10)); (c) the fused call, log-mel features bands-major.  Then (m):
+k_tracks_mel alone (opusgpu_tracks_mel_device: its uploads, the launch and the wait) over the int16 tracks of the same batch, and its
+share of (c).  Means, medians, min / max; no ratio is asked of (c) against (b): both are printed.
+One track of (c) is held against (b) away from the track's end, where (b) pads with zeros in place of reflecting.
+torch must be imported before the library is loaded: they then share one HIP runtime."""
+import time
+
+import numpy as np
+
+
+def compare(torch, pkg, decode_16k, decode_mel, mel_alone, batch, n_mels, reps, note=""):
+    """decode_16k(fmt, d_out, out_offsets, out_lengths, lengths, status) runs the library's mono 16 kHz call for the batch,
+    decode_mel(params, d_out, feat_offsets, frames, lengths, status) the fused one, mel_alone(spans, d_in, params, d_out) the
+    kernel's; each checks its code.  -> a dict for the JSON line."""
+    n = batch.n_files
+    planned = batch.info["track_samples"]
+    offs, total16 = pkg.resample_layout(planned, 16000)
+    feat_offs, planes, total_feat = pkg.mel_layout(planned, n_mels, "bands")
+    rec = pkg.mel_params(n_mels, "bands")
+    f32 = torch.empty(max(total16, 1), dtype=torch.float32, device="cuda:0")
+    s16 = torch.empty(max(total16, 1) + 64, dtype=torch.int16, device="cuda:0")
+    feat = torch.empty(max(total_feat, 1), dtype=torch.float32, device="cuda:0")
+    lengths, out_offsets, out_lengths, fo, frames = (np.zeros(n, dtype=np.int64) for _ in range(5))
+    status = np.zeros((n, 2), dtype=np.int32)
+    len16 = -(-planned // 3)
+    longest = int(len16.max(initial=1))
+    idx = offs[:, None] + np.arange(longest)[None, :]
+    valid = np.arange(longest)[None, :] < len16[:, None]
+    gather = torch.tensor(np.where(valid, idx, 0), device="cuda:0")
+    mask = torch.tensor(valid, device="cuda:0")
+    window = torch.hann_window(400, periodic=True, device="cuda:0")
+    bank_t = torch.tensor(pkg.mel_filterbank(n_mels).T.copy(), device="cuda:0")  # [201, n_mels]
+
+    def a():
+        decode_16k(pkg.TRACKS_F32, f32.data_ptr(), out_offsets.ctypes.data, out_lengths.ctypes.data, lengths.ctypes.data, status.ctypes.data)
+
+    def b():
+        a()
+        x = torch.where(mask, f32[gather], torch.zeros((), device="cuda:0"))
+        spec = torch.stft(x, 400, 160, window=window, center=True, return_complex=True)[..., :-1]  # [files, 201, frames]
+        out = torch.log10(torch.clamp((spec.abs() ** 2).transpose(1, 2) @ bank_t, min=1e-10))     # [files, frames, n_mels]
+        torch.cuda.synchronize()
+        return out
+
+    def c():
+        decode_mel(rec.ctypes.data, feat.data_ptr(), fo.ctypes.data, frames.ctypes.data, lengths.ctypes.data, status.ctypes.data)
+
+    decode_16k(pkg.TRACKS_S16, s16.data_ptr(), out_offsets.ctypes.data, out_lengths.ctypes.data, lengths.ctypes.data, status.ctypes.data)
+    spans = np.zeros(n, dtype=pkg.MEL_SPAN_DTYPE)
+    spans["in_offset"], spans["in_samples"], spans["out_offset"], spans["plane"], spans["scale"] = offs, out_lengths, feat_offs, planes, 2.0 ** -15
+
+    def m():
+        mel_alone(spans, s16.data_ptr(), rec, feat.data_ptr())
+
+    times = {"a": [], "b": [], "c": [], "m": []}
+    for fn in (a, b, c, m):
+        fn()
+    for _ in range(reps):
+        for name, fn in (("a", a), ("b", b), ("c", c), ("m", m)):
+            t0 = time.perf_counter()
+            fn()
+            times[name].append((time.perf_counter() - t0) * 1e3)
+    assert (status[:, 0] == 0).all() and (lengths == planned).all() and (fo == feat_offs).all() and (frames == len16 // 160).all()
+    # one track of (c) against (b): the same features up to float rounding, but for the last two frames, where (b) sees padding
+    c()
+    want = b()
+    worst = None
+    fits = [j for j in range(n // 2, n) if frames[j] > 4]
+    if fits:
+        i = fits[0]
+        F, o, p = int(frames[i]), int(feat_offs[i]), int(planes[i])
+        got = feat[o:o + n_mels * p].view(n_mels, p)[:, :F - 2].t()
+        worst = float((got - want[i, :F - 2]).abs().max())
+        assert worst < 1e-2, worst
+    out = {"mel": n_mels, "files": n, "frames": int(frames.sum()), "reps": reps, "note": note, "scratch_s16_16k_bytes": int(total16) * 2,
+           "out_bytes": int(total_feat) * 4, "padded_batch_floats_of_b": n * longest,
+           "worst_abs_log10_vs_torch": worst if fits else "not checked: no track of more than 4 frames"}
+    for k, label in (("a", "a_f32_16k_mono"), ("b", "b_f32_then_torch_stft_mel"), ("c", "c_fused_logmel"), ("m", "m_k_tracks_mel_call")):
+        v = np.array(times[k])
+        out[label] = {"mean_ms": round(float(v.mean()), 3), "median_ms": round(float(np.median(v)), 3),
+                      "min_max_ms": [round(float(v.min()), 3), round(float(v.max()), 3)]}
+    out["mel_share_of_c"] = round(float(np.mean(times["m"]) / np.mean(times["c"])), 3)
+    out["c_le_b"] = bool(np.mean(times["c"]) <= np.mean(times["b"]))
+    return out

@@ -14,7 +14,9 @@ ms_rate.py's count per step).
 --format f32 | f32_planar: the whole call per track format instead (tools/format_rate.py).
 --rate R: the whole call at a track rate instead (tools/resample_rate.py).
 --rate R --mix mono | stereo: the same through the 5.1 default downmix table (opusgpu_ms_files_decode_mixed).
-usage (GPU box): python3 tools/ms_files_rate.py [--n N] [--reps R] [--format F | --rate R [--mix M]] | python3 tools/ms_files_rate.py --stats DIR [--n N]"""
+--mel [--n-mels N]: the fused log-mel call (opusgpu_ms_files_decode_mel through the default mono downmix) next to float32 16 kHz mono
+tracks followed by torch.stft, the filterbank matmul and log10, and k_tracks_mel's share of the call (tools/mel_rate.py).
+usage (GPU box): python3 tools/ms_files_rate.py [--n N] [--reps R] [--format F | --rate R [--mix M] | --mel [--n-mels N]] | python3 tools/ms_files_rate.py --stats DIR [--n N]"""
 import argparse
 import ctypes as C
 import glob
@@ -38,10 +40,14 @@ ap.add_argument("--format", choices=["f32", "f32_planar"], default=None,
 ap.add_argument("--rate", type=int, choices=[24000, 16000, 12000, 8000], default=None,
                 help="compare the whole decode call: int16 tracks, int16 + resampling in torch, the resampled tracks (tools/resample_rate.py)")
 ap.add_argument("--mix", choices=["mono", "stereo"], default=None, help="with --rate: the 5.1 default downmix table as a channel mix")
+ap.add_argument("--mel", action="store_true", help="compare the fused log-mel call with 16 kHz mono float tracks + torch.stft (tools/mel_rate.py)")
+ap.add_argument("--n-mels", type=int, choices=[80, 128], default=80)
 args = ap.parse_args()
 if args.mix and not args.rate:
     ap.error("--mix goes with --rate")
-if args.format or args.rate:
+if args.mel and (args.rate or args.format):
+    ap.error("--mel goes without --rate and --format")
+if args.format or args.rate or args.mel:
     import torch  # before the library is loaded: one HIP runtime for both
 n = args.n
 
@@ -155,6 +161,23 @@ if args.rate:
     print(json.dumps(resample_rate.compare(
         torch, pkg, lambda d, ln, st: ms._chk(ms.lib.opusgpu_ms_files_decode(ms.h, b.h, d, ln, st), "opusgpu_ms_files_decode"), resampled,
         b, args.rate, False, args.reps, "in_order", mix=pkg.downmix_matrix(CH, 1 if args.mix == "mono" else 2) if args.mix else None)))
+    ms.close()
+    raise SystemExit(0)
+
+if args.mel:
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import mel_rate
+    ms = pkg.MultistreamContext(0, n, *LAYOUT)
+    mem = pkg.Context(0)
+    rec = pkg.mix_matrix("mono", CH)
+    print(json.dumps(mel_rate.compare(
+        torch, pkg,
+        lambda fmt, d, oo, ol, ln, st: ms._chk(ms.lib.opusgpu_ms_files_decode_mixed(ms.h, b.h, 16000, rec.ctypes.data, fmt, None, d, oo, ol, ln, st),
+                                               "opusgpu_ms_files_decode_mixed"),
+        lambda p, d, fo, fr, ln, st: ms._chk(ms.lib.opusgpu_ms_files_decode_mel(ms.h, b.h, rec.ctypes.data, p, None, d, fo, fr, ln, st),
+                                             "opusgpu_ms_files_decode_mel"),
+        lambda spans, d_in, mp, d_out: mem.tracks_mel_device(spans, d_in, mp, None, d_out), b, args.n_mels, args.reps, "in_order")))
+    mem.close()
     ms.close()
     raise SystemExit(0)
 
