@@ -1013,6 +1013,18 @@ static void denormalise(const i16 *X, i32 *freq, const i16 *bandLogE, int start,
     memset(&freq[bound], 0, (N - bound) * sizeof(*freq));
 }
 
+/* unit entry for tests/test_rare_paths.py: coefficient x of `band` with log energy bandLogE through denormalise (20 ms layout) */
+i32 oc_test_denorm_coef(int band, int bandLogE, int x) {
+    i16 X[960], E[NB];
+    i32 freq[960];
+    memset(X, 0, sizeof(X));
+    memset(E, 0, sizeof(E));
+    E[band] = (i16)bandLogE;
+    X[8 * rom_eband[band]] = (i16)x;
+    denormalise(X, freq, E, band, band + 1, 8, 0);
+    return freq[8 * rom_eband[band]];
+}
+
 /* celt.cpp:2057 */
 static void synthesis(oc_celt *st, const i16 *X, i32 *out_syn[2], const i16 *bandE, int start, int effEnd, int C,
                       int CC, int transient, int LM, int silence, oc_celt_taps *taps) {

@@ -187,6 +187,8 @@ static i32 log2lin(i32 inLog_Q7) { /* silk.cpp:2248 */
     return out;
 }
 
+i32 oc_test_log2lin(i32 inLog_Q7) { return log2lin(inLog_Q7); } /* unit entry for tests/test_rare_paths.py */
+
 /* ---- codebook selection (silk_NLSF_CB_struct silk.h:639; instances silk.cpp:384-427) --------------------- */
 typedef struct {
     int order;
@@ -600,6 +602,15 @@ static void nlsf2a(i16 *a_Q12, const i16 *NLSF, int d) {
         bwexpander_32(a32_QA1, d, 65536 - shl32(2, i));
         for (k = 0; k < d; k++) a_Q12[k] = (i16)rshift_round(a32_QA1[k], 5);
     }
+}
+
+/* unit entry for tests/golden/make_rare_paths.py: stage-1 index and residuals -> NLSF -> LPC, as decode_parameters does for a frame */
+void oc_test_nlsf2a(const signed char *NLSFIndices, int wb, i16 *a_Q12) {
+    nlsf_cb cb;
+    i16 nlsf[MAX_LPC];
+    get_cb(&cb, wb);
+    nlsf_decode(nlsf, NLSFIndices, &cb);
+    nlsf2a(a_Q12, nlsf, cb.order);
 }
 
 /* silk_decode_pitch silk.cpp:2055 */

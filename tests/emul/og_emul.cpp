@@ -126,6 +126,20 @@ extern "C" unsigned emu_pvq_leaf(int n, int k, unsigned index, int B, int gain, 
     return cm;
 }
 
+// ---- unit entries: the kernels' arithmetic helpers, for their corner inputs (tests/test_rare_paths.py) ---------------
+extern "C" {
+int emu_celt_sqrt(int x) { return og::celt_sqrt(x); }
+int emu_celt_exp2(int x) { return og::celt_exp2(x); }
+int emu_cos_norm(int x) { return og::cos_norm(x); }
+int emu_silk_log2lin(int x) { return og::silk_log2lin(x); }
+// denorm_gains' (gain, shift) for one band with log energy bandLogE: gain in the low half, shift in the high half
+int emu_denorm_gain(int band, int bandLogE) {
+    og::S.bandE_row()[band] = (int16_t)bandLogE;
+    og::denorm_gains(band, band + 1, 1, 0);
+    return (int)(uint16_t)og::S.dn_g_row()[band] | (int)og::S.dn_shift_row()[band] << 16;
+}
+}
+
 // ---- stage taps -------------------------------------------------------------------------------
 static int16_t tap_X[1920], tap_bandE[42];
 static int32_t tap_syn_pre[2][1080], tap_syn_post[2][1080];
