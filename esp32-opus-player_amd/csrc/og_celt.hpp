@@ -492,6 +492,66 @@ OG_DEV void fft_stage(i32 *base, int nblk, int blk_stride, int p, int m, int Nre
     OG_SYNC();
 }
 
+// ---- the last two stages of the 480-point transform as the long block runs them (imdct_channel) ------------------------------
+// fft_stage(.., 3, 32, 5, 96, 5) and fft_stage(.., 5, 96, 1, 1, 1) with the wave's 64 lanes written out.  A lane's butterflies
+// use the same few twiddles in every pass, so they are fetched once, as packed words (rom_fft_tw32: re | im << 16), and long
+// before the stage runs -- the generic stage fetches two halves per twiddle per pass behind its opening barrier and waits.
+//   radix-3: 160 butterflies, three passes (the third: lanes 0 .. 31).  Butterfly id = lane + 64 pass has j = id mod 32 =
+//            lane mod 32 in EVERY pass (64 is a multiple of m = 32): twiddles 5 j and 10 j, two words per lane.
+//   radix-5: 96 butterflies, two passes (the second: lanes 0 .. 31, u = 64 + lane): twiddles u, 2 u, 3 u, 4 u, eight words.
+// Lanes without a butterfly in a pass still name a valid table index (the fetch is unconditional).
+struct LongStage {
+    static constexpr int R3_PASSES = 3, R5_PASSES = 2;
+    static constexpr bool r3_live(int lane, int pass) { return pass < 2 || lane < 32; }
+    static constexpr int r3_elem(int lane, int pass) { return 96 * (2 * pass + (lane >> 5)) + (lane & 31); } // i * mm + j
+    static constexpr int r3_tw(int lane, int k) { return 5 * k * (lane & 31); }                              // k j fstride
+    static constexpr bool r5_live(int lane, int pass) { return pass == 0 || lane < 32; }
+    static constexpr int r5_elem(int lane, int pass) { return pass ? 64 + (lane & 31) : lane; } // u
+    static constexpr int r5_tw(int lane, int pass, int k) { return k * r5_elem(lane, pass); }   // k u fstride
+};
+OG_DEV Cpx ctwp(Cpx a, u32 w) { // ctw() by a packed twiddle
+    const i32 wr = (i32)(i16)(w & 0xffff), wi = (i32)w >> 16;
+    Cpx m = {subw(OG_SMUL(a.r, wr), OG_SMUL(a.i, wi)), addw(OG_SMUL(a.r, wi), OG_SMUL(a.i, wr))};
+    return m;
+}
+// kf_bfly3 (celt.cpp:2891) on elements o, o + 32, o + 64: fft_stage's p == 3 arithmetic, twiddles in hand
+OG_DEV void long_bfly3(i32 *F, int o, u32 w1, u32 w2) {
+    const int m = 32;
+    Cpx f0 = cld(F, o);
+    Cpx s1 = ctwp(cld(F, o + m), w1), s2 = ctwp(cld(F, o + 2 * m), w2);
+    Cpx s3 = cadd(s1, s2), s0 = csub(s1, s2);
+    Cpx f1 = {subw(f0.r, s3.r >> 1), subw(f0.i, s3.i >> 1)};
+    s0.r = OG_SMUL(s0.r, -28378);
+    s0.i = OG_SMUL(s0.i, -28378);
+    f0 = cadd(f0, s3);
+    Cpx f2 = {addw(f1.r, s0.i), subw(f1.i, s0.r)};
+    f1.r = subw(f1.r, s0.i);
+    f1.i = addw(f1.i, s0.r);
+    cst(F, o, f0); cst(F, o + m, f1); cst(F, o + 2 * m, f2);
+}
+// kf_bfly5 (celt.cpp:2934) on elements u, u + 96, .. u + 384: fft_stage's p == 5 arithmetic, twiddles in hand
+OG_DEV void long_bfly5(i32 *F, int o, u32 w1, u32 w2, u32 w3, u32 w4) {
+    const int m = 96;
+    const i32 ya_r = 10126, ya_i = -31164, yb_r = -26510, yb_i = -19261;
+    Cpx s0 = cld(F, o);
+    Cpx s1 = ctwp(cld(F, o + m), w1), s2 = ctwp(cld(F, o + 2 * m), w2);
+    Cpx s3 = ctwp(cld(F, o + 3 * m), w3), s4 = ctwp(cld(F, o + 4 * m), w4);
+    Cpx s7 = cadd(s1, s4), s10 = csub(s1, s4), s8 = cadd(s2, s3), s9 = csub(s2, s3);
+    Cpx f0 = {addw(s0.r, addw(s7.r, s8.r)), addw(s0.i, addw(s7.i, s8.i))};
+    Cpx s5 = {addw(s0.r, addw(OG_SMUL(s7.r, ya_r), OG_SMUL(s8.r, yb_r))),
+              addw(s0.i, addw(OG_SMUL(s7.i, ya_r), OG_SMUL(s8.i, yb_r)))};
+    Cpx s6 = {addw(OG_SMUL(s10.i, ya_i), OG_SMUL(s9.i, yb_i)),
+              negw(addw(OG_SMUL(s10.r, ya_i), OG_SMUL(s9.r, yb_i)))};
+    Cpx s11 = {addw(s0.r, addw(OG_SMUL(s7.r, yb_r), OG_SMUL(s8.r, ya_r))),
+               addw(s0.i, addw(OG_SMUL(s7.i, yb_r), OG_SMUL(s8.i, ya_r)))};
+    Cpx s12 = {subw(OG_SMUL(s9.i, ya_i), OG_SMUL(s10.i, yb_i)), subw(OG_SMUL(s10.r, yb_i), OG_SMUL(s9.r, ya_i))};
+    cst(F, o, f0);
+    cst(F, o + m, csub(s5, s6));
+    cst(F, o + 4 * m, cadd(s5, s6));
+    cst(F, o + 2 * m, cadd(s11, s12));
+    cst(F, o + 3 * m, csub(s11, s12));
+}
+
 // all stages of the 480- or 60-point transform (opus_fft_impl celt.cpp:2997; factor schedules :589-626)
 OG_DEV void fft_blocks(i32 *base, int nblk, int blk_stride, int shift) {
     if (shift == 0) { // 480 = 5*3*4*2*4: innermost radix first
@@ -598,6 +658,8 @@ OG_DEV CpxT ctw32(CpxT a, u32 w) { // C_MUL by a packed twiddle (rom_fft_tw32)
 // `SYF`: the transform's 480 complex points (&SY[60]); `xs`: the coded channel's spectrum; binpar_row() holds its gains
 OG_DEV void imdct_long_front(i32 *SYF, const i16 *xs) {
     const int g = OG_LANE;
+    // (stage B's twiddles, j = lane & 7: requested here, two barriers before the stage)
+    const u32 w1 = rom_fft_tw32[15 * (g & 7)], w2 = rom_fft_tw32[30 * (g & 7)], w3 = rom_fft_tw32[45 * (g & 7)];
     CpxT v[8];
     if (g < 60) {
         const int d0 = g / 12, r12 = g - 12 * d0, i0 = d0 + 5 * (r12 >> 2) + 15 * (r12 & 3);
@@ -661,7 +723,6 @@ OG_DEV void imdct_long_front(i32 *SYF, const i16 *xs) {
     {
         const int j = OG_LANE & 7, ia = OG_LANE >> 3, ib = 8 + ia;
         const bool has_b = ib < 15;
-        const u32 w1 = rom_fft_tw32[15 * j], w2 = rom_fft_tw32[30 * j], w3 = rom_fft_tw32[45 * j];
         CpxT in[2][4];
 #pragma unroll
         for (int it = 0; it < 2; it++) {
@@ -696,13 +757,28 @@ OG_DEV void imdct_long_front(i32 *SYF, const i16 *xs) {
 // (120 .. 959) and final; for i < 30 the first two (60 .. 119) are still the TDAC's input and the last two (960 .. 1019) are
 // the overlap tail the next frame starts from -- neither is saturated (the generic code saturates SY[0 .. 960) in a pass of its
 // own).  The TDAC writes words 0 .. 119: final.  Twiddles: trig[i] | trig[480 + i] packed (rom_prerot480).
-OG_DEV void imdct_long_back(i32 *SY) {
+// The table words come with the call: `t` as long_back_request() asked for them a stage earlier, the TDAC's two window
+// entries w1 = rom_win120[lane], w2 = rom_win120[OVERLAP - 1 - lane].
+struct LongBackTw { u32 a[4], b[4]; };
+OG_DEV LongBackTw long_back_request() { // pass k rotates pair i = lane + 64 k (every index inside the table, pair or no pair)
+    LongBackTw t;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        t.a[k] = rom_prerot480[OG_LANE + 64 * k];
+        t.b[k] = rom_prerot480[479 - OG_LANE - 64 * k];
+    }
+    return t;
+}
+OG_DEV void imdct_long_back(i32 *SY, const LongBackTw &t, i32 w1, i32 w2) {
     i32 *const F = &SY[OVERLAP >> 1];
     OG_SYNC();
-    for (int i = OG_LANE; i < 240; i += OG_NLANES) {
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int i = OG_LANE + 64 * k;
+        if (i >= 240) break;
         i32 *yp0 = &F[2 * i], *yp1 = &F[958 - 2 * i];
         const og_v2i a = *reinterpret_cast<const og_v2i *>(yp0), b = *reinterpret_cast<const og_v2i *>(yp1);
-        const u32 ta = rom_prerot480[i], tb = rom_prerot480[479 - i];
+        const u32 ta = t.a[k], tb = t.b[k];
         const i32 t0 = (i32)(i16)(ta & 0xffff), t1 = (i32)ta >> 16, u0 = (i32)(i16)(tb & 0xffff), u1 = (i32)tb >> 16;
         // (re, im) = (word 1, word 0) of a point
         i32 yr = addw(mul16x32_q15(t0, a.y), mul16x32_q15(t1, a.x)), yi = subw(mul16x32_q15(t1, a.y), mul16x32_q15(t0, a.x));
@@ -717,7 +793,6 @@ OG_DEV void imdct_long_back(i32 *SY) {
     if (OG_LANE < OVERLAP / 2) { // TDAC mirror
         const int i = OG_LANE;
         const i32 x1 = SY[OVERLAP - 1 - i], x2 = SY[i];
-        const i32 w1 = rom_win120[i], w2 = rom_win120[OVERLAP - 1 - i];
         SY[i] = clampsym(subw(mul16x32_q15(w2, x2), mul16x32_q15(w1, x1)), SIG_SAT);
         SY[OVERLAP - 1 - i] = clampsym(addw(mul16x32_q15(w1, x2), mul16x32_q15(w2, x1)), SIG_SAT);
     }
@@ -746,11 +821,31 @@ OG_DEVN void imdct_channel(const i32 *tail, int co, int N, int LM, int B, int sh
         if (long_fast) {
             const int c_src = (CC == 2 && C == 1) ? 0 : co;
             const i32 tail_l = OG_LANE < OVERLAP / 2 ? tail[OG_LANE] : 0; // (requested before the stages, stored behind them)
-            imdct_long_front(&SY[OVERLAP >> 1], &S.v[V_X + c_src * N]);
-            if (OG_LANE < OVERLAP / 2) SY[OG_LANE] = tail_l;
-            fft_stage(&SY[OVERLAP >> 1], 1, NBk, 3, 32, 5, 96, 5);
-            fft_stage(&SY[OVERLAP >> 1], 1, NBk, 5, 96, 1, 1, 1);
-            imdct_long_back(SY);
+            // Every stage's table words are requested a stage or more ahead of the barrier they used to be fetched behind, in
+            // the order they are used: a request costs the registers it lands in and nothing else, the wave no longer waits a
+            // memory round trip at the head of each stage.
+            const int lane = OG_LANE;
+            i32 *const F = &SY[OVERLAP >> 1];
+            const u32 c1 = rom_fft_tw32[LongStage::r3_tw(lane, 1)], c2 = rom_fft_tw32[LongStage::r3_tw(lane, 2)];
+            u32 d[LongStage::R5_PASSES][4];
+#pragma unroll
+            for (int pass = 0; pass < LongStage::R5_PASSES; pass++)
+#pragma unroll
+                for (int k = 1; k <= 4; k++) d[pass][k - 1] = rom_fft_tw32[LongStage::r5_tw(lane, pass, k)];
+            imdct_long_front(F, &S.v[V_X + c_src * N]);
+            if (lane < OVERLAP / 2) SY[lane] = tail_l;
+            const LongBackTw bt = long_back_request();
+            OG_SYNC();
+#pragma unroll
+            for (int pass = 0; pass < LongStage::R3_PASSES; pass++)
+                if (LongStage::r3_live(lane, pass)) long_bfly3(F, LongStage::r3_elem(lane, pass), c1, c2);
+            const i32 win1 = rom_win120[lane], win2 = rom_win120[OVERLAP - 1 - lane]; // (lanes 60 .. 63: inside the table, unused)
+            OG_SYNC();
+#pragma unroll
+            for (int pass = 0; pass < LongStage::R5_PASSES; pass++)
+                if (LongStage::r5_live(lane, pass))
+                    long_bfly5(F, LongStage::r5_elem(lane, pass), d[pass][0], d[pass][1], d[pass][2], d[pass][3]);
+            imdct_long_back(SY, bt, win1, win2);
             return;
         } else {
 #endif
@@ -989,6 +1084,8 @@ OG_DEVN void comb_filter(const CeltState *st, int c, int off, int T0, int T1, in
                 t3 = __builtin_amdgcn_update_dpp(__builtin_amdgcn_readlane(w, 1), t2, 0x138, 0xf, 0xf, false);
                 t4 = __builtin_amdgcn_update_dpp(__builtin_amdgcn_readlane(w, 0), t3, 0x138, 0xf, 0xf, false);
             };
+            // (the cross-fade's window entry: requested before the taps, not between them and the multiplies)
+            const i32 wf = base + it < overlap ? (i32)rom_win120[OG_MIN(i, OVERLAP - 1)] : 0;
             i32 a4 = 0, a3 = 0, a2 = 0, a1 = 0, a0 = 0;
             if (use1) window(T1, a4, a3, a2, a1, a0);
             i32 y;
@@ -996,7 +1093,7 @@ OG_DEVN void comb_filter(const CeltState *st, int c, int off, int T0, int T1, in
                 i32 b4 = 0, b3 = 0, b2 = 0, b1 = 0, b0 = 0;
                 if (use0) window(T0, b4, b3, b2, b1, b0);
                 if (i < overlap) {
-                    const i32 f = tr16(mul16_q15(rom_win120[i], rom_win120[i]));
+                    const i32 f = tr16(mul16_q15(wf, wf));
                     y = y0 + mul16x32_q15(mul16_q15(32767 - f, g00), b2) + mul16x32_q15(mul16_q15(32767 - f, g01), b1 + b3) +
                         mul16x32_q15(mul16_q15(32767 - f, g02), b0 + b4) + mul16x32_q15(mul16_q15(f, g10), a2) +
                         mul16x32_q15(mul16_q15(f, g11), a1 + a3) + mul16x32_q15(mul16_q15(f, g12), a0 + a4);
