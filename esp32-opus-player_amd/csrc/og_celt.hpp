@@ -515,8 +515,7 @@ OG_DEV Cpx ctwp(Cpx a, u32 w) { // ctw() by a packed twiddle
     return m;
 }
 // kf_bfly3 (celt.cpp:2891) on elements o, o + 32, o + 64: fft_stage's p == 3 arithmetic, twiddles in hand
-OG_DEV void long_bfly3(i32 *F, int o, u32 w1, u32 w2) {
-    const int m = 32;
+OG_DEV void bfly3_tw(i32 *F, int o, int m, u32 w1, u32 w2) { // (m: the stage's stride, a constant at every call)
     Cpx f0 = cld(F, o);
     Cpx s1 = ctwp(cld(F, o + m), w1), s2 = ctwp(cld(F, o + 2 * m), w2);
     Cpx s3 = cadd(s1, s2), s0 = csub(s1, s2);
@@ -529,9 +528,9 @@ OG_DEV void long_bfly3(i32 *F, int o, u32 w1, u32 w2) {
     f1.i = addw(f1.i, s0.r);
     cst(F, o, f0); cst(F, o + m, f1); cst(F, o + 2 * m, f2);
 }
+OG_DEV void long_bfly3(i32 *F, int o, u32 w1, u32 w2) { bfly3_tw(F, o, 32, w1, w2); }
 // kf_bfly5 (celt.cpp:2934) on elements u, u + 96, .. u + 384: fft_stage's p == 5 arithmetic, twiddles in hand
-OG_DEV void long_bfly5(i32 *F, int o, u32 w1, u32 w2, u32 w3, u32 w4) {
-    const int m = 96;
+OG_DEV void bfly5_tw(i32 *F, int o, int m, u32 w1, u32 w2, u32 w3, u32 w4) {
     const i32 ya_r = 10126, ya_i = -31164, yb_r = -26510, yb_i = -19261;
     Cpx s0 = cld(F, o);
     Cpx s1 = ctwp(cld(F, o + m), w1), s2 = ctwp(cld(F, o + 2 * m), w2);
@@ -551,6 +550,7 @@ OG_DEV void long_bfly5(i32 *F, int o, u32 w1, u32 w2, u32 w3, u32 w4) {
     cst(F, o + 2 * m, cadd(s11, s12));
     cst(F, o + 3 * m, csub(s11, s12));
 }
+OG_DEV void long_bfly5(i32 *F, int o, u32 w1, u32 w2, u32 w3, u32 w4) { bfly5_tw(F, o, 96, w1, w2, w3, w4); }
 
 // all stages of the 480- or 60-point transform (opus_fft_impl celt.cpp:2997; factor schedules :589-626)
 OG_DEV void fft_blocks(i32 *base, int nblk, int blk_stride, int shift) {
@@ -668,12 +668,27 @@ OG_DEV void imdct_long_front(i32 *SYF, const i16 *xs) {
         const u32 *tp = rom_prerot480 + i0;
 #pragma unroll
         for (int m = 0; m < 8; m++) { // input i0 + 60 m -> point 4 (m & 1) + (m >> 1) of the lane's eight
-            const i32 x1 = denorm_coef(x_lo[120 * m], p_lo[15 * m]), x2 = denorm_coef(x_hi[-120 * m], p_hi[-15 * m]);
             const u32 tt = tp[60 * m];
             const i32 t0 = (i32)(i16)(tt & 0xffff), t1 = (i32)tt >> 16;
+            const int k = 4 * (m & 1) + (m >> 1);
+            // Coefficients 800 .. 959 are not coded: their bins' gain is zero (denorm_bins), whatever the spectrum's top holds
+            // (og_state.hpp).  m = 0 has x2 = coefficient 959 - 2 i0 >= 841 in every lane, m = 7 has x1 = coefficient
+            // 2 (i0 + 420) >= 840: neither is loaded, and a product with zero and its sum are dropped (exactly 0 and y).
+            if (m == 0) {
+                const i32 x1 = denorm_coef(x_lo[0], p_lo[0]);
+                v[k].r = mul16x32_q15(t0, x1);
+                v[k].i = mul16x32_q15(t1, x1);
+                continue;
+            }
+            if (m == 7) {
+                const i32 x2 = denorm_coef(x_hi[-120 * m], p_hi[-15 * m]);
+                v[k].r = negw(mul16x32_q15(t1, x2));
+                v[k].i = mul16x32_q15(t0, x2);
+                continue;
+            }
+            const i32 x1 = denorm_coef(x_lo[120 * m], p_lo[15 * m]), x2 = denorm_coef(x_hi[-120 * m], p_hi[-15 * m]);
             const i32 yr = addw(mul16x32_q15(t0, x2), mul16x32_q15(t1, x1));
             const i32 yi = subw(mul16x32_q15(t0, x1), mul16x32_q15(t1, x2));
-            const int k = 4 * (m & 1) + (m >> 1);
             v[k].r = yi;
             v[k].i = yr;
         }
@@ -798,6 +813,116 @@ OG_DEV void imdct_long_back(i32 *SY, const LongBackTw &t, i32 w1, i32 w2) {
     }
     OG_SYNC();
 }
+
+// ---- the eight short blocks of a transient frame (eight 240-point transforms per channel), written out for 8 x 60 points -----
+// clt_mdct_backward celt.cpp:3204 + opus_fft_impl :2997 for nfft = 60 = 4 x 3 x 5 (innermost radix first, twiddle stride 8), the
+// arithmetic of every butterfly as fft_stage's; all eight blocks side by side, block = lane & 7 in every stage (no lane divides
+// its index):
+//   front  rom_bitrev60 puts input i = d0 + 5 d1 + 15 q (d0 < 5, d1 < 3, q < 4) at position 4 (3 d0 + d1) + q: the four inputs
+//          i0 + 15 q of butterfly g = 3 d0 + d1 ARE the four points of its radix-4 (m = 1) butterfly.  Task (block, g), 120 of
+//          them in two passes, de-normalises and pre-rotates those four and runs the butterfly in registers: no scatter through
+//          the permutation table, no LDS round trip before the first stage.  Like every transform that reads the spectrum
+//          under the buffer (og_state.hpp), every read is an instruction before the first store;
+//   r3, r5 radix-3 (m = 4: 160 butterflies, three passes, j = (lane >> 3) & 3 in every pass) and radix-5 (m = 12: 96, two
+//          passes) with packed twiddles fetched once, behind the front's stores: a stage ahead for the radix-5;
+//   back   the post-rotation of all 8 x 30 pairs in four passes (the generic code: eight passes of 30 lanes), then the TDAC
+//          mirror -- which writes every one of the 960 output samples exactly once (block b's words 120 b .. 120 b + 119), so
+//          the saturation (celt_synthesis celt.cpp:2121) is folded into its stores; the overlap tail (words 960 .. 1019) is
+//          not saturated, as before.
+struct ShortStage {
+    static constexpr int FRONT_PASSES = 2, R3_PASSES = 3, R5_PASSES = 2, POST_PASSES = 4, TDAC_PASSES = 8;
+    static constexpr int r3_j(int lane) { return (lane >> 3) & 3; }
+    static constexpr int r3_i(int lane, int pass) { return (lane >> 5) + 2 * pass; }              // live: < 5
+    static constexpr int r5_u(int lane, int pass) { return pass ? 8 + ((lane >> 3) & 3) : lane >> 3; } // pass 1 live: lane < 32
+};
+OG_DEV void imdct_short8(i32 *SY, const i16 *xs, const i32 *tail) {
+    const int lane = OG_LANE, blk = lane & 7, sub = lane >> 3;
+    const i16 *const trig = rom_mdct_trig + 1680;
+    i32 *const F = &SY[OVERLAP >> 1] + 120 * blk; // the lane's block
+    const i32 tail_l = lane < OVERLAP / 2 ? tail[lane] : 0;
+    CpxT v[ShortStage::FRONT_PASSES][4];
+#pragma unroll
+    for (int pass = 0; pass < ShortStage::FRONT_PASSES; pass++) {
+        const int g = sub + 8 * pass; // butterfly 0 .. 14 of the block (pass 1, lanes 56 .. 63: none)
+        if (g < 15) {
+            const int d0 = g / 3, i0 = d0 + 5 * (g - 3 * d0);
+            CpxT f[4];
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                const int i = i0 + 15 * q; // coefficients blk + 8 (2 i) and blk + 8 (119 - 2 i): bins 2 i and 119 - 2 i
+                const i32 x1 = denorm_coef(xs[blk + 16 * i], binpar_row()[2 * i]);
+                const i32 x2 = denorm_coef(xs[blk + 952 - 16 * i], binpar_row()[119 - 2 * i]);
+                const i32 t0 = trig[i], t1 = trig[60 + i];
+                f[q].i = addw(mul16x32_q15(t0, x2), mul16x32_q15(t1, x1));
+                f[q].r = subw(mul16x32_q15(t0, x1), mul16x32_q15(t1, x2));
+            }
+            // radix-4, m = 1 (kf_bfly4 celt.cpp:2841 with unit twiddles)
+            CpxT f0 = f[0], f1 = f[1], f2 = f[2], f3 = f[3];
+            CpxT s0 = {subw(f0.r, f2.r), subw(f0.i, f2.i)};
+            f0.r = addw(f0.r, f2.r); f0.i = addw(f0.i, f2.i);
+            CpxT s1 = {addw(f1.r, f3.r), addw(f1.i, f3.i)};
+            f2.r = subw(f0.r, s1.r); f2.i = subw(f0.i, s1.i);
+            f0.r = addw(f0.r, s1.r); f0.i = addw(f0.i, s1.i);
+            s1.r = subw(f1.r, f3.r); s1.i = subw(f1.i, f3.i);
+            f1.r = addw(s0.r, s1.i); f1.i = subw(s0.i, s1.r);
+            f3.r = subw(s0.r, s1.i); f3.i = addw(s0.i, s1.r);
+            v[pass][0] = f0; v[pass][1] = f1; v[pass][2] = f2; v[pass][3] = f3;
+        }
+    }
+    OG_SYNC(); // (every read of the spectrum and of the per-bin gains above, every store below)
+#pragma unroll
+    for (int pass = 0; pass < ShortStage::FRONT_PASSES; pass++) {
+        const int g = sub + 8 * pass;
+        if (g < 15) {
+            *reinterpret_cast<og_v4i *>(&F[8 * g]) = og_v4i{v[pass][0].r, v[pass][0].i, v[pass][1].r, v[pass][1].i};
+            *reinterpret_cast<og_v4i *>(&F[8 * g + 4]) = og_v4i{v[pass][2].r, v[pass][2].i, v[pass][3].r, v[pass][3].i};
+        }
+    }
+    if (lane < OVERLAP / 2) SY[lane] = tail_l;
+    // (both stages' twiddles: requested here, once the front's held points are stored -- with them it was two registers too many)
+    const u32 c1 = rom_fft_tw32[40 * ShortStage::r3_j(lane)], c2 = rom_fft_tw32[80 * ShortStage::r3_j(lane)];
+    u32 d[ShortStage::R5_PASSES][4];
+#pragma unroll
+    for (int pass = 0; pass < ShortStage::R5_PASSES; pass++)
+#pragma unroll
+        for (int k = 1; k <= 4; k++) d[pass][k - 1] = rom_fft_tw32[8 * k * ShortStage::r5_u(lane, pass)];
+    OG_SYNC();
+#pragma unroll
+    for (int pass = 0; pass < ShortStage::R3_PASSES; pass++)
+        if (ShortStage::r3_i(lane, pass) < 5) bfly3_tw(F, 12 * ShortStage::r3_i(lane, pass) + ShortStage::r3_j(lane), 4, c1, c2);
+    OG_SYNC();
+#pragma unroll
+    for (int pass = 0; pass < ShortStage::R5_PASSES; pass++)
+        if (pass == 0 || lane < 32) bfly5_tw(F, ShortStage::r5_u(lane, pass), 12, d[pass][0], d[pass][1], d[pass][2], d[pass][3]);
+    OG_SYNC();
+    // post-rotation, pairs (i, 59 - i) of every block (celt.cpp:3252-3284): pair i = sub + 8 pass
+#pragma unroll
+    for (int pass = 0; pass < ShortStage::POST_PASSES; pass++) {
+        const int i = sub + 8 * pass;
+        if (i >= 30) break;
+        i32 *yp0 = &F[2 * i], *yp1 = &F[118 - 2 * i];
+        const og_v2i a = *reinterpret_cast<const og_v2i *>(yp0), b = *reinterpret_cast<const og_v2i *>(yp1);
+        const i32 t0 = trig[i], t1 = trig[60 + i], u0 = trig[59 - i], u1 = trig[119 - i];
+        // (re, im) = (word 1, word 0) of a point
+        const i32 yr = addw(mul16x32_q15(t0, a.y), mul16x32_q15(t1, a.x)), yi = subw(mul16x32_q15(t1, a.y), mul16x32_q15(t0, a.x));
+        const i32 zr = addw(mul16x32_q15(u0, b.y), mul16x32_q15(u1, b.x)), zi = subw(mul16x32_q15(u1, b.y), mul16x32_q15(u0, b.x));
+        *reinterpret_cast<og_v2i *>(yp0) = og_v2i{yr, zi};
+        *reinterpret_cast<og_v2i *>(yp1) = og_v2i{zr, yi};
+    }
+    OG_SYNC();
+    // TDAC mirror (celt.cpp:3286-3296) of block blk over words 120 blk .. 120 blk + 119, saturated where it is stored
+    i32 *const o = SY + 120 * blk;
+#pragma unroll
+    for (int pass = 0; pass < ShortStage::TDAC_PASSES; pass++) {
+        const int i = sub + 8 * pass;
+        if (i >= OVERLAP / 2) break;
+        const i32 x1 = o[OVERLAP - 1 - i], x2 = o[i];
+        const i32 w1 = rom_win120[i], w2 = rom_win120[OVERLAP - 1 - i];
+        o[i] = clampsym(subw(mul16x32_q15(w2, x2), mul16x32_q15(w1, x1)), SIG_SAT);
+        o[OVERLAP - 1 - i] = clampsym(addw(mul16x32_q15(w1, x2), mul16x32_q15(w2, x1)), SIG_SAT);
+    }
+    OG_SYNC();
+}
 #endif
 
 // Inverse MDCT of every block of one output channel (clt_mdct_backward celt.cpp:3204), reading
@@ -847,12 +972,15 @@ OG_DEVN void imdct_channel(const i32 *tail, int co, int N, int LM, int B, int sh
                     long_bfly5(F, LongStage::r5_elem(lane, pass), d[pass][0], d[pass][1], d[pass][2], d[pass][3]);
             imdct_long_back(SY, bt, win1, win2);
             return;
+        } else if (B == 8 && !(CC == 1 && C == 2)) { // (a down-mix: generic code, as above)
+            imdct_short8(SY, &S.v[V_X + ((CC == 2 && C == 1) ? 0 : co) * N], tail);
+            return;
         } else {
 #endif
 #ifdef OG_RECON_TIGHT
 #if !defined(OG_HOST_EMUL)
-        // (short blocks: the coefficient's gain from the per-bin table of denorm_bins -- one look-up instead of three -- unless
-        // this is a down-mix, which reads two spectra with two sets of gains)
+        // (what is left to this code in the 20 ms kernel: down-mixes, which read two spectra with two sets of gains.  Any other
+        // channel would take its coefficient's gain from the per-bin table of denorm_bins -- one look-up instead of three)
         const bool bins = !(CC == 1 && C == 2);
         const i16 *const xsrc = &S.v[V_X + ((CC == 2 && C == 1) ? 0 : co) * N];
 #define OG_FREQ(j) (bins ? denorm_coef(xsrc[(j)], binpar_row()[(j) >> 3]) : freq_out(co, (j), N, LM, C, CC))

@@ -510,8 +510,9 @@ struct LcgTab {
 // noise amplitude r -- a division, an exp2, a reciprocal square root -- in every lane alike, up to 42 times one after the other (the
 // values come from LDS rows: vector work, not scalar), and steps the noise generator with its squaring loop per lane: a frame with
 // anti-collapse (one in sixteen of the bench payloads) cost the wave 60 % more than one without.  Here lane (channel, band) derives
-// its own r, one pass for all of them, into a scratch row; the fills read it back and jump the generator by the frame's table.
-OG_DEV void anti_collapse_pm(const LcgTab &lcg, int LM, int C, int size, int start, int end, u32 seed) {
+// its own r, one pass for all of them, into a scratch row (anti_collapse_r); the fills read it back and jump the generator by the
+// frame's table -- band by band here, in whole-wave passes in the 20 ms kernel's own layout (og_celt_recon_pm.hpp).
+OG_DEV i16 *anti_collapse_r(int LM, int C, int start, int end) { // -> r of (channel c, band i) at [c * NBANDS + i]
     i16 *const rrow = &S.v[V_TMP]; // (the band loop's scratch row: free by now)
     OG_LSYNC();
     OG_FOR_LANES(l, C * NBANDS) {
@@ -544,6 +545,11 @@ OG_DEV void anti_collapse_pm(const LcgTab &lcg, int LM, int C, int size, int sta
         rrow[l] = (i16)r;
     }
     OG_LSYNC();
+    return rrow;
+}
+#ifndef OG_RECON_TIGHT // (the 20 ms kernel's own: og_celt_recon_pm.hpp)
+OG_DEV void anti_collapse_pm(const LcgTab &lcg, int LM, int C, int size, int start, int end, u32 seed) {
+    const i16 *const rrow = anti_collapse_r(LM, C, start, end);
     for (int i = start; i < end; i++) {
         const int N0 = rom_eband[i + 1] - rom_eband[i];
         for (int c = 0; c < C; c++) {
@@ -563,6 +569,7 @@ OG_DEV void anti_collapse_pm(const LcgTab &lcg, int LM, int C, int size, int sta
         }
     }
 }
+#endif
 
 // The leaves of one job (quant_partition celt.cpp:1382 flattened by the parse kernel), vector half.  The leaves with
 // pulses are complete already (pvq_leaf_lane) and only contribute their collapse masks, which the leaf pass ORed, pre-shifted,

@@ -471,4 +471,104 @@ OG_DEV void recon_all_bands_pm(const ParseRec *rec, const LcgTab &lcg, int C, in
     seed_io = seed;
 }
 
+#ifdef OG_RECON_TIGHT
+// anti_collapse (celt.cpp:1010) of the 20 ms kernel, in whole-wave passes.  The band-by-band form (og_celt_recon.hpp) visits every
+// (band, channel, block) cell of a transient frame -- 336 of them -- one after the other: a barrier, a fill by N0 <= 22 lanes
+// and two dependent table loads per collapsed cell, a renormalise() per band touched.  What ties the cells together is only the
+// noise generator, which the reference steps in the order band, channel, block, N0 draws per collapsed block; a jump ahead is
+// one multiply-add (LcgTab), so every draw can be named by its position:
+//   1  lane (band i, channel c), in the order e = i C + c, counts its collapsed blocks; an exclusive prefix over the wave of
+//      (blocks x N0) is the number of draws before the entry, and lcg_skip by it (at most 1,600) the entry's seed;
+//   2  a lane per group of 8 coefficients: coefficient j's eight blocks are the 16 contiguous bytes at x + 8 j.  Block k, if
+//      collapsed, takes the sign of draw rank(k) N0 + j of its entry (rank: collapsed blocks below k; at most 7 * 22 + 21 = 175,
+//      inside rom_lcg_jump).  The group's sum of squares is taken while its values are in registers;
+//   3  a lane per entry adds its groups' sums (wrapping 32-bit sums: any order) and derives the gain of renormalise();
+//   4  one apply pass over the groups of the entries that had a fill.
+// The per-entry words lie beside r in the Hadamard scratch row, the groups' sums over the front of the band loop's tables
+// (jdesc .. jcm: dead since the bands' collapse masks were gathered; binband / binoff behind them are still read here).
+static_assert(sizeof(i32) * 2 * PM_GROUPS <= offsetof(PmLds, binband), "the groups' sums end before the bin tables");
+static_assert(48 + 2 * 2 * NBANDS <= 200 && (V_TMP + 48) % 2 == 0, "r and the entries' words fit the scratch row");
+OG_DEV void anti_collapse_pm(const LcgTab &lcg, int LM, int C, int size, int start, int end, u32 seed) {
+    const PmLds &P = PM();
+    const i16 *const rrow = anti_collapse_r(LM, C, start, end);
+    u32 *const ent = reinterpret_cast<u32 *>(&S.v[V_TMP + 48]); // per entry e: its seed, then gain | shift << 16 | touched << 31
+    i32 *const part = reinterpret_cast<i32 *>(&S.v[V_NORM]);    // per (channel, group): sum of squares
+    const int NE = C * NBANDS;
+    OG_STAT(32, 1);                                             // frames that run anti-collapse
+    u32 run = 0; // (one lane: the prefix as a running sum)
+    (void)run;
+    OG_FOR_LANES(e, OG_NLANES > 1 ? OG_NLANES : NE) { // (every lane of the wave takes part in the prefix)
+        const int i = C == 2 ? e >> 1 : e;
+        int draws = 0;
+        if (e < NE && i >= start && i < end) {
+            const int cnt = __builtin_popcount(~(u32)S.cmask_row()[e] & 0xffu);
+            draws = cnt * (rom_eband[i + 1] - rom_eband[i]);
+            OG_STAT(30, cnt);                                   // cells filled
+            OG_STAT(31, cnt != 0);                              // (band, channel) entries renormalised
+        }
+#ifdef OG_HOST_EMUL
+        const u32 before = run;
+        run += (u32)draws;
+#else
+        const u32 before = (u32)(wave_scan_add(draws) - draws);
+#endif
+        if (e < NE) ent[e] = lcg_skip(seed, before);
+    }
+    OG_LSYNC();
+    OG_FOR_LANES(t, C * PM_GROUPS) {
+        const int c = t >= PM_GROUPS, g = t - PM_GROUPS * c;
+        const int i = P.binband[g], j = P.binoff[g], e = i * C + c;
+        const u32 clr = (i >= start && i < end) ? ~(u32)S.cmask_row()[e] & 0xffu : 0u;
+        if (clr) {
+            const int N0 = rom_eband[i + 1] - rom_eband[i];
+            const i32 r = rrow[c * NBANDS + i];
+            const u32 base = ent[e];
+            V8 x = ld8(V_X + c * size + 8 * g);
+            int at = j;
+            i32 ss = 0;
+#pragma unroll
+            for (int k = 0; k < 8; k++) {
+                const u32 s = lcg.at(base, at); // (a block that is not filled names the next one's draw: inside the table)
+                if ((clr >> k) & 1u) {
+                    x.v[k] = (i16)((s & 0x8000) ? r : -r);
+                    at += N0;
+                }
+                ss += mul16(x.v[k], x.v[k]);
+            }
+            st8(V_X + c * size + 8 * g, x);
+            part[t] = ss;
+        }
+    }
+    OG_LSYNC();
+    OG_FOR_LANES(e, NE) { // renormalise()'s gain for the entries that had a fill
+        const int i = C == 2 ? e >> 1 : e, c = e - i * C;
+        u32 w = 0;
+        if (i >= start && i < end && (~(u32)S.cmask_row()[e] & 0xffu)) {
+            const int g0 = rom_eband[i], g1 = rom_eband[i + 1];
+            i32 E = 1;
+            for (int g = g0; g < g1; g++) E += part[c * PM_GROUPS + g];
+            const int k = ilog2(E) >> 1;
+            const i32 t = vshr32(E, 2 * (k - 7));
+            const i32 gn = tr16(mul16_p15(rsqrt_norm(t), 32767));
+            w = ((u32)gn & 0xffffu) | (u32)((k + 1) & 63) << 16 | 1u << 31;
+        }
+        ent[e] = w;
+    }
+    OG_LSYNC();
+    OG_FOR_LANES(t, C * PM_GROUPS) {
+        const int c = t >= PM_GROUPS, g = t - PM_GROUPS * c;
+        const u32 w = ent[P.binband[g] * C + c];
+        if (w) {
+            const i32 gn = (i32)(i16)(w & 0xffff);
+            const int sh = (int)(w >> 16) & 63;
+            V8 x = ld8(V_X + c * size + 8 * g);
+#pragma unroll
+            for (int k = 0; k < 8; k++) x.v[k] = (i16)pshr32(mul16(gn, x.v[k]), sh);
+            st8(V_X + c * size + 8 * g, x);
+        }
+    }
+    OG_LSYNC();
+}
+#endif
+
 } // namespace og
