@@ -138,6 +138,12 @@ int emu_denorm_gain(int band, int bandLogE) {
     og::denorm_gains(band, band + 1, 1, 0);
     return (int)(uint16_t)og::S.dn_g_row()[band] | (int)og::S.dn_shift_row()[band] << 16;
 }
+// the saturating helpers of og_common.hpp, for their known answers (tests/test_saturation_paths.py)
+int emu_add_sat32(int a, int b) { return og::add_sat32(a, b); }
+int emu_sub_sat32(int a, int b) { return og::sub_sat32(a, b); }
+int emu_lshift_sat32(int a, int s) { return og::lshift_sat32(a, s); }
+int emu_limit32(int a, int l1, int l2) { return og::limit32(a, l1, l2); }
+int emu_sat16(int x) { return og::sat16(x); }
 }
 
 // ---- stage taps -------------------------------------------------------------------------------

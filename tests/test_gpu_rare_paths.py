@@ -32,10 +32,11 @@ CORPUS = json.load(open(os.path.join(ROOT, "tests", "golden", "rare_paths.json")
 N, SEAMS, FILL_LEN = 256, (0, 31, 32, 63), 60
 
 
-def _groups():
-    """corpus entries by (TOC sequence, decoder channels), four at a time: one batch each"""
+def _groups(corpus=CORPUS):
+    """corpus entries by (TOC sequence, decoder channels), four at a time: one batch each.  (The helpers and the two test bodies take
+    the corpus as a parameter: tests/test_gpu_saturation_paths.py runs them over its own.)"""
     by = {}
-    for i, e in enumerate(CORPUS["entries"]):
+    for i, e in enumerate(corpus["entries"]):
         by.setdefault((tuple(int(p[:2], 16) for p in e["packets"]), e["channels"]), []).append(i)
     return [(tocs, ch, ids[k:k + 4]) for (tocs, ch), ids in sorted(by.items()) for k in range(0, len(ids), 4)]
 
@@ -44,9 +45,9 @@ GROUPS = _groups()
 IDS = [f"toc{'_'.join('%02x' % t for t in tocs)}-ch{ch}-e{'_'.join(map(str, ids))}" for tocs, ch, ids in GROUPS]
 
 
-def _batch(pkg, tocs, ids, layout):
+def _batch(pkg, tocs, ids, layout, corpus=CORPUS):
     """-> packets[frame][stream] (bytes), owner[stream] = corpus entry or -1, the TOC of every step"""
-    ents = [CORPUS["entries"][i] for i in ids]
+    ents = [corpus["entries"][i] for i in ids]
     tocs = list(tocs) + [tocs[-1]]  # (+ 1 step: an ordinary packet on the state the corpus packets leave)
     frames = len(tocs)
     pay = pkg.lcg_payloads(N, frames, FILL_LEN, seed_base=0x4A2E + tocs[0])
@@ -65,7 +66,7 @@ def _batch(pkg, tocs, ids, layout):
     return pk, owner, tocs
 
 
-def _oracle(oracle, channels, pk, owner):
+def _oracle(oracle, channels, pk, owner, corpus=CORPUS):
     frames = len(pk)
     pcm = np.zeros((frames, N, 960 * channels), dtype=np.int16)
     rets = np.zeros((frames, N), dtype=np.int32)
@@ -78,8 +79,8 @@ def _oracle(oracle, channels, pk, owner):
             rets[f, s], rngs[f, s] = r, oracle.lib.oc_decoder_final_range(d.h)
             if r > 0:
                 pcm[f, s] = ref[:960].reshape(-1)
-            if owner[s] >= 0 and f < len(CORPUS["entries"][owner[s]]["packets"]):  # no comparison of nothing
-                exp = CORPUS["entries"][owner[s]]["expect"][f]
+            if owner[s] >= 0 and f < len(corpus["entries"][owner[s]]["packets"]):  # no comparison of nothing
+                exp = corpus["entries"][owner[s]]["expect"][f]
                 assert [r, int(rngs[f, s]), zlib.crc32(ref[:max(r, 0)].tobytes())] == exp, ("the oracle moved", owner[s], f)
     return pcm, rets, rngs
 
@@ -112,10 +113,13 @@ def _same(pcm, res, ref, rets, what):
 @pytest.mark.parametrize("layout", ["seams", "wave"])
 @pytest.mark.parametrize("toc_seq, channels, ids", GROUPS, ids=IDS)
 def test_corpus_streams_on_three_routes(pkg, oracle, gpu_ctx, toc_seq, channels, ids, layout):
-    ctx = gpu_ctx
-    pk, owner, step_toc = _batch(pkg, toc_seq, ids, layout)
+    streams_on_three_routes(CORPUS, pkg, oracle, gpu_ctx, toc_seq, channels, ids, layout)
+
+
+def streams_on_three_routes(corpus, pkg, oracle, ctx, toc_seq, channels, ids, layout):
+    pk, owner, step_toc = _batch(pkg, toc_seq, ids, layout, corpus)
     frames = len(pk)
-    ref, rets, rngs = _oracle(oracle, channels, pk, owner)
+    ref, rets, rngs = _oracle(oracle, channels, pk, owner, corpus)
     arena, offs, lens = _arena(pk)
     tocs = np.repeat(np.array(step_toc, dtype=np.uint8)[:, None], N, axis=1)
     masks = {pkg.toc_modes(t) for t in step_toc}
@@ -155,8 +159,11 @@ def _otap(oracle, d, what, c, dtype, count):
 def test_corpus_stage_taps(pkg, oracle, gpu_ctx, toc_seq, channels, ids):
     """CELT: record header, energies, pulses, tf_res, synthesis output after the comb filter, overlap tail.  SILK: gains, both LPC
     sets, LTP taps, the core output."""
-    ctx = gpu_ctx
-    pk, owner, step_toc = _batch(pkg, toc_seq, ids, "seams")
+    stage_taps(CORPUS, pkg, oracle, gpu_ctx, toc_seq, channels, ids)
+
+
+def stage_taps(corpus, pkg, oracle, ctx, toc_seq, channels, ids):
+    pk, owner, step_toc = _batch(pkg, toc_seq, ids, "seams", corpus)
     frames = len(pk)
     arena, offs, lens = _arena(pk)
     ctx.streams_alloc(N, channels)
@@ -189,8 +196,8 @@ def test_corpus_stage_taps(pkg, oracle, gpu_ctx, toc_seq, channels, ids):
             ctx.synchronize()
             for s in mine:
                 ref, r = decs[s].decode(pk[f][s])  # (the SILK taps are those of this call)
-                if f < len(CORPUS["entries"][owner[s]]["packets"]):
-                    exp = CORPUS["entries"][owner[s]]["expect"][f]
+                if f < len(corpus["entries"][owner[s]]["packets"]):
+                    exp = corpus["entries"][owner[s]]["expect"][f]
                     assert [r, oracle.lib.oc_decoder_final_range(decs[s].h), zlib.crc32(ref[:max(r, 0)].tobytes())] == exp
                 if r != 960:
                     continue
