@@ -43,6 +43,8 @@ EXPORTS = [
     "opusgpu_downmix_matrix", "opusgpu_tracks_resample_mixed_device", "opusgpu_files_decode_mixed", "opusgpu_ms_files_decode_mixed",
     "opusgpu_mel_basis", "opusgpu_mel_filterbank", "opusgpu_mel_layout", "opusgpu_tracks_mel_device", "opusgpu_files_decode_mel",
     "opusgpu_ms_files_decode_mel",
+    "opusgpu_resample_ratio_taps", "opusgpu_resample_ratio_layout", "opusgpu_tracks_resample_ratio_device", "opusgpu_files_decode_ratio",
+    "opusgpu_ms_files_decode_ratio",
 ]
 
 
@@ -249,6 +251,12 @@ def load_lib():
     lib.opusgpu_files_decode_resampled.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
     lib.opusgpu_ms_files_decode_resampled.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
     lib.opusgpu_downmix_matrix.argtypes = [C.c_int, C.c_int, vp]
+    lib.opusgpu_resample_ratio_taps.argtypes = [C.c_int, C.c_int, C.POINTER(vp)]
+    lib.opusgpu_resample_ratio_layout.argtypes = [C.c_int, vp, C.c_int, C.c_int, vp]
+    lib.opusgpu_resample_ratio_layout.restype = C.c_int64
+    lib.opusgpu_tracks_resample_ratio_device.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp]
+    lib.opusgpu_files_decode_ratio.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp]
+    lib.opusgpu_ms_files_decode_ratio.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp]
     lib.opusgpu_tracks_resample_mixed_device.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp]
     lib.opusgpu_files_decode_mixed.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp]
     lib.opusgpu_ms_files_decode_mixed.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp]
@@ -614,6 +622,77 @@ def track_rate_args(batch, rate=48000, mono=False, format="s16", out=None, devic
     return TRACK_RATES[rate], ch_out, offsets, total, out
 
 
+def track_ratio(resample):
+    """A resample= argument as its reduced (up, down) (include/opusgpu.h TRACK RATIOS): a pair (up, down) as for
+    scipy.signal.resample_poly, or the output rate as an int, which is reduced against 48000 -- 44100 is (147, 160).  Raises
+    ValueError for anything else and for a ratio outside 1 <= up <= 160, up < down <= min(8 up, 640)."""
+    import math
+    import numbers
+    if isinstance(resample, numbers.Integral) and not isinstance(resample, bool):
+        pair = (int(resample), 48000)
+    else:
+        try:
+            pair = tuple(resample)
+        except TypeError:
+            pair = ()
+        if len(pair) != 2 or not all(isinstance(v, numbers.Integral) and not isinstance(v, bool) for v in pair):
+            raise ValueError(f"resample must be (up, down) or an output rate in Hz as an int, not {resample!r}")
+    up, down = int(pair[0]), int(pair[1])
+    if up < 1 or down < 1:
+        raise ValueError(f"resample must be positive, not {resample!r}")
+    g = math.gcd(up, down)
+    up, down = up // g, down // g
+    if not (up <= 160 and up < down <= min(8 * up, 640)):
+        raise ValueError(f"resample {resample!r} is {up}/{down}: outside 1 <= up <= 160, up < down <= min(8 up, 640)")
+    return up, down
+
+
+def resample_ratio_taps(up, down):
+    """opusgpu_resample_ratio_taps: the Q15 taps of up / down as an int16 array of 24 down' + 1, down' the reduced down."""
+    p = C.c_void_p()
+    n = load_lib().opusgpu_resample_ratio_taps(int(up), int(down), C.byref(p))
+    if n < 0:
+        raise ValueError(f"no taps for the ratio {up!r}/{down!r}")
+    return np.ctypeslib.as_array((C.c_int16 * n).from_address(p.value)).copy()
+
+
+def resample_ratio_layout(planned_samples, up, down):
+    """opusgpu_resample_ratio_layout: the grid of the tracks at up / down -> (out_offsets [int64], total samples per channel)."""
+    planned = np.ascontiguousarray(planned_samples, dtype=np.int64)
+    offsets = np.zeros(planned.size, dtype=np.int64)
+    total = load_lib().opusgpu_resample_ratio_layout(planned.size, planned.ctypes.data, int(up), int(down), offsets.ctypes.data)
+    if total < 0:
+        raise ValueError(f"opusgpu_resample_ratio_layout refused the ratio {up!r}/{down!r} or a negative length")
+    return offsets, int(total)
+
+
+def track_ratio_args(batch, resample, mono=False, mix=None, format="s16", out=None, device=0, allow_mono=True, rate=None, features=None):
+    """What decode_files makes of its resample= for a planned batch, before any device work: ((up, down) reduced, output channels,
+    out_offsets, total samples per channel, out flattened or None, the matrix record or None).  Raises ValueError for what
+    track_ratio and mix_matrix refuse, resample= together with a rate= (other than None) or with features=, mono together with a mix,
+    mono with more than 2 channels (or where there is no mono: allow_mono False), a format that does not exist, and an `out` that
+    does not fit the RESAMPLED tracks: total * output channels elements, otherwise as track_format_args says."""
+    if rate is not None:
+        raise ValueError("resample= and rate= exclude each other")
+    if features is not None:
+        raise ValueError("features are made of the track at 16000 Hz: there is no resample= with them")
+    up, down = track_ratio(resample)
+    if mono and not allow_mono:
+        raise ValueError("there is no mono downmix of multistream tracks: use mix='mono'")
+    if mix is not None and mono:
+        raise ValueError("mix and mono=True exclude each other: the row {8192, 8192} is mono")
+    rec = None if mix is None else mix_matrix(mix, batch.channels)
+    if mono and batch.channels > 2:
+        raise ValueError(f"mono needs 1 or 2 channels, not {batch.channels}")
+    if format not in TRACK_FORMATS:
+        raise ValueError(f"format must be one of {sorted(TRACK_FORMATS)}, not {format!r}")
+    ch_out = int(rec["out_channels"][0]) if rec is not None else 1 if mono else batch.channels
+    offsets, total = resample_ratio_layout(batch.info["track_samples"], up, down)
+    if out is not None:
+        out = _out_flat(out, max(total, 1) * ch_out, format, device)
+    return (up, down), ch_out, offsets, total, out, rec
+
+
 def downmix_matrix(channels, out_channels):
     """opusgpu_downmix_matrix: the default table that takes `channels` (1 - 8, Vorbis order) to 2 or 1 -> int16 [out, in], Q14."""
     rec = np.zeros(1, dtype=MIX_MATRIX_DTYPE)
@@ -830,10 +909,12 @@ def _decode_planned(lib, chk, name, handle, batch, mem, args):
 
 def _decode_planned_resampled(chk, name, call, batch, mem, args, rargs):
     """_decode_planned for resampled tracks: call(fmt, scale pointer, d_out, four array pointers) runs the decode call `name`;
-    args: what track_format_args returned for out=None, rargs: what track_rate_args returned.  -> (tracks, info): tracks of
-    [ceil(len / D), output channels] (planar: [output channels, ceil(len / D)]), info with `out_samples` and `out_offset` more."""
+    args: what track_format_args returned for out=None, rargs: what track_rate_args returned, or the first five of track_ratio_args
+    (a pair (up, down) in place of D).  -> (tracks, info): tracks of [ceil(len / D), output channels] (planar: [output channels,
+    ceil(len / D)]), info with `out_samples` and `out_offset` more."""
     fmt, scale, _ = args
     D, ch, offsets, total, out = rargs
+    up, D = D if isinstance(D, tuple) else (1, D)
     n = batch.n_files
     out_offsets, out_lengths, lengths = (np.zeros(n, dtype=np.int64) for _ in range(3))
     status = np.zeros((n, 2), dtype=np.int32)
@@ -862,7 +943,7 @@ def _decode_planned_resampled(chk, name, call, batch, mem, args, rargs):
     info["track_samples"], info["final_status"], info["bad_packet"] = lengths, status[:, 0], status[:, 1]
     info["out_samples"], info["out_offset"] = out_lengths, out_offsets
     if fmt == TRACKS_F32_PLANAR:
-        planes = ((batch.info["track_samples"] + D - 1) // D + 63) // 64 * 64
+        planes = ((batch.info["track_samples"] * up + D - 1) // D + 63) // 64 * 64
         tracks = [packed[ch * o:ch * (o + p)].reshape(ch, p)[:, :ln] for o, p, ln in zip(out_offsets, planes, out_lengths)]
     else:
         tracks = [packed[ch * o:ch * (o + ln)].reshape(ln, ch) for o, ln in zip(out_offsets, out_lengths)]
@@ -1053,6 +1134,15 @@ class Context:
         self._chk(self.lib.opusgpu_tracks_resample_mixed_device(self.h, spans.size, spans.ctypes.data, d_in, channels, int(rate),
                                                                 rec.ctypes.data, format, d_out, stream), "opusgpu_tracks_resample_mixed_device")
 
+    def tracks_resample_ratio_device(self, spans, d_in, channels, up, down, mono, mix, format, d_out, stream=None):
+        """k_tracks_resample_ratio alone (include/opusgpu.h TRACK RATIOS): as tracks_resample_device with up / down in place of the
+        rate; mix: None, or what tracks_resample_mixed_device takes.  Waits for the kernel."""
+        spans = np.ascontiguousarray(spans, dtype=RESAMPLE_SPAN_DTYPE)
+        rec = None if mix is None else np.ascontiguousarray(mix if getattr(mix, "dtype", None) == MIX_MATRIX_DTYPE else mix_matrix(mix, channels))
+        self._chk(self.lib.opusgpu_tracks_resample_ratio_device(self.h, spans.size, spans.ctypes.data, d_in, channels, int(up), int(down),
+                                                                1 if mono else 0, None if rec is None else rec.ctypes.data, format, d_out,
+                                                                stream), "opusgpu_tracks_resample_ratio_device")
+
     def tracks_mel_device(self, spans, d_in, n_mels, feature_layout, d_out, stream=None):
         """k_tracks_mel alone (include/opusgpu.h TRACK FEATURES): spans a HOST array of MEL_SPAN_DTYPE, d_in packed int16 mono tracks
         at 16 kHz, d_out the float32 feature tracks; feature_layout "bands" or "frames" (or a MEL_PARAMS_DTYPE record in place of
@@ -1063,7 +1153,7 @@ class Context:
                   "opusgpu_tracks_mel_device")
 
     def decode_files(self, files, rfc=False, flags=PAGES_GROUP_BY_MODE, threads=1, batch=None, format=None, scale=None, out=None,
-                     rate=None, mono=False, mix=None, features=None, n_mels=80, feature_layout="bands"):
+                     rate=None, mono=False, mix=None, features=None, n_mels=80, feature_layout="bands", resample=None):
         """Whole Ogg Opus files -> (list of int16 arrays [samples, channels], one trimmed track per file, info).  The context's
         streams 0 .. len(files) - 1 are (re)allocated when there are too few and get fresh state; its mode is set to `rfc`.
         info: FILE_INFO_DTYPE records with two more fields: `final_status` (the first failed frame's code, else the plan's status)
@@ -1088,7 +1178,13 @@ class Context:
         any format but "f32" (track_feature_args).  The result is a list of float32 arrays [n_mels, F] (feature_layout "bands") or
         [F, n_mels] ("frames"), F = ceil(len / 3) // 160, or views of `out` (mel_layout's total floats); info has `feat_offset` more
         and its `frames` is F (the plan's count of Opus frames stays in batch.info["frames"]).  Whisper's clip-wide max - 8 clamp
-        and (x + 4) / 4 are not applied: they are two torch operations on the result."""
+        and (x + 4) / 4 are not applied: they are two torch operations on the result.
+        resample: None, or (up, down) as for scipy.signal.resample_poly, or an output rate in Hz as an int, which is reduced against
+        48000 -- 44100 is (147, 160), 32000 is (2, 3), 22050 is (147, 320) -- for tracks at 48000 up / down Hz by a rational FIR on
+        the GPU (include/opusgpu.h TRACK RATIOS: integer arithmetic over the int16 track, bit-exact; track_ratio says which ratios
+        there are).  mono, mix, format, scale and out act as with rate=: the tracks are [ceil(len up / down), output channels],
+        `out` is sized for them (track_ratio_args) and info has `out_samples` and `out_offset` more.  Not together with rate= or
+        features=."""
         if mix is not None and mono:
             raise ValueError("mix and mono=True exclude each other: the row {8192, 8192} is mono")
         own = batch is None
@@ -1096,6 +1192,18 @@ class Context:
         if own:
             batch = FileBatch(files, channels=channels, rfc=rfc, flags=flags, threads=threads)
         try:
+            if resample is not None:
+                format = "s16" if format is None else format
+                qargs = track_ratio_args(batch, resample, mono, mix, format, out, self.device, rate=rate, features=features)
+                args = track_format_args(batch, format, scale, None, self.device)
+                if self.n_streams < batch.n_files or self.channels != batch.channels:
+                    self.streams_alloc(max(batch.n_files, 1), batch.channels)
+                self.set_mode(batch.rfc)
+
+                def call(fmt, scale_p, d_out, *arrays):
+                    return self.lib.opusgpu_files_decode_ratio(self.h, batch.h, qargs[0][0], qargs[0][1], 1 if mono else 0,
+                                                               None if qargs[5] is None else qargs[5].ctypes.data, fmt, scale_p, d_out, *arrays)
+                return _decode_planned_resampled(self._chk, "opusgpu_files_decode_ratio", call, batch, self, args, qargs[:5])
             fargs = track_feature_args(batch, features, n_mels, feature_layout, rate, mono, mix, format, scale, out, self.device)
             rate, format = 48000 if rate is None else rate, "s16" if format is None else format
             if fargs is not None:
@@ -1289,19 +1397,31 @@ class MultistreamContext:
                   "opusgpu_ms_tracks_assemble_device_as")
 
     def decode_files(self, files, rfc=False, threads=1, batch=None, format=None, scale=None, out=None, rate=None, mix=None, features=None,
-                     n_mels=80, feature_layout="bands"):
+                     n_mels=80, feature_layout="bands", resample=None):
         """Whole Ogg Opus files of this object's layout -> (list of int16 arrays [samples, channels], one trimmed track per file,
         info), as Context.decode_files returns them: FILE_INFO_DTYPE records plus `final_status` and `bad_packet`, `track_samples`
         the FINAL length.  Decoders 0 .. len(files) - 1 get fresh state; the object's mode is set to the batch's.  batch: an
         MsFileBatch made beforehand from the same files (of this layout; `rfc` is then the batch's).  format, scale, out, rate: as
         for Context.decode_files, all channels at `rate`.  mix: as for Context.decode_files -- "mono" and "stereo" are the default
         downmix tables of the layout's channel count; there is no `mono` argument here.
-        features, n_mels, feature_layout: as for Context.decode_files, with mix="mono" or a matrix of one row."""
+        features, n_mels, feature_layout: as for Context.decode_files, with mix="mono" or a matrix of one row.
+        resample: as for Context.decode_files, all channels or those of the mix."""
         own = batch is None
         if own:
             batch = MsFileBatch(files, self.layout, rfc=rfc, threads=threads)
         mem = None
         try:
+            if resample is not None:
+                format = "s16" if format is None else format
+                qargs = track_ratio_args(batch, resample, False, mix, format, out, self.device, allow_mono=False, rate=rate, features=features)
+                args = track_format_args(batch, format, scale, None, self.device)
+                mem = Context(self.device)
+                self.set_mode(batch.rfc)
+
+                def call(fmt, scale_p, d_out, *arrays):
+                    return self.lib.opusgpu_ms_files_decode_ratio(self.h, batch.h, qargs[0][0], qargs[0][1],
+                                                                  None if qargs[5] is None else qargs[5].ctypes.data, fmt, scale_p, d_out, *arrays)
+                return _decode_planned_resampled(self._chk, "opusgpu_ms_files_decode_ratio", call, batch, mem, args, qargs[:5])
             fargs = track_feature_args(batch, features, n_mels, feature_layout, rate, False, mix, format, scale, out, self.device, allow_mono=False)
             rate, format = 48000 if rate is None else rate, "s16" if format is None else format
             if fargs is not None:

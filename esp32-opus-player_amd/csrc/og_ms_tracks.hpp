@@ -1,7 +1,7 @@
 // og_ms_tracks.hpp -- whole multistream files (include/opusgpu.h, WHOLE FILES / MULTISTREAM): the kernel that maps channels and
 // assembles tracks in one pass, and what the driver of a planned batch (og_files_run.hpp) needs of an opusgpu_ms.  Included at the
-// end of og_api.hip behind og_ms.hpp (opusgpu_ms, ms_step_impl), og_tracks.hpp (TrackSeg, TrackState), og_tracks_resample.hpp and
-// og_tracks_mel.hpp.
+// end of og_api.hip behind og_ms.hpp (opusgpu_ms, ms_step_impl), og_tracks.hpp (TrackSeg, TrackState), og_tracks_resample.hpp,
+// og_tracks_resample_ratio.hpp and og_tracks_mel.hpp.
 #pragma once
 
 // ---- kernel -------------------------------------------------------------------------------------------
@@ -476,6 +476,20 @@ int opusgpu_ms_files_decode_mixed(opusgpu_ms *ms, const opusgpu_ms_file_batch *b
             return ms_files_decode_run(ms, batch, OPUSGPU_TRACKS_S16, nullptr, d_s16, lengths, status);
         },
         [&](int code, const char *what, hipError_t e) { return ms_fail(ms, code, what, e); }, mix);
+}
+
+// opusgpu_files_decode_ratio behind opusgpu_ms_files_decode (og_tracks_resample_ratio.hpp): the layout's channels, through *mix if
+// there is one, at up / down of 48 kHz.
+int opusgpu_ms_files_decode_ratio(opusgpu_ms *ms, const opusgpu_ms_file_batch *batch, int up, int down, const opusgpu_mix_matrix *mix,
+                                  int format, const float *scale, void *d_out, int64_t *out_offsets, int64_t *out_lengths,
+                                  int64_t *track_lengths_out, int32_t *status_out) {
+    if (!ms || !batch) return OPUSGPU_BAD_ARG;
+    return files_ratio_run(
+        *batch, ms->device, ms->stream, up, down, 0, mix, format, scale, d_out, out_offsets, out_lengths, track_lengths_out, status_out,
+        [&](void *d_s16, int64_t *lengths, int32_t *status) {
+            return ms_files_decode_run(ms, batch, OPUSGPU_TRACKS_S16, nullptr, d_s16, lengths, status);
+        },
+        [&](int code, const char *what, hipError_t e) { return ms_fail(ms, code, what, e); });
 }
 
 // opusgpu_files_decode_mel behind opusgpu_ms_files_decode (og_tracks_mel.hpp): the layout's channels through a one-row *mix.

@@ -140,6 +140,51 @@ __device__ __forceinline__ void rs_store(const i16 *yo, const ResampleSpan &sp, 
     }
 }
 
+// Step 1 of k_tracks_resample<D>, and of k_tracks_resample_ratio without a mix: the window of Wn samples from sample n0 of the track
+// (negative at a track's head), all C channels or their mono downmix -> put(channel, sample in the window, value), which says where
+// in LDS it goes.
+template <class Put>
+__device__ __forceinline__ void rs_stage(const i16 *__restrict__ in, const ResampleSpan &sp, int C, bool mono, long long n0, int Wn, int tid,
+                                         Put put) {
+    const int W = Wn * C;                                 // the window's elements, all input channels
+    const long long G0 = (sp.in_offset + n0) * C;         // its first element in the buffer
+    const int mis = (int)(G0 & 7);                        // elements between the aligned piece's first and it
+    const long long V0 = sp.in_offset * C, V1 = (sp.in_offset + sp.in_samples) * C; // the track's elements; V0 is a multiple of 8
+    const int pieces = (W + mis + 7) >> 3;
+    const bool mix = mono && C == 2;
+    for (int k = tid; k < pieces; k += 256) {
+        const long long g = G0 - mis + 8LL * k;
+        uint4 v = make_uint4(0, 0, 0, 0);
+        if (g >= V0 && g < V1) v = *reinterpret_cast<const uint4 *>(in + g);
+        const u32 w32[4] = {v.x, v.y, v.z, v.w};
+        const int w = 8 * k - mis;        // the piece's first window element (-7 .. -1 possible in piece 0)
+        int rel = (w + 8 * C) / C - 8;    // its sample in the window (floor) and channel
+        int ch = w - rel * C;
+        if (mix) { // pairs never straddle pieces: G0 is even
+#pragma unroll
+            for (int h = 0; h < 8; h += 2) {
+                if (w + h >= 0 && w + h < W) {
+                    const int r = rel + (h >> 1);
+                    const long long n = n0 + r;
+                    const u32 lr = w32[h >> 1];
+                    const int m = n >= 0 && n < sp.in_samples ? ((int)(i16)lr + (int)(i16)(lr >> 16) + 1) >> 1 : 0;
+                    put(0, r, (i16)m);
+                }
+            }
+        } else {
+#pragma unroll
+            for (int h = 0; h < 8; h++) {
+                if (w + h >= 0 && w + h < W) {
+                    const long long n = n0 + rel;
+                    const i16 s = n >= 0 && n < sp.in_samples ? (i16)(w32[h >> 1] >> (16 * (h & 1))) : (i16)0;
+                    put(ch, rel, s);
+                }
+                if (++ch == C) ch = 0, rel++;
+            }
+        }
+    }
+}
+
 template <int D>
 __global__ void __launch_bounds__(256) k_tracks_resample(const ResampleTile *__restrict__ tiles, const ResampleSpan *__restrict__ spans,
                                                           const i16 *__restrict__ in, int C, int mono, int format, int tile_shift,
@@ -158,47 +203,9 @@ __global__ void __launch_bounds__(256) k_tracks_resample(const ResampleTile *__r
     i16 *const yo = D == 1 ? lds : lds + CO * D * Q;
     const bool planar = format == OPUSGPU_TRACKS_F32_PLANAR;
 
-    // 1. the window -> LDS
-    {
-        const long long n0 = (tl.first - LEAD) * D;           // the window's first input sample; negative at a track's head
-        const int W = (n_out + 2 * LEAD) * D * C;             // its elements, all input channels
-        const long long G0 = (sp.in_offset + n0) * C;         // its first element in the buffer
-        const int mis = (int)(G0 & 7);                        // elements between the aligned piece's first and it
-        const long long V0 = sp.in_offset * C, V1 = (sp.in_offset + sp.in_samples) * C; // the track's elements; V0 is a multiple of 8
-        const int pieces = (W + mis + 7) >> 3;
-        const bool mix = mono && C == 2;
-        for (int k = tid; k < pieces; k += 256) {
-            const long long g = G0 - mis + 8LL * k;
-            uint4 v = make_uint4(0, 0, 0, 0);
-            if (g >= V0 && g < V1) v = *reinterpret_cast<const uint4 *>(in + g);
-            const u32 w32[4] = {v.x, v.y, v.z, v.w};
-            const int w = 8 * k - mis;        // the piece's first window element (-7 .. -1 possible in piece 0)
-            int rel = (w + 8 * C) / C - 8;    // its sample in the window (floor) and channel
-            int ch = w - rel * C;
-            if (mix) { // pairs never straddle pieces: G0 is even
-#pragma unroll
-                for (int h = 0; h < 8; h += 2) {
-                    if (w + h >= 0 && w + h < W) {
-                        const int r = rel + (h >> 1);
-                        const long long n = n0 + r;
-                        const u32 lr = w32[h >> 1];
-                        const int m = n >= 0 && n < sp.in_samples ? ((int)(i16)lr + (int)(i16)(lr >> 16) + 1) >> 1 : 0;
-                        lds[(r % D) * Q + r / D] = (i16)m;
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int h = 0; h < 8; h++) {
-                    if (w + h >= 0 && w + h < W) {
-                        const long long n = n0 + rel;
-                        const i16 s = n >= 0 && n < sp.in_samples ? (i16)(w32[h >> 1] >> (16 * (h & 1))) : (i16)0;
-                        lds[(ch * D + rel % D) * Q + rel / D] = s;
-                    }
-                    if (++ch == C) ch = 0, rel++;
-                }
-            }
-        }
-    }
+    // 1. the window -> LDS: sample r of channel ch at place r / D of plane (ch, r % D)
+    rs_stage(in, sp, C, mono != 0, (tl.first - LEAD) * D, (n_out + 2 * LEAD) * D, tid,
+             [=](int ch, int r, i16 s) { lds[(ch * D + r % D) * Q + r / D] = s; });
     __syncthreads();
 
     rs_mac<D>(lds, yo, CO, tile_shift, n_out, planar, tid);          // 2. four outputs per lane
@@ -223,9 +230,11 @@ struct RsMixArgs {
     u32 pair[8][9];
 };
 
-template <int D, int C>
-__device__ __forceinline__ void rs_stage_mix(i16 *lds, const i16 *__restrict__ in, const ResampleSpan &sp, const RsMixArgs &mx, long long n0,
-                                             int Wn, int Q, int tile, bool planar, int tid) {
+// at_of(sample in the window) says where a sample goes within an output channel's area, put(o, that place, value) stores it:
+// k_tracks_resample_ratio stages its own layout through the same body.
+template <int C, class At, class Put>
+__device__ __forceinline__ void rs_stage_mix_at(const i16 *__restrict__ in, const ResampleSpan &sp, const RsMixArgs &mx, long long n0, int Wn,
+                                                int tid, At at_of, Put put) {
     const int CO = mx.co;
     const long long a0 = n0 & ~7LL;  // the group of 8 that holds the window's first sample (floor, also in front of the track)
     const int lead = (int)(n0 - a0); // samples of it in front of the window
@@ -242,11 +251,11 @@ __device__ __forceinline__ void rs_stage_mix(i16 *lds, const i16 *__restrict__ i
             w[4 * j] = v.x, w[4 * j + 1] = v.y, w[4 * j + 2] = v.z, w[4 * j + 3] = v.w;
         }
         const int r0 = 8 * k - lead; // the lane's first sample in the window (-7 .. -1 possible in group 0)
-        int at[8];                   // where sample s goes in the planes of channel 0, -1: outside the window
+        int at[8];                   // where sample s goes in the area of channel 0, -1: outside the window
 #pragma unroll
         for (int s = 0; s < 8; s++) {
             const int r = r0 + s;
-            at[s] = r < 0 || r >= Wn ? -1 : D == 1 ? r : (r % D) * Q + r / D;
+            at[s] = r < 0 || r >= Wn ? -1 : at_of(r);
         }
         for (int o = 0; o < CO; o++) {
 #pragma unroll
@@ -257,10 +266,19 @@ __device__ __forceinline__ void rs_stage_mix(i16 *lds, const i16 *__restrict__ i
                 acc >>= 14;
                 const long long n = nb + s;
                 const i16 x = n >= 0 && n < sp.in_samples ? (i16)(acc < -32768 ? -32768 : acc > 32767 ? 32767 : acc) : (i16)0;
-                if (at[s] >= 0) lds[D == 1 ? (planar ? o * tile + at[s] : at[s] * CO + o) : o * D * Q + at[s]] = x;
+                if (at[s] >= 0) put(o, at[s], x);
             }
         }
     }
+}
+
+template <int D, int C>
+__device__ __forceinline__ void rs_stage_mix(i16 *lds, const i16 *__restrict__ in, const ResampleSpan &sp, const RsMixArgs &mx, long long n0,
+                                             int Wn, int Q, int tile, bool planar, int tid) {
+    const int CO = mx.co;
+    rs_stage_mix_at<C>(
+        in, sp, mx, n0, Wn, tid, [=](int r) { return D == 1 ? r : (r % D) * Q + r / D; },
+        [=](int o, int at, i16 x) { lds[D == 1 ? (planar ? o * tile + at : at * CO + o) : o * D * Q + at] = x; });
 }
 
 template <int D>
@@ -363,6 +381,26 @@ struct RsDevBuf {
     }
 };
 
+// A tile's outputs per channel, as a shift: 1,024 outputs of one channel .. 256 of eight, four per lane of k_tracks_resample.
+static int rs_tile_shift(int CO) { return CO == 1 ? 10 : CO == 2 ? 9 : 8; }
+// The spans held against the rules of opusgpu_resample_span for tracks of ceil(in_samples * up / down) outputs (TRACK RATES: up 1,
+// down D), and the tile table of their outputs; false: a span breaks a rule, or there are more tiles than a grid takes.
+static bool rs_tiles(int n_tracks, const opusgpu_resample_span *spans, int up, int down, int tile_shift, int format,
+                     std::vector<ResampleTile> &tiles) {
+    const int64_t tile = (int64_t)1 << tile_shift;
+    for (int t = 0; t < n_tracks; t++) {
+        const opusgpu_resample_span &sp = spans[t];
+        if (sp.in_offset < 0 || sp.in_offset % 8 || sp.in_samples < 0 || sp.out_offset < 0 || sp.out_offset % 64) return false;
+        if (sp.in_samples > INT64_MAX / 256) return false; // in_samples * up stays an int64
+        const int64_t out_len = (sp.in_samples * up + down - 1) / down;
+        if (format == OPUSGPU_TRACKS_F32_PLANAR && (sp.out_plane % 64 || sp.out_plane < out_len)) return false;
+        if (format != OPUSGPU_TRACKS_S16 && !std::isfinite(sp.scale)) return false;
+        if ((out_len + tile - 1) / tile + (int64_t)tiles.size() > 0x7fffffff) return false;
+        for (int64_t m = 0; m < out_len; m += tile) tiles.push_back(ResampleTile{t, 0, m});
+    }
+    return true;
+}
+
 // The kernel over n tracks: checks the spans, builds the tile table, uploads both, launches on `s` and waits.
 // hip_failed(code, what, e) keeps the message of the object the call belongs to and returns `code`.
 template <class Fail>
@@ -371,18 +409,10 @@ static int tracks_resample_run(int device, hipStream_t s, int n_tracks, const op
     const int D = rs_args_factor(channels, rate, mono, format, mix);
     if (!D || n_tracks < 0 || (n_tracks && !spans)) return OPUSGPU_BAD_ARG;
     const int CO = mix ? mix->out_channels : mono ? 1 : channels;
-    const int tile_shift = CO == 1 ? 10 : CO == 2 ? 9 : 8; // 1,024 outputs of one channel .. 256 of eight: four per lane
-    const int64_t tile = (int64_t)1 << tile_shift;
+    const int tile_shift = rs_tile_shift(CO);
     std::vector<ResampleTile> tiles;
-    for (int t = 0; t < n_tracks; t++) {
-        const opusgpu_resample_span &sp = spans[t];
-        if (sp.in_offset < 0 || sp.in_offset % 8 || sp.in_samples < 0 || sp.out_offset < 0 || sp.out_offset % 64) return OPUSGPU_BAD_ARG;
-        const int64_t out_len = (sp.in_samples + D - 1) / D;
-        if (format == OPUSGPU_TRACKS_F32_PLANAR && (sp.out_plane % 64 || sp.out_plane < out_len)) return OPUSGPU_BAD_ARG;
-        if (format != OPUSGPU_TRACKS_S16 && !std::isfinite(sp.scale)) return OPUSGPU_BAD_ARG;
-        if ((out_len + tile - 1) / tile + (int64_t)tiles.size() > 0x7fffffff) return OPUSGPU_BAD_ARG;
-        for (int64_t m = 0; m < out_len; m += tile) tiles.push_back(ResampleTile{t, 0, m});
-    }
+    if (!rs_tiles(n_tracks, spans, 1, D, tile_shift, format, tiles)) return OPUSGPU_BAD_ARG;
+    const int64_t tile = (int64_t)1 << tile_shift;
     if (tiles.empty()) return OPUSGPU_OK;
     if (!d_in || !d_out || ((uintptr_t)d_in & 15) || ((uintptr_t)d_out & 127)) return OPUSGPU_BAD_ARG;
 #define RS_CHK(call)                                                              \
@@ -422,28 +452,29 @@ static int tracks_resample_run(int device, hipStream_t s, int n_tracks, const op
     return OPUSGPU_OK;
 }
 
-// The spans of a planned batch whose S16 tracks have been decoded: final lengths in, the resampled grid out.
-static void rs_batch_spans(const og_batch &b, int D, const int64_t *final_lengths, const float *scale, std::vector<int64_t> &out_offsets,
-                           std::vector<opusgpu_resample_span> &spans) {
+// The spans of a planned batch whose S16 tracks have been decoded: final lengths in, the grid of the tracks at up / down of their
+// rate out (TRACK RATES: up 1, down D).
+static void rs_batch_spans(const og_batch &b, int up, int down, const int64_t *final_lengths, const float *scale,
+                           std::vector<int64_t> &out_offsets, std::vector<opusgpu_resample_span> &spans) {
     const size_t n = (size_t)b.n_files;
     out_offsets.resize(n);
     spans.resize(n);
     int64_t at = 0;
     for (size_t i = 0; i < n; i++) {
-        const int64_t plane = rs_round64((b.info[i].track_samples + D - 1) / D);
+        const int64_t plane = rs_round64((b.info[i].track_samples * up + down - 1) / down);
         out_offsets[i] = at;
         spans[i] = opusgpu_resample_span{b.info[i].track_offset, final_lengths[i], at, plane, scale ? scale[i] : 1.0f / 32768, 0};
         at += plane;
     }
 }
 
-// What both whole-file calls do around their decoder: `decode(d_s16, lengths, status)` runs the batch into the scratch S16 tracks.
-template <class Decode, class Fail>
-static int files_resampled_run(const og_batch &b, int device, hipStream_t s, int rate, int mono, int format, const float *scale, void *d_out,
-                               int64_t *out_offsets, int64_t *out_lengths, int64_t *track_lengths_out, int32_t *status_out, Decode decode,
-                               Fail hip_failed, const opusgpu_mix_matrix *mix = nullptr) {
-    const int D = rs_args_factor(b.channels, rate, mono, format, mix);
-    if (!D || !rs_scale_ok(format, scale, b.n_files)) return OPUSGPU_BAD_ARG;
+// What every whole-file call that ends in a resampling kernel does around its decoder, its arguments checked by the caller:
+// `decode(d_s16, lengths, status)` runs the batch into the scratch S16 tracks, `run(n, spans, d_s16)` the kernel that makes tracks
+// at up / down of their rate from them.
+template <class Decode, class Run, class Fail>
+static int files_resampled_to(const og_batch &b, int device, int up, int down, int format, const float *scale, int64_t *out_offsets,
+                              int64_t *out_lengths, int64_t *track_lengths_out, int32_t *status_out, Decode decode, Run run, Fail hip_failed) {
+    if (!rs_scale_ok(format, scale, b.n_files)) return OPUSGPU_BAD_ARG;
     const size_t n = (size_t)b.n_files;
     std::vector<int64_t> lengths(n, 0), offsets;
     std::vector<int32_t> status(2 * n, 0);
@@ -455,16 +486,30 @@ static int files_resampled_run(const og_batch &b, int device, hipStream_t s, int
         if (e != hipSuccess) return hip_failed(OPUSGPU_ALLOC_FAIL, "hipMalloc(resample scratch)", e);
     }
     if (int rc = decode(s16.p, lengths.data(), status.data())) return rc;
-    rs_batch_spans(b, D, lengths.data(), scale, offsets, spans);
-    if (int rc = tracks_resample_run(device, s, b.n_files, spans.data(), s16.p, b.channels, rate, mono, format, d_out, hip_failed, mix))
-        return rc;
+    rs_batch_spans(b, up, down, lengths.data(), scale, offsets, spans);
+    if (int rc = run(b.n_files, spans.data(), s16.p)) return rc;
     for (size_t i = 0; i < n; i++) {
         if (out_offsets) out_offsets[i] = offsets[i];
-        if (out_lengths) out_lengths[i] = (lengths[i] + D - 1) / D;
+        if (out_lengths) out_lengths[i] = (lengths[i] * up + down - 1) / down;
         if (track_lengths_out) track_lengths_out[i] = lengths[i];
     }
     if (status_out) std::copy(status.begin(), status.end(), status_out);
     return OPUSGPU_OK;
+}
+
+// files_resampled_to for the rates of TRACK RATES, behind a mono downmix or a channel mix.
+template <class Decode, class Fail>
+static int files_resampled_run(const og_batch &b, int device, hipStream_t s, int rate, int mono, int format, const float *scale, void *d_out,
+                               int64_t *out_offsets, int64_t *out_lengths, int64_t *track_lengths_out, int32_t *status_out, Decode decode,
+                               Fail hip_failed, const opusgpu_mix_matrix *mix = nullptr) {
+    const int D = rs_args_factor(b.channels, rate, mono, format, mix);
+    if (!D) return OPUSGPU_BAD_ARG;
+    return files_resampled_to(
+        b, device, 1, D, format, scale, out_offsets, out_lengths, track_lengths_out, status_out, decode,
+        [&](int n, const opusgpu_resample_span *spans, const void *d_s16) {
+            return tracks_resample_run(device, s, n, spans, d_s16, b.channels, rate, mono, format, d_out, hip_failed, mix);
+        },
+        hip_failed);
 }
 
 extern "C" {

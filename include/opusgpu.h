@@ -721,6 +721,61 @@ int opusgpu_files_decode_mixed(opusgpu_ctx *ctx, const opusgpu_file_batch *batch
                                const float *scale, void *d_out, int64_t *out_offsets, int64_t *out_lengths, int64_t *track_lengths_out,
                                int32_t *status_out);
 
+/* TRACK RATIOS.  Tracks at 48000 * up / down Hz by a rational polyphase FIR, for the rates that do not divide 48000: 44100 is
+ * 147 / 160, 32000 is 2 / 3, 22050 is 147 / 320.  The arguments are those of scipy.signal.resample_poly(x, up, down).  Like TRACK
+ * RATES the result is a pure function of the S16 track, bit for bit, in exact integer arithmetic.  TRACK RATES, its taps and its
+ * refusals (rate 44100, rate 32000) are unchanged: this is a section of its own with calls of its own.
+ *   RATIO.  up and down are divided by their gcd first.  The reduced pair must keep 1 <= up <= 160 and up < down <=
+ *   min(8 * up, 640); everything else is OPUSGPU_BAD_ARG before any device work.  147/160, 2/3, 147/320 and 147/640 are inside, and so
+ *   are the plain 1 / D, which go through THIS filter with THIS section's taps -- 1 / 2 is not promised to equal rate 24000.
+ *   VALUE.  Let x[n] be the int16 track after `mono` or the mix, exactly as TRACK RATES and CHANNEL MIX define it (`mono`: (l + r +
+ *   1) >> 1 of a stereo track; a mix: sat16((sum_c M[o][c] * s_c[n] + 8192) >> 14)), x[n] = 0 for n < 0 and for n >= the track's
+ *   FINAL length len.  With Lp = 24 * down + 1 and c = 12 * down, output sample m of each channel, for m in [0, ceil(len * up /
+ *   down)), is
+ *       y[m] = sat16((sum_n h[m * down + c - n * up] * x[n] + 16384) >> 15),
+ *   the sum over those n whose tap index m * down + c - n * up lies in [0, Lp), >> arithmetic, the sum exact in int32, sat16 a
+ *   clamp to [-32768, 32767]: a filter on the 48000 * up grid of which every output takes one phase, the taps h[p], h[p + up], ...
+ *   with p = (m * down + c) mod up.  The float formats follow TRACK FORMATS: (float)y * scale[track], one IEEE multiply.
+ *   TAPS.  h is an int16 table of Lp entries in Q15, built in double at first use, kept per reduced (up, down) for the life of the
+ *   process, safe to ask for from any number of threads.  The prototype is TRACK RATES' design moved to the fine grid,
+ *       g[i] = fc * sinc(fc * (i - c)) * I0(8 * sqrt(1 - ((i - c) / c)^2)) / I0(8),   fc = 0.92 / down,  sinc(t) = sin(pi t) / (pi t):
+ *   a Kaiser window of beta 8 over a low-pass at 0.92 of the OUTPUT's Nyquist.  Each of the up phases g[p], g[p + up], ... is
+ *   scaled to sum 32768 and rounded to nearest; the phase's largest rounded tap (the first of them when tied) is then corrected so
+ *   that the phase sums to exactly 32768: every phase has a DC gain of exactly 1, a constant track comes back as it is.  The
+ *   builder holds sum |h_phase| <= 65535 for every phase (65535 * 32768 + 16384 < 2^31: the argument that makes TRACK RATES' sum
+ *   exact), and a ratio whose table broke that would be refused like one outside RATIO.  The table is NOT promised to be
+ *   symmetric -- the correction breaks the symmetry for 2 / 3 -- and sin, sqrt and the rounding are the host's: the table that
+ *   opusgpu_resample_ratio_taps hands out is the definition, and tests compute against it.
+ *   LAYOUT.  TRACK RATES' grid with ceil(planned * up / down) in place of ceil(planned / D): out_offset[t] is the running sum of
+ *   roundup64(ceil(planned[u] * up / down)); tracks begin at multiples of 64 samples, the planes of OPUSGPU_TRACKS_F32_PLANAR are
+ *   roundup64(ceil(planned[t] * up / down)) long; padding is never written.  opusgpu_resample_span is reused, its out_plane a
+ *   multiple of 64 and >= ceil(in_samples * up / down).
+ *   ARITHMETIC.  Everything that multiplies a sample index by up or down is 64-bit. */
+/* The taps of up / down: returns Lp = 24 * down' + 1 for the reduced down' and sets *taps (may be NULL) to the table, which stays
+ * valid for the life of the process; OPUSGPU_BAD_ARG for a ratio outside RATIO.  Host only. */
+int opusgpu_resample_ratio_taps(int up, int down, const int16_t **taps);
+/* LAYOUT above for n tracks of planned_samples[i] samples: writes out_offsets[i] (may be NULL) and returns the total in samples per
+ * channel.  Serves both kinds of batch.  OPUSGPU_BAD_ARG for a ratio outside RATIO or a negative length.  Host only. */
+int64_t opusgpu_resample_ratio_layout(int n, const int64_t *planned_samples, int up, int down, int64_t *out_offsets);
+/* k_tracks_resample_ratio alone: opusgpu_tracks_resample_mixed_device's contract and refusals with the ratio in place of the rate
+ * -- d_in packed interleaved int16 tracks of `channels` (1 - 8) channels, 16-byte aligned, read in aligned 16-byte pieces up to the
+ * one that holds a track's last sample; `spans` a HOST array; d_out 128-byte aligned; uploads the spans, the tile table and the tap
+ * rows, launches on the context's stream (or `hip_stream`), waits, frees them on every way out.  mix NULL: no matrix, and `mono` as
+ * in opusgpu_tracks_resample_device (1 or 2 channels) or all channels.  OPUSGPU_BAD_ARG before any device work: a ratio outside
+ * RATIO, an unknown format, `mono` with more than 2 channels, `mono` together with a mix, a matrix that CHANNEL MIX refuses, a span
+ * that breaks the rules, a scale that is not finite with a float format. */
+int opusgpu_tracks_resample_ratio_device(opusgpu_ctx *ctx, int n_tracks, const opusgpu_resample_span *spans, const void *d_in, int channels,
+                                         int up, int down, int mono, const opusgpu_mix_matrix *mix /* NULL: none */, int format, void *d_out,
+                                         void *hip_stream);
+/* opusgpu_files_decode_mixed with the ratio in place of the rate, and `mono` where there is no matrix (mix NULL): the same scratch
+ * S16 buffer, the same decode, LAYOUT above with the output channels as its channel count; out_lengths[i] = ceil(final * up /
+ * down).  OPUSGPU_BAD_ARG before any device work: what opusgpu_tracks_resample_ratio_device refuses of its ratio, format, `mono`
+ * and mix, a scale with OPUSGPU_TRACKS_S16, a scale entry that is not finite.  On a failure the caller's arrays are left as they
+ * were. */
+int opusgpu_files_decode_ratio(opusgpu_ctx *ctx, const opusgpu_file_batch *batch, int up, int down, int mono,
+                               const opusgpu_mix_matrix *mix /* NULL: none */, int format, const float *scale, void *d_out,
+                               int64_t *out_offsets, int64_t *out_lengths, int64_t *track_lengths_out, int32_t *status_out);
+
 /* TRACK FEATURES.  Log-mel features of the mono track at 16 kHz, the front end of Whisper-style speech models, in the same call
  * that decodes the files.  Like the float formats, the rates and the mix, the features are a function of an array that is pinned
  * bit for bit; they are themselves float sums, pinned to a tolerance and to two exact properties (below).
@@ -890,6 +945,11 @@ int opusgpu_ms_files_decode_resampled(opusgpu_ms *ms, const opusgpu_ms_file_batc
 int opusgpu_ms_files_decode_mixed(opusgpu_ms *ms, const opusgpu_ms_file_batch *batch, int rate, const opusgpu_mix_matrix *mix, int format,
                                   const float *scale, void *d_out, int64_t *out_offsets, int64_t *out_lengths, int64_t *track_lengths_out,
                                   int32_t *status_out);
+/* opusgpu_files_decode_ratio behind opusgpu_ms_files_decode (TRACK RATIOS): the layout's channels through *mix, or all of them
+ * with mix NULL, at up / down of 48 kHz.  There is no `mono` here: the row of a mono mix is what it would be. */
+int opusgpu_ms_files_decode_ratio(opusgpu_ms *ms, const opusgpu_ms_file_batch *batch, int up, int down,
+                                  const opusgpu_mix_matrix *mix /* NULL: none */, int format, const float *scale, void *d_out,
+                                  int64_t *out_offsets, int64_t *out_lengths, int64_t *track_lengths_out, int32_t *status_out);
 /* opusgpu_files_decode_mel behind opusgpu_ms_files_decode (TRACK FEATURES): the layout's channels through *mix, which must have
  * out_channels == 1; there is no `mono` here.  Refusals as there, plus a NULL mix. */
 int opusgpu_ms_files_decode_mel(opusgpu_ms *ms, const opusgpu_ms_file_batch *batch, const opusgpu_mix_matrix *mix,

@@ -14,7 +14,10 @@ k_tracks_resample's row as well.
 --mono; `--mix mono` and `--mono` produce the same tracks, so their times show what the general staging costs.
 --mel [--n-mels N]: the fused log-mel call (opusgpu_files_decode_mel, mono) next to float32 16 kHz mono tracks followed by
 torch.stft, the filterbank matmul and log10, and k_tracks_mel's share of the call (tools/mel_rate.py).
-usage (GPU box): python3 tools/files_rate.py [--n N] [--reps R] [--format F | --rate R [--mono | --mix M] | --mel [--n-mels N]] | python3 tools/files_rate.py --stats DIR [--n N]"""
+--resample UP/DOWN [--mono | --mix M]: the fused ratio call (opusgpu_files_decode_ratio, include/opusgpu.h TRACK RATIOS) next to
+rate=24000 on the same corpus and to float32 48 kHz tracks resampled by a polyphase conv1d in torch, interleaved, and the two
+kernels alone per output sample (tools/ratio_rate.py).
+usage (GPU box): python3 tools/files_rate.py [--n N] [--reps R] [--format F | --rate R [--mono | --mix M] | --resample U/D [--mono | --mix M] | --mel [--n-mels N]] | python3 tools/files_rate.py --stats DIR [--n N]"""
 import argparse
 import ctypes as C
 import glob
@@ -40,15 +43,19 @@ ap.add_argument("--rate", type=int, choices=[48000, 24000, 16000, 12000, 8000], 
                 help="compare the whole decode call: int16 tracks, int16 + resampling in torch, the resampled tracks (tools/resample_rate.py)")
 ap.add_argument("--mono", action="store_true")
 ap.add_argument("--mix", choices=["mono", "stereo"], default=None, help="with --rate: the default downmix table as a channel mix")
+ap.add_argument("--resample", default=None, metavar="UP/DOWN",
+                help="compare the fused ratio call with rate=24000 and with 48 kHz float tracks + a polyphase conv1d in torch (tools/ratio_rate.py)")
 ap.add_argument("--mel", action="store_true", help="compare the fused log-mel call with 16 kHz mono float tracks + torch.stft (tools/mel_rate.py)")
 ap.add_argument("--n-mels", type=int, choices=[80, 128], default=80)
 args = ap.parse_args()
-if args.mix and (args.mono or not args.rate):
-    ap.error("--mix goes with --rate and without --mono")
-if args.mel and (args.rate or args.format):
-    ap.error("--mel goes without --rate and --format")
+if args.mix and (args.mono or not (args.rate or args.resample)):
+    ap.error("--mix goes with --rate or --resample and without --mono")
+if args.mel and (args.rate or args.format or args.resample):
+    ap.error("--mel goes without --rate, --resample and --format")
+if args.resample and (args.rate or args.format):
+    ap.error("--resample goes without --rate and --format")
 n = args.n
-if args.format or args.rate or args.mel:
+if args.format or args.rate or args.mel or args.resample:
     import torch  # before the library: one HIP runtime for both
 
 spec = importlib.util.spec_from_file_location("esp32_opus_player_amd", os.path.join(here, "..", "esp32-opus-player_amd", "__init__.py"))
@@ -109,6 +116,40 @@ if args.rate:
         print(json.dumps(resample_rate.compare(
             torch, pkg, lambda d, ln, st: ctx._chk(ctx.lib.opusgpu_files_decode(ctx.h, b.h, d, ln, st), "opusgpu_files_decode"), resampled,
             b, args.rate, args.mono, args.reps, name, mix=pkg.downmix_matrix(2, 1 if args.mix == "mono" else 2) if args.mix else None)))
+    ctx.close()
+    raise SystemExit(0)
+
+if args.resample:
+    import ratio_rate
+    up, down = pkg.track_ratio(tuple(int(v) for v in args.resample.split("/")))
+    b = pkg.FileBatch([r.tobytes() for r in files], channels=2, flags=pkg.PAGES_GROUP_BY_MODE, threads=args.threads)
+    assert (b.info["status"] == 0).all() and b.n_steps == 10
+    ctx = pkg.Context(0)
+    ctx.streams_alloc(n, 2)
+    rec = pkg.mix_matrix(args.mix, 2) if args.mix else None
+    rec_p = None if rec is None else rec.ctypes.data
+
+    def at_24000(fmt, d, oo, ol, ln, st):
+        if rec is not None:
+            return ctx._chk(ctx.lib.opusgpu_files_decode_mixed(ctx.h, b.h, 24000, rec_p, fmt, None, d, oo, ol, ln, st), "opusgpu_files_decode_mixed")
+        return ctx._chk(ctx.lib.opusgpu_files_decode_resampled(ctx.h, b.h, 24000, int(args.mono), fmt, None, d, oo, ol, ln, st),
+                        "opusgpu_files_decode_resampled")
+
+    def at_24000_kernel(spans, d_in, fmt, d_out):
+        if rec is not None:
+            return ctx.tracks_resample_mixed_device(spans, d_in, 2, 24000, rec, fmt, d_out)
+        return ctx.tracks_resample_device(spans, d_in, 2, 24000, args.mono, fmt, d_out)
+    for name, pipe in (("in_order", 0), ("pipelined", 1)):
+        ctx.set_pipeline(pipe)
+        print(json.dumps(ratio_rate.compare(
+            torch, pkg,
+            lambda d, ln, st: ctx._chk(ctx.lib.opusgpu_files_decode_as(ctx.h, b.h, pkg.TRACKS_F32, None, d, ln, st), "opusgpu_files_decode_as"),
+            at_24000,
+            lambda fmt, d, oo, ol, ln, st: ctx._chk(ctx.lib.opusgpu_files_decode_ratio(ctx.h, b.h, up, down, int(args.mono), rec_p, fmt, None, d,
+                                                                                       oo, ol, ln, st), "opusgpu_files_decode_ratio"),
+            lambda d, ln, st: ctx._chk(ctx.lib.opusgpu_files_decode(ctx.h, b.h, d, ln, st), "opusgpu_files_decode"),
+            (lambda spans, d_in, fmt, d_out: ctx.tracks_resample_ratio_device(spans, d_in, 2, up, down, args.mono, rec, fmt, d_out), at_24000_kernel),
+            b, up, down, args.mono, args.reps, name, mix=pkg.downmix_matrix(2, 1 if args.mix == "mono" else 2) if args.mix else None)))
     ctx.close()
     raise SystemExit(0)
 

@@ -16,7 +16,9 @@ ms_rate.py's count per step).
 --rate R --mix mono | stereo: the same through the 5.1 default downmix table (opusgpu_ms_files_decode_mixed).
 --mel [--n-mels N]: the fused log-mel call (opusgpu_ms_files_decode_mel through the default mono downmix) next to float32 16 kHz mono
 tracks followed by torch.stft, the filterbank matmul and log10, and k_tracks_mel's share of the call (tools/mel_rate.py).
-usage (GPU box): python3 tools/ms_files_rate.py [--n N] [--reps R] [--format F | --rate R [--mix M] | --mel [--n-mels N]] | python3 tools/ms_files_rate.py --stats DIR [--n N]"""
+--resample UP/DOWN [--mix M]: the fused ratio call (opusgpu_ms_files_decode_ratio) next to rate=24000 on the same corpus and to
+float32 48 kHz tracks resampled by a polyphase conv1d in torch, and the two kernels alone (tools/ratio_rate.py).
+usage (GPU box): python3 tools/ms_files_rate.py [--n N] [--reps R] [--format F | --rate R [--mix M] | --resample U/D [--mix M] | --mel [--n-mels N]] | python3 tools/ms_files_rate.py --stats DIR [--n N]"""
 import argparse
 import ctypes as C
 import glob
@@ -40,14 +42,18 @@ ap.add_argument("--format", choices=["f32", "f32_planar"], default=None,
 ap.add_argument("--rate", type=int, choices=[24000, 16000, 12000, 8000], default=None,
                 help="compare the whole decode call: int16 tracks, int16 + resampling in torch, the resampled tracks (tools/resample_rate.py)")
 ap.add_argument("--mix", choices=["mono", "stereo"], default=None, help="with --rate: the 5.1 default downmix table as a channel mix")
+ap.add_argument("--resample", default=None, metavar="UP/DOWN",
+                help="compare the fused ratio call with rate=24000 and with 48 kHz float tracks + a polyphase conv1d in torch (tools/ratio_rate.py)")
 ap.add_argument("--mel", action="store_true", help="compare the fused log-mel call with 16 kHz mono float tracks + torch.stft (tools/mel_rate.py)")
 ap.add_argument("--n-mels", type=int, choices=[80, 128], default=80)
 args = ap.parse_args()
-if args.mix and not args.rate:
-    ap.error("--mix goes with --rate")
-if args.mel and (args.rate or args.format):
-    ap.error("--mel goes without --rate and --format")
-if args.format or args.rate or args.mel:
+if args.mix and not (args.rate or args.resample):
+    ap.error("--mix goes with --rate or --resample")
+if args.mel and (args.rate or args.format or args.resample):
+    ap.error("--mel goes without --rate, --resample and --format")
+if args.resample and (args.rate or args.format):
+    ap.error("--resample goes without --rate and --format")
+if args.format or args.rate or args.mel or args.resample:
     import torch  # before the library is loaded: one HIP runtime for both
 n = args.n
 
@@ -161,6 +167,37 @@ if args.rate:
     print(json.dumps(resample_rate.compare(
         torch, pkg, lambda d, ln, st: ms._chk(ms.lib.opusgpu_ms_files_decode(ms.h, b.h, d, ln, st), "opusgpu_ms_files_decode"), resampled,
         b, args.rate, False, args.reps, "in_order", mix=pkg.downmix_matrix(CH, 1 if args.mix == "mono" else 2) if args.mix else None)))
+    ms.close()
+    raise SystemExit(0)
+
+if args.resample:
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import ratio_rate
+    up, down = pkg.track_ratio(tuple(int(v) for v in args.resample.split("/")))
+    ms = pkg.MultistreamContext(0, n, *LAYOUT)
+    mem = pkg.Context(0)  # the kernels alone are a plain context's calls
+    rec = pkg.mix_matrix(args.mix, CH) if args.mix else None
+    rec_p = None if rec is None else rec.ctypes.data
+
+    def at_24000(fmt, d, oo, ol, ln, st):
+        if rec is not None:
+            return ms._chk(ms.lib.opusgpu_ms_files_decode_mixed(ms.h, b.h, 24000, rec_p, fmt, None, d, oo, ol, ln, st), "opusgpu_ms_files_decode_mixed")
+        return ms._chk(ms.lib.opusgpu_ms_files_decode_resampled(ms.h, b.h, 24000, fmt, None, d, oo, ol, ln, st), "opusgpu_ms_files_decode_resampled")
+
+    def at_24000_kernel(spans, d_in, fmt, d_out):
+        if rec is not None:
+            return mem.tracks_resample_mixed_device(spans, d_in, CH, 24000, rec, fmt, d_out)
+        return mem.tracks_resample_device(spans, d_in, CH, 24000, False, fmt, d_out)
+    print(json.dumps(ratio_rate.compare(
+        torch, pkg,
+        lambda d, ln, st: ms._chk(ms.lib.opusgpu_ms_files_decode_as(ms.h, b.h, pkg.TRACKS_F32, None, d, ln, st), "opusgpu_ms_files_decode_as"),
+        at_24000,
+        lambda fmt, d, oo, ol, ln, st: ms._chk(ms.lib.opusgpu_ms_files_decode_ratio(ms.h, b.h, up, down, rec_p, fmt, None, d, oo, ol, ln, st),
+                                               "opusgpu_ms_files_decode_ratio"),
+        lambda d, ln, st: ms._chk(ms.lib.opusgpu_ms_files_decode(ms.h, b.h, d, ln, st), "opusgpu_ms_files_decode"),
+        (lambda spans, d_in, fmt, d_out: mem.tracks_resample_ratio_device(spans, d_in, CH, up, down, False, rec, fmt, d_out), at_24000_kernel),
+        b, up, down, False, args.reps, "in_order", mix=pkg.downmix_matrix(CH, 1 if args.mix == "mono" else 2) if args.mix else None)))
+    mem.close()
     ms.close()
     raise SystemExit(0)
 
