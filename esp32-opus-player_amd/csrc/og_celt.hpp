@@ -925,11 +925,88 @@ OG_DEV void imdct_short8(i32 *SY, const i16 *xs, const i32 *tail) {
 }
 #endif
 
+// The comb filter's history, touched ahead of the filter.  A tap before the frame's first sample comes from the stream's ring in
+// HBM, which the step before wrote: the filter's steps load it at their point of use and wait the whole trip, five steps per frame
+// on the bench payloads.  Nothing in those addresses depends on this frame -- the ring head, the three lags and their gains are in
+// the record's header -- so the kernel of 20 ms frames requests the lines before the channel's transform and the filter's loads
+// find them in the cache.  One load covers a run: lane k reads history sample lo + 32 k (a 128-byte line further each lane),
+// clamped to the run's last sample hi; every line that holds a sample of [lo, hi] then holds one that is read, wherever the ring
+// starts in its first line.  The values are not used.  [lo, hi] lies inside [-1024, -1] relative to the ring head: the frame's
+// own 960 samples go to [0, 960) of a ring of 2048, so a touch never reads what this wave (or anyone else, this step) writes.
+constexpr int COMB_TOUCH_STEP = 32; // i32 samples per 128-byte line
+struct CombRun { int lo, hi; };     // history samples lo .. hi relative to the ring head; lo > hi: none
+// the ring taps of a comb_filter call that filters samples off .. off + span - 1 at lag T (taps x[p - T - 2] .. x[p - T + 2])
+OG_DEV CombRun comb_run(int off, int T, int span) {
+    CombRun r;
+    T = OG_MAX(T, 15);
+    r.lo = off - T - 2;
+    r.hi = OG_MIN(-1, off + span - 1 - T + 2);
+    if (span <= 0) r.hi = r.lo - 1;
+    return r;
+}
+OG_DEV CombRun comb_run_join(CombRun a, CombRun b) { // (two runs of ONE lag: they meet or overlap whenever both exist)
+    if (a.lo > a.hi) return b;
+    if (b.lo > b.hi) return a;
+    CombRun r;
+    r.lo = OG_MIN(a.lo, b.lo);
+    r.hi = OG_MAX(a.hi, b.hi);
+    return r;
+}
+// The three runs of one channel of a frame that is not lost (celt_synthesis' two calls): the lag in force (T1 of the first call,
+// T0 of the second's cross-fade), the lag before it (the first call's cross-fade), the frame's own (the second call).  A filter
+// whose gain is zero fetches no taps, a call whose two filters are the same has no cross-fade (comb_filter).
+struct CombTouchPlan { CombRun cur, old, next; };
+OG_DEV CombTouchPlan comb_touch_plan(int ppo, int pp, int pf, i32 pgo, i32 pg, i32 pfg, int pto, int pt, int pft, int N) {
+    CombTouchPlan q;
+    const int fade1 = (pgo == pg && OG_MAX(ppo, 15) == OG_MAX(pp, 15) && pto == pt) ? 0 : OVERLAP;
+    const int fade2 = (pg == pfg && OG_MAX(pp, 15) == OG_MAX(pf, 15) && pt == pft) ? 0 : OVERLAP;
+    const bool call1 = pgo != 0 || pg != 0, call2 = pg != 0 || pfg != 0;
+    q.old = comb_run(0, ppo, call1 && pgo != 0 ? fade1 : 0);
+    q.cur = comb_run_join(comb_run(0, pp, call1 && pg != 0 ? OVERLAP : 0), comb_run(OVERLAP, pp, call2 && pg != 0 ? fade2 : 0));
+    q.next = comb_run(OVERLAP, pf, call2 && pfg != 0 ? N - OVERLAP : 0);
+    return q;
+}
+// One load for the three: the span from the lowest sample of any run to the highest is at most 1,024 samples, 33 lanes.  Where
+// the lags differ by much, lines between the runs are read that no tap needs -- with the lags of one voice they overlap.
+OG_DEV CombRun comb_touch_span(const CombTouchPlan &q) {
+    CombRun r;
+    r.lo = 0;
+    r.hi = -(1 << 20);
+    const CombRun runs[3] = {q.cur, q.old, q.next};
+    for (int k = 0; k < 3; k++)
+        if (runs[k].lo <= runs[k].hi) {
+            r.lo = OG_MIN(r.lo, runs[k].lo);
+            r.hi = OG_MAX(r.hi, runs[k].hi);
+        }
+    return r;
+}
+// history sample lane k of the touch reads (the caller skips an empty span)
+OG_DEV int comb_touch_index(CombRun r, int k) { return OG_MIN(r.lo + COMB_TOUCH_STEP * k, r.hi); }
+// the span as one word for the transform, which issues the load: ring index of its first sample | length - 1 << 11 | 1 << 21
+OG_DEV int comb_touch_code(CombRun r, int ring_pos) { return ((ring_pos + r.lo) & RING_MASK) | (r.hi - r.lo) << 11 | 1 << 21; }
+OG_DEV int comb_touch_at(int code, int k) { // ring index lane k reads: comb_touch_index() from the ring's start
+    return ((code & RING_MASK) + OG_MIN(COMB_TOUCH_STEP * k, (code >> 11) & 1023)) & RING_MASK;
+}
+
 // Inverse MDCT of every block of one output channel (clt_mdct_backward celt.cpp:3204), reading
 // the denormalised coefficients on the fly.  B blocks of NBk = N/B outputs, transform size 2*NBk.
-OG_DEVN void imdct_channel(const i32 *tail, int co, int N, int LM, int B, int shift, int C, int CC) {
+// (`touch_ring`, `touch_code`, the 20 ms kernel: the channel's history ring and comb_touch_code() of the span to touch, or 0.  Both
+// are the wave's and live in scalar registers: the transform's vector registers are all taken in its radix-5 stage, one more
+// held across it costs a saved register in scratch.  The lines are requested behind that stage -- behind every request of the
+// transform's own, so that none of its waits, which complete in the order of the requests, includes them -- and have the
+// post-rotation's and the TDAC's time to arrive.)
+OG_DEVN void imdct_channel(const i32 *tail, int co, int N, int LM, int B, int shift, int C, int CC, const i32 *touch_ring = nullptr,
+                           int touch_code = 0) {
     // (the wave's values, in vector registers because the function is not inlined: scalar again, see comb_filter)
     co = OG_UNI(co); N = OG_UNI(N); LM = OG_UNI(LM); B = OG_UNI(B); shift = OG_UNI(shift); C = OG_UNI(C); CC = OG_UNI(CC);
+#if defined(OG_RECON_TIGHT) && !defined(OG_HOST_EMUL)
+    touch_code = OG_UNI(touch_code);
+    const __attribute__((address_space(1))) i32 *const tring = (const __attribute__((address_space(1))) i32 *)(
+        (u64)(u32)OG_UNI((u32)(u64)touch_ring) | (u64)(u32)OG_UNI((u32)((u64)touch_ring >> 32)) << 32);
+    i32 touched = 0;
+#else
+    (void)touch_ring; (void)touch_code;
+#endif
 #if defined(OG_RECON_TIGHT) && !defined(OG_HOST_EMUL)
     // this layout only sees 20 ms frames: one 1920-point transform or eight 240-point ones (the code of the other two sizes --
     // a third of the kernel's instruction bytes -- is not generated)
@@ -970,10 +1047,14 @@ OG_DEVN void imdct_channel(const i32 *tail, int co, int N, int LM, int B, int sh
             for (int pass = 0; pass < LongStage::R5_PASSES; pass++)
                 if (LongStage::r5_live(lane, pass))
                     long_bfly5(F, LongStage::r5_elem(lane, pass), d[pass][0], d[pass][1], d[pass][2], d[pass][3]);
+            if (touch_code) touched = tring[comb_touch_at(touch_code, lane)];
             imdct_long_back(SY, bt, win1, win2);
+            asm volatile("" ::"v"(touched)); // (the touch's register ends here: nothing reads the value)
             return;
         } else if (B == 8 && !(CC == 1 && C == 2)) { // (a down-mix: generic code, as above)
+            if (touch_code) touched = tring[comb_touch_at(touch_code, OG_LANE)]; // (one frame in eight: ahead of the eight blocks, which wait for it)
             imdct_short8(SY, &S.v[V_X + ((CC == 2 && C == 1) ? 0 : co) * N], tail);
+            asm volatile("" ::"v"(touched));
             return;
         } else {
 #endif
@@ -1557,6 +1638,15 @@ OG_DEV void celt_synthesis(CeltState *st, const CeltSynth &p) {
     const int pt = p.have_state ? p.st_pf_tapset : st->pf_tapset, pto = p.have_state ? p.st_pf_tapset_old : st->pf_tapset_old;
     const int pos = p.have_state ? p.st_ring_pos : st->ring_pos;
     i32 *const SY = syn_buf();
+#if defined(OG_RECON_TIGHT) && !defined(OG_HOST_EMUL)
+    // where the comb filter's history lines lie, the same span in both channels' rings: the transform requests them (imdct_channel;
+    // a down-mix runs the transform's generic code and gets no touch -- its filter waits for the ring as before)
+    int touch_code = 0;
+    if (!p.lost && LM != 0 && (pgo != 0 || pg != 0 || pf_gain != 0)) {
+        const CombRun span = comb_touch_span(comb_touch_plan(ppo, pp, pf_pitch, pgo, pg, pf_gain, pto, pt, pf_tapset, N));
+        if (span.lo <= span.hi) touch_code = comb_touch_code(span, pos);
+    }
+#endif
     // ---- one output channel at a time through the single synthesis buffer
     // (the 8 KB layout synthesises the second channel first: its spectrum lies where the buffer starts)
 #ifdef OG_RECON_TIGHT
@@ -1568,8 +1658,10 @@ OG_DEV void celt_synthesis(CeltState *st, const CeltSynth &p) {
         OG_MARK(14);
 #if defined(OG_RECON_TIGHT) && !defined(OG_HOST_EMUL)
         if (!(CC == 1 && C == 2)) denorm_bins((CC == 2 && C == 1) ? 0 : c); // (from denorm_gains' rows)
-#endif
+        imdct_channel(st->tail[c], c, N, LM, B, shift, C, CC, st->ring[c], touch_code);
+#else
         imdct_channel(st->tail[c], c, N, LM, B, shift, C, CC);
+#endif
         OG_MARK(15);
         OG_TAP(2 + 16 * c); // IMDCT output
         if (!p.lost) {

@@ -464,6 +464,7 @@ struct RecCur { // read positions in the record: next word, first word of the wi
 };
 OG_DEV u32 rec_word(RecCur &cur) {
     if ((unsigned)(cur.w - cur.base) >= 64u) { // the window moves to the word wanted (the sequential walk: every 64 words)
+        OG_STAT(26, 1);                             // window refills at the point of use
         OG_LSYNC();
         OG_FOR_LANES(l, 64) S.word_window()[l] = cur.words[OG_MIN(cur.w + l, REC_WORDS_CAP - 1)];
         OG_LSYNC();
@@ -504,6 +505,22 @@ struct LcgTab {
         const u32 a = rom_lcg_jump[2 * j], c = rom_lcg_jump[2 * j + 1];
         return a * seed + c;
     }
+#if defined(OG_RECON_TIGHT) && !defined(OG_HOST_EMUL)
+    // The 20 ms kernel: a lane loop's first pass has j = the lane's index, the same pair for every fill leaf of the frame.  hold()
+    // requests it once (two registers, nothing indexed: see above); entries from 64 on stay loads at their use.
+    u32 a_lane, c_lane;
+    OG_MEMBER void hold() {
+        a_lane = rom_lcg_jump[2 * OG_LANE];
+        c_lane = rom_lcg_jump[2 * OG_LANE + 1];
+    }
+    OG_MEMBER u32 at_lane(u32 seed, int j) const { // at(seed, j) for j = lane + a multiple of 64, after hold()
+        if (j < OG_NLANES) return a_lane * seed + c_lane;
+        return at(seed, j);
+    }
+#else
+    OG_MEMBER void hold() {}
+    OG_MEMBER u32 at_lane(u32 seed, int j) const { return at(seed, j); }
+#endif
 };
 
 // anti_collapse (celt.cpp:1010) for the reconstruction kernel of 20 ms frames.  The shared form (og_celt_bands.hpp) derives a band's
@@ -594,11 +611,11 @@ OG_DEV u32 recon_job_leaves(RecCur &cur, const LcgTab &lcg, u32 jw, u32 &seed_io
             u32 cm;
             OG_LSYNC();
             if (low_job < 0) { // noise
-                OG_FOR_LANES(j, N) S.v[x + j] = (i16)((i32)lcg.at(seed, j) >> 20);
+                OG_FOR_LANES(j, N) S.v[x + j] = (i16)((i32)lcg.at_lane(seed, j) >> 20);
                 cm = cm_mask;
             } else { // folded spectrum, +-1/256 dither
                 const int low = low_job + (x - x_job);
-                OG_FOR_LANES(j, N) S.v[x + j] = (i16)(S.v[low + j] + ((lcg.at(seed, j) & 0x8000) ? 4 : -4));
+                OG_FOR_LANES(j, N) S.v[x + j] = (i16)(S.v[low + j] + ((lcg.at_lane(seed, j) & 0x8000) ? 4 : -4));
                 cm = (u32)fill;
             }
             seed_io = lcg_skip(seed, (u32)N);
@@ -947,6 +964,7 @@ struct ReconCtx {
     // pulses, of the stream's two energy histories as they were BEFORE a reset), or not (pre == false: read there)
     bool pre = false;
     i32 pre_bandE, pre_logE1, pre_logE2, pre_pulses;
+    i32 pre_band_w; // (entry `lane` of the record's band_w: recon_begin puts it where the band loop's set-up reads it, S.band_w_row())
 };
 OG_DEV bool recon_fast_eligible(const ReconHdr &h) {
     if (h.flags & (RF_SKIP | RF_BAD_CELT)) return false;
@@ -997,6 +1015,9 @@ OG_DEV bool recon_begin(StreamState *st, const ParseRec *rec, int mode, int ch, 
         }
 #endif
         OG_FOR_LANES(i, 2 * NBANDS) S.job_mask_row()[i] = 0;
+#ifdef OG_RECON_TIGHT
+        if (rx.pre && OG_LANE < NBANDS) S.band_w_row()[OG_LANE] = (u16)rx.pre_band_w;
+#endif
 #ifdef OG_HOST_EMUL
         OG_FOR_LANES(i, 2 * 960) S.v[V_X + i] = 0;
 #else
@@ -1091,7 +1112,7 @@ OG_DEV int recon_finish(StreamState *st, const ParseRec *rec, const ReconCtx &rx
 #endif
         u32 seed = rx.h.rng;
 #ifdef OG_RECON_TIGHT
-        recon_all_bands_pm(rec, lcg, C, transient ? M : 0, seed, start);
+        recon_all_bands_pm(rec, lcg, C, transient ? M : 0, seed, start, rx.pre);
         // what anti-collapse and the synthesis read besides the spectrum, staged only now (og_state.hpp, V_LATE: the rows
         // were the band loop's scratch until here; the bands' collapse masks are there already)
         if (rx.pre) {

@@ -101,7 +101,9 @@ OG_DEV PmGrp pm_group(int g) { // group g of the coded spectrum: 0..99 first cha
 // B: one lane per (band, decode slot).  Returns (wave-uniform) which time-frequency passes some job needs: bit 0 the
 // interleave, bit 1 + 4 k + c the Haar stride 1 << c at step k; fill_lo / fill_hi: the jobs phase D has to run.
 // (`start`: the frame's first band -- 17 for the CELT layer of a hybrid frame; the bands below it have no words in the record)
-OG_DEV u32 pm_setup_jobs(const ParseRec *rec, int C, int B, u32 &fill_lo, u32 &fill_hi, int &dual_end, int start = 0) {
+// (`bw_staged`: the kernel fetched the record's band_w with its first round trip and S.band_w_row() holds it -- one dependent trip
+// to the record less here)
+OG_DEV u32 pm_setup_jobs(const ParseRec *rec, int C, int B, u32 &fill_lo, u32 &fill_hi, int &dual_end, int start = 0, bool bw_staged = false) {
     PmLds &P = PM();
     OG_LSYNC();
     OG_FOR_LANES(bin, PM_GROUPS) { // (tables: the search they replace was up to 21 dependent loads per lane)
@@ -117,7 +119,12 @@ OG_DEV u32 pm_setup_jobs(const ParseRec *rec, int C, int B, u32 &fill_lo, u32 &f
     const int logBf = ilog2(B);
     OG_FOR_LANES(l, 2 * NBANDS) {
         const int band = l >> 1, jb = l & 1, coded = band >= start;
-        const u32 *wp = rec->words + (coded ? rec->band_w[band] : 0);
+#ifdef OG_RECON_TIGHT
+        const int bw = !coded ? 0 : bw_staged ? (int)S.band_w_row()[band] : (int)rec->band_w[band];
+#else
+        const int bw = coded ? (int)rec->band_w[band] : 0;
+#endif
+        const u32 *wp = rec->words + bw;
         const u32 w0 = coded ? wp[0] : 0u, w1 = coded ? wp[1] : 0u, w2 = coded ? wp[2] : 0u, w3 = coded ? wp[3] : 0u, jw0 = coded ? wp[4] : 0u;
         const int N = (int)(w1 >> 22) & 255;
         const int stereo = (w0 & BW_STEREO) != 0, dual = (w0 & BW_DUAL) != 0, mid_first = (w0 & BW_MID_FIRST) != 0;
@@ -131,7 +138,7 @@ OG_DEV u32 pm_setup_jobs(const ParseRec *rec, int C, int B, u32 &fill_lo, u32 &f
         }
         const int exists = jb < njobs;
         const int ch = dual ? jb : stereo ? (((jb == 0) == mid_first) ? 0 : 1) : 0;
-        const int jpos = (coded ? rec->band_w[band] : 0) + 4 + (jb ? 1 + 2 * (int)(jw0 & 31) : 0);
+        const int jpos = bw + 4 + (jb ? 1 + 2 * (int)(jw0 & 31) : 0);
         u32 jw = jw0;
         if (jb && exists) jw = rec->words[OG_MIN(jpos, REC_WORDS_CAP - 1)];
         const int n_fill = (int)(jw & 31), n_pvq = (int)(jw >> JW_NPVQ_SHIFT) & 31;
@@ -349,6 +356,7 @@ OG_DEV void pm_fill_jobs(const u32 *words, const LcgTab &lcg, u32 fill_lo, u32 f
             continue; // (its mask P.jcm is zero from the set-up, the seed does not move: celt.cpp:1481-1520 under `if (fill)`)
         }
         cur.w = (int)(aux & 0xffff);
+        OG_STAT(27, 1);                             // fill jobs that run
         const u32 jw = rec_word(cur);
         int low = -1;
         if ((w0 & BW_HAS_LOW) && want_low && (jw & JW_NEED_LOW)) {
@@ -367,6 +375,9 @@ OG_DEV void pm_stereo_merge(int C) {
     PmLds &P = PM();
     if (C != 2) return;
     OG_LSYNC();
+    // (the band edges of the lane-per-band pass below: requested here, ahead of the partial sums -- behind the barrier that
+    // closes them the pass waited a round trip for the pair)
+    const int eb_lo = rom_eband[OG_MIN(OG_LANE, NBANDS - 1)], eb_hi = rom_eband[OG_MIN(OG_LANE, NBANDS - 1) + 1];
     OG_FOR_LANES(g, PM_GROUPS) { // partial sums of a group of 8
         const int band = P.binband[g];
         if (P.bw0[band] & BW_STEREO) {
@@ -385,7 +396,8 @@ OG_DEV void pm_stereo_merge(int C) {
     OG_FOR_LANES(band, NBANDS) { // the band's two gains
         const u32 w0 = P.bw0[band];
         if (w0 & BW_STEREO) {
-            const int g0 = rom_eband[band], g1 = rom_eband[band + 1];
+            // (one band per lane and one pass, band == lane: the pair fetched above; the one-lane emulation walks the bands)
+            const int g0 = OG_NLANES > 1 ? eb_lo : rom_eband[band], g1 = OG_NLANES > 1 ? eb_hi : rom_eband[band + 1];
             i32 xp = 0, side = 0;
             for (int g = g0; g < g1; g++) {
                 xp += pm_part()[g][0];
@@ -443,12 +455,30 @@ OG_DEV void pm_stereo_merge(int C) {
     OG_LSYNC();
 }
 
-OG_DEV void recon_all_bands_pm(const ParseRec *rec, const LcgTab &lcg, int C, int shortBlocks, u32 &seed_io, int start = 0) {
+OG_DEV void recon_all_bands_pm(const ParseRec *rec, LcgTab &lcg, int C, int shortBlocks, u32 &seed_io, int start = 0, bool bw_staged = false) {
     const int B = shortBlocks ? 8 : 1;
     u32 fill_lo, fill_hi, seed = seed_io;
     int dual_end;
     OG_MARK(3);
-    const u32 tfm = pm_setup_jobs(rec, C, B, fill_lo, fill_hi, dual_end, start);
+    const u32 tfm = pm_setup_jobs(rec, C, B, fill_lo, fill_hi, dual_end, start, bw_staged);
+    if (fill_lo | fill_hi) lcg.hold(); // the lane's noise-generator pair, for the fill jobs: in flight during the parallel pass
+#if defined(OG_HOST_EMUL) && defined(OG_STATS)
+    { // fill jobs per frame, and how far apart their words lie in the record (tests/test_fill_windows_emul.py)
+        int n_fill_jobs = 0, w_prev = -1;
+        bool close_pair = false;
+        for (int l = 0; l < 2 * NBANDS; l++)
+            if ((l < 32 ? fill_lo >> l : fill_hi >> (l - 32)) & 1u) {
+                const int w = (int)(PM().jaux[l] & 0xffff);
+                close_pair |= w_prev >= 0 && w - w_prev < 64;
+                w_prev = w;
+                n_fill_jobs++;
+            }
+        OG_STAT(33, n_fill_jobs == 0);              // frames with no / one / four or more fill jobs
+        OG_STAT(34, n_fill_jobs == 1);
+        OG_STAT(35, n_fill_jobs >= 4);
+        OG_STAT(36, close_pair);                    // frames with two fill jobs less than a window apart
+    }
+#endif
     OG_STAT(0, 1);                                  // frames
     OG_STAT(19, shortBlocks != 0);                  // transient frames
     OG_STAT(21, tfm != 0);                          // frames with a time-frequency change to undo in the parallel pass

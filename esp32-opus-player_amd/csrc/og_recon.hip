@@ -60,6 +60,7 @@ __global__ void __launch_bounds__(64, OG_FAST_WAVES) k_celt_recon_fb(const Frame
         }
         rx.pre_bandE = rec->bandE[lane < 2 * NBANDS ? lane : 0];
         rx.pre_pulses = rec->pulses[lane < NBANDS ? lane : 0];
+        rx.pre_band_w = rec->band_w[lane < NBANDS ? lane : 0];
         const int mode = desc_mode(d.flags);
         bool ok = !(d.stream < 0 || d.stream >= n_streams || !(mode == MODE_CELT || (mode == MODE_HYBRID && hybrid)) || desc_rfc(d.flags));
         if (ok) {

@@ -207,7 +207,9 @@ constexpr int V_LATE = V_IY;
 constexpr int V_WIN = V_TMP + 200;      // window of the record's word stream (64 x u32; fill jobs)
 constexpr int V_JOBM = V_NORM + 1152;   // the jobs' collapse masks (2 * NBANDS x u32), from the leaf pass to the band loop: behind
                                         // the PVQ table's rows 4 - 8 + row bases (1134 + 16 entries) and behind the window
-constexpr int V_TOTAL = V_JOBM + 4 * NBANDS;
+constexpr int V_BANDW = V_JOBM + 4 * NBANDS; // where each band's words start in the record (NBANDS x u16): fetched with the kernel's
+                                            // first round trip, read by the band loop's set-up
+constexpr int V_TOTAL = V_BANDW + NBANDS;
 constexpr int V_SYN = 960;              // the synthesis buffer: second channel's spectrum + what lies behind X
 constexpr int SYN_LEN = 1088;
 struct FrameLds {
@@ -221,6 +223,7 @@ struct FrameLds {
     OG_MEMBER i16 *logE1_row() { return &v[V_LATE + 24 + 4 * NBANDS]; }
     OG_MEMBER i16 *logE2_row() { return &v[V_LATE + 24 + 6 * NBANDS]; }
     OG_MEMBER u32 *job_mask_row() { return reinterpret_cast<u32 *>(&v[V_JOBM]); }
+    OG_MEMBER u16 *band_w_row() { return reinterpret_cast<u16 *>(&v[V_BANDW]); }
     OG_MEMBER u32 *word_window() { return reinterpret_cast<u32 *>(&v[V_WIN]); }
     OG_MEMBER u8 *rot_marker() { return reinterpret_cast<u8 *>(&v[X_TOP1 + 104]); }  // 64 bytes behind the PVQ table's rows 12 - 14 (leaf pass)
     OG_MEMBER i16 *dn_g_row() { return &v[X_TOP0]; }                                  // synthesis only: 2 * NBANDS each
@@ -228,6 +231,7 @@ struct FrameLds {
     OG_MEMBER u8 *bin2band_row() { return reinterpret_cast<u8 *>(&v[X_TOP0 + 4 * NBANDS]); } // 120 bytes
 };
 static_assert(V_SYN * 2 + SYN_LEN * 4 <= V_TOTAL * 2, "the synthesis buffer fits");
+static_assert(V_BANDW == V_JOBM + 4 * NBANDS && V_BANDW + NBANDS <= V_TOTAL, "the bands' word positions lie behind the jobs' collapse masks");
 static_assert(X_TOP0 + 4 * NBANDS + 60 <= 960, "the synthesis' per-band gains and the bin -> band table fit the first channel's unused top");
 static_assert(V_LATE + 24 + 8 * NBANDS <= V_WIN && (V_LATE + 24) % 2 == 0, "the late-staged arrays fit the scratch rows");
 static_assert(V_NORM % 8 == 0 && V_IY % 8 == 0 && V_WIN % 2 == 0 && V_WIN + 128 <= V_JOBM && V_JOBM % 2 == 0 && X_TOP1 % 8 == 0, "alignment of the overlays");
