@@ -45,6 +45,8 @@ EXPORTS = [
     "opusgpu_ms_files_decode_mel",
     "opusgpu_resample_ratio_taps", "opusgpu_resample_ratio_layout", "opusgpu_tracks_resample_ratio_device", "opusgpu_files_decode_ratio",
     "opusgpu_ms_files_decode_ratio",
+    "opusgpu_spec_basis", "opusgpu_spec_filterbank", "opusgpu_spec_layout", "opusgpu_tracks_melspec_device", "opusgpu_files_decode_melspec",
+    "opusgpu_ms_files_decode_melspec",
 ]
 
 
@@ -134,6 +136,14 @@ MEL_SPAN_DTYPE = np.dtype([("in_offset", "<i8"), ("in_samples", "<i8"), ("out_of
 MEL_NFFT, MEL_HOP, MEL_SR, MEL_BINS = 400, 160, 16000, 201
 MEL_BANDS_MAJOR, MEL_FRAMES_MAJOR = 0, 1
 MEL_LAYOUTS = {"bands": MEL_BANDS_MAJOR, "frames": MEL_FRAMES_MAJOR}
+# opusgpu_spec_params and its enums (include/opusgpu.h, TRACK SPECTROGRAMS)
+SPEC_PARAMS_DTYPE = np.dtype([("sample_rate", "<i4"), ("n_fft", "<i4"), ("win_length", "<i4"), ("hop", "<i4"), ("n_mels", "<i4"),
+                              ("mel_scale", "<i4"), ("norm", "<i4"), ("power", "<i4"), ("log", "<i4"), ("frames", "<i4"), ("layout", "<i4"),
+                              ("fmin", "<f4"), ("fmax", "<f4"), ("floor", "<f4"), ("reserved", "<i4", (2,))])
+SPEC_SCALES = {"slaney": 0, "htk": 1}
+SPEC_NORMS = {"slaney": 0, None: 1, "none": 1}
+SPEC_LOGS = {None: 0, "none": 0, "log10": 1, "ln": 2}
+SPEC_FRAMES = {"torch": 0, "whisper": 1}
 OPUSGPU_BAD_ARG, OPUSGPU_UNIMPLEMENTED, OPUSGPU_CELT_BAD_ARG = -1, -5, -18
 RFC_FRAME = 2880
 
@@ -267,6 +277,13 @@ def load_lib():
     lib.opusgpu_tracks_mel_device.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
     lib.opusgpu_files_decode_mel.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.opusgpu_ms_files_decode_mel.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.opusgpu_spec_basis.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    lib.opusgpu_spec_filterbank.argtypes = [vp, C.POINTER(vp)]
+    lib.opusgpu_spec_layout.argtypes = [C.c_int, vp, C.c_int, C.c_int, vp, vp]
+    lib.opusgpu_spec_layout.restype = C.c_int64
+    lib.opusgpu_tracks_melspec_device.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
+    lib.opusgpu_files_decode_melspec.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.opusgpu_ms_files_decode_melspec.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
     _lib = lib
     return lib
 
@@ -827,12 +844,150 @@ def track_feature_args(batch, features=None, n_mels=80, feature_layout="bands", 
     return rec, mrec, scale, offsets, planes, total, out
 
 
+def mel_spec(sample_rate, n_fft, hop, win_length=None, n_mels=80, fmin=0.0, fmax=None, mel_scale="slaney", norm="slaney", power=2,
+             log="log10", floor=1e-10, frames="torch", feature_layout="bands"):
+    """An opusgpu_spec_params record (a SPEC_PARAMS_DTYPE array of one; include/opusgpu.h TRACK SPECTROGRAMS): the numbers that
+    torchaudio's MelSpectrogram and librosa's melspectrogram take.  win_length None is n_fft, fmax None is sample_rate / 2; mel_scale
+    "slaney" or "htk"; norm "slaney" or None; power 1 or 2; log "log10", "ln" or None; frames "torch" (n // hop + 1) or "whisper"
+    (n // hop); feature_layout as for mel_params.  Raises ValueError for what the record's rules refuse."""
+    import numbers
+
+    def whole(name, v):
+        if not isinstance(v, numbers.Integral) or isinstance(v, bool):
+            raise ValueError(f"{name} must be an int, not {v!r}")
+        return int(v)
+    sample_rate, n_fft, hop, n_mels = whole("sample_rate", sample_rate), whole("n_fft", n_fft), whole("hop", hop), whole("n_mels", n_mels)
+    win = n_fft if win_length is None else whole("win_length", win_length)
+    if not 1 <= sample_rate <= 1048576:
+        raise ValueError(f"sample_rate must be in [1, 1048576], not {sample_rate}")
+    if not 64 <= n_fft <= 2048 or n_fft % 16:
+        raise ValueError(f"n_fft must be a multiple of 16 in [64, 2048], not {n_fft}")
+    if not 16 <= win <= n_fft or win % 2:
+        raise ValueError(f"win_length must be even and in [16, n_fft], not {win}")
+    if not 1 <= hop <= n_fft or 31 * hop + n_fft > 32768:
+        raise ValueError(f"hop must be in [1, n_fft] with 31 * hop + n_fft <= 32768, not {hop}")
+    if not 1 <= n_mels <= 128:
+        raise ValueError(f"n_mels must be in [1, 128], not {n_mels}")
+    for name, v, table in (("mel_scale", mel_scale, SPEC_SCALES), ("norm", norm, SPEC_NORMS), ("log", log, SPEC_LOGS), ("frames", frames, SPEC_FRAMES),
+                           ("feature_layout", feature_layout, MEL_LAYOUTS)):
+        if not isinstance(v, (str, type(None))) or v not in table:
+            raise ValueError(f"{name} must be one of {sorted(table, key=str)}, not {v!r}")
+    if power not in (1, 2) or isinstance(power, bool):
+        raise ValueError(f"power must be 1 or 2, not {power!r}")
+    rec = np.zeros(1, dtype=SPEC_PARAMS_DTYPE)
+    rec["sample_rate"], rec["n_fft"], rec["win_length"], rec["hop"], rec["n_mels"] = sample_rate, n_fft, win, hop, n_mels
+    rec["mel_scale"], rec["norm"], rec["power"], rec["log"] = SPEC_SCALES[mel_scale], SPEC_NORMS[norm], int(power), SPEC_LOGS[log]
+    rec["frames"], rec["layout"] = SPEC_FRAMES[frames], MEL_LAYOUTS[feature_layout]
+    try:
+        rec["fmin"], rec["fmax"], rec["floor"] = float(fmin), sample_rate / 2 if fmax is None else float(fmax), float(floor)
+    except (TypeError, ValueError):
+        raise ValueError(f"fmin, fmax and floor must be numbers, not {fmin!r}, {fmax!r}, {floor!r}") from None
+    fmin32, fmax32, floor32 = float(rec["fmin"][0]), float(rec["fmax"][0]), float(rec["floor"][0])
+    if not (0 <= fmin32 < fmax32 <= sample_rate / 2):
+        raise ValueError(f"0 <= fmin < fmax <= sample_rate / 2 must hold, not fmin {fmin!r}, fmax {fmax!r}")
+    if not np.isfinite(floor32) or floor32 < 0 or (rec["log"][0] and not floor32 > 0):
+        raise ValueError(f"floor must be finite and >= 0, and > 0 with a log, not {floor!r}")
+    return rec
+
+
+def _spec_rec(rec):
+    if getattr(rec, "dtype", None) != SPEC_PARAMS_DTYPE or np.size(rec) != 1:
+        raise ValueError("a spectrogram's parameters are a mel_spec() record")
+    return np.ascontiguousarray(rec).reshape(1)
+
+
+def spec_basis(rec):
+    """opusgpu_spec_basis: the windowed DFT basis of a mel_spec record -> (Wc, Ws), float32 [n_fft, n_fft / 2 + 1] each."""
+    rec = _spec_rec(rec)
+    wc, ws = C.c_void_p(), C.c_void_p()
+    n = load_lib().opusgpu_spec_basis(rec.ctypes.data, C.byref(wc), C.byref(ws))
+    if n < 0:
+        raise ValueError("opusgpu_spec_basis refused the record")
+    n_fft = int(rec["n_fft"][0])
+    return tuple(np.ctypeslib.as_array((C.c_float * n).from_address(p.value)).reshape(n_fft, n_fft // 2 + 1).copy() for p in (wc, ws))
+
+
+def spec_filterbank(rec):
+    """opusgpu_spec_filterbank: the filterbank of a mel_spec record -> float32 [n_mels, n_fft / 2 + 1]."""
+    rec = _spec_rec(rec)
+    p = C.c_void_p()
+    n = load_lib().opusgpu_spec_filterbank(rec.ctypes.data, C.byref(p))
+    if n < 0:
+        raise ValueError("opusgpu_spec_filterbank refused the record")
+    return np.ctypeslib.as_array((C.c_float * n).from_address(p.value)).reshape(int(rec["n_mels"][0]), -1).copy()
+
+
+def spec_frames(rec, samples):
+    """F of TRACK SPECTROGRAMS for tracks of `samples` samples at the record's rate."""
+    rec = _spec_rec(rec)
+    n, hop = np.asarray(samples, dtype=np.int64), int(rec["hop"][0])
+    return n // hop if int(rec["frames"][0]) == SPEC_FRAMES["whisper"] else np.where(n > 0, n // hop + 1, 0)
+
+
+def spec_layout(planned_48k_samples, up, down, rec):
+    """opusgpu_spec_layout: the grid of the spectrograms of tracks at up / down of 48 kHz -> (feat_offsets [int64], planes [int64],
+    total floats)."""
+    rec = _spec_rec(rec)
+    planned = np.ascontiguousarray(planned_48k_samples, dtype=np.int64)
+    offsets = np.zeros(planned.size, dtype=np.int64)
+    total = load_lib().opusgpu_spec_layout(planned.size, planned.ctypes.data, int(up), int(down), rec.ctypes.data, offsets.ctypes.data)
+    if total < 0:
+        raise ValueError(f"opusgpu_spec_layout refused the record, the ratio {up!r}/{down!r} or a negative length")
+    planes = (spec_frames(rec, -(-planned * int(up) // int(down))) + 63) // 64 * 64
+    return offsets, planes, int(total)
+
+
+def track_spectrogram_args(batch, features, rate=None, resample=None, mono=False, mix=None, format=None, scale=None, out=None, device=0,
+                           allow_mono=True):
+    """What decode_files makes of a mel_spec record as its features= for a planned batch, before any device work: (record, mix record
+    or None, float32 scale array or None, feat_offsets, planes, total floats, out flattened or None, (rate or 0, up, down) as the C
+    call takes them).  rate= names a rate of TRACK RATES, resample= a ratio of TRACK RATIOS; with neither, the record's sample_rate
+    is taken as the one or the other.  Raises ValueError for a record that breaks a rule, both rate= and resample=, a rate or ratio
+    that does not exist or is not the record's sample_rate, and for what track_feature_args refuses of format, mono, mix, scale and
+    out."""
+    rec = _spec_rec(features)
+    sr = int(rec["sample_rate"][0])
+    if rate is not None and resample is not None:
+        raise ValueError("resample= and rate= exclude each other")
+    if rate is None and resample is None:
+        rate, resample = (sr, None) if sr in TRACK_RATES else (None, sr)
+    if rate is not None:
+        if rate not in TRACK_RATES:
+            raise ValueError(f"rate must be one of {sorted(TRACK_RATES)}, not {rate!r}")
+        how, up, down = (int(rate), 0, 0), 1, TRACK_RATES[rate]
+    else:
+        up, down = track_ratio(resample)
+        how = (0, up, down)
+    if sr * down != 48000 * up:
+        raise ValueError(f"the record's sample_rate {sr} is not the track's rate, 48000 * {up} / {down}")
+    if format not in (None, "f32"):
+        raise ValueError(f"features are float32: format must be absent or 'f32', not {format!r}")
+    if mono and not allow_mono:
+        raise ValueError("there is no mono downmix of multistream tracks: use mix='mono'")
+    if mix is not None and mono:
+        raise ValueError("mix and mono=True exclude each other: the row {8192, 8192} is mono")
+    if mix is None and not mono:
+        raise ValueError("features are made of ONE channel: pass mono=True or a mix of one row (mix='mono')")
+    mrec = None
+    if mix is not None:
+        mrec = mix_matrix(mix, batch.channels)
+        if int(mrec["out_channels"][0]) != 1:
+            raise ValueError(f"features are made of ONE channel: the mix has {int(mrec['out_channels'][0])} rows")
+    elif batch.channels > 2:
+        raise ValueError(f"mono needs 1 or 2 channels, not {batch.channels}")
+    _, scale, _ = track_format_args(batch, "f32", scale, None, device)
+    offsets, planes, total = spec_layout(batch.info["track_samples"], up, down, rec)
+    if out is not None:
+        out = _out_flat(out, max(total, 1), "f32", device)
+    return rec, mrec, scale, offsets, planes, total, out, how
+
+
 def _decode_planned_mel(chk, name, call, batch, mem, fargs):
     """_decode_planned for feature tracks: call(scale pointer, d_out, four array pointers) runs the decode call `name`; fargs: what
     track_feature_args returned.  -> (features, info): float32 arrays [n_mels, F] or [F, n_mels]; info has `feat_offset` more, and
     its `frames` is F, the track's feature frames, as `track_samples` is its final length (the plan's count of Opus frames is
     batch.info["frames"])."""
-    rec, _, scale, offsets, planes, total, out = fargs
+    rec, _, scale, offsets, planes, total, out = fargs[:7]
     n, n_mels, frames_major = batch.n_files, int(rec["n_mels"][0]), int(rec["layout"][0]) == MEL_FRAMES_MAJOR
     feat_offsets, frames, lengths = (np.zeros(n, dtype=np.int64) for _ in range(3))
     status = np.zeros((n, 2), dtype=np.int32)
@@ -1152,6 +1307,14 @@ class Context:
         self._chk(self.lib.opusgpu_tracks_mel_device(self.h, spans.size, spans.ctypes.data, d_in, rec.ctypes.data, d_out, stream),
                   "opusgpu_tracks_mel_device")
 
+    def tracks_melspec_device(self, spans, d_in, rec, d_out, stream=None):
+        """k_tracks_melspec alone (include/opusgpu.h TRACK SPECTROGRAMS): spans a HOST array of MEL_SPAN_DTYPE, d_in packed int16 mono
+        tracks at the record's rate, rec a mel_spec record, d_out the float32 feature tracks.  Waits for the kernel."""
+        spans = np.ascontiguousarray(spans, dtype=MEL_SPAN_DTYPE)
+        rec = _spec_rec(rec)
+        self._chk(self.lib.opusgpu_tracks_melspec_device(self.h, spans.size, spans.ctypes.data, d_in, rec.ctypes.data, d_out, stream),
+                  "opusgpu_tracks_melspec_device")
+
     def decode_files(self, files, rfc=False, flags=PAGES_GROUP_BY_MODE, threads=1, batch=None, format=None, scale=None, out=None,
                      rate=None, mono=False, mix=None, features=None, n_mels=80, feature_layout="bands", resample=None):
         """Whole Ogg Opus files -> (list of int16 arrays [samples, channels], one trimmed track per file, info).  The context's
@@ -1184,7 +1347,11 @@ class Context:
         the GPU (include/opusgpu.h TRACK RATIOS: integer arithmetic over the int16 track, bit-exact; track_ratio says which ratios
         there are).  mono, mix, format, scale and out act as with rate=: the tracks are [ceil(len up / down), output channels],
         `out` is sized for them (track_ratio_args) and info has `out_samples` and `out_offset` more.  Not together with rate= or
-        features=."""
+        features="logmel".
+        features may also be a mel_spec() record: a mel spectrogram of the mono track at the record's sample_rate (include/opusgpu.h
+        TRACK SPECTROGRAMS: n_fft, win_length, hop, n_mels, fmin / fmax, Slaney or HTK, power 1 or 2, log10 / ln / none and a floor
+        are fields), with rate= or resample= naming that rate (or neither: the record's is taken), mono=True or a mix of one row,
+        and scale=, out= and info as with "logmel"; n_mels= and feature_layout= are the record's (track_spectrogram_args)."""
         if mix is not None and mono:
             raise ValueError("mix and mono=True exclude each other: the row {8192, 8192} is mono")
         own = batch is None
@@ -1192,6 +1359,17 @@ class Context:
         if own:
             batch = FileBatch(files, channels=channels, rfc=rfc, flags=flags, threads=threads)
         try:
+            if getattr(features, "dtype", None) == SPEC_PARAMS_DTYPE:
+                sargs = track_spectrogram_args(batch, features, rate, resample, mono, mix, format, scale, out, self.device)
+                if self.n_streams < batch.n_files or self.channels != batch.channels:
+                    self.streams_alloc(max(batch.n_files, 1), batch.channels)
+                self.set_mode(batch.rfc)
+
+                def call(scale_p, d_out, *arrays):
+                    return self.lib.opusgpu_files_decode_melspec(self.h, batch.h, *sargs[7], 1 if mono else 0,
+                                                                 None if sargs[1] is None else sargs[1].ctypes.data, sargs[0].ctypes.data,
+                                                                 scale_p, d_out, *arrays)
+                return _decode_planned_mel(self._chk, "opusgpu_files_decode_melspec", call, batch, self, sargs)
             if resample is not None:
                 format = "s16" if format is None else format
                 qargs = track_ratio_args(batch, resample, mono, mix, format, out, self.device, rate=rate, features=features)
@@ -1405,12 +1583,21 @@ class MultistreamContext:
         for Context.decode_files, all channels at `rate`.  mix: as for Context.decode_files -- "mono" and "stereo" are the default
         downmix tables of the layout's channel count; there is no `mono` argument here.
         features, n_mels, feature_layout: as for Context.decode_files, with mix="mono" or a matrix of one row.
-        resample: as for Context.decode_files, all channels or those of the mix."""
+        resample: as for Context.decode_files, all channels or those of the mix.  features may be a mel_spec() record as there."""
         own = batch is None
         if own:
             batch = MsFileBatch(files, self.layout, rfc=rfc, threads=threads)
         mem = None
         try:
+            if getattr(features, "dtype", None) == SPEC_PARAMS_DTYPE:
+                sargs = track_spectrogram_args(batch, features, rate, resample, False, mix, format, scale, out, self.device, allow_mono=False)
+                mem = Context(self.device)
+                self.set_mode(batch.rfc)
+
+                def call(scale_p, d_out, *arrays):
+                    return self.lib.opusgpu_ms_files_decode_melspec(self.h, batch.h, *sargs[7], sargs[1].ctypes.data, sargs[0].ctypes.data,
+                                                                    scale_p, d_out, *arrays)
+                return _decode_planned_mel(self._chk, "opusgpu_ms_files_decode_melspec", call, batch, mem, sargs)
             if resample is not None:
                 format = "s16" if format is None else format
                 qargs = track_ratio_args(batch, resample, False, mix, format, out, self.device, allow_mono=False, rate=rate, features=features)

@@ -187,18 +187,45 @@ struct MelTables {
 static double mel_point_hz(double m) { // Slaney's scale: linear below 1 kHz at 200 / 3 Hz per mel, logarithmic above
     return m < 15.0 ? 200.0 / 3.0 * m : 1000.0 * std::exp(std::log(6.4) / 27.0 * (m - 15.0));
 }
-static MelTables mel_tables_make() {
-    MelTables t;
+static double mel_point_mel(double f) { return f < 1000.0 ? 3.0 * f / 200.0 : 15.0 + std::log(f / 1000.0) / (std::log(6.4) / 27.0); }
+static double mel_htk_hz(double m) { return 700.0 * (std::pow(10.0, m / 2595.0) - 1.0); }
+static double mel_htk_mel(double f) { return 2595.0 * std::log10(1.0 + f / 700.0); }
+// The two builders that TRACK FEATURES and TRACK SPECTROGRAMS (og_tracks_melspec.hpp) share.
+// Wc, Ws [n_fft][n_fft / 2 + 1]: a periodic Hann window of `win` taps, centred in the frame, times cos and sin of 2 pi i k / n_fft.
+static void mel_basis_make(int n_fft, int win, std::vector<float> &wc, std::vector<float> &ws) {
     const double pi = 3.14159265358979323846;
-    t.wc.resize(400 * 201), t.ws.resize(400 * 201);
-    for (int i = 0; i < 400; i++) {
-        const double w = 0.5 - 0.5 * std::cos(2.0 * pi * i / 400.0);
-        for (int k = 0; k <= 200; k++) {
-            const double a = 2.0 * pi * ((i * k) % 400) / 400.0; // the angle reduced in integers
-            t.wc[i * 201 + k] = (float)(w * std::cos(a));
-            t.ws[i * 201 + k] = (float)(w * std::sin(a));
+    const int bins = n_fft / 2 + 1, left = (n_fft - win) / 2;
+    wc.assign((size_t)n_fft * bins, 0.f), ws.assign((size_t)n_fft * bins, 0.f);
+    for (int i = left; i < left + win; i++) {
+        const double w = 0.5 - 0.5 * std::cos(2.0 * pi * (i - left) / (double)win);
+        for (int k = 0; k < bins; k++) {
+            const double a = 2.0 * pi * ((i * k) % n_fft) / (double)n_fft; // the angle reduced in integers
+            wc[(size_t)i * bins + k] = (float)(w * std::cos(a));
+            ws[(size_t)i * bins + k] = (float)(w * std::sin(a));
         }
     }
+}
+// B [n_mels][bins]: triangles over n_mels + 2 points evenly spaced in mel over [fmin, fmax], bin k at k * bin_hz.
+static void mel_bank_make(double bin_hz, int bins, int n_mels, bool htk, bool slaney_norm, double fmin, double fmax, std::vector<float> &bank) {
+    const double m0 = htk ? mel_htk_mel(fmin) : mel_point_mel(fmin), m1 = htk ? mel_htk_mel(fmax) : mel_point_mel(fmax);
+    std::vector<double> pts(n_mels + 2);
+    for (int j = 0; j < n_mels + 2; j++) {
+        const double m = j == n_mels + 1 ? m1 : m0 + j * ((m1 - m0) / (n_mels + 1));
+        pts[j] = htk ? mel_htk_hz(m) : mel_point_hz(m);
+    }
+    bank.assign((size_t)n_mels * bins, 0.f);
+    for (int j = 0; j < n_mels; j++) {
+        const double lo = pts[j], ce = pts[j + 1], hi = pts[j + 2];
+        for (int k = 0; k < bins; k++) {
+            const double fr = bin_hz * k, lower = (fr - lo) / (ce - lo), upper = (hi - fr) / (hi - ce);
+            const double w = std::fmax(0.0, std::fmin(lower, upper));
+            bank[(size_t)j * bins + k] = (float)(slaney_norm ? w * (2.0 / (hi - lo)) : w);
+        }
+    }
+}
+static MelTables mel_tables_make() {
+    MelTables t;
+    mel_basis_make(OPUSGPU_MEL_NFFT, OPUSGPU_MEL_NFFT, t.wc, t.ws);
     t.basis.assign((size_t)MEL_NB * MEL_KS * 64 * 2, 0.f);
     for (int nb = 0; nb < MEL_NB; nb++)
         for (int ks = 0; ks < MEL_KS; ks++)
@@ -209,20 +236,9 @@ static MelTables mel_tables_make() {
                 d[0] = i == 200 ? 0.5f * t.wc[i * 201 + k] : t.wc[i * 201 + k]; // u_200 = 2 x_200
                 d[1] = i == 200 ? 0.f : t.ws[i * 201 + k];                       // v_200 = 0
             }
-    const double mmax = 15.0 + std::log(8000.0 / 1000.0) / (std::log(6.4) / 27.0);
     for (int v = 0; v < 2; v++) {
         const int n_mels = v ? 128 : 80, MB = n_mels / 32 + (n_mels % 32 != 0);
-        std::vector<double> pts(n_mels + 2);
-        for (int j = 0; j < n_mels + 2; j++) pts[j] = mel_point_hz(j == n_mels + 1 ? mmax : j * (mmax / (n_mels + 1)));
-        t.bank[v].assign((size_t)n_mels * 201, 0.f);
-        for (int j = 0; j < n_mels; j++) {
-            const double lo = pts[j], ce = pts[j + 1], hi = pts[j + 2];
-            for (int k = 0; k <= 200; k++) {
-                const double fr = 40.0 * k, lower = (fr - lo) / (ce - lo), upper = (hi - fr) / (hi - ce);
-                const double w = std::fmax(0.0, std::fmin(lower, upper));
-                t.bank[v][(size_t)j * 201 + k] = (float)(w * (2.0 / (hi - lo)));
-            }
-        }
+        mel_bank_make(40.0, OPUSGPU_MEL_BINS, n_mels, false, true, OPUSGPU_MEL_FMIN, OPUSGPU_MEL_FMAX, t.bank[v]);
         t.fb[v].assign((size_t)MEL_NB * MB * 16 * 64, 0.f);
         for (int nb = 0; nb < MEL_NB; nb++)
             for (int mm = 0; mm < MB; mm++)

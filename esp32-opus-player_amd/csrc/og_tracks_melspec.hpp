@@ -1,0 +1,468 @@
+// og_tracks_melspec.hpp -- mel spectrograms of the mono track at any rate, n_fft and hop (include/opusgpu.h, TRACK SPECTROGRAMS): the
+// tables per parameter set, the kernel that turns packed int16 mono tracks into float32 feature tracks, its host side, and the
+// whole-file call that ends in it.  Included at the end of og_api.hip behind og_tracks_mel.hpp, whose table builders
+// (mel_basis_make, mel_bank_make), span record and design it shares, and in front of og_ms_tracks.hpp, which holds the multistream
+// twin of the whole-file call.
+#pragma once
+#include <map>
+#include <memory>
+#include <mutex>
+#include <tuple>
+
+// ---- kernel -------------------------------------------------------------------------------------------
+// k_tracks_melspec: k_tracks_mel (og_tracks_mel.hpp, whose head comment says what the four steps are) with its constants as
+// arguments.  One workgroup per entry of a tile table built on the host, a tile being T = 128, 64 or 32 consecutive frames of one
+// track, 32 per wave: the workgroup has T / 32 waves.  What differs:
+//   1. STAGE.  The tile's window -- W = (T - 1) hop + n_fft samples, the first of them sample hop * first - n_fft / 2 of the track
+//      -- lies in LDS cut by phase: place p is at row p % hop, column p / hop, the rows packed without room between them (the first
+//      W % hop rows hold W / hop + 1 places, the others W / hop), so a window of 32,768 samples takes 65,536 bytes whatever the hop.
+//      Neither the hop nor the window's first sample need be a multiple of 8: the track comes through aligned 16-byte loads of the
+//      BUFFER, one piece per lane, and every sample of a piece finds its own place (a piece does not stay in one row).  Nothing is
+//      read behind the piece that holds the track's last sample.  The places in front of the track and behind it are then filled by
+//      the reflection rule from LDS -- or, where the reflected sample lies in front of the window (the last frame of F = n / hop + 1
+//      when hop divides n and that frame is its tile's first), from the track itself --, 0 outside the track.  Only the places that
+//      the tile's WORKING waves read are filled.
+//   2. DFT.  The fold of k_tracks_mel: taps 1 .. n_fft / 2 of u_i = x_i + x_{n_fft - i} and v_i = x_i - x_{n_fft - i} (w[0] = 0 and
+//      w[i] = w[n_fft - i] for every window of the section), row n_fft / 2 halved for u and zero for v, n_fft / 4 k-steps of two
+//      taps.  A lane walks its two taps' (row, column) by additions: there is no division in the loop.  Only the blocks of 32 bins
+//      that a band weights are walked (the host's list: the tables hold those blocks alone), and a wave whose 32 frames all lie at or
+//      behind the track's F walks none and stores nothing; it still reaches every barrier.
+//   3. POWER, MEL.  S = Re^2 + Im^2 or its sqrtf, in the accumulators, is the B operand of the band product; four blocks of 32
+//      bands, those without a weight in the bin block skipped (4 mask bits per kept bin block, with the kernel's arguments).
+//   4. STORE.  max(mel, floor), its log10f or logf or neither, through LDS into the destination's order and out in aligned 16-byte
+//      pieces where a piece is whole and aligned (frames-major rows of an n_mels that is no multiple of 4 are not: element stores).
+// No float atomics, no sum whose order depends on the launch: the same input gives the same bits.
+constexpr int MS_MAXW = 32768;      // samples of the largest window: 65,536 bytes of LDS, which a launch asks for by its own window
+constexpr int MS_MAXBLK = 33;       // blocks of 32 bins at n_fft 2048
+struct MsArgs {
+    i32 n_fft, hop, n_mels;
+    i32 n_blocks;                   // kept blocks of 32 bins
+    i32 power, log, whisper_frames, frames_major;
+    float floor;
+    u8 mask[MS_MAXBLK + 3];         // bit mm of mask[b]: band block mm has a weight in kept bin block b
+};
+
+__global__ void __launch_bounds__(256) k_tracks_melspec(const MelTile *__restrict__ tiles, const MelSpan *__restrict__ spans,
+                                                        const i16 *__restrict__ in, const float2 *__restrict__ basis,
+                                                        const float *__restrict__ fb, MsArgs a, float *__restrict__ out) {
+    extern __shared__ __align__(16) i16 lds[]; // the window by phase, W places (spec_lds_bytes); afterwards a store area of [32][MEL_STG] floats per wave
+    const int tid = (int)threadIdx.x, nthr = (int)blockDim.x, lane = tid & 63, wave = tid >> 6;
+    const int T = nthr >> 1, N = a.n_fft, H = a.hop;
+    const MelTile tl = tiles[blockIdx.x];
+    const MelSpan sp = spans[tl.track];
+    const long long n = sp.in_samples;
+    const long long F = a.whisper_frames ? n / H : n ? n / H + 1 : 0;
+    const long long left = F - tl.first;
+    const int nf = left < T ? (int)left : T; // frames of this tile that exist
+    if (nf <= 0) return;
+    const int waves_on = (nf + 31) >> 5;                       // waves that have a frame
+    const int W = (T - 1) * H + N;                             // the tile's window, which fixes the places
+    const int Wuse = (32 * waves_on - 1) * H + N;              // what the working waves read of it
+    const int Qm = W / H, Qr = W % H;                          // row `ph` begins at ph * Qm + min(ph, Qr)
+    auto place = [=](int p) {
+        const int ph = p % H;
+        return ph * Qm + (ph < Qr ? ph : Qr) + p / H;
+    };
+
+    // 1. the window -> LDS
+    const i16 *const trk = in + sp.in_offset;
+    const long long base = (long long)H * tl.first - N / 2;    // its first sample, counted from the track's
+    const long long qa = base < 0 ? 0 : base;                  // the track's samples inside what is used of it: [qa, qb)
+    const long long qb = n < base + Wuse ? n : base + Wuse;
+    for (long long k = (qa >> 3) + tid; 8 * k < qb; k += nthr) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(trk + 8 * k);
+        const u32 w32[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int h = 0; h < 8; h++) {
+            const long long q = 8 * k + h;
+            if (q >= qa && q < qb) lds[place((int)(q - base))] = (i16)(w32[h >> 1] >> (16 * (h & 1)));
+        }
+    }
+    __syncthreads();
+    {
+        const int lo_n = base < 0 ? (int)-base : 0;                     // places in front of the track
+        const int hi_0 = n - base < Wuse ? (int)(n - base) : Wuse;      // the first place behind it
+        for (int x = tid; x < lo_n + (Wuse - hi_0); x += nthr) {
+            const int p = x < lo_n ? x : hi_0 + (x - lo_n);
+            const long long q = base + p;
+            const long long r = q < 0 ? -q : 2 * (n - 1) - q;           // reflected once
+            i16 s = 0;
+            if (r >= 0 && r < n) s = r >= qa && r < qb ? lds[place((int)(r - base))] : trk[r]; // places of the track: not written here
+            lds[place(p)] = s;
+        }
+    }
+    __syncthreads();
+
+    // 2. and 3. 32 frames per wave: the kept bin blocks, then the bands
+    const int fl = lane & 31, kh = lane >> 5;
+    const float scale = sp.scale;
+    og_f32x16 mel[4];
+#pragma unroll
+    for (int mm = 0; mm < 4; mm++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) mel[mm][r] = 0.f;
+    if (wave < waves_on && a.n_blocks > 0) { // (no kept block: no band has a weight, and mel stays 0)
+        const int KS = N >> 2;
+        const int m2 = 2 % H, d2 = 2 / H;
+        const int ia0 = 1 + kh - 2, ib0 = N - ia0;       // one step in front of the lane's first taps, 1 + kh and n_fft - 1 - kh
+        const int f = wave * 32 + fl;                    // the lane's frame in the tile
+        const int pa0 = ia0 < 0 ? H - 1 - ((-ia0 - 1) % H) : ia0 % H, ca0 = ia0 < 0 ? -1 - (-ia0 - 1) / H : ia0 / H;
+        const int pb0 = ib0 % H, cb0 = ib0 / H;
+        // the basis comes a k-step at a time, 512 bytes per wave, from L2 at best: requested two groups of 4 k-steps ahead of its
+        // use (the table is one run over all kept blocks), or every k-step would wait out a load with nothing to hide it behind
+        const int G = KS >> 2, GT = a.n_blocks * G;
+        const float2 *const bp = basis + lane;
+        float2 w0[4], w1[4], w2[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) w0[j] = bp[(size_t)j * 64], w1[j] = bp[(size_t)(4 * (GT > 1 ? 1 : 0) + j) * 64];
+        int gg = 0;
+        for (int b = 0; b < a.n_blocks; b++) {
+            og_f32x16 re, im;
+#pragma unroll
+            for (int r = 0; r < 16; r++) re[r] = 0.f, im[r] = 0.f;
+            int pa = pa0, ca = ca0 + f, pb = pb0, cb = cb0 + f;
+            for (int g = 0; g < G; g++, gg++) {
+                const int ahead = gg + 2 < GT ? gg + 2 : GT - 1;
+#pragma unroll
+                for (int j = 0; j < 4; j++) w2[j] = bp[(size_t)(4 * ahead + j) * 64];
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    pa += m2, ca += d2;
+                    if (pa >= H) pa -= H, ca++;
+                    pb -= m2, cb -= d2;
+                    if (pb < 0) pb += H, cb--;
+                    const float xa = __fmul_rn((float)lds[pa * Qm + (pa < Qr ? pa : Qr) + ca], scale);
+                    const float xb = __fmul_rn((float)lds[pb * Qm + (pb < Qr ? pb : Qr) + cb], scale);
+                    re = __builtin_amdgcn_mfma_f32_32x32x2f32(w0[j].x, xa + xb, re, 0, 0, 0);
+                    im = __builtin_amdgcn_mfma_f32_32x32x2f32(w0[j].y, xa - xb, im, 0, 0, 0);
+                }
+#pragma unroll
+                for (int j = 0; j < 4; j++) w0[j] = w1[j], w1[j] = w2[j];
+            }
+            og_f32x16 P = re * re + im * im;
+            if (a.power == 1) {
+#pragma unroll
+                for (int r = 0; r < 16; r++) P[r] = sqrtf(P[r]);
+            }
+            const u32 mk = a.mask[b];
+#pragma unroll
+            for (int mm = 0; mm < 4; mm++) {
+                if ((mk >> mm) & 1) { // wave-uniform
+                    const float *const fp = fb + (size_t)((b * 4 + mm) * 16) * 64 + lane;
+#pragma unroll
+                    for (int r = 0; r < 16; r++) mel[mm] = __builtin_amdgcn_mfma_f32_32x32x2f32(fp[r * 64], P[r], mel[mm], 0, 0, 0);
+                }
+            }
+        }
+    }
+    __syncthreads(); // every wave has read its last sample
+
+    // 4. floor, log and out, 32 bands at a time: register r of the lane is band 8 (r >> 2) + 4 kh + (r & 3) of the block, frame fl
+    float *const stg = reinterpret_cast<float *>(lds) + wave * 32 * MEL_STG;
+    const int wf = nf - wave * 32 < 32 ? nf - wave * 32 : 32; // frames of this wave that exist (may be <= 0)
+    float *const dst = out + sp.out_offset;
+    const long long f0 = (long long)tl.first + wave * 32;
+    const int n_mels = a.n_mels, frames_major = a.frames_major;
+    const bool whole4 = (n_mels & 3) == 0;
+#pragma unroll
+    for (int mm = 0; mm < 4; mm++) {
+        if (32 * mm < n_mels) { // the same for every wave: the barriers inside are reached by all
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                const int band = 8 * (r >> 2) + 4 * kh + (r & 3);
+                float v = fmaxf(mel[mm][r], a.floor);
+                if (a.log == 1) v = log10f(v);
+                if (a.log == 2) v = logf(v);
+                stg[frames_major ? fl * MEL_STG + band : band * MEL_STG + fl] = v;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int it = 0; it < 4; it++) { // 32 rows of 8 pieces
+                const int row = (lane + 64 * it) >> 3, pc = lane & 7;
+                const og_f32x4 v = *reinterpret_cast<const og_f32x4 *>(stg + row * MEL_STG + 4 * pc);
+                if (frames_major) { // row: frame, piece: bands 32 mm + 4 pc .. + 3
+                    const int j0 = 32 * mm + 4 * pc;
+                    if (row < wf && j0 < n_mels) {
+                        float *const d = dst + (f0 + row) * n_mels + j0;
+                        if (whole4) {
+                            *reinterpret_cast<og_f32x4 *>(d) = v;
+                        } else {
+#pragma unroll
+                            for (int h = 0; h < 4; h++)
+                                if (j0 + h < n_mels) d[h] = v[h];
+                        }
+                    }
+                } else {            // row: band, piece: frames f0 + 4 pc .. + 3
+                    if (32 * mm + row < n_mels && 4 * pc < wf) {
+                        float *const d = dst + (32 * mm + row) * sp.plane + f0 + 4 * pc;
+                        if (4 * pc + 4 <= wf) {
+                            *reinterpret_cast<og_f32x4 *>(d) = v;
+                        } else {
+#pragma unroll
+                            for (int h = 0; h < 4; h++)
+                                if (4 * pc + h < wf) d[h] = v[h];
+                        }
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// ---- tables -------------------------------------------------------------------------------------------
+// TRACK SPECTROGRAMS, TABLES: made in double at first use, rounded once, kept per distinct set of the fields that reach them for the
+// life of the process: the tables as the accessors hand them out, and the same numbers in the order the kernel's lanes load them.
+struct SpecTables {
+    int n_fft = 0, bins = 0, n_mels = 0;
+    std::vector<float> wc, ws;      // [n_fft][bins]
+    std::vector<float> bank;        // [n_mels][bins]
+    std::vector<int> blocks;        // the blocks of 32 bins in which the bank has a non-zero entry
+    std::vector<float> basis;       // [kept block][n_fft / 4][64 lanes][cos, sin]: tap 1 + 2 ks + (lane >> 5), bin 32 nb + (lane & 31)
+    std::vector<float> fb;          // [kept block][4][16][64 lanes]: band 32 mm + (lane & 31), bin 32 nb + 8 (r >> 2) + 4 (lane >> 5) + (r & 3)
+    u8 mask[MS_MAXBLK + 3] = {};
+};
+typedef std::tuple<int, int, int, int, int, int, float, float> SpecKey; // sample_rate, n_fft, win, n_mels, mel_scale, norm, fmin, fmax
+
+static int spec_win(const opusgpu_spec_params &p) { return p.win_length ? p.win_length : p.n_fft; }
+
+static bool spec_params_ok(const opusgpu_spec_params *p) {
+    if (!p) return false;
+    if (p->n_fft < 64 || p->n_fft > 2048 || p->n_fft % 16) return false;
+    if (p->win_length && (p->win_length < 16 || p->win_length > p->n_fft || p->win_length % 2)) return false;
+    if (p->hop < 1 || p->hop > p->n_fft || 31 * p->hop + p->n_fft > MS_MAXW) return false;
+    if (p->n_mels < 1 || p->n_mels > 128) return false;
+    if (p->mel_scale != OPUSGPU_SPEC_SLANEY && p->mel_scale != OPUSGPU_SPEC_HTK) return false;
+    if (p->norm != OPUSGPU_SPEC_NORM_SLANEY && p->norm != OPUSGPU_SPEC_NORM_NONE) return false;
+    if (p->power != 1 && p->power != 2) return false;
+    if (p->log != OPUSGPU_SPEC_LOG_NONE && p->log != OPUSGPU_SPEC_LOG10 && p->log != OPUSGPU_SPEC_LN) return false;
+    if (p->frames != OPUSGPU_SPEC_FRAMES_TORCH && p->frames != OPUSGPU_SPEC_FRAMES_WHISPER) return false;
+    if (p->layout != OPUSGPU_MEL_BANDS_MAJOR && p->layout != OPUSGPU_MEL_FRAMES_MAJOR) return false;
+    if (p->sample_rate < 1 || p->sample_rate > 1048576) return false;
+    if (!(p->fmin >= 0.f) || !(p->fmin < p->fmax) || !((double)p->fmax <= p->sample_rate / 2.0)) return false;
+    if (!std::isfinite(p->floor) || p->floor < 0.f || (p->log != OPUSGPU_SPEC_LOG_NONE && !(p->floor > 0.f))) return false;
+    return !p->reserved[0] && !p->reserved[1];
+}
+
+static std::unique_ptr<SpecTables> spec_tables_make(const opusgpu_spec_params &p) {
+    std::unique_ptr<SpecTables> t(new SpecTables);
+    const int N = p.n_fft, bins = N / 2 + 1, KS = N / 4, n_mels = p.n_mels;
+    t->n_fft = N, t->bins = bins, t->n_mels = n_mels;
+    mel_basis_make(N, spec_win(p), t->wc, t->ws);
+    mel_bank_make((double)p.sample_rate / N, bins, n_mels, p.mel_scale == OPUSGPU_SPEC_HTK, p.norm == OPUSGPU_SPEC_NORM_SLANEY, p.fmin, p.fmax,
+                  t->bank);
+    const int nblk = (bins + 31) / 32;
+    for (int nb = 0; nb < nblk; nb++) {
+        bool any = false;
+        for (int j = 0; j < n_mels && !any; j++)
+            for (int k = 32 * nb; k < 32 * nb + 32 && k < bins && !any; k++) any = t->bank[(size_t)j * bins + k] != 0.f;
+        if (any) t->blocks.push_back(nb);
+    }
+    const size_t nk = t->blocks.size();
+    t->basis.assign(nk * KS * 64 * 2, 0.f);
+    t->fb.assign(nk * 4 * 16 * 64, 0.f);
+    for (size_t b = 0; b < nk; b++) {
+        const int nb = t->blocks[b];
+        for (int ks = 0; ks < KS; ks++)
+            for (int lane = 0; lane < 64; lane++) {
+                const int i = 1 + 2 * ks + (lane >> 5), k = 32 * nb + (lane & 31);
+                if (k >= bins) continue;
+                float *const d = &t->basis[((b * KS + ks) * 64 + lane) * 2];
+                d[0] = i == N / 2 ? 0.5f * t->wc[(size_t)i * bins + k] : t->wc[(size_t)i * bins + k]; // u = 2 x at the middle tap
+                d[1] = i == N / 2 ? 0.f : t->ws[(size_t)i * bins + k];                                  // v = 0 there
+            }
+        for (int mm = 0; mm < 4; mm++)
+            for (int r = 0; r < 16; r++)
+                for (int lane = 0; lane < 64; lane++) {
+                    const int j = 32 * mm + (lane & 31), k = 32 * nb + 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3);
+                    if (j >= n_mels || k >= bins) continue;
+                    const float w = t->bank[(size_t)j * bins + k];
+                    t->fb[((b * 4 + mm) * 16 + r) * 64 + lane] = w;
+                    if (w != 0.f) t->mask[b] |= (u8)(1u << mm);
+                }
+    }
+    return t;
+}
+
+// The tables of a parameter set that spec_params_ok has passed; safe from any number of threads.
+static const SpecTables &spec_tables(const opusgpu_spec_params &p) {
+    static std::mutex mu;
+    static std::map<SpecKey, std::unique_ptr<SpecTables>> cache;
+    const SpecKey key(p.sample_rate, p.n_fft, spec_win(p), p.n_mels, p.mel_scale, p.norm, p.fmin, p.fmax);
+    std::lock_guard<std::mutex> lock(mu);
+    auto it = cache.find(key);
+    if (it == cache.end()) it = cache.emplace(key, spec_tables_make(p)).first;
+    return *it->second;
+}
+
+// ---- host side ----------------------------------------------------------------------------------------
+static int64_t spec_frames(const opusgpu_spec_params &p, int64_t n) {
+    return p.frames == OPUSGPU_SPEC_FRAMES_WHISPER ? n / p.hop : n ? n / p.hop + 1 : 0;
+}
+// The tile in frames: the largest of 128, 64, 32 whose window fits the kernel's LDS (32 does: spec_params_ok).
+static int spec_tile(const opusgpu_spec_params &p) {
+    for (int T = 128; T > 32; T >>= 1)
+        if ((T - 1) * p.hop + p.n_fft <= MS_MAXW) return T;
+    return 32;
+}
+
+// A launch's LDS: the tile's window as int16, and no less than the waves' store areas; at most 65,536 bytes (spec_tile).
+static size_t spec_lds_bytes(const opusgpu_spec_params &p, int T) {
+    const size_t window = ((size_t)(T - 1) * p.hop + p.n_fft) * 2, store = (size_t)(T / 32) * 32 * MEL_STG * 4;
+    return ((window > store ? window : store) + 15) / 16 * 16;
+}
+
+// The kernel over n tracks: checks the spans, builds the tile table, uploads it with the spans and the tables, launches on `s` and
+// waits; every device buffer of the call is freed on every way out.
+template <class Fail>
+static int tracks_melspec_run(int device, hipStream_t s, int n_tracks, const opusgpu_mel_span *spans, const void *d_in,
+                              const opusgpu_spec_params *params, void *d_out, Fail hip_failed) {
+    if (!spec_params_ok(params) || n_tracks < 0 || (n_tracks && !spans)) return OPUSGPU_BAD_ARG;
+    const int T = spec_tile(*params);
+    std::vector<MelTile> tiles;
+    for (int t = 0; t < n_tracks; t++) {
+        const opusgpu_mel_span &sp = spans[t];
+        if (sp.in_offset < 0 || sp.in_offset % 8 || sp.in_samples < 0 || sp.out_offset < 0 || sp.out_offset % 64 || sp.reserved)
+            return OPUSGPU_BAD_ARG;
+        const int64_t F = spec_frames(*params, sp.in_samples);
+        if (sp.plane < F || sp.plane % 64 || !std::isfinite(sp.scale)) return OPUSGPU_BAD_ARG;
+        if (F > 0x7fffffff - T || (F + T - 1) / T + (int64_t)tiles.size() > 0x7fffffff) return OPUSGPU_BAD_ARG;
+        for (int64_t f = 0; f < F; f += T) tiles.push_back(MelTile{t, (i32)f});
+    }
+    if (tiles.empty()) return OPUSGPU_OK;
+    if (!d_in || !d_out || ((uintptr_t)d_in & 15) || ((uintptr_t)d_out & 127)) return OPUSGPU_BAD_ARG;
+    const SpecTables &tab = spec_tables(*params);
+    MsArgs a{};
+    a.n_fft = params->n_fft, a.hop = params->hop, a.n_mels = params->n_mels, a.n_blocks = (i32)tab.blocks.size();
+    a.power = params->power, a.log = params->log, a.whisper_frames = params->frames == OPUSGPU_SPEC_FRAMES_WHISPER;
+    a.frames_major = params->layout == OPUSGPU_MEL_FRAMES_MAJOR, a.floor = params->floor;
+    std::copy(std::begin(tab.mask), std::end(tab.mask), a.mask);
+#define MS_CHK(call)                                                              \
+    do {                                                                          \
+        const hipError_t e_ = (call);                                             \
+        if (e_ != hipSuccess) return hip_failed(OPUSGPU_ERR_HIP, #call, e_);      \
+    } while (0)
+    MS_CHK(hipSetDevice(device));
+    RsDevBuf d_spans, d_tiles, d_basis, d_fb;
+    MS_CHK(d_spans.upload(spans, (size_t)n_tracks * sizeof(MelSpan)));
+    MS_CHK(d_tiles.upload(tiles.data(), tiles.size() * sizeof(MelTile)));
+    MS_CHK(d_basis.upload(tab.basis.data(), tab.basis.size() * sizeof(float)));
+    MS_CHK(d_fb.upload(tab.fb.data(), tab.fb.size() * sizeof(float)));
+    hipLaunchKernelGGL(k_tracks_melspec, dim3((unsigned)tiles.size()), dim3(2 * T), spec_lds_bytes(*params, T), s, (const MelTile *)d_tiles.p, (const MelSpan *)d_spans.p,
+                       (const i16 *)d_in, (const float2 *)d_basis.p, (const float *)d_fb.p, a, (float *)d_out);
+    MS_CHK(hipGetLastError());
+    MS_CHK(hipStreamSynchronize(s));
+#undef MS_CHK
+    return OPUSGPU_OK;
+}
+
+static int64_t spec_plane(const opusgpu_spec_params &p, int64_t planned_48k, int up, int down) {
+    return rs_round64(spec_frames(p, (planned_48k * up + down - 1) / down));
+}
+static bool spec_ratio_ok(int up, int down) { return up >= 1 && up <= down && down <= 48000; }
+
+// What the whole-file calls refuse before any device work -> the track's up / down of 48 kHz (1 / D for a rate), or false.
+static bool files_melspec_args(const og_batch &b, int rate, int &up, int &down, int mono, const opusgpu_mix_matrix *mix,
+                               const opusgpu_spec_params *params, const float *scale, const void *d_out) {
+    if (!spec_params_ok(params) || ((uintptr_t)d_out & 127)) return false;
+    if (mix ? mono || mix->out_channels != 1 : !mono) return false;
+    if (rate) {
+        if (up || down) return false;
+        const int D = rs_args_factor(b.channels, rate, mono, OPUSGPU_TRACKS_S16, mix);
+        if (!D) return false;
+        up = 1, down = D;
+    } else {
+        if (!rr_args_taps(b.channels, up, down, mono, OPUSGPU_TRACKS_S16, mix)) return false;
+        if (48000LL * up % down) return false; // the track's rate is no integer: no sample_rate names it
+    }
+    if ((int64_t)params->sample_rate * down != 48000LL * up) return false;
+    return rs_scale_ok(OPUSGPU_TRACKS_F32, scale, b.n_files);
+}
+
+// Both whole-file calls: files_resampled_run or files_ratio_run (with the caller's decoder) into a scratch buffer of int16 mono
+// tracks at the spectrogram's rate, on that call's grid -- the 48 kHz scratch is theirs and is gone when they return --, then
+// k_tracks_melspec from there into d_out.  The caller's arrays are written last.
+template <class Decode, class Fail>
+static int files_melspec_run(const og_batch &b, int device, hipStream_t s, int rate, int up, int down, int mono, const opusgpu_mix_matrix *mix,
+                             const opusgpu_spec_params *params, const float *scale, void *d_out, int64_t *feat_offsets, int64_t *frames_out,
+                             int64_t *track_lengths_out, int32_t *status_out, Decode decode, Fail hip_failed) {
+    if (!files_melspec_args(b, rate, up, down, mono, mix, params, scale, d_out)) return OPUSGPU_BAD_ARG;
+    const size_t n = (size_t)b.n_files;
+    std::vector<int64_t> planned(n), offs(n, 0), len(n, 0), lengths(n, 0), feat(n, 0);
+    std::vector<int32_t> status(2 * n, 0);
+    for (size_t i = 0; i < n; i++) planned[i] = b.info[i].track_samples;
+    const int64_t total = rate ? opusgpu_resample_layout((int)n, planned.data(), rate, nullptr)
+                               : opusgpu_resample_ratio_layout((int)n, planned.data(), up, down, nullptr);
+    if (total < 0 || opusgpu_spec_layout((int)n, planned.data(), up, down, params, feat.data()) < 0) return OPUSGPU_BAD_ARG;
+    RsDevBuf y; // the int16 mono tracks at the spectrogram's rate, for the length of this call
+    if (!b.segs.empty()) {
+        hipError_t e = hipSetDevice(device);
+        if (e == hipSuccess) e = y.alloc((size_t)total * 2 + 128);
+        if (e != hipSuccess) return hip_failed(OPUSGPU_ALLOC_FAIL, "hipMalloc(spectrogram scratch)", e);
+    }
+    const int rc = rate ? files_resampled_run(b, device, s, rate, mono, OPUSGPU_TRACKS_S16, nullptr, y.p, offs.data(), len.data(), lengths.data(),
+                                              status.data(), decode, hip_failed, mix)
+                        : files_ratio_run(b, device, s, up, down, mono, mix, OPUSGPU_TRACKS_S16, nullptr, y.p, offs.data(), len.data(),
+                                          lengths.data(), status.data(), decode, hip_failed);
+    if (rc) return rc;
+    std::vector<opusgpu_mel_span> spans(n);
+    for (size_t i = 0; i < n; i++)
+        spans[i] = opusgpu_mel_span{offs[i], len[i], feat[i], spec_plane(*params, planned[i], up, down), scale ? scale[i] : 1.0f / 32768, 0};
+    if (int rc2 = tracks_melspec_run(device, s, (int)n, spans.data(), y.p, params, d_out, hip_failed)) return rc2;
+    for (size_t i = 0; i < n; i++) {
+        if (feat_offsets) feat_offsets[i] = feat[i];
+        if (frames_out) frames_out[i] = spec_frames(*params, len[i]);
+        if (track_lengths_out) track_lengths_out[i] = lengths[i];
+    }
+    if (status_out) std::copy(status.begin(), status.end(), status_out);
+    return OPUSGPU_OK;
+}
+
+extern "C" {
+
+int opusgpu_spec_basis(const opusgpu_spec_params *p, const float **wc, const float **ws) {
+    if (!spec_params_ok(p)) return OPUSGPU_BAD_ARG;
+    const SpecTables &t = spec_tables(*p);
+    if (wc) *wc = t.wc.data();
+    if (ws) *ws = t.ws.data();
+    return t.n_fft * t.bins;
+}
+
+int opusgpu_spec_filterbank(const opusgpu_spec_params *p, const float **b) {
+    if (!spec_params_ok(p)) return OPUSGPU_BAD_ARG;
+    const SpecTables &t = spec_tables(*p);
+    if (b) *b = t.bank.data();
+    return t.n_mels * t.bins;
+}
+
+int64_t opusgpu_spec_layout(int n, const int64_t *planned_48k_samples, int up, int down, const opusgpu_spec_params *p, int64_t *feat_offsets) {
+    if (!spec_params_ok(p) || !spec_ratio_ok(up, down) || n < 0 || (n && !planned_48k_samples)) return OPUSGPU_BAD_ARG;
+    int64_t at = 0;
+    for (int i = 0; i < n; i++) {
+        if (planned_48k_samples[i] < 0 || planned_48k_samples[i] > INT64_MAX / 65536) return OPUSGPU_BAD_ARG;
+        if (feat_offsets) feat_offsets[i] = at;
+        at += p->n_mels * spec_plane(*p, planned_48k_samples[i], up, down);
+    }
+    return at;
+}
+
+int opusgpu_tracks_melspec_device(opusgpu_ctx *ctx, int n_tracks, const opusgpu_mel_span *spans, const void *d_in_mono,
+                                  const opusgpu_spec_params *p, void *d_out, void *hip_stream) {
+    if (!ctx) return OPUSGPU_BAD_ARG;
+    return tracks_melspec_run(ctx->device, hip_stream ? (hipStream_t)hip_stream : ctx->stream, n_tracks, spans, d_in_mono, p, d_out,
+                              [&](int code, const char *what, hipError_t e) { return fail(ctx, code, what, e); });
+}
+
+int opusgpu_files_decode_melspec(opusgpu_ctx *ctx, const opusgpu_file_batch *batch, int rate, int up, int down, int mono,
+                                 const opusgpu_mix_matrix *mix, const opusgpu_spec_params *p, const float *scale, void *d_out,
+                                 int64_t *feat_offsets, int64_t *frames_out, int64_t *track_lengths_out, int32_t *status_out) {
+    if (!ctx || !batch) return OPUSGPU_BAD_ARG;
+    return files_melspec_run(
+        *batch, ctx->device, ctx->stream, rate, up, down, mono, mix, p, scale, d_out, feat_offsets, frames_out, track_lengths_out, status_out,
+        [&](void *d_s16, int64_t *lengths, int32_t *status) {
+            return files_decode_run(ctx, batch, OPUSGPU_TRACKS_S16, nullptr, d_s16, lengths, status);
+        },
+        [&](int code, const char *what, hipError_t e) { return fail(ctx, code, what, e); });
+}
+
+} // extern "C"

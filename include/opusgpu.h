@@ -859,6 +859,98 @@ int opusgpu_files_decode_mel(opusgpu_ctx *ctx, const opusgpu_file_batch *batch, 
                              const opusgpu_mel_params *params, const float *scale, void *d_out, int64_t *feat_offsets, int64_t *frames_out,
                              int64_t *track_lengths_out, int32_t *status_out);
 
+/* TRACK SPECTROGRAMS.  Mel spectrograms of the mono track at any rate of TRACK RATES and TRACK RATIOS, with the numbers that
+ * torchaudio.transforms.MelSpectrogram and librosa.feature.melspectrogram take as FIELDS: the front ends of vocoders (22050 Hz,
+ * 1024 / 256, 80 Slaney bands, ln of the magnitude), Kaldi-style filterbanks (16000 Hz, 512 / 400 / 160, HTK), audio taggers (48000 or
+ * 32000 Hz, 64 HTK bands) and music models (44100 Hz, 2048 / 441), in the same call that decodes the files.  TRACK FEATURES, its
+ * record, its refusals and its kernel are unchanged: this is a section of its own with a record, calls and a kernel of its own.
+ * The definition is this comment.
+ *   INPUT.  An int16 mono track y[m], m in [0, n), exactly as TRACK RATES, TRACK RATIOS and CHANNEL MIX define it.
+ *   FRAMES.  OPUSGPU_SPEC_FRAMES_TORCH: F = n / hop + 1 (floor; F = 0 for n == 0), torch.stft(center=True).  _WHISPER: F = n / hop.
+ *   WINDOW.  L = win_length (n_fft if 0), left = (n_fft - L) / 2; w[i] = 0.5 - 0.5 cos(2 pi (i - left) / L) for i in [left, left + L),
+ *   else 0: the periodic Hann window that torch.stft centres in the frame.  n_fft and L are even, so w[i] = w[n_fft - i].
+ *   WINDOW INDEX.  TRACK FEATURES' rule with the constants as fields: frame f, tap i in [0, n_fft) reads q = hop * f - n_fft / 2 + i,
+ *   reflected ONCE: q < 0 becomes -q, q >= n becomes 2 (n - 1) - q; if q is still outside [0, n) the sample is 0.  Unlike
+ *   torch.stft, which refuses n <= n_fft / 2, the value is defined for every n.
+ *   SAMPLE.  x_i = (float)y[q] * scale[track], one IEEE multiply; the default scale is 1 / 32768.
+ *   DFT.  Re[k] = sum_i Wc[i][k] x_i, Im[k] = sum_i Ws[i][k] x_i, k in [0, n_fft / 2]; Wc[i][k] = w[i] cos(a), Ws[i][k] = w[i] sin(a),
+ *   a = 2 pi ((i k) mod n_fft) / n_fft.  S[k] = Re^2 + Im^2 (power 2) or sqrtf of it (power 1).
+ *   MEL.  mel[j] = sum_k B[j][k] S[k], j in [0, n_mels).
+ *   OUTPUT.  v = max(mel[j], floor); v, log10f(v) or logf(v) as `log` says, float32.
+ *   FILTERBANK.  Bin k lies at k * (sample_rate / n_fft) Hz, in double.  OPUSGPU_SPEC_SLANEY: mel(f) = 3 f / 200 below 1000 Hz, else
+ *   15 + ln(f / 1000) / (ln 6.4 / 27); hz(m) as TRACK FEATURES writes it.  OPUSGPU_SPEC_HTK: mel(f) = 2595 log10(1 + f / 700), hz(m) =
+ *   700 (10^(m / 2595) - 1).  m0 = mel(fmin), m1 = mel(fmax); p[j] = hz(m0 + j * ((m1 - m0) / (n_mels + 1))) for j in [0, n_mels],
+ *   p[n_mels + 1] = hz(m1); B[j][k] = max(0, min((fk - p[j]) / (p[j + 1] - p[j]), (p[j + 2] - fk) / (p[j + 2] - p[j + 1]))), times
+ *   2 / (p[j + 2] - p[j]) for OPUSGPU_SPEC_NORM_SLANEY only.
+ *   TABLES.  float32, each entry computed in double and rounded once, at first use, kept per distinct (sample_rate, n_fft, win_length,
+ *   n_mels, mel_scale, norm, fmin, fmax) for the life of the process and safe to ask for from any number of threads.  A cached set
+ *   holds Wc and Ws -- 2 x n_fft x (n_fft / 2 + 1) floats, 2 x 2048 x 1025 floats = 16.8 MB at the top end --, B, and the kernel's
+ *   copy of the half of the basis and of B that it multiplies (half of that again at most).  With Whisper's numbers (16000, 400,
+ *   0 or 400, 160, 80 or 128, Slaney, Slaney, 0, 8000) Wc, Ws and B are opusgpu_mel_basis' and opusgpu_mel_filterbank's bit for bit:
+ *   one builder makes both.
+ *   SUMMATION ORDER is not part of the contract, as in TRACK FEATURES (the kernel folds x_i +- x_{n_fft - i} against half the
+ *   basis).  What is: the tolerance of tests/test_gpu_tracks_melspec.py (8 x the error of a float32 restatement against float64,
+ *   DESIGN.md section 13f), the same bits from the same call on the same input, and one bit pattern in every cell of an all-zero
+ *   track.
+ *   LAYOUT.  TRACK FEATURES' grid with the new F: plane[t] = roundup64(F(ceil(planned_48k[t] * up / down))), up / down the track's
+ *   rate over 48000 (1 / D for a rate of TRACK RATES); feat_offset[t] the running sum of n_mels * plane[u]; both layouts of TRACK
+ *   FEATURES; padding is never written; a track cut short by a failed frame keeps its planned plane and reports its shorter F. */
+#define OPUSGPU_SPEC_SLANEY 0
+#define OPUSGPU_SPEC_HTK 1
+#define OPUSGPU_SPEC_NORM_SLANEY 0
+#define OPUSGPU_SPEC_NORM_NONE 1
+#define OPUSGPU_SPEC_LOG_NONE 0
+#define OPUSGPU_SPEC_LOG10 1
+#define OPUSGPU_SPEC_LN 2
+#define OPUSGPU_SPEC_FRAMES_TORCH 0
+#define OPUSGPU_SPEC_FRAMES_WHISPER 1
+typedef struct opusgpu_spec_params { /* 64 bytes (ABI) */
+    int32_t sample_rate; /* Hz of the mono track the frames are cut from, 1 .. 1048576; places the filterbank, and the whole-file calls check it */
+    int32_t n_fft;       /* a multiple of 16 in [64, 2048] */
+    int32_t win_length;  /* even, in [16, n_fft]; 0 means n_fft */
+    int32_t hop;         /* in [1, n_fft], and 31 * hop + n_fft <= 32768 */
+    int32_t n_mels;      /* 1 .. 128 */
+    int32_t mel_scale;   /* OPUSGPU_SPEC_SLANEY 0 | OPUSGPU_SPEC_HTK 1 */
+    int32_t norm;        /* OPUSGPU_SPEC_NORM_SLANEY 0 | OPUSGPU_SPEC_NORM_NONE 1 */
+    int32_t power;       /* 1: sqrt(Re^2 + Im^2); 2: Re^2 + Im^2 */
+    int32_t log;         /* OPUSGPU_SPEC_LOG_NONE 0 | OPUSGPU_SPEC_LOG10 1 | OPUSGPU_SPEC_LN 2 */
+    int32_t frames;      /* OPUSGPU_SPEC_FRAMES_TORCH 0: F = n / hop + 1 (0 for n == 0); OPUSGPU_SPEC_FRAMES_WHISPER 1: F = n / hop */
+    int32_t layout;      /* OPUSGPU_MEL_BANDS_MAJOR | OPUSGPU_MEL_FRAMES_MAJOR */
+    float fmin, fmax;    /* Hz, 0 <= fmin < fmax <= sample_rate / 2 */
+    float floor;         /* finite, >= 0; > 0 with a log */
+    int32_t reserved[2]; /* 0 */
+} opusgpu_spec_params;
+/* The DFT basis of *p: sets *wc and *ws (either may be NULL) to Wc and Ws, [n_fft][n_fft / 2 + 1] floats each, valid for the life
+ * of the process, and returns n_fft * (n_fft / 2 + 1); OPUSGPU_BAD_ARG for a record that breaks a rule above.  Host only. */
+int opusgpu_spec_basis(const opusgpu_spec_params *p, const float **wc, const float **ws);
+/* The filterbank of *p: sets *b (may be NULL) to B, [n_mels][n_fft / 2 + 1] floats, and returns their count; OPUSGPU_BAD_ARG as
+ * above.  Host only. */
+int opusgpu_spec_filterbank(const opusgpu_spec_params *p, const float **b);
+/* LAYOUT above for n tracks of planned_48k_samples[i] samples at 48 kHz whose spectrograms are cut at up / down of that rate (1 <=
+ * up <= down <= 48000; not reduced, not held against sample_rate): writes feat_offsets[i] (may be NULL) and returns the total in
+ * floats.  OPUSGPU_BAD_ARG: a record that breaks a rule, such an up / down, a negative length.  Host only. */
+int64_t opusgpu_spec_layout(int n, const int64_t *planned_48k_samples, int up, int down, const opusgpu_spec_params *p, int64_t *feat_offsets);
+/* k_tracks_melspec alone: opusgpu_tracks_mel_device's contract and alignment rules -- d_in_mono packed int16 mono tracks, 16-byte
+ * aligned, read in aligned 16-byte pieces up to the one that holds a track's last sample; `spans` a HOST array of opusgpu_mel_span,
+ * whose plane must be a multiple of 64 and >= F; d_out floats, 128-byte aligned -- with *p in place of the constants.  sample_rate
+ * places the filterbank and is held against nothing.  A track without a frame writes nothing.  Uploads the records, its tile table
+ * and the kernel's tables, launches on the context's stream (or `hip_stream`), waits, and frees all of them on every way out.
+ * OPUSGPU_BAD_ARG before any device work: a record that breaks a rule, a span that does, a scale that is not finite. */
+int opusgpu_tracks_melspec_device(opusgpu_ctx *ctx, int n_tracks, const opusgpu_mel_span *spans, const void *d_in_mono,
+                                  const opusgpu_spec_params *p, void *d_out, void *hip_stream);
+/* opusgpu_files_decode into spectrograms.  rate != 0 (and up == down == 0): the track of TRACK RATES at that rate, 48000 included,
+ * through opusgpu_files_decode_resampled (`mono` 1, mix NULL) or opusgpu_files_decode_mixed (`mono` 0, *mix of one row).  rate == 0:
+ * the track of TRACK RATIOS at up / down through opusgpu_files_decode_ratio.  Either runs into a scratch buffer of int16 mono
+ * tracks (its own 48 kHz scratch is freed before the kernel starts), then k_tracks_melspec from there into d_out: opusgpu_spec_layout's
+ * total in floats, 128-byte aligned.  scale, feat_offsets, frames_out (F of the final length), track_lengths_out and status_out as
+ * for opusgpu_files_decode_mel; they are written last.  OPUSGPU_BAD_ARG before any device work, the buffer and the caller's arrays
+ * left as they were: a record that breaks a rule; a sample_rate that is not the track's rate, a ratio whose rate is no integer
+ * included; neither `mono` nor a mix, or both, or a mix of more than one row; what the rate and ratio calls refuse; a scale entry
+ * that is not finite; a d_out that is not 128-byte aligned. */
+int opusgpu_files_decode_melspec(opusgpu_ctx *ctx, const opusgpu_file_batch *batch, int rate, int up, int down, int mono,
+                                 const opusgpu_mix_matrix *mix, const opusgpu_spec_params *p, const float *scale, void *d_out,
+                                 int64_t *feat_offsets, int64_t *frames_out, int64_t *track_lengths_out, int32_t *status_out);
+
 /* ---- WHOLE FILES / MULTISTREAM: N surround Ogg Opus files in, N trimmed interleaved tracks in HBM out -----------------------------
  * The two sections above joined: files whose OpusHead carries channel mapping family 1 (1 - 8 channels, `streams` elementary
  * streams) are planned by the same reader-driven loop as stereo files and decoded by an opusgpu_ms of their layout.  The reader's
@@ -955,6 +1047,12 @@ int opusgpu_ms_files_decode_ratio(opusgpu_ms *ms, const opusgpu_ms_file_batch *b
 int opusgpu_ms_files_decode_mel(opusgpu_ms *ms, const opusgpu_ms_file_batch *batch, const opusgpu_mix_matrix *mix,
                                 const opusgpu_mel_params *params, const float *scale, void *d_out, int64_t *feat_offsets, int64_t *frames_out,
                                 int64_t *track_lengths_out, int32_t *status_out);
+
+/* opusgpu_files_decode_melspec behind opusgpu_ms_files_decode (TRACK SPECTROGRAMS): the layout's channels through *mix, which must
+ * have out_channels == 1; there is no `mono` here.  Refusals as there, plus a NULL mix. */
+int opusgpu_ms_files_decode_melspec(opusgpu_ms *ms, const opusgpu_ms_file_batch *batch, int rate, int up, int down,
+                                    const opusgpu_mix_matrix *mix, const opusgpu_spec_params *p, const float *scale, void *d_out,
+                                    int64_t *feat_offsets, int64_t *frames_out, int64_t *track_lengths_out, int32_t *status_out);
 
 #ifdef __cplusplus
 }

@@ -14,10 +14,15 @@ k_tracks_resample's row as well.
 --mono; `--mix mono` and `--mono` produce the same tracks, so their times show what the general staging costs.
 --mel [--n-mels N]: the fused log-mel call (opusgpu_files_decode_mel, mono) next to float32 16 kHz mono tracks followed by
 torch.stft, the filterbank matmul and log10, and k_tracks_mel's share of the call (tools/mel_rate.py).
+--melspec tts | kaldi | clap | music: the fused mel-spectrogram call (opusgpu_files_decode_melspec, mono; include/opusgpu.h TRACK
+SPECTROGRAMS) at that set's rate next to float32 mono tracks at the rate followed by torch.stft, the filterbank matmul, the floor and
+the log, and k_tracks_melspec's share of the call (tools/mel_rate.py: compare_spec).
+--packets-per-file P: files of P packets of 20 ms (in pages of at most 250) in place of the default 10, for --mel and --melspec: long
+tracks, whose tiles are full.
 --resample UP/DOWN [--mono | --mix M]: the fused ratio call (opusgpu_files_decode_ratio, include/opusgpu.h TRACK RATIOS) next to
 rate=24000 on the same corpus and to float32 48 kHz tracks resampled by a polyphase conv1d in torch, interleaved, and the two
 kernels alone per output sample (tools/ratio_rate.py).
-usage (GPU box): python3 tools/files_rate.py [--n N] [--reps R] [--format F | --rate R [--mono | --mix M] | --resample U/D [--mono | --mix M] | --mel [--n-mels N]] | python3 tools/files_rate.py --stats DIR [--n N]"""
+usage (GPU box): python3 tools/files_rate.py [--n N] [--reps R] [--format F | --rate R [--mono | --mix M] | --resample U/D [--mono | --mix M] | --mel [--n-mels N] | --melspec SET] [--packets-per-file P] | python3 tools/files_rate.py --stats DIR [--n N]"""
 import argparse
 import ctypes as C
 import glob
@@ -47,7 +52,14 @@ ap.add_argument("--resample", default=None, metavar="UP/DOWN",
                 help="compare the fused ratio call with rate=24000 and with 48 kHz float tracks + a polyphase conv1d in torch (tools/ratio_rate.py)")
 ap.add_argument("--mel", action="store_true", help="compare the fused log-mel call with 16 kHz mono float tracks + torch.stft (tools/mel_rate.py)")
 ap.add_argument("--n-mels", type=int, choices=[80, 128], default=80)
+ap.add_argument("--melspec", choices=["tts", "kaldi", "clap", "music"], default=None,
+                help="compare the fused mel-spectrogram call with float mono tracks at the set's rate + torch.stft (tools/mel_rate.py)")
+ap.add_argument("--packets-per-file", type=int, default=10, help="with --mel or --melspec: packets of 20 ms per file")
 args = ap.parse_args()
+if args.melspec and (args.rate or args.format or args.resample or args.mel):
+    ap.error("--melspec goes without --rate, --resample, --format and --mel")
+if args.packets_per_file != 10 and not (args.mel or args.melspec):
+    ap.error("--packets-per-file goes with --mel or --melspec")
 if args.mix and (args.mono or not (args.rate or args.resample)):
     ap.error("--mix goes with --rate or --resample and without --mono")
 if args.mel and (args.rate or args.format or args.resample):
@@ -55,7 +67,7 @@ if args.mel and (args.rate or args.format or args.resample):
 if args.resample and (args.rate or args.format):
     ap.error("--resample goes without --rate and --format")
 n = args.n
-if args.format or args.rate or args.mel or args.resample:
+if args.format or args.rate or args.mel or args.resample or args.melspec:
     import torch  # before the library: one HIP runtime for both
 
 spec = importlib.util.spec_from_file_location("esp32_opus_player_amd", os.path.join(here, "..", "esp32-opus-player_amd", "__init__.py"))
@@ -63,8 +75,10 @@ pkg = importlib.util.module_from_spec(spec)
 spec.loader.exec_module(pkg)
 import files_util as fu  # noqa: E402
 
-files, pre, trim = fu.bulk_files(pkg, n, pkg.TOC_CELT_FB_STEREO, 160, pages=1, per_page=10)
-kept = int((9600 - pre - trim).sum())          # samples per channel of all tracks
+PAGES = -(-args.packets_per_file // 250)
+PER_PAGE = -(-args.packets_per_file // PAGES)  # (a count that no number of equal pages makes is rounded up)
+files, pre, trim = fu.bulk_files(pkg, n, pkg.TOC_CELT_FB_STEREO, 160, pages=PAGES, per_page=PER_PAGE)
+kept = int((960 * PAGES * PER_PAGE - pre - trim).sum())  # samples per channel of all tracks
 MOVED = 2 * kept * 4                           # bytes the assembly reads + writes per batch
 
 if args.stats:
@@ -153,10 +167,35 @@ if args.resample:
     ctx.close()
     raise SystemExit(0)
 
+if args.melspec:
+    import mel_rate
+    kw, up, down = mel_rate.SPEC_SETS[args.melspec]
+    rec = pkg.mel_spec(**kw)
+    rate = 48000 // down if up == 1 else 0
+    b = pkg.FileBatch([r.tobytes() for r in files], channels=2, flags=pkg.PAGES_GROUP_BY_MODE, threads=args.threads)
+    assert (b.info["status"] == 0).all() and b.n_steps == PAGES * PER_PAGE
+    ctx = pkg.Context(0)
+    ctx.streams_alloc(n, 2)
+
+    def tracks(fmt, d, oo, ol, ln, st):
+        if rate:
+            return ctx._chk(ctx.lib.opusgpu_files_decode_resampled(ctx.h, b.h, rate, 1, fmt, None, d, oo, ol, ln, st), "opusgpu_files_decode_resampled")
+        return ctx._chk(ctx.lib.opusgpu_files_decode_ratio(ctx.h, b.h, up, down, 1, None, fmt, None, d, oo, ol, ln, st), "opusgpu_files_decode_ratio")
+    for name, pipe in (("in_order", 0), ("pipelined", 1)):
+        ctx.set_pipeline(pipe)
+        print(json.dumps(mel_rate.compare_spec(
+            torch, pkg, tracks,
+            lambda p, d, fo, fr, ln, st: ctx._chk(ctx.lib.opusgpu_files_decode_melspec(ctx.h, b.h, rate, 0 if rate else up, 0 if rate else down, 1,
+                                                                                       None, p, None, d, fo, fr, ln, st), "opusgpu_files_decode_melspec"),
+            lambda spans, d_in, r, d_out: ctx.tracks_melspec_device(spans, d_in, r, d_out), b, rec, up, down, args.reps,
+            f"{args.melspec}, {name}, {PAGES * PER_PAGE} packets per file")), flush=True)
+    ctx.close()
+    raise SystemExit(0)
+
 if args.mel:
     import mel_rate
     b = pkg.FileBatch([r.tobytes() for r in files], channels=2, flags=pkg.PAGES_GROUP_BY_MODE, threads=args.threads)
-    assert (b.info["status"] == 0).all() and b.n_steps == 10
+    assert (b.info["status"] == 0).all() and b.n_steps == PAGES * PER_PAGE
     ctx = pkg.Context(0)
     ctx.streams_alloc(n, 2)
     for name, pipe in (("in_order", 0), ("pipelined", 1)):

@@ -7,6 +7,9 @@ frame, |.|^2, the filterbank matmul, log10(clamp(1e-10)); (c) the fused call, lo
 k_tracks_mel alone (opusgpu_tracks_mel_device: its uploads, the launch and the wait) over the int16 tracks of the same batch, and its
 share of (c).  Means, medians, min / max; no ratio is asked of (c) against (b): both are printed.
 One track of (c) is held against (b) away from the track's end, where (b) pads with zeros in place of reflecting.
+compare_spec is the same for --melspec (include/opusgpu.h TRACK SPECTROGRAMS) with a mel_spec record in place of Whisper's constants:
+(a) float32 mono tracks at the record's rate, (b) (a) + torch.stft(n_fft, hop, win_length, periodic Hann, center=True), |.| or |.|^2,
+the filterbank matmul, the floor and the log, (c) the fused call, (m) opusgpu_tracks_melspec_device alone.
 torch must be imported before the library is loaded: they then share one HIP runtime."""
 import time
 
@@ -87,3 +90,96 @@ def compare(torch, pkg, decode_16k, decode_mel, mel_alone, batch, n_mels, reps, 
     out["mel_share_of_c"] = round(float(np.mean(times["m"]) / np.mean(times["c"])), 3)
     out["c_le_b"] = bool(np.mean(times["c"]) <= np.mean(times["b"]))
     return out
+
+
+def compare_spec(torch, pkg, decode_tracks, decode_spec, spec_alone, batch, rec, up, down, reps, note=""):
+    """decode_tracks(fmt, d_out, out_offsets, out_lengths, lengths, status) runs the library's mono call at up / down of 48 kHz for the
+    batch, decode_spec(params, d_out, feat_offsets, frames, lengths, status) the fused one, spec_alone(spans, d_in, rec, d_out) the
+    kernel's; each checks its code.  -> a dict for the JSON line."""
+    n = batch.n_files
+    planned = batch.info["track_samples"]
+    offs, total = pkg.resample_ratio_layout(planned, up, down) if up != 1 or down not in (1, 2, 3, 4, 6) else pkg.resample_layout(planned, 48000 // down)
+    feat_offs, planes, total_feat = pkg.spec_layout(planned, up, down, rec)
+    n_fft, hop, n_mels = int(rec["n_fft"][0]), int(rec["hop"][0]), int(rec["n_mels"][0])
+    win, power, log, floor = int(rec["win_length"][0]) or n_fft, int(rec["power"][0]), int(rec["log"][0]), float(rec["floor"][0])
+    whisper = int(rec["frames"][0]) == 1
+    f32 = torch.empty(max(total, 1), dtype=torch.float32, device="cuda:0")
+    s16 = torch.empty(max(total, 1) + 64, dtype=torch.int16, device="cuda:0")
+    feat = torch.empty(max(total_feat, 1), dtype=torch.float32, device="cuda:0")
+    lengths, out_offsets, out_lengths, fo, frames = (np.zeros(n, dtype=np.int64) for _ in range(5))
+    status = np.zeros((n, 2), dtype=np.int32)
+    len_r = -(-planned * up // down)
+    longest = int(len_r.max(initial=1))
+    idx = offs[:, None] + np.arange(longest)[None, :]
+    valid = np.arange(longest)[None, :] < len_r[:, None]
+    gather = torch.tensor(np.where(valid, idx, 0), device="cuda:0")
+    mask = torch.tensor(valid, device="cuda:0")
+    window = torch.hann_window(win, periodic=True, device="cuda:0")
+    bank_t = torch.tensor(pkg.spec_filterbank(rec).T.copy(), device="cuda:0")  # [bins, n_mels]
+
+    def a():
+        decode_tracks(pkg.TRACKS_F32, f32.data_ptr(), out_offsets.ctypes.data, out_lengths.ctypes.data, lengths.ctypes.data, status.ctypes.data)
+
+    def b():
+        a()
+        x = torch.where(mask, f32[gather], torch.zeros((), device="cuda:0"))
+        spec = torch.stft(x, n_fft, hop, win_length=win, window=window, center=True, return_complex=True)  # [files, bins, frames]
+        mag = spec.abs()
+        out = torch.clamp((mag if power == 1 else mag ** 2).transpose(1, 2) @ bank_t, min=floor)            # [files, frames, n_mels]
+        out = torch.log10(out) if log == 1 else torch.log(out) if log == 2 else out
+        torch.cuda.synchronize()
+        return out
+
+    def c():
+        decode_spec(rec.ctypes.data, feat.data_ptr(), fo.ctypes.data, frames.ctypes.data, lengths.ctypes.data, status.ctypes.data)
+
+    decode_tracks(pkg.TRACKS_S16, s16.data_ptr(), out_offsets.ctypes.data, out_lengths.ctypes.data, lengths.ctypes.data, status.ctypes.data)
+    spans = np.zeros(n, dtype=pkg.MEL_SPAN_DTYPE)
+    spans["in_offset"], spans["in_samples"], spans["out_offset"], spans["plane"], spans["scale"] = offs, out_lengths, feat_offs, planes, 2.0 ** -15
+
+    def m():
+        spec_alone(spans, s16.data_ptr(), rec, feat.data_ptr())
+
+    times = {"a": [], "b": [], "c": [], "m": []}
+    for fn in (a, b, c, m):
+        fn()
+    for _ in range(reps):
+        for name, fn in (("a", a), ("b", b), ("c", c), ("m", m)):
+            t0 = time.perf_counter()
+            fn()
+            times[name].append((time.perf_counter() - t0) * 1e3)
+    assert (status[:, 0] == 0).all() and (lengths == planned).all() and (fo == feat_offs).all() and (frames == pkg.spec_frames(rec, len_r)).all()
+    # one track of (c) against (b) away from the track's ends, where (b) pads the batch with zeros in place of reflecting
+    c()
+    want = b()
+    edge = n_fft // 2 // hop + 2
+    worst = None
+    fits = [j for j in range(n // 2, n) if frames[j] > 2 * edge + 2]
+    if fits:
+        i = fits[0]
+        F, o, p = int(frames[i]), int(feat_offs[i]), int(planes[i])
+        got = feat[o:o + n_mels * p].view(n_mels, p)[:, edge:F - edge].t()
+        ref = want[i, edge:F - edge]
+        d = (got - ref).abs()
+        worst = float((d if log else d / ref.abs().clamp(min=1e-30)).max())
+        assert worst < 1e-2, worst
+    out = {"melspec": [int(rec[k][0]) for k in ("sample_rate", "n_fft", "win_length", "hop", "n_mels")], "files": n, "frames": int(frames.sum()),
+           "reps": reps, "note": note, "scratch_s16_bytes": int(total) * 2, "out_bytes": int(total_feat) * 4, "padded_batch_floats_of_b": n * longest,
+           "worst_error_vs_torch": worst if fits else "not checked: no track long enough"}
+    for k, label in (("a", "a_f32_mono"), ("b", "b_f32_then_torch_stft_mel"), ("c", "c_fused_melspec"), ("m", "m_k_tracks_melspec_call")):
+        v = np.array(times[k])
+        out[label] = {"mean_ms": round(float(v.mean()), 3), "median_ms": round(float(np.median(v)), 3),
+                      "min_max_ms": [round(float(v.min()), 3), round(float(v.max()), 3)]}
+    out["melspec_share_of_c"] = round(float(np.mean(times["m"]) / np.mean(times["c"])), 3)
+    out["c_le_b"] = bool(np.mean(times["c"]) <= np.mean(times["b"]))
+    return out
+
+
+# the parameter sets of --melspec: (mel_spec arguments, up, down)
+SPEC_SETS = {
+    "tts": (dict(sample_rate=22050, n_fft=1024, hop=256, n_mels=80, fmax=8000.0, power=1, log="ln", floor=1e-5), 147, 320),
+    "kaldi": (dict(sample_rate=16000, n_fft=512, hop=160, win_length=400, n_mels=80, fmin=20.0, mel_scale="htk", norm=None, log="ln",
+                   floor=1.1920929e-7), 1, 3),
+    "clap": (dict(sample_rate=48000, n_fft=1024, hop=480, n_mels=64, fmin=50.0, fmax=14000.0, mel_scale="htk", norm=None), 1, 1),
+    "music": (dict(sample_rate=44100, n_fft=2048, hop=441, win_length=1102, n_mels=128), 147, 160),
+}

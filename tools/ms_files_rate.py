@@ -16,9 +16,12 @@ ms_rate.py's count per step).
 --rate R --mix mono | stereo: the same through the 5.1 default downmix table (opusgpu_ms_files_decode_mixed).
 --mel [--n-mels N]: the fused log-mel call (opusgpu_ms_files_decode_mel through the default mono downmix) next to float32 16 kHz mono
 tracks followed by torch.stft, the filterbank matmul and log10, and k_tracks_mel's share of the call (tools/mel_rate.py).
+--melspec tts | kaldi | clap | music: the fused mel-spectrogram call (opusgpu_ms_files_decode_melspec through the default mono downmix)
+next to float32 mono tracks at the set's rate followed by torch.stft, the filterbank matmul, the floor and the log, and
+k_tracks_melspec's share of the call (tools/mel_rate.py: compare_spec).
 --resample UP/DOWN [--mix M]: the fused ratio call (opusgpu_ms_files_decode_ratio) next to rate=24000 on the same corpus and to
 float32 48 kHz tracks resampled by a polyphase conv1d in torch, and the two kernels alone (tools/ratio_rate.py).
-usage (GPU box): python3 tools/ms_files_rate.py [--n N] [--reps R] [--format F | --rate R [--mix M] | --resample U/D [--mix M] | --mel [--n-mels N]] | python3 tools/ms_files_rate.py --stats DIR [--n N]"""
+usage (GPU box): python3 tools/ms_files_rate.py [--n N] [--reps R] [--format F | --rate R [--mix M] | --resample U/D [--mix M] | --mel [--n-mels N] | --melspec SET] | python3 tools/ms_files_rate.py --stats DIR [--n N]"""
 import argparse
 import ctypes as C
 import glob
@@ -46,14 +49,18 @@ ap.add_argument("--resample", default=None, metavar="UP/DOWN",
                 help="compare the fused ratio call with rate=24000 and with 48 kHz float tracks + a polyphase conv1d in torch (tools/ratio_rate.py)")
 ap.add_argument("--mel", action="store_true", help="compare the fused log-mel call with 16 kHz mono float tracks + torch.stft (tools/mel_rate.py)")
 ap.add_argument("--n-mels", type=int, choices=[80, 128], default=80)
+ap.add_argument("--melspec", choices=["tts", "kaldi", "clap", "music"], default=None,
+                help="compare the fused mel-spectrogram call with float mono tracks at the set's rate + torch.stft (tools/mel_rate.py)")
 args = ap.parse_args()
+if args.melspec and (args.rate or args.format or args.resample or args.mel):
+    ap.error("--melspec goes without --rate, --resample, --format and --mel")
 if args.mix and not (args.rate or args.resample):
     ap.error("--mix goes with --rate or --resample")
 if args.mel and (args.rate or args.format or args.resample):
     ap.error("--mel goes without --rate, --resample and --format")
 if args.resample and (args.rate or args.format):
     ap.error("--resample goes without --rate and --format")
-if args.format or args.rate or args.mel or args.resample:
+if args.format or args.rate or args.mel or args.resample or args.melspec:
     import torch  # before the library is loaded: one HIP runtime for both
 n = args.n
 
@@ -197,6 +204,32 @@ if args.resample:
         lambda d, ln, st: ms._chk(ms.lib.opusgpu_ms_files_decode(ms.h, b.h, d, ln, st), "opusgpu_ms_files_decode"),
         (lambda spans, d_in, fmt, d_out: mem.tracks_resample_ratio_device(spans, d_in, CH, up, down, False, rec, fmt, d_out), at_24000_kernel),
         b, up, down, False, args.reps, "in_order", mix=pkg.downmix_matrix(CH, 1 if args.mix == "mono" else 2) if args.mix else None)))
+    mem.close()
+    ms.close()
+    raise SystemExit(0)
+
+if args.melspec:
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import mel_rate
+    kw, up, down = mel_rate.SPEC_SETS[args.melspec]
+    srec = pkg.mel_spec(**kw)
+    rate = 48000 // down if up == 1 else 0
+    ms = pkg.MultistreamContext(0, n, *LAYOUT)
+    mem = pkg.Context(0)
+    rec = pkg.mix_matrix("mono", CH)
+
+    def tracks(fmt, d, oo, ol, ln, st):
+        if rate:
+            return ms._chk(ms.lib.opusgpu_ms_files_decode_mixed(ms.h, b.h, rate, rec.ctypes.data, fmt, None, d, oo, ol, ln, st),
+                           "opusgpu_ms_files_decode_mixed")
+        return ms._chk(ms.lib.opusgpu_ms_files_decode_ratio(ms.h, b.h, up, down, rec.ctypes.data, fmt, None, d, oo, ol, ln, st),
+                       "opusgpu_ms_files_decode_ratio")
+    print(json.dumps(mel_rate.compare_spec(
+        torch, pkg, tracks,
+        lambda p, d, fo, fr, ln, st: ms._chk(ms.lib.opusgpu_ms_files_decode_melspec(ms.h, b.h, rate, 0 if rate else up, 0 if rate else down,
+                                                                                    rec.ctypes.data, p, None, d, fo, fr, ln, st),
+                                             "opusgpu_ms_files_decode_melspec"),
+        lambda spans, d_in, r, d_out: mem.tracks_melspec_device(spans, d_in, r, d_out), b, srec, up, down, args.reps, f"{args.melspec}, in_order")))
     mem.close()
     ms.close()
     raise SystemExit(0)
