@@ -8,6 +8,7 @@ The directory name has a hyphen, so import it with `importlib` (see tests/confte
 """
 import ctypes as C
 import os
+import typing
 
 import numpy as np
 
@@ -598,23 +599,35 @@ def _out_flat(out, need, format, device):
     return out.view(-1)
 
 
+def _tables(name, ctype, args, count, refused):
+    """What a table accessor of the library hands out: `name`(*args, `count` pointers out) -> copies of the `count` arrays of
+    `ctype`, flat; ValueError(refused) where the call refuses."""
+    ptrs = [C.c_void_p() for _ in range(count)]
+    n = getattr(load_lib(), name)(*args, *(C.byref(p) for p in ptrs))
+    if n < 0:
+        raise ValueError(refused)
+    return [np.ctypeslib.as_array((ctype * n).from_address(p.value)).copy() for p in ptrs]
+
+
+def _layout(name, planned_samples, args, refused):
+    """A layout call of the library: `name`(n, planned, *args, offsets out) -> (planned [int64], offsets [int64], total);
+    ValueError where the call refuses."""
+    planned = np.ascontiguousarray(planned_samples, dtype=np.int64)
+    offsets = np.zeros(planned.size, dtype=np.int64)
+    total = getattr(load_lib(), name)(planned.size, planned.ctypes.data, *args, offsets.ctypes.data)
+    if total < 0:
+        raise ValueError(f"{name} refused {refused}")
+    return planned, offsets, int(total)
+
+
 def resample_taps(rate):
     """opusgpu_resample_taps: the Q15 decimation taps of `rate` (24000, 16000, 12000, 8000) as an int16 array of 24 D + 1."""
-    p = C.c_void_p()
-    n = load_lib().opusgpu_resample_taps(int(rate), C.byref(p))
-    if n < 0:
-        raise ValueError(f"no taps for rate {rate!r}")
-    return np.ctypeslib.as_array((C.c_int16 * n).from_address(p.value)).copy()
+    return _tables("opusgpu_resample_taps", C.c_int16, (int(rate),), 1, f"no taps for rate {rate!r}")[0]
 
 
 def resample_layout(planned_samples, rate):
     """opusgpu_resample_layout: the grid of the resampled tracks -> (out_offsets [int64], total samples per channel)."""
-    planned = np.ascontiguousarray(planned_samples, dtype=np.int64)
-    offsets = np.zeros(planned.size, dtype=np.int64)
-    total = load_lib().opusgpu_resample_layout(planned.size, planned.ctypes.data, int(rate), offsets.ctypes.data)
-    if total < 0:
-        raise ValueError(f"opusgpu_resample_layout refused rate {rate!r} or a negative length")
-    return offsets, int(total)
+    return _layout("opusgpu_resample_layout", planned_samples, (int(rate),), f"rate {rate!r} or a negative length")[1:]
 
 
 def track_rate_args(batch, rate=48000, mono=False, format="s16", out=None, device=0, allow_mono=True):
@@ -666,21 +679,31 @@ def track_ratio(resample):
 
 def resample_ratio_taps(up, down):
     """opusgpu_resample_ratio_taps: the Q15 taps of up / down as an int16 array of 24 down' + 1, down' the reduced down."""
-    p = C.c_void_p()
-    n = load_lib().opusgpu_resample_ratio_taps(int(up), int(down), C.byref(p))
-    if n < 0:
-        raise ValueError(f"no taps for the ratio {up!r}/{down!r}")
-    return np.ctypeslib.as_array((C.c_int16 * n).from_address(p.value)).copy()
+    return _tables("opusgpu_resample_ratio_taps", C.c_int16, (int(up), int(down)), 1, f"no taps for the ratio {up!r}/{down!r}")[0]
 
 
 def resample_ratio_layout(planned_samples, up, down):
     """opusgpu_resample_ratio_layout: the grid of the tracks at up / down -> (out_offsets [int64], total samples per channel)."""
-    planned = np.ascontiguousarray(planned_samples, dtype=np.int64)
-    offsets = np.zeros(planned.size, dtype=np.int64)
-    total = load_lib().opusgpu_resample_ratio_layout(planned.size, planned.ctypes.data, int(up), int(down), offsets.ctypes.data)
-    if total < 0:
-        raise ValueError(f"opusgpu_resample_ratio_layout refused the ratio {up!r}/{down!r} or a negative length")
-    return offsets, int(total)
+    return _layout("opusgpu_resample_ratio_layout", planned_samples, (int(up), int(down)),
+                   f"the ratio {up!r}/{down!r} or a negative length")[1:]
+
+
+def _channel_mix(batch, mono, mix, allow_mono, one=False):
+    """What mono= and mix= make of the channels of a planned batch: the matrix record of a mix, None for mono or all channels.
+    one: the result must be ONE channel (features).  Raises ValueError for mono where there is none (allow_mono False) or on more
+    than 2 channels, mono together with a mix, what mix_matrix refuses, and with `one` for neither and for a mix of more rows."""
+    if mono and not allow_mono:
+        raise ValueError("there is no mono downmix of multistream tracks: use mix='mono'")
+    if mix is not None and mono:
+        raise ValueError("mix and mono=True exclude each other: the row {8192, 8192} is mono")
+    if one and mix is None and not mono:
+        raise ValueError("features are made of ONE channel: pass mono=True or a mix of one row (mix='mono')")
+    rec = None if mix is None else mix_matrix(mix, batch.channels)
+    if one and rec is not None and int(rec["out_channels"][0]) != 1:
+        raise ValueError(f"features are made of ONE channel: the mix has {int(rec['out_channels'][0])} rows")
+    if mono and batch.channels > 2:
+        raise ValueError(f"mono needs 1 or 2 channels, not {batch.channels}")
+    return rec
 
 
 def track_ratio_args(batch, resample, mono=False, mix=None, format="s16", out=None, device=0, allow_mono=True, rate=None, features=None):
@@ -694,13 +717,7 @@ def track_ratio_args(batch, resample, mono=False, mix=None, format="s16", out=No
     if features is not None:
         raise ValueError("features are made of the track at 16000 Hz: there is no resample= with them")
     up, down = track_ratio(resample)
-    if mono and not allow_mono:
-        raise ValueError("there is no mono downmix of multistream tracks: use mix='mono'")
-    if mix is not None and mono:
-        raise ValueError("mix and mono=True exclude each other: the row {8192, 8192} is mono")
-    rec = None if mix is None else mix_matrix(mix, batch.channels)
-    if mono and batch.channels > 2:
-        raise ValueError(f"mono needs 1 or 2 channels, not {batch.channels}")
+    rec = _channel_mix(batch, mono, mix, allow_mono)
     if format not in TRACK_FORMATS:
         raise ValueError(f"format must be one of {sorted(TRACK_FORMATS)}, not {format!r}")
     ch_out = int(rec["out_channels"][0]) if rec is not None else 1 if mono else batch.channels
@@ -781,30 +798,20 @@ def mel_params(n_mels=80, feature_layout="bands"):
 
 def mel_basis():
     """opusgpu_mel_basis: the windowed DFT basis the kernel multiplies -> (Wc, Ws), float32 [400, 201] each."""
-    wc, ws = C.c_void_p(), C.c_void_p()
-    n = load_lib().opusgpu_mel_basis(C.byref(wc), C.byref(ws))
-    return tuple(np.ctypeslib.as_array((C.c_float * n).from_address(p.value)).reshape(MEL_NFFT, MEL_BINS).copy() for p in (wc, ws))
+    return tuple(a.reshape(MEL_NFFT, MEL_BINS) for a in _tables("opusgpu_mel_basis", C.c_float, (), 2, None))
 
 
 def mel_filterbank(n_mels):
     """opusgpu_mel_filterbank: the Slaney filterbank of 80 or 128 bands -> float32 [n_mels, 201]."""
-    p = C.c_void_p()
-    n = load_lib().opusgpu_mel_filterbank(int(n_mels), C.byref(p))
-    if n < 0:
-        raise ValueError(f"n_mels must be 80 or 128, not {n_mels!r}")
-    return np.ctypeslib.as_array((C.c_float * n).from_address(p.value)).reshape(int(n_mels), MEL_BINS).copy()
+    bank = _tables("opusgpu_mel_filterbank", C.c_float, (int(n_mels),), 1, f"n_mels must be 80 or 128, not {n_mels!r}")[0]
+    return bank.reshape(int(n_mels), MEL_BINS)
 
 
 def mel_layout(planned_48k_samples, n_mels=80, feature_layout="bands"):
     """opusgpu_mel_layout: the grid of the feature tracks -> (feat_offsets [int64], planes [int64], total floats)."""
     rec = mel_params(n_mels, feature_layout)
-    planned = np.ascontiguousarray(planned_48k_samples, dtype=np.int64)
-    offsets = np.zeros(planned.size, dtype=np.int64)
-    total = load_lib().opusgpu_mel_layout(planned.size, planned.ctypes.data, rec.ctypes.data, offsets.ctypes.data)
-    if total < 0:
-        raise ValueError("opusgpu_mel_layout refused a negative length")
-    planes = ((planned + 2) // 3 // MEL_HOP + 63) // 64 * 64
-    return offsets, planes, int(total)
+    planned, offsets, total = _layout("opusgpu_mel_layout", planned_48k_samples, (rec.ctypes.data,), "a negative length")
+    return offsets, ((planned + 2) // 3 // MEL_HOP + 63) // 64 * 64, total
 
 
 def track_feature_args(batch, features=None, n_mels=80, feature_layout="bands", rate=None, mono=False, mix=None, format=None, scale=None,
@@ -824,19 +831,7 @@ def track_feature_args(batch, features=None, n_mels=80, feature_layout="bands", 
         raise ValueError(f"features are made of the track at {MEL_SR} Hz: rate must be absent or {MEL_SR}, not {rate!r}")
     if format not in (None, "f32"):
         raise ValueError(f"features are float32: format must be absent or 'f32', not {format!r}")
-    if mono and not allow_mono:
-        raise ValueError("there is no mono downmix of multistream tracks: use mix='mono'")
-    if mix is not None and mono:
-        raise ValueError("mix and mono=True exclude each other: the row {8192, 8192} is mono")
-    if mix is None and not mono:
-        raise ValueError("features are made of ONE channel: pass mono=True or a mix of one row (mix='mono')")
-    mrec = None
-    if mix is not None:
-        mrec = mix_matrix(mix, batch.channels)
-        if int(mrec["out_channels"][0]) != 1:
-            raise ValueError(f"features are made of ONE channel: the mix has {int(mrec['out_channels'][0])} rows")
-    elif batch.channels > 2:
-        raise ValueError(f"mono needs 1 or 2 channels, not {batch.channels}")
+    mrec = _channel_mix(batch, mono, mix, allow_mono, one=True)
     _, scale, _ = track_format_args(batch, "f32", scale, None, device)
     offsets, planes, total = mel_layout(batch.info["track_samples"], n_mels, feature_layout)
     if out is not None:
@@ -899,22 +894,15 @@ def _spec_rec(rec):
 def spec_basis(rec):
     """opusgpu_spec_basis: the windowed DFT basis of a mel_spec record -> (Wc, Ws), float32 [n_fft, n_fft / 2 + 1] each."""
     rec = _spec_rec(rec)
-    wc, ws = C.c_void_p(), C.c_void_p()
-    n = load_lib().opusgpu_spec_basis(rec.ctypes.data, C.byref(wc), C.byref(ws))
-    if n < 0:
-        raise ValueError("opusgpu_spec_basis refused the record")
-    n_fft = int(rec["n_fft"][0])
-    return tuple(np.ctypeslib.as_array((C.c_float * n).from_address(p.value)).reshape(n_fft, n_fft // 2 + 1).copy() for p in (wc, ws))
+    tables = _tables("opusgpu_spec_basis", C.c_float, (rec.ctypes.data,), 2, "opusgpu_spec_basis refused the record")
+    return tuple(a.reshape(int(rec["n_fft"][0]), -1) for a in tables)
 
 
 def spec_filterbank(rec):
     """opusgpu_spec_filterbank: the filterbank of a mel_spec record -> float32 [n_mels, n_fft / 2 + 1]."""
     rec = _spec_rec(rec)
-    p = C.c_void_p()
-    n = load_lib().opusgpu_spec_filterbank(rec.ctypes.data, C.byref(p))
-    if n < 0:
-        raise ValueError("opusgpu_spec_filterbank refused the record")
-    return np.ctypeslib.as_array((C.c_float * n).from_address(p.value)).reshape(int(rec["n_mels"][0]), -1).copy()
+    bank = _tables("opusgpu_spec_filterbank", C.c_float, (rec.ctypes.data,), 1, "opusgpu_spec_filterbank refused the record")[0]
+    return bank.reshape(int(rec["n_mels"][0]), -1)
 
 
 def spec_frames(rec, samples):
@@ -928,13 +916,9 @@ def spec_layout(planned_48k_samples, up, down, rec):
     """opusgpu_spec_layout: the grid of the spectrograms of tracks at up / down of 48 kHz -> (feat_offsets [int64], planes [int64],
     total floats)."""
     rec = _spec_rec(rec)
-    planned = np.ascontiguousarray(planned_48k_samples, dtype=np.int64)
-    offsets = np.zeros(planned.size, dtype=np.int64)
-    total = load_lib().opusgpu_spec_layout(planned.size, planned.ctypes.data, int(up), int(down), rec.ctypes.data, offsets.ctypes.data)
-    if total < 0:
-        raise ValueError(f"opusgpu_spec_layout refused the record, the ratio {up!r}/{down!r} or a negative length")
-    planes = (spec_frames(rec, -(-planned * int(up) // int(down))) + 63) // 64 * 64
-    return offsets, planes, int(total)
+    planned, offsets, total = _layout("opusgpu_spec_layout", planned_48k_samples, (int(up), int(down), rec.ctypes.data),
+                                      f"the record, the ratio {up!r}/{down!r} or a negative length")
+    return offsets, (spec_frames(rec, -(-planned * int(up) // int(down))) + 63) // 64 * 64, total
 
 
 def track_spectrogram_args(batch, features, rate=None, resample=None, mono=False, mix=None, format=None, scale=None, out=None, device=0,
@@ -962,19 +946,7 @@ def track_spectrogram_args(batch, features, rate=None, resample=None, mono=False
         raise ValueError(f"the record's sample_rate {sr} is not the track's rate, 48000 * {up} / {down}")
     if format not in (None, "f32"):
         raise ValueError(f"features are float32: format must be absent or 'f32', not {format!r}")
-    if mono and not allow_mono:
-        raise ValueError("there is no mono downmix of multistream tracks: use mix='mono'")
-    if mix is not None and mono:
-        raise ValueError("mix and mono=True exclude each other: the row {8192, 8192} is mono")
-    if mix is None and not mono:
-        raise ValueError("features are made of ONE channel: pass mono=True or a mix of one row (mix='mono')")
-    mrec = None
-    if mix is not None:
-        mrec = mix_matrix(mix, batch.channels)
-        if int(mrec["out_channels"][0]) != 1:
-            raise ValueError(f"features are made of ONE channel: the mix has {int(mrec['out_channels'][0])} rows")
-    elif batch.channels > 2:
-        raise ValueError(f"mono needs 1 or 2 channels, not {batch.channels}")
+    mrec = _channel_mix(batch, mono, mix, allow_mono, one=True)
     _, scale, _ = track_format_args(batch, "f32", scale, None, device)
     offsets, planes, total = spec_layout(batch.info["track_samples"], up, down, rec)
     if out is not None:
@@ -982,127 +954,114 @@ def track_spectrogram_args(batch, features, rate=None, resample=None, mono=False
     return rec, mrec, scale, offsets, planes, total, out, how
 
 
-def _decode_planned_mel(chk, name, call, batch, mem, fargs):
-    """_decode_planned for feature tracks: call(scale pointer, d_out, four array pointers) runs the decode call `name`; fargs: what
-    track_feature_args returned.  -> (features, info): float32 arrays [n_mels, F] or [F, n_mels]; info has `feat_offset` more, and
-    its `frames` is F, the track's feature frames, as `track_samples` is its final length (the plan's count of Opus frames is
-    batch.info["frames"])."""
-    rec, _, scale, offsets, planes, total, out = fargs[:7]
-    n, n_mels, frames_major = batch.n_files, int(rec["n_mels"][0]), int(rec["layout"][0]) == MEL_FRAMES_MAJOR
-    feat_offsets, frames, lengths = (np.zeros(n, dtype=np.int64) for _ in range(3))
+class FilesRequest(typing.NamedTuple):
+    """What one decode_files call asks of the library, made by files_request before any decoder is touched."""
+    entry: str        # the C entry point without its opusgpu_ / opusgpu_ms_ prefix
+    args: tuple       # its scalar and record arguments between the batch and the format, in call order (a record: an array of one, or None)
+    kind: str         # "tracks" (the planned grid at 48 kHz), "resampled" or "features"
+    fmt: int          # TRACKS_*
+    scale: object     # float32 array or None
+    out: object       # the caller's tensor, flattened, or None
+    channels: int     # output channels
+    offsets: object   # the planned grid of the result: offsets, planes (planar tracks and band-major features) and total, per channel
+    planes: object
+    total: int
+    mix: object       # the matrix record or None
+    params: object    # the features' record or None
+
+
+def files_request(batch, multistream=False, device=0, format=None, scale=None, out=None, rate=None, mono=False, mix=None, features=None,
+                  n_mels=80, feature_layout="bands", resample=None):
+    """The keywords of decode_files for a planned batch -> the FilesRequest that _run_files_request carries out.  Every refusal of
+    decode_files is raised here, as ValueError, by the track_*_args helpers; nothing of a decoder is needed.  multistream: the batch
+    is an MsFileBatch, whose C calls take no `mono` and whose tracks have no mono downmix."""
+    if mix is not None and mono:
+        raise ValueError("mix and mono=True exclude each other: the row {8192, 8192} is mono")
+    allow_mono, mono_arg = not multistream, () if multistream else (1 if mono else 0,)
+    planned = batch.info["track_samples"]
+    if getattr(features, "dtype", None) == SPEC_PARAMS_DTYPE:
+        sargs = track_spectrogram_args(batch, features, rate, resample, mono, mix, format, scale, out, device, allow_mono)
+        rec, mrec, scale, offsets, planes, total, out, how = sargs
+        return FilesRequest("files_decode_melspec", how + mono_arg + (mrec, rec), "features", TRACKS_F32, scale, out, 1, offsets, planes, total,
+                            mrec, rec)
+    if resample is not None:
+        format = "s16" if format is None else format
+        (up, down), ch, offsets, total, out, mrec = track_ratio_args(batch, resample, mono, mix, format, out, device, allow_mono, rate, features)
+        fmt, scale, _ = track_format_args(batch, format, scale, None, device)
+        return FilesRequest("files_decode_ratio", (up, down) + mono_arg + (mrec,), "resampled", fmt, scale, out, ch, offsets,
+                            ((planned * up + down - 1) // down + 63) // 64 * 64, total, mrec, None)
+    fargs = track_feature_args(batch, features, n_mels, feature_layout, rate, mono, mix, format, scale, out, device, allow_mono)
+    if fargs is not None:
+        rec, mrec, scale, offsets, planes, total, out = fargs
+        return FilesRequest("files_decode_mel", mono_arg + (mrec, rec), "features", TRACKS_F32, scale, out, 1, offsets, planes, total, mrec, rec)
+    rate, format = 48000 if rate is None else rate, "s16" if format is None else format
+    mrec = None
+    if mix is not None:
+        D, ch, offsets, total, rout, mrec = track_mix_args(batch, mix, rate, format, out, device)
+        entry, args = "files_decode_mixed", (int(rate), mrec)
+    else:
+        rargs = track_rate_args(batch, rate, mono, format, out, device, allow_mono)
+        if rargs is None:
+            fmt, scale, out = track_format_args(batch, format, scale, out, device)
+            return FilesRequest("files_decode" if fmt == TRACKS_S16 else "files_decode_as", (), "tracks", fmt, scale, out, batch.channels,
+                                batch.info["track_offset"], (planned + 63) // 64 * 64, int(batch.track_samples), None, None)
+        D, ch, offsets, total, rout = rargs
+        entry, args = "files_decode_resampled", (int(rate),) + mono_arg
+    fmt, scale, _ = track_format_args(batch, format, scale, None, device)
+    return FilesRequest(entry, args, "resampled", fmt, scale, rout, ch, offsets, ((planned + D - 1) // D + 63) // 64 * 64, total, mrec, None)
+
+
+def _run_files_request(req, lib, prefix, handle, chk, batch, mem):
+    """Carries out a FilesRequest for the decoder `handle` (its C family `prefix`: "opusgpu_" or "opusgpu_ms_") over `batch`, into
+    req.out (a torch tensor on the device: nothing comes to the host) or into a buffer from `mem` (a Context: dev_alloc, d2h,
+    dev_free); chk(code, what) raises.  -> (tracks or features, info).  Tracks are [samples, channels] (planar: transposed), features
+    float32 [n_mels, F] or [F, n_mels].  info: FILE_INFO_DTYPE records plus `final_status` and `bad_packet`, `track_samples` the FINAL
+    length at 48 kHz; resampled tracks have `out_samples` and `out_offset` more; features `feat_offset`, and their `frames` is F, the
+    track's feature frames (the plan's count of Opus frames is batch.info["frames"])."""
+    name = prefix + req.entry
+    n, ch, fmt = batch.n_files, req.channels, req.fmt
+    offsets, counts, lengths = (np.zeros(n, dtype=np.int64) for _ in range(3))
     status = np.zeros((n, 2), dtype=np.int32)
+    head = [a.ctypes.data if isinstance(a, np.ndarray) else a for a in req.args]
+    if req.entry != "files_decode":  # (which has neither)
+        head += ([] if req.kind == "features" else [fmt]) + [None if req.scale is None else req.scale.ctypes.data]
+    tail = [a.ctypes.data for a in ((lengths, status) if req.kind == "tracks" else (offsets, counts, lengths, status))]
 
     def run(d_out):
-        chk(call(None if scale is None else scale.ctypes.data, d_out, feat_offsets.ctypes.data, frames.ctypes.data, lengths.ctypes.data,
-                 status.ctypes.data), name)
-    if out is not None:
+        chk(getattr(lib, name)(handle, batch.h, *head, d_out, *tail), name)
+    if req.out is not None:
         import torch
-        torch.cuda.current_stream(out.device).synchronize()  # as in _decode_planned
-        run(out.data_ptr())
-        packed = out
+        torch.cuda.current_stream(req.out.device).synchronize()  # whatever filled `out` has finished; the call itself waits for its own work
+        run(req.out.data_ptr())
+        packed = req.out
     else:
-        packed = np.zeros(max(total, 1), dtype=np.float32)
+        packed = np.zeros(max(req.total, 1) * ch, dtype=np.int16 if fmt == TRACKS_S16 else np.float32)
         d_out = mem.dev_alloc(packed.nbytes)
         try:
             run(d_out)
             mem.d2h(packed, d_out)
         finally:
             mem.dev_free(d_out)
-    assert (feat_offsets == offsets).all()
-    info = np.zeros(n, dtype=np.dtype(FILE_INFO_DTYPE.descr + [("final_status", "<i4"), ("bad_packet", "<i4"), ("feat_offset", "<i8")]))
+    # the result's own count and offset per file: the fields of `info` that hold them, and which of them are new
+    count_field, offset_field, more = {"tracks": (None, None, []), "resampled": ("out_samples", "out_offset", ["out_samples", "out_offset"]),
+                                       "features": ("frames", "feat_offset", ["feat_offset"])}[req.kind]
+    info = np.zeros(n, dtype=np.dtype(FILE_INFO_DTYPE.descr + [("final_status", "<i4"), ("bad_packet", "<i4")] + [(f, "<i8") for f in more]))
     for field in FILE_INFO_DTYPE.names:
         info[field] = batch.info[field]
     info["track_samples"], info["final_status"], info["bad_packet"] = lengths, status[:, 0], status[:, 1]
-    info["frames"], info["feat_offset"] = frames, feat_offsets
-    if frames_major:
-        feats = [packed[o:o + F * n_mels].reshape(F, n_mels) for o, F in zip(feat_offsets, frames)]
+    if req.kind == "tracks":
+        offsets, counts = req.offsets, lengths
     else:
-        feats = [packed[o:o + n_mels * p].reshape(n_mels, p)[:, :F] for o, p, F in zip(feat_offsets, planes, frames)]
-    return feats, info
-
-
-def _decode_planned(lib, chk, name, handle, batch, mem, args):
-    """The shared body of the two decode_files: runs the decode call `name` of `lib` (`name`_as for a float format) for the decoder
-    `handle` over `batch` into `out` (a torch tensor on the device: nothing comes to the host) or into a track buffer from `mem` (a
-    Context: dev_alloc, d2h, dev_free); args: what track_format_args returned; chk(code, what) raises.  -> (tracks, info)."""
-    fmt, scale, out = args
-    n, ch = batch.n_files, batch.channels
-    total = max(int(batch.track_samples), 1) * ch
-    lengths = np.zeros(n, dtype=np.int64)
-    status = np.zeros((n, 2), dtype=np.int32)
-
-    def run(d_tracks):
-        if fmt == TRACKS_S16:
-            chk(getattr(lib, name)(handle, batch.h, d_tracks, lengths.ctypes.data, status.ctypes.data), name)
-        else:
-            chk(getattr(lib, name + "_as")(handle, batch.h, fmt, None if scale is None else scale.ctypes.data, d_tracks,
-                                           lengths.ctypes.data, status.ctypes.data), name + "_as")
-    if out is not None:
-        import torch
-        torch.cuda.current_stream(out.device).synchronize()  # whatever filled `out` has finished; the call itself waits for its own work
-        run(out.data_ptr())
-        packed = out
-    else:
-        packed = np.zeros(total, dtype=np.int16 if fmt == TRACKS_S16 else np.float32)
-        d_tracks = mem.dev_alloc(packed.nbytes)
-        try:
-            run(d_tracks)
-            mem.d2h(packed, d_tracks)
-        finally:
-            mem.dev_free(d_tracks)
-    info = np.zeros(n, dtype=np.dtype(FILE_INFO_DTYPE.descr + [("final_status", "<i4"), ("bad_packet", "<i4")]))
-    for field in FILE_INFO_DTYPE.names:
-        info[field] = batch.info[field]
-    info["track_samples"], info["final_status"], info["bad_packet"] = lengths, status[:, 0], status[:, 1]
+        assert (offsets == req.offsets).all()
+        info[count_field], info[offset_field] = counts, offsets
+    if req.kind == "features":
+        n_mels = int(req.params["n_mels"][0])
+        if int(req.params["layout"][0]) == MEL_FRAMES_MAJOR:
+            return [packed[o:o + F * n_mels].reshape(F, n_mels) for o, F in zip(offsets, counts)], info
+        return [packed[o:o + n_mels * p].reshape(n_mels, p)[:, :F] for o, p, F in zip(offsets, req.planes, counts)], info
     if fmt == TRACKS_F32_PLANAR:  # track t: `ch` planes of its planned length rounded up to 64, where its interleaved form would lie
-        planes = (batch.info["track_samples"] + 63) // 64 * 64
-        tracks = [packed[ch * o:ch * (o + p)].reshape(ch, p)[:, :ln] for o, p, ln in zip(batch.info["track_offset"], planes, lengths)]
-    else:
-        tracks = [packed[ch * o:ch * (o + ln)].reshape(ln, ch) for o, ln in zip(batch.info["track_offset"], lengths)]
-    return tracks, info
-
-
-def _decode_planned_resampled(chk, name, call, batch, mem, args, rargs):
-    """_decode_planned for resampled tracks: call(fmt, scale pointer, d_out, four array pointers) runs the decode call `name`;
-    args: what track_format_args returned for out=None, rargs: what track_rate_args returned, or the first five of track_ratio_args
-    (a pair (up, down) in place of D).  -> (tracks, info): tracks of [ceil(len / D), output channels] (planar: [output channels,
-    ceil(len / D)]), info with `out_samples` and `out_offset` more."""
-    fmt, scale, _ = args
-    D, ch, offsets, total, out = rargs
-    up, D = D if isinstance(D, tuple) else (1, D)
-    n = batch.n_files
-    out_offsets, out_lengths, lengths = (np.zeros(n, dtype=np.int64) for _ in range(3))
-    status = np.zeros((n, 2), dtype=np.int32)
-
-    def run(d_out):
-        chk(call(fmt, None if scale is None else scale.ctypes.data, d_out, out_offsets.ctypes.data, out_lengths.ctypes.data,
-                 lengths.ctypes.data, status.ctypes.data), name)
-    if out is not None:
-        import torch
-        torch.cuda.current_stream(out.device).synchronize()  # as in _decode_planned
-        run(out.data_ptr())
-        packed = out
-    else:
-        packed = np.zeros(max(total, 1) * ch, dtype=np.int16 if fmt == TRACKS_S16 else np.float32)
-        d_out = mem.dev_alloc(packed.nbytes)
-        try:
-            run(d_out)
-            mem.d2h(packed, d_out)
-        finally:
-            mem.dev_free(d_out)
-    assert (out_offsets == offsets).all()
-    info = np.zeros(n, dtype=np.dtype(FILE_INFO_DTYPE.descr + [("final_status", "<i4"), ("bad_packet", "<i4"), ("out_samples", "<i8"),
-                                                               ("out_offset", "<i8")]))
-    for field in FILE_INFO_DTYPE.names:
-        info[field] = batch.info[field]
-    info["track_samples"], info["final_status"], info["bad_packet"] = lengths, status[:, 0], status[:, 1]
-    info["out_samples"], info["out_offset"] = out_lengths, out_offsets
-    if fmt == TRACKS_F32_PLANAR:
-        planes = ((batch.info["track_samples"] * up + D - 1) // D + 63) // 64 * 64
-        tracks = [packed[ch * o:ch * (o + p)].reshape(ch, p)[:, :ln] for o, p, ln in zip(out_offsets, planes, out_lengths)]
-    else:
-        tracks = [packed[ch * o:ch * (o + ln)].reshape(ln, ch) for o, ln in zip(out_offsets, out_lengths)]
-    return tracks, info
+        return [packed[ch * o:ch * (o + p)].reshape(ch, p)[:, :ln] for o, p, ln in zip(offsets, req.planes, counts)], info
+    return [packed[ch * o:ch * (o + ln)].reshape(ln, ch) for o, ln in zip(offsets, counts)], info
 
 
 class Context:
@@ -1352,62 +1311,17 @@ class Context:
         TRACK SPECTROGRAMS: n_fft, win_length, hop, n_mels, fmin / fmax, Slaney or HTK, power 1 or 2, log10 / ln / none and a floor
         are fields), with rate= or resample= naming that rate (or neither: the record's is taken), mono=True or a mix of one row,
         and scale=, out= and info as with "logmel"; n_mels= and feature_layout= are the record's (track_spectrogram_args)."""
-        if mix is not None and mono:
+        if mix is not None and mono:  # (files_request's first refusal, ahead of the plan as it always was)
             raise ValueError("mix and mono=True exclude each other: the row {8192, 8192} is mono")
         own = batch is None
-        channels = self.channels or 2
         if own:
-            batch = FileBatch(files, channels=channels, rfc=rfc, flags=flags, threads=threads)
+            batch = FileBatch(files, channels=self.channels or 2, rfc=rfc, flags=flags, threads=threads)
         try:
-            if getattr(features, "dtype", None) == SPEC_PARAMS_DTYPE:
-                sargs = track_spectrogram_args(batch, features, rate, resample, mono, mix, format, scale, out, self.device)
-                if self.n_streams < batch.n_files or self.channels != batch.channels:
-                    self.streams_alloc(max(batch.n_files, 1), batch.channels)
-                self.set_mode(batch.rfc)
-
-                def call(scale_p, d_out, *arrays):
-                    return self.lib.opusgpu_files_decode_melspec(self.h, batch.h, *sargs[7], 1 if mono else 0,
-                                                                 None if sargs[1] is None else sargs[1].ctypes.data, sargs[0].ctypes.data,
-                                                                 scale_p, d_out, *arrays)
-                return _decode_planned_mel(self._chk, "opusgpu_files_decode_melspec", call, batch, self, sargs)
-            if resample is not None:
-                format = "s16" if format is None else format
-                qargs = track_ratio_args(batch, resample, mono, mix, format, out, self.device, rate=rate, features=features)
-                args = track_format_args(batch, format, scale, None, self.device)
-                if self.n_streams < batch.n_files or self.channels != batch.channels:
-                    self.streams_alloc(max(batch.n_files, 1), batch.channels)
-                self.set_mode(batch.rfc)
-
-                def call(fmt, scale_p, d_out, *arrays):
-                    return self.lib.opusgpu_files_decode_ratio(self.h, batch.h, qargs[0][0], qargs[0][1], 1 if mono else 0,
-                                                               None if qargs[5] is None else qargs[5].ctypes.data, fmt, scale_p, d_out, *arrays)
-                return _decode_planned_resampled(self._chk, "opusgpu_files_decode_ratio", call, batch, self, args, qargs[:5])
-            fargs = track_feature_args(batch, features, n_mels, feature_layout, rate, mono, mix, format, scale, out, self.device)
-            rate, format = 48000 if rate is None else rate, "s16" if format is None else format
-            if fargs is not None:
-                if self.n_streams < batch.n_files or self.channels != batch.channels:
-                    self.streams_alloc(max(batch.n_files, 1), batch.channels)
-                self.set_mode(batch.rfc)
-
-                def call(scale_p, d_out, *arrays):
-                    return self.lib.opusgpu_files_decode_mel(self.h, batch.h, 1 if mono else 0, None if fargs[1] is None else fargs[1].ctypes.data,
-                                                             fargs[0].ctypes.data, scale_p, d_out, *arrays)
-                return _decode_planned_mel(self._chk, "opusgpu_files_decode_mel", call, batch, self, fargs)
-            margs = None if mix is None else track_mix_args(batch, mix, rate, format, out, self.device)
-            rargs = track_rate_args(batch, rate, mono, format, out, self.device) if mix is None else margs[:5]
-            args = track_format_args(batch, format, scale, out if rargs is None else None, self.device)
+            req = files_request(batch, False, self.device, format, scale, out, rate, mono, mix, features, n_mels, feature_layout, resample)
             if self.n_streams < batch.n_files or self.channels != batch.channels:
                 self.streams_alloc(max(batch.n_files, 1), batch.channels)
             self.set_mode(batch.rfc)
-            if margs is not None:
-                def call(fmt, scale_p, d_out, *arrays):
-                    return self.lib.opusgpu_files_decode_mixed(self.h, batch.h, int(rate), margs[5].ctypes.data, fmt, scale_p, d_out, *arrays)
-                return _decode_planned_resampled(self._chk, "opusgpu_files_decode_mixed", call, batch, self, args, rargs)
-            if rargs is not None:
-                def call(fmt, scale_p, d_out, *arrays):
-                    return self.lib.opusgpu_files_decode_resampled(self.h, batch.h, int(rate), 1 if mono else 0, fmt, scale_p, d_out, *arrays)
-                return _decode_planned_resampled(self._chk, "opusgpu_files_decode_resampled", call, batch, self, args, rargs)
-            return _decode_planned(self.lib, self._chk, "opusgpu_files_decode", self.h, batch, self, args)
+            return _run_files_request(req, self.lib, "opusgpu_", self.h, self._chk, batch, self)
         finally:
             if own:
                 batch.close()
@@ -1589,49 +1503,10 @@ class MultistreamContext:
             batch = MsFileBatch(files, self.layout, rfc=rfc, threads=threads)
         mem = None
         try:
-            if getattr(features, "dtype", None) == SPEC_PARAMS_DTYPE:
-                sargs = track_spectrogram_args(batch, features, rate, resample, False, mix, format, scale, out, self.device, allow_mono=False)
-                mem = Context(self.device)
-                self.set_mode(batch.rfc)
-
-                def call(scale_p, d_out, *arrays):
-                    return self.lib.opusgpu_ms_files_decode_melspec(self.h, batch.h, *sargs[7], sargs[1].ctypes.data, sargs[0].ctypes.data,
-                                                                    scale_p, d_out, *arrays)
-                return _decode_planned_mel(self._chk, "opusgpu_ms_files_decode_melspec", call, batch, mem, sargs)
-            if resample is not None:
-                format = "s16" if format is None else format
-                qargs = track_ratio_args(batch, resample, False, mix, format, out, self.device, allow_mono=False, rate=rate, features=features)
-                args = track_format_args(batch, format, scale, None, self.device)
-                mem = Context(self.device)
-                self.set_mode(batch.rfc)
-
-                def call(fmt, scale_p, d_out, *arrays):
-                    return self.lib.opusgpu_ms_files_decode_ratio(self.h, batch.h, qargs[0][0], qargs[0][1],
-                                                                  None if qargs[5] is None else qargs[5].ctypes.data, fmt, scale_p, d_out, *arrays)
-                return _decode_planned_resampled(self._chk, "opusgpu_ms_files_decode_ratio", call, batch, mem, args, qargs[:5])
-            fargs = track_feature_args(batch, features, n_mels, feature_layout, rate, False, mix, format, scale, out, self.device, allow_mono=False)
-            rate, format = 48000 if rate is None else rate, "s16" if format is None else format
-            if fargs is not None:
-                mem = Context(self.device)
-                self.set_mode(batch.rfc)
-
-                def call(scale_p, d_out, *arrays):
-                    return self.lib.opusgpu_ms_files_decode_mel(self.h, batch.h, fargs[1].ctypes.data, fargs[0].ctypes.data, scale_p, d_out, *arrays)
-                return _decode_planned_mel(self._chk, "opusgpu_ms_files_decode_mel", call, batch, mem, fargs)
-            margs = None if mix is None else track_mix_args(batch, mix, rate, format, out, self.device)
-            rargs = track_rate_args(batch, rate, False, format, out, self.device, allow_mono=False) if mix is None else margs[:5]
-            args = track_format_args(batch, format, scale, out if rargs is None else None, self.device)
+            req = files_request(batch, True, self.device, format, scale, out, rate, False, mix, features, n_mels, feature_layout, resample)
             mem = Context(self.device)  # (device memory and copies are a plain context's calls)
             self.set_mode(batch.rfc)
-            if margs is not None:
-                def call(fmt, scale_p, d_out, *arrays):
-                    return self.lib.opusgpu_ms_files_decode_mixed(self.h, batch.h, int(rate), margs[5].ctypes.data, fmt, scale_p, d_out, *arrays)
-                return _decode_planned_resampled(self._chk, "opusgpu_ms_files_decode_mixed", call, batch, mem, args, rargs)
-            if rargs is not None:
-                def call(fmt, scale_p, d_out, *arrays):
-                    return self.lib.opusgpu_ms_files_decode_resampled(self.h, batch.h, int(rate), fmt, scale_p, d_out, *arrays)
-                return _decode_planned_resampled(self._chk, "opusgpu_ms_files_decode_resampled", call, batch, mem, args, rargs)
-            return _decode_planned(self.lib, self._chk, "opusgpu_ms_files_decode", self.h, batch, mem, args)
+            return _run_files_request(req, self.lib, "opusgpu_ms_", self.h, self._chk, batch, mem)
         finally:
             if mem is not None:
                 mem.close()

@@ -365,6 +365,10 @@ struct MsStepTimer {
     }
 };
 
+static TrackFail track_fail(opusgpu_ms *ms) {
+    return [ms](int code, const char *what, hipError_t e) { return ms_fail(ms, code, what, e); };
+}
+
 // opusgpu_ms_files_decode and opusgpu_ms_files_decode_as: `places` is null for int16 tracks, else the batch's table for `format`
 // (og_tracks.hpp: files_decode_run -- the driver does not depend on the format here either).
 static int ms_files_decode_run(opusgpu_ms *ms, const opusgpu_ms_file_batch *batch, int format, const std::vector<TrackPlace> *places,
@@ -378,10 +382,10 @@ static int ms_files_decode_run(opusgpu_ms *ms, const opusgpu_ms_file_batch *batc
     hipStream_t s = ms->stream;
     if (!batch->segs.empty())
         if (int rc = ms_enter(ms, s)) return rc;
-    TrackPlaceBuf d_place;
+    RsDevBuf d_place; // the place table, for the length of this call
     if (places && !batch->segs.empty()) {
         MSCHK(ms, hipSetDevice(ms->device));
-        MSCHK(ms, d_place.upload(*places));
+        MSCHK(ms, d_place.upload(places->data(), places->size() * sizeof(TrackPlace)));
     }
     std::unique_ptr<MsStepTimer> timer;
     FilesRunOps ops;
@@ -401,12 +405,21 @@ static int ms_files_decode_run(opusgpu_ms *ms, const opusgpu_ms_file_batch *batc
         return ms_tracks_launch(ms, s, n, d_segs, src, row, d_tracks, d_state);
     };
     ops.drain = [&] { return opusgpu_ms_synchronize(ms); };
-    ops.hip_failed = [&](int code, const char *what, hipError_t e) { return ms_fail(ms, code, what, e); };
+    ops.hip_failed = track_fail(ms);
     ops.loop_begin = [&] { timer.reset(new MsStepTimer(s)); };
     ops.loop_end = [&] { timer->stop(); };
     const int rc = files_run(*batch, ops, d_tracks, track_lengths_out, status_out);
     if (!rc && timer) g_ms_files_steps_ms = timer->elapsed_ms();
     return rc;
+}
+
+// The owner of a whole-file call over a multistream batch (og_tracks.hpp: FilesOwner).
+static FilesOwner files_owner(opusgpu_ms *ms, const opusgpu_ms_file_batch *batch) {
+    return FilesOwner{*batch, ms->device, ms->stream,
+                      [=](void *d_s16, int64_t *lengths, int32_t *status) {
+                          return ms_files_decode_run(ms, batch, OPUSGPU_TRACKS_S16, nullptr, d_s16, lengths, status);
+                      },
+                      track_fail(ms)};
 }
 
 extern "C" {
@@ -457,12 +470,8 @@ int opusgpu_ms_files_decode_resampled(opusgpu_ms *ms, const opusgpu_ms_file_batc
                                       void *d_out, int64_t *out_offsets, int64_t *out_lengths, int64_t *track_lengths_out,
                                       int32_t *status_out) {
     if (!ms || !batch) return OPUSGPU_BAD_ARG;
-    return files_resampled_run(
-        *batch, ms->device, ms->stream, rate, 0, format, scale, d_out, out_offsets, out_lengths, track_lengths_out, status_out,
-        [&](void *d_s16, int64_t *lengths, int32_t *status) {
-            return ms_files_decode_run(ms, batch, OPUSGPU_TRACKS_S16, nullptr, d_s16, lengths, status);
-        },
-        [&](int code, const char *what, hipError_t e) { return ms_fail(ms, code, what, e); });
+    return files_resampled_run(files_owner(ms, batch), rate, 0, nullptr, format, scale, d_out, out_offsets, out_lengths, track_lengths_out,
+                               status_out);
 }
 
 // opusgpu_files_decode_mixed behind opusgpu_ms_files_decode: the surround tracks mixed down (or about) on their way to `rate`.
@@ -470,12 +479,8 @@ int opusgpu_ms_files_decode_mixed(opusgpu_ms *ms, const opusgpu_ms_file_batch *b
                                   const float *scale, void *d_out, int64_t *out_offsets, int64_t *out_lengths, int64_t *track_lengths_out,
                                   int32_t *status_out) {
     if (!ms || !batch || !mix) return OPUSGPU_BAD_ARG;
-    return files_resampled_run(
-        *batch, ms->device, ms->stream, rate, 0, format, scale, d_out, out_offsets, out_lengths, track_lengths_out, status_out,
-        [&](void *d_s16, int64_t *lengths, int32_t *status) {
-            return ms_files_decode_run(ms, batch, OPUSGPU_TRACKS_S16, nullptr, d_s16, lengths, status);
-        },
-        [&](int code, const char *what, hipError_t e) { return ms_fail(ms, code, what, e); }, mix);
+    return files_resampled_run(files_owner(ms, batch), rate, 0, mix, format, scale, d_out, out_offsets, out_lengths, track_lengths_out,
+                               status_out);
 }
 
 // opusgpu_files_decode_ratio behind opusgpu_ms_files_decode (og_tracks_resample_ratio.hpp): the layout's channels, through *mix if
@@ -484,12 +489,8 @@ int opusgpu_ms_files_decode_ratio(opusgpu_ms *ms, const opusgpu_ms_file_batch *b
                                   int format, const float *scale, void *d_out, int64_t *out_offsets, int64_t *out_lengths,
                                   int64_t *track_lengths_out, int32_t *status_out) {
     if (!ms || !batch) return OPUSGPU_BAD_ARG;
-    return files_ratio_run(
-        *batch, ms->device, ms->stream, up, down, 0, mix, format, scale, d_out, out_offsets, out_lengths, track_lengths_out, status_out,
-        [&](void *d_s16, int64_t *lengths, int32_t *status) {
-            return ms_files_decode_run(ms, batch, OPUSGPU_TRACKS_S16, nullptr, d_s16, lengths, status);
-        },
-        [&](int code, const char *what, hipError_t e) { return ms_fail(ms, code, what, e); });
+    return files_ratio_run(files_owner(ms, batch), up, down, 0, mix, format, scale, d_out, out_offsets, out_lengths, track_lengths_out,
+                           status_out);
 }
 
 // opusgpu_files_decode_mel behind opusgpu_ms_files_decode (og_tracks_mel.hpp): the layout's channels through a one-row *mix.
@@ -497,12 +498,7 @@ int opusgpu_ms_files_decode_mel(opusgpu_ms *ms, const opusgpu_ms_file_batch *bat
                                 const opusgpu_mel_params *params, const float *scale, void *d_out, int64_t *feat_offsets, int64_t *frames_out,
                                 int64_t *track_lengths_out, int32_t *status_out) {
     if (!ms || !batch || !mix) return OPUSGPU_BAD_ARG;
-    return files_mel_run(
-        *batch, ms->device, ms->stream, 0, mix, params, scale, d_out, feat_offsets, frames_out, track_lengths_out, status_out,
-        [&](void *d_s16, int64_t *lengths, int32_t *status) {
-            return ms_files_decode_run(ms, batch, OPUSGPU_TRACKS_S16, nullptr, d_s16, lengths, status);
-        },
-        [&](int code, const char *what, hipError_t e) { return ms_fail(ms, code, what, e); });
+    return files_mel_run(files_owner(ms, batch), 0, mix, params, scale, d_out, feat_offsets, frames_out, track_lengths_out, status_out);
 }
 
 // opusgpu_files_decode_melspec behind opusgpu_ms_files_decode (og_tracks_melspec.hpp): the layout's channels through a one-row *mix.
@@ -510,12 +506,8 @@ int opusgpu_ms_files_decode_melspec(opusgpu_ms *ms, const opusgpu_ms_file_batch 
                                     const opusgpu_mix_matrix *mix, const opusgpu_spec_params *p, const float *scale, void *d_out,
                                     int64_t *feat_offsets, int64_t *frames_out, int64_t *track_lengths_out, int32_t *status_out) {
     if (!ms || !batch || !mix) return OPUSGPU_BAD_ARG;
-    return files_melspec_run(
-        *batch, ms->device, ms->stream, rate, up, down, 0, mix, p, scale, d_out, feat_offsets, frames_out, track_lengths_out, status_out,
-        [&](void *d_s16, int64_t *lengths, int32_t *status) {
-            return ms_files_decode_run(ms, batch, OPUSGPU_TRACKS_S16, nullptr, d_s16, lengths, status);
-        },
-        [&](int code, const char *what, hipError_t e) { return ms_fail(ms, code, what, e); });
+    return files_melspec_run(files_owner(ms, batch), rate, up, down, 0, mix, p, scale, d_out, feat_offsets, frames_out, track_lengths_out,
+                             status_out);
 }
 
 } // extern "C"

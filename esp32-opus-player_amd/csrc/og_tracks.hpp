@@ -226,14 +226,27 @@ static int track_places(const og_batch &b, int format, const float *scale, std::
     }
     return OPUSGPU_OK;
 }
-// Its device copy for the length of one decode call: freed on every way out.
-struct TrackPlaceBuf {
+// What the host side of every track header shares.
+// A HIP call inside a function that has a `hip_failed(code, what, e)` in reach: a failure leaves through it.
+#define TRK_CHK(call)                                                             \
+    do {                                                                          \
+        const hipError_t e_ = (call);                                             \
+        if (e_ != hipSuccess) return hip_failed(OPUSGPU_ERR_HIP, #call, e_);      \
+    } while (0)
+// hip_failed: keeps the message of the object the call belongs to and returns `code`.
+typedef std::function<int(int code, const char *what, hipError_t e)> TrackFail;
+static TrackFail track_fail(opusgpu_ctx *ctx) {
+    return [ctx](int code, const char *what, hipError_t e) { return fail(ctx, code, what, e); };
+}
+// A device buffer for the length of one call: freed on every way out.
+struct RsDevBuf {
     void *p = nullptr;
-    hipError_t upload(const std::vector<TrackPlace> &places) {
-        const hipError_t e = hipMalloc(&p, places.size() * sizeof(TrackPlace) + 16);
-        return e != hipSuccess ? e : hipMemcpy(p, places.data(), places.size() * sizeof(TrackPlace), hipMemcpyHostToDevice);
+    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes + 16); }
+    hipError_t upload(const void *src, size_t bytes) {
+        const hipError_t e = alloc(bytes);
+        return e != hipSuccess || !bytes ? e : hipMemcpy(p, src, bytes, hipMemcpyHostToDevice);
     }
-    ~TrackPlaceBuf() {
+    ~RsDevBuf() {
         if (p) (void)hipFree(p);
     }
 };
@@ -246,10 +259,10 @@ static int files_decode_run(opusgpu_ctx *ctx, const opusgpu_file_batch *batch, i
     if (!ctx || !batch) return OPUSGPU_BAD_ARG;
     if (!ctx->d_streams || ctx->n_streams < batch->n_files || ctx->channels != batch->channels || ctx->mode != batch->mode)
         return OPUSGPU_BAD_ARG;
-    TrackPlaceBuf d_place;
+    RsDevBuf d_place; // the place table, for the length of this call
     if (places && !batch->segs.empty()) {
         HIPCHK(ctx, hipSetDevice(ctx->device));
-        HIPCHK(ctx, d_place.upload(*places));
+        HIPCHK(ctx, d_place.upload(places->data(), places->size() * sizeof(TrackPlace)));
     }
     const int row = batch->mode == OPUSGPU_MODE_RFC ? OPUSGPU_RFC_FRAME_SAMPLES : OPUSGPU_FRAME_SAMPLES;
     FilesRunOps ops;
@@ -268,8 +281,26 @@ static int files_decode_run(opusgpu_ctx *ctx, const opusgpu_file_batch *batch, i
         const hipError_t e = hipStreamSynchronize(ctx->stream);
         return e == hipSuccess ? (int)OPUSGPU_OK : fail(ctx, OPUSGPU_ERR_HIP, "hipStreamSynchronize(files)", e);
     };
-    ops.hip_failed = [&](int code, const char *what, hipError_t e) { return fail(ctx, code, what, e); };
+    ops.hip_failed = track_fail(ctx);
     return files_run(*batch, ops, d_tracks, track_lengths_out, status_out);
+}
+
+// The owner of a whole-file call that ends in another kernel (TRACK RATES and all behind it): the batch, where its work runs, the
+// decoder that turns the batch into scratch S16 tracks, and who keeps the message of a HIP error.  One maker per kind of decoder:
+// here and in og_ms_tracks.hpp.
+struct FilesOwner {
+    const og_batch &b;
+    int device;
+    hipStream_t stream;
+    std::function<int(void *d_s16, int64_t *lengths, int32_t *status)> decode;
+    TrackFail hip_failed;
+};
+static FilesOwner files_owner(opusgpu_ctx *ctx, const opusgpu_file_batch *batch) {
+    return FilesOwner{*batch, ctx->device, ctx->stream,
+                      [=](void *d_s16, int64_t *lengths, int32_t *status) {
+                          return files_decode_run(ctx, batch, OPUSGPU_TRACKS_S16, nullptr, d_s16, lengths, status);
+                      },
+                      track_fail(ctx)};
 }
 
 extern "C" {

@@ -1,7 +1,7 @@
 // og_tracks_mel.hpp -- log-mel features of the 16 kHz mono tracks (include/opusgpu.h, TRACK FEATURES): the tables, the kernel that
 // turns packed int16 mono tracks into float32 feature tracks, its host side, and the whole-file call that ends in it.  Included at
-// the end of og_api.hip behind og_tracks_resample.hpp (files_resampled_run, RsDevBuf, track_f32) and in front of og_ms_tracks.hpp,
-// which holds the multistream twin of the whole-file call.
+// the end of og_api.hip behind og_tracks_resample_ratio.hpp (files_resampled_run, files_ratio_run; og_tracks.hpp: RsDevBuf,
+// track_f32) and in front of og_ms_tracks.hpp, which holds the multistream twin of the whole-file call.
 #pragma once
 #include <cmath>
 #include <vector>
@@ -223,33 +223,53 @@ static void mel_bank_make(double bin_hz, int bins, int n_mels, bool htk, bool sl
         }
     }
 }
+// The two packers that both kernels' tables go through: the numbers of Wc / Ws and of a bank in the order the lanes load them, for
+// a list of blocks of 32 bins (entry b of the list is block b of the packed table).
+// basis [block][n_fft / 4 k-steps][64 lanes][cos, sin]: tap 1 + 2 ks + (lane >> 5), bin 32 nb + (lane & 31); the middle tap folded
+// (u = 2 x there: cos halved; v = 0: no sin), 0 behind the last bin.
+static std::vector<float> feat_pack_basis(const std::vector<float> &wc, const std::vector<float> &ws, int n_fft,
+                                          const std::vector<int> &blocks) {
+    const int bins = n_fft / 2 + 1, KS = n_fft / 4;
+    std::vector<float> basis(blocks.size() * KS * 64 * 2, 0.f);
+    for (size_t b = 0; b < blocks.size(); b++)
+        for (int ks = 0; ks < KS; ks++)
+            for (int lane = 0; lane < 64; lane++) {
+                const int i = 1 + 2 * ks + (lane >> 5), k = 32 * blocks[b] + (lane & 31);
+                if (k >= bins) continue;
+                float *const d = &basis[((b * KS + ks) * 64 + lane) * 2];
+                d[0] = i == n_fft / 2 ? 0.5f * wc[(size_t)i * bins + k] : wc[(size_t)i * bins + k];
+                d[1] = i == n_fft / 2 ? 0.f : ws[(size_t)i * bins + k];
+            }
+    return basis;
+}
+// fb [block][MB band blocks][16][64 lanes]: band 32 mm + (lane & 31), bin 32 nb + 8 (r >> 2) + 4 (lane >> 5) + (r & 3), 0 behind
+// the last band and bin; weighted(b, mm) is told of every (block, band block) that holds a non-zero entry: the caller's mask bits.
+template <class Weighted>
+static std::vector<float> feat_pack_fb(const std::vector<float> &bank, int bins, int n_mels, const std::vector<int> &blocks, int MB,
+                                       Weighted weighted) {
+    std::vector<float> fb(blocks.size() * MB * 16 * 64, 0.f);
+    for (size_t b = 0; b < blocks.size(); b++)
+        for (int mm = 0; mm < MB; mm++)
+            for (int r = 0; r < 16; r++)
+                for (int lane = 0; lane < 64; lane++) {
+                    const int j = 32 * mm + (lane & 31), k = 32 * blocks[b] + 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3);
+                    if (j >= n_mels || k >= bins) continue;
+                    const float w = bank[(size_t)j * bins + k];
+                    fb[((b * MB + mm) * 16 + r) * 64 + lane] = w;
+                    if (w != 0.f) weighted((int)b, mm);
+                }
+    return fb;
+}
 static MelTables mel_tables_make() {
     MelTables t;
     mel_basis_make(OPUSGPU_MEL_NFFT, OPUSGPU_MEL_NFFT, t.wc, t.ws);
-    t.basis.assign((size_t)MEL_NB * MEL_KS * 64 * 2, 0.f);
-    for (int nb = 0; nb < MEL_NB; nb++)
-        for (int ks = 0; ks < MEL_KS; ks++)
-            for (int lane = 0; lane < 64; lane++) {
-                const int i = 1 + 2 * ks + (lane >> 5), k = 32 * nb + (lane & 31);
-                if (k > 200) continue;
-                float *const d = &t.basis[(((size_t)nb * MEL_KS + ks) * 64 + lane) * 2];
-                d[0] = i == 200 ? 0.5f * t.wc[i * 201 + k] : t.wc[i * 201 + k]; // u_200 = 2 x_200
-                d[1] = i == 200 ? 0.f : t.ws[i * 201 + k];                       // v_200 = 0
-            }
+    const std::vector<int> all{0, 1, 2, 3, 4, 5, 6}; // the kernel walks every block
+    static_assert(MEL_NB == 7 && MEL_KS == OPUSGPU_MEL_NFFT / 4, "k_tracks_mel's table");
+    t.basis = feat_pack_basis(t.wc, t.ws, OPUSGPU_MEL_NFFT, all);
     for (int v = 0; v < 2; v++) {
         const int n_mels = v ? 128 : 80, MB = n_mels / 32 + (n_mels % 32 != 0);
         mel_bank_make(40.0, OPUSGPU_MEL_BINS, n_mels, false, true, OPUSGPU_MEL_FMIN, OPUSGPU_MEL_FMAX, t.bank[v]);
-        t.fb[v].assign((size_t)MEL_NB * MB * 16 * 64, 0.f);
-        for (int nb = 0; nb < MEL_NB; nb++)
-            for (int mm = 0; mm < MB; mm++)
-                for (int r = 0; r < 16; r++)
-                    for (int lane = 0; lane < 64; lane++) {
-                        const int j = 32 * mm + (lane & 31), k = 32 * nb + 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3);
-                        if (j >= n_mels || k > 200) continue;
-                        const float b = t.bank[v][(size_t)j * 201 + k];
-                        t.fb[v][(((size_t)nb * MB + mm) * 16 + r) * 64 + lane] = b;
-                        if (b != 0.f) t.mask[v] |= 1u << (4 * nb + mm);
-                    }
+        t.fb[v] = feat_pack_fb(t.bank[v], OPUSGPU_MEL_BINS, n_mels, all, MB, [&](int nb, int mm) { t.mask[v] |= 1u << (4 * nb + mm); });
     }
     return t;
 }
@@ -268,94 +288,146 @@ static bool mel_params_ok(const opusgpu_mel_params *p) {
 }
 static int64_t mel_plane(int64_t planned_48k) { return rs_round64((planned_48k + 2) / 3 / OPUSGPU_MEL_HOP); }
 
-// The kernel over n tracks: checks the spans, builds the tile table, uploads it with the spans and the tables, launches on `s` and
-// waits; every device buffer of the call is freed on every way out.
-template <class Fail>
-static int tracks_mel_run(int device, hipStream_t s, int n_tracks, const opusgpu_mel_span *spans, const void *d_in,
-                          const opusgpu_mel_params *params, void *d_out, Fail hip_failed) {
-    if (!mel_params_ok(params) || n_tracks < 0 || (n_tracks && !spans)) return OPUSGPU_BAD_ARG;
+// Either feature kernel over n tracks: checks the spans, builds the tile table of T frames a tile, uploads it with the spans and the
+// two packed tables, launches on `s` and waits; every device buffer of the call is freed on every way out.  frames(in_samples) is
+// the kernel's frame count, max_frames the most a track may have; tables() is called once there is work and returns the packed
+// basis and filterbank, launch(n_tiles, d_tiles, d_spans, d_basis, d_fb) then queues the kernel.
+struct FeatTables {
+    const std::vector<float> *basis, *fb;
+};
+template <class Frames, class Tables, class Launch>
+static int tracks_feature_run(int device, hipStream_t s, int n_tracks, const opusgpu_mel_span *spans, const void *d_in, void *d_out, int T,
+                              int64_t max_frames, Frames frames, Tables tables, Launch launch, const TrackFail &hip_failed) {
+    if (n_tracks < 0 || (n_tracks && !spans)) return OPUSGPU_BAD_ARG;
     std::vector<MelTile> tiles;
     for (int t = 0; t < n_tracks; t++) {
         const opusgpu_mel_span &sp = spans[t];
         if (sp.in_offset < 0 || sp.in_offset % 8 || sp.in_samples < 0 || sp.out_offset < 0 || sp.out_offset % 64 || sp.reserved)
             return OPUSGPU_BAD_ARG;
-        const int64_t F = sp.in_samples / OPUSGPU_MEL_HOP;
+        const int64_t F = frames(sp.in_samples);
         if (sp.plane < F || sp.plane % 64 || !std::isfinite(sp.scale)) return OPUSGPU_BAD_ARG;
-        if (F > 0x7fffffff || (F + MEL_T - 1) / MEL_T + (int64_t)tiles.size() > 0x7fffffff) return OPUSGPU_BAD_ARG;
-        for (int64_t f = 0; f < F; f += MEL_T) tiles.push_back(MelTile{t, (i32)f});
+        if (F > max_frames || (F + T - 1) / T + (int64_t)tiles.size() > 0x7fffffff) return OPUSGPU_BAD_ARG;
+        for (int64_t f = 0; f < F; f += T) tiles.push_back(MelTile{t, (i32)f});
     }
     if (tiles.empty()) return OPUSGPU_OK;
     if (!d_in || !d_out || ((uintptr_t)d_in & 15) || ((uintptr_t)d_out & 127)) return OPUSGPU_BAD_ARG;
-    const MelTables &tab = mel_tables();
-    const int v = params->n_mels == 128;
-#define MEL_CHK(call)                                                             \
-    do {                                                                          \
-        const hipError_t e_ = (call);                                             \
-        if (e_ != hipSuccess) return hip_failed(OPUSGPU_ERR_HIP, #call, e_);      \
-    } while (0)
-    MEL_CHK(hipSetDevice(device));
+    const FeatTables tab = tables();
+    TRK_CHK(hipSetDevice(device));
     RsDevBuf d_spans, d_tiles, d_basis, d_fb;
-    MEL_CHK(d_spans.upload(spans, (size_t)n_tracks * sizeof(MelSpan)));
-    MEL_CHK(d_tiles.upload(tiles.data(), tiles.size() * sizeof(MelTile)));
-    MEL_CHK(d_basis.upload(tab.basis.data(), tab.basis.size() * sizeof(float)));
-    MEL_CHK(d_fb.upload(tab.fb[v].data(), tab.fb[v].size() * sizeof(float)));
-    auto go = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3((unsigned)tiles.size()), dim3(256), 0, s, (const MelTile *)d_tiles.p, (const MelSpan *)d_spans.p,
-                           (const i16 *)d_in, (const float2 *)d_basis.p, (const float *)d_fb.p, tab.mask[v], (int)params->n_mels,
-                           params->layout == OPUSGPU_MEL_FRAMES_MAJOR ? 1 : 0, (float *)d_out);
-    };
-    if (v)
-        go(k_tracks_mel<4>);
-    else
-        go(k_tracks_mel<3>);
-    MEL_CHK(hipGetLastError());
-    MEL_CHK(hipStreamSynchronize(s));
-#undef MEL_CHK
+    TRK_CHK(d_spans.upload(spans, (size_t)n_tracks * sizeof(MelSpan)));
+    TRK_CHK(d_tiles.upload(tiles.data(), tiles.size() * sizeof(MelTile)));
+    TRK_CHK(d_basis.upload(tab.basis->data(), tab.basis->size() * sizeof(float)));
+    TRK_CHK(d_fb.upload(tab.fb->data(), tab.fb->size() * sizeof(float)));
+    launch((unsigned)tiles.size(), (const MelTile *)d_tiles.p, (const MelSpan *)d_spans.p, (const float2 *)d_basis.p, (const float *)d_fb.p);
+    TRK_CHK(hipGetLastError());
+    TRK_CHK(hipStreamSynchronize(s));
     return OPUSGPU_OK;
 }
 
-// What the whole-file calls refuse before any device work, on top of the resampled call's own refusals: the result is one channel.
-static bool files_mel_args_ok(const og_batch &b, int mono, const opusgpu_mix_matrix *mix, const opusgpu_mel_params *params, const float *scale,
-                              const void *d_out) {
-    if (!mel_params_ok(params) || ((uintptr_t)d_out & 127)) return false;
-    if (mix ? mono || mix->out_channels != 1 : !mono) return false;
-    if (!rs_args_factor(b.channels, OPUSGPU_MEL_SR, mono, OPUSGPU_TRACKS_S16, mix)) return false;
-    return rs_scale_ok(OPUSGPU_TRACKS_F32, scale, b.n_files);
+// k_tracks_mel over n tracks.  A track may have any int32 count of frames here and 0x7fffffff - T of them in tracks_melspec_run
+// (og_tracks_melspec.hpp): the two bounds are kept as each call was published.  Neither kernel needs the stricter one -- both widen a
+// tile's first frame to 64 bits before they add to it -- so it only keeps first + T an int32 for code that may want it so.
+static int tracks_mel_run(int device, hipStream_t s, int n_tracks, const opusgpu_mel_span *spans, const void *d_in,
+                          const opusgpu_mel_params *params, void *d_out, const TrackFail &hip_failed) {
+    if (!mel_params_ok(params)) return OPUSGPU_BAD_ARG;
+    const int v = params->n_mels == 128;
+    const MelTables *tab = nullptr;
+    return tracks_feature_run(
+        device, s, n_tracks, spans, d_in, d_out, MEL_T, 0x7fffffff, [](int64_t n) { return n / OPUSGPU_MEL_HOP; },
+        [&] {
+            tab = &mel_tables();
+            return FeatTables{&tab->basis, &tab->fb[v]};
+        },
+        [&](unsigned n_tiles, const MelTile *d_tiles, const MelSpan *d_spans, const float2 *d_basis, const float *d_fb) {
+            auto go = [&](auto kern) {
+                hipLaunchKernelGGL(kern, dim3(n_tiles), dim3(256), 0, s, d_tiles, d_spans, (const i16 *)d_in, d_basis, d_fb, tab->mask[v],
+                                   (int)params->n_mels, params->layout == OPUSGPU_MEL_FRAMES_MAJOR ? 1 : 0, (float *)d_out);
+            };
+            if (v)
+                go(k_tracks_mel<4>);
+            else
+                go(k_tracks_mel<3>);
+        },
+        hip_failed);
 }
 
-// Both whole-file calls: files_resampled_run (with the caller's decoder) into a scratch buffer of int16 mono tracks at 16 kHz on
-// the grid of TRACK RATES, then k_tracks_mel from there into d_out.  The caller's arrays are written last.
-template <class Decode, class Fail>
-static int files_mel_run(const og_batch &b, int device, hipStream_t s, int mono, const opusgpu_mix_matrix *mix, const opusgpu_mel_params *params,
-                         const float *scale, void *d_out, int64_t *feat_offsets, int64_t *frames_out, int64_t *track_lengths_out,
-                         int32_t *status_out, Decode decode, Fail hip_failed) {
-    if (!files_mel_args_ok(b, mono, mix, params, scale, d_out)) return OPUSGPU_BAD_ARG;
+// What differs between the whole-file calls that end in a feature kernel.
+struct FeatFlow {
+    int sample_rate;                                        // the argument check: the rate the params name, 0: they are refused
+    const char *scratch_failed;                             // the message of a scratch buffer that could not be had
+    std::function<int64_t(int64_t planned_48k, int up, int down)> plane;
+    std::function<int64_t(int64_t len)> frames;             // of a track of `len` samples at the features' rate
+    std::function<int64_t(int n, const int64_t *planned_48k, int up, int down, int64_t *feat_offsets)> layout;
+    std::function<int(int n, const opusgpu_mel_span *spans, const void *d_in)> run; // the kernel, into d_out
+};
+
+// Every whole-file call that ends in a feature kernel: what it refuses before any device work -- on top of the resampling call's own
+// refusals the result is one channel, at the rate the params name --, then files_resampled_run (`rate`, with up = down = 0) or
+// files_ratio_run (rate 0) with the owner's decoder into a scratch buffer of int16 mono tracks at the features' rate, on that call's
+// grid -- the 48 kHz scratch is theirs and is gone when they return --, then the kernel from there into d_out.  The caller's arrays
+// are written last.
+static int files_feature_run(const FilesOwner &own, int rate, int up, int down, int mono, const opusgpu_mix_matrix *mix, const float *scale,
+                             void *d_out, int64_t *feat_offsets, int64_t *frames_out, int64_t *track_lengths_out, int32_t *status_out,
+                             const FeatFlow &flow) {
+    const og_batch &b = own.b;
+    const int sample_rate = flow.sample_rate;
+    if (!sample_rate || ((uintptr_t)d_out & 127)) return OPUSGPU_BAD_ARG;
+    if (mix ? mono || mix->out_channels != 1 : !mono) return OPUSGPU_BAD_ARG;
+    if (rate) {
+        if (up || down) return OPUSGPU_BAD_ARG;
+        const int D = rs_args_factor(b.channels, rate, mono, OPUSGPU_TRACKS_S16, mix);
+        if (!D) return OPUSGPU_BAD_ARG;
+        up = 1, down = D;
+    } else {
+        if (!rr_args_taps(b.channels, up, down, mono, OPUSGPU_TRACKS_S16, mix)) return OPUSGPU_BAD_ARG;
+        if (48000LL * up % down) return OPUSGPU_BAD_ARG; // the track's rate is no integer: no sample_rate names it
+    }
+    if ((int64_t)sample_rate * down != 48000LL * up) return OPUSGPU_BAD_ARG;
+    if (!rs_scale_ok(OPUSGPU_TRACKS_F32, scale, b.n_files)) return OPUSGPU_BAD_ARG;
     const size_t n = (size_t)b.n_files;
-    std::vector<int64_t> planned(n), offs16(n, 0), len16(n, 0), lengths(n, 0), feat(n, 0);
+    std::vector<int64_t> planned(n), offs(n, 0), len(n, 0), lengths(n, 0), feat(n, 0);
     std::vector<int32_t> status(2 * n, 0);
     for (size_t i = 0; i < n; i++) planned[i] = b.info[i].track_samples;
-    const int64_t total16 = opusgpu_resample_layout((int)n, planned.data(), OPUSGPU_MEL_SR, nullptr);
-    if (total16 < 0 || opusgpu_mel_layout((int)n, planned.data(), params, feat.data()) < 0) return OPUSGPU_BAD_ARG;
-    RsDevBuf y16; // the int16 mono tracks at 16 kHz, for the length of this call
+    const int64_t total = rate ? opusgpu_resample_layout((int)n, planned.data(), rate, nullptr)
+                               : opusgpu_resample_ratio_layout((int)n, planned.data(), up, down, nullptr);
+    if (total < 0 || flow.layout((int)n, planned.data(), up, down, feat.data()) < 0) return OPUSGPU_BAD_ARG;
+    RsDevBuf y; // the int16 mono tracks at the features' rate, for the length of this call
     if (!b.segs.empty()) {
-        hipError_t e = hipSetDevice(device);
-        if (e == hipSuccess) e = y16.alloc((size_t)total16 * 2 + 128);
-        if (e != hipSuccess) return hip_failed(OPUSGPU_ALLOC_FAIL, "hipMalloc(mel scratch)", e);
+        hipError_t e = hipSetDevice(own.device);
+        if (e == hipSuccess) e = y.alloc((size_t)total * 2 + 128);
+        if (e != hipSuccess) return own.hip_failed(OPUSGPU_ALLOC_FAIL, flow.scratch_failed, e);
     }
-    if (int rc = files_resampled_run(b, device, s, OPUSGPU_MEL_SR, mono, OPUSGPU_TRACKS_S16, nullptr, y16.p, offs16.data(), len16.data(),
-                                     lengths.data(), status.data(), decode, hip_failed, mix))
-        return rc;
+    const int rc = rate ? files_resampled_run(own, rate, mono, mix, OPUSGPU_TRACKS_S16, nullptr, y.p, offs.data(), len.data(), lengths.data(),
+                                              status.data())
+                        : files_ratio_run(own, up, down, mono, mix, OPUSGPU_TRACKS_S16, nullptr, y.p, offs.data(), len.data(), lengths.data(),
+                                          status.data());
+    if (rc) return rc;
     std::vector<opusgpu_mel_span> spans(n);
     for (size_t i = 0; i < n; i++)
-        spans[i] = opusgpu_mel_span{offs16[i], len16[i], feat[i], mel_plane(planned[i]), scale ? scale[i] : 1.0f / 32768, 0};
-    if (int rc = tracks_mel_run(device, s, (int)n, spans.data(), y16.p, params, d_out, hip_failed)) return rc;
+        spans[i] = opusgpu_mel_span{offs[i], len[i], feat[i], flow.plane(planned[i], up, down), scale ? scale[i] : 1.0f / 32768, 0};
+    if (int rc2 = flow.run((int)n, spans.data(), y.p)) return rc2;
     for (size_t i = 0; i < n; i++) {
         if (feat_offsets) feat_offsets[i] = feat[i];
-        if (frames_out) frames_out[i] = len16[i] / OPUSGPU_MEL_HOP;
+        if (frames_out) frames_out[i] = flow.frames(len[i]);
         if (track_lengths_out) track_lengths_out[i] = lengths[i];
     }
     if (status_out) std::copy(status.begin(), status.end(), status_out);
     return OPUSGPU_OK;
+}
+
+// opusgpu_files_decode_mel and its multistream twin (og_ms_tracks.hpp): the flow above at 16 kHz, through the rate branch.
+static int files_mel_run(const FilesOwner &own, int mono, const opusgpu_mix_matrix *mix, const opusgpu_mel_params *params, const float *scale,
+                         void *d_out, int64_t *feat_offsets, int64_t *frames_out, int64_t *track_lengths_out, int32_t *status_out) {
+    FeatFlow flow;
+    flow.sample_rate = mel_params_ok(params) ? OPUSGPU_MEL_SR : 0;
+    flow.scratch_failed = "hipMalloc(mel scratch)";
+    flow.plane = [](int64_t planned, int, int) { return mel_plane(planned); };
+    flow.frames = [](int64_t len) { return len / OPUSGPU_MEL_HOP; };
+    flow.layout = [=](int n, const int64_t *planned, int, int, int64_t *feat) { return opusgpu_mel_layout(n, planned, params, feat); };
+    flow.run = [&](int n, const opusgpu_mel_span *spans, const void *d_in) {
+        return tracks_mel_run(own.device, own.stream, n, spans, d_in, params, d_out, own.hip_failed);
+    };
+    return files_feature_run(own, OPUSGPU_MEL_SR, 0, 0, mono, mix, scale, d_out, feat_offsets, frames_out, track_lengths_out, status_out, flow);
 }
 
 extern "C" {
@@ -388,19 +460,14 @@ int opusgpu_tracks_mel_device(opusgpu_ctx *ctx, int n_tracks, const opusgpu_mel_
                               const opusgpu_mel_params *params, void *d_out, void *hip_stream) {
     if (!ctx) return OPUSGPU_BAD_ARG;
     return tracks_mel_run(ctx->device, hip_stream ? (hipStream_t)hip_stream : ctx->stream, n_tracks, spans, d_in16k_mono, params, d_out,
-                          [&](int code, const char *what, hipError_t e) { return fail(ctx, code, what, e); });
+                          track_fail(ctx));
 }
 
 int opusgpu_files_decode_mel(opusgpu_ctx *ctx, const opusgpu_file_batch *batch, int mono, const opusgpu_mix_matrix *mix,
                              const opusgpu_mel_params *params, const float *scale, void *d_out, int64_t *feat_offsets, int64_t *frames_out,
                              int64_t *track_lengths_out, int32_t *status_out) {
     if (!ctx || !batch) return OPUSGPU_BAD_ARG;
-    return files_mel_run(
-        *batch, ctx->device, ctx->stream, mono, mix, params, scale, d_out, feat_offsets, frames_out, track_lengths_out, status_out,
-        [&](void *d_s16, int64_t *lengths, int32_t *status) {
-            return files_decode_run(ctx, batch, OPUSGPU_TRACKS_S16, nullptr, d_s16, lengths, status);
-        },
-        [&](int code, const char *what, hipError_t e) { return fail(ctx, code, what, e); });
+    return files_mel_run(files_owner(ctx, batch), mono, mix, params, scale, d_out, feat_offsets, frames_out, track_lengths_out, status_out);
 }
 
 } // extern "C"

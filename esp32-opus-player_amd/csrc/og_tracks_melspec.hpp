@@ -1,7 +1,7 @@
 // og_tracks_melspec.hpp -- mel spectrograms of the mono track at any rate, n_fft and hop (include/opusgpu.h, TRACK SPECTROGRAMS): the
 // tables per parameter set, the kernel that turns packed int16 mono tracks into float32 feature tracks, its host side, and the
 // whole-file call that ends in it.  Included at the end of og_api.hip behind og_tracks_mel.hpp, whose table builders
-// (mel_basis_make, mel_bank_make), span record and design it shares, and in front of og_ms_tracks.hpp, which holds the multistream
+// and packers, span record, run function and whole-file flow it shares, and in front of og_ms_tracks.hpp, which holds the multistream
 // twin of the whole-file call.
 #pragma once
 #include <map>
@@ -246,7 +246,7 @@ static bool spec_params_ok(const opusgpu_spec_params *p) {
 
 static std::unique_ptr<SpecTables> spec_tables_make(const opusgpu_spec_params &p) {
     std::unique_ptr<SpecTables> t(new SpecTables);
-    const int N = p.n_fft, bins = N / 2 + 1, KS = N / 4, n_mels = p.n_mels;
+    const int N = p.n_fft, bins = N / 2 + 1, n_mels = p.n_mels;
     t->n_fft = N, t->bins = bins, t->n_mels = n_mels;
     mel_basis_make(N, spec_win(p), t->wc, t->ws);
     mel_bank_make((double)p.sample_rate / N, bins, n_mels, p.mel_scale == OPUSGPU_SPEC_HTK, p.norm == OPUSGPU_SPEC_NORM_SLANEY, p.fmin, p.fmax,
@@ -258,29 +258,8 @@ static std::unique_ptr<SpecTables> spec_tables_make(const opusgpu_spec_params &p
             for (int k = 32 * nb; k < 32 * nb + 32 && k < bins && !any; k++) any = t->bank[(size_t)j * bins + k] != 0.f;
         if (any) t->blocks.push_back(nb);
     }
-    const size_t nk = t->blocks.size();
-    t->basis.assign(nk * KS * 64 * 2, 0.f);
-    t->fb.assign(nk * 4 * 16 * 64, 0.f);
-    for (size_t b = 0; b < nk; b++) {
-        const int nb = t->blocks[b];
-        for (int ks = 0; ks < KS; ks++)
-            for (int lane = 0; lane < 64; lane++) {
-                const int i = 1 + 2 * ks + (lane >> 5), k = 32 * nb + (lane & 31);
-                if (k >= bins) continue;
-                float *const d = &t->basis[((b * KS + ks) * 64 + lane) * 2];
-                d[0] = i == N / 2 ? 0.5f * t->wc[(size_t)i * bins + k] : t->wc[(size_t)i * bins + k]; // u = 2 x at the middle tap
-                d[1] = i == N / 2 ? 0.f : t->ws[(size_t)i * bins + k];                                  // v = 0 there
-            }
-        for (int mm = 0; mm < 4; mm++)
-            for (int r = 0; r < 16; r++)
-                for (int lane = 0; lane < 64; lane++) {
-                    const int j = 32 * mm + (lane & 31), k = 32 * nb + 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3);
-                    if (j >= n_mels || k >= bins) continue;
-                    const float w = t->bank[(size_t)j * bins + k];
-                    t->fb[((b * 4 + mm) * 16 + r) * 64 + lane] = w;
-                    if (w != 0.f) t->mask[b] |= (u8)(1u << mm);
-                }
-    }
+    t->basis = feat_pack_basis(t->wc, t->ws, N, t->blocks);
+    t->fb = feat_pack_fb(t->bank, bins, n_mels, t->blocks, 4, [&](int b, int mm) { t->mask[b] |= (u8)(1u << mm); });
     return t;
 }
 
@@ -312,48 +291,28 @@ static size_t spec_lds_bytes(const opusgpu_spec_params &p, int T) {
     return ((window > store ? window : store) + 15) / 16 * 16;
 }
 
-// The kernel over n tracks: checks the spans, builds the tile table, uploads it with the spans and the tables, launches on `s` and
-// waits; every device buffer of the call is freed on every way out.
-template <class Fail>
+// k_tracks_melspec over n tracks (og_tracks_mel.hpp: tracks_feature_run, which also says why the frames' bound differs).
 static int tracks_melspec_run(int device, hipStream_t s, int n_tracks, const opusgpu_mel_span *spans, const void *d_in,
-                              const opusgpu_spec_params *params, void *d_out, Fail hip_failed) {
-    if (!spec_params_ok(params) || n_tracks < 0 || (n_tracks && !spans)) return OPUSGPU_BAD_ARG;
+                              const opusgpu_spec_params *params, void *d_out, const TrackFail &hip_failed) {
+    if (!spec_params_ok(params)) return OPUSGPU_BAD_ARG;
     const int T = spec_tile(*params);
-    std::vector<MelTile> tiles;
-    for (int t = 0; t < n_tracks; t++) {
-        const opusgpu_mel_span &sp = spans[t];
-        if (sp.in_offset < 0 || sp.in_offset % 8 || sp.in_samples < 0 || sp.out_offset < 0 || sp.out_offset % 64 || sp.reserved)
-            return OPUSGPU_BAD_ARG;
-        const int64_t F = spec_frames(*params, sp.in_samples);
-        if (sp.plane < F || sp.plane % 64 || !std::isfinite(sp.scale)) return OPUSGPU_BAD_ARG;
-        if (F > 0x7fffffff - T || (F + T - 1) / T + (int64_t)tiles.size() > 0x7fffffff) return OPUSGPU_BAD_ARG;
-        for (int64_t f = 0; f < F; f += T) tiles.push_back(MelTile{t, (i32)f});
-    }
-    if (tiles.empty()) return OPUSGPU_OK;
-    if (!d_in || !d_out || ((uintptr_t)d_in & 15) || ((uintptr_t)d_out & 127)) return OPUSGPU_BAD_ARG;
-    const SpecTables &tab = spec_tables(*params);
-    MsArgs a{};
-    a.n_fft = params->n_fft, a.hop = params->hop, a.n_mels = params->n_mels, a.n_blocks = (i32)tab.blocks.size();
-    a.power = params->power, a.log = params->log, a.whisper_frames = params->frames == OPUSGPU_SPEC_FRAMES_WHISPER;
-    a.frames_major = params->layout == OPUSGPU_MEL_FRAMES_MAJOR, a.floor = params->floor;
-    std::copy(std::begin(tab.mask), std::end(tab.mask), a.mask);
-#define MS_CHK(call)                                                              \
-    do {                                                                          \
-        const hipError_t e_ = (call);                                             \
-        if (e_ != hipSuccess) return hip_failed(OPUSGPU_ERR_HIP, #call, e_);      \
-    } while (0)
-    MS_CHK(hipSetDevice(device));
-    RsDevBuf d_spans, d_tiles, d_basis, d_fb;
-    MS_CHK(d_spans.upload(spans, (size_t)n_tracks * sizeof(MelSpan)));
-    MS_CHK(d_tiles.upload(tiles.data(), tiles.size() * sizeof(MelTile)));
-    MS_CHK(d_basis.upload(tab.basis.data(), tab.basis.size() * sizeof(float)));
-    MS_CHK(d_fb.upload(tab.fb.data(), tab.fb.size() * sizeof(float)));
-    hipLaunchKernelGGL(k_tracks_melspec, dim3((unsigned)tiles.size()), dim3(2 * T), spec_lds_bytes(*params, T), s, (const MelTile *)d_tiles.p, (const MelSpan *)d_spans.p,
-                       (const i16 *)d_in, (const float2 *)d_basis.p, (const float *)d_fb.p, a, (float *)d_out);
-    MS_CHK(hipGetLastError());
-    MS_CHK(hipStreamSynchronize(s));
-#undef MS_CHK
-    return OPUSGPU_OK;
+    const SpecTables *tab = nullptr;
+    return tracks_feature_run(
+        device, s, n_tracks, spans, d_in, d_out, T, 0x7fffffff - T, [&](int64_t n) { return spec_frames(*params, n); },
+        [&] {
+            tab = &spec_tables(*params);
+            return FeatTables{&tab->basis, &tab->fb};
+        },
+        [&](unsigned n_tiles, const MelTile *d_tiles, const MelSpan *d_spans, const float2 *d_basis, const float *d_fb) {
+            MsArgs a{};
+            a.n_fft = params->n_fft, a.hop = params->hop, a.n_mels = params->n_mels, a.n_blocks = (i32)tab->blocks.size();
+            a.power = params->power, a.log = params->log, a.whisper_frames = params->frames == OPUSGPU_SPEC_FRAMES_WHISPER;
+            a.frames_major = params->layout == OPUSGPU_MEL_FRAMES_MAJOR, a.floor = params->floor;
+            std::copy(std::begin(tab->mask), std::end(tab->mask), a.mask);
+            hipLaunchKernelGGL(k_tracks_melspec, dim3(n_tiles), dim3(2 * T), spec_lds_bytes(*params, T), s, d_tiles, d_spans, (const i16 *)d_in,
+                               d_basis, d_fb, a, (float *)d_out);
+        },
+        hip_failed);
 }
 
 static int64_t spec_plane(const opusgpu_spec_params &p, int64_t planned_48k, int up, int down) {
@@ -361,61 +320,22 @@ static int64_t spec_plane(const opusgpu_spec_params &p, int64_t planned_48k, int
 }
 static bool spec_ratio_ok(int up, int down) { return up >= 1 && up <= down && down <= 48000; }
 
-// What the whole-file calls refuse before any device work -> the track's up / down of 48 kHz (1 / D for a rate), or false.
-static bool files_melspec_args(const og_batch &b, int rate, int &up, int &down, int mono, const opusgpu_mix_matrix *mix,
-                               const opusgpu_spec_params *params, const float *scale, const void *d_out) {
-    if (!spec_params_ok(params) || ((uintptr_t)d_out & 127)) return false;
-    if (mix ? mono || mix->out_channels != 1 : !mono) return false;
-    if (rate) {
-        if (up || down) return false;
-        const int D = rs_args_factor(b.channels, rate, mono, OPUSGPU_TRACKS_S16, mix);
-        if (!D) return false;
-        up = 1, down = D;
-    } else {
-        if (!rr_args_taps(b.channels, up, down, mono, OPUSGPU_TRACKS_S16, mix)) return false;
-        if (48000LL * up % down) return false; // the track's rate is no integer: no sample_rate names it
-    }
-    if ((int64_t)params->sample_rate * down != 48000LL * up) return false;
-    return rs_scale_ok(OPUSGPU_TRACKS_F32, scale, b.n_files);
-}
-
-// Both whole-file calls: files_resampled_run or files_ratio_run (with the caller's decoder) into a scratch buffer of int16 mono
-// tracks at the spectrogram's rate, on that call's grid -- the 48 kHz scratch is theirs and is gone when they return --, then
-// k_tracks_melspec from there into d_out.  The caller's arrays are written last.
-template <class Decode, class Fail>
-static int files_melspec_run(const og_batch &b, int device, hipStream_t s, int rate, int up, int down, int mono, const opusgpu_mix_matrix *mix,
+// opusgpu_files_decode_melspec and its multistream twin (og_ms_tracks.hpp): files_feature_run at the record's rate.
+static int files_melspec_run(const FilesOwner &own, int rate, int up, int down, int mono, const opusgpu_mix_matrix *mix,
                              const opusgpu_spec_params *params, const float *scale, void *d_out, int64_t *feat_offsets, int64_t *frames_out,
-                             int64_t *track_lengths_out, int32_t *status_out, Decode decode, Fail hip_failed) {
-    if (!files_melspec_args(b, rate, up, down, mono, mix, params, scale, d_out)) return OPUSGPU_BAD_ARG;
-    const size_t n = (size_t)b.n_files;
-    std::vector<int64_t> planned(n), offs(n, 0), len(n, 0), lengths(n, 0), feat(n, 0);
-    std::vector<int32_t> status(2 * n, 0);
-    for (size_t i = 0; i < n; i++) planned[i] = b.info[i].track_samples;
-    const int64_t total = rate ? opusgpu_resample_layout((int)n, planned.data(), rate, nullptr)
-                               : opusgpu_resample_ratio_layout((int)n, planned.data(), up, down, nullptr);
-    if (total < 0 || opusgpu_spec_layout((int)n, planned.data(), up, down, params, feat.data()) < 0) return OPUSGPU_BAD_ARG;
-    RsDevBuf y; // the int16 mono tracks at the spectrogram's rate, for the length of this call
-    if (!b.segs.empty()) {
-        hipError_t e = hipSetDevice(device);
-        if (e == hipSuccess) e = y.alloc((size_t)total * 2 + 128);
-        if (e != hipSuccess) return hip_failed(OPUSGPU_ALLOC_FAIL, "hipMalloc(spectrogram scratch)", e);
-    }
-    const int rc = rate ? files_resampled_run(b, device, s, rate, mono, OPUSGPU_TRACKS_S16, nullptr, y.p, offs.data(), len.data(), lengths.data(),
-                                              status.data(), decode, hip_failed, mix)
-                        : files_ratio_run(b, device, s, up, down, mono, mix, OPUSGPU_TRACKS_S16, nullptr, y.p, offs.data(), len.data(),
-                                          lengths.data(), status.data(), decode, hip_failed);
-    if (rc) return rc;
-    std::vector<opusgpu_mel_span> spans(n);
-    for (size_t i = 0; i < n; i++)
-        spans[i] = opusgpu_mel_span{offs[i], len[i], feat[i], spec_plane(*params, planned[i], up, down), scale ? scale[i] : 1.0f / 32768, 0};
-    if (int rc2 = tracks_melspec_run(device, s, (int)n, spans.data(), y.p, params, d_out, hip_failed)) return rc2;
-    for (size_t i = 0; i < n; i++) {
-        if (feat_offsets) feat_offsets[i] = feat[i];
-        if (frames_out) frames_out[i] = spec_frames(*params, len[i]);
-        if (track_lengths_out) track_lengths_out[i] = lengths[i];
-    }
-    if (status_out) std::copy(status.begin(), status.end(), status_out);
-    return OPUSGPU_OK;
+                             int64_t *track_lengths_out, int32_t *status_out) {
+    FeatFlow flow;
+    flow.sample_rate = spec_params_ok(params) ? (int)params->sample_rate : 0;
+    flow.scratch_failed = "hipMalloc(spectrogram scratch)";
+    flow.plane = [=](int64_t planned, int u, int d) { return spec_plane(*params, planned, u, d); };
+    flow.frames = [=](int64_t len) { return spec_frames(*params, len); };
+    flow.layout = [=](int n, const int64_t *planned, int u, int d, int64_t *feat) {
+        return opusgpu_spec_layout(n, planned, u, d, params, feat);
+    };
+    flow.run = [&](int n, const opusgpu_mel_span *spans, const void *d_in) {
+        return tracks_melspec_run(own.device, own.stream, n, spans, d_in, params, d_out, own.hip_failed);
+    };
+    return files_feature_run(own, rate, up, down, mono, mix, scale, d_out, feat_offsets, frames_out, track_lengths_out, status_out, flow);
 }
 
 extern "C" {
@@ -450,19 +370,15 @@ int opusgpu_tracks_melspec_device(opusgpu_ctx *ctx, int n_tracks, const opusgpu_
                                   const opusgpu_spec_params *p, void *d_out, void *hip_stream) {
     if (!ctx) return OPUSGPU_BAD_ARG;
     return tracks_melspec_run(ctx->device, hip_stream ? (hipStream_t)hip_stream : ctx->stream, n_tracks, spans, d_in_mono, p, d_out,
-                              [&](int code, const char *what, hipError_t e) { return fail(ctx, code, what, e); });
+                              track_fail(ctx));
 }
 
 int opusgpu_files_decode_melspec(opusgpu_ctx *ctx, const opusgpu_file_batch *batch, int rate, int up, int down, int mono,
                                  const opusgpu_mix_matrix *mix, const opusgpu_spec_params *p, const float *scale, void *d_out,
                                  int64_t *feat_offsets, int64_t *frames_out, int64_t *track_lengths_out, int32_t *status_out) {
     if (!ctx || !batch) return OPUSGPU_BAD_ARG;
-    return files_melspec_run(
-        *batch, ctx->device, ctx->stream, rate, up, down, mono, mix, p, scale, d_out, feat_offsets, frames_out, track_lengths_out, status_out,
-        [&](void *d_s16, int64_t *lengths, int32_t *status) {
-            return files_decode_run(ctx, batch, OPUSGPU_TRACKS_S16, nullptr, d_s16, lengths, status);
-        },
-        [&](int code, const char *what, hipError_t e) { return fail(ctx, code, what, e); });
+    return files_melspec_run(files_owner(ctx, batch), rate, up, down, mono, mix, p, scale, d_out, feat_offsets, frames_out, track_lengths_out,
+                             status_out);
 }
 
 } // extern "C"

@@ -368,19 +368,6 @@ static bool rs_scale_ok(int format, const float *scale, int n) {
     return true;
 }
 
-// A device buffer for the length of one call: freed on every way out.
-struct RsDevBuf {
-    void *p = nullptr;
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes + 16); }
-    hipError_t upload(const void *src, size_t bytes) {
-        const hipError_t e = alloc(bytes);
-        return e != hipSuccess || !bytes ? e : hipMemcpy(p, src, bytes, hipMemcpyHostToDevice);
-    }
-    ~RsDevBuf() {
-        if (p) (void)hipFree(p);
-    }
-};
-
 // A tile's outputs per channel, as a shift: 1,024 outputs of one channel .. 256 of eight, four per lane of k_tracks_resample.
 static int rs_tile_shift(int CO) { return CO == 1 ? 10 : CO == 2 ? 9 : 8; }
 // The spans held against the rules of opusgpu_resample_span for tracks of ceil(in_samples * up / down) outputs (TRACK RATES: up 1,
@@ -402,10 +389,9 @@ static bool rs_tiles(int n_tracks, const opusgpu_resample_span *spans, int up, i
 }
 
 // The kernel over n tracks: checks the spans, builds the tile table, uploads both, launches on `s` and waits.
-// hip_failed(code, what, e) keeps the message of the object the call belongs to and returns `code`.
-template <class Fail>
 static int tracks_resample_run(int device, hipStream_t s, int n_tracks, const opusgpu_resample_span *spans, const void *d_in, int channels,
-                               int rate, int mono, int format, void *d_out, Fail hip_failed, const opusgpu_mix_matrix *mix = nullptr) {
+                               int rate, int mono, int format, void *d_out, const TrackFail &hip_failed,
+                               const opusgpu_mix_matrix *mix = nullptr) {
     const int D = rs_args_factor(channels, rate, mono, format, mix);
     if (!D || n_tracks < 0 || (n_tracks && !spans)) return OPUSGPU_BAD_ARG;
     const int CO = mix ? mix->out_channels : mono ? 1 : channels;
@@ -415,15 +401,10 @@ static int tracks_resample_run(int device, hipStream_t s, int n_tracks, const op
     const int64_t tile = (int64_t)1 << tile_shift;
     if (tiles.empty()) return OPUSGPU_OK;
     if (!d_in || !d_out || ((uintptr_t)d_in & 15) || ((uintptr_t)d_out & 127)) return OPUSGPU_BAD_ARG;
-#define RS_CHK(call)                                                              \
-    do {                                                                          \
-        const hipError_t e_ = (call);                                             \
-        if (e_ != hipSuccess) return hip_failed(OPUSGPU_ERR_HIP, #call, e_);      \
-    } while (0)
-    RS_CHK(hipSetDevice(device));
+    TRK_CHK(hipSetDevice(device));
     RsDevBuf d_spans, d_tiles;
-    RS_CHK(d_spans.upload(spans, (size_t)n_tracks * sizeof(ResampleSpan)));
-    RS_CHK(d_tiles.upload(tiles.data(), tiles.size() * sizeof(ResampleTile)));
+    TRK_CHK(d_spans.upload(spans, (size_t)n_tracks * sizeof(ResampleSpan)));
+    TRK_CHK(d_tiles.upload(tiles.data(), tiles.size() * sizeof(ResampleTile)));
     const size_t lds = ((size_t)CO * D * (tile + RS_PLANE_PAD) + (size_t)CO * tile) * 2;
     auto go = [&](auto kern) {
         hipLaunchKernelGGL(kern, dim3((unsigned)tiles.size()), dim3(256), lds, s, (const ResampleTile *)d_tiles.p, (const ResampleSpan *)d_spans.p,
@@ -446,9 +427,8 @@ static int tracks_resample_run(int device, hipStream_t s, int n_tracks, const op
         case -4: go_mix(k_tracks_resample_mix<4>); break;
         default: go_mix(k_tracks_resample_mix<6>); break;
     }
-    RS_CHK(hipGetLastError());
-    RS_CHK(hipStreamSynchronize(s));
-#undef RS_CHK
+    TRK_CHK(hipGetLastError());
+    TRK_CHK(hipStreamSynchronize(s));
     return OPUSGPU_OK;
 }
 
@@ -468,12 +448,13 @@ static void rs_batch_spans(const og_batch &b, int up, int down, const int64_t *f
     }
 }
 
-// What every whole-file call that ends in a resampling kernel does around its decoder, its arguments checked by the caller:
-// `decode(d_s16, lengths, status)` runs the batch into the scratch S16 tracks, `run(n, spans, d_s16)` the kernel that makes tracks
-// at up / down of their rate from them.
-template <class Decode, class Run, class Fail>
-static int files_resampled_to(const og_batch &b, int device, int up, int down, int format, const float *scale, int64_t *out_offsets,
-                              int64_t *out_lengths, int64_t *track_lengths_out, int32_t *status_out, Decode decode, Run run, Fail hip_failed) {
+// What every whole-file call that ends in a resampling kernel does around its owner's decoder, its arguments checked by the caller:
+// own.decode runs the batch into the scratch S16 tracks, `run(n, spans, d_s16)` the kernel that makes tracks at up / down of their
+// rate from them.
+template <class Run>
+static int files_resampled_to(const FilesOwner &own, int up, int down, int format, const float *scale, int64_t *out_offsets,
+                              int64_t *out_lengths, int64_t *track_lengths_out, int32_t *status_out, Run run) {
+    const og_batch &b = own.b;
     if (!rs_scale_ok(format, scale, b.n_files)) return OPUSGPU_BAD_ARG;
     const size_t n = (size_t)b.n_files;
     std::vector<int64_t> lengths(n, 0), offsets;
@@ -481,11 +462,11 @@ static int files_resampled_to(const og_batch &b, int device, int up, int down, i
     std::vector<opusgpu_resample_span> spans;
     RsDevBuf s16; // the int16 tracks: track_samples x channels, for the length of this call
     if (!b.segs.empty()) {
-        hipError_t e = hipSetDevice(device);
+        hipError_t e = hipSetDevice(own.device);
         if (e == hipSuccess) e = s16.alloc((size_t)b.track_samples * b.channels * 2);
-        if (e != hipSuccess) return hip_failed(OPUSGPU_ALLOC_FAIL, "hipMalloc(resample scratch)", e);
+        if (e != hipSuccess) return own.hip_failed(OPUSGPU_ALLOC_FAIL, "hipMalloc(resample scratch)", e);
     }
-    if (int rc = decode(s16.p, lengths.data(), status.data())) return rc;
+    if (int rc = own.decode(s16.p, lengths.data(), status.data())) return rc;
     rs_batch_spans(b, up, down, lengths.data(), scale, offsets, spans);
     if (int rc = run(b.n_files, spans.data(), s16.p)) return rc;
     for (size_t i = 0; i < n; i++) {
@@ -498,18 +479,15 @@ static int files_resampled_to(const og_batch &b, int device, int up, int down, i
 }
 
 // files_resampled_to for the rates of TRACK RATES, behind a mono downmix or a channel mix.
-template <class Decode, class Fail>
-static int files_resampled_run(const og_batch &b, int device, hipStream_t s, int rate, int mono, int format, const float *scale, void *d_out,
-                               int64_t *out_offsets, int64_t *out_lengths, int64_t *track_lengths_out, int32_t *status_out, Decode decode,
-                               Fail hip_failed, const opusgpu_mix_matrix *mix = nullptr) {
-    const int D = rs_args_factor(b.channels, rate, mono, format, mix);
+static int files_resampled_run(const FilesOwner &own, int rate, int mono, const opusgpu_mix_matrix *mix, int format, const float *scale,
+                               void *d_out, int64_t *out_offsets, int64_t *out_lengths, int64_t *track_lengths_out, int32_t *status_out) {
+    const int D = rs_args_factor(own.b.channels, rate, mono, format, mix);
     if (!D) return OPUSGPU_BAD_ARG;
-    return files_resampled_to(
-        b, device, 1, D, format, scale, out_offsets, out_lengths, track_lengths_out, status_out, decode,
-        [&](int n, const opusgpu_resample_span *spans, const void *d_s16) {
-            return tracks_resample_run(device, s, n, spans, d_s16, b.channels, rate, mono, format, d_out, hip_failed, mix);
-        },
-        hip_failed);
+    return files_resampled_to(own, 1, D, format, scale, out_offsets, out_lengths, track_lengths_out, status_out,
+                              [&](int n, const opusgpu_resample_span *spans, const void *d_s16) {
+                                  return tracks_resample_run(own.device, own.stream, n, spans, d_s16, own.b.channels, rate, mono, format, d_out,
+                                                             own.hip_failed, mix);
+                              });
 }
 
 extern "C" {
@@ -543,19 +521,15 @@ int opusgpu_tracks_resample_device(opusgpu_ctx *ctx, int n_tracks, const opusgpu
                                    int mono, int format, void *d_out, void *hip_stream) {
     if (!ctx) return OPUSGPU_BAD_ARG;
     return tracks_resample_run(ctx->device, hip_stream ? (hipStream_t)hip_stream : ctx->stream, n_tracks, spans, d_in, channels, rate, mono,
-                               format, d_out, [&](int code, const char *what, hipError_t e) { return fail(ctx, code, what, e); });
+                               format, d_out, track_fail(ctx));
 }
 
 int opusgpu_files_decode_resampled(opusgpu_ctx *ctx, const opusgpu_file_batch *batch, int rate, int mono, int format, const float *scale,
                                    void *d_out, int64_t *out_offsets, int64_t *out_lengths, int64_t *track_lengths_out,
                                    int32_t *status_out) {
     if (!ctx || !batch) return OPUSGPU_BAD_ARG;
-    return files_resampled_run(
-        *batch, ctx->device, ctx->stream, rate, mono, format, scale, d_out, out_offsets, out_lengths, track_lengths_out, status_out,
-        [&](void *d_s16, int64_t *lengths, int32_t *status) {
-            return files_decode_run(ctx, batch, OPUSGPU_TRACKS_S16, nullptr, d_s16, lengths, status);
-        },
-        [&](int code, const char *what, hipError_t e) { return fail(ctx, code, what, e); });
+    return files_resampled_run(files_owner(ctx, batch), rate, mono, nullptr, format, scale, d_out, out_offsets, out_lengths, track_lengths_out,
+                               status_out);
 }
 
 int opusgpu_downmix_matrix(int channels, int out_channels, opusgpu_mix_matrix *m) {
@@ -571,19 +545,15 @@ int opusgpu_tracks_resample_mixed_device(opusgpu_ctx *ctx, int n_tracks, const o
                                          int rate, const opusgpu_mix_matrix *mix, int format, void *d_out, void *hip_stream) {
     if (!ctx || !mix) return OPUSGPU_BAD_ARG;
     return tracks_resample_run(ctx->device, hip_stream ? (hipStream_t)hip_stream : ctx->stream, n_tracks, spans, d_in, channels, rate, 0, format,
-                               d_out, [&](int code, const char *what, hipError_t e) { return fail(ctx, code, what, e); }, mix);
+                               d_out, track_fail(ctx), mix);
 }
 
 int opusgpu_files_decode_mixed(opusgpu_ctx *ctx, const opusgpu_file_batch *batch, int rate, const opusgpu_mix_matrix *mix, int format,
                                const float *scale, void *d_out, int64_t *out_offsets, int64_t *out_lengths, int64_t *track_lengths_out,
                                int32_t *status_out) {
     if (!ctx || !batch || !mix) return OPUSGPU_BAD_ARG;
-    return files_resampled_run(
-        *batch, ctx->device, ctx->stream, rate, 0, format, scale, d_out, out_offsets, out_lengths, track_lengths_out, status_out,
-        [&](void *d_s16, int64_t *lengths, int32_t *status) {
-            return files_decode_run(ctx, batch, OPUSGPU_TRACKS_S16, nullptr, d_s16, lengths, status);
-        },
-        [&](int code, const char *what, hipError_t e) { return fail(ctx, code, what, e); }, mix);
+    return files_resampled_run(files_owner(ctx, batch), rate, 0, mix, format, scale, d_out, out_offsets, out_lengths, track_lengths_out,
+                               status_out);
 }
 
 } // extern "C"

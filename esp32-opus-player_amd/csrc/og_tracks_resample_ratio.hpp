@@ -224,10 +224,9 @@ static RrPlan rr_plan(const RrTaps &t, int CO) {
 
 // The kernel over n tracks, as tracks_resample_run: checks the spans, builds the tile table, uploads it, the spans and the tap rows,
 // launches on `s` and waits.
-template <class Fail>
 static int tracks_resample_ratio_run(int device, hipStream_t s, int n_tracks, const opusgpu_resample_span *spans, const void *d_in,
                                      int channels, int up, int down, int mono, const opusgpu_mix_matrix *mix, int format, void *d_out,
-                                     Fail hip_failed) {
+                                     const TrackFail &hip_failed) {
     const RrTaps *const t = rr_args_taps(channels, up, down, mono, format, mix);
     if (!t || n_tracks < 0 || (n_tracks && !spans)) return OPUSGPU_BAD_ARG;
     const int CO = mix ? mix->out_channels : mono ? 1 : channels;
@@ -236,39 +235,30 @@ static int tracks_resample_ratio_run(int device, hipStream_t s, int n_tracks, co
     if (!rs_tiles(n_tracks, spans, up, down, pl.tile_shift, format, tiles)) return OPUSGPU_BAD_ARG;
     if (tiles.empty()) return OPUSGPU_OK;
     if (!d_in || !d_out || ((uintptr_t)d_in & 15) || ((uintptr_t)d_out & 127)) return OPUSGPU_BAD_ARG;
-#define RR_CHK(call)                                                              \
-    do {                                                                          \
-        const hipError_t e_ = (call);                                             \
-        if (e_ != hipSuccess) return hip_failed(OPUSGPU_ERR_HIP, #call, e_);      \
-    } while (0)
-    RR_CHK(hipSetDevice(device));
+    TRK_CHK(hipSetDevice(device));
     RsDevBuf d_spans, d_tiles, d_taps;
-    RR_CHK(d_spans.upload(spans, (size_t)n_tracks * sizeof(ResampleSpan)));
-    RR_CHK(d_tiles.upload(tiles.data(), tiles.size() * sizeof(ResampleTile)));
-    RR_CHK(d_taps.upload(t->rows.data(), t->rows.size() * sizeof(int16_t)));
+    TRK_CHK(d_spans.upload(spans, (size_t)n_tracks * sizeof(ResampleSpan)));
+    TRK_CHK(d_tiles.upload(tiles.data(), tiles.size() * sizeof(ResampleTile)));
+    TRK_CHK(d_taps.upload(t->rows.data(), t->rows.size() * sizeof(int16_t)));
     const RrArgs ra{up, down, t->taps_per_phase, t->groups, pl.plane, mix ? 1 : 0};
     const RsMixArgs mx = mix ? rs_mix_args(*mix) : RsMixArgs{};
     hipLaunchKernelGGL(k_tracks_resample_ratio, dim3((unsigned)tiles.size()), dim3(256), pl.lds, s, (const ResampleTile *)d_tiles.p,
                        (const ResampleSpan *)d_spans.p, (const i16 *)d_in, channels, mono ? 1 : 0, mx, ra, (const uint4 *)d_taps.p, format,
                        pl.tile_shift, d_out);
-    RR_CHK(hipGetLastError());
-    RR_CHK(hipStreamSynchronize(s));
-#undef RR_CHK
+    TRK_CHK(hipGetLastError());
+    TRK_CHK(hipStreamSynchronize(s));
     return OPUSGPU_OK;
 }
 
 // files_resampled_to for a ratio: what opusgpu_files_decode_ratio and opusgpu_ms_files_decode_ratio (og_ms_tracks.hpp) share.
-template <class Decode, class Fail>
-static int files_ratio_run(const og_batch &b, int device, hipStream_t s, int up, int down, int mono, const opusgpu_mix_matrix *mix, int format,
-                           const float *scale, void *d_out, int64_t *out_offsets, int64_t *out_lengths, int64_t *track_lengths_out,
-                           int32_t *status_out, Decode decode, Fail hip_failed) {
-    if (!rr_args_taps(b.channels, up, down, mono, format, mix)) return OPUSGPU_BAD_ARG;
-    return files_resampled_to(
-        b, device, up, down, format, scale, out_offsets, out_lengths, track_lengths_out, status_out, decode,
-        [&](int n, const opusgpu_resample_span *spans, const void *d_s16) {
-            return tracks_resample_ratio_run(device, s, n, spans, d_s16, b.channels, up, down, mono, mix, format, d_out, hip_failed);
-        },
-        hip_failed);
+static int files_ratio_run(const FilesOwner &own, int up, int down, int mono, const opusgpu_mix_matrix *mix, int format, const float *scale,
+                           void *d_out, int64_t *out_offsets, int64_t *out_lengths, int64_t *track_lengths_out, int32_t *status_out) {
+    if (!rr_args_taps(own.b.channels, up, down, mono, format, mix)) return OPUSGPU_BAD_ARG;
+    return files_resampled_to(own, up, down, format, scale, out_offsets, out_lengths, track_lengths_out, status_out,
+                              [&](int n, const opusgpu_resample_span *spans, const void *d_s16) {
+                                  return tracks_resample_ratio_run(own.device, own.stream, n, spans, d_s16, own.b.channels, up, down, mono, mix,
+                                                                   format, d_out, own.hip_failed);
+                              });
 }
 
 extern "C" {
@@ -297,19 +287,15 @@ int opusgpu_tracks_resample_ratio_device(opusgpu_ctx *ctx, int n_tracks, const o
                                          void *hip_stream) {
     if (!ctx) return OPUSGPU_BAD_ARG;
     return tracks_resample_ratio_run(ctx->device, hip_stream ? (hipStream_t)hip_stream : ctx->stream, n_tracks, spans, d_in, channels, up, down,
-                                     mono, mix, format, d_out, [&](int code, const char *what, hipError_t e) { return fail(ctx, code, what, e); });
+                                     mono, mix, format, d_out, track_fail(ctx));
 }
 
 int opusgpu_files_decode_ratio(opusgpu_ctx *ctx, const opusgpu_file_batch *batch, int up, int down, int mono, const opusgpu_mix_matrix *mix,
                                int format, const float *scale, void *d_out, int64_t *out_offsets, int64_t *out_lengths,
                                int64_t *track_lengths_out, int32_t *status_out) {
     if (!ctx || !batch) return OPUSGPU_BAD_ARG;
-    return files_ratio_run(
-        *batch, ctx->device, ctx->stream, up, down, mono, mix, format, scale, d_out, out_offsets, out_lengths, track_lengths_out, status_out,
-        [&](void *d_s16, int64_t *lengths, int32_t *status) {
-            return files_decode_run(ctx, batch, OPUSGPU_TRACKS_S16, nullptr, d_s16, lengths, status);
-        },
-        [&](int code, const char *what, hipError_t e) { return fail(ctx, code, what, e); });
+    return files_ratio_run(files_owner(ctx, batch), up, down, mono, mix, format, scale, d_out, out_offsets, out_lengths, track_lengths_out,
+                           status_out);
 }
 
 } // extern "C"
