@@ -217,7 +217,8 @@ OG_DEV u32 pvq_row_sel(int r, u32 v2, u32 v3) {
 // form of the expression is two masks and a full 32-bit multiply), and the bare v_sqrt_f32 -- one ulp, where the precise sqrtf is a
 // dozen instructions of rounding fix-ups: its argument is below 2^15 here (tq <= 176^2), where neighbouring integers' roots are
 // 0.0028 apart at least and a float's ulp is 2^-16, so the truncated result is the root's floor, or one less when the root is an
-// integer -- which the caller's upward correction covers.
+// integer -- which the caller's upward correction covers.  (tests/test_gpu_device_forms.py runs both on the GPU over their whole
+// domain, h < 2^11 and tq <= 176^2: on an MI355X the root came out as the floor everywhere)
 #ifdef OG_HOST_EMUL
 OG_DEV u32 pvq_u3(u32 h) { return 2u * h * (h - 1u) + 1u; }
 OG_DEV int pvq_isqrt_near(u32 tq) { return (int)__builtin_sqrtf((float)tq); }
@@ -234,7 +235,8 @@ OG_DEV int pvq_isqrt_near(u32 tq) { return (int)__builtin_amdgcn_sqrtf((float)tq
 // (j * M) >> 16 for M = floor(65536 / blen) + 1 -- or that plus one -- whenever j < 176 and blen <= 176 (the error j (M - 65536 /
 // blen) / 65536 stays below 1 / blen; tests/test_pvq_walk_sites.py walks every j, blen and both M).  On the GPU M comes from the
 // reciprocal instruction: one ulp, and 65536 / blen is an integer (exactly represented, blen a power of two) or at least
-// 1 / blen away from one, which is 80 times the error of the product -- so the truncation is the floor.
+// 1 / blen away from one, which is 80 times the error of the product -- so the truncation is the floor.  (Which M the GPU takes,
+// and pvq_block_of with it for every j and blen: tests/test_gpu_device_forms.py; the smaller one everywhere on an MI355X.)
 #ifdef OG_HOST_EMUL
 OG_DEV u32 pvq_block_mul(int blen) { return blen > 0 ? 65536u / (u32)blen + 1u : 0u; }
 OG_DEV int pvq_block_of(int j, u32 mul) { return (int)(((u32)j * mul) >> 16); }

@@ -118,6 +118,15 @@ extern long long og_stats[64];
 #define OG_STAT(id, n) ((void)0)
 #endif
 
+#ifndef OG_HOST_EMUL
+// The track resamplers' multiply-accumulate (og_tracks_resample.hpp, og_tracks_resample_ratio.hpp; no host emulation runs them):
+// acc + x.lo * taps.lo + x.hi * taps.hi in wrapping 32-bit arithmetic (v_dot2_i32_i16, no clamp).
+typedef short og_i16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ i32 rs_dot2(u32 x, u32 taps, i32 acc) {
+    return __builtin_amdgcn_sdot2(__builtin_bit_cast(og_i16x2, x), __builtin_bit_cast(og_i16x2, taps), acc, false);
+}
+#endif
+
 #define OG_MIN(a, b) ((a) < (b) ? (a) : (b))
 #define OG_MAX(a, b) ((a) > (b) ? (a) : (b))
 

@@ -56,10 +56,7 @@ __device__ __forceinline__ const u32 *rs_pairs() {
     if constexpr (D == 6) return og_rs_pairs_6;
     return nullptr;
 }
-typedef short og_i16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ i32 rs_dot2(u32 x, u32 taps, i32 acc) { // acc + x.lo * taps.lo + x.hi * taps.hi (v_dot2_i32_i16)
-    return __builtin_amdgcn_sdot2(__builtin_bit_cast(og_i16x2, x), __builtin_bit_cast(og_i16x2, taps), acc, false);
-}
+// (rs_dot2, the multiply-accumulate of step 2: og_common.hpp, where tests/gpu_kat can reach it without this file's host side)
 
 // Step 2 of k_tracks_resample<D> and k_tracks_resample_mix<D>: the planes of CO channels -> the tile's results in `yo`.
 template <int D>
