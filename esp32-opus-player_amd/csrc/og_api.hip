@@ -388,7 +388,8 @@ extern "C" void og_launch_decode_rfc(hipStream_t s, const void *descs, const voi
 __global__ void __launch_bounds__(64, OG_RECON_WAVES) k_celt_recon(const FrameDesc *__restrict__ descs, StreamState *st,
                                                                       const ParseRec *recs, ReconOut *rout, int n,
                                                                       int n_streams, int hybrid, int rest_only) {
-    // rest_only (k_celt_recon_fb ran before): what is left -- records that overflowed -- is almost nothing, so a workgroup
+    // rest_only (k_celt_recon_fb ran before): what is left -- frames without leaves (RF_BAD_CELT, RF_SKIP); a record cannot overflow,
+    // tests/test_kernel_paths.py -- is almost nothing, so a workgroup
     // looks at 64 slots, one per lane, and reconstructs the few left to it one after the other (see k_decode_step)
     unsigned long long todo = 1ull;
     int base = (int)blockIdx.x;

@@ -63,6 +63,21 @@ int emu_decode_frame(void *stv, const uint8_t *payload, int len, int mode, int b
     for (int c = 0; c < st->channels; c++) og::celt_post(st, &rec, ret, c, pcm, h ? h->pcm : nullptr, ch);
     return ret;
 }
+// A CELT-only frame the way a pipelined CELT window reconstructs it (og_step.hpp): the kernel of 20 ms frames first, in its role
+// RECON_FAST_ONLY; what it leaves (RECON_NOT_MINE: recon_begin found the record not fast) goes to the general kernel in its
+// role RECON_REST_ONLY.  (k_celt_recon's lanes pick those frames with the conditions of recon_fast_eligible written out,
+// og_api.hip; tests/test_kernel_paths.py holds the two texts together.)  Returns -1000 for any other mode.
+int emu_decode_frame_roles(void *stv, const uint8_t *payload, int len, int mode, int bw, int ch, int16_t *pcm) {
+    (void)bw;
+    og::StreamState *st = (og::StreamState *)stv;
+    if (mode != og::MODE_CELT) return -1000;
+    og::parse_tables_load();
+    og::celt_parse_lane(st, payload, len, ch, &rec, nullptr);
+    int ret = og::celt_recon_wave(st, &rec, mode, ch, og::RECON_FAST_ONLY);
+    if (ret == og::RECON_NOT_MINE) ret = og::celt_recon_wave(st, &rec, mode, ch, og::RECON_REST_ONLY);
+    for (int c = 0; c < st->channels; c++) og::celt_post(st, &rec, ret, c, pcm, nullptr, ch);
+    return ret;
+}
 // A SILK-only / hybrid frame the way pipelined SILK-only steps decode it: the entropy half takes the past from `shadow` (128 bytes,
 // og::SilkShadow) when that carries `epoch`, from the state otherwise, and leaves the next frame's past there.
 int emu_decode_frame_shadowed(void *stv, void *shadow, unsigned epoch, const uint8_t *payload, int len, int mode, int bw, int ch, int16_t *pcm) {

@@ -194,19 +194,20 @@ TAPSET_ICDF = [2, 1, 0]
 SMALL_ENERGY_ICDF = [2, 1, 0]
 
 
-def celt_frame(nbytes, channels=2, *, silence=0, postfilter=None, transient=0, intra=0, coarse=None, fill=None):
-    """A CELT frame of `nbytes` bytes (payload only: prepend the TOC) whose leading symbols are pinned:
+def celt_frame(nbytes, channels=2, *, silence=0, postfilter=None, transient=0, intra=0, coarse=None, fill=None, LM=3):
+    """A CELT frame of `nbytes` bytes (payload only: prepend the TOC) whose leading symbols are pinned (LM 3: a 20 ms frame, the only
+    size reference mode decodes; LM 0..2: the 2.5 / 5 / 10 ms frames of RFC mode, whose TOC names that duration):
     the silence flag; postfilter = None (flag 0) or (octave, period_low_bits, gain_index, tapset); transient; intra;
     coarse = list over bands from 0 of the Laplace value qi, or of one qi per channel (bands not listed are left to the
     fill, as is everything after the coarse energies).
     The writer follows the decoder's budget checks; a symbol the decoder would not read at that point raises CraftError."""
     e = Encoder()
-    celt_symbols(e, nbytes * 8, channels, silence, postfilter, transient, intra, coarse)
+    celt_symbols(e, nbytes * 8, channels, silence, postfilter, transient, intra, coarse, LM)
     return e.done(nbytes, fill)
 
 
-def celt_symbols(e, total, C, silence=0, postfilter=None, transient=0, intra=0, coarse=None):
-    """the symbols of celt_frame on encoder e (a 20 ms CELT-only frame: LM 3, bands from 0)"""
+def celt_symbols(e, total, C, silence=0, postfilter=None, transient=0, intra=0, coarse=None, LM=3):
+    """the symbols of celt_frame on encoder e (a CELT-only frame of 120 << LM samples, bands from 0)"""
     NB = 21
     if e.tell() >= total:
         return
@@ -229,15 +230,15 @@ def celt_symbols(e, total, C, silence=0, postfilter=None, transient=0, intra=0, 
                 raise CraftError("no bits left for the tapset")
     elif postfilter:
         raise CraftError("no post-filter symbols here")
-    if e.tell() + 3 <= total:
+    if LM > 0 and e.tell() + 3 <= total:
         e.bit_logp(transient, 3)
     elif transient:
-        raise CraftError("no bits left for the transient flag")
+        raise CraftError("no transient flag here (LM 0, or no bits left)")
     if e.tell() + 3 <= total:
         e.bit_logp(intra, 3)
     elif intra:
         raise CraftError("no bits left for the intra flag")
-    pm = rom("rom_eprob")[(3 * 2 + intra) * 42:][:42]  # (LM 3)
+    pm = rom("rom_eprob")[(LM * 2 + intra) * 42:][:42]
     for i in range(min(NB, len(coarse or ()))):
         for c in range(C):
             qi = coarse[i]

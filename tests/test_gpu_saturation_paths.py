@@ -28,6 +28,7 @@ import zlib
 import numpy as np
 import pytest
 
+import rfc_common as rc
 import test_gpu_rare_paths as rp
 
 pytestmark = pytest.mark.gpu
@@ -135,6 +136,7 @@ def test_saturating_streams_and_their_losses_in_rfc_mode(pkg, oracle, gpu_ctx, c
         d.init()
         d.set_rfc(True)
         decs.append(d)
+    last = [None] * N  # (rfc_common.oracle_step: what a stream's lost packet is concealed like)
     ctx.set_mode(True)
     try:
         ctx.streams_alloc(N, channels)
@@ -142,7 +144,7 @@ def test_saturating_streams_and_their_losses_in_rfc_mode(pkg, oracle, gpu_ctx, c
             pcm, res = ctx.decode_packets(np.arange(N), pk[f], frame_capacity=6)
             rng = rp._final_ranges(ctx)
             for s in range(N):
-                ref, r = decs[s].decode(pk[f][s]) if pk[f][s] else decs[s].conceal(960)
+                ref, r, domain, last[s] = rc.oracle_step(oracle, decs[s], pk[f][s], last[s], channels)
                 want_rng = oracle.lib.oc_decoder_final_range(decs[s].h)
                 if owner[s] >= 0:
                     exp = ents[owner[s]]["expect"][f]
@@ -150,6 +152,7 @@ def test_saturating_streams_and_their_losses_in_rfc_mode(pkg, oracle, gpu_ctx, c
                 where = (f, s, "lost" if not pk[f][s] else hex(pk[f][s][0]), "corpus entry %d" % ids[owner[s]] if owner[s] >= 0 else "neighbour")
                 assert res[s] == r == 960, ("return code", where, int(res[s]), r)
                 assert int(rng[s]) == want_rng, ("final range", where)
+                assert rc.same_step(pcm[s], res[s], ref, r, domain, channels) is None, ("over the entries the packet defines", where)
                 got, want = np.asarray(pcm[s])[:960].reshape(-1), ref[:960].reshape(-1)
                 bad = np.argwhere(got != want)
                 assert not len(bad), ("PCM", where, "first differing entries", bad[:4].reshape(-1).tolist())

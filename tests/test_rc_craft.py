@@ -170,6 +170,36 @@ def test_celt_frame_pins_what_it_says(oracle, intra):
     assert (h[0], h[1], h[7], h[8]) == (0, 0, 0, 0)
 
 
+@pytest.mark.parametrize("LM", [0, 1, 2])
+def test_celt_frame_of_a_shorter_duration_pins_what_it_says_in_rfc_mode(oracle, LM):
+    """celt_frame(LM=...) writes the 2.5 / 5 / 10 ms frames RFC mode decodes at their own duration (tests/golden/make_kernel_paths.py): the
+    frame comes back with that LM, the pinned flags and post-filter, and the coarse energies of LM's own probability model"""
+    import numpy as np
+    coarse = [[2, 2]] * 14 + [[1, 1]] * 7
+    noise = [(53 * i + 7) & 0xFF for i in range(300)]
+    transient = 1 if LM else 0
+    body = rc_craft.celt_frame(120, 2, postfilter=(2, 21, 4, 1), transient=transient, intra=1, coarse=coarse, fill=noise, LM=LM)
+    d = oracle.decoder(2)
+    d.init()
+    d.set_rfc(True)
+    oracle.lib.oc_taps_enable.argtypes = [C.c_void_p]
+    oracle.lib.oc_taps_copy.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    assert oracle.lib.oc_taps_enable(d.h)
+    _, r = d.decode(bytes([0xE4 | LM << 3]) + body)  # CELT fullband, stereo, 2.5 << LM ms
+    assert r == 120 << LM
+    h, e = np.zeros(75, dtype=np.int32), np.zeros(42, dtype=np.int16)
+    assert oracle.lib.oc_taps_copy(d.h, 4, 0, h.ctypes.data) == h.nbytes and oracle.lib.oc_taps_copy(d.h, 1, 0, e.ctypes.data) == e.nbytes
+    assert (h[0], h[1], h[6]) == (transient, 0, LM)
+    assert (h[7], h[8], h[9]) == ((16 << 2) + 21 - 1, 3072 * 5, 1)
+    want = _coarse_on_fresh_state(coarse, 4915)  # (intra: the predictor does not depend on LM, the Laplace model does)
+    for c in range(2):
+        for i in range(21):
+            assert abs(int(e[c * 21 + i]) - want[c][i]) <= 768, (LM, c, i, int(e[c * 21 + i]), want[c][i])
+    if LM == 0:
+        with pytest.raises(rc_craft.CraftError):  # a 2.5 ms frame has no transient flag
+            rc_craft.celt_frame(120, 2, transient=1, LM=0)
+
+
 @pytest.mark.parametrize("fs, toc, stereo", [(8, 0x08, 0), (16, 0x48, 0), (12, 0x2C, 1)])
 def test_silk_frame_pins_what_it_says(oracle, fs, toc, stereo):
     import numpy as np
