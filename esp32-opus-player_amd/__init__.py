@@ -48,6 +48,8 @@ EXPORTS = [
     "opusgpu_ms_files_decode_ratio",
     "opusgpu_spec_basis", "opusgpu_spec_filterbank", "opusgpu_spec_layout", "opusgpu_tracks_melspec_device", "opusgpu_files_decode_melspec",
     "opusgpu_ms_files_decode_melspec",
+    "opusgpu_loudness_weights", "opusgpu_loudness_gain", "opusgpu_tracks_loudness_device", "opusgpu_set_loudness", "opusgpu_last_loudness",
+    "opusgpu_ms_set_loudness", "opusgpu_ms_last_loudness",
 ]
 
 
@@ -145,6 +147,11 @@ SPEC_SCALES = {"slaney": 0, "htk": 1}
 SPEC_NORMS = {"slaney": 0, None: 1, "none": 1}
 SPEC_LOGS = {None: 0, "none": 0, "log10": 1, "ln": 2}
 SPEC_FRAMES = {"torch": 0, "whisper": 1}
+# opusgpu_loudness_span / opusgpu_loudness / opusgpu_loudness_req and the request's modes (include/opusgpu.h, TRACK LOUDNESS)
+LOUDNESS_SPAN_DTYPE = np.dtype([("in_offset", "<i8"), ("in_samples", "<i8")])
+LOUDNESS_DTYPE = np.dtype([("lufs", "<f4"), ("peak", "<f4"), ("blocks", "<i4"), ("gated", "<i4")])
+LOUDNESS_REQ_DTYPE = np.dtype([("mode", "<i4"), ("target_lufs", "<f4"), ("peak_limit", "<f4"), ("n_weights", "<i4"), ("weights", "<f4", (8,))])
+LOUDNESS_OFF, LOUDNESS_MEASURE, LOUDNESS_NORMALIZE = 0, 1, 2
 OPUSGPU_BAD_ARG, OPUSGPU_UNIMPLEMENTED, OPUSGPU_CELT_BAD_ARG = -1, -5, -18
 RFC_FRAME = 2880
 
@@ -285,6 +292,14 @@ def load_lib():
     lib.opusgpu_tracks_melspec_device.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
     lib.opusgpu_files_decode_melspec.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.opusgpu_ms_files_decode_melspec.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.opusgpu_loudness_weights.argtypes = [C.c_int, vp]
+    lib.opusgpu_loudness_gain.argtypes = [vp, C.c_double, C.c_double]
+    lib.opusgpu_loudness_gain.restype = C.c_double
+    lib.opusgpu_tracks_loudness_device.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, vp, vp]
+    for name in ("opusgpu_set_loudness", "opusgpu_ms_set_loudness"):
+        getattr(lib, name).argtypes = [vp, vp]
+    for name in ("opusgpu_last_loudness", "opusgpu_ms_last_loudness"):
+        getattr(lib, name).argtypes = [vp, C.c_int, vp, vp]
     _lib = lib
     return lib
 
@@ -954,6 +969,54 @@ def track_spectrogram_args(batch, features, rate=None, resample=None, mono=False
     return rec, mrec, scale, offsets, planes, total, out, how
 
 
+def loudness_weights(channels):
+    """opusgpu_loudness_weights: the default BS.1770-4 channel weights of `channels` (1 - 8, Vorbis order) channels, float32."""
+    w = np.zeros(8, dtype=np.float32)
+    if load_lib().opusgpu_loudness_weights(int(channels), w.ctypes.data) != 0:
+        raise ValueError(f"there are no loudness weights for {channels!r} channels")
+    return w[:channels].copy()
+
+
+def loudness_gain(record, target_lufs, peak_limit=1.0):
+    """opusgpu_loudness_gain: the linear gain that takes a track with this LOUDNESS_DTYPE record to target_lufs, held to
+    peak * gain <= peak_limit when peak_limit > 0; 1 for a track without loudness (lufs -inf).  A double."""
+    rec = np.zeros(1, dtype=LOUDNESS_DTYPE)
+    rec[0] = record
+    return float(load_lib().opusgpu_loudness_gain(rec.ctypes.data, float(target_lufs), float(peak_limit)))
+
+
+def loudness_request(batch, loudness=None, peak_limit=1.0, channel_weights=None):
+    """What decode_files makes of its loudness=, peak_limit= and channel_weights= for a planned batch, before any device work: None
+    for loudness=None (today's calls), else the opusgpu_loudness_req record (a LOUDNESS_REQ_DTYPE array of one).  Raises ValueError
+    for a loudness that is neither "measure" nor a finite number, a peak_limit that is not finite, and weights that are not one
+    finite number >= 0 per channel of the batch (or given without loudness=)."""
+    import numbers
+    if loudness is None:
+        if channel_weights is not None:
+            raise ValueError("channel_weights needs loudness=")
+        return None
+    rec = np.zeros(1, dtype=LOUDNESS_REQ_DTYPE)
+    if isinstance(loudness, str):
+        if loudness != "measure":
+            raise ValueError(f"loudness must be None, 'measure' or a target in LUFS, not {loudness!r}")
+        rec["mode"] = LOUDNESS_MEASURE
+    else:
+        if not isinstance(loudness, numbers.Real) or isinstance(loudness, bool) or not np.isfinite(loudness):
+            raise ValueError(f"loudness must be None, 'measure' or a finite target in LUFS, not {loudness!r}")
+        if not isinstance(peak_limit, numbers.Real) or isinstance(peak_limit, bool) or not np.isfinite(peak_limit):
+            raise ValueError(f"peak_limit must be a finite number (<= 0: none), not {peak_limit!r}")
+        rec["mode"], rec["target_lufs"], rec["peak_limit"] = LOUDNESS_NORMALIZE, loudness, peak_limit
+    if channel_weights is not None:
+        w = np.asarray(channel_weights, dtype=np.float64)
+        if w.shape != (batch.channels,):
+            raise ValueError(f"channel_weights must have one entry per channel ({batch.channels}), not shape {w.shape}")
+        if not np.isfinite(w).all() or (w < 0).any():
+            raise ValueError("channel_weights must be finite and >= 0")
+        rec["n_weights"] = batch.channels
+        rec["weights"][0, :batch.channels] = w
+    return rec
+
+
 class FilesRequest(typing.NamedTuple):
     """What one decode_files call asks of the library, made by files_request before any decoder is touched."""
     entry: str        # the C entry point without its opusgpu_ / opusgpu_ms_ prefix
@@ -968,13 +1031,26 @@ class FilesRequest(typing.NamedTuple):
     total: int
     mix: object       # the matrix record or None
     params: object    # the features' record or None
+    loudness: object = None  # the loudness request's record (loudness_request) or None
 
 
 def files_request(batch, multistream=False, device=0, format=None, scale=None, out=None, rate=None, mono=False, mix=None, features=None,
-                  n_mels=80, feature_layout="bands", resample=None):
+                  n_mels=80, feature_layout="bands", resample=None, loudness=None, peak_limit=1.0, channel_weights=None):
     """The keywords of decode_files for a planned batch -> the FilesRequest that _run_files_request carries out.  Every refusal of
     decode_files is raised here, as ValueError, by the track_*_args helpers; nothing of a decoder is needed.  multistream: the batch
-    is an MsFileBatch, whose C calls take no `mono` and whose tracks have no mono downmix."""
+    is an MsFileBatch, whose C calls take no `mono` and whose tracks have no mono downmix.
+    loudness=None is exactly the request it always was.  Otherwise the request carries the loudness record; a target needs a float
+    format or features; and float tracks at 48 kHz without a mix, whose call (files_decode_as) never has an int16 track to measure,
+    go through files_decode_mixed with the identity matrix, which writes the same elements (include/opusgpu.h TRACK LOUDNESS)."""
+    lreq = loudness_request(batch, loudness, peak_limit, channel_weights)
+    if lreq is not None:
+        req = files_request(batch, multistream, device, format, scale, out, rate, mono, mix, features, n_mels, feature_layout, resample)
+        if req.entry == "files_decode_as":
+            identity = 16384 * np.eye(batch.channels, dtype=np.int16)
+            req = files_request(batch, multistream, device, format, scale, out, rate, mono, identity, features, n_mels, feature_layout, resample)
+        if int(lreq["mode"][0]) == LOUDNESS_NORMALIZE and req.kind != "features" and req.fmt == TRACKS_S16:
+            raise ValueError("a loudness target needs a float format or features: int16 tracks are not scaled")
+        return req._replace(loudness=lreq)
     if mix is not None and mono:
         raise ValueError("mix and mono=True exclude each other: the row {8192, 8192} is mono")
     allow_mono, mono_arg = not multistream, () if multistream else (1 if mono else 0,)
@@ -1017,7 +1093,9 @@ def _run_files_request(req, lib, prefix, handle, chk, batch, mem):
     dev_free); chk(code, what) raises.  -> (tracks or features, info).  Tracks are [samples, channels] (planar: transposed), features
     float32 [n_mels, F] or [F, n_mels].  info: FILE_INFO_DTYPE records plus `final_status` and `bad_packet`, `track_samples` the FINAL
     length at 48 kHz; resampled tracks have `out_samples` and `out_offset` more; features `feat_offset`, and their `frames` is F, the
-    track's feature frames (the plan's count of Opus frames is batch.info["frames"])."""
+    track's feature frames (the plan's count of Opus frames is batch.info["frames"]).  With a loudness request (req.loudness) the
+    request is set on the decoder for this call alone and cleared behind it, and info has `lufs`, `peak`, `loudness_blocks`,
+    `loudness_gated` and `gain` more."""
     name = prefix + req.entry
     n, ch, fmt = batch.n_files, req.channels, req.fmt
     offsets, counts, lengths = (np.zeros(n, dtype=np.int64) for _ in range(3))
@@ -1027,8 +1105,20 @@ def _run_files_request(req, lib, prefix, handle, chk, batch, mem):
         head += ([] if req.kind == "features" else [fmt]) + [None if req.scale is None else req.scale.ctypes.data]
     tail = [a.ctypes.data for a in ((lengths, status) if req.kind == "tracks" else (offsets, counts, lengths, status))]
 
+    loud = np.zeros(n, dtype=LOUDNESS_DTYPE)
+    gains = np.ones(n, dtype=np.float64)
+
     def run(d_out):
-        chk(getattr(lib, name)(handle, batch.h, *head, d_out, *tail), name)
+        if req.loudness is None:
+            chk(getattr(lib, name)(handle, batch.h, *head, d_out, *tail), name)
+            return
+        chk(getattr(lib, prefix + "set_loudness")(handle, req.loudness.ctypes.data), prefix + "set_loudness")
+        try:
+            chk(getattr(lib, name)(handle, batch.h, *head, d_out, *tail), name)
+            got = getattr(lib, prefix + "last_loudness")(handle, n, loud.ctypes.data, gains.ctypes.data)
+            assert got == n, (got, n)
+        finally:
+            getattr(lib, prefix + "set_loudness")(handle, None)
     if req.out is not None:
         import torch
         torch.cuda.current_stream(req.out.device).synchronize()  # whatever filled `out` has finished; the call itself waits for its own work
@@ -1045,7 +1135,12 @@ def _run_files_request(req, lib, prefix, handle, chk, batch, mem):
     # the result's own count and offset per file: the fields of `info` that hold them, and which of them are new
     count_field, offset_field, more = {"tracks": (None, None, []), "resampled": ("out_samples", "out_offset", ["out_samples", "out_offset"]),
                                        "features": ("frames", "feat_offset", ["feat_offset"])}[req.kind]
-    info = np.zeros(n, dtype=np.dtype(FILE_INFO_DTYPE.descr + [("final_status", "<i4"), ("bad_packet", "<i4")] + [(f, "<i8") for f in more]))
+    louder = [] if req.loudness is None else [("lufs", "<f4"), ("peak", "<f4"), ("loudness_blocks", "<i4"), ("loudness_gated", "<i4"), ("gain", "<f8")]
+    info = np.zeros(n, dtype=np.dtype(FILE_INFO_DTYPE.descr + [("final_status", "<i4"), ("bad_packet", "<i4")] + [(f, "<i8") for f in more] +
+                                      louder))
+    if louder:
+        info["lufs"], info["peak"], info["loudness_blocks"], info["loudness_gated"] = loud["lufs"], loud["peak"], loud["blocks"], loud["gated"]
+        info["gain"] = gains
     for field in FILE_INFO_DTYPE.names:
         info[field] = batch.info[field]
     info["track_samples"], info["final_status"], info["bad_packet"] = lengths, status[:, 0], status[:, 1]
@@ -1274,8 +1369,23 @@ class Context:
         self._chk(self.lib.opusgpu_tracks_melspec_device(self.h, spans.size, spans.ctypes.data, d_in, rec.ctypes.data, d_out, stream),
                   "opusgpu_tracks_melspec_device")
 
+    def tracks_loudness_device(self, spans, d_in, channels, weights=None, stream=None):
+        """k_tracks_loudness_seg and k_tracks_loudness_gate alone (include/opusgpu.h TRACK LOUDNESS): spans a HOST array of
+        LOUDNESS_SPAN_DTYPE, d_in packed int16 tracks of `channels` channels, weights None (the defaults) or one float per channel
+        -> a LOUDNESS_DTYPE record per track.  Waits for the kernels."""
+        spans = np.ascontiguousarray(spans, dtype=LOUDNESS_SPAN_DTYPE)
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float32)
+        if w is not None and w.shape != (channels,):
+            raise ValueError(f"weights must have one entry per channel ({channels}), not shape {w.shape}")
+        out = np.zeros(spans.size, dtype=LOUDNESS_DTYPE)
+        self._chk(self.lib.opusgpu_tracks_loudness_device(self.h, spans.size, spans.ctypes.data, d_in, channels,
+                                                          None if w is None else w.ctypes.data, out.ctypes.data, stream),
+                  "opusgpu_tracks_loudness_device")
+        return out
+
     def decode_files(self, files, rfc=False, flags=PAGES_GROUP_BY_MODE, threads=1, batch=None, format=None, scale=None, out=None,
-                     rate=None, mono=False, mix=None, features=None, n_mels=80, feature_layout="bands", resample=None):
+                     rate=None, mono=False, mix=None, features=None, n_mels=80, feature_layout="bands", resample=None, loudness=None,
+                     peak_limit=1.0, channel_weights=None):
         """Whole Ogg Opus files -> (list of int16 arrays [samples, channels], one trimmed track per file, info).  The context's
         streams 0 .. len(files) - 1 are (re)allocated when there are too few and get fresh state; its mode is set to `rfc`.
         info: FILE_INFO_DTYPE records with two more fields: `final_status` (the first failed frame's code, else the plan's status)
@@ -1310,14 +1420,22 @@ class Context:
         features may also be a mel_spec() record: a mel spectrogram of the mono track at the record's sample_rate (include/opusgpu.h
         TRACK SPECTROGRAMS: n_fft, win_length, hop, n_mels, fmin / fmax, Slaney or HTK, power 1 or 2, log10 / ln / none and a floor
         are fields), with rate= or resample= naming that rate (or neither: the record's is taken), mono=True or a mix of one row,
-        and scale=, out= and info as with "logmel"; n_mels= and feature_layout= are the record's (track_spectrogram_args)."""
+        and scale=, out= and info as with "logmel"; n_mels= and feature_layout= are the record's (track_spectrogram_args).
+        loudness: None, or "measure" for the integrated loudness (ITU-R BS.1770-4) and sample peak of every track, measured on the
+        GPU on the 48 kHz int16 track in the same call (include/opusgpu.h TRACK LOUDNESS) -- the result is what it is without it,
+        and info gains `lufs` (-inf: no block passed the gates), `peak`, `loudness_blocks`, `loudness_gated` and `gain` (1.0) --, or
+        a target in LUFS (e.g. -23.0): every track is then scaled by loudness_gain(record, target, peak_limit) on top of scale=,
+        `gain` says by how much, and the result must be a float format or features (ValueError otherwise, before any device
+        work).  peak_limit: the largest sample peak a gain may leave (<= 0: none).  channel_weights: one weight per decoded channel
+        in place of the defaults (loudness_weights).  The measurement is taken on all decoded channels, in front of mix and rate."""
         if mix is not None and mono:  # (files_request's first refusal, ahead of the plan as it always was)
             raise ValueError("mix and mono=True exclude each other: the row {8192, 8192} is mono")
         own = batch is None
         if own:
             batch = FileBatch(files, channels=self.channels or 2, rfc=rfc, flags=flags, threads=threads)
         try:
-            req = files_request(batch, False, self.device, format, scale, out, rate, mono, mix, features, n_mels, feature_layout, resample)
+            req = files_request(batch, False, self.device, format, scale, out, rate, mono, mix, features, n_mels, feature_layout, resample,
+                                loudness, peak_limit, channel_weights)
             if self.n_streams < batch.n_files or self.channels != batch.channels:
                 self.streams_alloc(max(batch.n_files, 1), batch.channels)
             self.set_mode(batch.rfc)
@@ -1489,7 +1607,7 @@ class MultistreamContext:
                   "opusgpu_ms_tracks_assemble_device_as")
 
     def decode_files(self, files, rfc=False, threads=1, batch=None, format=None, scale=None, out=None, rate=None, mix=None, features=None,
-                     n_mels=80, feature_layout="bands", resample=None):
+                     n_mels=80, feature_layout="bands", resample=None, loudness=None, peak_limit=1.0, channel_weights=None):
         """Whole Ogg Opus files of this object's layout -> (list of int16 arrays [samples, channels], one trimmed track per file,
         info), as Context.decode_files returns them: FILE_INFO_DTYPE records plus `final_status` and `bad_packet`, `track_samples`
         the FINAL length.  Decoders 0 .. len(files) - 1 get fresh state; the object's mode is set to the batch's.  batch: an
@@ -1497,13 +1615,16 @@ class MultistreamContext:
         for Context.decode_files, all channels at `rate`.  mix: as for Context.decode_files -- "mono" and "stereo" are the default
         downmix tables of the layout's channel count; there is no `mono` argument here.
         features, n_mels, feature_layout: as for Context.decode_files, with mix="mono" or a matrix of one row.
-        resample: as for Context.decode_files, all channels or those of the mix.  features may be a mel_spec() record as there."""
+        resample: as for Context.decode_files, all channels or those of the mix.  features may be a mel_spec() record as there.
+        loudness, peak_limit, channel_weights: as for Context.decode_files; the default weights are those of the layout's channel
+        count (1.41 for the rear pair, 0 for the LFE)."""
         own = batch is None
         if own:
             batch = MsFileBatch(files, self.layout, rfc=rfc, threads=threads)
         mem = None
         try:
-            req = files_request(batch, True, self.device, format, scale, out, rate, False, mix, features, n_mels, feature_layout, resample)
+            req = files_request(batch, True, self.device, format, scale, out, rate, False, mix, features, n_mels, feature_layout, resample,
+                                loudness, peak_limit, channel_weights)
             mem = Context(self.device)  # (device memory and copies are a plain context's calls)
             self.set_mode(batch.rfc)
             return _run_files_request(req, self.lib, "opusgpu_ms_", self.h, self._chk, batch, mem)

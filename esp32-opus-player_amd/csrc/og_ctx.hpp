@@ -80,6 +80,14 @@ struct HostPool {
     }
 };
 
+// TRACK LOUDNESS: the request that holds for the whole-file calls that follow (opusgpu_set_loudness), and what the last of them
+// measured and applied (opusgpu_last_loudness).  One per context of either kind.
+struct LoudnessState {
+    opusgpu_loudness_req req{}; // mode 0: off
+    std::vector<opusgpu_loudness> records;
+    std::vector<double> gains;
+};
+
 struct opusgpu_ctx {
     int device = -1;
     hipStream_t stream = nullptr;
@@ -142,6 +150,7 @@ struct opusgpu_ctx {
     // RFC mode, host side of the loss path: per stream, the frame count and descriptor flags of the last packet framed by
     // opusgpu_decode_packets -- what a lost packet of that stream is concealed as (0 frames: nothing framed yet)
     std::vector<int32_t> last_count, last_flags;
+    LoudnessState loud;
     char err[256] = {0};
 };
 

@@ -176,6 +176,7 @@ struct opusgpu_ms {
     // the host path: packet bytes, placements, output
     void *d_arena = nullptr, *d_place = nullptr, *d_out = nullptr, *d_res = nullptr;
     size_t cap_arena = 0, cap_place = 0, cap_out = 0, cap_res = 0;
+    LoudnessState loud;
     char err[256] = {0};
 };
 

@@ -419,7 +419,7 @@ static FilesOwner files_owner(opusgpu_ms *ms, const opusgpu_ms_file_batch *batch
                       [=](void *d_s16, int64_t *lengths, int32_t *status) {
                           return ms_files_decode_run(ms, batch, OPUSGPU_TRACKS_S16, nullptr, d_s16, lengths, status);
                       },
-                      track_fail(ms)};
+                      track_fail(ms), &ms->loud};
 }
 
 extern "C" {
@@ -454,7 +454,11 @@ int opusgpu_ms_tracks_assemble_device(opusgpu_ms *ms, int n_segs, const void *d_
 
 int opusgpu_ms_files_decode(opusgpu_ms *ms, const opusgpu_ms_file_batch *batch, void *d_tracks, int64_t *track_lengths_out,
                             int32_t *status_out) {
-    return ms_files_decode_run(ms, batch, OPUSGPU_TRACKS_S16, nullptr, d_tracks, track_lengths_out, status_out);
+    if (!ms || !batch || ms->loud.req.mode == OPUSGPU_LOUDNESS_OFF)
+        return ms_files_decode_run(ms, batch, OPUSGPU_TRACKS_S16, nullptr, d_tracks, track_lengths_out, status_out);
+    return files_decode_measured(files_owner(ms, batch), d_tracks, track_lengths_out, status_out, [&](int64_t *lengths, int32_t *status) {
+        return ms_files_decode_run(ms, batch, OPUSGPU_TRACKS_S16, nullptr, d_tracks, lengths, status);
+    });
 }
 
 int opusgpu_ms_files_decode_as(opusgpu_ms *ms, const opusgpu_ms_file_batch *batch, int format, const float *scale, void *d_tracks,
@@ -462,7 +466,12 @@ int opusgpu_ms_files_decode_as(opusgpu_ms *ms, const opusgpu_ms_file_batch *batc
     if (!ms || !batch) return OPUSGPU_BAD_ARG;
     std::vector<TrackPlace> places;
     if (int rc = track_places(*batch, format, scale, places)) return rc;
-    return ms_files_decode_run(ms, batch, format, format == OPUSGPU_TRACKS_S16 ? nullptr : &places, d_tracks, track_lengths_out, status_out);
+    if (format == OPUSGPU_TRACKS_S16) return opusgpu_ms_files_decode(ms, batch, d_tracks, track_lengths_out, status_out);
+    if (ms->loud.req.mode != OPUSGPU_LOUDNESS_OFF) {
+        snprintf(ms->err, sizeof(ms->err), "%s", OG_LOUD_AS_REFUSED);
+        return OPUSGPU_BAD_ARG;
+    }
+    return ms_files_decode_run(ms, batch, format, &places, d_tracks, track_lengths_out, status_out);
 }
 
 // opusgpu_files_decode_resampled behind opusgpu_ms_files_decode (og_tracks_resample.hpp): all channels, no downmix.

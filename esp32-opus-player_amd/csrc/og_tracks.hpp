@@ -294,14 +294,26 @@ struct FilesOwner {
     hipStream_t stream;
     std::function<int(void *d_s16, int64_t *lengths, int32_t *status)> decode;
     TrackFail hip_failed;
+    LoudnessState *loud = nullptr; // TRACK LOUDNESS (og_tracks_loudness.hpp): the owner's request and what the call measures
+    bool scale_later = false;      // the S16 tracks of this call feed a feature kernel, which applies the scale and a gain with it
 };
 static FilesOwner files_owner(opusgpu_ctx *ctx, const opusgpu_file_batch *batch) {
     return FilesOwner{*batch, ctx->device, ctx->stream,
                       [=](void *d_s16, int64_t *lengths, int32_t *status) {
                           return files_decode_run(ctx, batch, OPUSGPU_TRACKS_S16, nullptr, d_s16, lengths, status);
                       },
-                      track_fail(ctx)};
+                      track_fail(ctx), &ctx->loud};
 }
+
+// With a loudness request on, the int16 tracks of `run` are measured where the caller has them (og_tracks_loudness.hpp); without one
+// this is run(track_lengths_out, status_out).
+template <class Run>
+static int files_decode_measured(const FilesOwner &own, void *d_tracks, int64_t *track_lengths_out, int32_t *status_out, Run run);
+// What opusgpu_files_decode_as and its multistream twin answer for a float format while a request is on: the float store is fused
+// into the assembly, so there is never an S16 track to measure.
+#define OG_LOUD_AS_REFUSED                                                                                                       \
+    "a loudness request is on and this call has no int16 track to measure: use the _mixed call at rate 48000 with the identity " \
+    "matrix (16384 on the diagonal), which writes the same elements"
 
 extern "C" {
 
@@ -330,7 +342,11 @@ int opusgpu_tracks_assemble_device(opusgpu_ctx *ctx, int n_segs, const void *d_s
 
 int opusgpu_files_decode(opusgpu_ctx *ctx, const opusgpu_file_batch *batch, void *d_tracks, int64_t *track_lengths_out,
                          int32_t *status_out) {
-    return files_decode_run(ctx, batch, OPUSGPU_TRACKS_S16, nullptr, d_tracks, track_lengths_out, status_out);
+    if (!ctx || !batch || ctx->loud.req.mode == OPUSGPU_LOUDNESS_OFF)
+        return files_decode_run(ctx, batch, OPUSGPU_TRACKS_S16, nullptr, d_tracks, track_lengths_out, status_out);
+    return files_decode_measured(files_owner(ctx, batch), d_tracks, track_lengths_out, status_out, [&](int64_t *lengths, int32_t *status) {
+        return files_decode_run(ctx, batch, OPUSGPU_TRACKS_S16, nullptr, d_tracks, lengths, status);
+    });
 }
 
 int opusgpu_files_decode_as(opusgpu_ctx *ctx, const opusgpu_file_batch *batch, int format, const float *scale, void *d_tracks,
@@ -338,7 +354,12 @@ int opusgpu_files_decode_as(opusgpu_ctx *ctx, const opusgpu_file_batch *batch, i
     if (!ctx || !batch) return OPUSGPU_BAD_ARG;
     std::vector<TrackPlace> places;
     if (int rc = track_places(*batch, format, scale, places)) return rc;
-    return files_decode_run(ctx, batch, format, format == OPUSGPU_TRACKS_S16 ? nullptr : &places, d_tracks, track_lengths_out, status_out);
+    if (format == OPUSGPU_TRACKS_S16) return opusgpu_files_decode(ctx, batch, d_tracks, track_lengths_out, status_out);
+    if (ctx->loud.req.mode != OPUSGPU_LOUDNESS_OFF) {
+        snprintf(ctx->err, sizeof(ctx->err), "%s", OG_LOUD_AS_REFUSED);
+        return OPUSGPU_BAD_ARG;
+    }
+    return files_decode_run(ctx, batch, format, &places, d_tracks, track_lengths_out, status_out);
 }
 
 } // extern "C"

@@ -397,14 +397,17 @@ static int files_feature_run(const FilesOwner &own, int rate, int up, int down, 
         if (e == hipSuccess) e = y.alloc((size_t)total * 2 + 128);
         if (e != hipSuccess) return own.hip_failed(OPUSGPU_ALLOC_FAIL, flow.scratch_failed, e);
     }
-    const int rc = rate ? files_resampled_run(own, rate, mono, mix, OPUSGPU_TRACKS_S16, nullptr, y.p, offs.data(), len.data(), lengths.data(),
+    FilesOwner inner = own; // TRACK LOUDNESS: measured there on the 48 kHz scratch, the gain applied here with the scale
+    inner.scale_later = true;
+    const int rc = rate ? files_resampled_run(inner, rate, mono, mix, OPUSGPU_TRACKS_S16, nullptr, y.p, offs.data(), len.data(), lengths.data(),
                                               status.data())
-                        : files_ratio_run(own, up, down, mono, mix, OPUSGPU_TRACKS_S16, nullptr, y.p, offs.data(), len.data(), lengths.data(),
+                        : files_ratio_run(inner, up, down, mono, mix, OPUSGPU_TRACKS_S16, nullptr, y.p, offs.data(), len.data(), lengths.data(),
                                           status.data());
     if (rc) return rc;
     std::vector<opusgpu_mel_span> spans(n);
     for (size_t i = 0; i < n; i++)
-        spans[i] = opusgpu_mel_span{offs[i], len[i], feat[i], flow.plane(planned[i], up, down), scale ? scale[i] : 1.0f / 32768, 0};
+        spans[i] = opusgpu_mel_span{offs[i], len[i], feat[i], flow.plane(planned[i], up, down),
+                                    loud_normalizes(own) ? loud_scale(own, scale, i) : scale ? scale[i] : 1.0f / 32768, 0};
     if (int rc2 = flow.run((int)n, spans.data(), y.p)) return rc2;
     for (size_t i = 0; i < n; i++) {
         if (feat_offsets) feat_offsets[i] = feat[i];

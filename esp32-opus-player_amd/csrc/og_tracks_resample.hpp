@@ -453,6 +453,9 @@ static int files_resampled_to(const FilesOwner &own, int up, int down, int forma
                               int64_t *out_lengths, int64_t *track_lengths_out, int32_t *status_out, Run run) {
     const og_batch &b = own.b;
     if (!rs_scale_ok(format, scale, b.n_files)) return OPUSGPU_BAD_ARG;
+    // TRACK LOUDNESS: int16 tracks take no gain, unless they only feed a feature kernel that applies it
+    if (loud_normalizes(own) && format == OPUSGPU_TRACKS_S16 && !own.scale_later) return OPUSGPU_BAD_ARG;
+    if (loud_on(own) && own.loud->req.n_weights && own.loud->req.n_weights != b.channels) return OPUSGPU_BAD_ARG;
     const size_t n = (size_t)b.n_files;
     std::vector<int64_t> lengths(n, 0), offsets;
     std::vector<int32_t> status(2 * n, 0);
@@ -464,7 +467,11 @@ static int files_resampled_to(const FilesOwner &own, int up, int down, int forma
         if (e != hipSuccess) return own.hip_failed(OPUSGPU_ALLOC_FAIL, "hipMalloc(resample scratch)", e);
     }
     if (int rc = own.decode(s16.p, lengths.data(), status.data())) return rc;
+    if (loud_on(own)) // the S16 tracks at their final lengths, all decoded channels, in front of the mix and the rate
+        if (int rc = files_loudness(own, s16.p, lengths.data())) return rc;
     rs_batch_spans(b, up, down, lengths.data(), scale, offsets, spans);
+    if (loud_normalizes(own) && format != OPUSGPU_TRACKS_S16)
+        for (size_t i = 0; i < n; i++) spans[i].scale = loud_scale(own, scale, i);
     if (int rc = run(b.n_files, spans.data(), s16.p)) return rc;
     for (size_t i = 0; i < n; i++) {
         if (out_offsets) out_offsets[i] = offsets[i];

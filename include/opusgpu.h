@@ -951,6 +951,86 @@ int opusgpu_files_decode_melspec(opusgpu_ctx *ctx, const opusgpu_file_batch *bat
                                  const opusgpu_mix_matrix *mix, const opusgpu_spec_params *p, const float *scale, void *d_out,
                                  int64_t *feat_offsets, int64_t *frames_out, int64_t *track_lengths_out, int32_t *status_out);
 
+/* TRACK LOUDNESS.  Integrated loudness per ITU-R BS.1770-4 and the sample peak of every track, measured on the GPU, and optionally
+ * a gain to a target loudness folded into the float scale of the same call.  All of it is a function of the S16 track at 48 kHz:
+ * the int16 samples s_c[n] the default path writes, at the track's FINAL length len.  Samples at or past len are never read as
+ * signal.
+ *   K-WEIGHTING.  The two 48 kHz biquads of BS.1770-4 with the standard's own numbers, y[n] = b0 x[n] + b1 x[n-1] + b2 x[n-2]
+ *   - a1 y[n-1] - a2 y[n-2]:  stage 1  b = {1.53512485958697, -2.69169618940638, 1.19839281085285}, a = {1, -1.69065929318241,
+ *   0.73248077421585};  stage 2  b = {1, -2, 1}, a = {1, -1.99004745483398, 0.99007225036621}.  The input is x_c[n] = s_c[n] / 32768,
+ *   the state is zero at the track's first sample, the output is z_c.
+ *   SEGMENTS AND BLOCKS.  Segment j of channel c has the energy e_c[j] = sum z_c[n]^2 over n in [4800 j, 4800 j + 4800); only whole
+ *   segments count, floor(len / 4800) of them.  Block j covers segments j .. j + 3 (400 ms, 75 % overlap):
+ *       p[j] = sum_c G_c (e_c[j] + e_c[j+1] + e_c[j+2] + e_c[j+3]) / 19200,         blocks = max(0, floor(len / 4800) - 3).
+ *   GATING.  The blocks with -0.691 + 10 log10 p[j] > -70 pass the absolute gate; those among them with p[j] > 0.1 x the mean of
+ *   the blocks that passed the absolute gate pass the relative gate (10 LU below that mean);  lufs = -0.691 + 10 log10(mean of
+ *   the blocks that passed the relative gate), `gated` their count.  If no block passes, lufs = -inf and gated = 0.
+ *   CHANNEL WEIGHTS.  G_c defaults by channel count in the Vorbis order of CHANNEL MIX, by BS.1770-4's azimuth rule at the nominal
+ *   positions (between 60 and 120 degrees: 1.41; the LFE: 0; else 1):  1: {1};  2: {1, 1};  3: {1, 1, 1};  4: {1, 1, 1.41, 1.41};
+ *   5: {1, 1, 1, 1.41, 1.41};  6: {1, 1, 1, 1.41, 1.41, 0};  7: {1, 1, 1, 1.41, 1.41, 1, 0};  8: {1, 1, 1, 1.41, 1.41, 1, 1, 0}.  A
+ *   caller may pass weights of their own: finite and >= 0.
+ *   PEAK.  max |s_c[n]| / 32768 over all channels, the LFE included, and over all len samples.  It is exact.
+ *   GAIN.  A pure function of the record, on the host in double:  g = 10^((target - lufs) / 20);  if peak_limit > 0 and peak * g >
+ *   peak_limit, g = peak_limit / peak;  if lufs is -inf, g = 1.  The scale a normalising call applies to track t is
+ *   (float)((double)scale[t] * g), and every float sample is then (float)s * that, as TRACK FORMATS says: normalised tracks stay a
+ *   bit-for-bit function of the int16 tracks and the record.
+ *   PRECISION.  The kernels filter and sum the segment energies in float32 (every operation rounded on its own, nothing fused; a
+ *   segment's starting state comes from one segment of warm-up, which leaves out 0.99502^4800 = 4e-11 of it) and gate in double;
+ *   the result is the same bits from run to run, and a track's record does not depend on which other tracks are in the call.
+ *   Against the definition in double lufs differs by rounding alone (DESIGN 13h has the measured bound); peak, blocks and gated
+ *   do not differ unless a block lies within that rounding of a gate. */
+typedef struct opusgpu_loudness_span { /* 16 bytes, one per track (ABI) */
+    int64_t in_offset;  /* where the S16 track begins in d_in, samples per channel; a multiple of 8 */
+    int64_t in_samples; /* its FINAL length */
+} opusgpu_loudness_span;
+typedef struct opusgpu_loudness { /* 16 bytes, one per track (ABI) */
+    float lufs;     /* integrated loudness, -inf when no block passes */
+    float peak;     /* sample peak, 0 .. 1 */
+    int32_t blocks; /* 400 ms blocks of the track */
+    int32_t gated;  /* of which passed both gates */
+} opusgpu_loudness;
+/* The default weights of `channels` (1 - 8) channels into weights[0 .. channels); anything else is OPUSGPU_BAD_ARG.  Host only. */
+int opusgpu_loudness_weights(int channels, float *weights);
+/* GAIN above for the record *r (NULL: 1).  Host only. */
+double opusgpu_loudness_gain(const opusgpu_loudness *r, double target_lufs, double peak_limit);
+/* k_tracks_loudness_seg and k_tracks_loudness_gate alone: d_in holds packed interleaved int16 tracks of `channels` (1 - 8) channels,
+ * 16-byte aligned, read in aligned 16-byte pieces up to the one that holds a track's last sample; `spans` is a HOST array of
+ * n_tracks records, `weights` a host array of `channels` floats or NULL for the defaults, `out` a HOST array of n_tracks records.
+ * Uploads the spans and its tile table, launches on the context's stream (or `hip_stream`), waits, brings 16 bytes per track back
+ * and frees everything on every way out; `out` is written only on success.  OPUSGPU_BAD_ARG before any device work: channels
+ * outside 1 - 8, a span that breaks the rules above, a weight that is negative or not finite. */
+int opusgpu_tracks_loudness_device(opusgpu_ctx *ctx, int n_tracks, const opusgpu_loudness_span *spans, const void *d_in, int channels,
+                                   const float *weights /* NULL: defaults */, opusgpu_loudness *out, void *hip_stream);
+#define OPUSGPU_LOUDNESS_OFF 0
+#define OPUSGPU_LOUDNESS_MEASURE 1   /* records only: every result is what it is without the request */
+#define OPUSGPU_LOUDNESS_NORMALIZE 2 /* and GAIN folded into the float scale */
+typedef struct opusgpu_loudness_req { /* 48 bytes (ABI) */
+    int32_t mode;
+    float target_lufs; /* OPUSGPU_LOUDNESS_NORMALIZE: the target, e.g. -23 (EBU R 128) */
+    float peak_limit;  /* OPUSGPU_LOUDNESS_NORMALIZE: see GAIN; <= 0: none */
+    int32_t n_weights; /* 0: the defaults of the tracks' channel count; else it must be that count */
+    float weights[8];
+} opusgpu_loudness_req;
+/* The request that holds for the whole-file calls that follow, as opusgpu_set_mode does; NULL or mode 0 is off, the default, and
+ * every call is then exactly what it is above.  OPUSGPU_BAD_ARG: an unknown mode, n_weights outside 0 - 8, a weight that is negative
+ * or not finite, a target or limit that is not finite.  With a request on:
+ *   every whole-file call that holds scratch S16 tracks -- _resampled, _mixed, _ratio, _mel and _melspec, of both kinds of context --
+ *   measures them between its decode and its own kernel, at their final lengths (a failed track too), on all decoded channels, in
+ *   front of the mix and the rate; with OPUSGPU_LOUDNESS_NORMALIZE the gain goes into the scale its kernel applies;
+ *   opusgpu_files_decode and opusgpu_ms_files_decode (and the _as calls with OPUSGPU_TRACKS_S16) measure the int16 tracks in the
+ *   caller's buffer after the last step;
+ *   OPUSGPU_LOUDNESS_NORMALIZE with an int16 result is OPUSGPU_BAD_ARG before any device work, as a scale with S16 is, and so is a
+ *   request whose n_weights is neither 0 nor the batch's channel count;
+ *   opusgpu_files_decode_as and opusgpu_ms_files_decode_as with a float format fuse the float store into the assembly and never
+ *   have an S16 track: they return OPUSGPU_BAD_ARG, and the message names the way round -- the _mixed call at rate 48000 with
+ *   the identity matrix (16384 on the diagonal), which is exact (sat16((16384 s + 8192) >> 14) = s) and writes the same elements. */
+int opusgpu_set_loudness(opusgpu_ctx *ctx, const opusgpu_loudness_req *req);
+/* What the last whole-file call with a request on measured and applied: returns the number of its tracks (0: none yet) and writes
+ * the first min(n, that) records and gains (either may be NULL; a gain is 1 when the request only measured). */
+int opusgpu_last_loudness(const opusgpu_ctx *ctx, int n, opusgpu_loudness *records, double *gains);
+int opusgpu_ms_set_loudness(opusgpu_ms *ms, const opusgpu_loudness_req *req);
+int opusgpu_ms_last_loudness(const opusgpu_ms *ms, int n, opusgpu_loudness *records, double *gains);
+
 /* ---- WHOLE FILES / MULTISTREAM: N surround Ogg Opus files in, N trimmed interleaved tracks in HBM out -----------------------------
  * The two sections above joined: files whose OpusHead carries channel mapping family 1 (1 - 8 channels, `streams` elementary
  * streams) are planned by the same reader-driven loop as stereo files and decoded by an opusgpu_ms of their layout.  The reader's

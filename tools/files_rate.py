@@ -22,7 +22,11 @@ tracks, whose tiles are full.
 --resample UP/DOWN [--mono | --mix M]: the fused ratio call (opusgpu_files_decode_ratio, include/opusgpu.h TRACK RATIOS) next to
 rate=24000 on the same corpus and to float32 48 kHz tracks resampled by a polyphase conv1d in torch, interleaved, and the two
 kernels alone per output sample (tools/ratio_rate.py).
-usage (GPU box): python3 tools/files_rate.py [--n N] [--reps R] [--format F | --rate R [--mono | --mix M] | --resample U/D [--mono | --mix M] | --mel [--n-mels N] | --melspec SET] [--packets-per-file P] | python3 tools/files_rate.py --stats DIR [--n N]"""
+--loudness [TARGET] [--rate R --mono] [--packets-per-file P]: what a loudness request adds to the call (include/opusgpu.h TRACK
+LOUDNESS; tools/loudness_rate.py): float32 tracks at 48 kHz, or mono ones at --rate, without the request, with loudness="measure"
+and, with a TARGET in LUFS, normalising -- interleaved; the added time per call and its share of the call.  Tracks need 400 ms for
+a block: --packets-per-file 500 gives 10 s files.
+usage (GPU box): python3 tools/files_rate.py [--n N] [--reps R] [--loudness [T] |--format F | --rate R [--mono | --mix M] | --resample U/D [--mono | --mix M] | --mel [--n-mels N] | --melspec SET] [--packets-per-file P] | python3 tools/files_rate.py --stats DIR [--n N]"""
 import argparse
 import ctypes as C
 import glob
@@ -54,12 +58,16 @@ ap.add_argument("--mel", action="store_true", help="compare the fused log-mel ca
 ap.add_argument("--n-mels", type=int, choices=[80, 128], default=80)
 ap.add_argument("--melspec", choices=["tts", "kaldi", "clap", "music"], default=None,
                 help="compare the fused mel-spectrogram call with float mono tracks at the set's rate + torch.stft (tools/mel_rate.py)")
-ap.add_argument("--packets-per-file", type=int, default=10, help="with --mel or --melspec: packets of 20 ms per file")
+ap.add_argument("--packets-per-file", type=int, default=10, help="with --mel, --melspec or --loudness: packets of 20 ms per file")
+ap.add_argument("--loudness", nargs="?", const="measure", default=None, metavar="TARGET",
+                help="what a loudness request adds to the float32 call, measuring and (with a target in LUFS) normalising (tools/loudness_rate.py)")
 args = ap.parse_args()
+if args.loudness and (args.format or args.mel or args.melspec or args.resample or args.mix or (args.rate and not args.mono)):
+    ap.error("--loudness goes alone or with --rate R --mono")
 if args.melspec and (args.rate or args.format or args.resample or args.mel):
     ap.error("--melspec goes without --rate, --resample, --format and --mel")
-if args.packets_per_file != 10 and not (args.mel or args.melspec):
-    ap.error("--packets-per-file goes with --mel or --melspec")
+if args.packets_per_file != 10 and not (args.mel or args.melspec or args.loudness):
+    ap.error("--packets-per-file goes with --mel, --melspec or --loudness")
 if args.mix and (args.mono or not (args.rate or args.resample)):
     ap.error("--mix goes with --rate or --resample and without --mono")
 if args.mel and (args.rate or args.format or args.resample):
@@ -67,7 +75,7 @@ if args.mel and (args.rate or args.format or args.resample):
 if args.resample and (args.rate or args.format):
     ap.error("--resample goes without --rate and --format")
 n = args.n
-if args.format or args.rate or args.mel or args.resample or args.melspec:
+if (args.format or args.rate or args.mel or args.resample or args.melspec) and not args.loudness:
     import torch  # before the library: one HIP runtime for both
 
 spec = importlib.util.spec_from_file_location("esp32_opus_player_amd", os.path.join(here, "..", "esp32-opus-player_amd", "__init__.py"))
@@ -97,6 +105,22 @@ if args.stats:
         print(json.dumps({"kernel": r["Name"].split("(")[0], "calls": int(r["Calls"]), "avg_ms_per_launch": round(avg_ms, 4),
                           "min_ms": round(float(r["MinNs"]) / 1e6, 4), "ms_per_batch_of_10": round(avg_ms * 10, 3),
                           "bytes_per_batch": moved, "tb_per_s": round(moved / 10 / (avg_ms / 1e3) / 1e12, 2)}))
+    raise SystemExit(0)
+
+if args.loudness:
+    import loudness_rate
+    b = pkg.FileBatch([r.tobytes() for r in files], channels=2, flags=pkg.PAGES_GROUP_BY_MODE, threads=args.threads)
+    assert (b.info["status"] == 0).all() and b.n_steps == PAGES * PER_PAGE
+    ctx = pkg.Context(0)
+    ctx.streams_alloc(n, 2)
+    ctx.set_mode(b.rfc)
+    kw = dict(rate=args.rate, mono=True, format="f32") if args.rate else dict(format="f32")
+    target = None if args.loudness == "measure" else float(args.loudness)
+    for name, pipe in (("in_order", 0), ("pipelined", 1)):
+        ctx.set_pipeline(pipe)
+        what = f"stereo, {'%d Hz mono' % args.rate if args.rate else '48 kHz'} f32, {PAGES * PER_PAGE} packets per file, {name}"
+        print(json.dumps(loudness_rate.compare(pkg, ctx, ctx.lib, "opusgpu_", ctx.h, ctx._chk, b, False, args.reps, target, what, **kw)), flush=True)
+    ctx.close()
     raise SystemExit(0)
 
 if args.format:

@@ -21,7 +21,11 @@ next to float32 mono tracks at the set's rate followed by torch.stft, the filter
 k_tracks_melspec's share of the call (tools/mel_rate.py: compare_spec).
 --resample UP/DOWN [--mix M]: the fused ratio call (opusgpu_ms_files_decode_ratio) next to rate=24000 on the same corpus and to
 float32 48 kHz tracks resampled by a polyphase conv1d in torch, and the two kernels alone (tools/ratio_rate.py).
-usage (GPU box): python3 tools/ms_files_rate.py [--n N] [--reps R] [--format F | --rate R [--mix M] | --resample U/D [--mix M] | --mel [--n-mels N] | --melspec SET] | python3 tools/ms_files_rate.py --stats DIR [--n N]"""
+--loudness [TARGET] [--packets-per-file P]: what a loudness request adds to the float32 call at 48 kHz (include/opusgpu.h TRACK
+LOUDNESS; tools/loudness_rate.py): without the request, with loudness="measure" and, with a TARGET in LUFS, normalising --
+interleaved; the added time per call and its share of the call.  P (at most 80: one page) packets per file in place of 10: tracks
+need 400 ms for a block.
+usage (GPU box): python3 tools/ms_files_rate.py [--n N] [--reps R] [--loudness [T] [--packets-per-file P] | --format F | --rate R [--mix M] | --resample U/D [--mix M] | --mel [--n-mels N] | --melspec SET] | python3 tools/ms_files_rate.py --stats DIR [--n N]"""
 import argparse
 import ctypes as C
 import glob
@@ -51,7 +55,14 @@ ap.add_argument("--mel", action="store_true", help="compare the fused log-mel ca
 ap.add_argument("--n-mels", type=int, choices=[80, 128], default=80)
 ap.add_argument("--melspec", choices=["tts", "kaldi", "clap", "music"], default=None,
                 help="compare the fused mel-spectrogram call with float mono tracks at the set's rate + torch.stft (tools/mel_rate.py)")
+ap.add_argument("--loudness", nargs="?", const="measure", default=None, metavar="TARGET",
+                help="what a loudness request adds to the float32 call, measuring and (with a target in LUFS) normalising (tools/loudness_rate.py)")
+ap.add_argument("--packets-per-file", type=int, default=10, help="with --loudness: packets of 20 ms per file, at most 80")
 args = ap.parse_args()
+if args.loudness and (args.format or args.rate or args.mel or args.melspec or args.resample or args.mix):
+    ap.error("--loudness goes alone")
+if args.packets_per_file != 10 and (not args.loudness or not 1 <= args.packets_per_file <= 80):
+    ap.error("--packets-per-file goes with --loudness and is at most 80: the files have one page")
 if args.melspec and (args.rate or args.format or args.resample or args.mel):
     ap.error("--melspec goes without --rate, --resample, --format and --mel")
 if args.mix and not (args.rate or args.resample):
@@ -72,7 +83,7 @@ import ms_files_util as mf  # noqa: E402
 import ogg_util  # noqa: E402
 
 LAYOUT = (6, 4, 2, [0, 4, 1, 2, 3, 5])
-CH, S, CP, L, PACKETS = 6, 4, 2, 160, 10
+CH, S, CP, L, PACKETS = 6, 4, 2, 160, args.packets_per_file
 rng = np.random.default_rng(3)
 pre = rng.integers(0, 2001, n)
 trim = rng.integers(0, 2001, n)
@@ -150,6 +161,19 @@ b = pkg.MsFileBatch(blobs, LAYOUT, threads=args.threads)
 plan_s = time.perf_counter() - t0
 assert (b.info["status"] == 0).all() and b.n_steps == PACKETS, (np.unique(b.info["status"]), b.n_steps)
 assert (b.info["track_samples"] == PACKETS * 960 - pre - trim).all()
+
+if args.loudness:
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import loudness_rate
+    ms = pkg.MultistreamContext(0, n, *LAYOUT)
+    ms.set_mode(b.rfc)
+    mem = pkg.Context(0)  # (device memory is a plain context's call)
+    target = None if args.loudness == "measure" else float(args.loudness)
+    print(json.dumps(loudness_rate.compare(pkg, mem, ms.lib, "opusgpu_ms_", ms.h, ms._chk, b, True, args.reps, target,
+                                           f"5.1, 48 kHz f32, {PACKETS} packets per file", format="f32")))
+    mem.close()
+    ms.close()
+    raise SystemExit(0)
 
 if args.format:
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
