@@ -27,7 +27,10 @@ struct WaveArr {
     OG_MEMBER i32 &fine_quant(int i) const { return S.fine_quant[i]; }
     OG_MEMBER i32 &fine_prio(int i) const { return S.fine_prio[i]; }
     OG_MEMBER i32 &tf_res(int i) const { return S.tf_res[i]; }
-    OG_MEMBER i32 &offsets(int i) const { return S.offsets[i]; }
+    // a band's dynalloc boost: n steps of the band's quanta (dynalloc_quanta) as celt_parse_header decodes them, the bits as
+    // compute_allocation reads them.  (A provider may keep the count alone: og_celt_parse.hpp.)
+    OG_MEMBER void boost_put(int i, int n, int quanta) const { S.offsets[i] = n * quanta; }
+    OG_MEMBER i32 boost(int i, int, int) const { return S.offsets[i]; }
     OG_MEMBER i32 &bits1(int i) const { return S.bits1[i]; }
     OG_MEMBER i32 &bits2(int i) const { return S.bits2[i]; }
     OG_MEMBER i16 &bandE(int i) const { return S.bandE_row()[i]; }
@@ -152,12 +155,22 @@ OG_DEV i32 celt_band_cap(int j, int LM, int C) {
     return (T::pulse_caps(NBANDS * (2 * LM + C - 1) + j) + 64) * C * Nb >> 2;
 }
 
+// The step of a band's dynalloc boost, in 1/8 bit (celt.cpp:2284-2286).  A boost is a whole number of these and its loop ends at
+// the band's cap: at most ceil(cap / quanta) steps, which is 66 over every band, LM and channel count (tests/test_celt_residency.py
+// walks them all) -- a count fits a byte.
+template <class T>
+OG_DEV i32 dynalloc_quanta(int j, int LM, int C) {
+    const int width = C * (T::eband(j + 1) - T::eband(j)) << LM;
+    return OG_MIN(width << BITRES, OG_MAX(6 << BITRES, width));
+}
+
 // ---- bit allocation (clt_compute_allocation celt.cpp:3523, interp_bits2pulses :3298) ----------------
 template <class A, class R>
 OG_DEV int compute_allocation(A a, R &rc, int start, int end, int alloc_trim, i32 &intensity, i32 &dual_stereo, i32 total,
                                i32 &balance_out, int C, int LM) {
     typedef typename A::Rom T;
     int skip_start = start, intensity_rsv = 0, dual_stereo_rsv = 0;
+    OG_STAT(59, total < 0);                                               // frames whose budget went negative (a silent frame's: everything is spent)
     total = OG_MAX(total, 0);
     int skip_rsv = total >= 1 << BITRES ? 1 << BITRES : 0;
     total -= skip_rsv;
@@ -192,7 +205,7 @@ OG_DEV int compute_allocation(A a, R &rc, int start, int end, int alloc_trim, i3
             int w = T::eband(j + 1) - T::eband(j);
             i32 bitsj = C * w * T::band_alloc(mid * NBANDS + j) << LM >> 2;
             if (bitsj > 0) bitsj = OG_MAX(0, bitsj + trim_off_of(j));
-            bitsj += a.offsets(j);
+            bitsj += a.boost(j, C, LM);
             if (bitsj >= thresh_of(j) || done) {
                 done = 1;
                 psum += OG_MIN(bitsj, celt_band_cap<T>(j, LM, C));
@@ -208,9 +221,10 @@ OG_DEV int compute_allocation(A a, R &rc, int start, int end, int alloc_trim, i3
         i32 b2 = hi >= 11 ? celt_band_cap<T>(j, LM, C) : C * w * T::band_alloc(hi * NBANDS + j) << LM >> 2;
         if (b1 > 0) b1 = OG_MAX(0, b1 + trim_off_of(j));
         if (b2 > 0) b2 = OG_MAX(0, b2 + trim_off_of(j));
-        if (lo > 0) b1 += a.offsets(j);
-        b2 += a.offsets(j);
-        if (a.offsets(j) > 0) skip_start = j;
+        const i32 boost = a.boost(j, C, LM);
+        if (lo > 0) b1 += boost;
+        b2 += boost;
+        if (boost > 0) skip_start = j;
         b2 = OG_MAX(0, b2 - b1);
         a.bits1(j) = b1;
         a.bits2(j) = b2;
@@ -1393,24 +1407,29 @@ OG_DEV void celt_parse_header(A a, R &rc, int start, int end, int C, int LM, Cel
     }
     // init_caps celt.cpp:911: a band's cap is a product of per-band constants -- computed where it is used instead of being kept
     // in a per-band array (1.3 KB of the lane-per-frame parse kernel's LDS per wave: one allocation granule, see celt_band_cap)
-    int dynalloc_logp = 6;
+    int dynalloc_logp = 6, any_boost = 0;
     total_bits <<= BITRES;
     tell = (i32)rc_tell_frac(rc);
     for (int i = start; i < end; i++) {
-        int width = C * (T::eband(i + 1) - T::eband(i)) << LM;
-        int quanta = OG_MIN(width << BITRES, OG_MAX(6 << BITRES, width));
-        int loop_logp = dynalloc_logp, boost = 0;
+        const int quanta = dynalloc_quanta<T>(i, LM, C);
+        int loop_logp = dynalloc_logp, boost = 0, steps = 0;
         while (tell + (loop_logp << BITRES) < total_bits && boost < celt_band_cap<T>(i, LM, C)) {
             int flag = rc_bit_logp(rc, loop_logp);
             tell = (i32)rc_tell_frac(rc);
             if (!flag) break;
             boost += quanta;
+            steps++;
             total_bits -= quanta;
             loop_logp = 1;
         }
-        a.offsets(i) = boost;
+        OG_STAT(57, steps >= 3);                                          // bands boosted three times or more
+        OG_STAT(58, steps > 0 && boost >= celt_band_cap<T>(i, LM, C));    // boosts stopped by the band's cap
+        any_boost |= steps > 0;
+        a.boost_put(i, steps, quanta);
         if (boost > 0) dynalloc_logp = OG_MAX(2, dynalloc_logp - 1);
     }
+    OG_STAT(56, any_boost);                                               // frames with a dynalloc boost
+    (void)any_boost;
     int alloc_trim = 5;
     if (tell + (6 << BITRES) <= total_bits) { // trim_icdf, ftb 7
         u32 s = rc.rng, d = rc.val, r = s >> 7, t;

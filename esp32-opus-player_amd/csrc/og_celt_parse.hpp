@@ -28,6 +28,7 @@ namespace og {
 #endif
 #define OG_PL_FRAMES (OG_PL_LANES * OG_PL_WAVES) // frames per workgroup
 struct ParseLds { // [element][lane]: lanes of a wave touch consecutive addresses, no bank conflicts
+    // (from the dynalloc boosts until compute_allocation settles the fine bits, fine_quant holds the bands' BOOST COUNTS -- see LaneArr::boost)
     i8 fine_quant[NBANDS][OG_PL_LANES];
     i8 tf_prio[NBANDS][OG_PL_LANES]; // bits 0-3: tf_res (-3 .. 3, two's complement), bit 4: fine_prio
     // Three tenants, one after the other (next to the reconstruction the kernel's LDS is what keeps that kernel's waves out: 16.1 KB
@@ -37,7 +38,7 @@ struct ParseLds { // [element][lane]: lanes of a wave touch consecutive addresse
         // finalise pass); in between they rest in the frame's record (LaneArr::energies_rest / energies_back: 21 words each way)
         i16 bandE[2 * NBANDS][OG_PL_LANES];
         struct { // from the dynalloc boosts until compute_allocation returns, i.e. before the first band is parsed
-            i16 offsets[NBANDS][OG_PL_LANES]; // (the bands' caps are computed where they are used: celt_band_cap)
+            // (the bands' caps are computed where they are used: celt_band_cap; their dynalloc boosts rest as counts in fine_quant)
             // One word per band: the two allocation vectors' entries (bits1 | bits2 << 16) while compute_allocation interpolates
             // between them, then -- written over them band by band by the pass that settles the interpolation -- the band's bits
             // (32 bits: a frame whose budget went negative carries wrapped values here, as the reference does).  When the allocation
@@ -121,7 +122,6 @@ struct LaneArr {
     OG_MEMBER void energies_rest() const {
         for (int i = 0; i < 2 * NBANDS; i += 2)
             *reinterpret_cast<u32 *>(&rest[i]) = (u32)(u16)PL.u.bandE[i][OG_PCOL] | (u32)(u16)PL.u.bandE[i + 1][OG_PCOL] << 16;
-        for (int i = 0; i < NBANDS; i++) PL.u.al.offsets[i][OG_PCOL] = 0;
     }
     OG_MEMBER void energies_back() const {
         u32 w[NBANDS];
@@ -150,7 +150,17 @@ struct LaneArr {
     OG_MEMBER i8 &fine_quant(int i) const { return PL.fine_quant[i][OG_PCOL]; }
     OG_MEMBER FinePrioView fine_prio(int i) const { return FinePrioView{&PL.tf_prio[i][OG_PCOL]}; }
     OG_MEMBER TfResView tf_res(int i) const { return TfResView{&PL.tf_prio[i][OG_PCOL]}; }
-    OG_MEMBER i16 &offsets(int i) const { return PL.u.al.offsets[i][OG_PCOL]; }
+    // A band's dynalloc boost is a whole number of the band's quanta, at most 66 of them (dynalloc_quanta), and nothing reads
+    // fine_quant between the boosts and the end of compute_allocation, whose last loop writes it after the last boost was read:
+    // the count rests in that byte (zero from celt_parse_lane for the bands a frame does not code) and the bits are a multiply
+    // away.  An i16 array of the boosts took 2.7 KB of a 64-frame wave's LDS: the workgroup's 20 granules are 16 without it.
+    OG_MEMBER void boost_put(int i, int n, int) const {
+#ifdef OG_HOST_EMUL
+        if (n < 0 || n > 127) __builtin_trap();
+#endif
+        PL.fine_quant[i][OG_PCOL] = (i8)n;
+    }
+    OG_MEMBER i32 boost(int i, int C, int LM) const { return (i32)PL.fine_quant[i][OG_PCOL] * dynalloc_quanta<RomLds>(i, LM, C); }
     OG_MEMBER u16a &bits1(int i) const { return reinterpret_cast<u16a *>(&PL.u.al.bw[i][OG_PCOL])[0]; }
     OG_MEMBER u16a &bits2(int i) const { return reinterpret_cast<u16a *>(&PL.u.al.bw[i][OG_PCOL])[1]; }
     OG_MEMBER i16 &bandE(int i) const { return PL.u.bandE[i][OG_PCOL]; }
@@ -579,7 +589,7 @@ OG_DEV void celt_parse_lane(StreamState *st, const u8 *payload, int len, int ch,
     for (int i = 0; i < 2 * NBANDS; i++) a.bandE(i) = st->celt.bandE[i];
     if (C == 1)
         for (int i = 0; i < NBANDS; i++) a.bandE(i) = (i16)OG_MAX((i32)a.bandE(i), (i32)a.bandE(NBANDS + i));
-    for (int i = 0; i < NBANDS; i++) { // (the dynalloc offsets are cleared where the energies make room for them: energies_rest;
+    for (int i = 0; i < NBANDS; i++) { // (this also clears the dynalloc boosts, which rest in fine_quant: LaneArr::boost;
                                        // the bits per band outside start .. end where they leave the allocation scratch: pulses_rest)
         a.fine_quant(i) = 0;
         a.fine_prio(i) = 0;

@@ -16,7 +16,15 @@ enum { PARSE_ALL = 0, PARSE_CELT_ONLY = 1, PARSE_HYBRID_ONLY = 2 };
 #ifndef OG_PARSE_WAVES_PER_SIMD
 #define OG_PARSE_WAVES_PER_SIMD 2 // (the register budget the compiler works to: 512 / this)
 #endif
-__global__ void __attribute__((amdgpu_waves_per_eu(OG_PARSE_WAVES_PER_SIMD, 8))) __launch_bounds__(64 * OG_PL_WAVES) OG_PARSE_KERNEL_NAME(const FrameDesc *__restrict__ descs, const u8 *__restrict__ arena,
+// OG_PARSE_NUM_VGPR: a register budget between two steps of the waves-per-SIMD ladder.  On this target the attribute counts in
+// PAIRS (the compiler doubles it: the unified file of 512 holds vector and accumulation registers) and is dropped without a word
+// when the doubled value is above what the waves-per-SIMD attribute allows -- amdgpu_num_vgpr(152) changed nothing, 76 gives 152.
+#ifdef OG_PARSE_NUM_VGPR
+#define OG_PARSE_VGPR_ATTR __attribute__((amdgpu_num_vgpr(OG_PARSE_NUM_VGPR / 2)))
+#else
+#define OG_PARSE_VGPR_ATTR
+#endif
+__global__ void OG_PARSE_VGPR_ATTR __attribute__((amdgpu_waves_per_eu(OG_PARSE_WAVES_PER_SIMD, 8))) __launch_bounds__(64 * OG_PL_WAVES) OG_PARSE_KERNEL_NAME(const FrameDesc *__restrict__ descs, const u8 *__restrict__ arena,
                                                       StreamState *st, ParseRec *recs, int n, int n_streams,
                                                       const SilkHandoff *handoff, int which, int groups, u32 *started) {
     // `groups`: a workgroup parses that many groups of OG_PL_FRAMES frames one after the other (1: the grid covers the step once)
