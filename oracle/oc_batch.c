@@ -123,9 +123,11 @@ int oc_taps_enable(oc_decoder *d) {
 }
 /* what: 0 = X (i16[1920]), 1 = bandE (i16[42]), 2 = syn_pre ch c (i32[1080]), 3 = syn_post ch c (i32[960]),
  * 4 = the frame's header as i32[75]: {is_transient, silence, coded_bands, intensity, dual_stereo, spread, LM, pf_pitch, pf_gain,
- * pf_tapset, anti_collapse_on, rng after the frame} then pulses[21], fine_quant[21], tf_res[21] */
-int oc_taps_copy(const oc_decoder *d, int what, int c, void *dst) {
-    const oc_celt_taps *t = d->taps;
+ * pf_tapset, anti_collapse_on, rng after the frame} then pulses[21], fine_quant[21], tf_res[21],
+ * 5 = what frame it was as i32[8]: {start, end, frame_size, stream_channels, channels, kind (OC_TAP_*), resets_before, 0} (the last
+ * two are the log's: 0 in oc_taps_copy).  X holds channel c's frame_size coefficients at c * frame_size; of syn_pre the first
+ * frame_size + 120 entries and of syn_post the first frame_size entries are the frame's. */
+static int taps_copy(const oc_celt_taps *t, int what, int c, void *dst) {
     if (!t || !t->valid) return -1;
     switch (what) {
         case 4: {
@@ -137,12 +139,40 @@ int oc_taps_copy(const oc_decoder *d, int what, int c, void *dst) {
             memcpy(dst, v, sizeof(v));
             return (int)sizeof(v);
         }
+        case 5: {
+            i32 v[8] = {t->start, t->end, t->frame_size, t->stream_channels, t->channels, t->kind, t->resets_before, 0};
+            memcpy(dst, v, sizeof(v));
+            return (int)sizeof(v);
+        }
         case 0: memcpy(dst, t->X, sizeof(t->X)); return (int)sizeof(t->X);
         case 1: memcpy(dst, t->bandE, sizeof(t->bandE)); return (int)sizeof(t->bandE);
         case 2: memcpy(dst, t->syn_pre[c], sizeof(t->syn_pre[c])); return (int)sizeof(t->syn_pre[c]);
         case 3: memcpy(dst, t->syn_post[c], sizeof(t->syn_post[c])); return (int)sizeof(t->syn_post[c]);
     }
     return -1;
+}
+int oc_taps_copy(const oc_decoder *d, int what, int c, void *dst) { return taps_copy(d->taps, what, c, dst); }
+
+/* The tap LOG: one record per CELT frame the decoder runs from here on, in decoding order -- every frame of a multi-frame packet,
+ * hybrid's CELT layers, and the frames no TOC names (OC_TAP_Q4 / _FADE / _REDUNDANT).  Room for `cap` records; the caller reads
+ * them with oc_taps_log_copy (`what` as in oc_taps_copy) and empties the log with oc_taps_log_clear, typically once a packet.
+ * A frame that finds the log full is counted in oc_taps_log_dropped and not recorded.  Decoding is untouched. */
+int oc_taps_log_enable(oc_decoder *d, int cap) {
+    if (cap < 1 || !oc_taps_enable(d)) return 0;
+    if (!d->log || d->log_cap != cap) {
+        free(d->log);
+        d->log = (oc_celt_taps *)calloc((size_t)cap, sizeof(oc_celt_taps));
+        d->log_cap = d->log ? cap : 0;
+    }
+    d->log_n = d->log_dropped = d->log_resets = 0;
+    return d->log != NULL;
+}
+int oc_taps_log_count(const oc_decoder *d) { return d->log_n; }
+int oc_taps_log_dropped(const oc_decoder *d) { return d->log_dropped; }
+void oc_taps_log_clear(oc_decoder *d) { d->log_n = 0; }
+int oc_taps_log_copy(const oc_decoder *d, int index, int what, int c, void *dst) {
+    if (!d->log || index < 0 || index >= d->log_n) return -1;
+    return taps_copy(&d->log[index], what, c, dst);
 }
 
 /* TEST ENTRY: the mode of the last frame (0 before the first one): what a concealment would run in */

@@ -1204,6 +1204,7 @@ int oc_celt_decode(oc_celt *st, oc_rc *rc, i16 *pcm, int frame_size, oc_celt_tap
         taps->intensity = intensity; taps->dual_stereo = dual_stereo; taps->spread = spread; taps->LM = LM;
         taps->pf_pitch = pf_pitch; taps->pf_gain = pf_gain; taps->pf_tapset = pf_tapset;
         taps->anti_collapse_on = anti_collapse_on;
+        taps->start = start; taps->end = end; taps->frame_size = N; taps->stream_channels = C; taps->channels = CC;
         memcpy(taps->pulses, pulses, sizeof(pulses));
         memcpy(taps->fine_quant, fine_quant, sizeof(fine_quant));
         memcpy(taps->tf_res, tf_res, sizeof(tf_res));

@@ -101,7 +101,15 @@ typedef struct {
     i32 syn_pre[2][960 + OC_OVERLAP];  /* IMDCT output before the comb filter */
     i32 syn_post[2][960];  /* after the comb filter */
     u32 rc_rng_end;
+    /* what a model of the synthesis chain needs beside X, bandE and the header (tests/celt_model.py) */
+    i32 start, end, frame_size, stream_channels, channels;
+    i32 kind;              /* log records only: OC_TAP_MAIN .. OC_TAP_REDUNDANT */
+    i32 resets_before;     /* log records only: oc_celt_reset calls since the record before */
 } oc_celt_taps;
+#define OC_TAP_MAIN 0      /* the frame the TOC names (CELT-only, or hybrid's CELT layer) */
+#define OC_TAP_Q4 1        /* reference mode: the 120-sample frame off the stale coder at hybrid -> SILK-only (Q4) */
+#define OC_TAP_FADE 2      /* RFC mode: the silence frame that fades the MDCT out at hybrid -> SILK-only */
+#define OC_TAP_REDUNDANT 3 /* RFC mode: a redundant 5 ms frame of a mode transition */
 
 void oc_celt_init(oc_celt *st, int channels);           /* celt_decoder_init  celt.cpp:1933 */
 void oc_celt_reset(oc_celt *st);                        /* OPUS_RESET_STATE   celt.cpp:2479 (partial, Q5) */
@@ -149,6 +157,8 @@ typedef struct oc_decoder {
     oc_celt celt;
     oc_silk *silk;         /* allocated by oc_decoder_create */
     oc_celt_taps *taps;    /* optional */
+    oc_celt_taps *log;     /* optional (oc_taps_log_enable): one record per CELT frame decoded, internal frames included */
+    i32 log_n, log_cap, log_dropped, log_resets;
 } oc_decoder;
 
 oc_decoder *oc_decoder_create(int channels);             /* fresh state == opus_multistream_decoder_init */

@@ -153,12 +153,14 @@ void oc_decoder_set_rfc(oc_decoder *d, int on) { d->rfc = on ? 1 : 0; }
 
 void oc_decoder_init(oc_decoder *d, int channels) { /* opus_decoder.cpp:82 */
     oc_silk *silk = d->silk;
-    oc_celt_taps *taps = d->taps;
-    const i32 rfc = d->rfc;
+    oc_celt_taps *taps = d->taps, *log = d->log;
+    const i32 rfc = d->rfc, log_cap = d->log_cap;
     memset(d, 0, sizeof(*d));
     d->rfc = rfc;
     d->silk = silk;
     d->taps = taps;
+    d->log = log;
+    d->log_cap = log_cap;
     d->channels = d->stream_channels = channels;
     oc_silk_init(d->silk);
     oc_celt_init(&d->celt, channels);
@@ -200,7 +202,40 @@ oc_decoder *oc_decoder_create(int channels) {
 void oc_decoder_destroy(oc_decoder *d) {
     if (!d) return;
     free(d->silk);
+    free(d->taps);
+    free(d->log);
     free(d);
+}
+
+/* the tap log (oc_taps_log_enable): where the next CELT frame's taps go, or NULL; and the record's commit once the frame has run */
+static oc_celt_taps *log_next(oc_decoder *d) {
+    oc_celt_taps *t;
+    if (!d->log) return NULL;
+    if (d->log_n >= d->log_cap) {
+        d->log_dropped++;
+        return NULL;
+    }
+    t = &d->log[d->log_n];
+    t->valid = 0;
+    return t;
+}
+static void log_commit(oc_decoder *d, const oc_celt_taps *src, int kind) {
+    oc_celt_taps *t;
+    if (!d->log || !src || !src->valid) return;
+    if (d->log_n >= d->log_cap) { /* (only the frame the TOC names gets here with the log full: it has taps of its own) */
+        d->log_dropped++;
+        return;
+    }
+    t = &d->log[d->log_n];
+    if (src != t) memcpy(t, src, sizeof(*t));
+    t->kind = kind;
+    t->resets_before = d->log_resets;
+    d->log_resets = 0;
+    d->log_n++;
+}
+static void celt_reset_logged(oc_decoder *d) {
+    oc_celt_reset(&d->celt);
+    d->log_resets++;
 }
 
 /* RFC mode: CELT's last band by audio bandwidth (RFC 6716 section 4.3: NB 13, WB 17, SWB 19, FB 21 bands; the CELT-only
@@ -354,17 +389,25 @@ static int decode_frame(oc_decoder *d, const u8 *inbuf, i32 len, i16 *out, int f
         oc_rc rr;
         d->celt.start_band = 0;
         oc_rc_init(&rr, inbuf + len, redundancy_bytes);
-        (void)oc_celt_decode(&d->celt, &rr, redundant_audio, 240, NULL);
+        {
+            oc_celt_taps *t = log_next(d);
+            (void)oc_celt_decode(&d->celt, &rr, redundant_audio, 240, t);
+            log_commit(d, t, OC_TAP_REDUNDANT);
+        }
         redundant_rng = d->celt.rng;
     }
     d->celt.start_band = start_band;
 
     if (mode != OC_MODE_SILK) {
-        if (mode != d->prev_mode && d->prev_mode > 0 && !d->prev_redundancy) oc_celt_reset(&d->celt);
+        if (mode != d->prev_mode && d->prev_mode > 0 && !d->prev_redundancy) celt_reset_logged(d);
         if (fec || celt_lost)
             celt_ret = oc_celt_decode_lost(&d->celt, out, audiosize);
-        else
-            celt_ret = oc_celt_decode(&d->celt, rc, out, audiosize, d->taps); /* (CELT frames are 2.5 - 20 ms) */
+        else {
+            oc_celt_taps *t = d->taps ? d->taps : log_next(d);
+            if (d->log && t) t->valid = 0; /* (with the log on, a refused frame leaves no record and no stale taps) */
+            celt_ret = oc_celt_decode(&d->celt, rc, out, audiosize, t); /* (CELT frames are 2.5 - 20 ms) */
+            log_commit(d, t, OC_TAP_MAIN);
+        }
     } else {
         for (i = 0; i < nmix; i++) out[i] = 0;
         if (d->prev_mode == OC_MODE_HYBRID && !(redundancy && celt_to_silk && d->prev_redundancy)) {
@@ -372,10 +415,15 @@ static int decode_frame(oc_decoder *d, const u8 *inbuf, i32 len, i16 *out, int f
             if (d->rfc) { /* RFC 6716 section 4.5.2: let the MDCT fade out by decoding a silence frame */
                 static const u8 silence[2] = {0xFF, 0xFF};
                 oc_rc rs;
+                oc_celt_taps *t = log_next(d);
                 oc_rc_init(&rs, silence, 2);
-                (void)oc_celt_decode(&d->celt, &rs, out, 120, NULL);
-            } else /* Q4: the reference runs the 2.5 ms frame off the coder SILK has just used */
-                (void)oc_celt_decode(&d->celt, rc, out, 120, NULL);
+                (void)oc_celt_decode(&d->celt, &rs, out, 120, t);
+                log_commit(d, t, OC_TAP_FADE);
+            } else { /* Q4: the reference runs the 2.5 ms frame off the coder SILK has just used */
+                oc_celt_taps *t = log_next(d);
+                (void)oc_celt_decode(&d->celt, rc, out, 120, t);
+                log_commit(d, t, OC_TAP_Q4);
+            }
         }
     }
     if (mode != OC_MODE_CELT)
@@ -385,10 +433,12 @@ static int decode_frame(oc_decoder *d, const u8 *inbuf, i32 len, i16 *out, int f
         i16 *a, *b, *o;
         if (!celt_to_silk) { /* SILK -> CELT: the redundant frame starts a fresh CELT state; its second half fades in at the end */
             oc_rc rr;
-            oc_celt_reset(&d->celt);
+            oc_celt_taps *t = log_next(d);
+            celt_reset_logged(d);
             d->celt.start_band = 0;
             oc_rc_init(&rr, inbuf + len, redundancy_bytes);
-            (void)oc_celt_decode(&d->celt, &rr, redundant_audio, 240, NULL);
+            (void)oc_celt_decode(&d->celt, &rr, redundant_audio, 240, t);
+            log_commit(d, t, OC_TAP_REDUNDANT);
             redundant_rng = d->celt.rng;
             a = out + CC * (audiosize - 120);
             b = redundant_audio + CC * 120;
