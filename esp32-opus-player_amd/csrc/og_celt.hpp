@@ -12,6 +12,7 @@
 // read, 960 new history samples + tail + ~300 B of scalars written, per channel.
 #pragma once
 #include "og_celt_bands.hpp"
+#include "og_celt_packed.hpp"
 
 namespace og {
 
@@ -1703,8 +1704,15 @@ OG_DEV void celt_synthesis(CeltState *st, const CeltSynth &p) {
         OG_SYNC();
         // history ring and overlap tail
         OG_MARK(16);
+#if defined(OG_RECON_TIGHT) && !defined(OG_HOST_EMUL)
+        pk_ring_tail_store(st->ring[c], st->tail[c], SY, pos, N); // (16 bytes per lane and store: og_celt_packed.hpp)
+#else
+        OG_STAT(61, (pos & 7) != 0);                // ring writes whose head is no multiple of 8 samples
+        OG_STAT(62, pos + N > RING);                // ring writes that wrap
+        OG_STAT(63, 1);                             // ring writes
         OG_FOR_LANES(i, N) st->ring[c][(pos + i) & RING_MASK] = SY[i];
         OG_FOR_LANES(i, OVERLAP / 2) st->tail[c][i] = SY[N + i];
+#endif
     }
     OG_SYNC();
     if (OG_LANE == 0 && p.lost) {

@@ -83,6 +83,9 @@ OG_DEV void haar8(V8 &r) { // the Haar step of stride S_ (1, 2, 4) inside one gr
         if (!(i & S_)) haar_pair(r.v[i], r.v[i + S_]);
 }
 
+template <bool PACKED> struct PmHold { typedef V8 type; }; // a group held between the gather's reads and its writes
+template <> struct PmHold<true> { typedef W4 type; };
+
 struct PmGrp { int band, job, x, gj, N; u32 jd; };
 constexpr int PM_GROUPS = 100; // coded groups of 8 per channel (eband5ms[21] = 100)
 OG_DEV PmGrp pm_group(int g) { // group g of the coded spectrum: 0..99 first channel, 100..199 second
@@ -196,10 +199,14 @@ OG_DEV u32 pm_setup_jobs(const ParseRec *rec, int C, int B, u32 &fill_lo, u32 &f
 }
 
 // C: undo the time-frequency changes of every job without fill leaves, a lane per group of 8 coefficients.
+// (PACKED: the group stays four packed words from its read to its write -- the gather by rows, the butterflies as dot products,
+// og_celt_packed.hpp; what the device runs in the tight layout.  The host emulation runs the general forms.)
+template <bool PACKED = PM_PACKED>
 OG_DEV void pm_tf_undo(u32 tfm) {
     constexpr int NG = (2 * PM_GROUPS + OG_NLANES - 1) / OG_NLANES;
+    typedef typename PmHold<PACKED>::type Hold;
     if (tfm & 1u) { // interleave_hadamard celt.cpp:1183 as a gather: all groups read, then all write
-        V8 hold[NG];
+        Hold hold[NG];
         u8 mark[NG];
 #pragma unroll
         for (int it = 0; it < NG; it++) {
@@ -210,10 +217,14 @@ OG_DEV void pm_tf_undo(u32 tfm) {
                 const int ls = (int)(q.jd >> JD_PERM_SHIFT) & 7;
                 if ((q.jd & JD_VALID) && !(q.jd & JD_FILL) && ls) {
                     const int stride = 1 << ls, n0 = q.N >> ls, had = (q.jd & JD_HAD) != 0;
+                    if constexpr (PACKED)
+                        hold[it] = pk_gather(&S.v[q.x], q.N, q.gj, ls, had);
+                    else {
 #pragma unroll
-                    for (int k = 0; k < 8; k++) {
-                        const int inter = 8 * q.gj + k, j = inter >> ls, i = inter & (stride - 1);
-                        hold[it].v[k] = S.v[q.x + (had ? ordery(stride, i) : i) * n0 + j];
+                        for (int k = 0; k < 8; k++) {
+                            const int inter = 8 * q.gj + k, j = inter >> ls, i = inter & (stride - 1);
+                            hold[it].v[k] = S.v[q.x + (had ? ordery(stride, i) : i) * n0 + j];
+                        }
                     }
                     mark[it] = 1;
                 }
@@ -225,7 +236,8 @@ OG_DEV void pm_tf_undo(u32 tfm) {
             const int g = OG_LANE + it * OG_NLANES;
             if (mark[it]) {
                 const PmGrp q = pm_group(g);
-                st8(q.x + 8 * q.gj, hold[it]);
+                if constexpr (PACKED) stw4(&S.v[q.x + 8 * q.gj], hold[it]);
+                else st8(q.x + 8 * q.gj, hold[it]);
             }
         }
         OG_LSYNC();
@@ -237,11 +249,18 @@ OG_DEV void pm_tf_undo(u32 tfm) {
             if (g < 2 * PM_GROUPS) {
                 const PmGrp q = pm_group(g);
                 if ((q.jd & JD_VALID) && !(q.jd & JD_FILL) && ((q.jd >> JD_STEP_SHIFT) & 15) == 4 && !(q.gj & 1)) {
-                    V8 a = ld8(q.x + 8 * q.gj), b = ld8(q.x + 8 * q.gj + 8);
+                    if constexpr (PACKED) {
+                        W4 a = ldw4(&S.v[q.x + 8 * q.gj]), b = ldw4(&S.v[q.x + 8 * q.gj + 8]);
+                        pk_haar16(a, b);
+                        stw4(&S.v[q.x + 8 * q.gj], a);
+                        stw4(&S.v[q.x + 8 * q.gj + 8], b);
+                    } else {
+                        V8 a = ld8(q.x + 8 * q.gj), b = ld8(q.x + 8 * q.gj + 8);
 #pragma unroll
-                    for (int k = 0; k < 8; k++) haar_pair(a.v[k], b.v[k]);
-                    st8(q.x + 8 * q.gj, a);
-                    st8(q.x + 8 * q.gj + 8, b);
+                        for (int k = 0; k < 8; k++) haar_pair(a.v[k], b.v[k]);
+                        st8(q.x + 8 * q.gj, a);
+                        st8(q.x + 8 * q.gj + 8, b);
+                    }
                 }
             }
         }
@@ -255,14 +274,25 @@ OG_DEV void pm_tf_undo(u32 tfm) {
                 const PmGrp q = pm_group(g);
                 const u32 steps = (q.jd & JD_VALID) && !(q.jd & JD_FILL) ? (q.jd >> JD_STEP_SHIFT) & 0xfffu : 0u;
                 if (steps & 0x777u) { // (a step of stride 8 has code 4: bit 3 of its nibble only)
-                    V8 r = ld8(q.x + 8 * q.gj);
-                    for (int k = 0; k < 3; k++) {
-                        const int c = (int)(steps >> (4 * k)) & 15;
-                        if (c == 1) haar8<1>(r);
-                        else if (c == 2) haar8<2>(r);
-                        else if (c == 3) haar8<4>(r);
+                    if constexpr (PACKED) {
+                        W4 r = ldw4(&S.v[q.x + 8 * q.gj]);
+                        for (int k = 0; k < 3; k++) {
+                            const int c = (int)(steps >> (4 * k)) & 15;
+                            if (c == 1) pk_haar8_1(r);
+                            else if (c == 2) pk_haar8_2(r);
+                            else if (c == 3) pk_haar8_4(r);
+                        }
+                        stw4(&S.v[q.x + 8 * q.gj], r);
+                    } else {
+                        V8 r = ld8(q.x + 8 * q.gj);
+                        for (int k = 0; k < 3; k++) {
+                            const int c = (int)(steps >> (4 * k)) & 15;
+                            if (c == 1) haar8<1>(r);
+                            else if (c == 2) haar8<2>(r);
+                            else if (c == 3) haar8<4>(r);
+                        }
+                        st8(q.x + 8 * q.gj, r);
                     }
-                    st8(q.x + 8 * q.gj, r);
                 }
             }
         }
@@ -371,6 +401,8 @@ OG_DEV void pm_fill_jobs(const u32 *words, const LcgTab &lcg, u32 fill_lo, u32 f
 }
 
 // E: every stereo merge of the frame (stereo_merge celt.cpp:1113, the sign flip of celt.cpp:1731)
+// (PACKED: the sums and the apply pass on packed words, og_celt_packed.hpp; as for pm_tf_undo)
+template <bool PACKED = PM_PACKED>
 OG_DEV void pm_stereo_merge(int C) {
     PmLds &P = PM();
     if (C != 2) return;
@@ -381,12 +413,17 @@ OG_DEV void pm_stereo_merge(int C) {
     OG_FOR_LANES(g, PM_GROUPS) { // partial sums of a group of 8
         const int band = P.binband[g];
         if (P.bw0[band] & BW_STEREO) {
-            const V8 a = ld8(V_X + 8 * g), b = ld8(V_X + 960 + 8 * g);
+            OG_STAT(29, 1);                         // groups whose partial sums are taken
             i32 xp = 0, side = 0;
+            if constexpr (PACKED)
+                pk_merge_sums(ldw4(&S.v[V_X + 8 * g]), ldw4(&S.v[V_X + 960 + 8 * g]), xp, side);
+            else {
+                const V8 a = ld8(V_X + 8 * g), b = ld8(V_X + 960 + 8 * g);
 #pragma unroll
-            for (int k = 0; k < 8; k++) {
-                xp += mul16(b.v[k], a.v[k]);
-                side += mul16(b.v[k], b.v[k]);
+                for (int k = 0; k < 8; k++) {
+                    xp += mul16(b.v[k], a.v[k]);
+                    side += mul16(b.v[k], b.v[k]);
+                }
             }
             pm_part()[g][0] = xp;
             pm_part()[g][1] = side;
@@ -433,23 +470,37 @@ OG_DEV void pm_stereo_merge(int C) {
             const u32 m1 = P.mpar[band][1];
             const i32 lgain = (i32)(i16)(m1 & 0xffff), rgain = (i32)m1 >> 16, mid = (i32)(i16)(P.bw2[band] & 0xffff);
             const int kl = (m0 >> 8) & 255, kr = (m0 >> 16) & 255;
-            V8 a = ld8(V_X + 8 * g), b = ld8(V_X + 960 + 8 * g);
-#pragma unroll
-            for (int k = 0; k < 8; k++) {
-                i32 xo, yo;
-                if (m0 & 2) {
-                    xo = a.v[k];
-                    yo = a.v[k];
-                } else {
-                    const i32 l = tr16(mul16_p15(mid, a.v[k])), r = b.v[k];
-                    xo = tr16(pshr32(mul16(lgain, sub16(l, r)), kl + 1));
-                    yo = tr16(pshr32(mul16(rgain, add16(l, r)), kr + 1));
+            OG_STAT(37, 1);                         // groups merged
+            OG_STAT(38, (m0 & 2) != 0);             // ... in the copy mode
+            if constexpr (PACKED) {
+                W4 a = ldw4(&S.v[V_X + 8 * g]), b;
+                if (m0 & 2)
+                    b = (m0 & 4) ? pk_neg(a) : a;
+                else {
+                    b = ldw4(&S.v[V_X + 960 + 8 * g]);
+                    pk_merge_apply(a, b, mid, lgain, rgain, kl, kr, (m0 & 4) != 0);
+                    stw4(&S.v[V_X + 8 * g], a);
                 }
-                a.v[k] = xo;
-                b.v[k] = (m0 & 4) ? tr16(-yo) : yo;
+                stw4(&S.v[V_X + 960 + 8 * g], b);
+            } else {
+                V8 a = ld8(V_X + 8 * g), b = ld8(V_X + 960 + 8 * g);
+#pragma unroll
+                for (int k = 0; k < 8; k++) {
+                    i32 xo, yo;
+                    if (m0 & 2) {
+                        xo = a.v[k];
+                        yo = a.v[k];
+                    } else {
+                        const i32 l = tr16(mul16_p15(mid, a.v[k])), r = b.v[k];
+                        xo = tr16(pshr32(mul16(lgain, sub16(l, r)), kl + 1));
+                        yo = tr16(pshr32(mul16(rgain, add16(l, r)), kr + 1));
+                    }
+                    a.v[k] = xo;
+                    b.v[k] = (m0 & 4) ? tr16(-yo) : yo;
+                }
+                if (!(m0 & 2)) st8(V_X + 8 * g, a);
+                st8(V_X + 960 + 8 * g, b);
             }
-            if (!(m0 & 2)) st8(V_X + 8 * g, a);
-            st8(V_X + 960 + 8 * g, b);
         }
     }
     OG_LSYNC();
@@ -477,6 +528,28 @@ OG_DEV void recon_all_bands_pm(const ParseRec *rec, LcgTab &lcg, int C, int shor
         OG_STAT(34, n_fill_jobs == 1);
         OG_STAT(35, n_fill_jobs >= 4);
         OG_STAT(36, close_pair);                    // frames with two fill jobs less than a window apart
+    }
+    { // the parallel pass's work by class of job (tools/tf_undo_census.py): groups of 8 coefficients
+        OG_STAT(25, (tfm & (1u << 4)) != 0);        // frames that run the pass over pairs of groups (a first Haar step of stride 8)
+        OG_STAT(28, (tfm & 0x0eeeu) != 0);          // frames that run the pass of Haar steps inside a group
+        for (int l = 0; l < 2 * NBANDS; l++) {
+            const u32 jd = PM().jdesc[l];
+            const int groups = (int)((PM().bw1[l >> 1] >> 22) & 255) / 8;
+            if (!(jd & JD_VALID) || !(jd & ~(u32)(JD_VALID | JD_FILL))) continue; // no job, or a job without a change
+            if (jd & JD_FILL) {
+                OG_STAT(60, groups);                // groups of jobs with a change that phase D undoes (fill jobs)
+                continue;
+            }
+            const u32 steps = (jd >> JD_STEP_SHIFT) & 0xfffu; // (step k in nibble k)
+            const int ls = (int)(jd >> JD_PERM_SHIFT) & 7, had = (jd & JD_HAD) != 0;
+            OG_STAT(ls == 2 && had && steps == 0x012u ? 39   // long block: stride 4 ordered, steps (2, 1)
+                    : ls == 3 && had && steps == 0x123u ? 43 // long block: stride 8 ordered, steps (3, 2, 1)
+                    : ls == 0 && steps == 0x321u ? 47        // transient: no interleave, steps (1, 2, 3)
+                    : ls == 3 && !had && steps == 0x001u ? 48 // transient: stride 8, step (1)
+                    : ls == 3 && !had && steps == 0u ? 49    // transient: stride 8, no step
+                    : ls == 4 && !had && steps == 0x004u ? 54 // transient: stride 16, the step over pairs of groups
+                    : 55, groups);                  // anything else
+        }
     }
 #endif
     OG_STAT(0, 1);                                  // frames
