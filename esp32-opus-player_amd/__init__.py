@@ -48,6 +48,8 @@ EXPORTS = [
     "opusgpu_ms_files_decode_ratio",
     "opusgpu_spec_basis", "opusgpu_spec_filterbank", "opusgpu_spec_layout", "opusgpu_tracks_melspec_device", "opusgpu_files_decode_melspec",
     "opusgpu_ms_files_decode_melspec",
+    "opusgpu_fbank_window", "opusgpu_fbank_filterbank", "opusgpu_fbank_dct", "opusgpu_fbank_layout", "opusgpu_tracks_fbank_device",
+    "opusgpu_files_decode_fbank", "opusgpu_ms_files_decode_fbank",
     "opusgpu_loudness_weights", "opusgpu_loudness_gain", "opusgpu_tracks_loudness_device", "opusgpu_set_loudness", "opusgpu_last_loudness",
     "opusgpu_ms_set_loudness", "opusgpu_ms_last_loudness",
 ]
@@ -147,6 +149,14 @@ SPEC_SCALES = {"slaney": 0, "htk": 1}
 SPEC_NORMS = {"slaney": 0, None: 1, "none": 1}
 SPEC_LOGS = {None: 0, "none": 0, "log10": 1, "ln": 2}
 SPEC_FRAMES = {"torch": 0, "whisper": 1}
+# opusgpu_fbank_params and its enums (include/opusgpu.h, TRACK KALDI FEATURES)
+FBANK_PARAMS_DTYPE = np.dtype([("sample_rate", "<i4"), ("frame_length", "<i4"), ("frame_shift", "<i4"), ("n_fft", "<i4"), ("n_mels", "<i4"),
+                               ("n_ceps", "<i4"), ("window", "<i4"), ("snip_edges", "u1"), ("remove_dc", "u1"), ("power", "u1"), ("log", "u1"),
+                               ("layout", "<i4"), ("preemphasis", "<f4"), ("low_freq", "<f4"), ("high_freq", "<f4"), ("floor", "<f4"),
+                               ("cepstral_lifter", "<f4"), ("reserved", "<i4", (2,))])
+FBANK_WINDOWS = {"povey": 0, "hanning": 1, "hamming": 2, "rectangular": 3, "blackman": 4}
+FBANK_LOG_NONE, FBANK_LOG_LN = 0, 1
+FBANK_FLOOR = 1.1920929e-07  # FLT_EPSILON, Kaldi's floor under the log
 # opusgpu_loudness_span / opusgpu_loudness / opusgpu_loudness_req and the request's modes (include/opusgpu.h, TRACK LOUDNESS)
 LOUDNESS_SPAN_DTYPE = np.dtype([("in_offset", "<i8"), ("in_samples", "<i8")])
 LOUDNESS_DTYPE = np.dtype([("lufs", "<f4"), ("peak", "<f4"), ("blocks", "<i4"), ("gated", "<i4")])
@@ -292,6 +302,14 @@ def load_lib():
     lib.opusgpu_tracks_melspec_device.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
     lib.opusgpu_files_decode_melspec.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.opusgpu_ms_files_decode_melspec.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.opusgpu_fbank_window.argtypes = [vp, C.POINTER(vp)]
+    lib.opusgpu_fbank_filterbank.argtypes = [vp, C.POINTER(vp)]
+    lib.opusgpu_fbank_dct.argtypes = [vp, C.POINTER(vp)]
+    lib.opusgpu_fbank_layout.argtypes = [C.c_int, vp, C.c_int, C.c_int, vp, vp]
+    lib.opusgpu_fbank_layout.restype = C.c_int64
+    lib.opusgpu_tracks_fbank_device.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
+    lib.opusgpu_files_decode_fbank.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.opusgpu_ms_files_decode_fbank.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.opusgpu_loudness_weights.argtypes = [C.c_int, vp]
     lib.opusgpu_loudness_gain.argtypes = [vp, C.c_double, C.c_double]
     lib.opusgpu_loudness_gain.restype = C.c_double
@@ -944,7 +962,11 @@ def track_spectrogram_args(batch, features, rate=None, resample=None, mono=False
     is taken as the one or the other.  Raises ValueError for a record that breaks a rule, both rate= and resample=, a rate or ratio
     that does not exist or is not the record's sample_rate, and for what track_feature_args refuses of format, mono, mix, scale and
     out."""
-    rec = _spec_rec(features)
+    return _record_feature_args(batch, _spec_rec(features), spec_layout, rate, resample, mono, mix, format, scale, out, device, allow_mono)
+
+
+def _record_feature_args(batch, rec, layout, rate, resample, mono, mix, format, scale, out, device, allow_mono):
+    """track_spectrogram_args and track_kaldi_args behind their record checks: layout(planned, up, down, rec) is the record's grid."""
     sr = int(rec["sample_rate"][0])
     if rate is not None and resample is not None:
         raise ValueError("resample= and rate= exclude each other")
@@ -963,10 +985,177 @@ def track_spectrogram_args(batch, features, rate=None, resample=None, mono=False
         raise ValueError(f"features are float32: format must be absent or 'f32', not {format!r}")
     mrec = _channel_mix(batch, mono, mix, allow_mono, one=True)
     _, scale, _ = track_format_args(batch, "f32", scale, None, device)
-    offsets, planes, total = spec_layout(batch.info["track_samples"], up, down, rec)
+    offsets, planes, total = layout(batch.info["track_samples"], up, down, rec)
     if out is not None:
         out = _out_flat(out, max(total, 1), "f32", device)
     return rec, mrec, scale, offsets, planes, total, out, how
+
+
+def _kaldi_record(sample_rate, frame_length, frame_shift, num_mel_bins, low_freq, high_freq, preemphasis_coefficient, remove_dc_offset,
+                  window_type, round_to_power_of_two, snip_edges, use_power, use_log_fbank, feature_layout, n_ceps, cepstral_lifter, rejected):
+    import numbers
+    not_offered = {  # keyword -> (the values that change nothing, why no other is taken)
+        "dither": ((0,), "the features are a function of the track: there is no dither"),
+        "use_energy": ((False,), "the energy coefficient is not offered"),
+        "raw_energy": ((True,), "the energy coefficient is not offered"),
+        "energy_floor": ((0, 1), "the energy coefficient is not offered"),
+        "htk_compat": ((False,), "HTK's coefficient order is not offered"),
+        "vtln_warp": ((1,), "VTLN warping is not offered"),
+        "vtln_low": ((100,), "VTLN warping is not offered"),
+        "vtln_high": ((-500,), "VTLN warping is not offered"),
+        "subtract_mean": ((False,), "subtract_mean is one torch operation on the result"),
+        "blackman_coeff": ((0.42,), "the Blackman window's coefficient is 0.42"),
+        "channel": ((-1, 0), "the track is mono"),
+        "min_duration": ((0,), "every track has its F frames"),
+    }
+    for name, v in rejected.items():
+        if name not in not_offered:
+            raise TypeError(f"unexpected keyword argument {name!r}")
+        same, why = not_offered[name]
+        if not isinstance(v, numbers.Real) or v not in same:
+            raise ValueError(f"{name}={v!r}: {why}")
+
+    def number(name, v):
+        if not isinstance(v, numbers.Real) or isinstance(v, bool) or not np.isfinite(v):
+            raise ValueError(f"{name} must be a finite number, not {v!r}")
+        return float(v)
+
+    def flag(name, v):
+        if not isinstance(v, (bool, np.bool_)):
+            raise ValueError(f"{name} must be True or False, not {v!r}")
+        return int(v)
+    if not isinstance(sample_rate, numbers.Real) or isinstance(sample_rate, bool) or sample_rate != int(sample_rate):
+        raise ValueError(f"sample_rate must be a whole number of Hz, not {sample_rate!r}")
+    sr = int(sample_rate)
+    if not 1 <= sr <= 1048576:
+        raise ValueError(f"sample_rate must be in [1, 1048576], not {sr}")
+    L, H = int(sr * 0.001 * number("frame_length", frame_length)), int(sr * 0.001 * number("frame_shift", frame_shift))  # as Kaldi does
+    if not 2 <= L <= 2048:
+        raise ValueError(f"frame_length must come to 2 .. 2048 samples, not {L}")
+    if H < 1 or 31 * H + L > 32768:
+        raise ValueError(f"frame_shift must come to >= 1 sample with 31 * frame_shift + frame_length <= 32768 samples, not {H}")
+    N = 64
+    while N < L:
+        N *= 2
+    if not flag("round_to_power_of_two", round_to_power_of_two):
+        if L < 64 or L % 16:  # the frame itself is the FFT's length: taken where the kernel has that length
+            raise ValueError(f"round_to_power_of_two=False needs a frame_length that is a multiple of 16 and >= 64 samples, not {L}")
+        N = L
+    if not isinstance(num_mel_bins, numbers.Integral) or isinstance(num_mel_bins, bool) or not 3 <= num_mel_bins <= 128:
+        raise ValueError(f"num_mel_bins must be an int in [3, 128], not {num_mel_bins!r}")
+    if not isinstance(n_ceps, numbers.Integral) or isinstance(n_ceps, bool) or not 0 <= n_ceps <= num_mel_bins:
+        raise ValueError(f"num_ceps must be an int in [1, num_mel_bins], not {n_ceps!r}")
+    if not isinstance(window_type, str) or window_type not in FBANK_WINDOWS:
+        raise ValueError(f"window_type must be one of {sorted(FBANK_WINDOWS)}, not {window_type!r}")
+    if not isinstance(feature_layout, str) or feature_layout not in MEL_LAYOUTS:
+        raise ValueError(f"feature_layout must be one of {sorted(MEL_LAYOUTS)}, not {feature_layout!r}")
+    rec = np.zeros(1, dtype=FBANK_PARAMS_DTYPE)
+    rec["sample_rate"], rec["frame_length"], rec["frame_shift"], rec["n_fft"], rec["n_mels"], rec["n_ceps"] = sr, L, H, N, num_mel_bins, n_ceps
+    rec["window"], rec["snip_edges"], rec["remove_dc"] = FBANK_WINDOWS[window_type], flag("snip_edges", snip_edges), flag("remove_dc_offset", remove_dc_offset)
+    rec["power"], rec["log"] = 2 if flag("use_power", use_power) else 1, FBANK_LOG_LN if flag("use_log_fbank", use_log_fbank) else FBANK_LOG_NONE
+    rec["layout"], rec["floor"] = MEL_LAYOUTS[feature_layout], FBANK_FLOOR
+    rec["preemphasis"], rec["low_freq"], rec["high_freq"] = (number("preemphasis_coefficient", preemphasis_coefficient), number("low_freq", low_freq),
+                                                             number("high_freq", high_freq))
+    rec["cepstral_lifter"] = number("cepstral_lifter", cepstral_lifter)
+    if not 0 <= float(rec["preemphasis"][0]) <= 1:
+        raise ValueError(f"preemphasis_coefficient must be in [0, 1], not {preemphasis_coefficient!r}")
+    low, high = float(rec["low_freq"][0]), float(rec["high_freq"][0])
+    high = high if high > 0 else sr / 2 + high
+    if not 0 <= low < high <= sr / 2:
+        raise ValueError(f"0 <= low_freq < high_freq <= sample_rate / 2 must hold (high_freq <= 0 counts from there), not {low_freq!r}, {high_freq!r}")
+    if float(rec["cepstral_lifter"][0]) < 0:
+        raise ValueError(f"cepstral_lifter must be >= 0, not {cepstral_lifter!r}")
+    return rec
+
+
+def kaldi_fbank(sample_rate=16000, frame_length=25.0, frame_shift=10.0, num_mel_bins=23, low_freq=20.0, high_freq=0.0,
+                preemphasis_coefficient=0.97, remove_dc_offset=True, window_type="povey", round_to_power_of_two=True, snip_edges=True,
+                use_power=True, use_log_fbank=True, feature_layout="frames", **rejected):
+    """An opusgpu_fbank_params record (a FBANK_PARAMS_DTYPE array of one; include/opusgpu.h TRACK KALDI FEATURES) from the arguments
+    of Kaldi's compute-fbank-feats and torchaudio.compliance.kaldi.fbank, with their defaults.  frame_length and frame_shift are
+    milliseconds and become samples as Kaldi does, int(sample_rate * 0.001 * ms); the floor is FLT_EPSILON.  Raises ValueError, with
+    the reason, for what the record's rules refuse and for what is not offered: dither other than 0, use_energy=True, htk_compat=True,
+    a vtln_warp other than 1, subtract_mean=True, another blackman_coeff."""
+    return _kaldi_record(sample_rate, frame_length, frame_shift, num_mel_bins, low_freq, high_freq, preemphasis_coefficient, remove_dc_offset,
+                         window_type, round_to_power_of_two, snip_edges, use_power, use_log_fbank, feature_layout, 0, 0.0, rejected)
+
+
+def kaldi_mfcc(sample_rate=16000, frame_length=25.0, frame_shift=10.0, num_mel_bins=23, low_freq=20.0, high_freq=0.0,
+               preemphasis_coefficient=0.97, remove_dc_offset=True, window_type="povey", round_to_power_of_two=True, snip_edges=True,
+               use_power=True, feature_layout="frames", num_ceps=13, cepstral_lifter=22.0, **rejected):
+    """kaldi_fbank's record with n_ceps = num_ceps (1 .. num_mel_bins) and the lifter: Kaldi's compute-mfcc-feats and
+    torchaudio.compliance.kaldi.mfcc without the energy coefficient (use_energy=False)."""
+    import numbers
+    if not isinstance(num_ceps, numbers.Integral) or isinstance(num_ceps, bool) or num_ceps < 1:
+        raise ValueError(f"num_ceps must be an int in [1, num_mel_bins], not {num_ceps!r}")
+    return _kaldi_record(sample_rate, frame_length, frame_shift, num_mel_bins, low_freq, high_freq, preemphasis_coefficient, remove_dc_offset,
+                         window_type, round_to_power_of_two, snip_edges, use_power, True, feature_layout, num_ceps, cepstral_lifter, rejected)
+
+
+def _fbank_rec(rec):
+    if getattr(rec, "dtype", None) != FBANK_PARAMS_DTYPE or np.size(rec) != 1:
+        raise ValueError("Kaldi features' parameters are a kaldi_fbank() or kaldi_mfcc() record")
+    return np.ascontiguousarray(rec).reshape(1)
+
+
+def fbank_width(rec):
+    """The feature width of a kaldi_fbank / kaldi_mfcc record: n_ceps when it is > 0, else n_mels."""
+    rec = _fbank_rec(rec)
+    return int(rec["n_ceps"][0]) or int(rec["n_mels"][0])
+
+
+def fbank_window(rec):
+    """opusgpu_fbank_window: the window of a kaldi_fbank / kaldi_mfcc record -> float32 [frame_length]."""
+    rec = _fbank_rec(rec)
+    return _tables("opusgpu_fbank_window", C.c_float, (rec.ctypes.data,), 1, "opusgpu_fbank_window refused the record")[0]
+
+
+def fbank_filterbank(rec):
+    """opusgpu_fbank_filterbank: the filterbank of a kaldi_fbank / kaldi_mfcc record -> float32 [n_mels, n_fft / 2]."""
+    rec = _fbank_rec(rec)
+    bank = _tables("opusgpu_fbank_filterbank", C.c_float, (rec.ctypes.data,), 1, "opusgpu_fbank_filterbank refused the record")[0]
+    return bank.reshape(int(rec["n_mels"][0]), -1)
+
+
+def fbank_dct(rec):
+    """opusgpu_fbank_dct: the lifted DCT of a kaldi_mfcc record -> float32 [n_ceps, n_mels] ([0, n_mels] for a kaldi_fbank record)."""
+    rec = _fbank_rec(rec)
+    n = load_lib().opusgpu_fbank_dct(rec.ctypes.data, None)
+    if n < 0:
+        raise ValueError("opusgpu_fbank_dct refused the record")
+    n_mels = int(rec["n_mels"][0])
+    if n == 0:
+        return np.zeros((0, n_mels), dtype=np.float32)
+    return _tables("opusgpu_fbank_dct", C.c_float, (rec.ctypes.data,), 1, "opusgpu_fbank_dct refused the record")[0].reshape(-1, n_mels)
+
+
+def fbank_frames(rec, samples):
+    """F of TRACK KALDI FEATURES for tracks of `samples` samples at the record's rate."""
+    rec = _fbank_rec(rec)
+    n, L, H = np.asarray(samples, dtype=np.int64), int(rec["frame_length"][0]), int(rec["frame_shift"][0])
+    if int(rec["snip_edges"][0]):
+        return np.where(n < L, 0, 1 + (n - L) // H)
+    return (n + H // 2) // H
+
+
+def fbank_layout(planned_48k_samples, up, down, rec):
+    """opusgpu_fbank_layout: the grid of the Kaldi features of tracks at up / down of 48 kHz -> (feat_offsets [int64], planes [int64],
+    total floats)."""
+    rec = _fbank_rec(rec)
+    planned, offsets, total = _layout("opusgpu_fbank_layout", planned_48k_samples, (int(up), int(down), rec.ctypes.data),
+                                      f"the record, the ratio {up!r}/{down!r} or a negative length")
+    return offsets, (fbank_frames(rec, -(-planned * int(up) // int(down))) + 63) // 64 * 64, total
+
+
+def track_kaldi_args(batch, features, rate=None, resample=None, mono=False, mix=None, format=None, scale=None, out=None, device=0,
+                     allow_mono=True):
+    """track_spectrogram_args for a kaldi_fbank / kaldi_mfcc record as decode_files' features=: the same tuple, the same refusals,
+    with the record checked by the library (opusgpu_fbank_layout) and fbank_layout's grid.  scale= may also be one number for every
+    track: scale=1.0 is Kaldi's convention of samples in the int16 range."""
+    import numbers
+    if isinstance(scale, numbers.Real) and not isinstance(scale, bool):
+        scale = np.full(batch.n_files, scale, dtype=np.float32)
+    return _record_feature_args(batch, _fbank_rec(features), fbank_layout, rate, resample, mono, mix, format, scale, out, device, allow_mono)
 
 
 def loudness_weights(channels):
@@ -1060,6 +1249,11 @@ def files_request(batch, multistream=False, device=0, format=None, scale=None, o
         rec, mrec, scale, offsets, planes, total, out, how = sargs
         return FilesRequest("files_decode_melspec", how + mono_arg + (mrec, rec), "features", TRACKS_F32, scale, out, 1, offsets, planes, total,
                             mrec, rec)
+    if getattr(features, "dtype", None) == FBANK_PARAMS_DTYPE:
+        rec, mrec, scale, offsets, planes, total, out, how = track_kaldi_args(batch, features, rate, resample, mono, mix, format, scale, out,
+                                                                              device, allow_mono)
+        return FilesRequest("files_decode_fbank", how + mono_arg + (mrec, rec), "features", TRACKS_F32, scale, out, 1, offsets, planes, total,
+                            mrec, rec)
     if resample is not None:
         format = "s16" if format is None else format
         (up, down), ch, offsets, total, out, mrec = track_ratio_args(batch, resample, mono, mix, format, out, device, allow_mono, rate, features)
@@ -1150,7 +1344,7 @@ def _run_files_request(req, lib, prefix, handle, chk, batch, mem):
         assert (offsets == req.offsets).all()
         info[count_field], info[offset_field] = counts, offsets
     if req.kind == "features":
-        n_mels = int(req.params["n_mels"][0])
+        n_mels = fbank_width(req.params) if req.params.dtype == FBANK_PARAMS_DTYPE else int(req.params["n_mels"][0])
         if int(req.params["layout"][0]) == MEL_FRAMES_MAJOR:
             return [packed[o:o + F * n_mels].reshape(F, n_mels) for o, F in zip(offsets, counts)], info
         return [packed[o:o + n_mels * p].reshape(n_mels, p)[:, :F] for o, p, F in zip(offsets, req.planes, counts)], info
@@ -1361,6 +1555,14 @@ class Context:
         self._chk(self.lib.opusgpu_tracks_mel_device(self.h, spans.size, spans.ctypes.data, d_in, rec.ctypes.data, d_out, stream),
                   "opusgpu_tracks_mel_device")
 
+    def tracks_fbank_device(self, spans, d_in, rec, d_out, stream=None):
+        """k_tracks_fbank alone (include/opusgpu.h TRACK KALDI FEATURES): spans a HOST array of MEL_SPAN_DTYPE, d_in packed int16 mono
+        tracks at the record's rate, rec a kaldi_fbank / kaldi_mfcc record, d_out the float32 feature tracks.  Waits for the kernel."""
+        spans = np.ascontiguousarray(spans, dtype=MEL_SPAN_DTYPE)
+        rec = _fbank_rec(rec)
+        self._chk(self.lib.opusgpu_tracks_fbank_device(self.h, spans.size, spans.ctypes.data, d_in, rec.ctypes.data, d_out, stream),
+                  "opusgpu_tracks_fbank_device")
+
     def tracks_melspec_device(self, spans, d_in, rec, d_out, stream=None):
         """k_tracks_melspec alone (include/opusgpu.h TRACK SPECTROGRAMS): spans a HOST array of MEL_SPAN_DTYPE, d_in packed int16 mono
         tracks at the record's rate, rec a mel_spec record, d_out the float32 feature tracks.  Waits for the kernel."""
@@ -1421,6 +1623,9 @@ class Context:
         TRACK SPECTROGRAMS: n_fft, win_length, hop, n_mels, fmin / fmax, Slaney or HTK, power 1 or 2, log10 / ln / none and a floor
         are fields), with rate= or resample= naming that rate (or neither: the record's is taken), mono=True or a mix of one row,
         and scale=, out= and info as with "logmel"; n_mels= and feature_layout= are the record's (track_spectrogram_args).
+        features may also be a kaldi_fbank() or kaldi_mfcc() record: Kaldi's fbank or MFCC features of the mono track at the record's
+        sample_rate (include/opusgpu.h TRACK KALDI FEATURES), with the same keywords as for a mel_spec() record (track_kaldi_args);
+        scale=1.0 gives Kaldi's int16-range convention.  The result is [F, n_mels or n_ceps] ("frames", the record's default).
         loudness: None, or "measure" for the integrated loudness (ITU-R BS.1770-4) and sample peak of every track, measured on the
         GPU on the 48 kHz int16 track in the same call (include/opusgpu.h TRACK LOUDNESS) -- the result is what it is without it,
         and info gains `lufs` (-inf: no block passed the gates), `peak`, `loudness_blocks`, `loudness_gated` and `gain` (1.0) --, or
@@ -1615,7 +1820,7 @@ class MultistreamContext:
         for Context.decode_files, all channels at `rate`.  mix: as for Context.decode_files -- "mono" and "stereo" are the default
         downmix tables of the layout's channel count; there is no `mono` argument here.
         features, n_mels, feature_layout: as for Context.decode_files, with mix="mono" or a matrix of one row.
-        resample: as for Context.decode_files, all channels or those of the mix.  features may be a mel_spec() record as there.
+        resample: as for Context.decode_files, all channels or those of the mix.  features may be a mel_spec(), kaldi_fbank() or kaldi_mfcc() record as there.
         loudness, peak_limit, channel_weights: as for Context.decode_files; the default weights are those of the layout's channel
         count (1.41 for the rear pair, 0 for the LFE)."""
         own = batch is None

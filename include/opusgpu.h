@@ -951,6 +951,109 @@ int opusgpu_files_decode_melspec(opusgpu_ctx *ctx, const opusgpu_file_batch *bat
                                  const opusgpu_mix_matrix *mix, const opusgpu_spec_params *p, const float *scale, void *d_out,
                                  int64_t *feat_offsets, int64_t *frames_out, int64_t *track_lengths_out, int32_t *status_out);
 
+/* TRACK KALDI FEATURES.  Kaldi's compute-fbank-feats / compute-mfcc-feats (torchaudio.compliance.kaldi.fbank and .mfcc) of the mono
+ * track at any rate of TRACK RATES and TRACK RATIOS, in the same call that decodes the files: the front end of WeNet, k2 / icefall,
+ * ESPnet recipes and most speaker-verification stacks.  No setting of opusgpu_spec_params is this computation -- frames that are not
+ * centred, a mean and a pre-emphasis per frame, a symmetric window at the start of a zero-padded FFT, triangles that are linear in
+ * mel -- so it is a section of its own with a record, calls and a kernel of its own; TRACK FEATURES and TRACK SPECTROGRAMS are
+ * unchanged.  The definition is this comment.
+ *   INPUT.  An int16 mono track y[m], m in [0, n), exactly as TRACK RATES, TRACK RATIOS and CHANNEL MIX define it.
+ *   NOT OFFERED.  Dither (the features are a function of the track); use_energy, raw_energy and energy_floor; htk_compat; VTLN
+ *   warping; subtract_mean (one torch operation on the result).
+ *   FRAMES.  L = frame_length, H = frame_shift.  snip_edges 1: F = 0 for n < L, else 1 + (n - L) / H (floor); frame f starts at s =
+ *   f H: only whole windows inside the track.  snip_edges 0: F = (n + H / 2) / H; frame f starts at s = f H + H / 2 - L / 2 (integer
+ *   halves), and an index q outside [0, n) is mapped by q < 0 -> -q - 1 and q >= n -> 2 n - 1 - q, REPEATED until it lies inside:
+ *   Kaldi's rule, not torch.stft's; the repeats matter for n < L.
+ *   PER FRAME, with x_i = y[q(s + i)], i in [0, L), written over the reals:
+ *     1. remove_dc 1: m = (sum_i x_i) / L and d_i = x_i - m.  The sum is an exact integer and the kernel takes it as one: a constant
+ *        track gives d_i = 0 exactly.  remove_dc 0: d_i = x_i.
+ *     2. e_0 = d_0 - c d_0 and e_i = d_i - c d_{i-1} for i >= 1, c = preemphasis: the frame's first sample is its own predecessor.
+ *     3. t_i = e_i * scale[track] * w[i]; the scale rule of TRACK FORMATS, default 1 / 32768.  A scale of 1 is Kaldi's convention of
+ *        samples in the int16 range.
+ *     4. X[k] = sum_{i < L} t_i e^{-2 pi i k / N}, k in [0, N / 2), N = n_fft: the frame at the START of a zero-padded FFT of N
+ *        points.  The Nyquist bin takes no part.
+ *     5. S[k] = |X[k]|^2 (power 2) or |X[k]| (power 1).
+ *   WINDOW.  Symmetric, a = 2 pi i / (L - 1):  OPUSGPU_FBANK_HANNING 0.5 - 0.5 cos a;  _POVEY that to the power 0.85;  _HAMMING
+ *   0.54 - 0.46 cos a;  _BLACKMAN 0.42 - 0.5 cos a + 0.08 cos 2a;  _RECTANGULAR 1.  w[i] = w[L - 1 - i].
+ *   FILTERBANK.  bw = sample_rate / N, in double.  mel(f) = 1127 ln(1 + f / 700).  high = high_freq if > 0, else sample_rate / 2 +
+ *   high_freq.  m_lo = mel(low_freq), m_hi = mel(high), delta = (m_hi - m_lo) / (n_mels + 1).  Band j: left = m_lo + j delta, centre
+ *   = left + delta, right = centre + delta;  B[j][k] = max(0, min((mel(k bw) - left) / (centre - left), (right - mel(k bw)) / (right
+ *   - centre))) for k in [0, N / 2): triangles that are linear in MEL (torchaudio's and librosa's HTK banks are linear in Hz).  No
+ *   normalisation.  A band that no bin reaches is a row of zeros, as in Kaldi.
+ *   OUTPUT, fbank (n_ceps 0).  v = max(sum_k B[j][k] S[k], floor); v (OPUSGPU_FBANK_LOG_NONE) or logf(v) (OPUSGPU_FBANK_LOG_LN),
+ *   float32.  Kaldi's floor is FLT_EPSILON = 1.1920929e-07.
+ *   OUTPUT, MFCC (n_ceps in [1, n_mels]; log must be LN).  g_j = logf(v_j), then c_q = lift[q] * sum_j D[q][j] g_j for q in [0,
+ *   n_ceps):  D[0][j] = sqrt(1 / n_mels), D[q][j] = sqrt(2 / n_mels) cos(pi q (j + 0.5) / n_mels);  lift[q] = 1 + 0.5 Q sin(pi q /
+ *   Q), Q = cepstral_lifter (Kaldi's is 22), lift = 1 for Q = 0.  The feature width is n_ceps when it is > 0, else n_mels.
+ *   TABLES.  float32, each entry computed in double and rounded once, at first use, kept per distinct (sample_rate, frame_length,
+ *   n_fft, n_mels, n_ceps, window, low_freq, high_freq, cepstral_lifter) for the life of the process and safe to ask for from any
+ *   number of threads: w[L] (opusgpu_fbank_window), B[n_mels][N / 2] (opusgpu_fbank_filterbank), lift[q] D[q][j] as [n_ceps][n_mels]
+ *   (opusgpu_fbank_dct).  The basis that the kernel multiplies is its own business.
+ *   PRECISION and SUMMATION ORDER are not part of the contract, as in TRACK SPECTROGRAMS (the kernel turns the spectrum by e^{i pi k
+ *   (L - 1) / N}, which changes no magnitude, and folds t_i +- t_{L - 1 - i} against half a basis that carries w).  What is: the
+ *   tolerance of tests/test_gpu_tracks_fbank.py (8 x the error of a float32 restatement against float64), the
+ *   same bits from the same call on the same input -- no float atomics --, one bit pattern in every cell of an all-zero track, and
+ *   with remove_dc one bit pattern in every cell of any constant track: the floor's value (for MFCC one pattern per coefficient q,
+ *   the DCT of a row of logf(floor)).
+ *   LAYOUT.  TRACK FEATURES' grid with this F and the feature width: plane[t] = roundup64(F(ceil(planned_48k[t] * up / down)));
+ *   feat_offset[t] the running sum of width * plane[u]; both layouts of TRACK FEATURES; padding is never written; a track cut short
+ *   by a failed frame keeps its planned plane and reports its shorter F. */
+#define OPUSGPU_FBANK_POVEY 0
+#define OPUSGPU_FBANK_HANNING 1
+#define OPUSGPU_FBANK_HAMMING 2
+#define OPUSGPU_FBANK_RECTANGULAR 3
+#define OPUSGPU_FBANK_BLACKMAN 4
+#define OPUSGPU_FBANK_LOG_NONE 0
+#define OPUSGPU_FBANK_LOG_LN 1
+typedef struct opusgpu_fbank_params { /* 64 bytes (ABI) */
+    int32_t sample_rate;  /* Hz of the mono track, 1 .. 1048576; places the filterbank, and the whole-file calls check it */
+    int32_t frame_length; /* L, samples, 2 .. 2048 (odd allowed) */
+    int32_t frame_shift;  /* H, samples, >= 1, and 31 * frame_shift + frame_length <= 32768 (32 frames' window in the kernel's LDS) */
+    int32_t n_fft;        /* N: a multiple of 16 in [64, 2048], >= L; 0 means the smallest power of two >= max(L, 64) */
+    int32_t n_mels;       /* 3 .. 128 */
+    int32_t n_ceps;       /* 0: fbank; 1 .. n_mels: MFCC with that many coefficients */
+    int32_t window;       /* OPUSGPU_FBANK_POVEY 0 | _HANNING 1 | _HAMMING 2 | _RECTANGULAR 3 | _BLACKMAN 4 */
+    uint8_t snip_edges;   /* 0 or 1 */
+    uint8_t remove_dc;    /* 0 or 1 */
+    uint8_t power;        /* 1: |X|; 2: |X|^2 */
+    uint8_t log;          /* OPUSGPU_FBANK_LOG_NONE 0 | OPUSGPU_FBANK_LOG_LN 1; MFCC requires LN */
+    int32_t layout;       /* OPUSGPU_MEL_BANDS_MAJOR | OPUSGPU_MEL_FRAMES_MAJOR */
+    float preemphasis;    /* c, in [0, 1] */
+    float low_freq;       /* Hz */
+    float high_freq;      /* Hz; <= 0 means sample_rate / 2 + high_freq; 0 <= low_freq < high <= sample_rate / 2 after that */
+    float floor;          /* finite, >= 0; > 0 with a log */
+    float cepstral_lifter; /* Q, finite, >= 0; read for MFCC only */
+    int32_t reserved[2];  /* 0 */
+} opusgpu_fbank_params;
+/* The window of *p: sets *w (may be NULL) to w, L floats, valid for the life of the process, and returns L; OPUSGPU_BAD_ARG for a
+ * record that breaks a rule above.  Host only. */
+int opusgpu_fbank_window(const opusgpu_fbank_params *p, const float **w);
+/* The filterbank of *p: sets *b (may be NULL) to B, [n_mels][N / 2] floats, and returns their count; OPUSGPU_BAD_ARG as above.
+ * Host only. */
+int opusgpu_fbank_filterbank(const opusgpu_fbank_params *p, const float **b);
+/* The lifted DCT of *p: sets *d (may be NULL) to lift[q] D[q][j], [n_ceps][n_mels] floats, and returns their count (0, and *d NULL,
+ * for n_ceps 0); OPUSGPU_BAD_ARG as above.  Host only. */
+int opusgpu_fbank_dct(const opusgpu_fbank_params *p, const float **d);
+/* LAYOUT above for n tracks of planned_48k_samples[i] samples at 48 kHz whose features are cut at up / down of that rate (1 <= up
+ * <= down <= 48000; not reduced, not held against sample_rate): writes feat_offsets[i] (may be NULL) and returns the total in
+ * floats.  OPUSGPU_BAD_ARG: a record that breaks a rule, such an up / down, a negative length.  Host only. */
+int64_t opusgpu_fbank_layout(int n, const int64_t *planned_48k_samples, int up, int down, const opusgpu_fbank_params *p, int64_t *feat_offsets);
+/* k_tracks_fbank alone: opusgpu_tracks_melspec_device's contract and alignment rules -- d_in_mono packed int16 mono tracks, 16-byte
+ * aligned, read in aligned 16-byte pieces up to the one that holds a track's last sample; `spans` a HOST array of opusgpu_mel_span,
+ * whose plane must be a multiple of 64 and >= F; d_out floats, 128-byte aligned -- with this section's record, F and feature width.
+ * sample_rate places the filterbank and is held against nothing.  A track without a frame writes nothing.  OPUSGPU_BAD_ARG before
+ * any device work: a record that breaks a rule, a span that does, a scale that is not finite. */
+int opusgpu_tracks_fbank_device(opusgpu_ctx *ctx, int n_tracks, const opusgpu_mel_span *spans, const void *d_in_mono,
+                                const opusgpu_fbank_params *p, void *d_out, void *hip_stream);
+/* opusgpu_files_decode into Kaldi features: opusgpu_files_decode_melspec's flow, arguments, "written last" and refusals with this
+ * section's record, kernel and layout: rate != 0 names a rate of TRACK RATES, rate == 0 the ratio up / down of TRACK RATIOS;
+ * `mono` 1 or a *mix of one row; d_out opusgpu_fbank_layout's total in floats, 128-byte aligned; frames_out is F of the final
+ * length.  OPUSGPU_BAD_ARG before any device work, the buffer and the caller's arrays left as they were: a record that breaks a
+ * rule; a sample_rate that is not the track's rate; whatever opusgpu_files_decode_melspec refuses of the other arguments. */
+int opusgpu_files_decode_fbank(opusgpu_ctx *ctx, const opusgpu_file_batch *batch, int rate, int up, int down, int mono,
+                               const opusgpu_mix_matrix *mix, const opusgpu_fbank_params *p, const float *scale, void *d_out,
+                               int64_t *feat_offsets, int64_t *frames_out, int64_t *track_lengths_out, int32_t *status_out);
+
 /* TRACK LOUDNESS.  Integrated loudness per ITU-R BS.1770-4 and the sample peak of every track, measured on the GPU, and optionally
  * a gain to a target loudness folded into the float scale of the same call.  All of it is a function of the S16 track at 48 kHz:
  * the int16 samples s_c[n] the default path writes, at the track's FINAL length len.  Samples at or past len are never read as
@@ -1133,6 +1236,12 @@ int opusgpu_ms_files_decode_mel(opusgpu_ms *ms, const opusgpu_ms_file_batch *bat
 int opusgpu_ms_files_decode_melspec(opusgpu_ms *ms, const opusgpu_ms_file_batch *batch, int rate, int up, int down,
                                     const opusgpu_mix_matrix *mix, const opusgpu_spec_params *p, const float *scale, void *d_out,
                                     int64_t *feat_offsets, int64_t *frames_out, int64_t *track_lengths_out, int32_t *status_out);
+
+/* opusgpu_files_decode_fbank behind opusgpu_ms_files_decode (TRACK KALDI FEATURES): the layout's channels through *mix, which must
+ * have out_channels == 1; there is no `mono` here.  Refusals as there, plus a NULL mix. */
+int opusgpu_ms_files_decode_fbank(opusgpu_ms *ms, const opusgpu_ms_file_batch *batch, int rate, int up, int down,
+                                  const opusgpu_mix_matrix *mix, const opusgpu_fbank_params *p, const float *scale, void *d_out,
+                                  int64_t *feat_offsets, int64_t *frames_out, int64_t *track_lengths_out, int32_t *status_out);
 
 #ifdef __cplusplus
 }

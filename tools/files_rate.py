@@ -17,6 +17,10 @@ torch.stft, the filterbank matmul and log10, and k_tracks_mel's share of the cal
 --melspec tts | kaldi | clap | music: the fused mel-spectrogram call (opusgpu_files_decode_melspec, mono; include/opusgpu.h TRACK
 SPECTROGRAMS) at that set's rate next to float32 mono tracks at the rate followed by torch.stft, the filterbank matmul, the floor and
 the log, and k_tracks_melspec's share of the call (tools/mel_rate.py: compare_spec).
+--fbank wenet | mfcc | mfcc8k | wide: the fused Kaldi fbank / MFCC call (opusgpu_files_decode_fbank, mono; include/opusgpu.h TRACK KALDI
+FEATURES) against float mono tracks at the set's rate followed by the torch restatement (unfold, mean, pre-emphasis, window, rfft,
+matmul, log), and k_tracks_fbank's share of the call (tools/mel_rate.py: compare_fbank); a set at 16 kHz is followed by --melspec
+kaldi's line at the same files, for the two kernels' shares side by side.
 --packets-per-file P: files of P packets of 20 ms (in pages of at most 250) in place of the default 10, for --mel and --melspec: long
 tracks, whose tiles are full.
 --resample UP/DOWN [--mono | --mix M]: the fused ratio call (opusgpu_files_decode_ratio, include/opusgpu.h TRACK RATIOS) next to
@@ -26,7 +30,7 @@ kernels alone per output sample (tools/ratio_rate.py).
 LOUDNESS; tools/loudness_rate.py): float32 tracks at 48 kHz, or mono ones at --rate, without the request, with loudness="measure"
 and, with a TARGET in LUFS, normalising -- interleaved; the added time per call and its share of the call.  Tracks need 400 ms for
 a block: --packets-per-file 500 gives 10 s files.
-usage (GPU box): python3 tools/files_rate.py [--n N] [--reps R] [--loudness [T] |--format F | --rate R [--mono | --mix M] | --resample U/D [--mono | --mix M] | --mel [--n-mels N] | --melspec SET] [--packets-per-file P] | python3 tools/files_rate.py --stats DIR [--n N]"""
+usage (GPU box): python3 tools/files_rate.py [--n N] [--reps R] [--loudness [T] |--format F | --rate R [--mono | --mix M] | --resample U/D [--mono | --mix M] | --mel [--n-mels N] | --melspec SET | --fbank SET] [--packets-per-file P] | python3 tools/files_rate.py --stats DIR [--n N]"""
 import argparse
 import ctypes as C
 import glob
@@ -58,16 +62,20 @@ ap.add_argument("--mel", action="store_true", help="compare the fused log-mel ca
 ap.add_argument("--n-mels", type=int, choices=[80, 128], default=80)
 ap.add_argument("--melspec", choices=["tts", "kaldi", "clap", "music"], default=None,
                 help="compare the fused mel-spectrogram call with float mono tracks at the set's rate + torch.stft (tools/mel_rate.py)")
-ap.add_argument("--packets-per-file", type=int, default=10, help="with --mel, --melspec or --loudness: packets of 20 ms per file")
+ap.add_argument("--fbank", choices=["wenet", "mfcc", "mfcc8k", "wide"], default=None,
+                help="compare the fused Kaldi fbank / MFCC call with float mono tracks at the set's rate + unfold / rfft in torch (tools/mel_rate.py)")
+ap.add_argument("--packets-per-file", type=int, default=10, help="with --mel, --melspec, --fbank or --loudness: packets of 20 ms per file")
 ap.add_argument("--loudness", nargs="?", const="measure", default=None, metavar="TARGET",
                 help="what a loudness request adds to the float32 call, measuring and (with a target in LUFS) normalising (tools/loudness_rate.py)")
 args = ap.parse_args()
+if args.fbank and (args.rate or args.format or args.resample or args.mel or args.melspec or args.loudness or args.mix or args.mono):
+    ap.error("--fbank goes alone")
 if args.loudness and (args.format or args.mel or args.melspec or args.resample or args.mix or (args.rate and not args.mono)):
     ap.error("--loudness goes alone or with --rate R --mono")
 if args.melspec and (args.rate or args.format or args.resample or args.mel):
     ap.error("--melspec goes without --rate, --resample, --format and --mel")
-if args.packets_per_file != 10 and not (args.mel or args.melspec or args.loudness):
-    ap.error("--packets-per-file goes with --mel, --melspec or --loudness")
+if args.packets_per_file != 10 and not (args.mel or args.melspec or args.fbank or args.loudness):
+    ap.error("--packets-per-file goes with --mel, --melspec, --fbank or --loudness")
 if args.mix and (args.mono or not (args.rate or args.resample)):
     ap.error("--mix goes with --rate or --resample and without --mono")
 if args.mel and (args.rate or args.format or args.resample):
@@ -75,7 +83,7 @@ if args.mel and (args.rate or args.format or args.resample):
 if args.resample and (args.rate or args.format):
     ap.error("--resample goes without --rate and --format")
 n = args.n
-if (args.format or args.rate or args.mel or args.resample or args.melspec) and not args.loudness:
+if (args.format or args.rate or args.mel or args.resample or args.melspec or args.fbank) and not args.loudness:
     import torch  # before the library: one HIP runtime for both
 
 spec = importlib.util.spec_from_file_location("esp32_opus_player_amd", os.path.join(here, "..", "esp32-opus-player_amd", "__init__.py"))
@@ -188,6 +196,37 @@ if args.resample:
             lambda d, ln, st: ctx._chk(ctx.lib.opusgpu_files_decode(ctx.h, b.h, d, ln, st), "opusgpu_files_decode"),
             (lambda spans, d_in, fmt, d_out: ctx.tracks_resample_ratio_device(spans, d_in, 2, up, down, args.mono, rec, fmt, d_out), at_24000_kernel),
             b, up, down, args.mono, args.reps, name, mix=pkg.downmix_matrix(2, 1 if args.mix == "mono" else 2) if args.mix else None)))
+    ctx.close()
+    raise SystemExit(0)
+
+if args.fbank:
+    import mel_rate
+    maker, kw, up, down = mel_rate.FBANK_SETS[args.fbank]
+    rec = getattr(pkg, maker)(**kw)
+    rate = 48000 // down
+    b = pkg.FileBatch([r.tobytes() for r in files], channels=2, flags=pkg.PAGES_GROUP_BY_MODE, threads=args.threads)
+    assert (b.info["status"] == 0).all() and b.n_steps == PAGES * PER_PAGE
+    ctx = pkg.Context(0)
+    ctx.streams_alloc(n, 2)
+
+    def tracks(fmt, d, oo, ol, ln, st):
+        return ctx._chk(ctx.lib.opusgpu_files_decode_resampled(ctx.h, b.h, rate, 1, fmt, None, d, oo, ol, ln, st), "opusgpu_files_decode_resampled")
+    for name, pipe in (("in_order", 0), ("pipelined", 1)):
+        ctx.set_pipeline(pipe)
+        note = f"{name}, {PAGES * PER_PAGE} packets per file"
+        print(json.dumps(mel_rate.compare_fbank(
+            torch, pkg, tracks,
+            lambda p, d, fo, fr, ln, st: ctx._chk(ctx.lib.opusgpu_files_decode_fbank(ctx.h, b.h, rate, 0, 0, 1, None, p, None, d, fo, fr, ln, st),
+                                                  "opusgpu_files_decode_fbank"),
+            lambda spans, d_in, r, d_out: ctx.tracks_fbank_device(spans, d_in, r, d_out), b, rec, up, down, args.reps,
+            f"{args.fbank}, {note}")), flush=True)
+        if rate == 16000:  # k_tracks_melspec's share at the same files
+            print(json.dumps(mel_rate.compare_spec(
+                torch, pkg, tracks,
+                lambda p, d, fo, fr, ln, st: ctx._chk(ctx.lib.opusgpu_files_decode_melspec(ctx.h, b.h, rate, 0, 0, 1, None, p, None, d, fo, fr, ln, st),
+                                                      "opusgpu_files_decode_melspec"),
+                lambda spans, d_in, r, d_out: ctx.tracks_melspec_device(spans, d_in, r, d_out), b, pkg.mel_spec(**mel_rate.SPEC_SETS["kaldi"][0]),
+                up, down, args.reps, f"melspec kaldi, {note}")), flush=True)
     ctx.close()
     raise SystemExit(0)
 

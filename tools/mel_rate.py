@@ -10,6 +10,10 @@ One track of (c) is held against (b) away from the track's end, where (b) pads w
 compare_spec is the same for --melspec (include/opusgpu.h TRACK SPECTROGRAMS) with a mel_spec record in place of Whisper's constants:
 (a) float32 mono tracks at the record's rate, (b) (a) + torch.stft(n_fft, hop, win_length, periodic Hann, center=True), |.| or |.|^2,
 the filterbank matmul, the floor and the log, (c) the fused call, (m) opusgpu_tracks_melspec_device alone.
+compare_fbank is the same for --fbank (include/opusgpu.h TRACK KALDI FEATURES) with a kaldi_fbank / kaldi_mfcc record (snip_edges on):
+(a) float32 mono tracks at the record's rate, (b) (a) + the torch restatement -- unfold, the frame's mean, the pre-emphasis, the
+window, torch.fft.rfft at n_fft, |.| or |.|^2 without the Nyquist bin, the filterbank matmul, the floor, the log and for MFCC the
+DCT matmul --, (c) the fused call, (m) opusgpu_tracks_fbank_device alone.
 torch must be imported before the library is loaded: they then share one HIP runtime."""
 import time
 
@@ -174,6 +178,101 @@ def compare_spec(torch, pkg, decode_tracks, decode_spec, spec_alone, batch, rec,
     out["c_le_b"] = bool(np.mean(times["c"]) <= np.mean(times["b"]))
     return out
 
+
+def compare_fbank(torch, pkg, decode_tracks, decode_fbank, fbank_alone, batch, rec, up, down, reps, note=""):
+    """compare_spec's arguments with a kaldi_fbank / kaldi_mfcc record whose snip_edges is on.  -> a dict for the JSON line."""
+    n = batch.n_files
+    planned = batch.info["track_samples"]
+    offs, total = pkg.resample_ratio_layout(planned, up, down) if up != 1 or down not in (1, 2, 3, 4, 6) else pkg.resample_layout(planned, 48000 // down)
+    feat_offs, planes, total_feat = pkg.fbank_layout(planned, up, down, rec)
+    L, H, width, n_mels = int(rec["frame_length"][0]), int(rec["frame_shift"][0]), pkg.fbank_width(rec), int(rec["n_mels"][0])
+    bank = pkg.fbank_filterbank(rec)
+    N = 2 * bank.shape[1]
+    power, log, floor, pre = int(rec["power"][0]), int(rec["log"][0]), float(rec["floor"][0]), float(rec["preemphasis"][0])
+    dc, n_ceps = int(rec["remove_dc"][0]), int(rec["n_ceps"][0])
+    assert int(rec["snip_edges"][0]) == 1 and int(rec["layout"][0]) == pkg.MEL_FRAMES_MAJOR
+    f32 = torch.empty(max(total, 1), dtype=torch.float32, device="cuda:0")
+    s16 = torch.empty(max(total, 1) + 64, dtype=torch.int16, device="cuda:0")
+    feat = torch.empty(max(total_feat, 1), dtype=torch.float32, device="cuda:0")
+    lengths, out_offsets, out_lengths, fo, frames = (np.zeros(n, dtype=np.int64) for _ in range(5))
+    status = np.zeros((n, 2), dtype=np.int32)
+    len_r = -(-planned * up // down)
+    longest = max(int(len_r.max(initial=1)), L)
+    idx = offs[:, None] + np.arange(longest)[None, :]
+    valid = np.arange(longest)[None, :] < len_r[:, None]
+    gather = torch.tensor(np.where(valid, idx, 0), device="cuda:0")
+    mask = torch.tensor(valid, device="cuda:0")
+    window = torch.tensor(pkg.fbank_window(rec), device="cuda:0")
+    bank_t = torch.tensor(bank.T.copy(), device="cuda:0")  # [N / 2, n_mels]
+    dct_t = torch.tensor(pkg.fbank_dct(rec).T.copy(), device="cuda:0") if n_ceps else None  # [n_mels, n_ceps]
+
+    def a():
+        decode_tracks(pkg.TRACKS_F32, f32.data_ptr(), out_offsets.ctypes.data, out_lengths.ctypes.data, lengths.ctypes.data, status.ctypes.data)
+
+    def b():
+        a()
+        x = torch.where(mask, f32[gather], torch.zeros((), device="cuda:0"))
+        fr = x.unfold(1, L, H)                                                                   # [files, frames, L]
+        if dc:
+            fr = fr - fr.mean(dim=2, keepdim=True)
+        fr = (fr - pre * torch.cat([fr[..., :1], fr[..., :-1]], dim=2)) * window
+        mag = torch.fft.rfft(fr, n=N)[..., :N // 2].abs()
+        out = torch.clamp((mag if power == 1 else mag ** 2) @ bank_t, min=floor)                 # [files, frames, n_mels]
+        out = torch.log(out) if log else out
+        out = out @ dct_t if n_ceps else out
+        torch.cuda.synchronize()
+        return out
+
+    def c():
+        decode_fbank(rec.ctypes.data, feat.data_ptr(), fo.ctypes.data, frames.ctypes.data, lengths.ctypes.data, status.ctypes.data)
+
+    decode_tracks(pkg.TRACKS_S16, s16.data_ptr(), out_offsets.ctypes.data, out_lengths.ctypes.data, lengths.ctypes.data, status.ctypes.data)
+    spans = np.zeros(n, dtype=pkg.MEL_SPAN_DTYPE)
+    spans["in_offset"], spans["in_samples"], spans["out_offset"], spans["plane"], spans["scale"] = offs, out_lengths, feat_offs, planes, 2.0 ** -15
+
+    def m():
+        fbank_alone(spans, s16.data_ptr(), rec, feat.data_ptr())
+
+    times = {"a": [], "b": [], "c": [], "m": []}
+    for fn in (a, b, c, m):
+        fn()
+    for _ in range(reps):
+        for name, fn in (("a", a), ("b", b), ("c", c), ("m", m)):
+            t0 = time.perf_counter()
+            fn()
+            times[name].append((time.perf_counter() - t0) * 1e3)
+    assert (status[:, 0] == 0).all() and (lengths == planned).all() and (fo == feat_offs).all() and (frames == pkg.fbank_frames(rec, len_r)).all()
+    # one track of (c) against (b): every frame lies inside the track, so all of them compare
+    c()
+    want = b()
+    worst = None
+    fits = [j for j in range(n // 2, n) if frames[j] > 2]
+    if fits:
+        i = fits[0]
+        F, o = int(frames[i]), int(feat_offs[i])
+        got, ref = feat[o:o + F * width].view(F, width), want[i, :F]
+        d = (got - ref).abs()
+        worst = float((d if log else d / ref.abs().clamp(min=1e-30)).max())
+        assert worst < 1e-2, worst
+    out = {"fbank": [int(rec[k][0]) for k in ("sample_rate", "frame_length", "frame_shift", "n_mels", "n_ceps")] + [N], "files": n,
+           "frames": int(frames.sum()), "reps": reps, "note": note, "scratch_s16_bytes": int(total) * 2, "out_bytes": int(total_feat) * 4,
+           "padded_batch_floats_of_b": n * longest, "worst_error_vs_torch": worst if fits else "not checked: no track long enough"}
+    for k, label in (("a", "a_f32_mono"), ("b", "b_f32_then_torch_unfold_rfft_mel"), ("c", "c_fused_fbank"), ("m", "m_k_tracks_fbank_call")):
+        v = np.array(times[k])
+        out[label] = {"mean_ms": round(float(v.mean()), 3), "median_ms": round(float(np.median(v)), 3),
+                      "min_max_ms": [round(float(v.min()), 3), round(float(v.max()), 3)]}
+    out["fbank_share_of_c"] = round(float(np.mean(times["m"]) / np.mean(times["c"])), 3)
+    out["c_le_b"] = bool(np.mean(times["c"]) <= np.mean(times["b"]))
+    return out
+
+
+# the parameter sets of --fbank: (maker, its arguments, up, down); those at 16 kHz are followed by --melspec kaldi at the same files
+FBANK_SETS = {
+    "wenet": ("kaldi_fbank", dict(sample_rate=16000, num_mel_bins=80), 1, 3),
+    "mfcc": ("kaldi_mfcc", dict(sample_rate=16000, num_mel_bins=23, num_ceps=13), 1, 3),
+    "mfcc8k": ("kaldi_mfcc", dict(sample_rate=8000, num_mel_bins=23, num_ceps=13), 1, 6),
+    "wide": ("kaldi_fbank", dict(sample_rate=48000, num_mel_bins=128, window_type="blackman", high_freq=-400.0), 1, 1),
+}
 
 # the parameter sets of --melspec: (mel_spec arguments, up, down)
 SPEC_SETS = {

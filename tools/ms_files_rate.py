@@ -19,13 +19,16 @@ tracks followed by torch.stft, the filterbank matmul and log10, and k_tracks_mel
 --melspec tts | kaldi | clap | music: the fused mel-spectrogram call (opusgpu_ms_files_decode_melspec through the default mono downmix)
 next to float32 mono tracks at the set's rate followed by torch.stft, the filterbank matmul, the floor and the log, and
 k_tracks_melspec's share of the call (tools/mel_rate.py: compare_spec).
+--fbank wenet | mfcc | mfcc8k | wide: the fused Kaldi fbank / MFCC call (opusgpu_ms_files_decode_fbank through the default mono downmix)
+next to float32 mono tracks at the set's rate followed by unfold, mean, pre-emphasis, window, rfft, matmul and log in torch, and
+k_tracks_fbank's share of the call (tools/mel_rate.py: compare_fbank); a set at 16 kHz is followed by --melspec kaldi's line.
 --resample UP/DOWN [--mix M]: the fused ratio call (opusgpu_ms_files_decode_ratio) next to rate=24000 on the same corpus and to
 float32 48 kHz tracks resampled by a polyphase conv1d in torch, and the two kernels alone (tools/ratio_rate.py).
 --loudness [TARGET] [--packets-per-file P]: what a loudness request adds to the float32 call at 48 kHz (include/opusgpu.h TRACK
 LOUDNESS; tools/loudness_rate.py): without the request, with loudness="measure" and, with a TARGET in LUFS, normalising --
 interleaved; the added time per call and its share of the call.  P (at most 80: one page) packets per file in place of 10: tracks
 need 400 ms for a block.
-usage (GPU box): python3 tools/ms_files_rate.py [--n N] [--reps R] [--loudness [T] [--packets-per-file P] | --format F | --rate R [--mix M] | --resample U/D [--mix M] | --mel [--n-mels N] | --melspec SET] | python3 tools/ms_files_rate.py --stats DIR [--n N]"""
+usage (GPU box): python3 tools/ms_files_rate.py [--n N] [--reps R] [--loudness [T] [--packets-per-file P] | --format F | --rate R [--mix M] | --resample U/D [--mix M] | --mel [--n-mels N] | --melspec SET | --fbank SET] | python3 tools/ms_files_rate.py --stats DIR [--n N]"""
 import argparse
 import ctypes as C
 import glob
@@ -55,10 +58,14 @@ ap.add_argument("--mel", action="store_true", help="compare the fused log-mel ca
 ap.add_argument("--n-mels", type=int, choices=[80, 128], default=80)
 ap.add_argument("--melspec", choices=["tts", "kaldi", "clap", "music"], default=None,
                 help="compare the fused mel-spectrogram call with float mono tracks at the set's rate + torch.stft (tools/mel_rate.py)")
+ap.add_argument("--fbank", choices=["wenet", "mfcc", "mfcc8k", "wide"], default=None,
+                help="compare the fused Kaldi fbank / MFCC call with float mono tracks at the set's rate + unfold / rfft in torch (tools/mel_rate.py)")
 ap.add_argument("--loudness", nargs="?", const="measure", default=None, metavar="TARGET",
                 help="what a loudness request adds to the float32 call, measuring and (with a target in LUFS) normalising (tools/loudness_rate.py)")
 ap.add_argument("--packets-per-file", type=int, default=10, help="with --loudness: packets of 20 ms per file, at most 80")
 args = ap.parse_args()
+if args.fbank and (args.rate or args.format or args.resample or args.mel or args.melspec or args.loudness or args.mix):
+    ap.error("--fbank goes alone")
 if args.loudness and (args.format or args.rate or args.mel or args.melspec or args.resample or args.mix):
     ap.error("--loudness goes alone")
 if args.packets_per_file != 10 and (not args.loudness or not 1 <= args.packets_per_file <= 80):
@@ -71,7 +78,7 @@ if args.mel and (args.rate or args.format or args.resample):
     ap.error("--mel goes without --rate, --resample and --format")
 if args.resample and (args.rate or args.format):
     ap.error("--resample goes without --rate and --format")
-if args.format or args.rate or args.mel or args.resample or args.melspec:
+if args.format or args.rate or args.mel or args.resample or args.melspec or args.fbank:
     import torch  # before the library is loaded: one HIP runtime for both
 n = args.n
 
@@ -228,6 +235,34 @@ if args.resample:
         lambda d, ln, st: ms._chk(ms.lib.opusgpu_ms_files_decode(ms.h, b.h, d, ln, st), "opusgpu_ms_files_decode"),
         (lambda spans, d_in, fmt, d_out: mem.tracks_resample_ratio_device(spans, d_in, CH, up, down, False, rec, fmt, d_out), at_24000_kernel),
         b, up, down, False, args.reps, "in_order", mix=pkg.downmix_matrix(CH, 1 if args.mix == "mono" else 2) if args.mix else None)))
+    mem.close()
+    ms.close()
+    raise SystemExit(0)
+
+if args.fbank:
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import mel_rate
+    maker, kw, up, down = mel_rate.FBANK_SETS[args.fbank]
+    frec = getattr(pkg, maker)(**kw)
+    rate = 48000 // down
+    ms = pkg.MultistreamContext(0, n, *LAYOUT)
+    mem = pkg.Context(0)
+    rec = pkg.mix_matrix("mono", CH)
+
+    def tracks(fmt, d, oo, ol, ln, st):
+        return ms._chk(ms.lib.opusgpu_ms_files_decode_mixed(ms.h, b.h, rate, rec.ctypes.data, fmt, None, d, oo, ol, ln, st), "opusgpu_ms_files_decode_mixed")
+    print(json.dumps(mel_rate.compare_fbank(
+        torch, pkg, tracks,
+        lambda p, d, fo, fr, ln, st: ms._chk(ms.lib.opusgpu_ms_files_decode_fbank(ms.h, b.h, rate, 0, 0, rec.ctypes.data, p, None, d, fo, fr, ln, st),
+                                             "opusgpu_ms_files_decode_fbank"),
+        lambda spans, d_in, r, d_out: mem.tracks_fbank_device(spans, d_in, r, d_out), b, frec, up, down, args.reps, f"{args.fbank}, in_order")), flush=True)
+    if rate == 16000:  # k_tracks_melspec's share at the same files
+        print(json.dumps(mel_rate.compare_spec(
+            torch, pkg, tracks,
+            lambda p, d, fo, fr, ln, st: ms._chk(ms.lib.opusgpu_ms_files_decode_melspec(ms.h, b.h, rate, 0, 0, rec.ctypes.data, p, None, d, fo, fr, ln, st),
+                                                 "opusgpu_ms_files_decode_melspec"),
+            lambda spans, d_in, r, d_out: mem.tracks_melspec_device(spans, d_in, r, d_out), b, pkg.mel_spec(**mel_rate.SPEC_SETS["kaldi"][0]), up, down,
+            args.reps, "melspec kaldi, in_order")))
     mem.close()
     ms.close()
     raise SystemExit(0)
