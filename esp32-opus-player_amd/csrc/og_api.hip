@@ -379,8 +379,9 @@ extern "C" int og_celt_parse64_frames(void); // frames per group of that kernel
 
 // Split CELT path, second half: one frame per wave, driven by the parse record.
 // (20 ms CELT-only frames are reconstructed by k_celt_recon_fb, og_recon.hip; `rest_only`: skip what that kernel took)
+// `empties`: that kernel also finishes the frames without leaves (a pipelined CELT-only step: nothing is left for k_celt_recon)
 extern "C" void og_launch_celt_recon_fb(hipStream_t s, const void *descs, void *streams, const void *recs, void *rout, int n,
-                                        int n_streams, int hybrid, unsigned *started);
+                                        int n_streams, int hybrid, unsigned *started, int empties);
 extern "C" int og_celt_recon_fb_signals(int n); // how often a launch over n frames bumps `started`
 // RFC mode (opt-in): every frame of a step, at its true duration, incl. the loss path (og_rfc.hip)
 extern "C" void og_launch_decode_rfc(hipStream_t s, const void *descs, const void *arena, void *streams, void *pcm, void *result, int n,
@@ -441,7 +442,18 @@ static __device__ __forceinline__ i32 pk_add_sat_i16(i32 a, i32 b) {
     const s2 r = __builtin_elementwise_add_sat(__builtin_bit_cast(s2, a), __builtin_bit_cast(s2, b));
     return __builtin_bit_cast(i32, r);
 }
-__global__ void __launch_bounds__(64) k_celt_post(const FrameDesc *__restrict__ descs, StreamState *st, const ParseRec *recs,
+// a wave-uniform pointer, held in scalar registers: a lane's address is then this plus a 32-bit offset of its own, and a loop that walks
+// such addresses carries the one offset, not a pointer per access
+template <class T>
+static __device__ __forceinline__ T *uniform_ptr(T *p) {
+    const unsigned long long a = (unsigned long long)p;
+    return (T *)((unsigned long long)(u32)__builtin_amdgcn_readfirstlane((int)(u32)a) |
+                 (unsigned long long)(u32)__builtin_amdgcn_readfirstlane((int)(u32)(a >> 32)) << 32);
+}
+// (five waves per SIMD, at most 96 registers, as before the row descriptions left LDS for registers -- 89 now, 92 then; the bound is
+// there so that a change which needs more shows as scratch in tests/test_post_budget.py, not as a lost wave)
+#define OG_POST_WAVES 5
+__global__ void __launch_bounds__(64, OG_POST_WAVES) k_celt_post(const FrameDesc *__restrict__ descs, StreamState *st, const ParseRec *recs,
                                                   const ReconOut *__restrict__ rout, i32 *__restrict__ result, i16 *pcm, int n,
                                                   int n_streams, int channels, int pcm_stride, const SilkHandoff *handoff,
                                                   int modes, int others_ran) {
@@ -452,19 +464,21 @@ __global__ void __launch_bounds__(64) k_celt_post(const FrameDesc *__restrict__ 
     // else takes the row-per-lane path with its 16-byte accesses (celt_post_lane).
     // (Round 3 moved 64-byte pieces: the memory system fetches 128-byte lines, and the other half of a row's line had left the L2
     // again by the time its turn came -- 36 KB of traffic per hybrid frame for 15 KB needed, in a kernel that does nothing but move.)
-    struct RowInfo {
-        const i32 *ring;
-        i16 *pcm;
-        const i16 *silk;
-        int pos, silk_n;
-    };
     constexpr int CS = 32, PCS = CS / 4, RSTEP = 64 / PCS; // samples per chunk and row; 16-byte pieces per row; rows between a lane's pieces
-    __shared__ RowInfo rows[64];
-    // (one buffer is enough: a chunk's rows are all read before the barrier that follows the PCM staging, the next chunk's are
-    // written behind it)
-    __shared__ __attribute__((aligned(16))) i32 tin[64][CS + 4];  // CS samples per row, rows padded by 16 bytes
-    __shared__ __attribute__((aligned(16))) i16 tout[64][CS + 8]; // CS outputs per row, rows padded by 16 bytes
-    // (16 KB per workgroup next to kernels that are short of LDS: measured by padding, 5 KB more cost the CELT step 0.8 %, mixed pages 0.6 %)
+    static_assert(RSTEP % 2 == 0, "a lane's rows are all of one channel");
+    // ONE buffer, 9,216 bytes, eight LDS granules of 1,280 (round 13: 16 KB, thirteen -- an output buffer of 5 KB and 2 KB of row
+    // descriptions besides; what a lane needs of other rows it now asks their lanes for, once, before the loop).  A row's int16
+    // outputs go over the first half of the row's own int32 inputs: the recurrence has read a group of eight inputs into registers
+    // before it stores the group's four packed words, and they land at or below the words just read.
+    // Banks: the recurrence reads and writes 16 bytes per lane, rows 36 words apart -- 36 i mod 64 is a different multiple of four
+    // for each of a group's 16 lanes: no conflict.  The PCM stage reads 8 bytes per lane from the left and from the right row, which
+    // the compiler fuses into one ds_read2_b64 (32 banks, 16 contiguous lanes per access = two frames): words 72 r0 + 2 q + {0, 1} for
+    // two values of r0 -- two runs of 16 banks that start 8 apart, so banks 8 .. 15 are asked twice: two-way, as it was from the
+    // output buffer (rows of 20 words, frames 40 words apart: 40 mod 32 = 8, the same pattern).
+    // (Next to kernels that are short of LDS.  Measured by padding in round 5: 5 KB more cost the CELT step 0.8 %, mixed pages 0.6 %.
+    // Measured in round 14, 16,384 -> 9,216 bytes: the pipelined CELT step 2.5 % shorter, this kernel through 0.25 ms before the
+    // reconstruction it runs beside instead of with it; hybrid-256k and mixed pages within their spread.  DESIGN.md 6m.)
+    __shared__ __attribute__((aligned(16))) i32 tin[64][CS + 4]; // CS samples per row, rows padded by 16 bytes
     const int lane = (int)threadIdx.x;
     const int t = (int)blockIdx.x * 64 + lane;
     const int f = channels == 2 ? t >> 1 : t, c = channels == 2 ? t & 1 : 0;
@@ -472,9 +486,10 @@ __global__ void __launch_bounds__(64) k_celt_post(const FrameDesc *__restrict__ 
     StreamState *ss = nullptr;
     const i16 *silk = nullptr;
     int silk_n = 0;
-    int pos = 0;
+    int pos = 0, stream = 0;
     if (f < n) {
         const FrameDesc d = descs[f];
+        stream = d.stream;
         const int mode = desc_mode(d.flags);
         const bool stream_ok = d.stream >= 0 && d.stream < n_streams;
         if (!(modes >> (d.flags & 3) & 1) || (!stream_ok && !others_ran)) { // (a frame the caller's mode set left out is an error, not a skip)
@@ -498,36 +513,47 @@ __global__ void __launch_bounds__(64) k_celt_post(const FrameDesc *__restrict__ 
         }
     }
     i16 *out = pcm + (size_t)(f < n ? f : 0) * pcm_stride;
-    const bool fast = channels == 2 && __all(live && emit && (pos & (CS - 1)) == 0);
+    // (... and the stream states within 2^32 16-byte pieces of each other, 64 GB: the fast path keeps a ring's place as one word)
+    const bool fast = channels == 2 && (size_t)n_streams * sizeof(StreamState) <= (size_t)16 << 32 && __all(live && emit && (pos & (CS - 1)) == 0);
     if (!fast) {
         if (live) celt_post_lane(&ss->celt, c, channels, 960, pos, emit ? out : nullptr, silk, silk_n);
         return;
     }
-    rows[lane].ring = ss->celt.ring[c];
-    rows[lane].pcm = out;
-    rows[lane].silk = silk;
-    rows[lane].pos = pos;
-    rows[lane].silk_n = silk_n;
-    __syncthreads();
-    // this lane's share of the cooperative traffic: piece q of rows r0, r0 + RSTEP, ..
+    // this lane's share of the cooperative traffic: piece q of rows r0, r0 + RSTEP, .. -- their rings and positions from the lanes
+    // that own them (row r: channel r & 1 = r0 & 1 of frame r >> 1 of the wave; every row is live here, so its stream index is good).
+    // Kept small, for the 32 registers of pieces in flight beside them: a ring as its distance from `st` in 16-byte pieces (one word,
+    // not a pointer), the positions in chunks of CS samples, four to a word; the lines that follow put the addresses together.
     const int q = lane % PCS, r0 = lane / PCS;
-    const i32 *src[PCS];
-    int spos[PCS];
+    constexpr u32 STATE16 = sizeof(StreamState) / 16, RING16 = (offsetof(StreamState, celt) + offsetof(CeltState, ring)) / 16, CHAN16 = RING * 4 / 16;
+    static_assert(sizeof(StreamState) % 16 == 0 && (offsetof(StreamState, celt) + offsetof(CeltState, ring)) % 16 == 0 && RING / CS <= 256, "ring pieces");
+    u32 row16[PCS], at_chunk[PCS / 4] = {};
 #pragma unroll
     for (int k = 0; k < PCS; k++) {
-        src[k] = rows[r0 + RSTEP * k].ring;
-        spos[k] = rows[r0 + RSTEP * k].pos + 4 * q;
+        row16[k] = (u32)__shfl(stream, r0 + RSTEP * k) * STATE16 + RING16 + (u32)(r0 & 1) * CHAN16 + (u32)q;
+        at_chunk[k / 4] |= (u32)(__shfl(pos, r0 + RSTEP * k) / CS) << (8 * (k % 4));
     }
+    // piece q of chunk `chunk` of the frame in row k of this lane's: 16 bytes, on a 16-byte boundary
+    auto piece = [&](int k, int chunk) -> og_v4i {
+        const u32 at = ((at_chunk[k / 4] >> (8 * (k % 4)) & 255u) + (u32)chunk) & (u32)(RING / CS - 1);
+        return *reinterpret_cast<const og_v4i *>(reinterpret_cast<const char *>(st) + (size_t)(row16[k] + at * (CS * 4 / 16)) * 16);
+    };
+    // ... and of the PCM's: piece q of frames r0, r0 + RSTEP, .. -- how much SILK PCM each has, in units of 960 (0: not a hybrid frame)
+    const size_t f_wave = (size_t)blockIdx.x * 32; // the wave's first frame
+    const u32 lane_pcm = 2u * (u32)(r0 * pcm_stride + 8 * q), lane_sk = (u32)r0 * (u32)sizeof(SilkHandoff) + 16u * (u32)q; // bytes
+    u32 sk_960 = 0;
+#pragma unroll
+    for (int k = 0; k < PCS / 2; k++) sk_960 |= (u32)(__shfl(silk_n, 2 * (r0 + RSTEP * k)) / 960) << (8 * k);
     og_v4i v[PCS];
 #pragma unroll
-    for (int k = 0; k < PCS; k++) v[k] = *reinterpret_cast<const og_v4i *>(src[k] + (spos[k] & RING_MASK));
-    i32 m = ss->celt.deemph[c];
+    for (int k = 0; k < PCS; k++) v[k] = piece(k, 0);
+    i32 m = st[stream].celt.deemph[c];
     for (int ch = 0; ch < 960 / CS; ch++) {
+        if (ch) __syncthreads(); // (the PCM stage of the chunk before has read its rows)
 #pragma unroll
         for (int k = 0; k < PCS; k++) *reinterpret_cast<og_v4i *>(&tin[r0 + RSTEP * k][4 * q]) = v[k];
         if (ch + 1 < 960 / CS) {
 #pragma unroll
-            for (int k = 0; k < PCS; k++) v[k] = *reinterpret_cast<const og_v4i *>(src[k] + ((spos[k] + CS * (ch + 1)) & RING_MASK));
+            for (int k = 0; k < PCS; k++) v[k] = piece(k, ch + 1);
         }
         __syncthreads();
         // the recurrence on this lane's own row (celt.cpp:1965-2055, sig2word16 celt.h:413)
@@ -557,7 +583,7 @@ __global__ void __launch_bounds__(64) k_celt_post(const FrameDesc *__restrict__ 
             w.y = (i32)((u32)(u16)o[2] | (u32)(u16)o[3] << 16);
             w.z = (i32)((u32)(u16)o[4] | (u32)(u16)o[5] << 16);
             w.w = (i32)((u32)(u16)o[6] | (u32)(u16)o[7] << 16);
-            *reinterpret_cast<og_v4i *>(&tout[lane][8 * g8]) = w;
+            *reinterpret_cast<og_v4i *>(&tin[lane][4 * g8]) = w; // (outputs 8 g8 .. 8 g8 + 7, over inputs 4 g8 .. 4 g8 + 3: read above)
         }
         __syncthreads();
         // PCM: frame fr's CS samples x 2 channels = 128 contiguous bytes; this lane writes piece q (samples 4q .. 4q+3) of frames
@@ -565,26 +591,29 @@ __global__ void __launch_bounds__(64) k_celt_post(const FrameDesc *__restrict__ 
 #pragma unroll
         for (int k = 0; k < PCS / 2; k++) {
             const int fr = r0 + RSTEP * k; // frame within the wave: rows 2 fr (left) and 2 fr + 1 (right)
-            const og_v2u L = *reinterpret_cast<const og_v2u *>(&tout[2 * fr][4 * q]);
-            const og_v2u R = *reinterpret_cast<const og_v2u *>(&tout[2 * fr + 1][4 * q]);
+            const og_v2u L = *reinterpret_cast<const og_v2u *>(&tin[2 * fr][2 * q]); // (int16 outputs 4 q .. 4 q + 3 of the row)
+            const og_v2u R = *reinterpret_cast<const og_v2u *>(&tin[2 * fr + 1][2 * q]);
             og_v4i w;
             w.x = (i32)((L.x & 0xffffu) | R.x << 16);
             w.y = (i32)(L.x >> 16 | (R.x & 0xffff0000u));
             w.z = (i32)((L.y & 0xffffu) | R.y << 16);
             w.w = (i32)(L.y >> 16 | (R.y & 0xffff0000u));
             const int at = (CS * ch + 4 * q) * 2; // the piece's place in the frame's interleaved PCM -- and in its SILK PCM (Q3: by linear index)
-            const i16 *const sk = rows[2 * fr].silk;
-            if (sk && at < rows[2 * fr].silk_n) { // SAT16(celt + silk), two samples per saturating packed add
-                const og_v4i a = *reinterpret_cast<const og_v4i *>(sk + at);
+            // (addresses as a wave-uniform base -- frame RSTEP k of the wave, sample CS ch -- plus the lane's 32-bit offset: one register
+            // for all of them, where a pointer per frame was two each, carried through the loop)
+            if (at < 960 * (int)(sk_960 >> (8 * k) & 255u)) { // SAT16(celt + silk), two samples per saturating packed add
+                const char *const sk = uniform_ptr(reinterpret_cast<const char *>(handoff[f_wave + RSTEP * k].pcm + 2 * CS * ch));
+                const og_v4i a = *reinterpret_cast<const og_v4i *>(sk + lane_sk);
                 w.x = pk_add_sat_i16(w.x, a.x);
                 w.y = pk_add_sat_i16(w.y, a.y);
                 w.z = pk_add_sat_i16(w.z, a.z);
                 w.w = pk_add_sat_i16(w.w, a.w);
             }
-            *reinterpret_cast<og_v4i *>(rows[2 * fr].pcm + at) = w;
+            char *const to = uniform_ptr(reinterpret_cast<char *>(pcm + (f_wave + RSTEP * k) * pcm_stride + 2 * CS * ch));
+            *reinterpret_cast<og_v4i *>(to + lane_pcm) = w;
         }
     }
-    ss->celt.deemph[c] = m;
+    st[stream].celt.deemph[c] = m;
 }
 
 #include "og_step.hpp"
@@ -652,9 +681,19 @@ void launch_celt_parse(opusgpu_ctx *ctx, hipStream_t q, const Step &st, size_t f
 }
 void launch_celt_recon_fb(opusgpu_ctx *ctx, hipStream_t q, const Step &st, size_t f0, int cnt, bool counts_in) {
     const StepRange r(st, f0);
-    og_launch_celt_recon_fb(q, r.dd, ctx->d_streams, r.recs, r.rout, cnt, ctx->n_streams, r.hh ? 1 : 0, counts_in ? ctx->sp.d_started + 16 : nullptr);
+    // A pipelined CELT-only step (the only caller that counts in; no hand-off, so no hybrid frames): the frames the kernel of 20 ms
+    // frames leaves are CELT frames of at most one byte, which it finishes itself (`empties`, og_recon.hip) -- the leftover launch
+    // behind it was a link of 1,024 workgroups with nothing to do in the chain from one reconstruction to the next.
+    // Every other step keeps that launch: hybrid frames, in-order steps (OPUSGPU_REST_IN_FB=0: pipelined CELT-only steps too).
+    ctx->recon_fb_took_rest = counts_in && !r.hh && st.modes == 4 && og_debug().rest_in_fb;
+    og_launch_celt_recon_fb(q, r.dd, ctx->d_streams, r.recs, r.rout, cnt, ctx->n_streams, r.hh ? 1 : 0, counts_in ? ctx->sp.d_started + 16 : nullptr,
+                            ctx->recon_fb_took_rest ? 1 : 0);
 }
 void launch_celt_recon(opusgpu_ctx *ctx, hipStream_t q, const Step &st, size_t f0, int cnt) {
+    if (ctx->fast_recon && ctx->recon_fb_took_rest) { // (launch_celt_recon_fb, called right before this for the same frames)
+        ctx->recon_fb_took_rest = false;
+        return;
+    }
     const StepRange r(st, f0);
     hipLaunchKernelGGL(k_celt_recon, dim3(ctx->fast_recon ? (cnt + 63) / 64 : cnt), dim3(64), 0, q, r.dd, ctx->d_streams, (const ParseRec *)r.recs,
                        r.rout, cnt, ctx->n_streams, r.hh ? 1 : 0, ctx->fast_recon);

@@ -133,6 +133,7 @@ struct opusgpu_ctx {
     int split_celt = 1;   // OPUSGPU_SPLIT=0 forces the single-kernel path for every mode (A/B measurements)
     int split_hybrid = 1; // OPUSGPU_SPLIT_HYBRID=0 keeps SILK-only and hybrid frames entirely on the single-kernel path
     int fast_recon = 1;   // OPUSGPU_FAST_RECON=0: every CELT frame through the general reconstruction kernel (A/B measurements)
+    bool recon_fb_took_rest = false; // the last launch_celt_recon_fb also finished the frames without leaves: launch_celt_recon has nothing to launch
     int mode = OPUSGPU_MODE_REFERENCE; // opusgpu_set_mode
     int pipeline = 0;               // opusgpu_set_pipeline: declared steps run ahead of the step before them (og_step.hpp)
     long long stall_ticks = 0;      // OPUSGPU_STALL_US in ticks of the device wall clock (0: no stalls, og_debug.hpp)

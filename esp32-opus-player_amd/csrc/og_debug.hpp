@@ -9,6 +9,7 @@
 //   OPUSGPU_SPLIT             split            1        0: every frame through the single kernel k_decode_step (round 1's design)
 //   OPUSGPU_SPLIT_HYBRID      split_hybrid     1        0: SILK-only and hybrid frames stay on the single kernel
 //   OPUSGPU_FAST_RECON        fast_recon       1        0: every CELT frame through the general reconstruction kernel
+//   OPUSGPU_REST_IN_FB        rest_in_fb       1        0: pipelined CELT-only steps keep the leftover launch of k_celt_recon behind k_celt_recon_fb (A/B measurements)
 //   OPUSGPU_SILK_PIPELINE     silk_pipeline    1        0: steps declared SILK-only run in order even with pipelining on (A/B measurements)
 //   OPUSGPU_HYBRID_PIPELINE   hybrid_pipeline  1        0: the same for steps declared hybrid (or SILK-only + hybrid)
 //   OPUSGPU_PARSE_WIDE        parse_wide       1        0: pipelined steps parse with 32 frames per wave like in-order steps (k_celt_parse instead of k_celt_parse64);
@@ -36,7 +37,7 @@
 #include <string.h>
 
 struct og_debug_knobs {
-    int split = 1, split_hybrid = 1, fast_recon = 1, hybrid_recon_aside = 1, silk_params_aside = 1, silk_nb_kernel = 1, halves = 1, silk_pipeline = 1, hybrid_pipeline = 1, parse_wide = 1, parse_groups = 1, parse_priority = 1, host_parts = 16, host_slices = 1, host_timing = 0,
+    int split = 1, split_hybrid = 1, fast_recon = 1, rest_in_fb = 1, hybrid_recon_aside = 1, silk_params_aside = 1, silk_nb_kernel = 1, halves = 1, silk_pipeline = 1, hybrid_pipeline = 1, parse_wide = 1, parse_groups = 1, parse_priority = 1, host_parts = 16, host_slices = 1, host_timing = 0,
         pages_timing = 0, launch_delay_us = 0, stall_stream = 0, stall_us = 0; // stall_stream: 0 none, 1 step, 2 parse, 3 recon, 4 side
 };
 inline const og_debug_knobs &og_debug() {
@@ -54,6 +55,7 @@ inline const og_debug_knobs &og_debug() {
         flag("OPUSGPU_SPLIT", v.split);
         flag("OPUSGPU_SPLIT_HYBRID", v.split_hybrid);
         flag("OPUSGPU_FAST_RECON", v.fast_recon);
+        flag("OPUSGPU_REST_IN_FB", v.rest_in_fb);
         number("OPUSGPU_HYBRID_RECON_ASIDE", v.hybrid_recon_aside, 0, 2);
         flag("OPUSGPU_SILK_PARAMS_ASIDE", v.silk_params_aside);
         flag("OPUSGPU_SILK_NB_KERNEL", v.silk_nb_kernel);

@@ -5,7 +5,8 @@
 // is chosen at compile time: here OG_RECON_TIGHT selects the layout without the folding-history rows, the packet buffer and
 // the entropy-decoding arrays, with the synthesis buffer starting inside X.  Only the phase-major band loop and the
 // synthesis run from this layout; frames it does not take (recon_fast_eligible, og_celt_recon.hpp) are left to the general
-// kernel k_celt_recon in og_api.hip, which is launched right behind this one and skips the frames done here.
+// kernel k_celt_recon in og_api.hip, which is launched right behind this one and skips the frames done here -- except in pipelined
+// CELT-only steps (`empties`, below), whose only leftover frames need none of the layout and are finished here.
 // Why: measured on the 10 KB layout, k_celt_recon's time goes with 1 / (waves per SIMD) -- 2.69 ms at three, 2.09 ms at four; and
 // in pipelined steps the kernel shares its CUs' LDS with the parse kernel's workgroups (og_state.hpp).
 //
@@ -28,7 +29,11 @@ using namespace og;
 // inside the spread of the runs -- not kept)
 __global__ void __launch_bounds__(64, OG_FAST_WAVES) k_celt_recon_fb(const FrameDesc *__restrict__ descs, StreamState *st,
                                                                            const ParseRec *recs, ReconOut *rout, int n, int n_streams,
-                                                                           int hybrid, u32 *started) {
+                                                                           int hybrid, u32 *started, int empties) {
+    // `empties` (pipelined CELT-only steps): the frames that recon_fast_eligible leaves out in such a step are the CELT frames of at
+    // most one byte (RF_BAD_CELT: no leaves, no synthesis; a record cannot overflow, tests/test_kernel_paths.py).  What the general
+    // kernel does for one in its role RECON_REST_ONLY -- the reset on a mode change, the stream's header words, the ReconOut -- touches
+    // no LDS, so this kernel does it in that role and no k_celt_recon is launched behind it (launch_celt_recon, og_api.hip).
     // `started` (steps queued as a window, opusgpu_decode_steps_device): every 64th workgroup counts itself in when it starts --
     // the de-emphasis of the step before is held until the first round of this launch has its places
     if (started && threadIdx.x == 0 && (blockIdx.x & 63) == 0) __hip_atomic_fetch_add(started, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -74,7 +79,8 @@ __global__ void __launch_bounds__(64, OG_FAST_WAVES) k_celt_recon_fb(const Frame
         }
         if (ok) {
             pos = rx.h.ring_pos; // where the frame's first sample goes
-            mine = recon_begin(sp, rec, mode, desc_channels(d.flags), RECON_FAST_ONLY, rx);
+            const int role = empties && mode == MODE_CELT && (rx.h.flags & (RF_SKIP | RF_BAD_CELT)) == RF_BAD_CELT ? (int)RECON_REST_ONLY : (int)RECON_FAST_ONLY;
+            mine = recon_begin(sp, rec, mode, desc_channels(d.flags), role, rx);
             if (mine) { // (the frame's result and what it leaves in the stream's header words: known here, see recon_bookkeeping)
                 if (OG_LANE == 0) rout[f] = ReconOut{recon_result(rx), pos};
                 recon_bookkeeping(sp, rx);
@@ -92,9 +98,9 @@ __global__ void __launch_bounds__(64, OG_FAST_WAVES) k_celt_recon_fb(const Frame
 }
 
 extern "C" void og_launch_celt_recon_fb(hipStream_t s, const void *descs, void *streams, const void *recs, void *rout, int n,
-                                        int n_streams, int hybrid, unsigned *started) {
+                                        int n_streams, int hybrid, unsigned *started, int empties) {
     hipLaunchKernelGGL(k_celt_recon_fb, dim3(n), dim3(64), 0, s, (const FrameDesc *)descs, (StreamState *)streams,
-                       (const ParseRec *)recs, (ReconOut *)rout, n, n_streams, hybrid, started);
+                       (const ParseRec *)recs, (ReconOut *)rout, n, n_streams, hybrid, started, empties);
 }
 extern "C" int og_celt_recon_fb_signals(int n) { return (n + 63) / 64; }
 
