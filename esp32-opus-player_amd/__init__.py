@@ -52,6 +52,8 @@ EXPORTS = [
     "opusgpu_files_decode_fbank", "opusgpu_ms_files_decode_fbank",
     "opusgpu_loudness_weights", "opusgpu_loudness_gain", "opusgpu_tracks_loudness_device", "opusgpu_set_loudness", "opusgpu_last_loudness",
     "opusgpu_ms_set_loudness", "opusgpu_ms_last_loudness",
+    "opusgpu_files_plan_cuts", "opusgpu_ms_files_plan_cuts", "opusgpu_file_batch_track_stride", "opusgpu_ms_file_batch_track_stride",
+    "opusgpu_tracks_fill_tail_device",
 ]
 
 
@@ -126,6 +128,11 @@ FILE_INFO_DTYPE = np.dtype([("status", "<i4"), ("channels", "<i4"), ("pre_skip",
                             ("packets", "<i4"), ("frames", "<i4"), ("holes", "<i4"), ("track_samples", "<i8"), ("track_offset", "<i8")])
 # opusgpu_track_place and the OPUSGPU_TRACKS_* formats (include/opusgpu.h, TRACK FORMATS)
 TRACK_PLACE_DTYPE = np.dtype([("track_offset", "<i8"), ("plane_samples", "<i8"), ("scale", "<f4"), ("reserved", "<i4")])
+# opusgpu_cut / opusgpu_cut_info / opusgpu_tail_span (include/opusgpu.h, WHOLE FILES / CUTS)
+CUT_DTYPE = np.dtype([("file", "<i4"), ("preroll", "<i4"), ("start", "<i8"), ("count", "<i8")])
+CUT_INFO_DTYPE = np.dtype([("first_packet", "<i4"), ("packets", "<i4"), ("lead", "<i4"), ("exact", "<i4"), ("start", "<i8")])
+TAIL_SPAN_DTYPE = np.dtype([("track_offset", "<i8"), ("plane_samples", "<i8"), ("first", "<i8"), ("end", "<i8")])
+CUT_PREROLL = 3840  # OPUSGPU_CUT_PREROLL: 80 ms, RFC 7845 section 4.6
 TRACKS_S16, TRACKS_F32, TRACKS_F32_PLANAR = 0, 1, 2
 TRACK_FORMATS = {"s16": TRACKS_S16, "f32": TRACKS_F32, "f32_planar": TRACKS_F32_PLANAR}
 # opusgpu_resample_span and the rates of the resampled tracks (include/opusgpu.h, TRACK RATES): rate -> D = 48000 / rate
@@ -267,6 +274,12 @@ def load_lib():
         f("packet_start").restype = C.c_int64
         f("free").argtypes = [vp]
         f("free").restype = None
+        f("track_stride").argtypes = [vp]
+        f("track_stride").restype = C.c_int64
+    lib.opusgpu_files_plan_cuts.argtypes = [C.c_int, vp, vp, C.c_int, vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.POINTER(vp)]
+    lib.opusgpu_ms_files_plan_cuts.argtypes = [C.c_int, vp, vp, C.c_int, vp, C.c_int64, C.POINTER(MsLayout), C.c_int, C.c_int, vp, vp,
+                                               C.POINTER(vp)]
+    lib.opusgpu_tracks_fill_tail_device.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, vp, vp]
     lib.opusgpu_ms_tracks_assemble_device.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp]
     lib.opusgpu_ms_files_decode.argtypes = [vp, vp, vp, vp, vp]
     lib.opusgpu_ms_tracks_assemble_device_as.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp]
@@ -467,27 +480,57 @@ class PageBatch:
             pass
 
 
+def cut_seconds(file, start_s, duration_s):
+    """A cut of file `file` given in seconds -> (file, start, count) in samples at 48 kHz, each rounded as round(s * 48000)."""
+    return int(file), int(round(start_s * 48000)), int(round(duration_s * 48000))
+
+
+def cut_records(cuts, preroll=CUT_PREROLL):
+    """cuts: a sequence of (file, start, count) or (file, start, count, preroll), in samples at 48 kHz on the axis of the file's
+    whole-file track; count None or negative: to the end; preroll: decoded samples wanted in front of `start` where the cut names
+    none (negative: 3840, 80 ms) -> CUT_DTYPE records (opusgpu_cut)."""
+    cuts = [tuple(c) for c in cuts]
+    rec = np.zeros(len(cuts), dtype=CUT_DTYPE)
+    for t, c in enumerate(cuts):
+        if len(c) not in (3, 4):
+            raise ValueError(f"a cut is (file, start, count) or (file, start, count, preroll), not {c!r}")
+        rec[t] = (int(c[0]), int(c[3] if len(c) == 4 else preroll), int(c[1]), -1 if c[2] is None else int(c[2]))
+    return rec
+
+
 class _PlannedFiles:
     """What FileBatch and MsFileBatch share: the plan call, the batch's accessors (the C family `_prefix`: opusgpu_file_batch /
     opusgpu_ms_file_batch) and its lifetime.  A slot of a step has `_width` descriptors."""
     _prefix, _width = None, 1
 
-    def _plan(self, files, rfc, name, call):
-        """call(n, file pointers, lengths, info, out handle) -> the code of the plan function `name`."""
+    def _plan(self, files, rfc, name, call, cuts=None, preroll=CUT_PREROLL, stride=None):
+        """call(n, file pointers, lengths, info, out handle, cut arguments) -> the code of the plan function `name` (cut arguments
+        None), or of its _cuts twin: (n_cuts, cut records, track_stride, cut info).  With cuts the batch's tracks are the cuts:
+        n_files and info count them, `cut_info` holds their CUT_INFO_DTYPE records and n_sources the files."""
         self.lib = load_lib()
         self._files = [np.frombuffer(bytes(f) + b"\0", dtype=np.uint8) for f in files]  # (kept alive; + 1: never an empty buffer)
         n = len(self._files)
         ptrs = np.array([a.ctypes.data for a in self._files], dtype=np.uint64)
         lens = np.array([a.size - 1 for a in self._files], dtype=np.int64)
-        self.info = np.zeros(n, dtype=FILE_INFO_DTYPE)
+        if cuts is None:
+            if stride:
+                raise ValueError("stride needs cuts")
+            self.cuts, self.cut_info, cut_args, n_tracks = None, None, None, n
+        else:
+            self.cuts = cut_records(cuts, preroll)
+            n_tracks = self.cuts.size
+            self.cut_info = np.zeros(n_tracks, dtype=CUT_INFO_DTYPE)
+            cut_args = (n_tracks, self.cuts.ctypes.data, int(stride or 0), self.cut_info.ctypes.data)
+        self.info = np.zeros(n_tracks, dtype=FILE_INFO_DTYPE)
         h = C.c_void_p()
-        r = call(n, ptrs.ctypes.data, lens.ctypes.data, self.info.ctypes.data, C.byref(h))
+        r = call(n, ptrs.ctypes.data, lens.ctypes.data, self.info.ctypes.data, C.byref(h), cut_args)
         if r != 0:
-            e = OpusGpuError(f"{name} failed: {r}")
+            e = OpusGpuError(f"{name}{'_cuts' if cut_args else ''} failed: {r}")
             e.code = r
             raise e
         self.h = h
-        self.n_files, self.rfc = n, bool(rfc)
+        self.n_files, self.n_sources, self.rfc = n_tracks, n, bool(rfc)
+        self.stride = int(stride or 0)
         self.row_samples = RFC_FRAME if rfc else FRAME
         self.n_steps = self._c("steps")(h)
         self.track_samples = self._c("track_samples")(h)
@@ -533,13 +576,22 @@ class _PlannedFiles:
 class FileBatch(_PlannedFiles):
     """Decode steps, packet arena and track segments planned from whole Ogg Opus files by opusgpu_files_plan (host only,
     include/opusgpu.h WHOLE FILES).  files: a list of bytes-like objects, file i = decoder stream i.  info: one FILE_INFO_DTYPE
-    record per file (status, OpusHead fields, packets, frames, holes, planned track length and offset)."""
+    record per file (status, OpusHead fields, packets, frames, holes, planned track length and offset).
+    cuts: None, or pieces of the files as the batch's tracks (cut_records says what they may be; include/opusgpu.h WHOLE FILES /
+    CUTS): cut t = decoder stream t, n_files and info count the cuts, cut_info holds their CUT_INFO_DTYPE records, and the files are
+    read once each.  preroll: for cuts that name none.  stride: None / 0 for packed tracks, else every track's distance."""
     _prefix = "opusgpu_file_batch"
 
-    def __init__(self, files, channels=2, rfc=False, flags=0, threads=1):
+    def __init__(self, files, channels=2, rfc=False, flags=0, threads=1, cuts=None, preroll=CUT_PREROLL, stride=None):
         self.channels = channels
-        self._plan(files, rfc, "opusgpu_files_plan", lambda n, ptrs, lens, info, out: load_lib().opusgpu_files_plan(
-            n, ptrs, lens, channels, 1 if rfc else 0, flags, threads, info, out))
+        mode = 1 if rfc else 0
+
+        def call(n, ptrs, lens, info, out, cut_args):
+            if cut_args is None:
+                return load_lib().opusgpu_files_plan(n, ptrs, lens, channels, mode, flags, threads, info, out)
+            n_cuts, recs, track_stride, cut_info = cut_args
+            return load_lib().opusgpu_files_plan_cuts(n, ptrs, lens, n_cuts, recs, track_stride, channels, mode, flags, threads, info, cut_info, out)
+        self._plan(files, rfc, "opusgpu_files_plan", call, cuts, preroll, stride)
 
     def step(self, k):
         """-> (descriptors [DESC_DTYPE], file of every slot [int32], segments [TRACK_SEG_DTYPE], modes); views, valid until close()."""
@@ -567,15 +619,22 @@ class MsFileBatch(_PlannedFiles):
     """Decode steps, packet arena and track segments planned from whole Ogg Opus files of ONE multistream layout by
     opusgpu_ms_files_plan (host only, include/opusgpu.h WHOLE FILES / MULTISTREAM).  files: a list of bytes-like objects, file i =
     decoder i; layout: (channels, streams, coupled, mapping) or an MsLayout.  A step is rows of `streams` descriptors, one row and
-    one segment per file that has a frame in it."""
+    one segment per file that has a frame in it.  cuts, preroll, stride: as for FileBatch."""
     _prefix = "opusgpu_ms_file_batch"
 
-    def __init__(self, files, layout, rfc=False, threads=1):
+    def __init__(self, files, layout, rfc=False, threads=1, cuts=None, preroll=CUT_PREROLL, stride=None):
         self.layout = layout if isinstance(layout, MsLayout) else ms_layout(*layout)
         self.channels, self.streams = int(self.layout.channels), int(self.layout.streams)
         self._width = self.streams
-        self._plan(files, rfc, "opusgpu_ms_files_plan", lambda n, ptrs, lens, info, out: load_lib().opusgpu_ms_files_plan(
-            n, ptrs, lens, C.byref(self.layout), 1 if rfc else 0, threads, info, out))
+        mode = 1 if rfc else 0
+
+        def call(n, ptrs, lens, info, out, cut_args):
+            if cut_args is None:
+                return load_lib().opusgpu_ms_files_plan(n, ptrs, lens, C.byref(self.layout), mode, threads, info, out)
+            n_cuts, recs, track_stride, cut_info = cut_args
+            return load_lib().opusgpu_ms_files_plan_cuts(n, ptrs, lens, n_cuts, recs, track_stride, C.byref(self.layout), mode, threads, info,
+                                                         cut_info, out)
+        self._plan(files, rfc, "opusgpu_ms_files_plan", call, cuts, preroll, stride)
 
     def step(self, k):
         """-> (descriptors [rows, streams] of DESC_DTYPE, file of every row [int32], segments [TRACK_SEG_DTYPE]); views, valid
@@ -1221,9 +1280,15 @@ class FilesRequest(typing.NamedTuple):
     mix: object       # the matrix record or None
     params: object    # the features' record or None
     loudness: object = None  # the loudness request's record (loudness_request) or None
+    stride: int = 0   # a strided batch of cuts: every track `stride` samples per channel apart, zeros behind its final length
+    cut_info: object = None  # the batch's CUT_INFO_DTYPE records (a batch of cuts) or None
 
 
-def files_request(batch, multistream=False, device=0, format=None, scale=None, out=None, rate=None, mono=False, mix=None, features=None,
+STRIDE_REFUSED = ("the batch has a stride, which only tracks at 48 kHz keep (format=, scale=, out=, and loudness= with \"s16\"): resampled, "
+                  "mixed and feature outputs have grids of their own -- plan the cuts without stride= for these arguments")
+
+
+def _files_request(batch, multistream=False, device=0, format=None, scale=None, out=None, rate=None, mono=False, mix=None, features=None,
                   n_mels=80, feature_layout="bands", resample=None, loudness=None, peak_limit=1.0, channel_weights=None):
     """The keywords of decode_files for a planned batch -> the FilesRequest that _run_files_request carries out.  Every refusal of
     decode_files is raised here, as ValueError, by the track_*_args helpers; nothing of a decoder is needed.  multistream: the batch
@@ -1233,10 +1298,10 @@ def files_request(batch, multistream=False, device=0, format=None, scale=None, o
     go through files_decode_mixed with the identity matrix, which writes the same elements (include/opusgpu.h TRACK LOUDNESS)."""
     lreq = loudness_request(batch, loudness, peak_limit, channel_weights)
     if lreq is not None:
-        req = files_request(batch, multistream, device, format, scale, out, rate, mono, mix, features, n_mels, feature_layout, resample)
+        req = _files_request(batch, multistream, device, format, scale, out, rate, mono, mix, features, n_mels, feature_layout, resample)
         if req.entry == "files_decode_as":
             identity = 16384 * np.eye(batch.channels, dtype=np.int16)
-            req = files_request(batch, multistream, device, format, scale, out, rate, mono, identity, features, n_mels, feature_layout, resample)
+            req = _files_request(batch, multistream, device, format, scale, out, rate, mono, identity, features, n_mels, feature_layout, resample)
         if int(lreq["mode"][0]) == LOUDNESS_NORMALIZE and req.kind != "features" and req.fmt == TRACKS_S16:
             raise ValueError("a loudness target needs a float format or features: int16 tracks are not scaled")
         return req._replace(loudness=lreq)
@@ -1279,6 +1344,22 @@ def files_request(batch, multistream=False, device=0, format=None, scale=None, o
         entry, args = "files_decode_resampled", (int(rate),) + mono_arg
     fmt, scale, _ = track_format_args(batch, format, scale, None, device)
     return FilesRequest(entry, args, "resampled", fmt, scale, rout, ch, offsets, ((planned + D - 1) // D + 63) // 64 * 64, total, mrec, None)
+
+
+def files_request(batch, multistream=False, device=0, format=None, scale=None, out=None, rate=None, mono=False, mix=None, features=None,
+                  n_mels=80, feature_layout="bands", resample=None, loudness=None, peak_limit=1.0, channel_weights=None):
+    """The keywords of decode_files for a planned batch -> the FilesRequest that _run_files_request carries out (_files_request says
+    how).  A batch of cuts (FileBatch(cuts=...)) is a batch like any other: the request carries its cut records, which only info
+    reads.  A strided one is refused here, as ValueError, with everything but tracks at 48 kHz; its planes lie the stride apart."""
+    stride, cut_info = int(getattr(batch, "stride", 0) or 0), getattr(batch, "cut_info", None)
+    if stride and (rate not in (None, 48000) or mono or mix is not None or features is not None or resample is not None or
+                   (loudness is not None and format not in (None, "s16"))):
+        raise ValueError(STRIDE_REFUSED)
+    req = _files_request(batch, multistream, device, format, scale, out, rate, mono, mix, features, n_mels, feature_layout, resample, loudness,
+                         peak_limit, channel_weights)
+    if stride:
+        req = req._replace(stride=stride, planes=np.full(batch.n_files, stride, dtype=np.int64))
+    return req if cut_info is None else req._replace(cut_info=cut_info)
 
 
 def _run_files_request(req, lib, prefix, handle, chk, batch, mem):
@@ -1330,8 +1411,11 @@ def _run_files_request(req, lib, prefix, handle, chk, batch, mem):
     count_field, offset_field, more = {"tracks": (None, None, []), "resampled": ("out_samples", "out_offset", ["out_samples", "out_offset"]),
                                        "features": ("frames", "feat_offset", ["feat_offset"])}[req.kind]
     louder = [] if req.loudness is None else [("lufs", "<f4"), ("peak", "<f4"), ("loudness_blocks", "<i4"), ("loudness_gated", "<i4"), ("gain", "<f8")]
+    cut_fields = [] if req.cut_info is None else [("cut_" + f, CUT_INFO_DTYPE[f].str) for f in CUT_INFO_DTYPE.names]
     info = np.zeros(n, dtype=np.dtype(FILE_INFO_DTYPE.descr + [("final_status", "<i4"), ("bad_packet", "<i4")] + [(f, "<i8") for f in more] +
-                                      louder))
+                                      louder + cut_fields))
+    for f in CUT_INFO_DTYPE.names if cut_fields else ():
+        info["cut_" + f] = req.cut_info[f]
     if louder:
         info["lufs"], info["peak"], info["loudness_blocks"], info["loudness_gated"] = loud["lufs"], loud["peak"], loud["blocks"], loud["gated"]
         info["gain"] = gains
@@ -1348,6 +1432,9 @@ def _run_files_request(req, lib, prefix, handle, chk, batch, mem):
         if int(req.params["layout"][0]) == MEL_FRAMES_MAJOR:
             return [packed[o:o + F * n_mels].reshape(F, n_mels) for o, F in zip(offsets, counts)], info
         return [packed[o:o + n_mels * p].reshape(n_mels, p)[:, :F] for o, p, F in zip(offsets, req.planes, counts)], info
+    if req.stride and req.out is not None:  # the caller's memory as the tensor it is: every track at its stride, zeros behind its length
+        shape = (n, ch, req.stride) if fmt == TRACKS_F32_PLANAR else (n, req.stride, ch)
+        return packed[:n * req.stride * ch].view(*shape), info
     if fmt == TRACKS_F32_PLANAR:  # track t: `ch` planes of its planned length rounded up to 64, where its interleaved form would lie
         return [packed[ch * o:ch * (o + p)].reshape(ch, p)[:, :ln] for o, p, ln in zip(offsets, req.planes, counts)], info
     return [packed[ch * o:ch * (o + ln)].reshape(ln, ch) for o, ln in zip(offsets, counts)], info
@@ -1585,9 +1672,18 @@ class Context:
                   "opusgpu_tracks_loudness_device")
         return out
 
+    def tracks_fill_tail(self, spans, format, channels, d_tracks, stream=None):
+        """opusgpu_tracks_fill_tail_device: zero samples [first, end) of every track named by spans (TAIL_SPAN_DTYPE records, or
+        rows of (track_offset, plane_samples, first, end)) in the device buffer d_tracks of `format` ("s16", "f32", "f32_planar")."""
+        if not (isinstance(spans, np.ndarray) and spans.dtype == TAIL_SPAN_DTYPE):
+            spans = np.array([tuple(int(v) for v in r) for r in spans], dtype=TAIL_SPAN_DTYPE)
+        spans = np.ascontiguousarray(spans)
+        self._chk(self.lib.opusgpu_tracks_fill_tail_device(self.h, spans.size, spans.ctypes.data, TRACK_FORMATS.get(format, format), channels,
+                                                           d_tracks, stream), "opusgpu_tracks_fill_tail_device")
+
     def decode_files(self, files, rfc=False, flags=PAGES_GROUP_BY_MODE, threads=1, batch=None, format=None, scale=None, out=None,
                      rate=None, mono=False, mix=None, features=None, n_mels=80, feature_layout="bands", resample=None, loudness=None,
-                     peak_limit=1.0, channel_weights=None):
+                     peak_limit=1.0, channel_weights=None, cuts=None, preroll=CUT_PREROLL, stride=None):
         """Whole Ogg Opus files -> (list of int16 arrays [samples, channels], one trimmed track per file, info).  The context's
         streams 0 .. len(files) - 1 are (re)allocated when there are too few and get fresh state; its mode is set to `rfc`.
         info: FILE_INFO_DTYPE records with two more fields: `final_status` (the first failed frame's code, else the plan's status)
@@ -1632,12 +1728,22 @@ class Context:
         a target in LUFS (e.g. -23.0): every track is then scaled by loudness_gain(record, target, peak_limit) on top of scale=,
         `gain` says by how much, and the result must be a float format or features (ValueError otherwise, before any device
         work).  peak_limit: the largest sample peak a gain may leave (<= 0: none).  channel_weights: one weight per decoded channel
-        in place of the defaults (loudness_weights).  The measurement is taken on all decoded channels, in front of mix and rate."""
+        in place of the defaults (loudness_weights).  The measurement is taken on all decoded channels, in front of mix and rate.
+        cuts: None, or a sequence of (file, start, count) or (file, start, count, preroll) in samples at 48 kHz (cut_seconds makes
+        them from seconds): the tracks are then these pieces of the files' whole-file tracks, one decoder stream per cut, each
+        decoded from a reset decoder that starts at least `preroll` samples (default 3840: 80 ms, RFC 7845 section 4.6) in front of
+        it (include/opusgpu.h WHOLE FILES / CUTS).  Tracks and info come back per cut; info gains `cut_first_packet`, `cut_packets`,
+        `cut_lead`, `cut_exact` and `cut_start`.  A cut with `cut_exact` is the whole-file track's slice bit for bit, any other is
+        not.  Every other keyword acts on the cuts as it does on files.  stride: None, or a multiple of 64 that holds every cut:
+        track t then begins at t * stride and is zero from its final length to the stride; with out= (n_cuts * stride * channels
+        elements) the result is that memory viewed as [n_cuts, stride, channels] ([n_cuts, channels, stride] planar) in place of
+        the list.  A stride goes with format=, scale=, out= and loudness= on "s16" only (ValueError otherwise)."""
         if mix is not None and mono:  # (files_request's first refusal, ahead of the plan as it always was)
             raise ValueError("mix and mono=True exclude each other: the row {8192, 8192} is mono")
         own = batch is None
         if own:
-            batch = FileBatch(files, channels=self.channels or 2, rfc=rfc, flags=flags, threads=threads)
+            batch = FileBatch(files, channels=self.channels or 2, rfc=rfc, flags=flags, threads=threads, cuts=cuts, preroll=preroll,
+                              stride=stride)
         try:
             req = files_request(batch, False, self.device, format, scale, out, rate, mono, mix, features, n_mels, feature_layout, resample,
                                 loudness, peak_limit, channel_weights)
@@ -1812,7 +1918,8 @@ class MultistreamContext:
                   "opusgpu_ms_tracks_assemble_device_as")
 
     def decode_files(self, files, rfc=False, threads=1, batch=None, format=None, scale=None, out=None, rate=None, mix=None, features=None,
-                     n_mels=80, feature_layout="bands", resample=None, loudness=None, peak_limit=1.0, channel_weights=None):
+                     n_mels=80, feature_layout="bands", resample=None, loudness=None, peak_limit=1.0, channel_weights=None, cuts=None,
+                     preroll=CUT_PREROLL, stride=None):
         """Whole Ogg Opus files of this object's layout -> (list of int16 arrays [samples, channels], one trimmed track per file,
         info), as Context.decode_files returns them: FILE_INFO_DTYPE records plus `final_status` and `bad_packet`, `track_samples`
         the FINAL length.  Decoders 0 .. len(files) - 1 get fresh state; the object's mode is set to the batch's.  batch: an
@@ -1822,10 +1929,10 @@ class MultistreamContext:
         features, n_mels, feature_layout: as for Context.decode_files, with mix="mono" or a matrix of one row.
         resample: as for Context.decode_files, all channels or those of the mix.  features may be a mel_spec(), kaldi_fbank() or kaldi_mfcc() record as there.
         loudness, peak_limit, channel_weights: as for Context.decode_files; the default weights are those of the layout's channel
-        count (1.41 for the rear pair, 0 for the LFE)."""
+        count (1.41 for the rear pair, 0 for the LFE).  cuts, preroll, stride: as for Context.decode_files."""
         own = batch is None
         if own:
-            batch = MsFileBatch(files, self.layout, rfc=rfc, threads=threads)
+            batch = MsFileBatch(files, self.layout, rfc=rfc, threads=threads, cuts=cuts, preroll=preroll, stride=stride)
         mem = None
         try:
             req = files_request(batch, True, self.device, format, scale, out, rate, False, mix, features, n_mels, feature_layout, resample,

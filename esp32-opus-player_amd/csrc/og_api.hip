@@ -1226,6 +1226,7 @@ static int grow(opusgpu_ctx *ctx, void **p, size_t *cap, size_t need) {
 #include "og_ms.hpp"
 #include "og_files_run.hpp"
 #include "og_tracks.hpp"
+#include "og_tracks_tail.hpp"
 #include "og_tracks_loudness.hpp"
 #include "og_tracks_resample.hpp"
 #include "og_tracks_resample_ratio.hpp"

@@ -19,6 +19,7 @@ struct og_batch {
     std::vector<int64_t> packet_start; // all files, file after file
     std::vector<size_t> packet_begin;  // n_files + 1
     int64_t track_samples = 0;
+    int64_t track_stride = 0; // a batch of cuts at a fixed stride (WHOLE FILES / CUTS): track t begins at t * track_stride; 0: packed
 
     // the planned start of packet `packet_seq` of file `file` (its packet count: the track length); -1 for bad arguments
     int64_t packet_start_of(int file, int packet_seq) const {

@@ -408,7 +408,7 @@ static int ms_files_decode_run(opusgpu_ms *ms, const opusgpu_ms_file_batch *batc
     ops.hip_failed = track_fail(ms);
     ops.loop_begin = [&] { timer.reset(new MsStepTimer(s)); };
     ops.loop_end = [&] { timer->stop(); };
-    const int rc = files_run(*batch, ops, d_tracks, track_lengths_out, status_out);
+    const int rc = files_run_tails(*batch, ops, s, format, d_tracks, track_lengths_out, status_out);
     if (!rc && timer) g_ms_files_steps_ms = timer->elapsed_ms();
     return rc;
 }
@@ -417,6 +417,10 @@ static int ms_files_decode_run(opusgpu_ms *ms, const opusgpu_ms_file_batch *batc
 static FilesOwner files_owner(opusgpu_ms *ms, const opusgpu_ms_file_batch *batch) {
     return FilesOwner{*batch, ms->device, ms->stream,
                       [=](void *d_s16, int64_t *lengths, int32_t *status) {
+                          if (batch->track_stride) {
+                              snprintf(ms->err, sizeof(ms->err), "%s", OG_STRIDE_REFUSED);
+                              return (int)OPUSGPU_BAD_ARG;
+                          }
                           return ms_files_decode_run(ms, batch, OPUSGPU_TRACKS_S16, nullptr, d_s16, lengths, status);
                       },
                       track_fail(ms), &ms->loud};

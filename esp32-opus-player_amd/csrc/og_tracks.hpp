@@ -222,7 +222,8 @@ static int track_places(const og_batch &b, int format, const float *scale, std::
     for (int i = 0; i < b.n_files; i++) {
         const float k = scale ? scale[i] : 1.0f / 32768;
         if (!std::isfinite(k)) return OPUSGPU_BAD_ARG;
-        places[i] = TrackPlace{b.info[i].track_offset, (b.info[i].track_samples + 63) / 64 * 64, k, 0};
+        // a track's planes lie its planned length, rounded up to 64, apart; those of a strided batch (WHOLE FILES / CUTS) its stride
+        places[i] = TrackPlace{b.info[i].track_offset, b.track_stride ? b.track_stride : (b.info[i].track_samples + 63) / 64 * 64, k, 0};
     }
     return OPUSGPU_OK;
 }
@@ -250,6 +251,24 @@ struct RsDevBuf {
         if (p) (void)hipFree(p);
     }
 };
+
+// files_run, and behind it the zeroed tails of a strided batch (og_tracks_tail.hpp: first = the final length, end = the stride), on
+// the stream `s` the steps ran on.  A packed batch is files_run alone: nothing new is queued.
+static int batch_fill_tails(const og_batch &b, int device, hipStream_t s, int format, const int64_t *final_lengths, void *d_tracks,
+                            const TrackFail &hip_failed);
+static int files_run_tails(const og_batch &b, const FilesRunOps &ops, hipStream_t s, int format, void *d_tracks, int64_t *track_lengths_out,
+                           int32_t *status_out) {
+    if (!b.track_stride) return files_run(b, ops, d_tracks, track_lengths_out, status_out);
+    std::vector<int64_t> lengths((size_t)b.n_files, 0);
+    if (int rc = files_run(b, ops, d_tracks, lengths.data(), status_out)) return rc;
+    if (int rc = batch_fill_tails(b, ops.device, s, format, lengths.data(), d_tracks, ops.hip_failed)) return rc;
+    if (track_lengths_out) std::copy(lengths.begin(), lengths.end(), track_lengths_out);
+    return OPUSGPU_OK;
+}
+// What a whole-file call that ends in another kernel answers for a strided batch: its output has a grid of its own.
+#define OG_STRIDE_REFUSED                                                                                                    \
+    "the batch has a track stride, which only the tracks at 48 kHz of opusgpu_files_decode and opusgpu_files_decode_as keep: " \
+    "resampled, mixed and feature outputs have grids of their own -- plan the cuts with track_stride 0 for these calls"
 
 // opusgpu_files_decode and opusgpu_files_decode_as: `places` is null for int16 tracks, else the batch's table for `format`.
 // Nothing of the driver depends on the format: the PCM rows and result codes the steps write are the same, and the float assembly
@@ -282,7 +301,7 @@ static int files_decode_run(opusgpu_ctx *ctx, const opusgpu_file_batch *batch, i
         return e == hipSuccess ? (int)OPUSGPU_OK : fail(ctx, OPUSGPU_ERR_HIP, "hipStreamSynchronize(files)", e);
     };
     ops.hip_failed = track_fail(ctx);
-    return files_run(*batch, ops, d_tracks, track_lengths_out, status_out);
+    return files_run_tails(*batch, ops, ctx->stream, format, d_tracks, track_lengths_out, status_out);
 }
 
 // The owner of a whole-file call that ends in another kernel (TRACK RATES and all behind it): the batch, where its work runs, the
@@ -300,6 +319,10 @@ struct FilesOwner {
 static FilesOwner files_owner(opusgpu_ctx *ctx, const opusgpu_file_batch *batch) {
     return FilesOwner{*batch, ctx->device, ctx->stream,
                       [=](void *d_s16, int64_t *lengths, int32_t *status) {
+                          if (batch->track_stride) {
+                              snprintf(ctx->err, sizeof(ctx->err), "%s", OG_STRIDE_REFUSED);
+                              return (int)OPUSGPU_BAD_ARG;
+                          }
                           return files_decode_run(ctx, batch, OPUSGPU_TRACKS_S16, nullptr, d_s16, lengths, status);
                       },
                       track_fail(ctx), &ctx->loud};

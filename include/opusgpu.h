@@ -1243,6 +1243,81 @@ int opusgpu_ms_files_decode_fbank(opusgpu_ms *ms, const opusgpu_ms_file_batch *b
                                   const opusgpu_mix_matrix *mix, const opusgpu_fbank_params *p, const float *scale, void *d_out,
                                   int64_t *feat_offsets, int64_t *frames_out, int64_t *track_lengths_out, int32_t *status_out);
 
+/* ---- WHOLE FILES / CUTS: pieces of files as tracks, with pre-roll, packed or at a fixed stride -------------------------------
+ * A cut is samples [start, start + count) of a file's whole-file track (the axis opusgpu_files_plan makes: pre-skip, hole discards
+ * and end trimming applied), decoded as a stream of its own the way RFC 7845 section 4.6 says: from a RESET decoder, starting at a
+ * packet at least `preroll` decoded samples in front of `start`, the pre-roll thrown away.  The planner runs the reader ONCE per
+ * file, however many cuts point into it, and makes an ordinary batch: track t and decoder stream t are cut t, its k-th decoded frame
+ * goes in step k, and every accessor, opusgpu_files_decode* call, loudness request and kernel takes the batch as it takes any other.
+ * WHICH PACKETS.  pa: the packet with packet_start[pa] <= start < packet_start[pa + 1].  D[p]: the decoded samples (TOC durations)
+ * of the packets in front of p.  The lead a start at packet p gives is  D[pa] - D[p] + skip[pa] + (start - packet_start[pa])
+ * (skip: what pre-skip or a hole's 80 ms discard takes off the front of pa).  first_packet is the largest p <= pa whose lead is at
+ * least `preroll`; if there is none it is 0.  The last packet is the one that holds sample start + count - 1.  Packets outside
+ * [first_packet, last] get no descriptor.
+ * EXACT.  first_packet == 0: the cut's decoder sees what the whole file's decoder saw, and the cut is the whole-file track's slice
+ * bit for bit.  Any other cut starts from reset state and is NOT bit-identical to that slice; it converges to it over the pre-roll
+ * (DESIGN 13j has figures per mode).
+ * CLAMPING.  start is clamped to [0, track length], count (< 0: to the end) to what is left.  A cut of 0 samples is legal: it has
+ * no packets and no frames, lead 0, exact 1.
+ * SEGMENTS of a cut keep, of the reader's kept range of every frame, what also lies in the cut; dst_first is relative to the cut's
+ * start (plus the track's offset).  Frames wholly in the pre-roll keep a segment of count 0, whose result still counts.  packet_seq
+ * counts from first_packet, and opusgpu_file_batch_packet_start(b, t, seq) is the cut's own table: 0 for the pre-roll packets, so a
+ * failed frame in the pre-roll ends the cut at 0 samples and one inside it at its packet's start, by the FAILED FRAMES rule as it is.
+ * BYTES.  The arena holds, per file, the bytes from the earliest first_packet to the latest last packet of its cuts, once;
+ * descriptors of different cuts may name the same bytes.
+ * INFO.  info[t]: the file's header fields, status and holes, with the cut's track_samples, track_offset, packets and frames.  A
+ * file the whole-file planner refuses gives each of its cuts that status and no frames; a plan that ends in an error gives each
+ * cut the status, and the cuts are clamped to the track planned up to there.  OPUSGPU_STEP_KEEPS_MODE is formed over the cuts'
+ * own frames.
+ * STRIDE.  track_stride 0: tracks are packed at multiples of 64 samples, as always.  Otherwise (a multiple of 64, at least every
+ * clamped count, else OPUSGPU_BAD_ARG) track t begins at t * track_stride, opusgpu_file_batch_track_samples is n_cuts *
+ * track_stride, the planes of OPUSGPU_TRACKS_F32_PLANAR lie track_stride apart, and opusgpu_files_decode / _as (and their
+ * multistream twins) set every sample between a track's FINAL length and the stride to zero behind the last step
+ * (opusgpu_tracks_fill_tail_device): the buffer is a [n_cuts, track_stride, channels] tensor ([n_cuts, channels, track_stride]
+ * planar).  The resampled and feature outputs have grids of their own: every call that ends in another kernel refuses a strided
+ * batch with OPUSGPU_BAD_ARG and says so in opusgpu_last_error.  Packed cut batches work with all of them.
+ * Returns OPUSGPU_OK, OPUSGPU_ALLOC_FAIL, or OPUSGPU_BAD_ARG: what opusgpu_files_plan refuses, n_cuts < 0, cuts NULL with n_cuts > 0,
+ * a `file` outside [0, n_files), a bad stride.  info (n_cuts entries) and cut_info (n_cuts entries) may be NULL.  Host only. */
+typedef struct opusgpu_cut { /* 24 bytes (ABI) */
+    int32_t file;    /* index into files[] */
+    int32_t preroll; /* decoded samples per channel at 48 kHz wanted in front of `start`; < 0: 3840 (80 ms) */
+    int64_t start;   /* first sample, on the axis of the file's whole-file track */
+    int64_t count;   /* samples per channel; < 0: to the end of the track */
+} opusgpu_cut;
+typedef struct opusgpu_cut_info { /* 24 bytes (ABI) */
+    int32_t first_packet; /* packet_seq, in the file, of the first packet decoded for the cut */
+    int32_t packets;      /* packets decoded for it */
+    int32_t lead;         /* decoded samples in front of `start` that the cut really gets (>= preroll unless exact) */
+    int32_t exact;        /* 1: decoding starts at the file's first packet */
+    int64_t start;        /* the cut's start after clamping to [0, track length] */
+} opusgpu_cut_info;
+#define OPUSGPU_CUT_PREROLL 3840
+int opusgpu_files_plan_cuts(int n_files, const uint8_t *const *files, const int64_t *file_lens, int n_cuts, const opusgpu_cut *cuts,
+                            int64_t track_stride, int channels, int mode, int flags, int threads, opusgpu_file_info *info,
+                            opusgpu_cut_info *cut_info, opusgpu_file_batch **out);
+int opusgpu_ms_files_plan_cuts(int n_files, const uint8_t *const *files, const int64_t *file_lens, int n_cuts, const opusgpu_cut *cuts,
+                               int64_t track_stride, const opusgpu_ms_layout *layout, int mode, int threads, opusgpu_file_info *info,
+                               opusgpu_cut_info *cut_info, opusgpu_ms_file_batch **out);
+/* The batch's stride in samples per channel; 0 for a packed batch (every batch of opusgpu_files_plan); -1 for NULL. */
+int64_t opusgpu_file_batch_track_stride(const opusgpu_file_batch *b);
+int64_t opusgpu_ms_file_batch_track_stride(const opusgpu_ms_file_batch *b);
+
+/* k_tracks_fill_tail: sets samples [first, end) per channel of every named track to zero, in the element size and placement of
+ * `format` (OPUSGPU_TRACKS_*; placement as opusgpu_track_place says: interleaved, sample n of a track is elements channels *
+ * (track_offset + n) ..; planar, channel c's are  channels * track_offset + c * plane_samples + n).  spans: HOST array, one per
+ * track; 0 <= first <= end, track_offset >= 0, and for the planar format end <= plane_samples; an empty range writes nothing.
+ * channels 1 .. 8.  One launch for all tracks: a lane owns an aligned 16-byte piece of the buffer and stores it whole; the first
+ * and last piece of a range, where covered in part, go out as element stores, so nothing outside a range is touched.  d_tracks is
+ * 128-byte aligned; the caller guarantees that the ranges lie inside it.  Queued on the context's stream (or `hip_stream`); the
+ * call returns when the kernel has finished.  OPUSGPU_BAD_ARG for a span that breaks a rule. */
+typedef struct opusgpu_tail_span { /* 32 bytes, one per track (ABI) */
+    int64_t track_offset;  /* where the track begins in the buffer, samples per channel */
+    int64_t plane_samples; /* planar: distance between the track's planes; interleaved: not read */
+    int64_t first, end;    /* samples per channel of the track to zero: [first, end) */
+} opusgpu_tail_span;
+int opusgpu_tracks_fill_tail_device(opusgpu_ctx *ctx, int n_tracks, const opusgpu_tail_span *spans, int format, int channels,
+                                    void *d_tracks, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

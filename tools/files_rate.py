@@ -30,6 +30,10 @@ kernels alone per output sample (tools/ratio_rate.py).
 LOUDNESS; tools/loudness_rate.py): float32 tracks at 48 kHz, or mono ones at --rate, without the request, with loudness="measure"
 and, with a TARGET in LUFS, normalising -- interleaved; the added time per call and its share of the call.  Tracks need 400 ms for
 a block: --packets-per-file 500 gives 10 s files.
+--cuts C --cut-seconds S [--stride] --n F --packets-per-file P: F long files of P packets decoded whole, then C random cuts of S
+seconds out of each as F x C tracks (include/opusgpu.h WHOLE FILES / CUTS; tools/cuts_rate.py), pipelined: both times, audio seconds
+out per second for both, both planner times, the pre-roll's share; --stride adds cuts of unequal length packed and strided, whose
+difference is what the zeroed tails cost.  --stats DIR --tail-bytes B reads k_tracks_fill_tail's row of a kernel trace of that run.
 usage (GPU box): python3 tools/files_rate.py [--n N] [--reps R] [--loudness [T] |--format F | --rate R [--mono | --mix M] | --resample U/D [--mono | --mix M] | --mel [--n-mels N] | --melspec SET | --fbank SET] [--packets-per-file P] | python3 tools/files_rate.py --stats DIR [--n N]"""
 import argparse
 import ctypes as C
@@ -67,15 +71,23 @@ ap.add_argument("--fbank", choices=["wenet", "mfcc", "mfcc8k", "wide"], default=
 ap.add_argument("--packets-per-file", type=int, default=10, help="with --mel, --melspec, --fbank or --loudness: packets of 20 ms per file")
 ap.add_argument("--loudness", nargs="?", const="measure", default=None, metavar="TARGET",
                 help="what a loudness request adds to the float32 call, measuring and (with a target in LUFS) normalising (tools/loudness_rate.py)")
+ap.add_argument("--cuts", type=int, default=None, metavar="C", help="C random cuts per file next to the whole files (tools/cuts_rate.py)")
+ap.add_argument("--cut-seconds", type=float, default=10.0, metavar="S")
+ap.add_argument("--stride", action="store_true", help="with --cuts: cuts of unequal length, packed and at a stride with zeroed tails")
+ap.add_argument("--tail-bytes", type=int, default=None, help="with --stats: stride.tail_bytes_s16 of the traced --cuts --stride run")
+ap.add_argument("--whole-reps", type=int, default=3, help="with --cuts: timed whole-file batches (a step per packet: long)")
 args = ap.parse_args()
+if args.cuts is not None and (args.fbank or args.loudness or args.melspec or args.mel or args.resample or args.rate or args.format or args.mix or
+                              args.mono):
+    ap.error("--cuts goes alone (with --cut-seconds, --stride, --n, --packets-per-file, --reps, --whole-reps)")
 if args.fbank and (args.rate or args.format or args.resample or args.mel or args.melspec or args.loudness or args.mix or args.mono):
     ap.error("--fbank goes alone")
 if args.loudness and (args.format or args.mel or args.melspec or args.resample or args.mix or (args.rate and not args.mono)):
     ap.error("--loudness goes alone or with --rate R --mono")
 if args.melspec and (args.rate or args.format or args.resample or args.mel):
     ap.error("--melspec goes without --rate, --resample, --format and --mel")
-if args.packets_per_file != 10 and not (args.mel or args.melspec or args.fbank or args.loudness):
-    ap.error("--packets-per-file goes with --mel, --melspec, --fbank or --loudness")
+if args.packets_per_file != 10 and not (args.mel or args.melspec or args.fbank or args.loudness or args.cuts is not None):
+    ap.error("--packets-per-file goes with --mel, --melspec, --fbank, --loudness or --cuts")
 if args.mix and (args.mono or not (args.rate or args.resample)):
     ap.error("--mix goes with --rate or --resample and without --mono")
 if args.mel and (args.rate or args.format or args.resample):
@@ -101,9 +113,16 @@ if args.stats:
     import csv
     rows = []
     for f in glob.glob(os.path.join(args.stats, "**", "*kernel_stats.csv"), recursive=True):
-        rows += [r for r in csv.DictReader(open(f)) if "k_tracks_assemble" in r["Name"] or "k_tracks_resample" in r["Name"]]
+        rows += [r for r in csv.DictReader(open(f)) if any(k in r["Name"] for k in ("k_tracks_assemble", "k_tracks_resample", "k_tracks_fill_tail"))]
     assert rows, "no k_tracks_assemble in the kernel statistics"
     for r in rows:
+        if "k_tracks_fill_tail" in r["Name"]:  # one launch per strided batch; --tail-bytes: what the run's record says it zeroes
+            o = {"kernel": r["Name"].split("(")[0], "calls": int(r["Calls"]), "avg_ms_per_launch": round(float(r["AverageNs"]) / 1e6, 4),
+                 "min_ms": round(float(r["MinNs"]) / 1e6, 4), "max_ms": round(float(r["MaxNs"]) / 1e6, 4)}
+            if args.tail_bytes:
+                o["bytes_per_launch"], o["tb_per_s"] = args.tail_bytes, round(args.tail_bytes / (float(r["AverageNs"]) / 1e9) / 1e12, 2)
+            print(json.dumps(o))
+            continue
         if "k_tracks_resample" in r["Name"]:  # one launch per batch; its bytes depend on rate and format: time only
             print(json.dumps({"kernel": r["Name"].split("(")[0], "calls": int(r["Calls"]), "avg_ms_per_launch": round(float(r["AverageNs"]) / 1e6, 4),
                               "min_ms": round(float(r["MinNs"]) / 1e6, 4), "s16_bytes_read_per_batch": MOVED // 2}))
@@ -113,6 +132,20 @@ if args.stats:
         print(json.dumps({"kernel": r["Name"].split("(")[0], "calls": int(r["Calls"]), "avg_ms_per_launch": round(avg_ms, 4),
                           "min_ms": round(float(r["MinNs"]) / 1e6, 4), "ms_per_batch_of_10": round(avg_ms * 10, 3),
                           "bytes_per_batch": moved, "tb_per_s": round(moved / 10 / (avg_ms / 1e3) / 1e12, 2)}))
+    raise SystemExit(0)
+
+if args.cuts is not None:
+    import cuts_rate
+    blobs = [r.tobytes() for r in files]
+    ctx = pkg.Context(0)
+    ctx.streams_alloc(n * args.cuts, 2)
+    ctx.set_pipeline(1)
+    ctx.set_mode(False)
+    print(json.dumps(cuts_rate.compare(
+        pkg, ctx, lambda **kw: pkg.FileBatch(blobs, channels=2, flags=pkg.PAGES_GROUP_BY_MODE, threads=args.threads, **kw),
+        lambda b, d, ln, st: ctx._chk(ctx.lib.opusgpu_files_decode(ctx.h, b.h, d, ln, st), "opusgpu_files_decode"), blobs, args.cuts,
+        args.cut_seconds, args.stride, args.reps, args.whole_reps, 3, f"stereo CELT-FB, {args.threads} planner threads, pipelined")))
+    ctx.close()
     raise SystemExit(0)
 
 if args.loudness:

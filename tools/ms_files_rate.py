@@ -28,6 +28,8 @@ float32 48 kHz tracks resampled by a polyphase conv1d in torch, and the two kern
 LOUDNESS; tools/loudness_rate.py): without the request, with loudness="measure" and, with a TARGET in LUFS, normalising --
 interleaved; the added time per call and its share of the call.  P (at most 80: one page) packets per file in place of 10: tracks
 need 400 ms for a block.
+--cuts C [--cut-seconds S] [--stride] [--packets-per-file P]: the files (one page, P <= 80 packets) decoded whole, then C random cuts
+of S seconds out of each as N x C tracks (include/opusgpu.h WHOLE FILES / CUTS; tools/cuts_rate.py, as tools/files_rate.py --cuts).
 usage (GPU box): python3 tools/ms_files_rate.py [--n N] [--reps R] [--loudness [T] [--packets-per-file P] | --format F | --rate R [--mix M] | --resample U/D [--mix M] | --mel [--n-mels N] | --melspec SET | --fbank SET] | python3 tools/ms_files_rate.py --stats DIR [--n N]"""
 import argparse
 import ctypes as C
@@ -63,13 +65,19 @@ ap.add_argument("--fbank", choices=["wenet", "mfcc", "mfcc8k", "wide"], default=
 ap.add_argument("--loudness", nargs="?", const="measure", default=None, metavar="TARGET",
                 help="what a loudness request adds to the float32 call, measuring and (with a target in LUFS) normalising (tools/loudness_rate.py)")
 ap.add_argument("--packets-per-file", type=int, default=10, help="with --loudness: packets of 20 ms per file, at most 80")
+ap.add_argument("--cuts", type=int, default=None, metavar="C", help="C random cuts per file next to the whole files (tools/cuts_rate.py)")
+ap.add_argument("--cut-seconds", type=float, default=0.5, metavar="S")
+ap.add_argument("--stride", action="store_true", help="with --cuts: cuts of unequal length, packed and at a stride with zeroed tails")
+ap.add_argument("--whole-reps", type=int, default=3, help="with --cuts: timed whole-file batches")
 args = ap.parse_args()
+if args.cuts is not None and (args.fbank or args.loudness or args.melspec or args.mel or args.resample or args.rate or args.format or args.mix):
+    ap.error("--cuts goes alone (with --cut-seconds, --stride, --n, --packets-per-file, --reps, --whole-reps)")
 if args.fbank and (args.rate or args.format or args.resample or args.mel or args.melspec or args.loudness or args.mix):
     ap.error("--fbank goes alone")
 if args.loudness and (args.format or args.rate or args.mel or args.melspec or args.resample or args.mix):
     ap.error("--loudness goes alone")
-if args.packets_per_file != 10 and (not args.loudness or not 1 <= args.packets_per_file <= 80):
-    ap.error("--packets-per-file goes with --loudness and is at most 80: the files have one page")
+if args.packets_per_file != 10 and (not (args.loudness or args.cuts is not None) or not 1 <= args.packets_per_file <= 80):
+    ap.error("--packets-per-file goes with --loudness or --cuts and is at most 80: the files have one page")
 if args.melspec and (args.rate or args.format or args.resample or args.mel):
     ap.error("--melspec goes without --rate, --resample, --format and --mel")
 if args.mix and not (args.rate or args.resample):
@@ -168,6 +176,21 @@ b = pkg.MsFileBatch(blobs, LAYOUT, threads=args.threads)
 plan_s = time.perf_counter() - t0
 assert (b.info["status"] == 0).all() and b.n_steps == PACKETS, (np.unique(b.info["status"]), b.n_steps)
 assert (b.info["track_samples"] == PACKETS * 960 - pre - trim).all()
+
+if args.cuts is not None:  # F files of P <= 80 packets whole, then C cuts of S seconds out of each (tools/cuts_rate.py)
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import cuts_rate
+    b.close()
+    ms = pkg.MultistreamContext(0, n * args.cuts, *LAYOUT)
+    ms.set_mode(False)
+    mem = pkg.Context(0)  # (device memory is a plain context's call)
+    print(json.dumps(cuts_rate.compare(
+        pkg, mem, lambda **kw: pkg.MsFileBatch(blobs, LAYOUT, threads=args.threads, **kw),
+        lambda bt, d, ln, st: ms._chk(ms.lib.opusgpu_ms_files_decode(ms.h, bt.h, d, ln, st), "opusgpu_ms_files_decode"), blobs, args.cuts,
+        args.cut_seconds, args.stride, args.reps, args.whole_reps, 3, f"5.1 CELT-FB, {args.threads} planner threads")))
+    mem.close()
+    ms.close()
+    raise SystemExit(0)
 
 if args.loudness:
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
