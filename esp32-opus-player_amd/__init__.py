@@ -54,6 +54,7 @@ EXPORTS = [
     "opusgpu_ms_set_loudness", "opusgpu_ms_last_loudness",
     "opusgpu_files_plan_cuts", "opusgpu_ms_files_plan_cuts", "opusgpu_file_batch_track_stride", "opusgpu_ms_file_batch_track_stride",
     "opusgpu_tracks_fill_tail_device",
+    "opusgpu_set_feature_batch", "opusgpu_ms_set_feature_batch", "opusgpu_feat_batch_layout", "opusgpu_tracks_feature_batch_device",
 ]
 
 
@@ -168,6 +169,13 @@ FBANK_FLOOR = 1.1920929e-07  # FLT_EPSILON, Kaldi's floor under the log
 LOUDNESS_SPAN_DTYPE = np.dtype([("in_offset", "<i8"), ("in_samples", "<i8")])
 LOUDNESS_DTYPE = np.dtype([("lufs", "<f4"), ("peak", "<f4"), ("blocks", "<i4"), ("gated", "<i4")])
 LOUDNESS_REQ_DTYPE = np.dtype([("mode", "<i4"), ("target_lufs", "<f4"), ("peak_limit", "<f4"), ("n_weights", "<i4"), ("weights", "<f4", (8,))])
+FEAT_BATCH_REQ_DTYPE = np.dtype([("stride_frames", "<i8"), ("var_floor", "<f8"), ("enabled", "<i4"), ("norm", "<i4"), ("pad_mode", "<i4"),
+                                 ("pad_value", "<f4"), ("range", "<f4"), ("add", "<f4"), ("mul", "<f4"), ("reserved", "<i4", (5,))])
+FEAT_SPAN_DTYPE = np.dtype([("grid_offset", "<i8"), ("plane", "<i8"), ("frames", "<i8")])
+FEAT_NORMS = {None: 0, "none": 0, "whisper": 1, "cmn": 2, "cmvn": 3, "affine": 4}
+FEAT_NORM_NONE, FEAT_NORM_WHISPER, FEAT_NORM_CMN, FEAT_NORM_CMVN, FEAT_NORM_AFFINE = range(5)
+FEAT_PAD_VALUE, FEAT_PAD_NORMALIZED = 0, 1
+FEAT_SEG = 1024  # OPUSGPU_FEAT_SEG: frames per segment of the statistics
 LOUDNESS_OFF, LOUDNESS_MEASURE, LOUDNESS_NORMALIZE = 0, 1, 2
 OPUSGPU_BAD_ARG, OPUSGPU_UNIMPLEMENTED, OPUSGPU_CELT_BAD_ARG = -1, -5, -18
 RFC_FRAME = 2880
@@ -331,6 +339,11 @@ def load_lib():
         getattr(lib, name).argtypes = [vp, vp]
     for name in ("opusgpu_last_loudness", "opusgpu_ms_last_loudness"):
         getattr(lib, name).argtypes = [vp, C.c_int, vp, vp]
+    for name in ("opusgpu_set_feature_batch", "opusgpu_ms_set_feature_batch"):
+        getattr(lib, name).argtypes = [vp, vp, vp, vp, C.c_int]
+    lib.opusgpu_feat_batch_layout.argtypes = [C.c_int, C.c_int, C.c_int64, vp]
+    lib.opusgpu_feat_batch_layout.restype = C.c_int64
+    lib.opusgpu_tracks_feature_batch_device.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
     _lib = lib
     return lib
 
@@ -1265,6 +1278,116 @@ def loudness_request(batch, loudness=None, peak_limit=1.0, channel_weights=None)
     return rec
 
 
+class FeatureNorm(typing.NamedTuple):
+    """feature_norm's record: a normalisation of FEATURE BATCHES with its numbers."""
+    norm: int           # FEAT_NORM_*
+    range: float = 8.0  # WHISPER: (max(x, m - range) + add) * mul
+    add: float = 4.0
+    mul: float = 0.25
+    var_floor: float = 1e-20  # CMVN: the floor under the variance (Kaldi's)
+    sub_vec: object = None    # AFFINE: (x - sub_vec[j]) * mul_vec[j], float32 arrays
+    mul_vec: object = None
+
+
+def feature_norm(kind, range=8.0, add=4.0, mul=0.25, var_floor=1e-20, sub=None, mul_vec=None):
+    """A normalisation for decode_files' normalize= with numbers of its own (include/opusgpu.h FEATURE BATCHES): kind is None / "none",
+    "whisper" (range, add, mul), "cmn", "cmvn" (var_floor) or "affine" (sub and mul_vec, one finite number per feature bin).  Raises
+    ValueError for an unknown kind, a number that is not finite, var_floor <= 0 and affine vectors that are absent, not finite or of
+    different lengths."""
+    if isinstance(kind, FeatureNorm):
+        return kind
+    if not isinstance(kind, (str, type(None))) or kind not in FEAT_NORMS:
+        raise ValueError(f"normalize must be None, 'whisper', 'cmn', 'cmvn', ('affine', sub, mul) or a feature_norm() record, not {kind!r}")
+    nums = [float(v) for v in (range, add, mul, var_floor)]
+    if not np.isfinite(nums).all() or nums[3] <= 0:
+        raise ValueError("range, add, mul and var_floor must be finite, and var_floor > 0")
+    norm = FEAT_NORMS[kind]
+    if norm != FEAT_NORM_AFFINE:
+        if sub is not None or mul_vec is not None:
+            raise ValueError("sub and mul_vec go with 'affine' only")
+        return FeatureNorm(norm, *nums)
+    if sub is None or mul_vec is None:
+        raise ValueError("'affine' needs sub and mul_vec, one number per feature bin each")
+    s, m = (np.ascontiguousarray(np.asarray(v, dtype=np.float32).reshape(-1)) for v in (sub, mul_vec))
+    if s.shape != m.shape or not 1 <= s.size <= 128 or not (np.isfinite(s).all() and np.isfinite(m).all()):
+        raise ValueError("the affine vectors must be finite and of one length, 1 - 128")
+    return FeatureNorm(norm, *nums, s, m)
+
+
+class FeatureBatch(typing.NamedTuple):
+    """The feature-batch request of one decode_files call: the opusgpu_feat_batch_req record (a FEAT_BATCH_REQ_DTYPE array of one), the
+    AFFINE vectors (float32 arrays or None), the features' width W and the stride S."""
+    rec: object
+    sub: object
+    mul: object
+    width: int
+    stride: int
+
+
+def feat_batch_layout(n, width, stride_frames):
+    """opusgpu_feat_batch_layout: the dense tensor of n tracks of stride_frames frames of `width` bins -> (feat_offsets [int64], total
+    floats)."""
+    offsets = np.zeros(max(int(n), 0), dtype=np.int64)
+    total = int(load_lib().opusgpu_feat_batch_layout(int(n), int(width), int(stride_frames), offsets.ctypes.data))
+    if total < 0:
+        raise ValueError(f"there is no feature batch of {n!r} tracks of {stride_frames!r} frames of {width!r} bins (stride * width <= 2^31 - 1)")
+    return offsets, total
+
+
+def feature_batch_request(planned_frames, width, feature_stride=None, normalize=None, feature_pad=None):
+    """What decode_files makes of feature_stride=, normalize= and feature_pad= for features of `width` bins whose tracks have
+    planned_frames[t] frames at their PLANNED lengths: a FeatureBatch.  feature_stride None: the largest planned F (at least 1).
+    normalize: None, "whisper", "cmn", "cmvn", ("affine", sub, mul) or a feature_norm() record.  feature_pad: None -- -10 normalised
+    under "whisper" (zero audio, as Whisper pads), else 0 verbatim --, a number (verbatim), or (number, "value" | "normalized").
+    Raises ValueError for an unknown normalize, affine vectors of the wrong width or not finite, a stride below a planned F and a
+    pad that is not finite."""
+    import numbers
+    planned_frames = np.asarray(planned_frames, dtype=np.int64)
+    if isinstance(normalize, tuple) and not isinstance(normalize, FeatureNorm):
+        if len(normalize) != 3 or normalize[0] != "affine":
+            raise ValueError(f"a normalize tuple must be ('affine', sub, mul), not {normalize!r}")
+        normalize = feature_norm("affine", sub=normalize[1], mul_vec=normalize[2])
+    fn = feature_norm(normalize)
+    if fn.norm == FEAT_NORM_AFFINE and fn.sub_vec.size != width:
+        raise ValueError(f"the affine vectors have {fn.sub_vec.size} entries, the features {width} bins")
+    most = int(planned_frames.max()) if planned_frames.size else 0
+    if feature_stride is None:
+        feature_stride = max(most, 1)
+    if not isinstance(feature_stride, numbers.Integral) or isinstance(feature_stride, bool) or feature_stride < 1:
+        raise ValueError(f"feature_stride must be an integer >= 1, not {feature_stride!r}")
+    if feature_stride < most:
+        raise ValueError(f"feature_stride {feature_stride} is below the {most} frames of the longest planned track")
+    if feature_pad is None:
+        feature_pad = (-10.0, "normalized") if fn.norm == FEAT_NORM_WHISPER else (0.0, "value")
+    if not isinstance(feature_pad, tuple):
+        feature_pad = (feature_pad, "value")
+    if (len(feature_pad) != 2 or feature_pad[1] not in ("value", "normalized") or not isinstance(feature_pad[0], numbers.Real) or
+            isinstance(feature_pad[0], bool) or not np.isfinite(feature_pad[0])):
+        raise ValueError(f"feature_pad must be a finite number or (number, 'value' | 'normalized'), not {feature_pad!r}")
+    feat_batch_layout(0, width, feature_stride)  # (stride * width must fit)
+    rec = np.zeros(1, dtype=FEAT_BATCH_REQ_DTYPE)
+    rec["enabled"], rec["stride_frames"], rec["norm"], rec["var_floor"] = 1, int(feature_stride), fn.norm, fn.var_floor
+    rec["pad_mode"], rec["pad_value"] = FEAT_PAD_NORMALIZED if feature_pad[1] == "normalized" else FEAT_PAD_VALUE, feature_pad[0]
+    rec["range"], rec["add"], rec["mul"] = fn.range, fn.add, fn.mul
+    return FeatureBatch(rec, fn.sub_vec, fn.mul_vec, int(width), int(feature_stride))
+
+
+def _planned_feature_frames(batch, req):
+    """The frames of every track of a "features" request at its PLANNED length."""
+    planned = np.asarray(batch.info["track_samples"], dtype=np.int64)
+    if req.entry == "files_decode_mel":
+        return -(-planned // 3) // MEL_HOP
+    rate, up, down = req.args[:3]
+    if rate:
+        up, down = 1, TRACK_RATES[rate]
+    frames = fbank_frames if req.params.dtype == FBANK_PARAMS_DTYPE else spec_frames
+    return frames(req.params, -(-planned * up // down))
+
+
+def _feature_width(params):
+    return fbank_width(params) if params.dtype == FBANK_PARAMS_DTYPE else int(params["n_mels"][0])
+
+
 class FilesRequest(typing.NamedTuple):
     """What one decode_files call asks of the library, made by files_request before any decoder is touched."""
     entry: str        # the C entry point without its opusgpu_ / opusgpu_ms_ prefix
@@ -1282,6 +1405,7 @@ class FilesRequest(typing.NamedTuple):
     loudness: object = None  # the loudness request's record (loudness_request) or None
     stride: int = 0   # a strided batch of cuts: every track `stride` samples per channel apart, zeros behind its final length
     cut_info: object = None  # the batch's CUT_INFO_DTYPE records (a batch of cuts) or None
+    feature_batch: object = None  # the FeatureBatch of feature_stride= / normalize= or None; with one, offsets and total are the dense tensor's
 
 
 STRIDE_REFUSED = ("the batch has a stride, which only tracks at 48 kHz keep (format=, scale=, out=, and loudness= with \"s16\"): resampled, "
@@ -1347,16 +1471,30 @@ def _files_request(batch, multistream=False, device=0, format=None, scale=None, 
 
 
 def files_request(batch, multistream=False, device=0, format=None, scale=None, out=None, rate=None, mono=False, mix=None, features=None,
-                  n_mels=80, feature_layout="bands", resample=None, loudness=None, peak_limit=1.0, channel_weights=None):
+                  n_mels=80, feature_layout="bands", resample=None, loudness=None, peak_limit=1.0, channel_weights=None,
+                  feature_stride=None, normalize=None, feature_pad=None):
     """The keywords of decode_files for a planned batch -> the FilesRequest that _run_files_request carries out (_files_request says
     how).  A batch of cuts (FileBatch(cuts=...)) is a batch like any other: the request carries its cut records, which only info
-    reads.  A strided one is refused here, as ValueError, with everything but tracks at 48 kHz; its planes lie the stride apart."""
+    reads.  A strided one is refused here, as ValueError, with everything but tracks at 48 kHz; its planes lie the stride apart.
+    feature_stride=, normalize= and feature_pad= (FEATURE BATCHES; feature_batch_request says what they may be) need features= and
+    turn the request's result into one dense tensor: its `feature_batch` carries the record, and total, offsets, planes (the stride
+    for every track) and the out= size check follow opusgpu_feat_batch_layout.  Without them the request is what it always was."""
     stride, cut_info = int(getattr(batch, "stride", 0) or 0), getattr(batch, "cut_info", None)
     if stride and (rate not in (None, 48000) or mono or mix is not None or features is not None or resample is not None or
                    (loudness is not None and format not in (None, "s16"))):
         raise ValueError(STRIDE_REFUSED)
-    req = _files_request(batch, multistream, device, format, scale, out, rate, mono, mix, features, n_mels, feature_layout, resample, loudness,
-                         peak_limit, channel_weights)
+    dense = feature_stride is not None or normalize is not None or feature_pad is not None
+    if dense and features is None:
+        raise ValueError("feature_stride=, normalize= and feature_pad= need features=")
+    req = _files_request(batch, multistream, device, format, scale, None if dense else out, rate, mono, mix, features, n_mels, feature_layout,
+                         resample, loudness, peak_limit, channel_weights)
+    if dense:
+        width = _feature_width(req.params)
+        fb = feature_batch_request(_planned_feature_frames(batch, req), width, feature_stride, normalize, feature_pad)
+        offsets, total = feat_batch_layout(batch.n_files, width, fb.stride)
+        if out is not None:
+            out = _out_flat(out, max(total, 1), "f32", device)
+        req = req._replace(feature_batch=fb, offsets=offsets, total=total, out=out, planes=np.full(batch.n_files, fb.stride, dtype=np.int64))
     if stride:
         req = req._replace(stride=stride, planes=np.full(batch.n_files, stride, dtype=np.int64))
     return req if cut_info is None else req._replace(cut_info=cut_info)
@@ -1370,7 +1508,9 @@ def _run_files_request(req, lib, prefix, handle, chk, batch, mem):
     length at 48 kHz; resampled tracks have `out_samples` and `out_offset` more; features `feat_offset`, and their `frames` is F, the
     track's feature frames (the plan's count of Opus frames is batch.info["frames"]).  With a loudness request (req.loudness) the
     request is set on the decoder for this call alone and cleared behind it, and info has `lufs`, `peak`, `loudness_blocks`,
-    `loudness_gated` and `gain` more."""
+    `loudness_gated` and `gain` more.  With a feature-batch request (req.feature_batch) that request is set and cleared the same way,
+    and the features are ONE float32 array or tensor [n, n_mels, S] or [n, S, n_mels] (with out=: a view of the caller's memory), padded
+    behind every track's info["frames"]; info["feat_offset"] is t * S * n_mels."""
     name = prefix + req.entry
     n, ch, fmt = batch.n_files, req.channels, req.fmt
     offsets, counts, lengths = (np.zeros(n, dtype=np.int64) for _ in range(3))
@@ -1383,7 +1523,19 @@ def _run_files_request(req, lib, prefix, handle, chk, batch, mem):
     loud = np.zeros(n, dtype=LOUDNESS_DTYPE)
     gains = np.ones(n, dtype=np.float64)
 
+    fb = req.feature_batch
+
     def run(d_out):
+        if fb is None:
+            return run_loud(d_out)
+        vecs = [None if v is None else v.ctypes.data for v in (fb.sub, fb.mul)]
+        chk(getattr(lib, prefix + "set_feature_batch")(handle, fb.rec.ctypes.data, *vecs, fb.width), prefix + "set_feature_batch")
+        try:
+            run_loud(d_out)
+        finally:
+            getattr(lib, prefix + "set_feature_batch")(handle, None, None, None, 0)
+
+    def run_loud(d_out):
         if req.loudness is None:
             chk(getattr(lib, name)(handle, batch.h, *head, d_out, *tail), name)
             return
@@ -1429,6 +1581,10 @@ def _run_files_request(req, lib, prefix, handle, chk, batch, mem):
         info[count_field], info[offset_field] = counts, offsets
     if req.kind == "features":
         n_mels = fbank_width(req.params) if req.params.dtype == FBANK_PARAMS_DTYPE else int(req.params["n_mels"][0])
+        if fb is not None:  # FEATURE BATCHES: one dense tensor, every track fb.stride frames, padded behind its info["frames"]
+            shape = (n, fb.stride, n_mels) if int(req.params["layout"][0]) == MEL_FRAMES_MAJOR else (n, n_mels, fb.stride)
+            dense = packed[:n * fb.stride * n_mels]
+            return (dense.view(*shape) if req.out is not None else dense.reshape(shape)), info
         if int(req.params["layout"][0]) == MEL_FRAMES_MAJOR:
             return [packed[o:o + F * n_mels].reshape(F, n_mels) for o, F in zip(offsets, counts)], info
         return [packed[o:o + n_mels * p].reshape(n_mels, p)[:, :F] for o, p, F in zip(offsets, req.planes, counts)], info
@@ -1650,6 +1806,16 @@ class Context:
         self._chk(self.lib.opusgpu_tracks_fbank_device(self.h, spans.size, spans.ctypes.data, d_in, rec.ctypes.data, d_out, stream),
                   "opusgpu_tracks_fbank_device")
 
+    def tracks_feature_batch_device(self, spans, width, feature_layout, request, d_grid, d_out, stream=None):
+        """k_feat_stats, k_feat_fold and k_feat_batch alone (include/opusgpu.h FEATURE BATCHES): spans a HOST array of FEAT_SPAN_DTYPE over
+        the packed float32 grid d_grid of `width` bins in feature_layout ("bands" or "frames"), request a FeatureBatch
+        (feature_batch_request), d_out the dense tensor of len(spans) * stride * width floats.  Waits for the kernels."""
+        spans = np.ascontiguousarray(spans, dtype=FEAT_SPAN_DTYPE)
+        vecs = [None if v is None else v.ctypes.data for v in (request.sub, request.mul)]
+        self._chk(self.lib.opusgpu_tracks_feature_batch_device(self.h, spans.size, spans.ctypes.data, int(width), MEL_LAYOUTS[feature_layout],
+                                                               request.rec.ctypes.data, *vecs, d_grid, d_out, stream),
+                  "opusgpu_tracks_feature_batch_device")
+
     def tracks_melspec_device(self, spans, d_in, rec, d_out, stream=None):
         """k_tracks_melspec alone (include/opusgpu.h TRACK SPECTROGRAMS): spans a HOST array of MEL_SPAN_DTYPE, d_in packed int16 mono
         tracks at the record's rate, rec a mel_spec record, d_out the float32 feature tracks.  Waits for the kernel."""
@@ -1683,7 +1849,8 @@ class Context:
 
     def decode_files(self, files, rfc=False, flags=PAGES_GROUP_BY_MODE, threads=1, batch=None, format=None, scale=None, out=None,
                      rate=None, mono=False, mix=None, features=None, n_mels=80, feature_layout="bands", resample=None, loudness=None,
-                     peak_limit=1.0, channel_weights=None, cuts=None, preroll=CUT_PREROLL, stride=None):
+                     peak_limit=1.0, channel_weights=None, cuts=None, preroll=CUT_PREROLL, stride=None, feature_stride=None, normalize=None,
+                     feature_pad=None):
         """Whole Ogg Opus files -> (list of int16 arrays [samples, channels], one trimmed track per file, info).  The context's
         streams 0 .. len(files) - 1 are (re)allocated when there are too few and get fresh state; its mode is set to `rfc`.
         info: FILE_INFO_DTYPE records with two more fields: `final_status` (the first failed frame's code, else the plan's status)
@@ -1708,7 +1875,7 @@ class Context:
         any format but "f32" (track_feature_args).  The result is a list of float32 arrays [n_mels, F] (feature_layout "bands") or
         [F, n_mels] ("frames"), F = ceil(len / 3) // 160, or views of `out` (mel_layout's total floats); info has `feat_offset` more
         and its `frames` is F (the plan's count of Opus frames stays in batch.info["frames"]).  Whisper's clip-wide max - 8 clamp
-        and (x + 4) / 4 are not applied: they are two torch operations on the result.
+        and (x + 4) / 4 are not applied: they are two torch operations on the result, or normalize="whisper" (below).
         resample: None, or (up, down) as for scipy.signal.resample_poly, or an output rate in Hz as an int, which is reduced against
         48000 -- 44100 is (147, 160), 32000 is (2, 3), 22050 is (147, 320) -- for tracks at 48000 up / down Hz by a rational FIR on
         the GPU (include/opusgpu.h TRACK RATIOS: integer arithmetic over the int16 track, bit-exact; track_ratio says which ratios
@@ -1737,7 +1904,16 @@ class Context:
         not.  Every other keyword acts on the cuts as it does on files.  stride: None, or a multiple of 64 that holds every cut:
         track t then begins at t * stride and is zero from its final length to the stride; with out= (n_cuts * stride * channels
         elements) the result is that memory viewed as [n_cuts, stride, channels] ([n_cuts, channels, stride] planar) in place of
-        the list.  A stride goes with format=, scale=, out= and loudness= on "s16" only (ValueError otherwise)."""
+        the list.  A stride goes with format=, scale=, out= and loudness= on "s16" only (ValueError otherwise).
+        feature_stride, normalize, feature_pad (with features= only; include/opusgpu.h FEATURE BATCHES): the features as ONE float32
+        array [n, n_mels, S] ("bands") or [n, S, n_mels] ("frames") -- with out= (n * S * n_mels floats) a view of it --, every track
+        normalised by statistics of its own info["frames"] real frames and padded to S = feature_stride frames (any integer that holds
+        every planned track, 3000 for Whisper; None: the longest planned track's frames); info["feat_offset"] is t * S * n_mels.
+        normalize: None, "whisper" ((max(x, track max - 8) + 4) / 4), "cmn" (per-bin mean removed, Kaldi's subtract_mean), "cmvn" (and
+        divided by the per-bin standard deviation), ("affine", sub, mul) ((x - sub[j]) * mul[j], global CMVN), or a feature_norm()
+        record with numbers of its own.  feature_pad: the pad cells' value, a number (verbatim) or (number, "normalized") for the
+        track's normalisation of it; None is (-10, "normalized") under "whisper" -- the log-mel of zero audio, as Whisper pads --
+        and 0 otherwise.  The batch's own stride= is still refused with features."""
         if mix is not None and mono:  # (files_request's first refusal, ahead of the plan as it always was)
             raise ValueError("mix and mono=True exclude each other: the row {8192, 8192} is mono")
         own = batch is None
@@ -1746,7 +1922,7 @@ class Context:
                               stride=stride)
         try:
             req = files_request(batch, False, self.device, format, scale, out, rate, mono, mix, features, n_mels, feature_layout, resample,
-                                loudness, peak_limit, channel_weights)
+                                loudness, peak_limit, channel_weights, feature_stride, normalize, feature_pad)
             if self.n_streams < batch.n_files or self.channels != batch.channels:
                 self.streams_alloc(max(batch.n_files, 1), batch.channels)
             self.set_mode(batch.rfc)
@@ -1919,7 +2095,7 @@ class MultistreamContext:
 
     def decode_files(self, files, rfc=False, threads=1, batch=None, format=None, scale=None, out=None, rate=None, mix=None, features=None,
                      n_mels=80, feature_layout="bands", resample=None, loudness=None, peak_limit=1.0, channel_weights=None, cuts=None,
-                     preroll=CUT_PREROLL, stride=None):
+                     preroll=CUT_PREROLL, stride=None, feature_stride=None, normalize=None, feature_pad=None):
         """Whole Ogg Opus files of this object's layout -> (list of int16 arrays [samples, channels], one trimmed track per file,
         info), as Context.decode_files returns them: FILE_INFO_DTYPE records plus `final_status` and `bad_packet`, `track_samples`
         the FINAL length.  Decoders 0 .. len(files) - 1 get fresh state; the object's mode is set to the batch's.  batch: an
@@ -1929,14 +2105,15 @@ class MultistreamContext:
         features, n_mels, feature_layout: as for Context.decode_files, with mix="mono" or a matrix of one row.
         resample: as for Context.decode_files, all channels or those of the mix.  features may be a mel_spec(), kaldi_fbank() or kaldi_mfcc() record as there.
         loudness, peak_limit, channel_weights: as for Context.decode_files; the default weights are those of the layout's channel
-        count (1.41 for the rear pair, 0 for the LFE).  cuts, preroll, stride: as for Context.decode_files."""
+        count (1.41 for the rear pair, 0 for the LFE).  cuts, preroll, stride: as for Context.decode_files.
+        feature_stride, normalize, feature_pad: as for Context.decode_files."""
         own = batch is None
         if own:
             batch = MsFileBatch(files, self.layout, rfc=rfc, threads=threads, cuts=cuts, preroll=preroll, stride=stride)
         mem = None
         try:
             req = files_request(batch, True, self.device, format, scale, out, rate, False, mix, features, n_mels, feature_layout, resample,
-                                loudness, peak_limit, channel_weights)
+                                loudness, peak_limit, channel_weights, feature_stride, normalize, feature_pad)
             mem = Context(self.device)  # (device memory and copies are a plain context's calls)
             self.set_mode(batch.rfc)
             return _run_files_request(req, self.lib, "opusgpu_ms_", self.h, self._chk, batch, mem)

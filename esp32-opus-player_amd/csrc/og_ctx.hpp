@@ -88,6 +88,13 @@ struct LoudnessState {
     std::vector<double> gains;
 };
 
+// FEATURE BATCHES: the request that holds for the whole-file feature calls that follow (opusgpu_set_feature_batch), with its own
+// copies of the AFFINE vectors.  One per context of either kind.
+struct FeatBatchState {
+    opusgpu_feat_batch_req req{}; // enabled 0: off
+    std::vector<float> sub, mul;
+};
+
 struct opusgpu_ctx {
     int device = -1;
     hipStream_t stream = nullptr;
@@ -152,6 +159,7 @@ struct opusgpu_ctx {
     // opusgpu_decode_packets -- what a lost packet of that stream is concealed as (0 frames: nothing framed yet)
     std::vector<int32_t> last_count, last_flags;
     LoudnessState loud;
+    FeatBatchState fbatch;
     char err[256] = {0};
 };
 

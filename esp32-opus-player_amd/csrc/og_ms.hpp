@@ -177,6 +177,7 @@ struct opusgpu_ms {
     void *d_arena = nullptr, *d_place = nullptr, *d_out = nullptr, *d_res = nullptr;
     size_t cap_arena = 0, cap_place = 0, cap_out = 0, cap_res = 0;
     LoudnessState loud;
+    FeatBatchState fbatch;
     char err[256] = {0};
 };
 

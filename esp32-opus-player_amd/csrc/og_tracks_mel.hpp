@@ -358,8 +358,15 @@ struct FeatFlow {
     std::function<int64_t(int64_t planned_48k, int up, int down)> plane;
     std::function<int64_t(int64_t len)> frames;             // of a track of `len` samples at the features' rate
     std::function<int64_t(int n, const int64_t *planned_48k, int up, int down, int64_t *feat_offsets)> layout;
-    std::function<int(int n, const opusgpu_mel_span *spans, const void *d_in)> run; // the kernel, into d_out
+    std::function<int(int n, const opusgpu_mel_span *spans, const void *d_in, void *d_feat)> run; // the kernel, into the grid at d_feat
+    int width = 0, frames_major = 0;                        // of a cell's row and the grid's layout (FEATURE BATCHES reads them)
 };
+
+// FEATURE BATCHES (og_feat_batch.hpp, behind the feature headers): the stage that turns a packed grid into the dense tensor.
+static const char *feat_batch_shape_wrong(const opusgpu_feat_batch_req &r, int affine_width, int W);
+static int feat_batch_run(int device, hipStream_t s, int n_tracks, const opusgpu_feat_span *spans, int W, int layout,
+                          const opusgpu_feat_batch_req *req, const float *sub, const float *mul_vec, const void *d_grid, void *d_out,
+                          const TrackFail &hip_failed, const std::function<void(const char *)> &why);
 
 // Every whole-file call that ends in a feature kernel: what it refuses before any device work -- on top of the resampling call's own
 // refusals the result is one channel, at the rate the params name --, then files_resampled_run (`rate`, with up = down = 0) or
@@ -390,11 +397,30 @@ static int files_feature_run(const FilesOwner &own, int rate, int up, int down, 
     for (size_t i = 0; i < n; i++) planned[i] = b.info[i].track_samples;
     const int64_t total = rate ? opusgpu_resample_layout((int)n, planned.data(), rate, nullptr)
                                : opusgpu_resample_ratio_layout((int)n, planned.data(), up, down, nullptr);
-    if (total < 0 || flow.layout((int)n, planned.data(), up, down, feat.data()) < 0) return OPUSGPU_BAD_ARG;
+    const int64_t feat_total = total < 0 ? -1 : flow.layout((int)n, planned.data(), up, down, feat.data());
+    if (feat_total < 0) return OPUSGPU_BAD_ARG;
+    // FEATURE BATCHES: with a request on, the kernel writes a scratch grid and feat_batch_run the caller's buffer from there
+    const FeatBatchState *fb = own.fbatch && own.fbatch->req.enabled ? own.fbatch : nullptr;
+    if (fb) {
+        const char *bad = feat_batch_shape_wrong(fb->req, (int)fb->sub.size(), flow.width);
+        for (size_t i = 0; i < n && !bad; i++)
+            if (flow.frames((planned[i] * up + down - 1) / down) > fb->req.stride_frames)
+                bad = "feature batch: stride_frames is below the frames of a track's planned length";
+        if (bad) {
+            if (own.refused) own.refused(bad);
+            return OPUSGPU_BAD_ARG;
+        }
+    }
     RsDevBuf y; // the int16 mono tracks at the features' rate, for the length of this call
+    RsDevBuf grid; // FEATURE BATCHES: the packed features, for the length of this call
     if (!b.segs.empty()) {
         hipError_t e = hipSetDevice(own.device);
         if (e == hipSuccess) e = y.alloc((size_t)total * 2 + 128);
+        if (e != hipSuccess) return own.hip_failed(OPUSGPU_ALLOC_FAIL, flow.scratch_failed, e);
+    }
+    if (fb && n) {
+        hipError_t e = hipSetDevice(own.device);
+        if (e == hipSuccess) e = grid.alloc((size_t)feat_total * 4 + 128);
         if (e != hipSuccess) return own.hip_failed(OPUSGPU_ALLOC_FAIL, flow.scratch_failed, e);
     }
     FilesOwner inner = own; // TRACK LOUDNESS: measured there on the 48 kHz scratch, the gain applied here with the scale
@@ -408,7 +434,15 @@ static int files_feature_run(const FilesOwner &own, int rate, int up, int down, 
     for (size_t i = 0; i < n; i++)
         spans[i] = opusgpu_mel_span{offs[i], len[i], feat[i], flow.plane(planned[i], up, down),
                                     loud_normalizes(own) ? loud_scale(own, scale, i) : scale ? scale[i] : 1.0f / 32768, 0};
-    if (int rc2 = flow.run((int)n, spans.data(), y.p)) return rc2;
+    if (int rc2 = flow.run((int)n, spans.data(), y.p, fb ? grid.p : d_out)) return rc2;
+    if (fb) {
+        std::vector<opusgpu_feat_span> cells(n);
+        for (size_t i = 0; i < n; i++) cells[i] = opusgpu_feat_span{feat[i], spans[i].plane, flow.frames(len[i])};
+        if (int rc2 = feat_batch_run(own.device, own.stream, (int)n, cells.data(), flow.width, flow.frames_major, &fb->req, fb->sub.data(),
+                                     fb->mul.data(), grid.p, d_out, own.hip_failed, own.refused))
+            return rc2;
+        opusgpu_feat_batch_layout((int)n, flow.width, fb->req.stride_frames, feat.data());
+    }
     for (size_t i = 0; i < n; i++) {
         if (feat_offsets) feat_offsets[i] = feat[i];
         if (frames_out) frames_out[i] = flow.frames(len[i]);
@@ -427,8 +461,9 @@ static int files_mel_run(const FilesOwner &own, int mono, const opusgpu_mix_matr
     flow.plane = [](int64_t planned, int, int) { return mel_plane(planned); };
     flow.frames = [](int64_t len) { return len / OPUSGPU_MEL_HOP; };
     flow.layout = [=](int n, const int64_t *planned, int, int, int64_t *feat) { return opusgpu_mel_layout(n, planned, params, feat); };
-    flow.run = [&](int n, const opusgpu_mel_span *spans, const void *d_in) {
-        return tracks_mel_run(own.device, own.stream, n, spans, d_in, params, d_out, own.hip_failed);
+    if (flow.sample_rate) flow.width = params->n_mels, flow.frames_major = params->layout == OPUSGPU_MEL_FRAMES_MAJOR;
+    flow.run = [&](int n, const opusgpu_mel_span *spans, const void *d_in, void *d_feat) {
+        return tracks_mel_run(own.device, own.stream, n, spans, d_in, params, d_feat, own.hip_failed);
     };
     return files_feature_run(own, OPUSGPU_MEL_SR, 0, 0, mono, mix, scale, d_out, feat_offsets, frames_out, track_lengths_out, status_out, flow);
 }

@@ -332,8 +332,9 @@ static int files_melspec_run(const FilesOwner &own, int rate, int up, int down, 
     flow.layout = [=](int n, const int64_t *planned, int u, int d, int64_t *feat) {
         return opusgpu_spec_layout(n, planned, u, d, params, feat);
     };
-    flow.run = [&](int n, const opusgpu_mel_span *spans, const void *d_in) {
-        return tracks_melspec_run(own.device, own.stream, n, spans, d_in, params, d_out, own.hip_failed);
+    if (flow.sample_rate) flow.width = params->n_mels, flow.frames_major = params->layout == OPUSGPU_MEL_FRAMES_MAJOR;
+    flow.run = [&](int n, const opusgpu_mel_span *spans, const void *d_in, void *d_feat) {
+        return tracks_melspec_run(own.device, own.stream, n, spans, d_in, params, d_feat, own.hip_failed);
     };
     return files_feature_run(own, rate, up, down, mono, mix, scale, d_out, feat_offsets, frames_out, track_lengths_out, status_out, flow);
 }

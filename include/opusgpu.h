@@ -789,7 +789,8 @@ int opusgpu_files_decode_ratio(opusgpu_ctx *ctx, const opusgpu_file_batch *batch
  *   POWER.  P[k] = (sum_i Wc[i][k] x_i)^2 + (sum_i Ws[i][k] x_i)^2, k in [0, 201).
  *   MEL.  mel[j] = sum_k B[j][k] P[k], j in [0, n_mels).
  *   OUTPUT.  log10f(max(mel[j], 1e-10f)), float32.  Whisper's clip-wide max - 8 clamp and (x + 4) / 4 are two element-wise
- *   operations on the result and are left to the caller.
+ *   operations on the result and are left to the caller -- or to FEATURE BATCHES (below), which applies them per track while it
+ *   pads the features into one tensor.
  *   TABLES.  float32, each entry computed in double and rounded once, at first use (once per process):
  *       w[i] = 0.5 - 0.5 cos(2 pi i / 400)                       the periodic Hann window
  *       Wc[i][k] = w[i] cos(a), Ws[i][k] = w[i] sin(a),           a = 2 pi ((i k) mod 400) / 400: 2 pi i k / 400 reduced in integers
@@ -959,7 +960,7 @@ int opusgpu_files_decode_melspec(opusgpu_ctx *ctx, const opusgpu_file_batch *bat
  * unchanged.  The definition is this comment.
  *   INPUT.  An int16 mono track y[m], m in [0, n), exactly as TRACK RATES, TRACK RATIOS and CHANNEL MIX define it.
  *   NOT OFFERED.  Dither (the features are a function of the track); use_energy, raw_energy and energy_floor; htk_compat; VTLN
- *   warping; subtract_mean (one torch operation on the result).
+ *   warping; subtract_mean (one torch operation on the result, or OPUSGPU_FEAT_NORM_CMN of FEATURE BATCHES below).
  *   FRAMES.  L = frame_length, H = frame_shift.  snip_edges 1: F = 0 for n < L, else 1 + (n - L) / H (floor); frame f starts at s =
  *   f H: only whole windows inside the track.  snip_edges 0: F = (n + H / 2) / H; frame f starts at s = f H + H / 2 - L / 2 (integer
  *   halves), and an index q outside [0, n) is mapped by q < 0 -> -q - 1 and q >= n -> 2 n - 1 - q, REPEATED until it lies inside:
@@ -1133,6 +1134,94 @@ int opusgpu_set_loudness(opusgpu_ctx *ctx, const opusgpu_loudness_req *req);
 int opusgpu_last_loudness(const opusgpu_ctx *ctx, int n, opusgpu_loudness *records, double *gains);
 int opusgpu_ms_set_loudness(opusgpu_ms *ms, const opusgpu_loudness_req *req);
 int opusgpu_ms_last_loudness(const opusgpu_ms *ms, int n, opusgpu_loudness *records, double *gains);
+
+/* FEATURE BATCHES.  The features of a call as ONE dense tensor, padded to a common length and normalised per track, behind the
+ * feature kernels of TRACK FEATURES, TRACK SPECTROGRAMS and TRACK KALDI FEATURES: what a model takes -- a [B, 80, 3000] Whisper
+ * input, a [B, T, 80] fbank batch with per-utterance CMVN -- without a loop over tracks in the caller's code.  Those three sections
+ * and their kernels are unchanged; this stage reads their packed grid and writes a second buffer.  The definition is this comment.
+ *   INPUT.  A packed feature grid exactly as those sections lay it out: feat_offset[t] and plane[t] multiples of 64 floats, width
+ *   W in [1, 128] (n_mels, or n_ceps for MFCC), OPUSGPU_MEL_BANDS_MAJOR (cell (j, f) at feat_offset[t] + j * plane[t] + f) or
+ *   OPUSGPU_MEL_FRAMES_MAJOR (feat_offset[t] + f * W + j).  F[t] is the frame count of the track's FINAL length: cells f >= F[t] of
+ *   the grid are never interpreted.  The real cells are finite; the caller of the stand-alone call guarantees it (a feature kernel
+ *   with a log and a floor > 0 writes nothing else).
+ *   OUTPUT.  A dense float32 tensor of n_tracks * S * W floats, S = stride_frames, in the grid's own layout.  Bands-major: cell
+ *   (t, j, f) at (t * W + j) * S + f -- [n, W, S].  Frames-major: cell (t, f, j) at (t * S + f) * W + j -- [n, S, W].  EVERY element
+ *   is written exactly once, the pad cells f >= F[t] included; nothing outside the tensor is touched.  S is any integer >= 1 that
+ *   holds every track's frames, with S * W <= 0x7fffffff: 3000 is not a multiple of 64, and nothing is asked of S's alignment.
+ *   STATISTICS are per track, over its F[t] real cells only: they never depend on pad cells, on the grid's padding or on which
+ *   other tracks are in the call.
+ *   NORMALISATIONS (norm), x a real cell of bin j:
+ *     OPUSGPU_FEAT_NORM_NONE     y = x.
+ *     OPUSGPU_FEAT_NORM_WHISPER  m = the max over ALL real cells of the track (every bin); y = (fmaxf(x, m - range) + add) * mul:
+ *       one float32 subtraction for m - range, then three float32 operations, each rounded on its own, nothing fused.  Whisper's
+ *       numbers are range 8, add 4, mul 0.25.  F = 0 gives m = -inf.
+ *     OPUSGPU_FEAT_NORM_CMN      mean_j = (sum_f (double)x[f][j]) / F;  y = (float)((double)x - mean_j).  Kaldi's subtract_mean, and
+ *       apply-cmvn --norm-vars=false per utterance.
+ *     OPUSGPU_FEAT_NORM_CMVN     and var_j = (sum_f (double)x[f][j]^2) / F - mean_j^2, the population variance in double in one
+ *       pass;  y = (float)(((double)x - mean_j) / sqrt(max(var_j, var_floor))), var_floor finite and > 0.
+ *       F = 0 gives mean 0 and var 0 under both.
+ *     OPUSGPU_FEAT_NORM_AFFINE   y = (x - sub[j]) * mul[j] in float32, two rounded operations; sub and mul are host arrays of W
+ *       finite floats given with the request and copied: global CMVN, the dataset's statistics per bin.
+ *   PAD CELLS (pad_mode).  OPUSGPU_FEAT_PAD_VALUE: pad_value verbatim.  OPUSGPU_FEAT_PAD_NORMALIZED: the track's normalisation
+ *   applied to pad_value as if it were a cell of that track and bin; it takes no part in the statistics.  Whisper pads with zero
+ *   audio, whose cells are log10(1e-10) = -10 before the clamp: that is pad_value -10 with OPUSGPU_FEAT_PAD_NORMALIZED.  What this
+ *   does NOT reproduce of Whisper's pad_or_trim: there the last real frames' windows reach into the zeros, here they see the
+ *   track's own reflection, as TRACK FEATURES defines them.
+ *   CONTRACT.  The same bits from the same call on the same input: no float atomics, and a summation order that depends only on the
+ *   track's own F, W and layout -- segments of 1024 frames, each summed in a fixed order, folded in ascending order.  NONE, WHISPER
+ *   and AFFINE are bit-for-bit functions of the grid.  The sums are kept in double, so a track whose real cells all hold one value
+ *   c gives exactly 0.0f in every real cell under CMN and CMVN (F * c and its division by F are exact in double for F < 2^29, which
+ *   is also the most frames a track may have here).  Against the definition in exact arithmetic a CMN / CMVN cell differs by at most
+ *   2^-23 |y| + 2^-30 max_f |x[f][j]| / d, d = 1 or sqrt(max(var_j, var_floor)) (tests/test_gpu_feat_batch.py). */
+#define OPUSGPU_FEAT_NORM_NONE 0
+#define OPUSGPU_FEAT_NORM_WHISPER 1
+#define OPUSGPU_FEAT_NORM_CMN 2
+#define OPUSGPU_FEAT_NORM_CMVN 3
+#define OPUSGPU_FEAT_NORM_AFFINE 4
+#define OPUSGPU_FEAT_PAD_VALUE 0
+#define OPUSGPU_FEAT_PAD_NORMALIZED 1
+#define OPUSGPU_FEAT_SEG 1024 /* frames per segment of the statistics: part of the summation order */
+typedef struct opusgpu_feat_batch_req { /* 64 bytes (ABI) */
+    int64_t stride_frames; /* S, >= 1 */
+    double var_floor;      /* CMVN: finite and > 0 (Kaldi floors at 1e-20) */
+    int32_t enabled;       /* opusgpu_set_feature_batch: 0 is off; the stand-alone call does not read it */
+    int32_t norm;          /* OPUSGPU_FEAT_NORM_* */
+    int32_t pad_mode;      /* OPUSGPU_FEAT_PAD_* */
+    float pad_value;
+    float range, add, mul; /* WHISPER: 8, 4, 0.25 */
+    int32_t reserved[5];   /* 0 */
+} opusgpu_feat_batch_req;
+typedef struct opusgpu_feat_span { /* 24 bytes, one per track (ABI) */
+    int64_t grid_offset; /* feat_offset[t], in floats; a multiple of 64 */
+    int64_t plane;       /* plane[t]: a multiple of 64 and >= frames */
+    int64_t frames;      /* F[t], 0 <= F <= S and F < 2^29 */
+} opusgpu_feat_span;
+/* The request that holds for the whole-file FEATURE calls that follow, as opusgpu_set_loudness does for its own; NULL or `enabled`
+ * 0 is off, the default, and every call is then byte for byte what it is above.  sub and mul_vec: host arrays of `width` floats for
+ * OPUSGPU_FEAT_NORM_AFFINE, copied; not read otherwise.  OPUSGPU_BAD_ARG, the request in force left as it was: an unknown norm or
+ * pad mode; a field that is not finite (pad_value, range, add, mul, var_floor); var_floor <= 0; stride_frames < 1; AFFINE without
+ * both arrays, with a width outside 1 - 128 or with an entry that is not finite; a reserved word that is not 0.  With a request on,
+ * opusgpu_files_decode_mel, _melspec and _fbank and their opusgpu_ms_ twins run as above into a scratch grid of their own layout
+ * call, then this stage writes d_out, which is now opusgpu_feat_batch_layout's total in floats, 128-byte aligned; feat_offsets[t]
+ * reports t * S * W; frames_out, track_lengths_out and status_out are what they were; the scratch is freed on every way out and
+ * the caller's arrays are written last.  OPUSGPU_BAD_ARG before any device work, the buffer and the arrays left as they were, with
+ * the reason in opusgpu_last_error: S below the frames of a track's PLANNED length; S * W above 0x7fffffff; AFFINE whose width is
+ * not the features' W.  A loudness request composes untouched: its gain is in the feature kernel's scale.  Whole-file calls
+ * without features ignore the request. */
+int opusgpu_set_feature_batch(opusgpu_ctx *ctx, const opusgpu_feat_batch_req *req, const float *sub, const float *mul_vec, int width);
+int opusgpu_ms_set_feature_batch(opusgpu_ms *ms, const opusgpu_feat_batch_req *req, const float *sub, const float *mul_vec, int width);
+/* OUTPUT above for n tracks: writes feat_offsets[t] = t * S * W (may be NULL) and returns the total n * S * W in floats.
+ * OPUSGPU_BAD_ARG: n < 0, width outside 1 - 128, stride_frames < 1, S * W above 0x7fffffff.  Host only. */
+int64_t opusgpu_feat_batch_layout(int n, int width, int64_t stride_frames, int64_t *feat_offsets);
+/* The stage alone over a packed grid in device memory (k_feat_stats, k_feat_fold, k_feat_batch): `spans` is a HOST array of n_tracks
+ * records, tracks come out in span order; d_grid floats, 128-byte aligned, read in aligned 16-byte pieces inside a track's plane;
+ * d_out n_tracks * S * W floats, 128-byte aligned, not overlapping the grid.  sub, mul_vec: as for opusgpu_set_feature_batch, `width`
+ * of them.  Uploads the spans, its segment table and the vectors, launches on the context's stream (or `hip_stream`), waits, and
+ * frees everything on every way out.  OPUSGPU_BAD_ARG before any device work: what opusgpu_set_feature_batch and
+ * opusgpu_feat_batch_layout refuse, an unknown layout, a span that breaks a rule above. */
+int opusgpu_tracks_feature_batch_device(opusgpu_ctx *ctx, int n_tracks, const opusgpu_feat_span *spans, int width, int layout,
+                                        const opusgpu_feat_batch_req *req, const float *sub, const float *mul_vec, const void *d_grid,
+                                        void *d_out, void *hip_stream);
 
 /* ---- WHOLE FILES / MULTISTREAM: N surround Ogg Opus files in, N trimmed interleaved tracks in HBM out -----------------------------
  * The two sections above joined: files whose OpusHead carries channel mapping family 1 (1 - 8 channels, `streams` elementary

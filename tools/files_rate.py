@@ -21,6 +21,9 @@ the log, and k_tracks_melspec's share of the call (tools/mel_rate.py: compare_sp
 FEATURES) against float mono tracks at the set's rate followed by the torch restatement (unfold, mean, pre-emphasis, window, rfft,
 matmul, log), and k_tracks_fbank's share of the call (tools/mel_rate.py: compare_fbank); a set at 16 kHz is followed by --melspec
 kaldi's line at the same files, for the two kernels' shares side by side.
+--feature-batch S[:NORM] with --mel or --fbank: the fused call under a feature-batch request (include/opusgpu.h FEATURE BATCHES; one
+dense padded tensor, NORM none | whisper | cmn | cmvn) next to the packed call followed by the gather into a padded tensor and the
+normalisation in torch (tools/mel_rate.py: compare_feature_batch).
 --packets-per-file P: files of P packets of 20 ms (in pages of at most 250) in place of the default 10, for --mel and --melspec: long
 tracks, whose tiles are full.
 --resample UP/DOWN [--mono | --mix M]: the fused ratio call (opusgpu_files_decode_ratio, include/opusgpu.h TRACK RATIOS) next to
@@ -68,6 +71,9 @@ ap.add_argument("--melspec", choices=["tts", "kaldi", "clap", "music"], default=
                 help="compare the fused mel-spectrogram call with float mono tracks at the set's rate + torch.stft (tools/mel_rate.py)")
 ap.add_argument("--fbank", choices=["wenet", "mfcc", "mfcc8k", "wide"], default=None,
                 help="compare the fused Kaldi fbank / MFCC call with float mono tracks at the set's rate + unfold / rfft in torch (tools/mel_rate.py)")
+ap.add_argument("--feature-batch", default=None, metavar="S[:NORM]",
+                help="with --mel or --fbank: the fused call with a feature-batch request (stride S; none, whisper, cmn or cmvn) next to the "
+                     "packed call followed by padding and normalising in torch (tools/mel_rate.py: compare_feature_batch)")
 ap.add_argument("--packets-per-file", type=int, default=10, help="with --mel, --melspec, --fbank or --loudness: packets of 20 ms per file")
 ap.add_argument("--loudness", nargs="?", const="measure", default=None, metavar="TARGET",
                 help="what a loudness request adds to the float32 call, measuring and (with a target in LUFS) normalising (tools/loudness_rate.py)")
@@ -86,6 +92,8 @@ if args.loudness and (args.format or args.mel or args.melspec or args.resample o
     ap.error("--loudness goes alone or with --rate R --mono")
 if args.melspec and (args.rate or args.format or args.resample or args.mel):
     ap.error("--melspec goes without --rate, --resample, --format and --mel")
+if args.feature_batch and not (args.mel or args.fbank):
+    ap.error("--feature-batch goes with --mel or --fbank")
 if args.packets_per_file != 10 and not (args.mel or args.melspec or args.fbank or args.loudness or args.cuts is not None):
     ap.error("--packets-per-file goes with --mel, --melspec, --fbank, --loudness or --cuts")
 if args.mix and (args.mono or not (args.rate or args.resample)):
@@ -232,6 +240,13 @@ if args.resample:
     ctx.close()
     raise SystemExit(0)
 
+def set_feature_batch(fb):
+    """The feature-batch request `fb` (a FeatureBatch; None: off) on the context `ctx` of the leg that runs."""
+    vecs = [None, None] if fb is None else [None if v is None else v.ctypes.data for v in (fb.sub, fb.mul)]
+    ctx._chk(ctx.lib.opusgpu_set_feature_batch(ctx.h, None if fb is None else fb.rec.ctypes.data, *vecs, 0 if fb is None else fb.width),
+             "opusgpu_set_feature_batch")
+
+
 if args.fbank:
     import mel_rate
     maker, kw, up, down = mel_rate.FBANK_SETS[args.fbank]
@@ -253,6 +268,14 @@ if args.fbank:
                                                   "opusgpu_files_decode_fbank"),
             lambda spans, d_in, r, d_out: ctx.tracks_fbank_device(spans, d_in, r, d_out), b, rec, up, down, args.reps,
             f"{args.fbank}, {note}")), flush=True)
+        if args.feature_batch:
+            S, norm = mel_rate.feature_batch_arg(args.feature_batch)
+            print(json.dumps(mel_rate.compare_feature_batch(
+                torch, pkg,
+                lambda p, d, fo, fr, ln, st: ctx._chk(ctx.lib.opusgpu_files_decode_fbank(ctx.h, b.h, rate, 0, 0, 1, None, p, None, d, fo, fr, ln, st),
+                                                      "opusgpu_files_decode_fbank"),
+                set_feature_batch, b, rec, pkg.fbank_layout(b.info["track_samples"], up, down, rec),
+                pkg.fbank_frames(rec, -(-b.info["track_samples"] * up // down)), S, norm, args.reps, f"{args.fbank}, {note}")), flush=True)
         if rate == 16000:  # k_tracks_melspec's share at the same files
             print(json.dumps(mel_rate.compare_spec(
                 torch, pkg, tracks,
@@ -303,6 +326,14 @@ if args.mel:
             lambda p, d, fo, fr, ln, st: ctx._chk(ctx.lib.opusgpu_files_decode_mel(ctx.h, b.h, 1, None, p, None, d, fo, fr, ln, st),
                                                   "opusgpu_files_decode_mel"),
             lambda spans, d_in, rec, d_out: ctx.tracks_mel_device(spans, d_in, rec, None, d_out), b, args.n_mels, args.reps, name)))
+        if args.feature_batch:
+            S, norm = mel_rate.feature_batch_arg(args.feature_batch)
+            print(json.dumps(mel_rate.compare_feature_batch(
+                torch, pkg,
+                lambda p, d, fo, fr, ln, st: ctx._chk(ctx.lib.opusgpu_files_decode_mel(ctx.h, b.h, 1, None, p, None, d, fo, fr, ln, st),
+                                                      "opusgpu_files_decode_mel"),
+                set_feature_batch, b, pkg.mel_params(args.n_mels, "bands"), pkg.mel_layout(b.info["track_samples"], args.n_mels, "bands"),
+                -(-b.info["track_samples"] // 3) // 160, S, norm, args.reps, f"{name}, {PAGES * PER_PAGE} packets per file")), flush=True)
     ctx.close()
     raise SystemExit(0)
 

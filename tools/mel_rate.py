@@ -14,6 +14,8 @@ compare_fbank is the same for --fbank (include/opusgpu.h TRACK KALDI FEATURES) w
 (a) float32 mono tracks at the record's rate, (b) (a) + the torch restatement -- unfold, the frame's mean, the pre-emphasis, the
 window, torch.fft.rfft at n_fft, |.| or |.|^2 without the Nyquist bin, the filterbank matmul, the floor, the log and for MFCC the
 DCT matmul --, (c) the fused call, (m) opusgpu_tracks_fbank_device alone.
+compare_feature_batch is --feature-batch S[:NORM] (include/opusgpu.h FEATURE BATCHES) behind --mel or --fbank: (p) the packed feature
+call, (b) (p) + the gather into a padded tensor and the normalisation in torch, (c) the call with the request on.
 torch must be imported before the library is loaded: they then share one HIP runtime."""
 import time
 
@@ -262,6 +264,96 @@ def compare_fbank(torch, pkg, decode_tracks, decode_fbank, fbank_alone, batch, r
         out[label] = {"mean_ms": round(float(v.mean()), 3), "median_ms": round(float(np.median(v)), 3),
                       "min_max_ms": [round(float(v.min()), 3), round(float(v.max()), 3)]}
     out["fbank_share_of_c"] = round(float(np.mean(times["m"]) / np.mean(times["c"])), 3)
+    out["c_le_b"] = bool(np.mean(times["c"]) <= np.mean(times["b"]))
+    return out
+
+
+def feature_batch_arg(text):
+    """--feature-batch S[:NORM] -> (S, NORM): NORM one of none, whisper, cmn, cmvn (default none)."""
+    s, _, norm = text.partition(":")
+    norm = norm or "none"
+    if norm not in ("none", "whisper", "cmn", "cmvn") or int(s) < 1:
+        raise ValueError(f"--feature-batch takes S[:none|whisper|cmn|cmvn] with S >= 1, not {text!r}")
+    return int(s), norm
+
+
+def compare_feature_batch(torch, pkg, decode_feat, set_request, batch, rec, layout, planned_frames, stride, norm, reps, note=""):
+    """--feature-batch S[:NORM] (include/opusgpu.h FEATURE BATCHES): decode_feat(params, d_out, feat_offsets, frames, lengths, status)
+    runs a fused feature call of the batch for the record `rec`, whose packed grid is layout = (feat_offsets, planes, total floats)
+    and whose tracks have planned_frames frames; set_request(FeatureBatch or None) puts a request on the decoder or takes it off.
+    (p) the packed feature call as it was; (b) (p) followed by the torch form a user writes today -- the ragged features gathered
+    into a padded [files, S, W] or [files, W, S] tensor (the gather index is made once, outside the timing), then amax / clamp for
+    whisper or the masked mean / variance per bin for cmn / cmvn; (c) the same call with the request on, which writes that tensor.
+    Variants interleaved per repeat; both are printed, no ratio is asked.  -> a dict for the JSON line."""
+    n = batch.n_files
+    feat_offs, planes, total_feat = layout
+    W = pkg.fbank_width(rec) if rec.dtype == pkg.FBANK_PARAMS_DTYPE else int(rec["n_mels"][0])
+    frames_major = int(rec["layout"][0]) == pkg.MEL_FRAMES_MAJOR
+    fb = pkg.feature_batch_request(planned_frames, W, stride, None if norm == "none" else norm)
+    S = fb.stride
+    pad_value = float(fb.rec["pad_value"][0])
+    packed = torch.empty(max(total_feat, 1), dtype=torch.float32, device="cuda:0")
+    dense = torch.empty(max(n * S * W, 1), dtype=torch.float32, device="cuda:0")
+    lengths, fo, frames = (np.zeros(n, dtype=np.int64) for _ in range(3))
+    status = np.zeros((n, 2), dtype=np.int32)
+    f, j = np.arange(S)[None, :, None], np.arange(W)[None, None, :]
+    F = np.asarray(planned_frames, dtype=np.int64)[:, None, None]
+    at = feat_offs[:, None, None] + (f * W + j if frames_major else j * planes[:, None, None] + f)
+    valid = np.broadcast_to(f < F, at.shape)
+    if not frames_major:
+        at, valid = at.transpose(0, 2, 1), valid.transpose(0, 2, 1)
+    gather = torch.tensor(np.where(valid, at, 0), device="cuda:0")
+    mask = torch.tensor(np.ascontiguousarray(valid), device="cuda:0")
+    count = torch.tensor(np.maximum(F, 1).astype(np.float32), device="cuda:0")
+    fdim = 1 if frames_major else 2
+    pad = torch.full((), pad_value, device="cuda:0")
+    zero = torch.zeros((), device="cuda:0")
+
+    def p():
+        decode_feat(rec.ctypes.data, packed.data_ptr(), fo.ctypes.data, frames.ctypes.data, lengths.ctypes.data, status.ctypes.data)
+
+    def b():
+        p()
+        x = torch.where(mask, packed[gather], pad)
+        if norm == "whisper":
+            m = torch.where(mask, x, torch.full((), -float("inf"), device="cuda:0")).amax(dim=(1, 2), keepdim=True)
+            x = (torch.maximum(x, m - 8.0) + 4.0) / 4.0
+        elif norm in ("cmn", "cmvn"):
+            mean = torch.where(mask, x, zero).sum(dim=fdim, keepdim=True) / count
+            d = x - mean
+            if norm == "cmvn":
+                var = torch.where(mask, d * d, zero).sum(dim=fdim, keepdim=True) / count
+                d = d / torch.sqrt(torch.clamp(var, min=float(fb.rec["var_floor"][0])))
+            x = torch.where(mask, d, pad)
+        torch.cuda.synchronize()
+        return x
+
+    def c():
+        set_request(fb)
+        try:
+            decode_feat(rec.ctypes.data, dense.data_ptr(), fo.ctypes.data, frames.ctypes.data, lengths.ctypes.data, status.ctypes.data)
+        finally:
+            set_request(None)
+
+    times = {"p": [], "b": [], "c": []}
+    for fn in (p, b, c):
+        fn()
+    for _ in range(reps):
+        for name, fn in (("p", p), ("b", b), ("c", c)):
+            t0 = time.perf_counter()
+            fn()
+            times[name].append((time.perf_counter() - t0) * 1e3)
+    c()
+    assert (status[:, 0] == 0).all() and (frames == np.asarray(planned_frames)).all() and (fo == np.arange(n) * S * W).all()
+    want = b()
+    worst = float((dense[:n * S * W].view(want.shape) - want).abs().max())
+    assert worst < 1e-3, worst
+    out = {"feature_batch": [S, norm], "width": W, "layout": "frames" if frames_major else "bands", "files": n, "frames": int(frames.sum()),
+           "reps": reps, "note": note, "packed_bytes": int(total_feat) * 4, "dense_bytes": n * S * W * 4, "worst_abs_vs_torch": worst}
+    for k, label in (("p", "p_packed_feature_call"), ("b", "b_packed_then_torch_pad_and_norm"), ("c", "c_fused_feature_batch")):
+        v = np.array(times[k])
+        out[label] = {"mean_ms": round(float(v.mean()), 3), "median_ms": round(float(np.median(v)), 3),
+                      "min_max_ms": [round(float(v.min()), 3), round(float(v.max()), 3)]}
     out["c_le_b"] = bool(np.mean(times["c"]) <= np.mean(times["b"]))
     return out
 
