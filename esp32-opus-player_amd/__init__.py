@@ -55,6 +55,8 @@ EXPORTS = [
     "opusgpu_files_plan_cuts", "opusgpu_ms_files_plan_cuts", "opusgpu_file_batch_track_stride", "opusgpu_ms_file_batch_track_stride",
     "opusgpu_tracks_fill_tail_device",
     "opusgpu_set_feature_batch", "opusgpu_ms_set_feature_batch", "opusgpu_feat_batch_layout", "opusgpu_tracks_feature_batch_device",
+    "opusgpu_set_wave_batch", "opusgpu_ms_set_wave_batch", "opusgpu_last_wave_stats", "opusgpu_ms_last_wave_stats",
+    "opusgpu_wave_batch_layout", "opusgpu_tracks_wave_batch_device",
 ]
 
 
@@ -176,6 +178,13 @@ FEAT_NORMS = {None: 0, "none": 0, "whisper": 1, "cmn": 2, "cmvn": 3, "affine": 4
 FEAT_NORM_NONE, FEAT_NORM_WHISPER, FEAT_NORM_CMN, FEAT_NORM_CMVN, FEAT_NORM_AFFINE = range(5)
 FEAT_PAD_VALUE, FEAT_PAD_NORMALIZED = 0, 1
 FEAT_SEG = 1024  # OPUSGPU_FEAT_SEG: frames per segment of the statistics
+WAVE_BATCH_REQ_DTYPE = np.dtype([("stride_samples", "<i8"), ("eps", "<f8"), ("target", "<f8"), ("enabled", "<i4"), ("norm", "<i4"),
+                                 ("pad_value", "<f4"), ("mask", "<i4"), ("reserved", "<i4", (6,))])
+WAVE_SPAN_DTYPE = np.dtype([("in_offset", "<i8"), ("samples", "<i8"), ("scale", "<f4"), ("reserved", "<i4")])
+WAVE_STAT_DTYPE = np.dtype([("count", "<i8"), ("sum", "<i8"), ("sumsq", "<u8"), ("sub", "<f8"), ("mul", "<f8"), ("peak", "<i4"), ("reserved", "<i4")])
+WAVE_NORMS = {None: 0, "none": 0, "zmuv": 1, "peak": 2}
+WAVE_NORM_NONE, WAVE_NORM_ZMUV, WAVE_NORM_PEAK = range(3)
+WAVE_EPS = 1e-7  # Wav2Vec2FeatureExtractor's
 LOUDNESS_OFF, LOUDNESS_MEASURE, LOUDNESS_NORMALIZE = 0, 1, 2
 OPUSGPU_BAD_ARG, OPUSGPU_UNIMPLEMENTED, OPUSGPU_CELT_BAD_ARG = -1, -5, -18
 RFC_FRAME = 2880
@@ -344,6 +353,13 @@ def load_lib():
     lib.opusgpu_feat_batch_layout.argtypes = [C.c_int, C.c_int, C.c_int64, vp]
     lib.opusgpu_feat_batch_layout.restype = C.c_int64
     lib.opusgpu_tracks_feature_batch_device.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
+    for name in ("opusgpu_set_wave_batch", "opusgpu_ms_set_wave_batch"):
+        getattr(lib, name).argtypes = [vp, vp]
+    for name in ("opusgpu_last_wave_stats", "opusgpu_ms_last_wave_stats"):
+        getattr(lib, name).argtypes = [vp, C.c_int, vp]
+    lib.opusgpu_wave_batch_layout.argtypes = [C.c_int, C.c_int, C.c_int64, C.c_int, vp]
+    lib.opusgpu_wave_batch_layout.restype = C.c_int64
+    lib.opusgpu_tracks_wave_batch_device.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
     _lib = lib
     return lib
 
@@ -1388,6 +1404,69 @@ def _feature_width(params):
     return fbank_width(params) if params.dtype == FBANK_PARAMS_DTYPE else int(params["n_mels"][0])
 
 
+class WaveBatch(typing.NamedTuple):
+    """The wave-batch request of one decode_files call: the opusgpu_wave_batch_req record (a WAVE_BATCH_REQ_DTYPE array of one), the
+    tracks' channels C, the stride S, whether a mask is written, and the buffer as opusgpu_wave_batch_layout lays it out for the
+    `n` tracks the request was made for: `floats` in all, the mask `mask_offset` bytes in."""
+    rec: object
+    channels: int
+    stride: int
+    mask: bool
+    n: int
+    floats: int
+    mask_offset: int
+
+
+def wave_batch_layout(n, channels, stride_samples, mask=False):
+    """opusgpu_wave_batch_layout: the dense tensor of n tracks of stride_samples samples of `channels` channels, and the mask behind
+    it -> (total floats of the buffer, the mask's byte offset or None)."""
+    at = C.c_int64(0)
+    total = int(load_lib().opusgpu_wave_batch_layout(int(n), int(channels), int(stride_samples), 1 if mask else 0, C.byref(at)))
+    if total < 0:
+        raise ValueError(f"there is no wave batch of {n!r} tracks of {stride_samples!r} samples of {channels!r} channels "
+                         "(stride * channels <= 2^31 - 1)")
+    return total, (int(at.value) if mask else None)
+
+
+def wave_batch_request(planned_out_samples, channels, wave_stride=None, wave_normalize=None, wave_pad=None, wave_mask=False):
+    """What decode_files makes of wave_stride=, wave_normalize=, wave_pad= and wave_mask= for tracks of `channels` channels whose
+    PLANNED lengths at the output's rate are planned_out_samples[t] (include/opusgpu.h WAVE BATCHES): a WaveBatch.  wave_stride None:
+    the longest planned track (at least 1).  wave_normalize: None / "none", "zmuv" (eps 1e-7, Wav2Vec2FeatureExtractor's), ("zmuv",
+    eps) or ("peak", target).  wave_pad: the pad cells' value, None is 0.  Raises ValueError for an unknown wave_normalize, an eps
+    or target that is not finite and > 0, a stride that is no integer >= 1 or lies below a planned length, stride * channels above
+    2^31 - 1, a pad that is not finite and a wave_mask that is no bool."""
+    import numbers
+
+    def number(v):
+        return isinstance(v, numbers.Real) and not isinstance(v, bool) and np.isfinite(v)
+    planned = np.asarray(planned_out_samples, dtype=np.int64)
+    norm, value = wave_normalize if isinstance(wave_normalize, tuple) and len(wave_normalize) == 2 else (wave_normalize, None)
+    if not isinstance(norm, (str, type(None))) or norm not in WAVE_NORMS or (value is not None and WAVE_NORMS[norm] == WAVE_NORM_NONE):
+        raise ValueError(f"wave_normalize must be None, 'zmuv', ('zmuv', eps) or ('peak', target), not {wave_normalize!r}")
+    norm = WAVE_NORMS[norm]
+    if norm == WAVE_NORM_PEAK and value is None:
+        raise ValueError("wave_normalize 'peak' needs its target: ('peak', target)")
+    if value is not None and not (number(value) and value > 0):
+        raise ValueError(f"the eps or target of wave_normalize must be finite and > 0, not {value!r}")
+    most = int(planned.max()) if planned.size else 0
+    if wave_stride is None:
+        wave_stride = max(most, 1)
+    if not isinstance(wave_stride, numbers.Integral) or isinstance(wave_stride, bool) or wave_stride < 1:
+        raise ValueError(f"wave_stride must be an integer >= 1, not {wave_stride!r}")
+    if wave_stride < most:
+        raise ValueError(f"wave_stride {wave_stride} is below the {most} samples of the longest planned track")
+    wave_pad = 0.0 if wave_pad is None else wave_pad
+    if not number(wave_pad):
+        raise ValueError(f"wave_pad must be a finite number, not {wave_pad!r}")
+    if not isinstance(wave_mask, (bool, np.bool_)):
+        raise ValueError(f"wave_mask must be True or False, not {wave_mask!r}")
+    floats, mask_offset = wave_batch_layout(planned.size, channels, wave_stride, bool(wave_mask))
+    rec = np.zeros(1, dtype=WAVE_BATCH_REQ_DTYPE)
+    rec["enabled"], rec["stride_samples"], rec["norm"], rec["pad_value"], rec["mask"] = 1, int(wave_stride), norm, wave_pad, 1 if wave_mask else 0
+    rec["eps"], rec["target"] = (value if norm == WAVE_NORM_ZMUV and value is not None else WAVE_EPS), (value if norm == WAVE_NORM_PEAK else 1.0)
+    return WaveBatch(rec, int(channels), int(wave_stride), bool(wave_mask), int(planned.size), floats, mask_offset)
+
+
 class FilesRequest(typing.NamedTuple):
     """What one decode_files call asks of the library, made by files_request before any decoder is touched."""
     entry: str        # the C entry point without its opusgpu_ / opusgpu_ms_ prefix
@@ -1406,6 +1485,7 @@ class FilesRequest(typing.NamedTuple):
     stride: int = 0   # a strided batch of cuts: every track `stride` samples per channel apart, zeros behind its final length
     cut_info: object = None  # the batch's CUT_INFO_DTYPE records (a batch of cuts) or None
     feature_batch: object = None  # the FeatureBatch of feature_stride= / normalize= or None; with one, offsets and total are the dense tensor's
+    wave_batch: object = None  # the WaveBatch of wave_stride= / wave_normalize= / wave_mask= or None; with one, offsets and total are the dense tensor's
 
 
 STRIDE_REFUSED = ("the batch has a stride, which only tracks at 48 kHz keep (format=, scale=, out=, and loudness= with \"s16\"): resampled, "
@@ -1472,22 +1552,43 @@ def _files_request(batch, multistream=False, device=0, format=None, scale=None, 
 
 def files_request(batch, multistream=False, device=0, format=None, scale=None, out=None, rate=None, mono=False, mix=None, features=None,
                   n_mels=80, feature_layout="bands", resample=None, loudness=None, peak_limit=1.0, channel_weights=None,
-                  feature_stride=None, normalize=None, feature_pad=None):
+                  feature_stride=None, normalize=None, feature_pad=None, wave_stride=None, wave_normalize=None, wave_pad=None,
+                  wave_mask=False):
     """The keywords of decode_files for a planned batch -> the FilesRequest that _run_files_request carries out (_files_request says
     how).  A batch of cuts (FileBatch(cuts=...)) is a batch like any other: the request carries its cut records, which only info
     reads.  A strided one is refused here, as ValueError, with everything but tracks at 48 kHz; its planes lie the stride apart.
     feature_stride=, normalize= and feature_pad= (FEATURE BATCHES; feature_batch_request says what they may be) need features= and
     turn the request's result into one dense tensor: its `feature_batch` carries the record, and total, offsets, planes (the stride
-    for every track) and the out= size check follow opusgpu_feat_batch_layout.  Without them the request is what it always was."""
+    for every track) and the out= size check follow opusgpu_feat_batch_layout.  Without them the request is what it always was.
+    wave_stride=, wave_normalize=, wave_pad= and wave_mask= (WAVE BATCHES; wave_batch_request says what they may be) need a float
+    format and no features=, and turn the TRACKS of the request into one dense tensor: its `wave_batch` carries the record and the
+    buffer's layout, total is n * S and offsets t * S.  Tracks at 48 kHz without a mix, whose call has no resampling kernel, go
+    through files_decode_mixed with the identity matrix, which writes the same elements."""
     stride, cut_info = int(getattr(batch, "stride", 0) or 0), getattr(batch, "cut_info", None)
-    if stride and (rate not in (None, 48000) or mono or mix is not None or features is not None or resample is not None or
+    wave = wave_stride is not None or wave_normalize is not None or wave_pad is not None or wave_mask is not False
+    if stride and (rate not in (None, 48000) or mono or mix is not None or features is not None or resample is not None or wave or
                    (loudness is not None and format not in (None, "s16"))):
         raise ValueError(STRIDE_REFUSED)
     dense = feature_stride is not None or normalize is not None or feature_pad is not None
     if dense and features is None:
         raise ValueError("feature_stride=, normalize= and feature_pad= need features=")
-    req = _files_request(batch, multistream, device, format, scale, None if dense else out, rate, mono, mix, features, n_mels, feature_layout,
-                         resample, loudness, peak_limit, channel_weights)
+    if wave and features is not None:
+        raise ValueError("wave_stride=, wave_normalize=, wave_pad= and wave_mask= are for tracks: features have feature_stride= and normalize=")
+    if wave and format in (None, "s16"):
+        raise ValueError("wave_stride=, wave_normalize=, wave_pad= and wave_mask= need format='f32' or 'f32_planar': the dense tensor is float32")
+    req = _files_request(batch, multistream, device, format, scale, None if dense or wave else out, rate, mono, mix, features, n_mels,
+                         feature_layout, resample, loudness, peak_limit, channel_weights)
+    if wave:
+        if req.entry == "files_decode_as":  # 16384 on the diagonal is exactly x = s
+            req = _files_request(batch, multistream, device, format, scale, None, rate, mono, 16384 * np.eye(batch.channels, dtype=np.int16),
+                                 features, n_mels, feature_layout, resample, loudness, peak_limit, channel_weights)
+        up, down = req.args[:2] if req.entry == "files_decode_ratio" else (1, TRACK_RATES[req.args[0]])
+        wb = wave_batch_request(-(-np.asarray(batch.info["track_samples"], dtype=np.int64) * up // down), req.channels, wave_stride, wave_normalize,
+                                wave_pad, wave_mask)
+        if out is not None:
+            out = _out_flat(out, max(wb.floats, 1), format, device)
+        req = req._replace(wave_batch=wb, offsets=np.arange(batch.n_files, dtype=np.int64) * wb.stride, total=batch.n_files * wb.stride, out=out,
+                           planes=np.full(batch.n_files, wb.stride, dtype=np.int64))
     if dense:
         width = _feature_width(req.params)
         fb = feature_batch_request(_planned_feature_frames(batch, req), width, feature_stride, normalize, feature_pad)
@@ -1510,7 +1611,10 @@ def _run_files_request(req, lib, prefix, handle, chk, batch, mem):
     request is set on the decoder for this call alone and cleared behind it, and info has `lufs`, `peak`, `loudness_blocks`,
     `loudness_gated` and `gain` more.  With a feature-batch request (req.feature_batch) that request is set and cleared the same way,
     and the features are ONE float32 array or tensor [n, n_mels, S] or [n, S, n_mels] (with out=: a view of the caller's memory), padded
-    behind every track's info["frames"]; info["feat_offset"] is t * S * n_mels."""
+    behind every track's info["frames"]; info["feat_offset"] is t * S * n_mels.  With a wave-batch request (req.wave_batch), set and
+    cleared the same way, the tracks are ONE float32 array or tensor [n, S, channels] ([n, S] for one channel; planar: [n, channels, S]),
+    padded behind every track's info["out_samples"]; info["out_offset"] is t * S, info["wave_stats"] the WAVE_STAT_DTYPE records and, with
+    a mask, info["mask"] the uint8 [n, S] mask."""
     name = prefix + req.entry
     n, ch, fmt = batch.n_files, req.channels, req.fmt
     offsets, counts, lengths = (np.zeros(n, dtype=np.int64) for _ in range(3))
@@ -1523,9 +1627,19 @@ def _run_files_request(req, lib, prefix, handle, chk, batch, mem):
     loud = np.zeros(n, dtype=LOUDNESS_DTYPE)
     gains = np.ones(n, dtype=np.float64)
 
-    fb = req.feature_batch
+    fb, wb = req.feature_batch, req.wave_batch
+    wave_stats = np.zeros(n, dtype=WAVE_STAT_DTYPE)
 
     def run(d_out):
+        if wb is not None:
+            chk(getattr(lib, prefix + "set_wave_batch")(handle, wb.rec.ctypes.data), prefix + "set_wave_batch")
+            try:
+                run_loud(d_out)
+                got = getattr(lib, prefix + "last_wave_stats")(handle, n, wave_stats.ctypes.data)
+                assert got == n, (got, n)
+            finally:
+                getattr(lib, prefix + "set_wave_batch")(handle, None)
+            return
         if fb is None:
             return run_loud(d_out)
         vecs = [None if v is None else v.ctypes.data for v in (fb.sub, fb.mul)]
@@ -1552,7 +1666,7 @@ def _run_files_request(req, lib, prefix, handle, chk, batch, mem):
         run(req.out.data_ptr())
         packed = req.out
     else:
-        packed = np.zeros(max(req.total, 1) * ch, dtype=np.int16 if fmt == TRACKS_S16 else np.float32)
+        packed = np.zeros(max(req.total, 1) * ch if wb is None else max(wb.floats, 1), dtype=np.int16 if fmt == TRACKS_S16 else np.float32)
         d_out = mem.dev_alloc(packed.nbytes)
         try:
             run(d_out)
@@ -1564,8 +1678,9 @@ def _run_files_request(req, lib, prefix, handle, chk, batch, mem):
                                        "features": ("frames", "feat_offset", ["feat_offset"])}[req.kind]
     louder = [] if req.loudness is None else [("lufs", "<f4"), ("peak", "<f4"), ("loudness_blocks", "<i4"), ("loudness_gated", "<i4"), ("gain", "<f8")]
     cut_fields = [] if req.cut_info is None else [("cut_" + f, CUT_INFO_DTYPE[f].str) for f in CUT_INFO_DTYPE.names]
+    wave_fields = [] if wb is None else [("wave_stats", WAVE_STAT_DTYPE)] + ([("mask", "u1", (wb.stride,))] if wb.mask else [])
     info = np.zeros(n, dtype=np.dtype(FILE_INFO_DTYPE.descr + [("final_status", "<i4"), ("bad_packet", "<i4")] + [(f, "<i8") for f in more] +
-                                      louder + cut_fields))
+                                      louder + cut_fields + wave_fields))
     for f in CUT_INFO_DTYPE.names if cut_fields else ():
         info["cut_" + f] = req.cut_info[f]
     if louder:
@@ -1588,6 +1703,17 @@ def _run_files_request(req, lib, prefix, handle, chk, batch, mem):
         if int(req.params["layout"][0]) == MEL_FRAMES_MAJOR:
             return [packed[o:o + F * n_mels].reshape(F, n_mels) for o, F in zip(offsets, counts)], info
         return [packed[o:o + n_mels * p].reshape(n_mels, p)[:, :F] for o, p, F in zip(offsets, req.planes, counts)], info
+    if wb is not None:  # WAVE BATCHES: one dense tensor, every track wb.stride samples, padded behind its info["out_samples"]
+        info["wave_stats"] = wave_stats
+        if wb.mask and req.out is not None:
+            mask = np.zeros((n, wb.stride), dtype=np.uint8)
+            mem.d2h(mask, C.c_void_p(req.out.data_ptr() + wb.mask_offset))
+            info["mask"] = mask
+        elif wb.mask:
+            info["mask"] = packed.view(np.uint8)[wb.mask_offset:wb.mask_offset + n * wb.stride].reshape(n, wb.stride)
+        shape = (n, ch, wb.stride) if fmt == TRACKS_F32_PLANAR else (n, wb.stride, ch) if ch > 1 else (n, wb.stride)
+        dense = packed[:n * wb.stride * ch]
+        return (dense.view(*shape) if req.out is not None else dense.reshape(shape)), info
     if req.stride and req.out is not None:  # the caller's memory as the tensor it is: every track at its stride, zeros behind its length
         shape = (n, ch, req.stride) if fmt == TRACKS_F32_PLANAR else (n, req.stride, ch)
         return packed[:n * req.stride * ch].view(*shape), info
@@ -1816,6 +1942,17 @@ class Context:
                                                                request.rec.ctypes.data, *vecs, d_grid, d_out, stream),
                   "opusgpu_tracks_feature_batch_device")
 
+    def tracks_wave_batch_device(self, spans, channels, format, request, d_s16, d_out, stream=None):
+        """k_wave_stats, k_wave_fold and k_wave_batch alone (include/opusgpu.h WAVE BATCHES): spans a HOST array of WAVE_SPAN_DTYPE over
+        the interleaved int16 tracks d_s16 of `channels` channels, format "f32" or "f32_planar", request a WaveBatch
+        (wave_batch_request), d_out the buffer of wave_batch_layout's floats.  Waits for the kernels -> the WAVE_STAT_DTYPE records."""
+        spans = np.ascontiguousarray(spans, dtype=WAVE_SPAN_DTYPE)
+        stats = np.zeros(spans.size, dtype=WAVE_STAT_DTYPE)
+        self._chk(self.lib.opusgpu_tracks_wave_batch_device(self.h, spans.size, spans.ctypes.data, int(channels), TRACK_FORMATS[format],
+                                                            request.rec.ctypes.data, d_s16, d_out, stats.ctypes.data, stream),
+                  "opusgpu_tracks_wave_batch_device")
+        return stats
+
     def tracks_melspec_device(self, spans, d_in, rec, d_out, stream=None):
         """k_tracks_melspec alone (include/opusgpu.h TRACK SPECTROGRAMS): spans a HOST array of MEL_SPAN_DTYPE, d_in packed int16 mono
         tracks at the record's rate, rec a mel_spec record, d_out the float32 feature tracks.  Waits for the kernel."""
@@ -1850,7 +1987,7 @@ class Context:
     def decode_files(self, files, rfc=False, flags=PAGES_GROUP_BY_MODE, threads=1, batch=None, format=None, scale=None, out=None,
                      rate=None, mono=False, mix=None, features=None, n_mels=80, feature_layout="bands", resample=None, loudness=None,
                      peak_limit=1.0, channel_weights=None, cuts=None, preroll=CUT_PREROLL, stride=None, feature_stride=None, normalize=None,
-                     feature_pad=None):
+                     feature_pad=None, wave_stride=None, wave_normalize=None, wave_pad=None, wave_mask=False):
         """Whole Ogg Opus files -> (list of int16 arrays [samples, channels], one trimmed track per file, info).  The context's
         streams 0 .. len(files) - 1 are (re)allocated when there are too few and get fresh state; its mode is set to `rfc`.
         info: FILE_INFO_DTYPE records with two more fields: `final_status` (the first failed frame's code, else the plan's status)
@@ -1913,7 +2050,16 @@ class Context:
         divided by the per-bin standard deviation), ("affine", sub, mul) ((x - sub[j]) * mul[j], global CMVN), or a feature_norm()
         record with numbers of its own.  feature_pad: the pad cells' value, a number (verbatim) or (number, "normalized") for the
         track's normalisation of it; None is (-10, "normalized") under "whisper" -- the log-mel of zero audio, as Whisper pads --
-        and 0 otherwise.  The batch's own stride= is still refused with features."""
+        and 0 otherwise.  The batch's own stride= is still refused with features.
+        wave_stride, wave_normalize, wave_pad, wave_mask (with format="f32" or "f32_planar", without features=; include/opusgpu.h WAVE
+        BATCHES): the tracks -- at any rate=, resample=, mono= or mix= -- as ONE float32 array [n, S, channels] ([n, S] for one channel;
+        "f32_planar": [n, channels, S]) -- with out= (wave_batch_layout's floats) a view of it --, every track padded with wave_pad (0)
+        to S = wave_stride samples (any integer that holds every planned track; None: the longest) behind its info["out_samples"];
+        info["out_offset"] is t * S.  wave_normalize: None, "zmuv" (zero mean and unit variance over the track's real samples of all
+        channels, eps 1e-7 under the root as Wav2Vec2FeatureExtractor has it), ("zmuv", eps) or ("peak", target) (the largest |sample|
+        becomes target), from exact integer statistics of the int16 track: info["wave_stats"] has them (WAVE_STAT_DTYPE) with the sub
+        and mul applied, (y * scale - sub) * mul.  wave_mask=True: info["mask"] is the uint8 [n, S] attention mask, 1 on real samples.
+        The batch's own stride= is still refused with these."""
         if mix is not None and mono:  # (files_request's first refusal, ahead of the plan as it always was)
             raise ValueError("mix and mono=True exclude each other: the row {8192, 8192} is mono")
         own = batch is None
@@ -1922,7 +2068,8 @@ class Context:
                               stride=stride)
         try:
             req = files_request(batch, False, self.device, format, scale, out, rate, mono, mix, features, n_mels, feature_layout, resample,
-                                loudness, peak_limit, channel_weights, feature_stride, normalize, feature_pad)
+                                loudness, peak_limit, channel_weights, feature_stride, normalize, feature_pad, wave_stride, wave_normalize,
+                                wave_pad, wave_mask)
             if self.n_streams < batch.n_files or self.channels != batch.channels:
                 self.streams_alloc(max(batch.n_files, 1), batch.channels)
             self.set_mode(batch.rfc)
@@ -2095,7 +2242,8 @@ class MultistreamContext:
 
     def decode_files(self, files, rfc=False, threads=1, batch=None, format=None, scale=None, out=None, rate=None, mix=None, features=None,
                      n_mels=80, feature_layout="bands", resample=None, loudness=None, peak_limit=1.0, channel_weights=None, cuts=None,
-                     preroll=CUT_PREROLL, stride=None, feature_stride=None, normalize=None, feature_pad=None):
+                     preroll=CUT_PREROLL, stride=None, feature_stride=None, normalize=None, feature_pad=None, wave_stride=None,
+                     wave_normalize=None, wave_pad=None, wave_mask=False):
         """Whole Ogg Opus files of this object's layout -> (list of int16 arrays [samples, channels], one trimmed track per file,
         info), as Context.decode_files returns them: FILE_INFO_DTYPE records plus `final_status` and `bad_packet`, `track_samples`
         the FINAL length.  Decoders 0 .. len(files) - 1 get fresh state; the object's mode is set to the batch's.  batch: an
@@ -2106,14 +2254,15 @@ class MultistreamContext:
         resample: as for Context.decode_files, all channels or those of the mix.  features may be a mel_spec(), kaldi_fbank() or kaldi_mfcc() record as there.
         loudness, peak_limit, channel_weights: as for Context.decode_files; the default weights are those of the layout's channel
         count (1.41 for the rear pair, 0 for the LFE).  cuts, preroll, stride: as for Context.decode_files.
-        feature_stride, normalize, feature_pad: as for Context.decode_files."""
+        feature_stride, normalize, feature_pad, wave_stride, wave_normalize, wave_pad, wave_mask: as for Context.decode_files."""
         own = batch is None
         if own:
             batch = MsFileBatch(files, self.layout, rfc=rfc, threads=threads, cuts=cuts, preroll=preroll, stride=stride)
         mem = None
         try:
             req = files_request(batch, True, self.device, format, scale, out, rate, False, mix, features, n_mels, feature_layout, resample,
-                                loudness, peak_limit, channel_weights, feature_stride, normalize, feature_pad)
+                                loudness, peak_limit, channel_weights, feature_stride, normalize, feature_pad, wave_stride, wave_normalize,
+                                wave_pad, wave_mask)
             mem = Context(self.device)  # (device memory and copies are a plain context's calls)
             self.set_mode(batch.rfc)
             return _run_files_request(req, self.lib, "opusgpu_ms_", self.h, self._chk, batch, mem)

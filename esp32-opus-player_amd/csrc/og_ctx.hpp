@@ -95,6 +95,13 @@ struct FeatBatchState {
     std::vector<float> sub, mul;
 };
 
+// WAVE BATCHES: the request that holds for the whole-file calls that follow (opusgpu_set_wave_batch), and the records of the last
+// of them that ran the stage (opusgpu_last_wave_stats).  One per context of either kind.
+struct WaveBatchState {
+    opusgpu_wave_batch_req req{}; // enabled 0: off
+    std::vector<opusgpu_wave_stat> records;
+};
+
 struct opusgpu_ctx {
     int device = -1;
     hipStream_t stream = nullptr;
@@ -160,6 +167,7 @@ struct opusgpu_ctx {
     std::vector<int32_t> last_count, last_flags;
     LoudnessState loud;
     FeatBatchState fbatch;
+    WaveBatchState wave;
     char err[256] = {0};
 };
 

@@ -178,6 +178,7 @@ struct opusgpu_ms {
     size_t cap_arena = 0, cap_place = 0, cap_out = 0, cap_res = 0;
     LoudnessState loud;
     FeatBatchState fbatch;
+    WaveBatchState wave;
     char err[256] = {0};
 };
 

@@ -445,25 +445,49 @@ static void rs_batch_spans(const og_batch &b, int up, int down, const int64_t *f
     }
 }
 
+// WAVE BATCHES (og_wave_batch.hpp, behind the feature headers): the stage that turns packed int16 tracks into the dense tensor.
+static const char *wave_batch_shape_wrong(const opusgpu_wave_batch_req &r, int C, int format);
+static int wave_batch_run(int device, hipStream_t s, int n_tracks, const opusgpu_wave_span *spans, int C, int format,
+                          const opusgpu_wave_batch_req *req, const void *d_s16, void *d_out, opusgpu_wave_stat *recs,
+                          const TrackFail &hip_failed, const std::function<void(const char *)> &why);
+
 // What every whole-file call that ends in a resampling kernel does around its owner's decoder, its arguments checked by the caller:
-// own.decode runs the batch into the scratch S16 tracks, `run(n, spans, d_s16)` the kernel that makes tracks at up / down of their
-// rate from them.
+// own.decode runs the batch into the scratch S16 tracks, `run(n, spans, d_s16, format, d_dst)` the kernel that makes tracks of CO
+// channels at up / down of their rate from them, in `format` at d_dst.  That is the call's own format and d_out -- unless the owner
+// holds a WAVE BATCHES request and the tracks are the call's result (they are not where they feed a feature kernel): then the
+// kernel writes int16 into a scratch grid of its own layout and wave_batch_run writes d_out from there.
 template <class Run>
-static int files_resampled_to(const FilesOwner &own, int up, int down, int format, const float *scale, int64_t *out_offsets,
-                              int64_t *out_lengths, int64_t *track_lengths_out, int32_t *status_out, Run run) {
+static int files_resampled_to(const FilesOwner &own, int up, int down, int CO, int format, const float *scale, void *d_out,
+                              int64_t *out_offsets, int64_t *out_lengths, int64_t *track_lengths_out, int32_t *status_out, Run run) {
     const og_batch &b = own.b;
     if (!rs_scale_ok(format, scale, b.n_files)) return OPUSGPU_BAD_ARG;
     // TRACK LOUDNESS: int16 tracks take no gain, unless they only feed a feature kernel that applies it
     if (loud_normalizes(own) && format == OPUSGPU_TRACKS_S16 && !own.scale_later) return OPUSGPU_BAD_ARG;
     if (loud_on(own) && own.loud->req.n_weights && own.loud->req.n_weights != b.channels) return OPUSGPU_BAD_ARG;
     const size_t n = (size_t)b.n_files;
+    WaveBatchState *const wb = own.wave && own.wave->req.enabled && !own.scale_later ? own.wave : nullptr;
+    int64_t mid_total = 0; // the scratch grid of a wave batch, in samples per channel
+    if (wb) {
+        const char *bad = wave_batch_shape_wrong(wb->req, CO, format);
+        for (size_t i = 0; i < n && !bad; i++) {
+            const int64_t planned = (b.info[i].track_samples * up + down - 1) / down;
+            if (planned > wb->req.stride_samples) bad = "wave batch: stride_samples is below a track's planned output length";
+            mid_total += rs_round64(planned);
+        }
+        if (bad) {
+            if (own.refused) own.refused(bad);
+            return OPUSGPU_BAD_ARG;
+        }
+    }
     std::vector<int64_t> lengths(n, 0), offsets;
     std::vector<int32_t> status(2 * n, 0);
     std::vector<opusgpu_resample_span> spans;
     RsDevBuf s16; // the int16 tracks: track_samples x channels, for the length of this call
+    RsDevBuf mid; // WAVE BATCHES: the int16 tracks at the output's rate and channels, for the length of this call
     if (!b.segs.empty()) {
         hipError_t e = hipSetDevice(own.device);
         if (e == hipSuccess) e = s16.alloc((size_t)b.track_samples * b.channels * 2);
+        if (e == hipSuccess && wb) e = mid.alloc((size_t)mid_total * CO * 2 + 128);
         if (e != hipSuccess) return own.hip_failed(OPUSGPU_ALLOC_FAIL, "hipMalloc(resample scratch)", e);
     }
     if (int rc = own.decode(s16.p, lengths.data(), status.data())) return rc;
@@ -472,7 +496,19 @@ static int files_resampled_to(const FilesOwner &own, int up, int down, int forma
     rs_batch_spans(b, up, down, lengths.data(), scale, offsets, spans);
     if (loud_normalizes(own) && format != OPUSGPU_TRACKS_S16)
         for (size_t i = 0; i < n; i++) spans[i].scale = loud_scale(own, scale, i);
-    if (int rc = run(b.n_files, spans.data(), s16.p)) return rc;
+    if (int rc = run(b.n_files, spans.data(), s16.p, wb ? (int)OPUSGPU_TRACKS_S16 : format, wb ? mid.p : d_out)) return rc;
+    if (wb) {
+        std::vector<opusgpu_wave_span> tracks(n);
+        std::vector<opusgpu_wave_stat> recs(n);
+        for (size_t i = 0; i < n; i++) {
+            tracks[i] = opusgpu_wave_span{offsets[i], (lengths[i] * up + down - 1) / down, spans[i].scale, 0};
+            offsets[i] = (int64_t)i * wb->req.stride_samples;
+        }
+        if (int rc = wave_batch_run(own.device, own.stream, b.n_files, tracks.data(), CO, format, &wb->req, mid.p, d_out, recs.data(),
+                                    own.hip_failed, own.refused))
+            return rc;
+        wb->records = recs;
+    }
     for (size_t i = 0; i < n; i++) {
         if (out_offsets) out_offsets[i] = offsets[i];
         if (out_lengths) out_lengths[i] = (lengths[i] * up + down - 1) / down;
@@ -487,9 +523,9 @@ static int files_resampled_run(const FilesOwner &own, int rate, int mono, const 
                                void *d_out, int64_t *out_offsets, int64_t *out_lengths, int64_t *track_lengths_out, int32_t *status_out) {
     const int D = rs_args_factor(own.b.channels, rate, mono, format, mix);
     if (!D) return OPUSGPU_BAD_ARG;
-    return files_resampled_to(own, 1, D, format, scale, out_offsets, out_lengths, track_lengths_out, status_out,
-                              [&](int n, const opusgpu_resample_span *spans, const void *d_s16) {
-                                  return tracks_resample_run(own.device, own.stream, n, spans, d_s16, own.b.channels, rate, mono, format, d_out,
+    return files_resampled_to(own, 1, D, mix ? mix->out_channels : mono ? 1 : own.b.channels, format, scale, d_out, out_offsets, out_lengths,
+                              track_lengths_out, status_out, [&](int n, const opusgpu_resample_span *spans, const void *d_s16, int fmt, void *d_dst) {
+                                  return tracks_resample_run(own.device, own.stream, n, spans, d_s16, own.b.channels, rate, mono, fmt, d_dst,
                                                              own.hip_failed, mix);
                               });
 }

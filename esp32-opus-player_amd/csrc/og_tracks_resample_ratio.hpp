@@ -254,10 +254,10 @@ static int tracks_resample_ratio_run(int device, hipStream_t s, int n_tracks, co
 static int files_ratio_run(const FilesOwner &own, int up, int down, int mono, const opusgpu_mix_matrix *mix, int format, const float *scale,
                            void *d_out, int64_t *out_offsets, int64_t *out_lengths, int64_t *track_lengths_out, int32_t *status_out) {
     if (!rr_args_taps(own.b.channels, up, down, mono, format, mix)) return OPUSGPU_BAD_ARG;
-    return files_resampled_to(own, up, down, format, scale, out_offsets, out_lengths, track_lengths_out, status_out,
-                              [&](int n, const opusgpu_resample_span *spans, const void *d_s16) {
+    return files_resampled_to(own, up, down, mix ? mix->out_channels : mono ? 1 : own.b.channels, format, scale, d_out, out_offsets, out_lengths,
+                              track_lengths_out, status_out, [&](int n, const opusgpu_resample_span *spans, const void *d_s16, int fmt, void *d_dst) {
                                   return tracks_resample_ratio_run(own.device, own.stream, n, spans, d_s16, own.b.channels, up, down, mono, mix,
-                                                                   format, d_out, own.hip_failed);
+                                                                   fmt, d_dst, own.hip_failed);
                               });
 }
 

@@ -1223,6 +1223,98 @@ int opusgpu_tracks_feature_batch_device(opusgpu_ctx *ctx, int n_tracks, const op
                                         const opusgpu_feat_batch_req *req, const float *sub, const float *mul_vec, const void *d_grid,
                                         void *d_out, void *hip_stream);
 
+/* WAVE BATCHES.  The waveforms of a call as ONE dense float32 tensor at the model's rate, every track normalised by statistics of its
+ * own and padded to a common length, with an attention mask: what wav2vec 2.0, HuBERT, WavLM and every pad_sequence collate function
+ * take -- [B, T] at 16 kHz, zero mean and unit variance per utterance -- without a loop over tracks in the caller's code.  A stage
+ * behind the kernels of TRACK RATES, CHANNEL MIX and TRACK RATIOS, which are unchanged: they write their int16 result into a
+ * scratch grid of their own layout, 2 bytes a sample, and this stage writes the caller's buffer from there.  The result stays a
+ * pure function of the int16 track, bit for bit.  The definition is this comment.
+ *   INPUT.  For track t: y_c[m], the int16 result of those sections, interleaved, C = out_channels in [1, 8]; L[t] its output
+ *   length, derived from the FINAL length; scale[t], the float scale the call would have used for a float format (a loudness gain is
+ *   folded into it as TRACK LOUDNESS says).
+ *   OUTPUT.  A dense float32 tensor of n * S * C elements, S = stride_samples.  OPUSGPU_TRACKS_F32: element (t * S + m) * C + c --
+ *   [n, S, C], [n, S] for one channel.  OPUSGPU_TRACKS_F32_PLANAR: element (t * C + c) * S + m -- [n, C, S].  EVERY element is
+ *   written exactly once, the pad cells m >= L[t] included; nothing outside the tensor is touched.  S is any integer >= 1 that holds
+ *   every track's PLANNED output length, with S * C <= 0x7fffffff; nothing is asked of its alignment.
+ *   MASK (optional).  uint8 [n, S]: 1 for m < L[t], else 0; every byte written once.  It lies behind the tensor in the same buffer,
+ *   on the next 128-byte boundary (opusgpu_wave_batch_layout).
+ *   STATISTICS are per track, over its N = L[t] * C real samples of all channels jointly: sum = sum y (int64), sumsq = sum y^2
+ *   (uint64; N < 2^31 keeps it below 2^61), peak = max |y| (0 .. 32768).  All three are exact integers: they do not depend on the
+ *   order of summation, on the padding or on which other tracks are in the call, so integer atomics keep the contract of identical
+ *   bits from call to call.
+ *   NORMALISATIONS (norm), y a real sample, k = (double)scale[t]:
+ *     OPUSGPU_WAVE_NORM_NONE  out = (float)y * scale[t], one float32 multiplication: the very bits TRACK FORMATS writes.  Nothing is
+ *       measured: the record's integers are 0, sub 0, mul 1.
+ *     OPUSGPU_WAVE_NORM_ZMUV  (eps finite and > 0; Wav2Vec2FeatureExtractor's is 1e-7)  V = N * sumsq - sum^2 as an exact integer (up
+ *       to 93 bits); sub = k * sum / N; mul = 1 / sqrt(k^2 * V / N^2 + eps).  N = 0: sub = 0, mul = 1 / sqrt(eps).
+ *     OPUSGPU_WAVE_NORM_PEAK  (target finite and > 0)  sub = 0; mul = target / (peak * k), or 1 where peak * k is 0.
+ *     Under ZMUV and PEAK a real cell is out = (float)(((double)y * k - sub) * mul): y * k is exact in double (16 x 24 bits), so the
+ *     subtraction, the multiplication and the conversion are each rounded once, fused with the product or not.
+ *   PAD CELLS hold pad_value verbatim (0: HF pads after normalising).
+ *   RECORD.  opusgpu_wave_stat per track: count = N, the three integers, and sub and mul AS COMPUTED AND USED, within relative 2^-48
+ *   of the definition above (eight double roundings of 2^-53, and as many for whoever checks it, doubled).  The output is a
+ *   bit-for-bit function of the int16 track and the record, as normalised tracks are of the opusgpu_loudness gain.  A constant track
+ *   has V = 0 and y * k - sub = 0 exactly (sub is formed as k * (sum / N), and sum / N is exact there): 0.0f in every real cell. */
+#define OPUSGPU_WAVE_NORM_NONE 0
+#define OPUSGPU_WAVE_NORM_ZMUV 1
+#define OPUSGPU_WAVE_NORM_PEAK 2
+typedef struct opusgpu_wave_batch_req { /* 64 bytes (ABI) */
+    int64_t stride_samples; /* S, >= 1 */
+    double eps;             /* ZMUV: finite and > 0 */
+    double target;          /* PEAK: finite and > 0, the peak of the result */
+    int32_t enabled;        /* opusgpu_set_wave_batch: 0 is off; the stand-alone call does not read it */
+    int32_t norm;           /* OPUSGPU_WAVE_NORM_* */
+    float pad_value;
+    int32_t mask;           /* 1: the mask is written behind the tensor */
+    int32_t reserved[6];    /* 0 */
+} opusgpu_wave_batch_req;
+typedef struct opusgpu_wave_span { /* 24 bytes, one per track (ABI) */
+    int64_t in_offset; /* the track's first sample in the int16 grid, per channel; a multiple of 8 */
+    int64_t samples;   /* L[t], 0 <= L <= S */
+    float scale;       /* finite */
+    int32_t reserved;  /* 0 */
+} opusgpu_wave_span;
+typedef struct opusgpu_wave_stat { /* 48 bytes, one per track (ABI) */
+    int64_t count;  /* N = L * C */
+    int64_t sum;
+    uint64_t sumsq;
+    double sub, mul;
+    int32_t peak;
+    int32_t reserved;
+} opusgpu_wave_stat;
+/* The request that holds for the whole-file calls that follow, as opusgpu_set_feature_batch does for its own; NULL or `enabled` 0
+ * is off, the default, and every call is then byte for byte what it is above.  OPUSGPU_BAD_ARG, the request in force left as it
+ * was: an unknown norm; a field that is not finite (eps, target, pad_value); eps <= 0 under ZMUV; target <= 0 under PEAK;
+ * stride_samples < 1; a mask that is neither 0 nor 1; a reserved word that is not 0.  With a request on, the float-format calls
+ * that end in a resampling kernel -- opusgpu_files_decode_resampled, _mixed and _ratio and their opusgpu_ms_ twins -- run their kernel
+ * into an int16 scratch grid, then this stage writes d_out, which is now opusgpu_wave_batch_layout's total in floats, 128-byte
+ * aligned; out_offsets[t] reports t * S; out_lengths, track_lengths_out and status_out are what they were, and a track that a failed
+ * frame cut short pads from its final length; opusgpu_last_wave_stats has the records.  OPUSGPU_BAD_ARG before any device work, the
+ * buffer and the arrays left as they were, with the reason in opusgpu_last_error: OPUSGPU_TRACKS_S16 with a request on; S below a
+ * track's PLANNED output length; S * C above 0x7fffffff.  A loudness request composes untouched: its gain is in the scale.
+ * opusgpu_files_decode, opusgpu_files_decode_as and the feature calls ignore the request. */
+int opusgpu_set_wave_batch(opusgpu_ctx *ctx, const opusgpu_wave_batch_req *req);
+int opusgpu_ms_set_wave_batch(opusgpu_ms *ms, const opusgpu_wave_batch_req *req);
+/* The records of the last whole-file call that ran the stage, as opusgpu_last_loudness: copies min(n, have) of them and returns
+ * `have`. */
+int opusgpu_last_wave_stats(const opusgpu_ctx *ctx, int n, opusgpu_wave_stat *records);
+int opusgpu_ms_last_wave_stats(const opusgpu_ms *ms, int n, opusgpu_wave_stat *records);
+/* OUTPUT above for n tracks: returns the buffer's total in floats.  Without a mask that is n * S * C.  With one, the mask begins
+ * *mask_byte_offset bytes (may be NULL) into the buffer, the first multiple of 128 at or behind the tensor's end, and the total
+ * covers its n * S bytes.  OPUSGPU_BAD_ARG: n < 0, channels outside 1 - 8, stride_samples < 1, S * C above 0x7fffffff, a mask that
+ * is neither 0 nor 1.  Host only. */
+int64_t opusgpu_wave_batch_layout(int n, int channels, int64_t stride_samples, int mask, int64_t *mask_byte_offset);
+/* The stage alone over int16 tracks in device memory (k_wave_stats, k_wave_fold, k_wave_batch): `spans` is a HOST array of n_tracks
+ * records, tracks come out in span order; d_s16 interleaved int16 tracks of `channels` channels, 16-byte aligned, read in aligned
+ * 16-byte pieces up to the one that holds a track's last sample; d_out opusgpu_wave_batch_layout's floats, 128-byte aligned, not
+ * overlapping the tracks; format OPUSGPU_TRACKS_F32 or OPUSGPU_TRACKS_F32_PLANAR; stats_out n_tracks records on the HOST, or NULL.
+ * Uploads the spans and its chunk table, launches on the context's stream (or `hip_stream`), waits, and frees everything on every
+ * way out.  OPUSGPU_BAD_ARG before any device work: what opusgpu_set_wave_batch and opusgpu_wave_batch_layout refuse, another
+ * format, a span that breaks a rule above. */
+int opusgpu_tracks_wave_batch_device(opusgpu_ctx *ctx, int n_tracks, const opusgpu_wave_span *spans, int channels, int format,
+                                     const opusgpu_wave_batch_req *req, const void *d_s16, void *d_out, opusgpu_wave_stat *stats_out,
+                                     void *hip_stream);
+
 /* ---- WHOLE FILES / MULTISTREAM: N surround Ogg Opus files in, N trimmed interleaved tracks in HBM out -----------------------------
  * The two sections above joined: files whose OpusHead carries channel mapping family 1 (1 - 8 channels, `streams` elementary
  * streams) are planned by the same reader-driven loop as stereo files and decoded by an opusgpu_ms of their layout.  The reader's

@@ -24,6 +24,9 @@ kaldi's line at the same files, for the two kernels' shares side by side.
 --feature-batch S[:NORM] with --mel or --fbank: the fused call under a feature-batch request (include/opusgpu.h FEATURE BATCHES; one
 dense padded tensor, NORM none | whisper | cmn | cmvn) next to the packed call followed by the gather into a padded tensor and the
 normalisation in torch (tools/mel_rate.py: compare_feature_batch).
+--rate R [--mono | --mix M] --wave-batch S[:NORM] [--packets-per-file P]: the fused call under a wave-batch request (include/opusgpu.h
+WAVE BATCHES; one dense padded float32 tensor and its mask, S 0: the longest planned track, NORM none | zmuv | peak) next to the packed
+float32 call followed by the gather into a padded tensor, the normalisation and the mask in torch (tools/wave_rate.py).
 --packets-per-file P: files of P packets of 20 ms (in pages of at most 250) in place of the default 10, for --mel and --melspec: long
 tracks, whose tiles are full.
 --resample UP/DOWN [--mono | --mix M]: the fused ratio call (opusgpu_files_decode_ratio, include/opusgpu.h TRACK RATIOS) next to
@@ -74,7 +77,11 @@ ap.add_argument("--fbank", choices=["wenet", "mfcc", "mfcc8k", "wide"], default=
 ap.add_argument("--feature-batch", default=None, metavar="S[:NORM]",
                 help="with --mel or --fbank: the fused call with a feature-batch request (stride S; none, whisper, cmn or cmvn) next to the "
                      "packed call followed by padding and normalising in torch (tools/mel_rate.py: compare_feature_batch)")
-ap.add_argument("--packets-per-file", type=int, default=10, help="with --mel, --melspec, --fbank or --loudness: packets of 20 ms per file")
+ap.add_argument("--wave-batch", default=None, metavar="S[:NORM]",
+                help="with --rate: the fused call with a wave-batch request (stride S, 0: the longest track; none, zmuv or peak) next to the "
+                     "packed float32 call followed by padding, normalising and masking in torch (tools/wave_rate.py)")
+ap.add_argument("--packets-per-file", type=int, default=10,
+                help="with --mel, --melspec, --fbank, --loudness or --wave-batch: packets of 20 ms per file")
 ap.add_argument("--loudness", nargs="?", const="measure", default=None, metavar="TARGET",
                 help="what a loudness request adds to the float32 call, measuring and (with a target in LUFS) normalising (tools/loudness_rate.py)")
 ap.add_argument("--cuts", type=int, default=None, metavar="C", help="C random cuts per file next to the whole files (tools/cuts_rate.py)")
@@ -94,8 +101,10 @@ if args.melspec and (args.rate or args.format or args.resample or args.mel):
     ap.error("--melspec goes without --rate, --resample, --format and --mel")
 if args.feature_batch and not (args.mel or args.fbank):
     ap.error("--feature-batch goes with --mel or --fbank")
-if args.packets_per_file != 10 and not (args.mel or args.melspec or args.fbank or args.loudness or args.cuts is not None):
-    ap.error("--packets-per-file goes with --mel, --melspec, --fbank, --loudness or --cuts")
+if args.wave_batch and (not args.rate or args.loudness or (args.rate == 48000 and not (args.mono or args.mix))):
+    ap.error("--wave-batch goes with --rate R, and at 48000 with --mono or --mix")
+if args.packets_per_file != 10 and not (args.mel or args.melspec or args.fbank or args.loudness or args.cuts is not None or args.wave_batch):
+    ap.error("--packets-per-file goes with --mel, --melspec, --fbank, --loudness, --cuts or --wave-batch")
 if args.mix and (args.mono or not (args.rate or args.resample)):
     ap.error("--mix goes with --rate or --resample and without --mono")
 if args.mel and (args.rate or args.format or args.resample):
@@ -187,7 +196,7 @@ if args.format:
 if args.rate:
     import resample_rate
     b = pkg.FileBatch([r.tobytes() for r in files], channels=2, flags=pkg.PAGES_GROUP_BY_MODE, threads=args.threads)
-    assert (b.info["status"] == 0).all() and b.n_steps == 10
+    assert (b.info["status"] == 0).all() and b.n_steps == PAGES * PER_PAGE
     ctx = pkg.Context(0)
     ctx.streams_alloc(n, 2)
     rec = pkg.mix_matrix(args.mix, 2) if args.mix else None
@@ -200,6 +209,15 @@ if args.rate:
                         "opusgpu_files_decode_resampled")
     for name, pipe in (("in_order", 0), ("pipelined", 1)):
         ctx.set_pipeline(pipe)
+        if args.wave_batch:
+            import wave_rate
+            S, norm = wave_rate.wave_batch_arg(args.wave_batch)
+            print(json.dumps(wave_rate.compare_wave_batch(
+                torch, pkg, resampled,
+                lambda wb: ctx._chk(ctx.lib.opusgpu_set_wave_batch(ctx.h, None if wb is None else wb.rec.ctypes.data), "opusgpu_set_wave_batch"),
+                b, 1, 48000 // args.rate, 1 if args.mono else int(rec["out_channels"][0]) if rec is not None else 2, S, norm, args.reps,
+                f"stereo CELT-FB, {PAGES * PER_PAGE} packets per file, {name}")), flush=True)
+            continue
         print(json.dumps(resample_rate.compare(
             torch, pkg, lambda d, ln, st: ctx._chk(ctx.lib.opusgpu_files_decode(ctx.h, b.h, d, ln, st), "opusgpu_files_decode"), resampled,
             b, args.rate, args.mono, args.reps, name, mix=pkg.downmix_matrix(2, 1 if args.mix == "mono" else 2) if args.mix else None)))

@@ -14,6 +14,9 @@ ms_rate.py's count per step).
 --format f32 | f32_planar: the whole call per track format instead (tools/format_rate.py).
 --rate R: the whole call at a track rate instead (tools/resample_rate.py).
 --rate R --mix mono | stereo: the same through the 5.1 default downmix table (opusgpu_ms_files_decode_mixed).
+--rate R [--mix M] --wave-batch S[:NORM] [--packets-per-file P]: the fused call under a wave-batch request (include/opusgpu.h WAVE
+BATCHES) next to the packed float32 call followed by padding, normalising and masking in torch (tools/wave_rate.py, as
+tools/files_rate.py --wave-batch).
 --mel [--n-mels N]: the fused log-mel call (opusgpu_ms_files_decode_mel through the default mono downmix) next to float32 16 kHz mono
 tracks followed by torch.stft, the filterbank matmul and log10, and k_tracks_mel's share of the call (tools/mel_rate.py).
 --melspec tts | kaldi | clap | music: the fused mel-spectrogram call (opusgpu_ms_files_decode_melspec through the default mono downmix)
@@ -64,7 +67,10 @@ ap.add_argument("--fbank", choices=["wenet", "mfcc", "mfcc8k", "wide"], default=
                 help="compare the fused Kaldi fbank / MFCC call with float mono tracks at the set's rate + unfold / rfft in torch (tools/mel_rate.py)")
 ap.add_argument("--loudness", nargs="?", const="measure", default=None, metavar="TARGET",
                 help="what a loudness request adds to the float32 call, measuring and (with a target in LUFS) normalising (tools/loudness_rate.py)")
-ap.add_argument("--packets-per-file", type=int, default=10, help="with --loudness: packets of 20 ms per file, at most 80")
+ap.add_argument("--wave-batch", default=None, metavar="S[:NORM]",
+                help="with --rate: the fused call with a wave-batch request (stride S, 0: the longest track; none, zmuv or peak) next to the "
+                     "packed float32 call followed by padding, normalising and masking in torch (tools/wave_rate.py)")
+ap.add_argument("--packets-per-file", type=int, default=10, help="with --loudness, --cuts or --wave-batch: packets of 20 ms per file, at most 80")
 ap.add_argument("--cuts", type=int, default=None, metavar="C", help="C random cuts per file next to the whole files (tools/cuts_rate.py)")
 ap.add_argument("--cut-seconds", type=float, default=0.5, metavar="S")
 ap.add_argument("--stride", action="store_true", help="with --cuts: cuts of unequal length, packed and at a stride with zeroed tails")
@@ -76,8 +82,10 @@ if args.fbank and (args.rate or args.format or args.resample or args.mel or args
     ap.error("--fbank goes alone")
 if args.loudness and (args.format or args.rate or args.mel or args.melspec or args.resample or args.mix):
     ap.error("--loudness goes alone")
-if args.packets_per_file != 10 and (not (args.loudness or args.cuts is not None) or not 1 <= args.packets_per_file <= 80):
-    ap.error("--packets-per-file goes with --loudness or --cuts and is at most 80: the files have one page")
+if args.wave_batch and not args.rate:
+    ap.error("--wave-batch goes with --rate R")
+if args.packets_per_file != 10 and (not (args.loudness or args.cuts is not None or args.wave_batch) or not 1 <= args.packets_per_file <= 80):
+    ap.error("--packets-per-file goes with --loudness, --cuts or --wave-batch and is at most 80: the files have one page")
 if args.melspec and (args.rate or args.format or args.resample or args.mel):
     ap.error("--melspec goes without --rate, --resample, --format and --mel")
 if args.mix and not (args.rate or args.resample):
@@ -225,6 +233,16 @@ if args.rate:
                            "opusgpu_ms_files_decode_mixed")
         return ms._chk(ms.lib.opusgpu_ms_files_decode_resampled(ms.h, b.h, args.rate, fmt, None, d, oo, ol, ln, st),
                        "opusgpu_ms_files_decode_resampled")
+    if args.wave_batch:
+        import wave_rate
+        stride, norm = wave_rate.wave_batch_arg(args.wave_batch)
+        print(json.dumps(wave_rate.compare_wave_batch(
+            torch, pkg, resampled,
+            lambda wb: ms._chk(ms.lib.opusgpu_ms_set_wave_batch(ms.h, None if wb is None else wb.rec.ctypes.data), "opusgpu_ms_set_wave_batch"),
+            b, 1, 48000 // args.rate, int(rec["out_channels"][0]) if rec is not None else CH, stride, norm, args.reps,
+            f"5.1 CELT-FB, {PACKETS} packets per file, in_order")))
+        ms.close()
+        raise SystemExit(0)
     print(json.dumps(resample_rate.compare(
         torch, pkg, lambda d, ln, st: ms._chk(ms.lib.opusgpu_ms_files_decode(ms.h, b.h, d, ln, st), "opusgpu_ms_files_decode"), resampled,
         b, args.rate, False, args.reps, "in_order", mix=pkg.downmix_matrix(CH, 1 if args.mix == "mono" else 2) if args.mix else None)))
