@@ -48,6 +48,8 @@ EXPORTS = [
     "opusgpu_ms_files_decode_ratio",
     "opusgpu_spec_basis", "opusgpu_spec_filterbank", "opusgpu_spec_layout", "opusgpu_tracks_melspec_device", "opusgpu_files_decode_melspec",
     "opusgpu_ms_files_decode_melspec",
+    "opusgpu_stft_basis", "opusgpu_stft_tile", "opusgpu_stft_layout", "opusgpu_tracks_stft_device", "opusgpu_files_decode_stft",
+    "opusgpu_ms_files_decode_stft",
     "opusgpu_fbank_window", "opusgpu_fbank_filterbank", "opusgpu_fbank_dct", "opusgpu_fbank_layout", "opusgpu_tracks_fbank_device",
     "opusgpu_files_decode_fbank", "opusgpu_ms_files_decode_fbank",
     "opusgpu_loudness_weights", "opusgpu_loudness_gain", "opusgpu_tracks_loudness_device", "opusgpu_set_loudness", "opusgpu_last_loudness",
@@ -159,6 +161,10 @@ SPEC_SCALES = {"slaney": 0, "htk": 1}
 SPEC_NORMS = {"slaney": 0, None: 1, "none": 1}
 SPEC_LOGS = {None: 0, "none": 0, "log10": 1, "ln": 2}
 SPEC_FRAMES = {"torch": 0, "whisper": 1}
+# opusgpu_stft_params (include/opusgpu.h, TRACK STFT); log, frames and layout take TRACK SPECTROGRAMS' and TRACK FEATURES' values
+STFT_PARAMS_DTYPE = np.dtype([("sample_rate", "<i4"), ("n_fft", "<i4"), ("win_length", "<i4"), ("hop", "<i4"), ("power", "<i4"), ("log", "<i4"),
+                              ("frames", "<i4"), ("layout", "<i4"), ("floor", "<f4"), ("reserved", "<i4", (7,))])
+STFT_COMPLEX = 0  # OPUSGPU_STFT_COMPLEX: power=None
 # opusgpu_fbank_params and its enums (include/opusgpu.h, TRACK KALDI FEATURES)
 FBANK_PARAMS_DTYPE = np.dtype([("sample_rate", "<i4"), ("frame_length", "<i4"), ("frame_shift", "<i4"), ("n_fft", "<i4"), ("n_mels", "<i4"),
                                ("n_ceps", "<i4"), ("window", "<i4"), ("snip_edges", "u1"), ("remove_dc", "u1"), ("power", "u1"), ("log", "u1"),
@@ -332,6 +338,13 @@ def load_lib():
     lib.opusgpu_tracks_melspec_device.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
     lib.opusgpu_files_decode_melspec.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.opusgpu_ms_files_decode_melspec.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.opusgpu_stft_basis.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    lib.opusgpu_stft_tile.argtypes = [vp]
+    lib.opusgpu_stft_layout.argtypes = [C.c_int, vp, C.c_int, C.c_int, vp, vp]
+    lib.opusgpu_stft_layout.restype = C.c_int64
+    lib.opusgpu_tracks_stft_device.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
+    lib.opusgpu_files_decode_stft.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.opusgpu_ms_files_decode_stft.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.opusgpu_fbank_window.argtypes = [vp, C.POINTER(vp)]
     lib.opusgpu_fbank_filterbank.argtypes = [vp, C.POINTER(vp)]
     lib.opusgpu_fbank_dct.argtypes = [vp, C.POINTER(vp)]
@@ -1079,6 +1092,100 @@ def _record_feature_args(batch, rec, layout, rate, resample, mono, mix, format, 
     return rec, mrec, scale, offsets, planes, total, out, how
 
 
+def stft_spec(sample_rate, n_fft, hop, win_length=None, power=2, log=None, floor=0.0, frames="torch", feature_layout="bands"):
+    """An opusgpu_stft_params record (an STFT_PARAMS_DTYPE array of one; include/opusgpu.h TRACK STFT): the numbers that
+    torchaudio's Spectrogram and torch.stft take.  win_length None is n_fft; power 2 (Re^2 + Im^2), 1 (its square root) or None: the
+    complex STFT, with torch.stft's sign; log "log10", "ln" or None, over `floor`; frames "torch" (n // hop + 1) or "whisper"
+    (n // hop); feature_layout "bands" ([bins, frames]) or "frames" ([frames, bins]).  Raises ValueError for what the record's rules
+    refuse."""
+    import numbers
+
+    def whole(name, v):
+        if not isinstance(v, numbers.Integral) or isinstance(v, bool):
+            raise ValueError(f"{name} must be an int, not {v!r}")
+        return int(v)
+    sample_rate, n_fft, hop = whole("sample_rate", sample_rate), whole("n_fft", n_fft), whole("hop", hop)
+    win = n_fft if win_length is None else whole("win_length", win_length)
+    if not 1 <= sample_rate <= 1048576:
+        raise ValueError(f"sample_rate must be in [1, 1048576], not {sample_rate}")
+    if not 64 <= n_fft <= 2048 or n_fft % 16:
+        raise ValueError(f"n_fft must be a multiple of 16 in [64, 2048], not {n_fft}")
+    if not 16 <= win <= n_fft or win % 2:
+        raise ValueError(f"win_length must be even and in [16, n_fft], not {win}")
+    if not 1 <= hop <= n_fft or 31 * hop + n_fft > 32768:
+        raise ValueError(f"hop must be in [1, n_fft] with 31 * hop + n_fft <= 32768, not {hop}")
+    for name, v, table in (("log", log, SPEC_LOGS), ("frames", frames, SPEC_FRAMES), ("feature_layout", feature_layout, MEL_LAYOUTS)):
+        if not isinstance(v, (str, type(None))) or v not in table:
+            raise ValueError(f"{name} must be one of {sorted(table, key=str)}, not {v!r}")
+    if power is not None and (power not in (1, 2) or isinstance(power, bool)):
+        raise ValueError(f"power must be 1, 2 or None (complex), not {power!r}")
+    if power is None and SPEC_LOGS[log]:
+        raise ValueError("a complex STFT (power=None) has no log")
+    rec = np.zeros(1, dtype=STFT_PARAMS_DTYPE)
+    rec["sample_rate"], rec["n_fft"], rec["win_length"], rec["hop"] = sample_rate, n_fft, win, hop
+    rec["power"], rec["log"] = STFT_COMPLEX if power is None else int(power), SPEC_LOGS[log]
+    rec["frames"], rec["layout"] = SPEC_FRAMES[frames], MEL_LAYOUTS[feature_layout]
+    try:
+        rec["floor"] = float(floor)
+    except (TypeError, ValueError):
+        raise ValueError(f"floor must be a number, not {floor!r}") from None
+    floor32 = float(rec["floor"][0])
+    if not np.isfinite(floor32) or floor32 < 0 or (rec["log"][0] and not floor32 > 0):
+        raise ValueError(f"floor must be finite and >= 0, and > 0 with a log, not {floor!r}")
+    return rec
+
+
+def _stft_rec(rec):
+    if getattr(rec, "dtype", None) != STFT_PARAMS_DTYPE or np.size(rec) != 1:
+        raise ValueError("an STFT's parameters are a stft_spec() record")
+    return np.ascontiguousarray(rec).reshape(1)
+
+
+def stft_basis(rec):
+    """opusgpu_stft_basis: the windowed DFT basis of a stft_spec record -> (Wc, Ws), float32 [n_fft, n_fft / 2 + 1] each;
+    Im = -(frame @ Ws)."""
+    rec = _stft_rec(rec)
+    tables = _tables("opusgpu_stft_basis", C.c_float, (rec.ctypes.data,), 2, "opusgpu_stft_basis refused the record")
+    return tuple(a.reshape(int(rec["n_fft"][0]), -1) for a in tables)
+
+
+def stft_tile(rec):
+    """opusgpu_stft_tile: the frames of a tile of k_tracks_stft for a stft_spec record, 128, 64 or 32."""
+    T = load_lib().opusgpu_stft_tile(_stft_rec(rec).ctypes.data)
+    if T < 0:
+        raise ValueError("opusgpu_stft_tile refused the record")
+    return int(T)
+
+
+def stft_width(rec):
+    """The floats of one frame of a stft_spec record: n_fft / 2 + 1 bins, twice that for the complex STFT."""
+    rec = _stft_rec(rec)
+    return (int(rec["n_fft"][0]) // 2 + 1) * (2 if int(rec["power"][0]) == STFT_COMPLEX else 1)
+
+
+def stft_frames(rec, samples):
+    """F of TRACK STFT for tracks of `samples` samples at the record's rate."""
+    rec = _stft_rec(rec)
+    n, hop = np.asarray(samples, dtype=np.int64), int(rec["hop"][0])
+    return n // hop if int(rec["frames"][0]) == SPEC_FRAMES["whisper"] else np.where(n > 0, n // hop + 1, 0)
+
+
+def stft_layout(planned_48k_samples, up, down, rec):
+    """opusgpu_stft_layout: the grid of the STFT spectrograms of tracks at up / down of 48 kHz -> (feat_offsets [int64], planes
+    [int64], total floats)."""
+    rec = _stft_rec(rec)
+    planned, offsets, total = _layout("opusgpu_stft_layout", planned_48k_samples, (int(up), int(down), rec.ctypes.data),
+                                      f"the record, the ratio {up!r}/{down!r} or a negative length")
+    return offsets, (stft_frames(rec, -(-planned * int(up) // int(down))) + 63) // 64 * 64, total
+
+
+def track_stft_args(batch, features, rate=None, resample=None, mono=False, mix=None, format=None, scale=None, out=None, device=0,
+                    allow_mono=True):
+    """track_spectrogram_args for a stft_spec record as decode_files' features=: the same tuple, the same refusals, with
+    stft_layout's grid (total and the out= size are in floats: a complex cell is two)."""
+    return _record_feature_args(batch, _stft_rec(features), stft_layout, rate, resample, mono, mix, format, scale, out, device, allow_mono)
+
+
 def _kaldi_record(sample_rate, frame_length, frame_shift, num_mel_bins, low_freq, high_freq, preemphasis_coefficient, remove_dc_offset,
                   window_type, round_to_power_of_two, snip_edges, use_power, use_log_fbank, feature_layout, n_ceps, cepstral_lifter, rejected):
     import numbers
@@ -1518,6 +1625,11 @@ def _files_request(batch, multistream=False, device=0, format=None, scale=None, 
         rec, mrec, scale, offsets, planes, total, out, how = sargs
         return FilesRequest("files_decode_melspec", how + mono_arg + (mrec, rec), "features", TRACKS_F32, scale, out, 1, offsets, planes, total,
                             mrec, rec)
+    if getattr(features, "dtype", None) == STFT_PARAMS_DTYPE:
+        rec, mrec, scale, offsets, planes, total, out, how = track_stft_args(batch, features, rate, resample, mono, mix, format, scale, out,
+                                                                             device, allow_mono)
+        return FilesRequest("files_decode_stft", how + mono_arg + (mrec, rec), "features", TRACKS_F32, scale, out, 1, offsets, planes, total,
+                            mrec, rec)
     if getattr(features, "dtype", None) == FBANK_PARAMS_DTYPE:
         rec, mrec, scale, offsets, planes, total, out, how = track_kaldi_args(batch, features, rate, resample, mono, mix, format, scale, out,
                                                                               device, allow_mono)
@@ -1572,6 +1684,9 @@ def files_request(batch, multistream=False, device=0, format=None, scale=None, o
     dense = feature_stride is not None or normalize is not None or feature_pad is not None
     if dense and features is None:
         raise ValueError("feature_stride=, normalize= and feature_pad= need features=")
+    if dense and getattr(features, "dtype", None) == STFT_PARAMS_DTYPE:
+        raise ValueError("feature_stride=, normalize= and feature_pad= do not go with a stft_spec() record: feature batches hold widths of "
+                         "1 - 128, a linear spectrogram has n_fft / 2 + 1 bins")
     if wave and features is not None:
         raise ValueError("wave_stride=, wave_normalize=, wave_pad= and wave_mask= are for tracks: features have feature_stride= and normalize=")
     if wave and format in (None, "s16"):
@@ -1694,6 +1809,20 @@ def _run_files_request(req, lib, prefix, handle, chk, batch, mem):
     else:
         assert (offsets == req.offsets).all()
         info[count_field], info[offset_field] = counts, offsets
+    if req.kind == "features" and req.params.dtype == STFT_PARAMS_DTYPE:  # TRACK STFT: [bins, F] or [F, bins], complex64 over the pairs
+        bins, pairs = int(req.params["n_fft"][0]) // 2 + 1, int(req.params["power"][0]) == STFT_COMPLEX
+        c = 2 if pairs else 1
+
+        def cells(flat, *shape):  # `flat`: the track's floats as they lie; a numpy array or a torch tensor
+            if not pairs:
+                return flat.reshape(*shape)
+            if isinstance(flat, np.ndarray):
+                return flat.view(np.complex64).reshape(*shape)
+            import torch
+            return torch.view_as_complex(flat.reshape(*shape, 2))
+        if int(req.params["layout"][0]) == MEL_FRAMES_MAJOR:
+            return [cells(packed[o:o + F * bins * c], F, bins) for o, F in zip(offsets, counts)], info
+        return [cells(packed[o:o + bins * p * c], bins, p)[:, :F] for o, p, F in zip(offsets, req.planes, counts)], info
     if req.kind == "features":
         n_mels = fbank_width(req.params) if req.params.dtype == FBANK_PARAMS_DTYPE else int(req.params["n_mels"][0])
         if fb is not None:  # FEATURE BATCHES: one dense tensor, every track fb.stride frames, padded behind its info["frames"]
@@ -1961,6 +2090,15 @@ class Context:
         self._chk(self.lib.opusgpu_tracks_melspec_device(self.h, spans.size, spans.ctypes.data, d_in, rec.ctypes.data, d_out, stream),
                   "opusgpu_tracks_melspec_device")
 
+    def tracks_stft_device(self, spans, d_in, rec, d_out, stream=None):
+        """k_tracks_stft alone (include/opusgpu.h TRACK STFT): spans a HOST array of MEL_SPAN_DTYPE, d_in packed int16 mono tracks at
+        the record's rate, rec a stft_spec record, d_out the float32 spectrogram tracks (pairs for the complex STFT).  Waits for the
+        kernel."""
+        spans = np.ascontiguousarray(spans, dtype=MEL_SPAN_DTYPE)
+        rec = _stft_rec(rec)
+        self._chk(self.lib.opusgpu_tracks_stft_device(self.h, spans.size, spans.ctypes.data, d_in, rec.ctypes.data, d_out, stream),
+                  "opusgpu_tracks_stft_device")
+
     def tracks_loudness_device(self, spans, d_in, channels, weights=None, stream=None):
         """k_tracks_loudness_seg and k_tracks_loudness_gate alone (include/opusgpu.h TRACK LOUDNESS): spans a HOST array of
         LOUDNESS_SPAN_DTYPE, d_in packed int16 tracks of `channels` channels, weights None (the defaults) or one float per channel
@@ -2026,6 +2164,11 @@ class Context:
         features may also be a kaldi_fbank() or kaldi_mfcc() record: Kaldi's fbank or MFCC features of the mono track at the record's
         sample_rate (include/opusgpu.h TRACK KALDI FEATURES), with the same keywords as for a mel_spec() record (track_kaldi_args);
         scale=1.0 gives Kaldi's int16-range convention.  The result is [F, n_mels or n_ceps] ("frames", the record's default).
+        features may also be a stft_spec() record: the linear spectrogram of the mono track at the record's sample_rate, all
+        n_fft / 2 + 1 bins as power, magnitude or the complex STFT with torch.stft's sign (include/opusgpu.h TRACK STFT), with the
+        same keywords as for a mel_spec() record (track_stft_args).  The result is float32 [bins, F] ("bands") or [F, bins]
+        ("frames"), complex64 for power=None (a view of the pairs; out= stays a float32 tensor of stft_layout's total floats).
+        feature_stride=, normalize= and feature_pad= are refused with it: feature batches hold widths of 1 - 128.
         loudness: None, or "measure" for the integrated loudness (ITU-R BS.1770-4) and sample peak of every track, measured on the
         GPU on the 48 kHz int16 track in the same call (include/opusgpu.h TRACK LOUDNESS) -- the result is what it is without it,
         and info gains `lufs` (-inf: no block passed the gates), `peak`, `loudness_blocks`, `loudness_gated` and `gain` (1.0) --, or

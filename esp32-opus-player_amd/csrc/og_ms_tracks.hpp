@@ -1,7 +1,7 @@
 // og_ms_tracks.hpp -- whole multistream files (include/opusgpu.h, WHOLE FILES / MULTISTREAM): the kernel that maps channels and
 // assembles tracks in one pass, and what the driver of a planned batch (og_files_run.hpp) needs of an opusgpu_ms.  Included at the
 // end of og_api.hip behind og_ms.hpp (opusgpu_ms, ms_step_impl), og_tracks.hpp (TrackSeg, TrackState), og_tracks_resample.hpp,
-// og_tracks_resample_ratio.hpp, og_tracks_mel.hpp, og_tracks_melspec.hpp and og_tracks_fbank.hpp.
+// og_tracks_resample_ratio.hpp, og_tracks_mel.hpp, og_tracks_melspec.hpp, og_tracks_stft.hpp and og_tracks_fbank.hpp.
 #pragma once
 
 // ---- kernel -------------------------------------------------------------------------------------------
@@ -522,6 +522,15 @@ int opusgpu_ms_files_decode_melspec(opusgpu_ms *ms, const opusgpu_ms_file_batch 
     if (!ms || !batch || !mix) return OPUSGPU_BAD_ARG;
     return files_melspec_run(files_owner(ms, batch), rate, up, down, 0, mix, p, scale, d_out, feat_offsets, frames_out, track_lengths_out,
                              status_out);
+}
+
+// opusgpu_files_decode_stft behind opusgpu_ms_files_decode (og_tracks_stft.hpp): the layout's channels through a one-row *mix.
+int opusgpu_ms_files_decode_stft(opusgpu_ms *ms, const opusgpu_ms_file_batch *batch, int rate, int up, int down,
+                                 const opusgpu_mix_matrix *mix, const opusgpu_stft_params *p, const float *scale, void *d_out,
+                                 int64_t *feat_offsets, int64_t *frames_out, int64_t *track_lengths_out, int32_t *status_out) {
+    if (!ms || !batch || !mix) return OPUSGPU_BAD_ARG;
+    return files_stft_run(files_owner(ms, batch), rate, up, down, 0, mix, p, scale, d_out, feat_offsets, frames_out, track_lengths_out,
+                          status_out);
 }
 
 // opusgpu_files_decode_fbank behind opusgpu_ms_files_decode (og_tracks_fbank.hpp): the layout's channels through a one-row *mix.

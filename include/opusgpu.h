@@ -1055,7 +1055,85 @@ int opusgpu_files_decode_fbank(opusgpu_ctx *ctx, const opusgpu_file_batch *batch
                                const opusgpu_mix_matrix *mix, const opusgpu_fbank_params *p, const float *scale, void *d_out,
                                int64_t *feat_offsets, int64_t *frames_out, int64_t *track_lengths_out, int32_t *status_out);
 
-/* TRACK LOUDNESS.  Integrated loudness per ITU-R BS.1770-4 and the sample peak of every track, measured on the GPU, and optionally
+/* TRACK STFT.  The spectrogram itself: all n_fft / 2 + 1 linear bins of the short-time Fourier transform of the mono track at any
+ * rate of TRACK RATES and TRACK RATIOS, as magnitude, power or complex numbers -- what torchaudio.transforms.Spectrogram and
+ * torch.stft(center=True, pad_mode="reflect", window=hann_window(win_length), return_complex=True) give -- in the same call that
+ * decodes the files: the input of VITS-style TTS (22050 Hz, 1024 / 256, magnitude), of speech enhancement and separation (16000 Hz,
+ * 512 / 400 / 128, complex), of music models (44100 Hz, 2048 points) and of any filterbank of the caller's own.  No setting of
+ * opusgpu_spec_params is this computation (n_mels is 1 .. 128 there and the band product always runs), so it is a section of its
+ * own with a record, calls and a kernel of its own; TRACK FEATURES, TRACK SPECTROGRAMS and TRACK KALDI FEATURES, their records,
+ * grids, refusals and kernels are unchanged.  The definition is this comment.
+ *   INPUT.  An int16 mono track y[m], m in [0, n), exactly as TRACK RATES, TRACK RATIOS and CHANNEL MIX define it.
+ *   FRAMES.  OPUSGPU_SPEC_FRAMES_TORCH: F = n / hop + 1 (floor; F = 0 for n == 0), torch.stft(center=True).  _WHISPER: F = n / hop.
+ *   WINDOW.  L = win_length (n_fft if 0), left = (n_fft - L) / 2; w[i] = 0.5 - 0.5 cos(2 pi (i - left) / L) for i in [left, left + L),
+ *   else 0: the periodic Hann window that torch.stft centres in the frame.  n_fft and L are even, so w[i] = w[n_fft - i].
+ *   WINDOW INDEX.  Frame f, tap i in [0, n_fft) reads q = hop * f - n_fft / 2 + i, reflected ONCE: q < 0 becomes -q, q >= n becomes
+ *   2 (n - 1) - q; if q is still outside [0, n) the sample is 0.  Unlike torch.stft, which refuses n <= n_fft / 2, the value is
+ *   defined for every n.
+ *   SAMPLE.  x_i = (float)y[q] * scale[track], one IEEE multiply; the default scale is 1 / 32768.
+ *   DFT.  Re[k] = sum_i Wc[i][k] x_i, Im[k] = -sum_i Ws[i][k] x_i, k in [0, n_fft / 2]; Wc[i][k] = w[i] cos(a), Ws[i][k] = w[i] sin(a),
+ *   a = 2 pi ((i k) mod n_fft) / n_fft.  Wc and Ws are TRACK SPECTROGRAMS' tables, made by the one builder: what opusgpu_stft_basis
+ *   hands out is what opusgpu_spec_basis hands out for the same n_fft and win_length, bit for bit.  SIGN: Ws as both accessors hand
+ *   it out is +w sin(a), the OPPOSITE of torch.stft's imaginary part (e^{-ia} = cos a - i sin a), which the mel path never sees
+ *   because it squares; Im here carries torch.stft's sign, hence the minus above.
+ *   OUTPUT, for every k in [0, n_fft / 2].  OPUSGPU_STFT_COMPLEX (power 0): the pair (Re[k], Im[k]) as two adjacent floats, torch's
+ *   view_as_real order; floor is not applied.  power 2: S = Re^2 + Im^2; power 1: S = sqrtf(Re^2 + Im^2); v = max(S, floor); then v,
+ *   log10f(v) or logf(v) as `log` says, float32.  A log is refused with OPUSGPU_STFT_COMPLEX.
+ *   TABLES.  float32, each entry computed in double and rounded once, at first use, kept per distinct (n_fft, win_length) for the
+ *   life of the process and safe to ask for from any number of threads: Wc, Ws (2 x n_fft x (n_fft / 2 + 1) floats) and the kernel's
+ *   copy of the half it multiplies.
+ *   SUMMATION ORDER is not part of the contract (the kernel folds x_i +- x_{n_fft - i} against half the basis).  What is: the
+ *   tolerance of tests/test_gpu_tracks_stft.py (8 x the error of a float32 restatement against float64), the
+ *   same bits from the same call on the same input, and one bit pattern in every cell of an all-zero track: the floor's value (its
+ *   log with a log), and +0.0f in both halves of every pair for OPUSGPU_STFT_COMPLEX -- never -0.0f, whatever the scale's sign.
+ *   LAYOUT.  TRACK FEATURES' grid at width bins * c, bins = n_fft / 2 + 1, c = 2 for OPUSGPU_STFT_COMPLEX, else 1: plane[t] =
+ *   roundup64(F(ceil(planned_48k[t] * up / down))) frames; feat_offset[t] the running sum of bins * c * plane[u], a multiple of 64
+ *   floats.  OPUSGPU_MEL_BANDS_MAJOR (bins-major): cell (k, f) at feat_offset + (k * plane + f) * c.  OPUSGPU_MEL_FRAMES_MAJOR: at
+ *   feat_offset + (f * bins + k) * c.  Padding is never written; a track cut short by a failed frame keeps its planned plane and
+ *   reports its shorter F. */
+#define OPUSGPU_STFT_COMPLEX 0
+typedef struct opusgpu_stft_params { /* 64 bytes (ABI) */
+    int32_t sample_rate; /* Hz of the mono track the frames are cut from, 1 .. 1048576; the whole-file calls check it */
+    int32_t n_fft;       /* a multiple of 16 in [64, 2048] */
+    int32_t win_length;  /* even, in [16, n_fft]; 0 means n_fft */
+    int32_t hop;         /* in [1, n_fft], and 31 * hop + n_fft <= 32768 */
+    int32_t power;       /* OPUSGPU_STFT_COMPLEX 0: (Re, Im) pairs; 1: sqrt(Re^2 + Im^2); 2: Re^2 + Im^2 */
+    int32_t log;         /* OPUSGPU_SPEC_LOG_NONE 0 | OPUSGPU_SPEC_LOG10 1 | OPUSGPU_SPEC_LN 2; OPUSGPU_SPEC_LOG_NONE with power 0 */
+    int32_t frames;      /* OPUSGPU_SPEC_FRAMES_TORCH 0: F = n / hop + 1 (0 for n == 0); OPUSGPU_SPEC_FRAMES_WHISPER 1: F = n / hop */
+    int32_t layout;      /* OPUSGPU_MEL_BANDS_MAJOR (bins-major) | OPUSGPU_MEL_FRAMES_MAJOR */
+    float floor;         /* finite, >= 0; > 0 with a log; not applied to pairs */
+    int32_t reserved[7]; /* 0 */
+} opusgpu_stft_params;
+/* The DFT basis of *p: sets *wc and *ws (either may be NULL) to Wc and Ws, [n_fft][n_fft / 2 + 1] floats each, valid for the life
+ * of the process, and returns n_fft * (n_fft / 2 + 1); OPUSGPU_BAD_ARG for a record that breaks a rule above.  Host only. */
+int opusgpu_stft_basis(const opusgpu_stft_params *p, const float **wc, const float **ws);
+/* The frames of a tile of k_tracks_stft for *p: the largest of 128, 64 and 32 whose window of (T - 1) hop + n_fft samples is at most
+ * 32768 samples (65,536 bytes of LDS), TRACK SPECTROGRAMS' rule: the kernel stores from its accumulators and needs no store area.
+ * OPUSGPU_BAD_ARG for a record that breaks a rule.  Host only. */
+int opusgpu_stft_tile(const opusgpu_stft_params *p);
+/* LAYOUT above for n tracks of planned_48k_samples[i] samples at 48 kHz whose frames are cut at up / down of that rate (1 <= up <=
+ * down <= 48000; not reduced, not held against sample_rate): writes feat_offsets[i] (may be NULL) and returns the total in floats.
+ * OPUSGPU_BAD_ARG: a record that breaks a rule, such an up / down, a negative length.  Host only. */
+int64_t opusgpu_stft_layout(int n, const int64_t *planned_48k_samples, int up, int down, const opusgpu_stft_params *p, int64_t *feat_offsets);
+/* k_tracks_stft alone: opusgpu_tracks_melspec_device's contract and alignment rules -- d_in_mono packed int16 mono tracks, 16-byte
+ * aligned, read in aligned 16-byte pieces up to the one that holds a track's last sample; `spans` a HOST array of opusgpu_mel_span,
+ * whose plane must be a multiple of 64 and >= F; d_out floats, 128-byte aligned -- with this section's record and width.
+ * sample_rate is held against nothing.  A track without a frame writes nothing.  Uploads the records, its tile table and the
+ * kernel's table, launches on the context's stream (or `hip_stream`), waits, and frees all of them on every way out.
+ * OPUSGPU_BAD_ARG before any device work: a record that breaks a rule, a span that does, a scale that is not finite. */
+int opusgpu_tracks_stft_device(opusgpu_ctx *ctx, int n_tracks, const opusgpu_mel_span *spans, const void *d_in_mono,
+                               const opusgpu_stft_params *p, void *d_out, void *hip_stream);
+/* opusgpu_files_decode into linear or complex spectrograms: opusgpu_files_decode_melspec's flow, arguments, "written last" and
+ * refusals with this section's record, kernel and layout: rate != 0 names a rate of TRACK RATES, rate == 0 the ratio up / down of
+ * TRACK RATIOS; `mono` 1 or a *mix of one row; d_out opusgpu_stft_layout's total in floats, 128-byte aligned; frames_out is F of
+ * the final length.  OPUSGPU_BAD_ARG before any device work, the buffer and the caller's arrays left as they were: a record that
+ * breaks a rule; a sample_rate that is not the track's rate; whatever opusgpu_files_decode_melspec refuses of the other arguments;
+ * a feature-batch request on the context (FEATURE BATCHES hold widths of 1 - 128). */
+int opusgpu_files_decode_stft(opusgpu_ctx *ctx, const opusgpu_file_batch *batch, int rate, int up, int down, int mono,
+                              const opusgpu_mix_matrix *mix, const opusgpu_stft_params *p, const float *scale, void *d_out,
+                              int64_t *feat_offsets, int64_t *frames_out, int64_t *track_lengths_out, int32_t *status_out);
+
+/* TRACK LOUDNESS. Integrated loudness per ITU-R BS.1770-4 and the sample peak of every track, measured on the GPU, and optionally
  * a gain to a target loudness folded into the float scale of the same call.  All of it is a function of the S16 track at 48 kHz:
  * the int16 samples s_c[n] the default path writes, at the track's FINAL length len.  Samples at or past len are never read as
  * signal.
@@ -1423,6 +1501,12 @@ int opusgpu_ms_files_decode_melspec(opusgpu_ms *ms, const opusgpu_ms_file_batch 
 int opusgpu_ms_files_decode_fbank(opusgpu_ms *ms, const opusgpu_ms_file_batch *batch, int rate, int up, int down,
                                   const opusgpu_mix_matrix *mix, const opusgpu_fbank_params *p, const float *scale, void *d_out,
                                   int64_t *feat_offsets, int64_t *frames_out, int64_t *track_lengths_out, int32_t *status_out);
+
+/* opusgpu_files_decode_stft behind opusgpu_ms_files_decode (TRACK STFT): the layout's channels through *mix, which must have
+ * out_channels == 1; there is no `mono` here.  Refusals as there, plus a NULL mix. */
+int opusgpu_ms_files_decode_stft(opusgpu_ms *ms, const opusgpu_ms_file_batch *batch, int rate, int up, int down,
+                                 const opusgpu_mix_matrix *mix, const opusgpu_stft_params *p, const float *scale, void *d_out,
+                                 int64_t *feat_offsets, int64_t *frames_out, int64_t *track_lengths_out, int32_t *status_out);
 
 /* ---- WHOLE FILES / CUTS: pieces of files as tracks, with pre-roll, packed or at a fixed stride -------------------------------
  * A cut is samples [start, start + count) of a file's whole-file track (the axis opusgpu_files_plan makes: pre-skip, hole discards

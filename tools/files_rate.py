@@ -17,6 +17,10 @@ torch.stft, the filterbank matmul and log10, and k_tracks_mel's share of the cal
 --melspec tts | kaldi | clap | music: the fused mel-spectrogram call (opusgpu_files_decode_melspec, mono; include/opusgpu.h TRACK
 SPECTROGRAMS) at that set's rate next to float32 mono tracks at the rate followed by torch.stft, the filterbank matmul, the floor and
 the log, and k_tracks_melspec's share of the call (tools/mel_rate.py: compare_spec).
+--stft tiny | enh | vits | wide | whisper_lin [--stft-layout bands | frames]: the fused linear / complex STFT call
+(opusgpu_files_decode_stft, mono; include/opusgpu.h TRACK STFT) at that set's rate next to float32 mono tracks at the rate followed by
+torch.stft, abs / abs ** 2 / nothing, the floor and the log, k_tracks_stft's share of the call and the bytes it writes per second
+(tools/mel_rate.py: compare_stft).
 --fbank wenet | mfcc | mfcc8k | wide: the fused Kaldi fbank / MFCC call (opusgpu_files_decode_fbank, mono; include/opusgpu.h TRACK KALDI
 FEATURES) against float mono tracks at the set's rate followed by the torch restatement (unfold, mean, pre-emphasis, window, rfft,
 matmul, log), and k_tracks_fbank's share of the call (tools/mel_rate.py: compare_fbank); a set at 16 kHz is followed by --melspec
@@ -40,7 +44,7 @@ a block: --packets-per-file 500 gives 10 s files.
 seconds out of each as F x C tracks (include/opusgpu.h WHOLE FILES / CUTS; tools/cuts_rate.py), pipelined: both times, audio seconds
 out per second for both, both planner times, the pre-roll's share; --stride adds cuts of unequal length packed and strided, whose
 difference is what the zeroed tails cost.  --stats DIR --tail-bytes B reads k_tracks_fill_tail's row of a kernel trace of that run.
-usage (GPU box): python3 tools/files_rate.py [--n N] [--reps R] [--loudness [T] |--format F | --rate R [--mono | --mix M] | --resample U/D [--mono | --mix M] | --mel [--n-mels N] | --melspec SET | --fbank SET] [--packets-per-file P] | python3 tools/files_rate.py --stats DIR [--n N]"""
+usage (GPU box): python3 tools/files_rate.py [--n N] [--reps R] [--loudness [T] |--format F | --rate R [--mono | --mix M] | --resample U/D [--mono | --mix M] | --mel [--n-mels N] | --melspec SET | --stft SET | --fbank SET] [--packets-per-file P] | python3 tools/files_rate.py --stats DIR [--n N]"""
 import argparse
 import ctypes as C
 import glob
@@ -72,6 +76,9 @@ ap.add_argument("--mel", action="store_true", help="compare the fused log-mel ca
 ap.add_argument("--n-mels", type=int, choices=[80, 128], default=80)
 ap.add_argument("--melspec", choices=["tts", "kaldi", "clap", "music"], default=None,
                 help="compare the fused mel-spectrogram call with float mono tracks at the set's rate + torch.stft (tools/mel_rate.py)")
+ap.add_argument("--stft", choices=["tiny", "enh", "vits", "wide", "whisper_lin"], default=None,
+                help="compare the fused STFT call with float mono tracks at the set's rate + torch.stft (tools/mel_rate.py: compare_stft)")
+ap.add_argument("--stft-layout", choices=["bands", "frames"], default="bands", help="with --stft: the record's feature_layout")
 ap.add_argument("--fbank", choices=["wenet", "mfcc", "mfcc8k", "wide"], default=None,
                 help="compare the fused Kaldi fbank / MFCC call with float mono tracks at the set's rate + unfold / rfft in torch (tools/mel_rate.py)")
 ap.add_argument("--feature-batch", default=None, metavar="S[:NORM]",
@@ -99,12 +106,16 @@ if args.loudness and (args.format or args.mel or args.melspec or args.resample o
     ap.error("--loudness goes alone or with --rate R --mono")
 if args.melspec and (args.rate or args.format or args.resample or args.mel):
     ap.error("--melspec goes without --rate, --resample, --format and --mel")
+if args.stft and (args.rate or args.format or args.resample or args.mel or args.melspec or args.fbank or args.loudness or args.mix or args.mono or
+                  args.cuts is not None):
+    ap.error("--stft goes alone (with --stft-layout, --n, --packets-per-file, --reps)")
 if args.feature_batch and not (args.mel or args.fbank):
     ap.error("--feature-batch goes with --mel or --fbank")
 if args.wave_batch and (not args.rate or args.loudness or (args.rate == 48000 and not (args.mono or args.mix))):
     ap.error("--wave-batch goes with --rate R, and at 48000 with --mono or --mix")
-if args.packets_per_file != 10 and not (args.mel or args.melspec or args.fbank or args.loudness or args.cuts is not None or args.wave_batch):
-    ap.error("--packets-per-file goes with --mel, --melspec, --fbank, --loudness, --cuts or --wave-batch")
+if args.packets_per_file != 10 and not (args.mel or args.melspec or args.stft or args.fbank or args.loudness or args.cuts is not None or
+                                        args.wave_batch):
+    ap.error("--packets-per-file goes with --mel, --melspec, --stft, --fbank, --loudness, --cuts or --wave-batch")
 if args.mix and (args.mono or not (args.rate or args.resample)):
     ap.error("--mix goes with --rate or --resample and without --mono")
 if args.mel and (args.rate or args.format or args.resample):
@@ -112,7 +123,7 @@ if args.mel and (args.rate or args.format or args.resample):
 if args.resample and (args.rate or args.format):
     ap.error("--resample goes without --rate and --format")
 n = args.n
-if (args.format or args.rate or args.mel or args.resample or args.melspec or args.fbank) and not args.loudness:
+if (args.format or args.rate or args.mel or args.resample or args.melspec or args.stft or args.fbank) and not args.loudness:
     import torch  # before the library: one HIP runtime for both
 
 spec = importlib.util.spec_from_file_location("esp32_opus_player_amd", os.path.join(here, "..", "esp32-opus-player_amd", "__init__.py"))
@@ -326,6 +337,31 @@ if args.melspec:
                                                                                        None, p, None, d, fo, fr, ln, st), "opusgpu_files_decode_melspec"),
             lambda spans, d_in, r, d_out: ctx.tracks_melspec_device(spans, d_in, r, d_out), b, rec, up, down, args.reps,
             f"{args.melspec}, {name}, {PAGES * PER_PAGE} packets per file")), flush=True)
+    ctx.close()
+    raise SystemExit(0)
+
+if args.stft:
+    import mel_rate
+    kw, up, down = mel_rate.STFT_SETS[args.stft]
+    rec = pkg.stft_spec(feature_layout=args.stft_layout, **kw)
+    rate = 48000 // down if up == 1 else 0
+    b = pkg.FileBatch([r.tobytes() for r in files], channels=2, flags=pkg.PAGES_GROUP_BY_MODE, threads=args.threads)
+    assert (b.info["status"] == 0).all() and b.n_steps == PAGES * PER_PAGE
+    ctx = pkg.Context(0)
+    ctx.streams_alloc(n, 2)
+
+    def tracks(fmt, d, oo, ol, ln, st):
+        if rate:
+            return ctx._chk(ctx.lib.opusgpu_files_decode_resampled(ctx.h, b.h, rate, 1, fmt, None, d, oo, ol, ln, st), "opusgpu_files_decode_resampled")
+        return ctx._chk(ctx.lib.opusgpu_files_decode_ratio(ctx.h, b.h, up, down, 1, None, fmt, None, d, oo, ol, ln, st), "opusgpu_files_decode_ratio")
+    for name, pipe in (("in_order", 0), ("pipelined", 1)):
+        ctx.set_pipeline(pipe)
+        print(json.dumps(mel_rate.compare_stft(
+            torch, pkg, tracks,
+            lambda p, d, fo, fr, ln, st: ctx._chk(ctx.lib.opusgpu_files_decode_stft(ctx.h, b.h, rate, 0 if rate else up, 0 if rate else down, 1,
+                                                                                    None, p, None, d, fo, fr, ln, st), "opusgpu_files_decode_stft"),
+            lambda spans, d_in, r, d_out: ctx.tracks_stft_device(spans, d_in, r, d_out), b, rec, up, down, args.reps,
+            f"{args.stft} {args.stft_layout}, {name}, {PAGES * PER_PAGE} packets per file")), flush=True)
     ctx.close()
     raise SystemExit(0)
 

@@ -14,6 +14,9 @@ compare_fbank is the same for --fbank (include/opusgpu.h TRACK KALDI FEATURES) w
 (a) float32 mono tracks at the record's rate, (b) (a) + the torch restatement -- unfold, the frame's mean, the pre-emphasis, the
 window, torch.fft.rfft at n_fft, |.| or |.|^2 without the Nyquist bin, the filterbank matmul, the floor, the log and for MFCC the
 DCT matmul --, (c) the fused call, (m) opusgpu_tracks_fbank_device alone.
+compare_stft is the same for --stft (include/opusgpu.h TRACK STFT) with a stft_spec record: (a) float32 mono tracks at the record's
+rate, (b) (a) + torch.stft + abs, abs ** 2 or nothing + the floor and the log, (c) the fused call, (m) opusgpu_tracks_stft_device
+alone, with the bytes it writes per second.
 compare_feature_batch is --feature-batch S[:NORM] (include/opusgpu.h FEATURE BATCHES) behind --mel or --fbank: (p) the packed feature
 call, (b) (p) + the gather into a padded tensor and the normalisation in torch, (c) the call with the request on.
 torch must be imported before the library is loaded: they then share one HIP runtime."""
@@ -177,6 +180,101 @@ def compare_spec(torch, pkg, decode_tracks, decode_spec, spec_alone, batch, rec,
         out[label] = {"mean_ms": round(float(v.mean()), 3), "median_ms": round(float(np.median(v)), 3),
                       "min_max_ms": [round(float(v.min()), 3), round(float(v.max()), 3)]}
     out["melspec_share_of_c"] = round(float(np.mean(times["m"]) / np.mean(times["c"])), 3)
+    out["c_le_b"] = bool(np.mean(times["c"]) <= np.mean(times["b"]))
+    return out
+
+
+def compare_stft(torch, pkg, decode_tracks, decode_stft, stft_alone, batch, rec, up, down, reps, note=""):
+    """compare_spec's arguments with a stft_spec record (include/opusgpu.h TRACK STFT): (a) float32 mono tracks at the record's rate,
+    (b) (a) + the gather into a padded batch + torch.stft(n_fft, hop, win_length, periodic Hann, center=True) + abs, abs ** 2 or
+    nothing + the floor and the log, (c) the fused call, (m) opusgpu_tracks_stft_device alone, with the bytes per second it writes.
+    -> a dict for the JSON line."""
+    n = batch.n_files
+    planned = batch.info["track_samples"]
+    offs, total = pkg.resample_ratio_layout(planned, up, down) if up != 1 or down not in (1, 2, 3, 4, 6) else pkg.resample_layout(planned, 48000 // down)
+    feat_offs, planes, total_feat = pkg.stft_layout(planned, up, down, rec)
+    n_fft, hop, bins, width = int(rec["n_fft"][0]), int(rec["hop"][0]), int(rec["n_fft"][0]) // 2 + 1, pkg.stft_width(rec)
+    win, power, log, floor = int(rec["win_length"][0]) or n_fft, int(rec["power"][0]), int(rec["log"][0]), float(rec["floor"][0])
+    whisper, frames_major = int(rec["frames"][0]) == 1, int(rec["layout"][0]) == pkg.MEL_FRAMES_MAJOR
+    f32 = torch.empty(max(total, 1), dtype=torch.float32, device="cuda:0")
+    s16 = torch.empty(max(total, 1) + 64, dtype=torch.int16, device="cuda:0")
+    feat = torch.empty(max(total_feat, 1), dtype=torch.float32, device="cuda:0")
+    lengths, out_offsets, out_lengths, fo, frames = (np.zeros(n, dtype=np.int64) for _ in range(5))
+    status = np.zeros((n, 2), dtype=np.int32)
+    len_r = -(-planned * up // down)
+    longest = max(int(len_r.max(initial=1)), n_fft // 2 + 1)  # (torch.stft's reflection needs that much)
+    idx = offs[:, None] + np.arange(longest)[None, :]
+    valid = np.arange(longest)[None, :] < len_r[:, None]
+    gather = torch.tensor(np.where(valid, idx, 0), device="cuda:0")
+    mask = torch.tensor(valid, device="cuda:0")
+    window = torch.hann_window(win, periodic=True, device="cuda:0")
+
+    def a():
+        decode_tracks(pkg.TRACKS_F32, f32.data_ptr(), out_offsets.ctypes.data, out_lengths.ctypes.data, lengths.ctypes.data, status.ctypes.data)
+
+    def b():
+        a()
+        x = torch.where(mask, f32[gather], torch.zeros((), device="cuda:0"))
+        out = torch.stft(x, n_fft, hop, win_length=win, window=window, center=True, return_complex=True)  # [files, bins, frames]
+        if whisper:
+            out = out[..., :-1]
+        if power:
+            out = torch.clamp(out.abs() if power == 1 else out.abs() ** 2, min=floor)
+            out = torch.log10(out) if log == 1 else torch.log(out) if log == 2 else out
+        if frames_major:
+            out = out.transpose(1, 2).contiguous()
+        torch.cuda.synchronize()
+        return out
+
+    def c():
+        decode_stft(rec.ctypes.data, feat.data_ptr(), fo.ctypes.data, frames.ctypes.data, lengths.ctypes.data, status.ctypes.data)
+
+    decode_tracks(pkg.TRACKS_S16, s16.data_ptr(), out_offsets.ctypes.data, out_lengths.ctypes.data, lengths.ctypes.data, status.ctypes.data)
+    spans = np.zeros(n, dtype=pkg.MEL_SPAN_DTYPE)
+    spans["in_offset"], spans["in_samples"], spans["out_offset"], spans["plane"], spans["scale"] = offs, out_lengths, feat_offs, planes, 2.0 ** -15
+
+    def m():
+        stft_alone(spans, s16.data_ptr(), rec, feat.data_ptr())
+
+    times = {"a": [], "b": [], "c": [], "m": []}
+    for fn in (a, b, c, m):
+        fn()
+    for _ in range(reps):
+        for name, fn in (("a", a), ("b", b), ("c", c), ("m", m)):
+            t0 = time.perf_counter()
+            fn()
+            times[name].append((time.perf_counter() - t0) * 1e3)
+    assert (status[:, 0] == 0).all() and (lengths == planned).all() and (fo == feat_offs).all() and (frames == pkg.stft_frames(rec, len_r)).all()
+    # one track of (c) against (b) away from the track's ends, where (b) pads the batch with zeros in place of reflecting
+    c()
+    want = b()
+    edge = n_fft // 2 // hop + 2
+    worst = None
+    fits = [j for j in range(n // 2, n) if frames[j] > 2 * edge + 2]
+    if fits:
+        i = fits[0]
+        F, o, p = int(frames[i]), int(feat_offs[i]), int(planes[i])
+        got = feat[o:o + width * F].view(F, width) if frames_major else feat[o:o + width * p].view(bins, p * (width // bins))
+        if power == 0:
+            got = torch.view_as_complex(got.reshape(F, bins, 2) if frames_major else got.reshape(bins, p, 2))
+        got = got[edge:F - edge] if frames_major else got[:, edge:F - edge]
+        ref = want[i, edge:F - edge] if frames_major else want[i, :, edge:F - edge]
+        if log:  # back to the linear value: a cell near the floor is all rounding in the log, in both
+            got, ref = (10.0 ** got, 10.0 ** ref) if log == 1 else (got.exp(), ref.exp())
+        top = ref.abs().amax(dim=1 if frames_major else 0, keepdim=True).clamp(min=1e-30)  # the frame's largest
+        worst = float(((got - ref).abs() / top).max())  # relative to the frame's largest cell
+        assert worst < 1e-4, worst
+    out = {"stft": [int(rec[k][0]) for k in ("sample_rate", "n_fft", "win_length", "hop", "power", "log", "layout")], "files": n,
+           "frames": int(frames.sum()), "reps": reps, "note": note, "tile": pkg.stft_tile(rec), "scratch_s16_bytes": int(total) * 2,
+           "out_bytes": int(total_feat) * 4, "padded_batch_floats_of_b": n * longest,
+           "worst_error_vs_torch": worst if fits else "not checked: no track long enough"}
+    for k, label in (("a", "a_f32_mono"), ("b", "b_f32_then_torch_stft"), ("c", "c_fused_stft"), ("m", "m_k_tracks_stft_call")):
+        v = np.array(times[k])
+        out[label] = {"mean_ms": round(float(v.mean()), 3), "median_ms": round(float(np.median(v)), 3),
+                      "min_max_ms": [round(float(v.min()), 3), round(float(v.max()), 3)]}
+    out["stft_share_of_c"] = round(float(np.mean(times["m"]) / np.mean(times["c"])), 3)
+    out["m_written_gb_per_s"] = round(float(frames.sum()) * width * 4 / (np.mean(times["m"]) * 1e-3) / 1e9, 2)
+    out["b_over_c"] = round(float(np.mean(times["b"]) / np.mean(times["c"])), 3)
     out["c_le_b"] = bool(np.mean(times["c"]) <= np.mean(times["b"]))
     return out
 
@@ -364,6 +462,15 @@ FBANK_SETS = {
     "mfcc": ("kaldi_mfcc", dict(sample_rate=16000, num_mel_bins=23, num_ceps=13), 1, 3),
     "mfcc8k": ("kaldi_mfcc", dict(sample_rate=8000, num_mel_bins=23, num_ceps=13), 1, 6),
     "wide": ("kaldi_fbank", dict(sample_rate=48000, num_mel_bins=128, window_type="blackman", high_freq=-400.0), 1, 1),
+}
+
+# the parameter sets of --stft, those of tests/test_tracks_stft.py: (stft_spec arguments, up, down)
+STFT_SETS = {
+    "tiny": (dict(sample_rate=8000, n_fft=64, hop=24, win_length=48, power=2, log="ln", floor=1e-10), 1, 6),
+    "enh": (dict(sample_rate=16000, n_fft=512, hop=128, win_length=400, power=None), 1, 3),
+    "vits": (dict(sample_rate=22050, n_fft=1024, hop=256, power=1), 147, 320),
+    "wide": (dict(sample_rate=44100, n_fft=2048, hop=960, power=2, log="log10", floor=1e-10), 147, 160),
+    "whisper_lin": (dict(sample_rate=16000, n_fft=400, hop=160, power=2, frames="whisper"), 1, 3),
 }
 
 # the parameter sets of --melspec: (mel_spec arguments, up, down)

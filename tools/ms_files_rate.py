@@ -22,6 +22,10 @@ tracks followed by torch.stft, the filterbank matmul and log10, and k_tracks_mel
 --melspec tts | kaldi | clap | music: the fused mel-spectrogram call (opusgpu_ms_files_decode_melspec through the default mono downmix)
 next to float32 mono tracks at the set's rate followed by torch.stft, the filterbank matmul, the floor and the log, and
 k_tracks_melspec's share of the call (tools/mel_rate.py: compare_spec).
+--stft tiny | enh | vits | wide | whisper_lin [--stft-layout bands | frames]: the fused linear / complex STFT call
+(opusgpu_ms_files_decode_stft through the default mono downmix; include/opusgpu.h TRACK STFT) next to float32 mono tracks at the set's
+rate followed by torch.stft, abs / abs ** 2 / nothing, the floor and the log, and k_tracks_stft's share of the call (tools/mel_rate.py:
+compare_stft).
 --fbank wenet | mfcc | mfcc8k | wide: the fused Kaldi fbank / MFCC call (opusgpu_ms_files_decode_fbank through the default mono downmix)
 next to float32 mono tracks at the set's rate followed by unfold, mean, pre-emphasis, window, rfft, matmul and log in torch, and
 k_tracks_fbank's share of the call (tools/mel_rate.py: compare_fbank); a set at 16 kHz is followed by --melspec kaldi's line.
@@ -33,7 +37,7 @@ interleaved; the added time per call and its share of the call.  P (at most 80: 
 need 400 ms for a block.
 --cuts C [--cut-seconds S] [--stride] [--packets-per-file P]: the files (one page, P <= 80 packets) decoded whole, then C random cuts
 of S seconds out of each as N x C tracks (include/opusgpu.h WHOLE FILES / CUTS; tools/cuts_rate.py, as tools/files_rate.py --cuts).
-usage (GPU box): python3 tools/ms_files_rate.py [--n N] [--reps R] [--loudness [T] [--packets-per-file P] | --format F | --rate R [--mix M] | --resample U/D [--mix M] | --mel [--n-mels N] | --melspec SET | --fbank SET] | python3 tools/ms_files_rate.py --stats DIR [--n N]"""
+usage (GPU box): python3 tools/ms_files_rate.py [--n N] [--reps R] [--loudness [T] [--packets-per-file P] | --format F | --rate R [--mix M] | --resample U/D [--mix M] | --mel [--n-mels N] | --melspec SET | --stft SET | --fbank SET] | python3 tools/ms_files_rate.py --stats DIR [--n N]"""
 import argparse
 import ctypes as C
 import glob
@@ -63,6 +67,9 @@ ap.add_argument("--mel", action="store_true", help="compare the fused log-mel ca
 ap.add_argument("--n-mels", type=int, choices=[80, 128], default=80)
 ap.add_argument("--melspec", choices=["tts", "kaldi", "clap", "music"], default=None,
                 help="compare the fused mel-spectrogram call with float mono tracks at the set's rate + torch.stft (tools/mel_rate.py)")
+ap.add_argument("--stft", choices=["tiny", "enh", "vits", "wide", "whisper_lin"], default=None,
+                help="compare the fused STFT call with float mono tracks at the set's rate + torch.stft (tools/mel_rate.py: compare_stft)")
+ap.add_argument("--stft-layout", choices=["bands", "frames"], default="bands", help="with --stft: the record's feature_layout")
 ap.add_argument("--fbank", choices=["wenet", "mfcc", "mfcc8k", "wide"], default=None,
                 help="compare the fused Kaldi fbank / MFCC call with float mono tracks at the set's rate + unfold / rfft in torch (tools/mel_rate.py)")
 ap.add_argument("--loudness", nargs="?", const="measure", default=None, metavar="TARGET",
@@ -88,13 +95,16 @@ if args.packets_per_file != 10 and (not (args.loudness or args.cuts is not None 
     ap.error("--packets-per-file goes with --loudness, --cuts or --wave-batch and is at most 80: the files have one page")
 if args.melspec and (args.rate or args.format or args.resample or args.mel):
     ap.error("--melspec goes without --rate, --resample, --format and --mel")
+if args.stft and (args.rate or args.format or args.resample or args.mel or args.melspec or args.fbank or args.loudness or args.mix or
+                  args.cuts is not None):
+    ap.error("--stft goes alone (with --stft-layout, --n, --reps)")
 if args.mix and not (args.rate or args.resample):
     ap.error("--mix goes with --rate or --resample")
 if args.mel and (args.rate or args.format or args.resample):
     ap.error("--mel goes without --rate, --resample and --format")
 if args.resample and (args.rate or args.format):
     ap.error("--resample goes without --rate and --format")
-if args.format or args.rate or args.mel or args.resample or args.melspec or args.fbank:
+if args.format or args.rate or args.mel or args.resample or args.melspec or args.stft or args.fbank:
     import torch  # before the library is loaded: one HIP runtime for both
 n = args.n
 
@@ -330,6 +340,33 @@ if args.melspec:
                                                                                     rec.ctypes.data, p, None, d, fo, fr, ln, st),
                                              "opusgpu_ms_files_decode_melspec"),
         lambda spans, d_in, r, d_out: mem.tracks_melspec_device(spans, d_in, r, d_out), b, srec, up, down, args.reps, f"{args.melspec}, in_order")))
+    mem.close()
+    ms.close()
+    raise SystemExit(0)
+
+if args.stft:
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import mel_rate
+    kw, up, down = mel_rate.STFT_SETS[args.stft]
+    srec = pkg.stft_spec(feature_layout=args.stft_layout, **kw)
+    rate = 48000 // down if up == 1 else 0
+    ms = pkg.MultistreamContext(0, n, *LAYOUT)
+    mem = pkg.Context(0)
+    rec = pkg.mix_matrix("mono", CH)
+
+    def tracks(fmt, d, oo, ol, ln, st):
+        if rate:
+            return ms._chk(ms.lib.opusgpu_ms_files_decode_mixed(ms.h, b.h, rate, rec.ctypes.data, fmt, None, d, oo, ol, ln, st),
+                           "opusgpu_ms_files_decode_mixed")
+        return ms._chk(ms.lib.opusgpu_ms_files_decode_ratio(ms.h, b.h, up, down, rec.ctypes.data, fmt, None, d, oo, ol, ln, st),
+                       "opusgpu_ms_files_decode_ratio")
+    print(json.dumps(mel_rate.compare_stft(
+        torch, pkg, tracks,
+        lambda p, d, fo, fr, ln, st: ms._chk(ms.lib.opusgpu_ms_files_decode_stft(ms.h, b.h, rate, 0 if rate else up, 0 if rate else down,
+                                                                                 rec.ctypes.data, p, None, d, fo, fr, ln, st),
+                                             "opusgpu_ms_files_decode_stft"),
+        lambda spans, d_in, r, d_out: mem.tracks_stft_device(spans, d_in, r, d_out), b, srec, up, down, args.reps,
+        f"{args.stft} {args.stft_layout}, in_order")))
     mem.close()
     ms.close()
     raise SystemExit(0)
