@@ -59,6 +59,7 @@ EXPORTS = [
     "opusgpu_set_feature_batch", "opusgpu_ms_set_feature_batch", "opusgpu_feat_batch_layout", "opusgpu_tracks_feature_batch_device",
     "opusgpu_set_wave_batch", "opusgpu_ms_set_wave_batch", "opusgpu_last_wave_stats", "opusgpu_ms_last_wave_stats",
     "opusgpu_wave_batch_layout", "opusgpu_tracks_wave_batch_device",
+    "opusgpu_set_stft_batch", "opusgpu_ms_set_stft_batch", "opusgpu_stft_batch_layout", "opusgpu_tracks_stft_batch_device",
 ]
 
 
@@ -184,6 +185,11 @@ FEAT_NORMS = {None: 0, "none": 0, "whisper": 1, "cmn": 2, "cmvn": 3, "affine": 4
 FEAT_NORM_NONE, FEAT_NORM_WHISPER, FEAT_NORM_CMN, FEAT_NORM_CMVN, FEAT_NORM_AFFINE = range(5)
 FEAT_PAD_VALUE, FEAT_PAD_NORMALIZED = 0, 1
 FEAT_SEG = 1024  # OPUSGPU_FEAT_SEG: frames per segment of the statistics
+STFT_BATCH_REQ_DTYPE = np.dtype(FEAT_BATCH_REQ_DTYPE.descr)  # opusgpu_stft_batch_req: the fields of opusgpu_feat_batch_req
+STFT_BATCH_SPAN_DTYPE = np.dtype(FEAT_SPAN_DTYPE.descr)      # opusgpu_stft_batch_span
+STFT_NORM_REFMAX = 5  # OPUSGPU_STFT_NORM_REFMAX
+STFT_NORMS = dict(FEAT_NORMS, refmax=STFT_NORM_REFMAX)
+STFT_BATCH_MAX_BINS = 1025
 WAVE_BATCH_REQ_DTYPE = np.dtype([("stride_samples", "<i8"), ("eps", "<f8"), ("target", "<f8"), ("enabled", "<i4"), ("norm", "<i4"),
                                  ("pad_value", "<f4"), ("mask", "<i4"), ("reserved", "<i4", (6,))])
 WAVE_SPAN_DTYPE = np.dtype([("in_offset", "<i8"), ("samples", "<i8"), ("scale", "<f4"), ("reserved", "<i4")])
@@ -373,6 +379,11 @@ def load_lib():
     lib.opusgpu_wave_batch_layout.argtypes = [C.c_int, C.c_int, C.c_int64, C.c_int, vp]
     lib.opusgpu_wave_batch_layout.restype = C.c_int64
     lib.opusgpu_tracks_wave_batch_device.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
+    for name in ("opusgpu_set_stft_batch", "opusgpu_ms_set_stft_batch"):
+        getattr(lib, name).argtypes = [vp, vp, vp, vp, C.c_int]
+    lib.opusgpu_stft_batch_layout.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int64, vp]
+    lib.opusgpu_stft_batch_layout.restype = C.c_int64
+    lib.opusgpu_tracks_stft_batch_device.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
     _lib = lib
     return lib
 
@@ -1503,12 +1514,104 @@ def _planned_feature_frames(batch, req):
     rate, up, down = req.args[:3]
     if rate:
         up, down = 1, TRACK_RATES[rate]
-    frames = fbank_frames if req.params.dtype == FBANK_PARAMS_DTYPE else spec_frames
+    frames = fbank_frames if req.params.dtype == FBANK_PARAMS_DTYPE else stft_frames if req.params.dtype == STFT_PARAMS_DTYPE else spec_frames
     return frames(req.params, -(-planned * up // down))
 
 
 def _feature_width(params):
     return fbank_width(params) if params.dtype == FBANK_PARAMS_DTYPE else int(params["n_mels"][0])
+
+
+def stft_norm(kind, range=8.0, add=4.0, mul=None, var_floor=1e-20, sub=None, mul_vec=None):
+    """A normalisation for decode_files' stft_normalize= with numbers of its own (include/opusgpu.h STFT BATCHES): feature_norm's
+    kinds -- None / "none", "whisper" (range, add, mul; mul None is 0.25), "cmn", "cmvn" (var_floor), "affine" (sub and mul_vec, one
+    finite number per bin, 1 - 1025 of them) -- and "refmax" (range, mul; mul None is 10: dB under the track's maximum for a log10 power
+    spectrogram, top_db = 10 * range).  -> a FeatureNorm.  Raises ValueError as feature_norm does."""
+    if isinstance(kind, FeatureNorm):
+        return kind
+    if not isinstance(kind, (str, type(None))) or kind not in STFT_NORMS:
+        raise ValueError("stft_normalize must be None, 'whisper', 'refmax', 'cmn', 'cmvn', ('affine', sub, mul) or a stft_norm() record, "
+                         f"not {kind!r}")
+    norm = STFT_NORMS[kind]
+    if mul is None:
+        mul = 10.0 if norm == STFT_NORM_REFMAX else 0.25
+    nums = [float(v) for v in (range, add, mul, var_floor)]
+    if not np.isfinite(nums).all() or nums[3] <= 0:
+        raise ValueError("range, add, mul and var_floor must be finite, and var_floor > 0")
+    if norm != FEAT_NORM_AFFINE:
+        if sub is not None or mul_vec is not None:
+            raise ValueError("sub and mul_vec go with 'affine' only")
+        return FeatureNorm(norm, *nums)
+    if sub is None or mul_vec is None:
+        raise ValueError("'affine' needs sub and mul_vec, one number per bin each")
+    s, m = (np.ascontiguousarray(np.asarray(v, dtype=np.float32).reshape(-1)) for v in (sub, mul_vec))
+    if s.shape != m.shape or not 1 <= s.size <= STFT_BATCH_MAX_BINS or not (np.isfinite(s).all() and np.isfinite(m).all()):
+        raise ValueError("the affine vectors must be finite and of one length, 1 - 1025")
+    return FeatureNorm(norm, *nums, s, m)
+
+
+class StftBatch(typing.NamedTuple):
+    """The STFT-batch request of one decode_files call: the opusgpu_stft_batch_req record (a STFT_BATCH_REQ_DTYPE array of one), the
+    AFFINE vectors (float32 arrays or None), the spectrogram's bins, c (1: real cells, 2: pairs) and the stride S."""
+    rec: object
+    sub: object
+    mul: object
+    bins: int
+    c: int
+    stride: int
+
+
+def stft_batch_layout(n, bins, c, stride_frames):
+    """opusgpu_stft_batch_layout: the dense tensor of n tracks of stride_frames frames of `bins` bins of c floats -> (feat_offsets
+    [int64], total floats)."""
+    offsets = np.zeros(max(int(n), 0), dtype=np.int64)
+    total = int(load_lib().opusgpu_stft_batch_layout(int(n), int(bins), int(c), int(stride_frames), offsets.ctypes.data))
+    if total < 0:
+        raise ValueError(f"there is no STFT batch of {n!r} tracks of {stride_frames!r} frames of {bins!r} bins of {c!r} floats "
+                         "(bins 1 - 1025, c 1 or 2, stride * bins * c <= 2^31 - 1)")
+    return offsets, total
+
+
+def stft_batch_request(planned_frames, bins, c, stft_stride=None, stft_normalize=None, stft_pad=None):
+    """What decode_files makes of stft_stride=, stft_normalize= and stft_pad= for spectrograms of `bins` bins of c floats (2: pairs)
+    whose tracks have planned_frames[t] frames at their PLANNED lengths: a StftBatch.  stft_stride None: the largest planned F (at
+    least 1).  stft_normalize: None, "whisper", "refmax", "cmn", "cmvn", ("affine", sub, mul) or a stft_norm() record; pairs take
+    None and affine only.  stft_pad: None -- -10 normalised under "whisper", else 0 verbatim --, a number (verbatim), or (number,
+    "value" | "normalized").  Raises ValueError for an unknown stft_normalize, a norm that pairs do not take, affine vectors of the
+    wrong length or not finite, a stride below a planned F and a pad that is not finite."""
+    import numbers
+    planned_frames = np.asarray(planned_frames, dtype=np.int64)
+    if c not in (1, 2):
+        raise ValueError(f"c must be 1 (real cells) or 2 (pairs), not {c!r}")
+    if isinstance(stft_normalize, tuple) and not isinstance(stft_normalize, FeatureNorm):
+        if len(stft_normalize) != 3 or stft_normalize[0] != "affine":
+            raise ValueError(f"a stft_normalize tuple must be ('affine', sub, mul), not {stft_normalize!r}")
+        stft_normalize = stft_norm("affine", sub=stft_normalize[1], mul_vec=stft_normalize[2])
+    fn = stft_norm(stft_normalize)
+    if c == 2 and fn.norm not in (FEAT_NORM_NONE, FEAT_NORM_AFFINE):
+        raise ValueError("complex spectrograms (pairs) take stft_normalize None and ('affine', sub, mul) only")
+    if fn.norm == FEAT_NORM_AFFINE and fn.sub_vec.size != bins:
+        raise ValueError(f"the affine vectors have {fn.sub_vec.size} entries, the spectrogram {bins} bins")
+    most = int(planned_frames.max()) if planned_frames.size else 0
+    if stft_stride is None:
+        stft_stride = max(most, 1)
+    if not isinstance(stft_stride, numbers.Integral) or isinstance(stft_stride, bool) or stft_stride < 1:
+        raise ValueError(f"stft_stride must be an integer >= 1, not {stft_stride!r}")
+    if stft_stride < most:
+        raise ValueError(f"stft_stride {stft_stride} is below the {most} frames of the longest planned track")
+    if stft_pad is None:
+        stft_pad = (-10.0, "normalized") if fn.norm == FEAT_NORM_WHISPER else (0.0, "value")
+    if not isinstance(stft_pad, tuple):
+        stft_pad = (stft_pad, "value")
+    if (len(stft_pad) != 2 or stft_pad[1] not in ("value", "normalized") or not isinstance(stft_pad[0], numbers.Real) or
+            isinstance(stft_pad[0], bool) or not np.isfinite(stft_pad[0])):
+        raise ValueError(f"stft_pad must be a finite number or (number, 'value' | 'normalized'), not {stft_pad!r}")
+    stft_batch_layout(0, bins, c, stft_stride)  # (stride * bins * c must fit)
+    rec = np.zeros(1, dtype=STFT_BATCH_REQ_DTYPE)
+    rec["enabled"], rec["stride_frames"], rec["norm"], rec["var_floor"] = 1, int(stft_stride), fn.norm, fn.var_floor
+    rec["pad_mode"], rec["pad_value"] = FEAT_PAD_NORMALIZED if stft_pad[1] == "normalized" else FEAT_PAD_VALUE, stft_pad[0]
+    rec["range"], rec["add"], rec["mul"] = fn.range, fn.add, fn.mul
+    return StftBatch(rec, fn.sub_vec, fn.mul_vec, int(bins), int(c), int(stft_stride))
 
 
 class WaveBatch(typing.NamedTuple):
@@ -1593,6 +1696,7 @@ class FilesRequest(typing.NamedTuple):
     cut_info: object = None  # the batch's CUT_INFO_DTYPE records (a batch of cuts) or None
     feature_batch: object = None  # the FeatureBatch of feature_stride= / normalize= or None; with one, offsets and total are the dense tensor's
     wave_batch: object = None  # the WaveBatch of wave_stride= / wave_normalize= / wave_mask= or None; with one, offsets and total are the dense tensor's
+    stft_batch: object = None  # the StftBatch of stft_stride= / stft_normalize= / stft_pad= or None; with one, offsets and total are the dense tensor's
 
 
 STRIDE_REFUSED = ("the batch has a stride, which only tracks at 48 kHz keep (format=, scale=, out=, and loudness= with \"s16\"): resampled, "
@@ -1665,7 +1769,7 @@ def _files_request(batch, multistream=False, device=0, format=None, scale=None, 
 def files_request(batch, multistream=False, device=0, format=None, scale=None, out=None, rate=None, mono=False, mix=None, features=None,
                   n_mels=80, feature_layout="bands", resample=None, loudness=None, peak_limit=1.0, channel_weights=None,
                   feature_stride=None, normalize=None, feature_pad=None, wave_stride=None, wave_normalize=None, wave_pad=None,
-                  wave_mask=False):
+                  wave_mask=False, stft_stride=None, stft_normalize=None, stft_pad=None):
     """The keywords of decode_files for a planned batch -> the FilesRequest that _run_files_request carries out (_files_request says
     how).  A batch of cuts (FileBatch(cuts=...)) is a batch like any other: the request carries its cut records, which only info
     reads.  A strided one is refused here, as ValueError, with everything but tracks at 48 kHz; its planes lie the stride apart.
@@ -1675,9 +1779,13 @@ def files_request(batch, multistream=False, device=0, format=None, scale=None, o
     wave_stride=, wave_normalize=, wave_pad= and wave_mask= (WAVE BATCHES; wave_batch_request says what they may be) need a float
     format and no features=, and turn the TRACKS of the request into one dense tensor: its `wave_batch` carries the record and the
     buffer's layout, total is n * S and offsets t * S.  Tracks at 48 kHz without a mix, whose call has no resampling kernel, go
-    through files_decode_mixed with the identity matrix, which writes the same elements."""
+    through files_decode_mixed with the identity matrix, which writes the same elements.
+    stft_stride=, stft_normalize= and stft_pad= (STFT BATCHES; stft_batch_request says what they may be) need a stft_spec() record as
+    features= and turn its result into one dense tensor: the request's `stft_batch` carries the record, and total, offsets, planes
+    (the stride for every track) and the out= size check follow opusgpu_stft_batch_layout."""
     stride, cut_info = int(getattr(batch, "stride", 0) or 0), getattr(batch, "cut_info", None)
     wave = wave_stride is not None or wave_normalize is not None or wave_pad is not None or wave_mask is not False
+    sdense = stft_stride is not None or stft_normalize is not None or stft_pad is not None
     if stride and (rate not in (None, 48000) or mono or mix is not None or features is not None or resample is not None or wave or
                    (loudness is not None and format not in (None, "s16"))):
         raise ValueError(STRIDE_REFUSED)
@@ -1687,11 +1795,13 @@ def files_request(batch, multistream=False, device=0, format=None, scale=None, o
     if dense and getattr(features, "dtype", None) == STFT_PARAMS_DTYPE:
         raise ValueError("feature_stride=, normalize= and feature_pad= do not go with a stft_spec() record: feature batches hold widths of "
                          "1 - 128, a linear spectrogram has n_fft / 2 + 1 bins")
+    if sdense and getattr(features, "dtype", None) != STFT_PARAMS_DTYPE:
+        raise ValueError("stft_stride=, stft_normalize= and stft_pad= need a stft_spec() record as features=")
     if wave and features is not None:
         raise ValueError("wave_stride=, wave_normalize=, wave_pad= and wave_mask= are for tracks: features have feature_stride= and normalize=")
     if wave and format in (None, "s16"):
         raise ValueError("wave_stride=, wave_normalize=, wave_pad= and wave_mask= need format='f32' or 'f32_planar': the dense tensor is float32")
-    req = _files_request(batch, multistream, device, format, scale, None if dense or wave else out, rate, mono, mix, features, n_mels,
+    req = _files_request(batch, multistream, device, format, scale, None if dense or wave or sdense else out, rate, mono, mix, features, n_mels,
                          feature_layout, resample, loudness, peak_limit, channel_weights)
     if wave:
         if req.entry == "files_decode_as":  # 16384 on the diagonal is exactly x = s
@@ -1711,6 +1821,13 @@ def files_request(batch, multistream=False, device=0, format=None, scale=None, o
         if out is not None:
             out = _out_flat(out, max(total, 1), "f32", device)
         req = req._replace(feature_batch=fb, offsets=offsets, total=total, out=out, planes=np.full(batch.n_files, fb.stride, dtype=np.int64))
+    if sdense:
+        bins, c = int(req.params["n_fft"][0]) // 2 + 1, 2 if int(req.params["power"][0]) == STFT_COMPLEX else 1
+        sb = stft_batch_request(_planned_feature_frames(batch, req), bins, c, stft_stride, stft_normalize, stft_pad)
+        offsets, total = stft_batch_layout(batch.n_files, bins, c, sb.stride)
+        if out is not None:
+            out = _out_flat(out, max(total, 1), "f32", device)
+        req = req._replace(stft_batch=sb, offsets=offsets, total=total, out=out, planes=np.full(batch.n_files, sb.stride, dtype=np.int64))
     if stride:
         req = req._replace(stride=stride, planes=np.full(batch.n_files, stride, dtype=np.int64))
     return req if cut_info is None else req._replace(cut_info=cut_info)
@@ -1742,7 +1859,7 @@ def _run_files_request(req, lib, prefix, handle, chk, batch, mem):
     loud = np.zeros(n, dtype=LOUDNESS_DTYPE)
     gains = np.ones(n, dtype=np.float64)
 
-    fb, wb = req.feature_batch, req.wave_batch
+    fb, wb, sb = req.feature_batch, req.wave_batch, req.stft_batch
     wave_stats = np.zeros(n, dtype=WAVE_STAT_DTYPE)
 
     def run(d_out):
@@ -1754,6 +1871,14 @@ def _run_files_request(req, lib, prefix, handle, chk, batch, mem):
                 assert got == n, (got, n)
             finally:
                 getattr(lib, prefix + "set_wave_batch")(handle, None)
+            return
+        if sb is not None:
+            vecs = [None if v is None else v.ctypes.data for v in (sb.sub, sb.mul)]
+            chk(getattr(lib, prefix + "set_stft_batch")(handle, sb.rec.ctypes.data, *vecs, sb.bins), prefix + "set_stft_batch")
+            try:
+                run_loud(d_out)
+            finally:
+                getattr(lib, prefix + "set_stft_batch")(handle, None, None, None, 0)
             return
         if fb is None:
             return run_loud(d_out)
@@ -1820,6 +1945,9 @@ def _run_files_request(req, lib, prefix, handle, chk, batch, mem):
                 return flat.view(np.complex64).reshape(*shape)
             import torch
             return torch.view_as_complex(flat.reshape(*shape, 2))
+        if sb is not None:  # STFT BATCHES: one dense tensor, every track sb.stride frames, padded behind its info["frames"]
+            shape = (n, sb.stride, bins) if int(req.params["layout"][0]) == MEL_FRAMES_MAJOR else (n, bins, sb.stride)
+            return cells(packed[:n * sb.stride * bins * c], *shape), info
         if int(req.params["layout"][0]) == MEL_FRAMES_MAJOR:
             return [cells(packed[o:o + F * bins * c], F, bins) for o, F in zip(offsets, counts)], info
         return [cells(packed[o:o + bins * p * c], bins, p)[:, :F] for o, p, F in zip(offsets, req.planes, counts)], info
@@ -2071,6 +2199,16 @@ class Context:
                                                                request.rec.ctypes.data, *vecs, d_grid, d_out, stream),
                   "opusgpu_tracks_feature_batch_device")
 
+    def tracks_stft_batch_device(self, spans, feature_layout, request, d_grid, d_out, stream=None):
+        """k_stft_stats, k_stft_fold and k_stft_batch alone (include/opusgpu.h STFT BATCHES): spans a HOST array of STFT_BATCH_SPAN_DTYPE
+        over the packed float32 grid d_grid in feature_layout ("bands" or "frames"), request a StftBatch (stft_batch_request: its bins
+        and c are the grid's), d_out the dense tensor of len(spans) * stride * bins * c floats.  Waits for the kernels."""
+        spans = np.ascontiguousarray(spans, dtype=STFT_BATCH_SPAN_DTYPE)
+        vecs = [None if v is None else v.ctypes.data for v in (request.sub, request.mul)]
+        self._chk(self.lib.opusgpu_tracks_stft_batch_device(self.h, spans.size, spans.ctypes.data, request.bins, request.c,
+                                                            MEL_LAYOUTS[feature_layout], request.rec.ctypes.data, *vecs, d_grid, d_out, stream),
+                  "opusgpu_tracks_stft_batch_device")
+
     def tracks_wave_batch_device(self, spans, channels, format, request, d_s16, d_out, stream=None):
         """k_wave_stats, k_wave_fold and k_wave_batch alone (include/opusgpu.h WAVE BATCHES): spans a HOST array of WAVE_SPAN_DTYPE over
         the interleaved int16 tracks d_s16 of `channels` channels, format "f32" or "f32_planar", request a WaveBatch
@@ -2125,7 +2263,8 @@ class Context:
     def decode_files(self, files, rfc=False, flags=PAGES_GROUP_BY_MODE, threads=1, batch=None, format=None, scale=None, out=None,
                      rate=None, mono=False, mix=None, features=None, n_mels=80, feature_layout="bands", resample=None, loudness=None,
                      peak_limit=1.0, channel_weights=None, cuts=None, preroll=CUT_PREROLL, stride=None, feature_stride=None, normalize=None,
-                     feature_pad=None, wave_stride=None, wave_normalize=None, wave_pad=None, wave_mask=False):
+                     feature_pad=None, wave_stride=None, wave_normalize=None, wave_pad=None, wave_mask=False, stft_stride=None,
+                     stft_normalize=None, stft_pad=None):
         """Whole Ogg Opus files -> (list of int16 arrays [samples, channels], one trimmed track per file, info).  The context's
         streams 0 .. len(files) - 1 are (re)allocated when there are too few and get fresh state; its mode is set to `rfc`.
         info: FILE_INFO_DTYPE records with two more fields: `final_status` (the first failed frame's code, else the plan's status)
@@ -2202,7 +2341,16 @@ class Context:
         channels, eps 1e-7 under the root as Wav2Vec2FeatureExtractor has it), ("zmuv", eps) or ("peak", target) (the largest |sample|
         becomes target), from exact integer statistics of the int16 track: info["wave_stats"] has them (WAVE_STAT_DTYPE) with the sub
         and mul applied, (y * scale - sub) * mul.  wave_mask=True: info["mask"] is the uint8 [n, S] attention mask, 1 on real samples.
-        The batch's own stride= is still refused with these."""
+        The batch's own stride= is still refused with these.
+        stft_stride, stft_normalize, stft_pad (with a stft_spec() record as features= only; include/opusgpu.h STFT BATCHES): the
+        spectrograms as ONE float32 array [n, bins, S] ("bands") or [n, S, bins] ("frames"), complex64 of that shape for power=None (a
+        view of the pairs) -- with out= (a float32 tensor of n * S * bins floats, twice that for pairs) a view of it --, every track
+        padded to S = stft_stride frames (any integer that holds every planned track; None: the longest planned track's frames)
+        behind its info["frames"]; info["feat_offset"] is t * S * bins (* 2 for pairs).  stft_normalize: what normalize= takes, with
+        vectors of `bins` entries, and "refmax" ((max(x, track max - 8) - track max) * 10: dB under the track's own maximum for a log10
+        power spectrogram, top_db 80), or a stft_norm() record with numbers of its own; complex spectrograms take None and ("affine",
+        sub, mul) only.  stft_pad: as feature_pad.  With stft_normalize None and S a multiple of 64 the kernel writes the tensor
+        itself and no scratch grid is allocated.  The batch's own stride= is still refused."""
         if mix is not None and mono:  # (files_request's first refusal, ahead of the plan as it always was)
             raise ValueError("mix and mono=True exclude each other: the row {8192, 8192} is mono")
         own = batch is None
@@ -2212,7 +2360,7 @@ class Context:
         try:
             req = files_request(batch, False, self.device, format, scale, out, rate, mono, mix, features, n_mels, feature_layout, resample,
                                 loudness, peak_limit, channel_weights, feature_stride, normalize, feature_pad, wave_stride, wave_normalize,
-                                wave_pad, wave_mask)
+                                wave_pad, wave_mask, stft_stride, stft_normalize, stft_pad)
             if self.n_streams < batch.n_files or self.channels != batch.channels:
                 self.streams_alloc(max(batch.n_files, 1), batch.channels)
             self.set_mode(batch.rfc)
@@ -2386,7 +2534,7 @@ class MultistreamContext:
     def decode_files(self, files, rfc=False, threads=1, batch=None, format=None, scale=None, out=None, rate=None, mix=None, features=None,
                      n_mels=80, feature_layout="bands", resample=None, loudness=None, peak_limit=1.0, channel_weights=None, cuts=None,
                      preroll=CUT_PREROLL, stride=None, feature_stride=None, normalize=None, feature_pad=None, wave_stride=None,
-                     wave_normalize=None, wave_pad=None, wave_mask=False):
+                     wave_normalize=None, wave_pad=None, wave_mask=False, stft_stride=None, stft_normalize=None, stft_pad=None):
         """Whole Ogg Opus files of this object's layout -> (list of int16 arrays [samples, channels], one trimmed track per file,
         info), as Context.decode_files returns them: FILE_INFO_DTYPE records plus `final_status` and `bad_packet`, `track_samples`
         the FINAL length.  Decoders 0 .. len(files) - 1 get fresh state; the object's mode is set to the batch's.  batch: an
@@ -2397,7 +2545,8 @@ class MultistreamContext:
         resample: as for Context.decode_files, all channels or those of the mix.  features may be a mel_spec(), kaldi_fbank() or kaldi_mfcc() record as there.
         loudness, peak_limit, channel_weights: as for Context.decode_files; the default weights are those of the layout's channel
         count (1.41 for the rear pair, 0 for the LFE).  cuts, preroll, stride: as for Context.decode_files.
-        feature_stride, normalize, feature_pad, wave_stride, wave_normalize, wave_pad, wave_mask: as for Context.decode_files."""
+        feature_stride, normalize, feature_pad, wave_stride, wave_normalize, wave_pad, wave_mask, stft_stride, stft_normalize, stft_pad:
+        as for Context.decode_files."""
         own = batch is None
         if own:
             batch = MsFileBatch(files, self.layout, rfc=rfc, threads=threads, cuts=cuts, preroll=preroll, stride=stride)
@@ -2405,7 +2554,7 @@ class MultistreamContext:
         try:
             req = files_request(batch, True, self.device, format, scale, out, rate, False, mix, features, n_mels, feature_layout, resample,
                                 loudness, peak_limit, channel_weights, feature_stride, normalize, feature_pad, wave_stride, wave_normalize,
-                                wave_pad, wave_mask)
+                                wave_pad, wave_mask, stft_stride, stft_normalize, stft_pad)
             mem = Context(self.device)  # (device memory and copies are a plain context's calls)
             self.set_mode(batch.rfc)
             return _run_files_request(req, self.lib, "opusgpu_ms_", self.h, self._chk, batch, mem)

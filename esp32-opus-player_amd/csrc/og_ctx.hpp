@@ -102,6 +102,13 @@ struct WaveBatchState {
     std::vector<opusgpu_wave_stat> records;
 };
 
+// STFT BATCHES: the request that holds for the whole-file STFT calls that follow (opusgpu_set_stft_batch), with its own copies of
+// the AFFINE vectors.  One per context of either kind.
+struct StftBatchState {
+    opusgpu_stft_batch_req req{}; // enabled 0: off
+    std::vector<float> sub, mul;
+};
+
 struct opusgpu_ctx {
     int device = -1;
     hipStream_t stream = nullptr;
@@ -168,6 +175,7 @@ struct opusgpu_ctx {
     LoudnessState loud;
     FeatBatchState fbatch;
     WaveBatchState wave;
+    StftBatchState sbatch;
     char err[256] = {0};
 };
 

@@ -360,6 +360,17 @@ struct FeatFlow {
     std::function<int64_t(int n, const int64_t *planned_48k, int up, int down, int64_t *feat_offsets)> layout;
     std::function<int(int n, const opusgpu_mel_span *spans, const void *d_in, void *d_feat)> run; // the kernel, into the grid at d_feat
     int width = 0, frames_major = 0;                        // of a cell's row and the grid's layout (FEATURE BATCHES reads them)
+    const struct FeatDense *dense = nullptr;                // STFT BATCHES: the flow's own dense tensor (below), or none
+};
+// STFT BATCHES (og_stft_batch.hpp), as files_stft_run hands them to files_feature_run: the tensor has every track `stride` frames
+// (`width` floats each) apart.  `wrong` is the reason of a refusal that needs no track, or nullptr.  direct: the tensor is itself
+// a grid for the kernel (plane = stride, a multiple of 64), which writes d_out, and run(n, cells, nullptr, d_out) the pad cells
+// behind it; else the kernel writes a scratch grid of the flow's own layout and run(n, cells, d_grid, d_out) the tensor from there.
+struct FeatDense {
+    int64_t stride;
+    bool direct;
+    const char *wrong, *stride_short;
+    std::function<int(int n, const opusgpu_feat_span *cells, const void *d_grid, void *d_out)> run;
 };
 
 // FEATURE BATCHES (og_feat_batch.hpp, behind the feature headers): the stage that turns a packed grid into the dense tensor.
@@ -411,14 +422,25 @@ static int files_feature_run(const FilesOwner &own, int rate, int up, int down, 
             return OPUSGPU_BAD_ARG;
         }
     }
+    const FeatDense *dn = fb ? nullptr : flow.dense;
+    if (dn) {
+        const char *bad = dn->wrong;
+        for (size_t i = 0; i < n && !bad; i++)
+            if (flow.frames((planned[i] * up + down - 1) / down) > dn->stride) bad = dn->stride_short;
+        if (bad) {
+            if (own.refused) own.refused(bad);
+            return OPUSGPU_BAD_ARG;
+        }
+    }
+    const bool scratch_grid = fb || (dn && !dn->direct);
     RsDevBuf y; // the int16 mono tracks at the features' rate, for the length of this call
-    RsDevBuf grid; // FEATURE BATCHES: the packed features, for the length of this call
+    RsDevBuf grid; // FEATURE BATCHES, STFT BATCHES: the packed features, for the length of this call
     if (!b.segs.empty()) {
         hipError_t e = hipSetDevice(own.device);
         if (e == hipSuccess) e = y.alloc((size_t)total * 2 + 128);
         if (e != hipSuccess) return own.hip_failed(OPUSGPU_ALLOC_FAIL, flow.scratch_failed, e);
     }
-    if (fb && n) {
+    if (scratch_grid && n) {
         hipError_t e = hipSetDevice(own.device);
         if (e == hipSuccess) e = grid.alloc((size_t)feat_total * 4 + 128);
         if (e != hipSuccess) return own.hip_failed(OPUSGPU_ALLOC_FAIL, flow.scratch_failed, e);
@@ -432,9 +454,16 @@ static int files_feature_run(const FilesOwner &own, int rate, int up, int down, 
     if (rc) return rc;
     std::vector<opusgpu_mel_span> spans(n);
     for (size_t i = 0; i < n; i++)
-        spans[i] = opusgpu_mel_span{offs[i], len[i], feat[i], flow.plane(planned[i], up, down),
+        spans[i] = opusgpu_mel_span{offs[i], len[i], dn && dn->direct ? (int64_t)i * dn->stride * flow.width : feat[i],
+                                    dn && dn->direct ? dn->stride : flow.plane(planned[i], up, down),
                                     loud_normalizes(own) ? loud_scale(own, scale, i) : scale ? scale[i] : 1.0f / 32768, 0};
-    if (int rc2 = flow.run((int)n, spans.data(), y.p, fb ? grid.p : d_out)) return rc2;
+    if (int rc2 = flow.run((int)n, spans.data(), y.p, scratch_grid ? grid.p : d_out)) return rc2;
+    if (dn) {
+        std::vector<opusgpu_feat_span> cells(n);
+        for (size_t i = 0; i < n; i++) cells[i] = opusgpu_feat_span{feat[i], spans[i].plane, flow.frames(len[i])};
+        if (int rc2 = dn->run((int)n, cells.data(), dn->direct ? nullptr : grid.p, d_out)) return rc2;
+        for (size_t i = 0; i < n; i++) feat[i] = (int64_t)i * dn->stride * flow.width;
+    }
     if (fb) {
         std::vector<opusgpu_feat_span> cells(n);
         for (size_t i = 0; i < n; i++) cells[i] = opusgpu_feat_span{feat[i], spans[i].plane, flow.frames(len[i])};

@@ -270,8 +270,19 @@ static int64_t stft_plane(const opusgpu_stft_params &p, int64_t planned_48k, int
     return rs_round64(stft_frames(p, (planned_48k * up + down - 1) / down));
 }
 
+// STFT BATCHES (og_stft_batch.hpp, behind this header): the stage that turns a packed grid into the dense tensor, and the pad cells
+// of the direct path.
+static const char *stft_batch_shape_wrong(const opusgpu_stft_batch_req &r, int affine_bins, int bins, int c);
+static int stft_batch_run(int device, hipStream_t s, int n_tracks, const opusgpu_stft_batch_span *spans, int bins, int c, int layout,
+                          const opusgpu_stft_batch_req *req, const float *sub, const float *mul_vec, const void *d_grid, void *d_out,
+                          const TrackFail &hip_failed, const std::function<void(const char *)> &why);
+static int stft_pad_run(int device, hipStream_t s, int n_tracks, const int64_t *frames, int bins, int c, int layout,
+                        const opusgpu_stft_batch_req &req, void *d_out, const TrackFail &hip_failed);
+
 // opusgpu_files_decode_stft and its multistream twin (og_ms_tracks.hpp): files_feature_run at the record's rate.  FEATURE BATCHES
-// hold widths of 1 - 128, which most of these are not: a request on the decoder is refused whole, before any device work.
+// hold widths of 1 - 128, which most of these are not: a request on the decoder is refused whole, before any device work.  STFT
+// BATCHES: with the owner's request on, the result is the dense tensor -- by the direct path (norm NONE and a stride of a multiple of
+// 64 frames: k_tracks_stft writes the tensor as its grid, k_stft_pad the cells behind every track's frames) or through a scratch grid.
 static int files_stft_run(const FilesOwner &own, int rate, int up, int down, int mono, const opusgpu_mix_matrix *mix,
                           const opusgpu_stft_params *params, const float *scale, void *d_out, int64_t *feat_offsets, int64_t *frames_out,
                           int64_t *track_lengths_out, int32_t *status_out) {
@@ -291,6 +302,27 @@ static int files_stft_run(const FilesOwner &own, int rate, int up, int down, int
     flow.run = [&](int n, const opusgpu_mel_span *spans, const void *d_in, void *d_feat) {
         return tracks_stft_run(own.device, own.stream, n, spans, d_in, params, d_feat, own.hip_failed);
     };
+    const StftBatchState *sb = own.sbatch && own.sbatch->req.enabled && flow.sample_rate ? own.sbatch : nullptr;
+    FeatDense dense;
+    if (sb) {
+        const int bins = params->n_fft / 2 + 1, c = params->power == OPUSGPU_STFT_COMPLEX ? 2 : 1, layout = params->layout;
+        dense.stride = sb->req.stride_frames;
+        dense.direct = sb->req.norm == OPUSGPU_FEAT_NORM_NONE && dense.stride % 64 == 0;
+        dense.wrong = stft_batch_shape_wrong(sb->req, (int)sb->sub.size(), bins, c);
+        dense.stride_short = "stft batch: stride_frames is below the frames of a track's planned length";
+        dense.run = [&own, sb, bins, c, layout](int n, const opusgpu_feat_span *cells, const void *d_grid, void *d_dense) {
+            if (!d_grid) {
+                std::vector<int64_t> frames((size_t)n);
+                for (int i = 0; i < n; i++) frames[(size_t)i] = cells[i].frames;
+                return stft_pad_run(own.device, own.stream, n, frames.data(), bins, c, layout, sb->req, d_dense, own.hip_failed);
+            }
+            std::vector<opusgpu_stft_batch_span> spans((size_t)n);
+            for (int i = 0; i < n; i++) spans[(size_t)i] = opusgpu_stft_batch_span{cells[i].grid_offset, cells[i].plane, cells[i].frames};
+            return stft_batch_run(own.device, own.stream, n, spans.data(), bins, c, layout, &sb->req, sb->sub.data(), sb->mul.data(), d_grid,
+                                  d_dense, own.hip_failed, own.refused);
+        };
+        flow.dense = &dense;
+    }
     return files_feature_run(own, rate, up, down, mono, mix, scale, d_out, feat_offsets, frames_out, track_lengths_out, status_out, flow);
 }
 

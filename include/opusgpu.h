@@ -1128,7 +1128,8 @@ int opusgpu_tracks_stft_device(opusgpu_ctx *ctx, int n_tracks, const opusgpu_mel
  * TRACK RATIOS; `mono` 1 or a *mix of one row; d_out opusgpu_stft_layout's total in floats, 128-byte aligned; frames_out is F of
  * the final length.  OPUSGPU_BAD_ARG before any device work, the buffer and the caller's arrays left as they were: a record that
  * breaks a rule; a sample_rate that is not the track's rate; whatever opusgpu_files_decode_melspec refuses of the other arguments;
- * a feature-batch request on the context (FEATURE BATCHES hold widths of 1 - 128). */
+ * a feature-batch request on the context (FEATURE BATCHES hold widths of 1 - 128).  With a request of STFT BATCHES (below) on the
+ * context, d_out is that section's dense tensor and feat_offsets reports its offsets. */
 int opusgpu_files_decode_stft(opusgpu_ctx *ctx, const opusgpu_file_batch *batch, int rate, int up, int down, int mono,
                               const opusgpu_mix_matrix *mix, const opusgpu_stft_params *p, const float *scale, void *d_out,
                               int64_t *feat_offsets, int64_t *frames_out, int64_t *track_lengths_out, int32_t *status_out);
@@ -1392,6 +1393,89 @@ int64_t opusgpu_wave_batch_layout(int n, int channels, int64_t stride_samples, i
 int opusgpu_tracks_wave_batch_device(opusgpu_ctx *ctx, int n_tracks, const opusgpu_wave_span *spans, int channels, int format,
                                      const opusgpu_wave_batch_req *req, const void *d_s16, void *d_out, opusgpu_wave_stat *stats_out,
                                      void *hip_stream);
+
+/* STFT BATCHES.  The spectrograms of a TRACK STFT call as ONE dense tensor, padded to a common length and normalised per track: the
+ * [B, 513, T] that VITS pads in its collate function, the complex [B, 257, T] of enhancement and separation models, the [B, 1025, T]
+ * of music models, a spectrogram image in dB under its own maximum -- without a loop over tracks in the caller's code.  FEATURE
+ * BATCHES, its record, its calls, its kernels and everything it refuses (widths above 128, an STFT call with a feature-batch
+ * request on the context) are unchanged; this is a section of its own with a record, calls, kernels and a request of its own.  The
+ * definition is this comment.
+ *   INPUT.  A packed TRACK STFT grid: bins in [1, 1025]; c = 1 for real cells, 2 for (Re, Im) pairs; feat_offset[t] and plane[t]
+ *   multiples of 64.  OPUSGPU_MEL_BANDS_MAJOR (bins-major): cell (k, f) at feat_offset[t] + (k * plane[t] + f) * c.
+ *   OPUSGPU_MEL_FRAMES_MAJOR: cell (f, k) at feat_offset[t] + (f * bins + k) * c.  F[t] is the frame count of the track's FINAL
+ *   length: cells f >= F[t] of the grid are never interpreted.  The real cells are finite; the caller of the stand-alone call
+ *   guarantees it.
+ *   OUTPUT.  One dense float32 tensor of n_tracks * S * bins * c floats, S = stride_frames, in the grid's own layout.  Bins-major:
+ *   [n, bins, S], or [n, bins, S, 2] for pairs.  Frames-major: [n, S, bins], or [n, S, bins, 2] for pairs.  Track t begins at
+ *   t * S * bins * c.  EVERY element is written exactly once, the pad cells f >= F[t] included; nothing outside the tensor is
+ *   touched.  S is any integer >= 1 that holds every track's planned frames, with S * bins * c <= 0x7fffffff; nothing is asked of
+ *   its alignment.
+ *   STATISTICS are per track, over its F[t] real cells only: they never depend on pad cells, on the grid's padding or on which
+ *   other tracks are in the call.
+ *   NORMALISATIONS (norm), x a real cell of bin k.  OPUSGPU_FEAT_NORM_NONE, _WHISPER, _CMN, _CMVN and _AFFINE (0 - 4) are defined
+ *   word for word as in FEATURE BATCHES, with `bins` in the place of W: sub and mul_vec have `bins` entries.  One more:
+ *     OPUSGPU_STFT_NORM_REFMAX  m = the max over ALL real cells of the track (every bin); lo = m - range, one float32 subtraction;
+ *       y = (fmaxf(x, lo) - m) * mul: two float32 operations, each rounded on its own, nothing fused.  With a log10 power
+ *       spectrogram, range 8 and mul 10 this is dB under the track's own maximum with top_db = 80, librosa.power_to_db(ref=np.max).
+ *       F = 0 has no maximum: every cell of such a track takes pad_value verbatim, whatever the pad mode.
+ *   PAIRS (c = 2) take OPUSGPU_FEAT_NORM_NONE and _AFFINE only; AFFINE applies (x - sub[k]) * mul[k] to both members of bin k.
+ *   Every other norm with pairs is refused before any device work, with the reason.
+ *   PAD CELLS (pad_mode) are those of FEATURE BATCHES: OPUSGPU_FEAT_PAD_VALUE, pad_value verbatim; OPUSGPU_FEAT_PAD_NORMALIZED, the
+ *   track's normalisation applied to pad_value as if it were a cell of that track and bin.  For pairs the pad value fills both
+ *   members.
+ *   CONTRACT.  The same bits from the same call on the same input; no float atomics.  NONE, WHISPER, REFMAX and AFFINE are
+ *   bit-for-bit functions of the grid.  CMN and CMVN keep the per-bin summation order that FEATURE BATCHES fixes: segments of
+ *   OPUSGPU_FEAT_SEG frames; bins-major a lane's cells (frames 4 l .. 4 l + 3 of every 256, l the lane) in ascending frame order,
+ *   then the butterfly over the 64 lanes; frames-major every fourth frame per wave, then the four waves in ascending order; the
+ *   segments folded in ascending order.  A bin's statistics therefore do not depend on `bins`: a grid of width <= 128 gives the same
+ *   bits through this stage as through opusgpu_tracks_feature_batch_device, and so do the first 128 bins of a wider one.  The bound
+ *   of FEATURE BATCHES holds unchanged, 2^-23 |y| + 2^-30 max_f |x[f][k]| / d, and a track whose real cells all hold one value gives
+ *   exactly 0.0f in every real cell under CMN and CMVN (tests/test_gpu_stft_batch.py). */
+#define OPUSGPU_STFT_NORM_REFMAX 5
+typedef struct opusgpu_stft_batch_req { /* 64 bytes (ABI): the fields of opusgpu_feat_batch_req */
+    int64_t stride_frames; /* S, >= 1 */
+    double var_floor;      /* CMVN: finite and > 0 */
+    int32_t enabled;       /* opusgpu_set_stft_batch: 0 is off; the stand-alone call does not read it */
+    int32_t norm;          /* OPUSGPU_FEAT_NORM_* 0 - 4 | OPUSGPU_STFT_NORM_REFMAX */
+    int32_t pad_mode;      /* OPUSGPU_FEAT_PAD_* */
+    float pad_value;
+    float range, add, mul; /* WHISPER: 8, 4, 0.25; REFMAX reads range and mul (dB: 8, 10) */
+    int32_t reserved[5];   /* 0 */
+} opusgpu_stft_batch_req;
+typedef struct opusgpu_stft_batch_span { /* 24 bytes, one per track (ABI) */
+    int64_t grid_offset; /* feat_offset[t], in floats; a multiple of 64 */
+    int64_t plane;       /* plane[t], in frames: a multiple of 64 and >= frames */
+    int64_t frames;      /* F[t], 0 <= F <= S and F < 2^29 */
+} opusgpu_stft_batch_span;
+/* The request that holds for the opusgpu_files_decode_stft / opusgpu_ms_files_decode_stft calls that follow, as
+ * opusgpu_set_feature_batch does for its calls; NULL or `enabled` 0 is off, the default, and every call is then byte for byte what
+ * it is above.  The other feature calls ignore the request.  sub and mul_vec: host arrays of `bins` floats for
+ * OPUSGPU_FEAT_NORM_AFFINE, copied; not read otherwise.  OPUSGPU_BAD_ARG, the request in force left as it was: what
+ * opusgpu_set_feature_batch refuses, with norms 0 - 5 and AFFINE vectors of 1 - 1025 entries.  With a request on, the two calls
+ * write d_out as this section's tensor: d_out is opusgpu_stft_batch_layout's total in floats, 128-byte aligned; feat_offsets[t]
+ * reports t * S * bins * c; frames_out, track_lengths_out and status_out are what they were; the caller's arrays are written last.
+ * DIRECT PATH: with OPUSGPU_FEAT_NORM_NONE and S a multiple of 64 the tensor is itself a valid grid for k_tracks_stft (feat_offset
+ * t * S * bins * c, plane S), which then writes the real cells straight into d_out, and k_stft_pad the pad cells behind them: no
+ * scratch grid and no second pass over the cells.  Every other request runs the kernel into a scratch grid of opusgpu_stft_layout's
+ * size, freed on every way out, and this stage from there.  Both paths give the same tensor bit for bit.  OPUSGPU_BAD_ARG before
+ * any device work, the buffer and the arrays left as they were, with the reason in opusgpu_last_error: S below the frames of a
+ * track's PLANNED length; S * bins * c above 0x7fffffff; AFFINE vectors that do not have `bins` entries; a norm that pairs do not
+ * take.  A loudness request composes untouched: its gain is in the kernel's scale. */
+int opusgpu_set_stft_batch(opusgpu_ctx *ctx, const opusgpu_stft_batch_req *req, const float *sub, const float *mul_vec, int bins);
+int opusgpu_ms_set_stft_batch(opusgpu_ms *ms, const opusgpu_stft_batch_req *req, const float *sub, const float *mul_vec, int bins);
+/* OUTPUT above for n tracks: writes feat_offsets[t] = t * S * bins * c (may be NULL) and returns the total n * S * bins * c in
+ * floats.  OPUSGPU_BAD_ARG: n < 0, bins outside 1 - 1025, c neither 1 nor 2, stride_frames < 1, S * bins * c above 0x7fffffff.
+ * Host only. */
+int64_t opusgpu_stft_batch_layout(int n, int bins, int c, int64_t stride_frames, int64_t *feat_offsets);
+/* The stage alone over a packed grid in device memory (k_stft_stats, k_stft_fold, k_stft_batch): opusgpu_tracks_feature_batch_device's
+ * contract, alignment and "frees everything on every way out" rules with this section's record and widths -- `spans` a HOST array of
+ * n_tracks records, tracks come out in span order; d_grid floats, 128-byte aligned, read in aligned 16-byte pieces inside a track's
+ * planes; d_out n_tracks * S * bins * c floats, 128-byte aligned, not overlapping the grid; sub, mul_vec `bins` floats each for
+ * AFFINE.  OPUSGPU_BAD_ARG before any device work, with the reason in opusgpu_last_error: what opusgpu_set_stft_batch and
+ * opusgpu_stft_batch_layout refuse, an unknown layout, a span that breaks a rule above, a norm that pairs do not take. */
+int opusgpu_tracks_stft_batch_device(opusgpu_ctx *ctx, int n_tracks, const opusgpu_stft_batch_span *spans, int bins, int c, int layout,
+                                     const opusgpu_stft_batch_req *req, const float *sub, const float *mul_vec, const void *d_grid,
+                                     void *d_out, void *hip_stream);
 
 /* ---- WHOLE FILES / MULTISTREAM: N surround Ogg Opus files in, N trimmed interleaved tracks in HBM out -----------------------------
  * The two sections above joined: files whose OpusHead carries channel mapping family 1 (1 - 8 channels, `streams` elementary

@@ -17,6 +17,10 @@ torch.stft, the filterbank matmul and log10, and k_tracks_mel's share of the cal
 --melspec tts | kaldi | clap | music: the fused mel-spectrogram call (opusgpu_files_decode_melspec, mono; include/opusgpu.h TRACK
 SPECTROGRAMS) at that set's rate next to float32 mono tracks at the rate followed by torch.stft, the filterbank matmul, the floor and
 the log, and k_tracks_melspec's share of the call (tools/mel_rate.py: compare_spec).
+--stft SET --stft-batch S[:NORM] [--stft-batch-only] [--pipe in_order | pipelined]: the dense STFT call (include/opusgpu.h STFT BATCHES)
+with the request as asked, without a norm on the general and on the direct path, next to the packed call and the packed call followed by
+padding and normalising in torch; the stage alone beside k_feat_batch, and the peak device memory of both paths (tools/mel_rate.py:
+compare_stft_batch).
 --stft tiny | enh | vits | wide | whisper_lin [--stft-layout bands | frames]: the fused linear / complex STFT call
 (opusgpu_files_decode_stft, mono; include/opusgpu.h TRACK STFT) at that set's rate next to float32 mono tracks at the rate followed by
 torch.stft, abs / abs ** 2 / nothing, the floor and the log, k_tracks_stft's share of the call and the bytes it writes per second
@@ -79,6 +83,12 @@ ap.add_argument("--melspec", choices=["tts", "kaldi", "clap", "music"], default=
 ap.add_argument("--stft", choices=["tiny", "enh", "vits", "wide", "whisper_lin"], default=None,
                 help="compare the fused STFT call with float mono tracks at the set's rate + torch.stft (tools/mel_rate.py: compare_stft)")
 ap.add_argument("--stft-layout", choices=["bands", "frames"], default="bands", help="with --stft: the record's feature_layout")
+ap.add_argument("--stft-batch", default=None, metavar="S[:NORM]",
+                help="with --stft: the dense call with an STFT-batch request (stride S, 0: the longest track; none, whisper, refmax, cmn or cmvn), "
+                     "on the general and the direct path, next to the packed call followed by padding and normalising in torch, and the stage "
+                     "alone beside k_feat_batch (tools/mel_rate.py: compare_stft_batch)")
+ap.add_argument("--stft-batch-only", action="store_true", help="with --stft-batch: skip compare_stft's legs")
+ap.add_argument("--pipe", choices=["both", "in_order", "pipelined"], default="both", help="with --stft: which step order to time")
 ap.add_argument("--fbank", choices=["wenet", "mfcc", "mfcc8k", "wide"], default=None,
                 help="compare the fused Kaldi fbank / MFCC call with float mono tracks at the set's rate + unfold / rfft in torch (tools/mel_rate.py)")
 ap.add_argument("--feature-batch", default=None, metavar="S[:NORM]",
@@ -109,6 +119,8 @@ if args.melspec and (args.rate or args.format or args.resample or args.mel):
 if args.stft and (args.rate or args.format or args.resample or args.mel or args.melspec or args.fbank or args.loudness or args.mix or args.mono or
                   args.cuts is not None):
     ap.error("--stft goes alone (with --stft-layout, --n, --packets-per-file, --reps)")
+if (args.stft_batch or args.stft_batch_only) and not args.stft:
+    ap.error("--stft-batch goes with --stft")
 if args.feature_batch and not (args.mel or args.fbank):
     ap.error("--feature-batch goes with --mel or --fbank")
 if args.wave_batch and (not args.rate or args.loudness or (args.rate == 48000 and not (args.mono or args.mix))):
@@ -354,14 +366,29 @@ if args.stft:
         if rate:
             return ctx._chk(ctx.lib.opusgpu_files_decode_resampled(ctx.h, b.h, rate, 1, fmt, None, d, oo, ol, ln, st), "opusgpu_files_decode_resampled")
         return ctx._chk(ctx.lib.opusgpu_files_decode_ratio(ctx.h, b.h, up, down, 1, None, fmt, None, d, oo, ol, ln, st), "opusgpu_files_decode_ratio")
+    def decode_stft(p, d, fo, fr, ln, st):
+        return ctx._chk(ctx.lib.opusgpu_files_decode_stft(ctx.h, b.h, rate, 0 if rate else up, 0 if rate else down, 1, None, p, None, d, fo, fr, ln, st),
+                        "opusgpu_files_decode_stft")
+
+    def set_stft_batch(sb):
+        """The STFT-batch request `sb` (a StftBatch; None: off) on the context."""
+        vecs = [None, None] if sb is None else [None if v is None else v.ctypes.data for v in (sb.sub, sb.mul)]
+        ctx._chk(ctx.lib.opusgpu_set_stft_batch(ctx.h, None if sb is None else sb.rec.ctypes.data, *vecs, 0 if sb is None else sb.bins),
+                 "opusgpu_set_stft_batch")
     for name, pipe in (("in_order", 0), ("pipelined", 1)):
+        if args.pipe not in ("both", name):
+            continue
         ctx.set_pipeline(pipe)
-        print(json.dumps(mel_rate.compare_stft(
-            torch, pkg, tracks,
-            lambda p, d, fo, fr, ln, st: ctx._chk(ctx.lib.opusgpu_files_decode_stft(ctx.h, b.h, rate, 0 if rate else up, 0 if rate else down, 1,
-                                                                                    None, p, None, d, fo, fr, ln, st), "opusgpu_files_decode_stft"),
-            lambda spans, d_in, r, d_out: ctx.tracks_stft_device(spans, d_in, r, d_out), b, rec, up, down, args.reps,
-            f"{args.stft} {args.stft_layout}, {name}, {PAGES * PER_PAGE} packets per file")), flush=True)
+        note = f"{args.stft} {args.stft_layout}, {name}, {PAGES * PER_PAGE} packets per file"
+        if not args.stft_batch_only:
+            print(json.dumps(mel_rate.compare_stft(
+                torch, pkg, tracks, decode_stft, lambda spans, d_in, r, d_out: ctx.tracks_stft_device(spans, d_in, r, d_out), b, rec, up, down,
+                args.reps, note)), flush=True)
+        if args.stft_batch:
+            S, norm = mel_rate.stft_batch_arg(args.stft_batch)
+            print(json.dumps(mel_rate.compare_stft_batch(
+                torch, pkg, decode_stft, set_stft_batch, ctx.tracks_stft_batch_device, ctx.tracks_feature_batch_device, b, rec, up, down, S, norm,
+                args.reps, note)), flush=True)
     ctx.close()
     raise SystemExit(0)
 

@@ -456,6 +456,177 @@ def compare_feature_batch(torch, pkg, decode_feat, set_request, batch, rec, layo
     return out
 
 
+def stft_batch_arg(text):
+    """--stft-batch S[:NORM] -> (S, NORM): NORM one of none, whisper, refmax, cmn, cmvn (default none); S 0 is the longest planned track."""
+    s, _, norm = text.partition(":")
+    norm = norm or "none"
+    if norm not in ("none", "whisper", "refmax", "cmn", "cmvn") or int(s) < 0:
+        raise ValueError(f"--stft-batch takes S[:none|whisper|refmax|cmn|cmvn] with S >= 0, not {text!r}")
+    return int(s), norm
+
+
+class _PeakMemory:
+    """The most device memory in use while the block runs, over what was in use before it: a thread polls the device's free bytes (the
+    library allocates with hipMalloc, which torch's own counters do not see; ctypes calls release the interpreter)."""
+
+    def __init__(self, torch):
+        import threading
+        self.torch, self.low, self.stop = torch, None, threading.Event()
+        self.thread = threading.Thread(target=self.poll)
+
+    def poll(self):
+        while not self.stop.is_set():
+            self.low = min(self.low, self.torch.cuda.mem_get_info()[0])
+            time.sleep(0.0005)
+
+    def __enter__(self):
+        self.before = self.low = self.torch.cuda.mem_get_info()[0]
+        self.thread.start()
+        return self
+
+    def __exit__(self, *exc):
+        self.stop.set()
+        self.thread.join()
+        self.bytes = self.before - self.low
+
+
+def compare_stft_batch(torch, pkg, decode_stft, set_request, stage_alone, feat_stage_alone, batch, rec, up, down, stride, norm, reps, note=""):
+    """--stft-batch S[:NORM] (include/opusgpu.h STFT BATCHES): decode_stft(params, d_out, feat_offsets, frames, lengths, status) runs the
+    whole-file STFT call of the batch; set_request(StftBatch or None) puts a request on the decoder or takes it off;
+    stage_alone(spans, layout, StftBatch, d_grid, d_out) is opusgpu_tracks_stft_batch_device and feat_stage_alone(spans, width, layout,
+    FeatureBatch, d_grid, d_out) opusgpu_tracks_feature_batch_device.  Legs, interleaved per repeat:
+    (p) the packed call as it was; (b) (p) followed by the torch form a user writes today -- the ragged cells gathered into a padded
+    [files, bins, S] or [files, S, bins] tensor (the gather index is made once, on the device, outside the timing), then the norm;
+    (c) the dense call with the request (S, NORM) as asked; (g) the dense call without a norm at a stride of S rounded up to 64, plus
+    one: the general path; (d) the same at the multiple of 64: the direct path; (s) the stage alone with (S, NORM) over (p)'s grid and
+    (f) k_feat_batch alone (norm NONE, width 128) over a grid of zeros with as many floats.  Then one more run of (g) and (d) each
+    with the device's free memory polled.  -> a dict for the JSON line."""
+    n = batch.n_files
+    planned = np.asarray(batch.info["track_samples"], dtype=np.int64)
+    feat_offs, planes, total = pkg.stft_layout(planned, up, down, rec)
+    bins, c = int(rec["n_fft"][0]) // 2 + 1, 2 if int(rec["power"][0]) == pkg.STFT_COMPLEX else 1
+    frames_major = int(rec["layout"][0]) == pkg.MEL_FRAMES_MAJOR
+    layout = "frames" if frames_major else "bands"
+    F = pkg.stft_frames(rec, -(-planned * up // down))
+    sb = pkg.stft_batch_request(F, bins, c, stride or None, None if norm == "none" else norm)
+    S = sb.stride
+    S64 = (S + 63) // 64 * 64
+    sb_direct, sb_general = pkg.stft_batch_request(F, bins, c, S64), pkg.stft_batch_request(F, bins, c, S64 + 1)
+    pad_value, normalized = float(sb.rec["pad_value"][0]), int(sb.rec["pad_mode"][0]) == pkg.FEAT_PAD_NORMALIZED
+    packed = torch.empty(max(total, 1), dtype=torch.float32, device="cuda:0")
+    dense = torch.empty(max(n * (S64 + 1) * bins * c, 1), dtype=torch.float32, device="cuda:0")
+    lengths, fo, frames = (np.zeros(n, dtype=np.int64) for _ in range(3))
+    status = np.zeros((n, 2), dtype=np.int32)
+    dev = dict(device="cuda:0")
+    f, k = torch.arange(S, **dev)[None, :, None], torch.arange(bins, **dev)[None, None, :]
+    Fd = torch.tensor(F, **dev)[:, None, None]
+    at = torch.tensor(feat_offs // c, **dev)[:, None, None] + (f * bins + k if frames_major else k * torch.tensor(planes, **dev)[:, None, None] + f)
+    mask = (f < Fd).expand(at.shape)
+    gather = torch.where(mask, at, torch.zeros((), dtype=torch.int64, **dev))
+    if not frames_major:
+        gather, mask = gather.transpose(1, 2).contiguous(), mask.transpose(1, 2).contiguous()
+    else:
+        mask = mask.contiguous()
+    del at
+    count = torch.clamp(Fd.to(torch.float32), min=1.0)
+    fdim = 1 if frames_major else 2
+    cells_of = (lambda t: torch.view_as_complex(t.view(-1, 2))) if c == 2 else (lambda t: t)
+    pad = torch.full((), pad_value, **dev).to(torch.complex64 if c == 2 else torch.float32) * (1 + 1j if c == 2 else 1)
+    zero, ninf = torch.zeros((), **dev), torch.full((), -float("inf"), **dev)
+
+    def p():
+        decode_stft(rec.ctypes.data, packed.data_ptr(), fo.ctypes.data, frames.ctypes.data, lengths.ctypes.data, status.ctypes.data)
+
+    def b():
+        p()
+        x = torch.where(mask, cells_of(packed)[gather], pad)
+        if norm in ("whisper", "refmax"):
+            m = torch.where(mask, x, ninf).amax(dim=(1, 2), keepdim=True)
+            y = (torch.maximum(x, m - 8.0) + 4.0) / 4.0 if norm == "whisper" else (torch.maximum(x, m - 8.0) - m) * 10.0
+            x = y if normalized else torch.where(mask, y, pad)
+        elif norm in ("cmn", "cmvn"):
+            mean = torch.where(mask, x, zero).sum(dim=fdim, keepdim=True) / count
+            d = x - mean
+            if norm == "cmvn":
+                var = torch.where(mask, d * d, zero).sum(dim=fdim, keepdim=True) / count
+                d = d / torch.sqrt(torch.clamp(var, min=float(sb.rec["var_floor"][0])))
+            x = torch.where(mask, d, pad)
+        torch.cuda.synchronize()
+        return x
+
+    def dense_call(request):
+        def run():
+            set_request(request)
+            try:
+                decode_stft(rec.ctypes.data, dense.data_ptr(), fo.ctypes.data, frames.ctypes.data, lengths.ctypes.data, status.ctypes.data)
+            finally:
+                set_request(None)
+        return run
+    c_leg, g_leg, d_leg = dense_call(sb), dense_call(sb_general), dense_call(sb_direct)
+
+    p()
+    spans = np.zeros(n, dtype=pkg.STFT_BATCH_SPAN_DTYPE)
+    spans["grid_offset"], spans["plane"], spans["frames"] = feat_offs, planes, frames
+
+    def s():
+        stage_alone(spans, layout, sb, packed.data_ptr(), dense.data_ptr())
+    # k_feat_batch beside it: norm NONE at width 128 over a grid of zeros with as many floats in the tensor
+    n_f = max(1, n * bins * c // 128)
+    fspans = np.zeros(n_f, dtype=pkg.FEAT_SPAN_DTYPE)
+    fplane = (S + 63) // 64 * 64
+    fspans["grid_offset"], fspans["plane"], fspans["frames"] = np.arange(n_f, dtype=np.int64) * 128 * fplane, fplane, int(np.round(F.mean()))
+    fgrid = torch.zeros(n_f * 128 * fplane + 64, dtype=torch.float32, **dev)
+    fdense = torch.empty(n_f * 128 * S + 64, dtype=torch.float32, **dev)
+    fb = pkg.feature_batch_request(fspans["frames"], 128, S)
+
+    def f_leg():
+        feat_stage_alone(fspans, 128, layout, fb, fgrid.data_ptr(), fdense.data_ptr())
+
+    legs = (("p", p), ("b", b), ("c", c_leg), ("g", g_leg), ("d", d_leg), ("s", s), ("f", f_leg))
+    times = {name: [] for name, _ in legs}
+    for _, fn in legs:
+        fn()
+    for _ in range(reps):
+        for name, fn in legs:
+            t0 = time.perf_counter()
+            fn()
+            times[name].append((time.perf_counter() - t0) * 1e3)
+    peaks = {}
+    for name, fn in (("g", g_leg), ("d", d_leg)):
+        torch.cuda.synchronize()
+        with _PeakMemory(torch) as peak:
+            fn()
+        peaks[name] = peak.bytes
+    # the results against each other: the two paths bit for bit over the real frames and the pad, (c) against torch
+    g_leg()
+    assert (status[:, 0] == 0).all() and (frames == F).all() and (fo == np.arange(n) * (S64 + 1) * bins * c).all()
+    gen = dense[:n * (S64 + 1) * bins * c].view((n, S64 + 1, bins * c) if frames_major else (n, bins, S64 + 1, c)).clone()
+    d_leg()
+    dire = dense[:n * S64 * bins * c].view((n, S64, bins * c) if frames_major else (n, bins, S64, c))
+    same = bool(torch.equal((gen[:, :S64] if frames_major else gen[:, :, :S64]).contiguous().view(torch.int32), dire.contiguous().view(torch.int32)))
+    assert same, "the direct and the general path differ"
+    c_leg()
+    want = b()
+    got = cells_of(dense[:n * S * bins * c]).view(want.shape)
+    worst = float((got - want).abs().max())
+    assert worst < 1e-3, worst
+    real = int(frames.sum()) * bins * c * 4
+    stage_bytes = real * (2 if norm in ("whisper", "refmax", "cmn", "cmvn") else 1) + n * S * bins * c * 4
+    feat_bytes = int(fspans["frames"].sum()) * 128 * 4 + n_f * S * 128 * 4
+    out = {"stft_batch": [S, norm], "bins": bins, "c": c, "layout": layout, "files": n, "frames": int(frames.sum()), "reps": reps, "note": note,
+           "packed_bytes": int(total) * 4, "dense_bytes": n * S * bins * c * 4, "direct_stride": S64, "paths_equal": same,
+           "worst_abs_vs_torch": worst, "peak_bytes_general": int(peaks["g"]), "peak_bytes_direct": int(peaks["d"]),
+           "stage_bytes": stage_bytes, "feat_stage_bytes": feat_bytes}
+    for key, label in (("p", "p_packed_call"), ("b", "b_packed_then_torch_pad_and_norm"), ("c", "c_dense_as_asked"), ("g", "g_dense_general_none"),
+                       ("d", "d_dense_direct_none"), ("s", "s_stage_call"), ("f", "f_feat_stage_call_none_w128")):
+        v = np.array(times[key])
+        out[label] = {"mean_ms": round(float(v.mean()), 3), "median_ms": round(float(np.median(v)), 3),
+                      "min_max_ms": [round(float(v.min()), 3), round(float(v.max()), 3)]}
+    out["s_gb_per_s"] = round(stage_bytes / np.mean(times["s"]) / 1e6, 1)
+    out["f_gb_per_s"] = round(feat_bytes / np.mean(times["f"]) / 1e6, 1)
+    return out
+
+
 # the parameter sets of --fbank: (maker, its arguments, up, down); those at 16 kHz are followed by --melspec kaldi at the same files
 FBANK_SETS = {
     "wenet": ("kaldi_fbank", dict(sample_rate=16000, num_mel_bins=80), 1, 3),

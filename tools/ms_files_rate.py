@@ -22,6 +22,8 @@ tracks followed by torch.stft, the filterbank matmul and log10, and k_tracks_mel
 --melspec tts | kaldi | clap | music: the fused mel-spectrogram call (opusgpu_ms_files_decode_melspec through the default mono downmix)
 next to float32 mono tracks at the set's rate followed by torch.stft, the filterbank matmul, the floor and the log, and
 k_tracks_melspec's share of the call (tools/mel_rate.py: compare_spec).
+--stft SET --stft-batch S[:NORM]: the dense STFT call (include/opusgpu.h STFT BATCHES; opusgpu_ms_set_stft_batch) on both paths next to the
+packed call and the packed call followed by padding and normalising in torch (tools/mel_rate.py: compare_stft_batch).
 --stft tiny | enh | vits | wide | whisper_lin [--stft-layout bands | frames]: the fused linear / complex STFT call
 (opusgpu_ms_files_decode_stft through the default mono downmix; include/opusgpu.h TRACK STFT) next to float32 mono tracks at the set's
 rate followed by torch.stft, abs / abs ** 2 / nothing, the floor and the log, and k_tracks_stft's share of the call (tools/mel_rate.py:
@@ -70,6 +72,9 @@ ap.add_argument("--melspec", choices=["tts", "kaldi", "clap", "music"], default=
 ap.add_argument("--stft", choices=["tiny", "enh", "vits", "wide", "whisper_lin"], default=None,
                 help="compare the fused STFT call with float mono tracks at the set's rate + torch.stft (tools/mel_rate.py: compare_stft)")
 ap.add_argument("--stft-layout", choices=["bands", "frames"], default="bands", help="with --stft: the record's feature_layout")
+ap.add_argument("--stft-batch", default=None, metavar="S[:NORM]",
+                help="with --stft: the dense call with an STFT-batch request (stride S, 0: the longest track; none, whisper, refmax, cmn or cmvn) "
+                     "next to the packed call followed by padding and normalising in torch (tools/mel_rate.py: compare_stft_batch)")
 ap.add_argument("--fbank", choices=["wenet", "mfcc", "mfcc8k", "wide"], default=None,
                 help="compare the fused Kaldi fbank / MFCC call with float mono tracks at the set's rate + unfold / rfft in torch (tools/mel_rate.py)")
 ap.add_argument("--loudness", nargs="?", const="measure", default=None, metavar="TARGET",
@@ -98,6 +103,8 @@ if args.melspec and (args.rate or args.format or args.resample or args.mel):
 if args.stft and (args.rate or args.format or args.resample or args.mel or args.melspec or args.fbank or args.loudness or args.mix or
                   args.cuts is not None):
     ap.error("--stft goes alone (with --stft-layout, --n, --reps)")
+if args.stft_batch and not args.stft:
+    ap.error("--stft-batch goes with --stft")
 if args.mix and not (args.rate or args.resample):
     ap.error("--mix goes with --rate or --resample")
 if args.mel and (args.rate or args.format or args.resample):
@@ -360,13 +367,23 @@ if args.stft:
                            "opusgpu_ms_files_decode_mixed")
         return ms._chk(ms.lib.opusgpu_ms_files_decode_ratio(ms.h, b.h, up, down, rec.ctypes.data, fmt, None, d, oo, ol, ln, st),
                        "opusgpu_ms_files_decode_ratio")
+    def decode_stft(p, d, fo, fr, ln, st):
+        return ms._chk(ms.lib.opusgpu_ms_files_decode_stft(ms.h, b.h, rate, 0 if rate else up, 0 if rate else down, rec.ctypes.data, p, None, d,
+                                                           fo, fr, ln, st), "opusgpu_ms_files_decode_stft")
+
+    def set_stft_batch(sb):
+        """The STFT-batch request `sb` (a StftBatch; None: off) on the multistream decoder."""
+        vecs = [None, None] if sb is None else [None if v is None else v.ctypes.data for v in (sb.sub, sb.mul)]
+        ms._chk(ms.lib.opusgpu_ms_set_stft_batch(ms.h, None if sb is None else sb.rec.ctypes.data, *vecs, 0 if sb is None else sb.bins),
+                "opusgpu_ms_set_stft_batch")
     print(json.dumps(mel_rate.compare_stft(
-        torch, pkg, tracks,
-        lambda p, d, fo, fr, ln, st: ms._chk(ms.lib.opusgpu_ms_files_decode_stft(ms.h, b.h, rate, 0 if rate else up, 0 if rate else down,
-                                                                                 rec.ctypes.data, p, None, d, fo, fr, ln, st),
-                                             "opusgpu_ms_files_decode_stft"),
-        lambda spans, d_in, r, d_out: mem.tracks_stft_device(spans, d_in, r, d_out), b, srec, up, down, args.reps,
-        f"{args.stft} {args.stft_layout}, in_order")))
+        torch, pkg, tracks, decode_stft, lambda spans, d_in, r, d_out: mem.tracks_stft_device(spans, d_in, r, d_out), b, srec, up, down, args.reps,
+        f"{args.stft} {args.stft_layout}, in_order")), flush=True)
+    if args.stft_batch:
+        S, norm = mel_rate.stft_batch_arg(args.stft_batch)
+        print(json.dumps(mel_rate.compare_stft_batch(
+            torch, pkg, decode_stft, set_stft_batch, mem.tracks_stft_batch_device, mem.tracks_feature_batch_device, b, srec, up, down, S, norm,
+            args.reps, f"{args.stft} {args.stft_layout}, in_order")), flush=True)
     mem.close()
     ms.close()
     raise SystemExit(0)
