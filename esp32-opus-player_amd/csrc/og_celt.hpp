@@ -13,6 +13,7 @@
 #pragma once
 #include "og_celt_bands.hpp"
 #include "og_celt_packed.hpp"
+#include "og_comb_step.hpp"
 
 namespace og {
 
@@ -1206,29 +1207,17 @@ OG_DEVN void comb_filter(const CeltState *st, int c, int off, int T0, int T1, in
     c = OG_UNI(c); off = OG_UNI(off); T0 = OG_UNI(T0); T1 = OG_UNI(T1); N = OG_UNI(N); g0 = OG_UNI(g0); g1 = OG_UNI(g1);
     tap0 = OG_UNI(tap0); tap1 = OG_UNI(tap1); ring_pos_now = OG_UNI(ring_pos_now);
     if (g0 == 0 && g1 == 0) return;
-    // gains[tapset][0..2] Q15 (celt.cpp:854)
-    T0 = OG_MAX(T0, 15);
-    T1 = OG_MAX(T1, 15);
+    const CombCall q = comb_call(T0, T1, N, g0, g1, tap0, tap1); // the lags, tap gains, cross-fade and step lengths: og_comb_step.hpp
+    T0 = q.T0;
+    T1 = q.T1;
     OG_STAT(50, 1);                                   // comb filter calls that filter
     OG_STAT(51, T1 == 15 || T0 == 15);                // ... at the shortest lag
     OG_STAT(52, T1 >= 1020 || T0 >= 1020);            // ... at (almost) the longest: 1020 .. 1022
     OG_STAT(53, T1 == 1022 || T0 == 1022);
-    i32 ga0 = tap0 == 0 ? 10048 : tap0 == 1 ? 15200 : 26208, ga1 = tap0 == 0 ? 7112 : tap0 == 1 ? 8784 : 3280,
-        ga2 = tap0 == 0 ? 4248 : 0;
-    i32 gb0 = tap1 == 0 ? 10048 : tap1 == 1 ? 15200 : 26208, gb1 = tap1 == 0 ? 7112 : tap1 == 1 ? 8784 : 3280,
-        gb2 = tap1 == 0 ? 4248 : 0;
-    i32 g00 = tr16(mul16_p15(g0, ga0)), g01 = tr16(mul16_p15(g0, ga1)), g02 = tr16(mul16_p15(g0, ga2));
-    i32 g10 = tr16(mul16_p15(g1, gb0)), g11 = tr16(mul16_p15(g1, gb1)), g12 = tr16(mul16_p15(g1, gb2));
-    int overlap = (g0 == g1 && T0 == T1 && tap0 == tap1) ? 0 : OVERLAP;
-    // Every tap that COUNTS lies >= T - 2 samples back: that many samples can be filtered without looking at each
-    // other's results (no barrier in between, their history loads overlap).  A filter whose gain is zero contributes
-    // exactly zero (its tap gains g?0..g?2 are zero, so is every product), so its lag does not limit the chunk and its
-    // taps are not fetched -- a frame that switches the post-filter on cross-fades from "off" at the minimum lag 15, which
-    // used to cut all 840 samples of the call into chunks of 13.  Past the cross-fade only T1 counts.
-    const bool use0 = g0 != 0, use1 = g1 != 0;
-    const int chunk_fade = OG_MIN(use0 ? T0 : 1 << 20, use1 ? T1 : 1 << 20) - 2, chunk_rest = T1 - 2;
-    int end = g1 == 0 ? overlap : N; // with g1 == 0 only the cross-fade part changes the signal
+    OG_COMB_CENSUS(q, off, ring_pos_now);
 #ifdef OG_HOST_EMUL
+    const int overlap = q.overlap, end = q.end, chunk_fade = q.chunk_fade, chunk_rest = q.chunk_rest;
+    const i32 g00 = q.g.g00, g01 = q.g.g01, g02 = q.g.g02, g10 = q.g.g10, g11 = q.g.g11, g12 = q.g.g12;
     for (int base = 0, chunk; base < end; base += chunk) {
         chunk = base < overlap ? chunk_fade : chunk_rest;
         OG_SYNC();
@@ -1253,81 +1242,19 @@ OG_DEVN void comb_filter(const CeltState *st, int c, int off, int T0, int T1, in
         }
     }
 #else
-    // 64 consecutive samples per step: the five taps of lane l are elements e[l] .. e[l+4] of one 68-element window of the
-    // signal (e[j] = x[p0 - T - 2 + j]).  Lane l fetches e[l+4] only; the other four arrive by shifting that register one
-    // lane at a time (DPP wave_shr:1), with e[3] .. e[0] (fetched by lanes 0..3) fed in at lane 0.
-    // The ring head does not move during the filter: read it once (a reload per tap would put an HBM round trip in front of
-    // every history load).  LDS taps are plain LDS reads (index clamped), only the history taps branch to a global load --
-    // never one generic pointer for both.
-    const int ring_pos = ring_pos_now; // (the ring head does not move during the frame: the caller has it)
-    // (explicit address spaces: two generic pointers would be folded back into one flat load)
-    const __attribute__((address_space(1))) i32 *ring = (const __attribute__((address_space(1))) i32 *)st->ring[c];
-    const __attribute__((address_space(3))) i32 *lds = (const __attribute__((address_space(3))) i32 *)syn_buf();
-    auto tap_at = [&](int idx) -> i32 {
-        const i32 in_lds = lds[OG_MAX(idx, 0)];
-        i32 in_ring = 0;
-        if (idx < 0) in_ring = ring[(ring_pos + idx) & RING_MASK];
-        return idx < 0 ? in_ring : in_lds;
-    };
-    // (a step: up to 64 consecutive samples, never more than the lag allows -- ANY run of at most T - 2 samples is independent, so
-    // the steps need not respect the boundaries of chunks of T - 2: 64, 64, 64 ... instead of 64, 34, 64, 34 ... at T = 100)
-    for (int base = 0, lim; base < end; base += lim) {
-        lim = OG_MIN(OG_MIN(base < overlap ? chunk_fade : chunk_rest, 64), end - base);
-        OG_SYNC();
-        {
-            const int it = 0;
-            const int i = base + it + OG_LANE, p = off + i;
-            const bool live = it + OG_LANE < lim;
-            const i32 y0 = live ? syn_buf()[p] : 0;
-            auto window = [&](int T, i32 &t4, i32 &t3, i32 &t2, i32 &t1, i32 &t0) {
-                // t0 = x[p-T+2] (e[l+4]) ... t4 = x[p-T-2] (e[l]).
-                // Where the step's whole 68-element window lies is the same for every lane (off, base, it and T are the wave's): all of
-                // it in the synthesis buffer -- five LDS reads at constant offsets from one address -- or all of it in the history
-                // ring without crossing the ring's end -- five loads at constant offsets -- are the common cases and cost no vector
-                // ALU work beyond one address (the kernel is bound by vector-instruction issue: the shifting scheme below spends
-                // 8 instructions moving four taps across lanes and 10 more telling the two memories apart).  A dead lane's taps
-                // (past the step's last live sample) may be anything: nothing is stored for it and no lane reads another's.
-                const int first = off + base + it - T - 2; // index of e[0] of lane 0
-                if (first >= 0) {
-                    const __attribute__((address_space(3))) i32 *e = lds + (p - T - 2);
-                    t4 = e[0]; t3 = e[1]; t2 = e[2]; t1 = e[3]; t0 = e[4];
-                    return;
-                }
-                const int head = (ring_pos + first) & RING_MASK; // where e[0] of lane 0 lies in the ring
-                if (first + 67 < 0 && head + 67 <= RING_MASK) {
-                    const __attribute__((address_space(1))) i32 *e = ring + head + OG_LANE;
-                    t4 = e[0]; t3 = e[1]; t2 = e[2]; t1 = e[3]; t0 = e[4];
-                    return;
-                }
-                // (a window that straddles the two memories or the ring's end; indices past this step's last live sample are clamped)
-                const int q = OG_MIN(p, off + base + lim - 1) - T + 2;
-                t0 = tap_at(q);
-                const i32 w = OG_LANE < 4 ? tap_at(off + base + it - T - 2 + OG_LANE) : 0;
-                t1 = __builtin_amdgcn_update_dpp(__builtin_amdgcn_readlane(w, 3), t0, 0x138, 0xf, 0xf, false);
-                t2 = __builtin_amdgcn_update_dpp(__builtin_amdgcn_readlane(w, 2), t1, 0x138, 0xf, 0xf, false);
-                t3 = __builtin_amdgcn_update_dpp(__builtin_amdgcn_readlane(w, 1), t2, 0x138, 0xf, 0xf, false);
-                t4 = __builtin_amdgcn_update_dpp(__builtin_amdgcn_readlane(w, 0), t3, 0x138, 0xf, 0xf, false);
-            };
-            // (the cross-fade's window entry: requested before the taps, not between them and the multiplies)
-            const i32 wf = base + it < overlap ? (i32)rom_win120[OG_MIN(i, OVERLAP - 1)] : 0;
-            i32 a4 = 0, a3 = 0, a2 = 0, a1 = 0, a0 = 0;
-            if (use1) window(T1, a4, a3, a2, a1, a0);
-            i32 y;
-            if (base + it < overlap) { // (the cross-fade region is a whole number of steps only up to its last step)
-                i32 b4 = 0, b3 = 0, b2 = 0, b1 = 0, b0 = 0;
-                if (use0) window(T0, b4, b3, b2, b1, b0);
-                if (i < overlap) {
-                    const i32 f = tr16(mul16_q15(wf, wf));
-                    y = y0 + mul16x32_q15(mul16_q15(32767 - f, g00), b2) + mul16x32_q15(mul16_q15(32767 - f, g01), b1 + b3) +
-                        mul16x32_q15(mul16_q15(32767 - f, g02), b0 + b4) + mul16x32_q15(mul16_q15(f, g10), a2) +
-                        mul16x32_q15(mul16_q15(f, g11), a1 + a3) + mul16x32_q15(mul16_q15(f, g12), a0 + a4);
-                } else
-                    y = y0 + mul16x32_q15(g10, a2) + mul16x32_q15(g11, a1 + a3) + mul16x32_q15(g12, a0 + a4);
-            } else
-                y = y0 + mul16x32_q15(g10, a2) + mul16x32_q15(g11, a1 + a3) + mul16x32_q15(g12, a0 + a4);
-            if (live) syn_buf()[p] = clampsym(y, SIG_SAT);
-        }
-    }
+    // The steps are og_comb_step.hpp's: up to 64 consecutive samples each, one per lane, never more than the lag allows (ANY run of
+    // at most T - 2 samples is independent, so the steps need not respect the boundaries of chunks of T - 2: 64, 64, 64 ... instead
+    // of 64, 34, 64, 34 ... at T = 100).  The ring head does not move during the frame: the caller has it.  The stream's state
+    // arrives in vector registers like every argument: the ring's address is made scalar again here, once per call.
+    CombDev m;
+    m.buf_lane = (u32)(uintptr_t)((const OG_AS_LDS i32 *)syn_buf() + OG_LANE);
+    m.lane4 = 4u * (u32)OG_LANE;
+    const u64 ring_v = (u64)(uintptr_t)st->ring[c];
+    m.ring = (const OG_AS_GLB char *)((u64)(u32)OG_UNI((u32)ring_v) | (u64)(u32)OG_UNI((u32)(ring_v >> 32)) << 32);
+    m.win120 = (const OG_AS_GLB char *)rom_win120;
+    m.ring_pos = ring_pos_now;
+    m.ring_mask = RING_MASK;
+    comb_steps(m, off, q, ring_pos_now, RING_MASK);
 #endif
     OG_SYNC();
 }
