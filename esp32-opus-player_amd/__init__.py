@@ -59,6 +59,8 @@ EXPORTS = [
     "opusgpu_set_feature_batch", "opusgpu_ms_set_feature_batch", "opusgpu_feat_batch_layout", "opusgpu_tracks_feature_batch_device",
     "opusgpu_set_wave_batch", "opusgpu_ms_set_wave_batch", "opusgpu_last_wave_stats", "opusgpu_ms_last_wave_stats",
     "opusgpu_wave_batch_layout", "opusgpu_tracks_wave_batch_device",
+    "opusgpu_set_wave_trim", "opusgpu_ms_set_wave_trim", "opusgpu_last_wave_trim", "opusgpu_ms_last_wave_trim",
+    "opusgpu_last_wave_trim_flags", "opusgpu_ms_last_wave_trim_flags", "opusgpu_tracks_wave_trim_device",
     "opusgpu_set_stft_batch", "opusgpu_ms_set_stft_batch", "opusgpu_stft_batch_layout", "opusgpu_tracks_stft_batch_device",
 ]
 
@@ -197,6 +199,11 @@ WAVE_STAT_DTYPE = np.dtype([("count", "<i8"), ("sum", "<i8"), ("sumsq", "<u8"), 
 WAVE_NORMS = {None: 0, "none": 0, "zmuv": 1, "peak": 2}
 WAVE_NORM_NONE, WAVE_NORM_ZMUV, WAVE_NORM_PEAK = range(3)
 WAVE_EPS = 1e-7  # Wav2Vec2FeatureExtractor's
+WAVE_TRIM_REQ_DTYPE = np.dtype([("ratio", "<f8"), ("threshold", "<u8"), ("enabled", "<i4"), ("mode", "<i4"), ("frame_length", "<i4"),
+                                ("hop", "<i4"), ("margin", "<i4"), ("flags", "<i4"), ("reserved", "<i4", (6,))])
+WAVE_TRIM_STAT_DTYPE = np.dtype([("start", "<i8"), ("count", "<i8"), ("full", "<i8"), ("emax", "<u8"), ("thr", "<u8"), ("frames", "<i4"),
+                                 ("first", "<i4"), ("last", "<i4"), ("active", "<i4"), ("reserved", "<i4", (2,))])
+WAVE_TRIM_REL, WAVE_TRIM_ABS = 0, 1
 LOUDNESS_OFF, LOUDNESS_MEASURE, LOUDNESS_NORMALIZE = 0, 1, 2
 OPUSGPU_BAD_ARG, OPUSGPU_UNIMPLEMENTED, OPUSGPU_CELT_BAD_ARG = -1, -5, -18
 RFC_FRAME = 2880
@@ -379,6 +386,14 @@ def load_lib():
     lib.opusgpu_wave_batch_layout.argtypes = [C.c_int, C.c_int, C.c_int64, C.c_int, vp]
     lib.opusgpu_wave_batch_layout.restype = C.c_int64
     lib.opusgpu_tracks_wave_batch_device.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
+    for name in ("opusgpu_set_wave_trim", "opusgpu_ms_set_wave_trim"):
+        getattr(lib, name).argtypes = [vp, vp]
+    for name in ("opusgpu_last_wave_trim", "opusgpu_ms_last_wave_trim"):
+        getattr(lib, name).argtypes = [vp, C.c_int, vp]
+    for name in ("opusgpu_last_wave_trim_flags", "opusgpu_ms_last_wave_trim_flags"):
+        getattr(lib, name).argtypes = [vp, C.c_int64, vp]
+        getattr(lib, name).restype = C.c_int64
+    lib.opusgpu_tracks_wave_trim_device.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp]
     for name in ("opusgpu_set_stft_batch", "opusgpu_ms_set_stft_batch"):
         getattr(lib, name).argtypes = [vp, vp, vp, vp, C.c_int]
     lib.opusgpu_stft_batch_layout.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int64, vp]
@@ -1677,6 +1692,68 @@ def wave_batch_request(planned_out_samples, channels, wave_stride=None, wave_nor
     return WaveBatch(rec, int(channels), int(wave_stride), bool(wave_mask), int(planned.size), floats, mask_offset)
 
 
+def trim_spec(top_db=60.0, frame_length=2048, hop_length=512, ref="max", margin=0, flags=False):
+    """The opusgpu_wave_trim_req record (a WAVE_TRIM_REQ_DTYPE array of one) of decode_files(wave_trim=...) and
+    Context.tracks_wave_trim_device (include/opusgpu.h WAVE TRIM).  Frames of frame_length samples every hop_length, centred as
+    librosa.feature.rms centres them; a frame is active where its energy lies less than top_db dB below the reference.  ref="max":
+    the track's loudest frame, librosa.effects.trim's default -- REL mode with ratio = 10^(-top_db / 10).  ref a number: dBFS, with a
+    frame of full-scale samples (32768^2 * frame_length) at 0 -- ABS mode with threshold = floor(frame_length * 2^30 *
+    10^((ref - top_db) / 10)).  margin: samples kept on either side of the active span.  flags=True keeps the per-frame activity
+    (info["activity"]; activity_intervals turns it into intervals).  Raises ValueError with the rule broken: frame_length a multiple of
+    16 in 16 - 8192, hop_length a multiple of 8 in 8 - frame_length, margin a multiple of 8 and >= 0, top_db finite and >= 0 under
+    ref="max" (a ratio in (0, 1]), a threshold that fits 64 bits, flags a bool."""
+    import math
+    import numbers
+
+    def integer(v):
+        return isinstance(v, numbers.Integral) and not isinstance(v, bool)
+
+    def number(v):
+        return isinstance(v, numbers.Real) and not isinstance(v, bool) and np.isfinite(v)
+    if not integer(frame_length) or frame_length < 16 or frame_length > 8192 or frame_length % 16:
+        raise ValueError(f"frame_length must be a multiple of 16 in 16 - 8192, not {frame_length!r}")
+    if not integer(hop_length) or hop_length < 8 or hop_length > frame_length or hop_length % 8:
+        raise ValueError(f"hop_length must be a multiple of 8 in 8 - frame_length, not {hop_length!r}")
+    if not integer(margin) or margin < 0 or margin % 8 or margin > 0x7fffffff:
+        raise ValueError(f"margin must be a multiple of 8 and >= 0, not {margin!r}")
+    if not number(top_db):
+        raise ValueError(f"top_db must be a finite number, not {top_db!r}")
+    if not isinstance(flags, (bool, np.bool_)):
+        raise ValueError(f"flags must be True or False, not {flags!r}")
+    rec = np.zeros(1, dtype=WAVE_TRIM_REQ_DTYPE)
+    rec["enabled"], rec["frame_length"], rec["hop"], rec["margin"], rec["flags"] = 1, frame_length, hop_length, margin, 1 if flags else 0
+    if isinstance(ref, str):
+        if ref != "max":
+            raise ValueError(f"ref must be 'max' or a level in dBFS, not {ref!r}")
+        ratio = 10.0 ** (-float(top_db) / 10)
+        if not 0 < ratio <= 1:
+            raise ValueError(f"top_db must be >= 0 and leave a ratio above 0 under ref='max', not {top_db!r}")
+        rec["mode"], rec["ratio"] = WAVE_TRIM_REL, ratio
+    else:
+        if not number(ref):
+            raise ValueError(f"ref must be 'max' or a finite level in dBFS, not {ref!r}")
+        threshold = math.floor(frame_length * 2.0 ** 30 * 10.0 ** ((float(ref) - float(top_db)) / 10))
+        if threshold >= 1 << 64:
+            raise ValueError(f"ref {ref!r} and top_db {top_db!r} give a threshold that does not fit 64 bits")
+        rec["mode"], rec["ratio"], rec["threshold"] = WAVE_TRIM_ABS, 1.0, threshold
+    return rec
+
+
+def wave_trim_frames(samples, hop):
+    """WAVE TRIM's frame count of a track (or an array of tracks) of `samples` samples: 1 + samples // hop."""
+    return 1 + np.asarray(samples, dtype=np.int64) // int(hop)
+
+
+def activity_intervals(flags, hop, length):
+    """The activity flags of one track (info["activity"][t]: one uint8 per frame) -> its active [start, end) sample intervals, an
+    int64 array [k, 2], as librosa.effects.split forms them: a run of active frames f0 .. f1 is [f0 * hop, (f1 + 1) * hop), cut at
+    `length`, the track's untrimmed length (info["wave_trim"][t]["full"]).  On the host."""
+    on = np.concatenate(([0], (np.asarray(flags).reshape(-1) != 0).astype(np.int8), [0]))
+    edges = np.flatnonzero(np.diff(on))  # rises at even places, falls at odd ones
+    out = np.minimum(edges.reshape(-1, 2).astype(np.int64) * int(hop), int(length))
+    return out[out[:, 1] > out[:, 0]]
+
+
 class FilesRequest(typing.NamedTuple):
     """What one decode_files call asks of the library, made by files_request before any decoder is touched."""
     entry: str        # the C entry point without its opusgpu_ / opusgpu_ms_ prefix
@@ -1696,6 +1773,7 @@ class FilesRequest(typing.NamedTuple):
     cut_info: object = None  # the batch's CUT_INFO_DTYPE records (a batch of cuts) or None
     feature_batch: object = None  # the FeatureBatch of feature_stride= / normalize= or None; with one, offsets and total are the dense tensor's
     wave_batch: object = None  # the WaveBatch of wave_stride= / wave_normalize= / wave_mask= or None; with one, offsets and total are the dense tensor's
+    wave_trim: object = None  # the trim_spec() record of wave_trim= or None; only beside a wave_batch
     stft_batch: object = None  # the StftBatch of stft_stride= / stft_normalize= / stft_pad= or None; with one, offsets and total are the dense tensor's
 
 
@@ -1769,7 +1847,7 @@ def _files_request(batch, multistream=False, device=0, format=None, scale=None, 
 def files_request(batch, multistream=False, device=0, format=None, scale=None, out=None, rate=None, mono=False, mix=None, features=None,
                   n_mels=80, feature_layout="bands", resample=None, loudness=None, peak_limit=1.0, channel_weights=None,
                   feature_stride=None, normalize=None, feature_pad=None, wave_stride=None, wave_normalize=None, wave_pad=None,
-                  wave_mask=False, stft_stride=None, stft_normalize=None, stft_pad=None):
+                  wave_mask=False, stft_stride=None, stft_normalize=None, stft_pad=None, wave_trim=None):
     """The keywords of decode_files for a planned batch -> the FilesRequest that _run_files_request carries out (_files_request says
     how).  A batch of cuts (FileBatch(cuts=...)) is a batch like any other: the request carries its cut records, which only info
     reads.  A strided one is refused here, as ValueError, with everything but tracks at 48 kHz; its planes lie the stride apart.
@@ -1780,11 +1858,17 @@ def files_request(batch, multistream=False, device=0, format=None, scale=None, o
     format and no features=, and turn the TRACKS of the request into one dense tensor: its `wave_batch` carries the record and the
     buffer's layout, total is n * S and offsets t * S.  Tracks at 48 kHz without a mix, whose call has no resampling kernel, go
     through files_decode_mixed with the identity matrix, which writes the same elements.
+    wave_trim= (WAVE TRIM: a trim_spec() record) counts as one of the wave keywords -- alone it makes the dense tensor with the
+    defaults of the others -- and becomes the request's `wave_trim`: every row is then the track without its leading and trailing
+    silence.  Anything but None or such a record of one element with `enabled` set raises ValueError.
     stft_stride=, stft_normalize= and stft_pad= (STFT BATCHES; stft_batch_request says what they may be) need a stft_spec() record as
     features= and turn its result into one dense tensor: the request's `stft_batch` carries the record, and total, offsets, planes
     (the stride for every track) and the out= size check follow opusgpu_stft_batch_layout."""
     stride, cut_info = int(getattr(batch, "stride", 0) or 0), getattr(batch, "cut_info", None)
-    wave = wave_stride is not None or wave_normalize is not None or wave_pad is not None or wave_mask is not False
+    wave = wave_stride is not None or wave_normalize is not None or wave_pad is not None or wave_mask is not False or wave_trim is not None
+    if wave_trim is not None and not (isinstance(wave_trim, np.ndarray) and wave_trim.dtype == WAVE_TRIM_REQ_DTYPE and wave_trim.shape == (1,)
+                                      and int(wave_trim["enabled"][0]) == 1):
+        raise ValueError(f"wave_trim must be None or a trim_spec() record, not {wave_trim!r}")
     sdense = stft_stride is not None or stft_normalize is not None or stft_pad is not None
     if stride and (rate not in (None, 48000) or mono or mix is not None or features is not None or resample is not None or wave or
                    (loudness is not None and format not in (None, "s16"))):
@@ -1798,9 +1882,9 @@ def files_request(batch, multistream=False, device=0, format=None, scale=None, o
     if sdense and getattr(features, "dtype", None) != STFT_PARAMS_DTYPE:
         raise ValueError("stft_stride=, stft_normalize= and stft_pad= need a stft_spec() record as features=")
     if wave and features is not None:
-        raise ValueError("wave_stride=, wave_normalize=, wave_pad= and wave_mask= are for tracks: features have feature_stride= and normalize=")
+        raise ValueError("wave_stride=, wave_normalize=, wave_pad=, wave_mask= and wave_trim= are for tracks: features have feature_stride= and normalize=")
     if wave and format in (None, "s16"):
-        raise ValueError("wave_stride=, wave_normalize=, wave_pad= and wave_mask= need format='f32' or 'f32_planar': the dense tensor is float32")
+        raise ValueError("wave_stride=, wave_normalize=, wave_pad=, wave_mask= and wave_trim= need format='f32' or 'f32_planar': the dense tensor is float32")
     req = _files_request(batch, multistream, device, format, scale, None if dense or wave or sdense else out, rate, mono, mix, features, n_mels,
                          feature_layout, resample, loudness, peak_limit, channel_weights)
     if wave:
@@ -1813,7 +1897,7 @@ def files_request(batch, multistream=False, device=0, format=None, scale=None, o
         if out is not None:
             out = _out_flat(out, max(wb.floats, 1), format, device)
         req = req._replace(wave_batch=wb, offsets=np.arange(batch.n_files, dtype=np.int64) * wb.stride, total=batch.n_files * wb.stride, out=out,
-                           planes=np.full(batch.n_files, wb.stride, dtype=np.int64))
+                           planes=np.full(batch.n_files, wb.stride, dtype=np.int64), wave_trim=None if wave_trim is None else wave_trim.copy())
     if dense:
         width = _feature_width(req.params)
         fb = feature_batch_request(_planned_feature_frames(batch, req), width, feature_stride, normalize, feature_pad)
@@ -1846,7 +1930,10 @@ def _run_files_request(req, lib, prefix, handle, chk, batch, mem):
     behind every track's info["frames"]; info["feat_offset"] is t * S * n_mels.  With a wave-batch request (req.wave_batch), set and
     cleared the same way, the tracks are ONE float32 array or tensor [n, S, channels] ([n, S] for one channel; planar: [n, channels, S]),
     padded behind every track's info["out_samples"]; info["out_offset"] is t * S, info["wave_stats"] the WAVE_STAT_DTYPE records and, with
-    a mask, info["mask"] the uint8 [n, S] mask."""
+    a mask, info["mask"] the uint8 [n, S] mask.  With a trim request beside it (req.wave_trim), set and cleared the same way, every row is
+    the track without its leading and trailing silence: info["out_samples"] is the trimmed length, info["trim_start"] and
+    info["trim_samples"] the samples kept of the untrimmed track, info["wave_trim"] the WAVE_TRIM_STAT_DTYPE records and, where the record
+    asks for flags, info["activity"] a list of uint8 arrays, one flag per frame."""
     name = prefix + req.entry
     n, ch, fmt = batch.n_files, req.channels, req.fmt
     offsets, counts, lengths = (np.zeros(n, dtype=np.int64) for _ in range(3))
@@ -1861,15 +1948,28 @@ def _run_files_request(req, lib, prefix, handle, chk, batch, mem):
 
     fb, wb, sb = req.feature_batch, req.wave_batch, req.stft_batch
     wave_stats = np.zeros(n, dtype=WAVE_STAT_DTYPE)
+    tr = req.wave_trim
+    trim_stats, activity = np.zeros(n, dtype=WAVE_TRIM_STAT_DTYPE), []
 
     def run(d_out):
         if wb is not None:
             chk(getattr(lib, prefix + "set_wave_batch")(handle, wb.rec.ctypes.data), prefix + "set_wave_batch")
             try:
+                if tr is not None:
+                    chk(getattr(lib, prefix + "set_wave_trim")(handle, tr.ctypes.data), prefix + "set_wave_trim")
                 run_loud(d_out)
                 got = getattr(lib, prefix + "last_wave_stats")(handle, n, wave_stats.ctypes.data)
                 assert got == n, (got, n)
+                if tr is not None:
+                    got = getattr(lib, prefix + "last_wave_trim")(handle, n, trim_stats.ctypes.data)
+                    assert got == n, (got, n)
+                if tr is not None and int(tr["flags"][0]):
+                    packed_flags = np.zeros(int(trim_stats["frames"].sum()), dtype=np.uint8)
+                    got = getattr(lib, prefix + "last_wave_trim_flags")(handle, packed_flags.size, packed_flags.ctypes.data)
+                    assert got == packed_flags.size, (got, packed_flags.size)
+                    activity.extend(np.split(packed_flags, np.cumsum(trim_stats["frames"])[:-1]))
             finally:
+                getattr(lib, prefix + "set_wave_trim")(handle, None)
                 getattr(lib, prefix + "set_wave_batch")(handle, None)
             return
         if sb is not None:
@@ -1919,6 +2019,9 @@ def _run_files_request(req, lib, prefix, handle, chk, batch, mem):
     louder = [] if req.loudness is None else [("lufs", "<f4"), ("peak", "<f4"), ("loudness_blocks", "<i4"), ("loudness_gated", "<i4"), ("gain", "<f8")]
     cut_fields = [] if req.cut_info is None else [("cut_" + f, CUT_INFO_DTYPE[f].str) for f in CUT_INFO_DTYPE.names]
     wave_fields = [] if wb is None else [("wave_stats", WAVE_STAT_DTYPE)] + ([("mask", "u1", (wb.stride,))] if wb.mask else [])
+    if tr is not None:
+        wave_fields += [("trim_start", "<i8"), ("trim_samples", "<i8"), ("wave_trim", WAVE_TRIM_STAT_DTYPE)]
+        wave_fields += [("activity", "O")] if int(tr["flags"][0]) else []  # (ragged: one array per track)
     info = np.zeros(n, dtype=np.dtype(FILE_INFO_DTYPE.descr + [("final_status", "<i4"), ("bad_packet", "<i4")] + [(f, "<i8") for f in more] +
                                       louder + cut_fields + wave_fields))
     for f in CUT_INFO_DTYPE.names if cut_fields else ():
@@ -1962,6 +2065,10 @@ def _run_files_request(req, lib, prefix, handle, chk, batch, mem):
         return [packed[o:o + n_mels * p].reshape(n_mels, p)[:, :F] for o, p, F in zip(offsets, req.planes, counts)], info
     if wb is not None:  # WAVE BATCHES: one dense tensor, every track wb.stride samples, padded behind its info["out_samples"]
         info["wave_stats"] = wave_stats
+        if tr is not None:
+            info["trim_start"], info["trim_samples"], info["wave_trim"] = trim_stats["start"], trim_stats["count"], trim_stats
+            for t, flags in enumerate(activity):
+                info["activity"][t] = flags
         if wb.mask and req.out is not None:
             mask = np.zeros((n, wb.stride), dtype=np.uint8)
             mem.d2h(mask, C.c_void_p(req.out.data_ptr() + wb.mask_offset))
@@ -2209,6 +2316,22 @@ class Context:
                                                             MEL_LAYOUTS[feature_layout], request.rec.ctypes.data, *vecs, d_grid, d_out, stream),
                   "opusgpu_tracks_stft_batch_device")
 
+    def tracks_wave_trim_device(self, spans, channels, request, d_s16, stream=None):
+        """k_wave_trim_energy and k_wave_trim_fold alone (include/opusgpu.h WAVE TRIM): spans a HOST array of WAVE_SPAN_DTYPE over the
+        interleaved int16 tracks d_s16 of `channels` channels, request a trim_spec() record.  Waits for the kernels -> (the
+        WAVE_TRIM_STAT_DTYPE records, the activity flags as a list of uint8 arrays -- one per track, one flag per frame -- or None
+        where the request keeps none)."""
+        spans = np.ascontiguousarray(spans, dtype=WAVE_SPAN_DTYPE)
+        request = np.ascontiguousarray(request, dtype=WAVE_TRIM_REQ_DTYPE)
+        stats = np.zeros(spans.size, dtype=WAVE_TRIM_STAT_DTYPE)
+        frames = wave_trim_frames(spans["samples"], max(int(request["hop"][0]), 1))
+        flags = np.zeros(int(frames.sum()), dtype=np.uint8) if int(request["flags"][0]) == 1 else None
+        self._chk(self.lib.opusgpu_tracks_wave_trim_device(self.h, spans.size, spans.ctypes.data, int(channels), request.ctypes.data,
+                                                           d_s16, stats.ctypes.data, None if flags is None else flags.ctypes.data,
+                                                           stream),
+                  "opusgpu_tracks_wave_trim_device")
+        return stats, (None if flags is None else np.split(flags, np.cumsum(frames)[:-1]))
+
     def tracks_wave_batch_device(self, spans, channels, format, request, d_s16, d_out, stream=None):
         """k_wave_stats, k_wave_fold and k_wave_batch alone (include/opusgpu.h WAVE BATCHES): spans a HOST array of WAVE_SPAN_DTYPE over
         the interleaved int16 tracks d_s16 of `channels` channels, format "f32" or "f32_planar", request a WaveBatch
@@ -2264,7 +2387,7 @@ class Context:
                      rate=None, mono=False, mix=None, features=None, n_mels=80, feature_layout="bands", resample=None, loudness=None,
                      peak_limit=1.0, channel_weights=None, cuts=None, preroll=CUT_PREROLL, stride=None, feature_stride=None, normalize=None,
                      feature_pad=None, wave_stride=None, wave_normalize=None, wave_pad=None, wave_mask=False, stft_stride=None,
-                     stft_normalize=None, stft_pad=None):
+                     stft_normalize=None, stft_pad=None, wave_trim=None):
         """Whole Ogg Opus files -> (list of int16 arrays [samples, channels], one trimmed track per file, info).  The context's
         streams 0 .. len(files) - 1 are (re)allocated when there are too few and get fresh state; its mode is set to `rfc`.
         info: FILE_INFO_DTYPE records with two more fields: `final_status` (the first failed frame's code, else the plan's status)
@@ -2342,6 +2465,12 @@ class Context:
         becomes target), from exact integer statistics of the int16 track: info["wave_stats"] has them (WAVE_STAT_DTYPE) with the sub
         and mul applied, (y * scale - sub) * mul.  wave_mask=True: info["mask"] is the uint8 [n, S] attention mask, 1 on real samples.
         The batch's own stride= is still refused with these.
+        wave_trim (a trim_spec() record; include/opusgpu.h WAVE TRIM): one of the wave keywords.  Every row of the dense tensor is the
+        track without its leading and trailing silence -- librosa.effects.trim's indices from exact integer frame energies of the int16
+        track, or an absolute dBFS gate --, and the statistics, the padding and the mask follow the trimmed track.  info["out_samples"]
+        is the trimmed length, info["trim_start"] and info["trim_samples"] the samples kept, info["wave_trim"] the records
+        (WAVE_TRIM_STAT_DTYPE: `full` the untrimmed length, emax, thr, frames, first, last, active) and, with trim_spec(flags=True),
+        info["activity"] a list of uint8 arrays, one flag per frame (activity_intervals).
         stft_stride, stft_normalize, stft_pad (with a stft_spec() record as features= only; include/opusgpu.h STFT BATCHES): the
         spectrograms as ONE float32 array [n, bins, S] ("bands") or [n, S, bins] ("frames"), complex64 of that shape for power=None (a
         view of the pairs) -- with out= (a float32 tensor of n * S * bins floats, twice that for pairs) a view of it --, every track
@@ -2360,7 +2489,7 @@ class Context:
         try:
             req = files_request(batch, False, self.device, format, scale, out, rate, mono, mix, features, n_mels, feature_layout, resample,
                                 loudness, peak_limit, channel_weights, feature_stride, normalize, feature_pad, wave_stride, wave_normalize,
-                                wave_pad, wave_mask, stft_stride, stft_normalize, stft_pad)
+                                wave_pad, wave_mask, stft_stride, stft_normalize, stft_pad, wave_trim)
             if self.n_streams < batch.n_files or self.channels != batch.channels:
                 self.streams_alloc(max(batch.n_files, 1), batch.channels)
             self.set_mode(batch.rfc)
@@ -2534,7 +2663,7 @@ class MultistreamContext:
     def decode_files(self, files, rfc=False, threads=1, batch=None, format=None, scale=None, out=None, rate=None, mix=None, features=None,
                      n_mels=80, feature_layout="bands", resample=None, loudness=None, peak_limit=1.0, channel_weights=None, cuts=None,
                      preroll=CUT_PREROLL, stride=None, feature_stride=None, normalize=None, feature_pad=None, wave_stride=None,
-                     wave_normalize=None, wave_pad=None, wave_mask=False, stft_stride=None, stft_normalize=None, stft_pad=None):
+                     wave_normalize=None, wave_pad=None, wave_mask=False, stft_stride=None, stft_normalize=None, stft_pad=None, wave_trim=None):
         """Whole Ogg Opus files of this object's layout -> (list of int16 arrays [samples, channels], one trimmed track per file,
         info), as Context.decode_files returns them: FILE_INFO_DTYPE records plus `final_status` and `bad_packet`, `track_samples`
         the FINAL length.  Decoders 0 .. len(files) - 1 get fresh state; the object's mode is set to the batch's.  batch: an
@@ -2545,8 +2674,8 @@ class MultistreamContext:
         resample: as for Context.decode_files, all channels or those of the mix.  features may be a mel_spec(), kaldi_fbank() or kaldi_mfcc() record as there.
         loudness, peak_limit, channel_weights: as for Context.decode_files; the default weights are those of the layout's channel
         count (1.41 for the rear pair, 0 for the LFE).  cuts, preroll, stride: as for Context.decode_files.
-        feature_stride, normalize, feature_pad, wave_stride, wave_normalize, wave_pad, wave_mask, stft_stride, stft_normalize, stft_pad:
-        as for Context.decode_files."""
+        feature_stride, normalize, feature_pad, wave_stride, wave_normalize, wave_pad, wave_mask, stft_stride, stft_normalize, stft_pad,
+        wave_trim: as for Context.decode_files."""
         own = batch is None
         if own:
             batch = MsFileBatch(files, self.layout, rfc=rfc, threads=threads, cuts=cuts, preroll=preroll, stride=stride)
@@ -2554,7 +2683,7 @@ class MultistreamContext:
         try:
             req = files_request(batch, True, self.device, format, scale, out, rate, False, mix, features, n_mels, feature_layout, resample,
                                 loudness, peak_limit, channel_weights, feature_stride, normalize, feature_pad, wave_stride, wave_normalize,
-                                wave_pad, wave_mask, stft_stride, stft_normalize, stft_pad)
+                                wave_pad, wave_mask, stft_stride, stft_normalize, stft_pad, wave_trim)
             mem = Context(self.device)  # (device memory and copies are a plain context's calls)
             self.set_mode(batch.rfc)
             return _run_files_request(req, self.lib, "opusgpu_ms_", self.h, self._chk, batch, mem)

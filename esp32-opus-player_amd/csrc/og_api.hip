@@ -1236,5 +1236,6 @@ static int grow(opusgpu_ctx *ctx, void **p, size_t *cap, size_t need) {
 #include "og_tracks_fbank.hpp"
 #include "og_feat_batch.hpp"
 #include "og_wave_batch.hpp"
+#include "og_wave_trim.hpp"
 #include "og_stft_batch.hpp"
 #include "og_ms_tracks.hpp"

@@ -102,6 +102,14 @@ struct WaveBatchState {
     std::vector<opusgpu_wave_stat> records;
 };
 
+// WAVE TRIM: the request that holds for the whole-file calls that follow (opusgpu_set_wave_trim), and the records and activity flags
+// of the last of them that ran the stage (opusgpu_last_wave_trim, opusgpu_last_wave_trim_flags).  One per context of either kind.
+struct WaveTrimState {
+    opusgpu_wave_trim_req req{}; // enabled 0: off
+    std::vector<opusgpu_wave_trim_stat> records;
+    std::vector<uint8_t> flags;
+};
+
 // STFT BATCHES: the request that holds for the whole-file STFT calls that follow (opusgpu_set_stft_batch), with its own copies of
 // the AFFINE vectors.  One per context of either kind.
 struct StftBatchState {
@@ -175,6 +183,7 @@ struct opusgpu_ctx {
     LoudnessState loud;
     FeatBatchState fbatch;
     WaveBatchState wave;
+    WaveTrimState trim;
     StftBatchState sbatch;
     char err[256] = {0};
 };

@@ -179,6 +179,7 @@ struct opusgpu_ms {
     LoudnessState loud;
     FeatBatchState fbatch;
     WaveBatchState wave;
+    WaveTrimState trim;
     StftBatchState sbatch;
     char err[256] = {0};
 };

@@ -424,7 +424,7 @@ static FilesOwner files_owner(opusgpu_ms *ms, const opusgpu_ms_file_batch *batch
                           return ms_files_decode_run(ms, batch, OPUSGPU_TRACKS_S16, nullptr, d_s16, lengths, status);
                       },
                       track_fail(ms), &ms->loud, false, &ms->fbatch,
-                      [=](const char *why) { snprintf(ms->err, sizeof(ms->err), "%s", why); }, &ms->wave, &ms->sbatch};
+                      [=](const char *why) { snprintf(ms->err, sizeof(ms->err), "%s", why); }, &ms->wave, &ms->sbatch, &ms->trim};
 }
 
 extern "C" {

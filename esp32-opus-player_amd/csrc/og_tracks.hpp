@@ -319,6 +319,7 @@ struct FilesOwner {
     std::function<void(const char *why)> refused; // keeps the reason of a refusal where opusgpu_last_error finds it
     WaveBatchState *wave = nullptr; // WAVE BATCHES (og_wave_batch.hpp): the owner's request and records, read by files_resampled_to alone
     const StftBatchState *sbatch = nullptr; // STFT BATCHES (og_stft_batch.hpp): the owner's request, read by files_stft_run alone
+    WaveTrimState *trim = nullptr; // WAVE TRIM (og_wave_trim.hpp): the owner's request, records and flags, read by files_resampled_to alone
 };
 static FilesOwner files_owner(opusgpu_ctx *ctx, const opusgpu_file_batch *batch) {
     return FilesOwner{*batch, ctx->device, ctx->stream,
@@ -330,7 +331,7 @@ static FilesOwner files_owner(opusgpu_ctx *ctx, const opusgpu_file_batch *batch)
                           return files_decode_run(ctx, batch, OPUSGPU_TRACKS_S16, nullptr, d_s16, lengths, status);
                       },
                       track_fail(ctx), &ctx->loud, false, &ctx->fbatch,
-                      [=](const char *why) { snprintf(ctx->err, sizeof(ctx->err), "%s", why); }, &ctx->wave, &ctx->sbatch};
+                      [=](const char *why) { snprintf(ctx->err, sizeof(ctx->err), "%s", why); }, &ctx->wave, &ctx->sbatch, &ctx->trim};
 }
 
 // With a loudness request on, the int16 tracks of `run` are measured where the caller has them (og_tracks_loudness.hpp); without one

@@ -450,12 +450,18 @@ static const char *wave_batch_shape_wrong(const opusgpu_wave_batch_req &r, int C
 static int wave_batch_run(int device, hipStream_t s, int n_tracks, const opusgpu_wave_span *spans, int C, int format,
                           const opusgpu_wave_batch_req *req, const void *d_s16, void *d_out, opusgpu_wave_stat *recs,
                           const TrackFail &hip_failed, const std::function<void(const char *)> &why);
+// WAVE TRIM (og_wave_trim.hpp, behind it): the stage in front of the wave batch that cuts leading and trailing silence off its spans.
+static int wave_trim_spans(const FilesOwner &own, WaveTrimState &st, std::vector<opusgpu_wave_span> &tracks, int C, const void *d_s16);
+#define OG_TRIM_NEEDS_BATCH                                                                                                        \
+    "wave trim: a request is on without a wave-batch request -- the packed grids are planned on the host and cannot shrink, only " \
+    "the dense tensor's rows can"
 
 // What every whole-file call that ends in a resampling kernel does around its owner's decoder, its arguments checked by the caller:
 // own.decode runs the batch into the scratch S16 tracks, `run(n, spans, d_s16, format, d_dst)` the kernel that makes tracks of CO
 // channels at up / down of their rate from them, in `format` at d_dst.  That is the call's own format and d_out -- unless the owner
 // holds a WAVE BATCHES request and the tracks are the call's result (they are not where they feed a feature kernel): then the
-// kernel writes int16 into a scratch grid of its own layout and wave_batch_run writes d_out from there.
+// kernel writes int16 into a scratch grid of its own layout and wave_batch_run writes d_out from there -- from the spans that
+// wave_trim_spans has shortened first, where the owner holds a WAVE TRIM request as well.
 template <class Run>
 static int files_resampled_to(const FilesOwner &own, int up, int down, int CO, int format, const float *scale, void *d_out,
                               int64_t *out_offsets, int64_t *out_lengths, int64_t *track_lengths_out, int32_t *status_out, Run run) {
@@ -466,6 +472,11 @@ static int files_resampled_to(const FilesOwner &own, int up, int down, int CO, i
     if (loud_on(own) && own.loud->req.n_weights && own.loud->req.n_weights != b.channels) return OPUSGPU_BAD_ARG;
     const size_t n = (size_t)b.n_files;
     WaveBatchState *const wb = own.wave && own.wave->req.enabled && !own.scale_later ? own.wave : nullptr;
+    WaveTrimState *const trim = own.trim && own.trim->req.enabled && !own.scale_later ? own.trim : nullptr;
+    if (trim && !wb) {
+        if (own.refused) own.refused(OG_TRIM_NEEDS_BATCH);
+        return OPUSGPU_BAD_ARG;
+    }
     int64_t mid_total = 0; // the scratch grid of a wave batch, in samples per channel
     if (wb) {
         const char *bad = wave_batch_shape_wrong(wb->req, CO, format);
@@ -504,6 +515,8 @@ static int files_resampled_to(const FilesOwner &own, int up, int down, int CO, i
             tracks[i] = opusgpu_wave_span{offsets[i], (lengths[i] * up + down - 1) / down, spans[i].scale, 0};
             offsets[i] = (int64_t)i * wb->req.stride_samples;
         }
+        if (trim) // WAVE TRIM: the wave batch sees the tracks without their leading and trailing silence
+            if (int rc = wave_trim_spans(own, *trim, tracks, CO, mid.p)) return rc;
         if (int rc = wave_batch_run(own.device, own.stream, b.n_files, tracks.data(), CO, format, &wb->req, mid.p, d_out, recs.data(),
                                     own.hip_failed, own.refused))
             return rc;
@@ -511,7 +524,7 @@ static int files_resampled_to(const FilesOwner &own, int up, int down, int CO, i
     }
     for (size_t i = 0; i < n; i++) {
         if (out_offsets) out_offsets[i] = offsets[i];
-        if (out_lengths) out_lengths[i] = (lengths[i] * up + down - 1) / down;
+        if (out_lengths) out_lengths[i] = trim ? trim->records[i].count : (lengths[i] * up + down - 1) / down;
         if (track_lengths_out) track_lengths_out[i] = lengths[i];
     }
     if (status_out) std::copy(status.begin(), status.end(), status_out);

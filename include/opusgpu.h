@@ -1394,7 +1394,91 @@ int opusgpu_tracks_wave_batch_device(opusgpu_ctx *ctx, int n_tracks, const opusg
                                      const opusgpu_wave_batch_req *req, const void *d_s16, void *d_out, opusgpu_wave_stat *stats_out,
                                      void *hip_stream);
 
-/* STFT BATCHES.  The spectrograms of a TRACK STFT call as ONE dense tensor, padded to a common length and normalised per track: the
+/* WAVE TRIM.  The silence in front of and behind an utterance cut off before the tracks of a WAVE BATCHES call are collated:
+ * librosa.effects.trim (top_db = 60 in most TTS recipes) and the absolute dBFS gate of ASR data preparation, as a stage between the
+ * resampling kernel and the wave batch.  Trimming changes a row's length, the statistics ZMUV and PEAK are taken over and the mask,
+ * so it cannot follow the dense tensor; here the wave batch simply sees shorter tracks.  A frame's energy of an int16 track is an
+ * exact integer, so the trimmed batch stays a bit-for-bit function of the int16 track and a small record.  WAVE BATCHES, its records,
+ * calls and kernels are unchanged.  The definition is this comment.
+ *   INPUT.  For track t: y_c[m], the interleaved int16 result of the resampling kernel, C = out_channels in [1, 8]; L its output
+ *   length, derived from the FINAL length, exactly as WAVE BATCHES takes it.
+ *   PARAMETERS.  frame_length fl: a multiple of 16, 16 <= fl <= 8192.  hop: a multiple of 8, 8 <= hop <= fl.  margin: a multiple of
+ *   8, >= 0, the samples kept on either side.  mode: OPUSGPU_WAVE_TRIM_REL or _ABS.  ratio: a double in (0, 1], read in REL mode --
+ *   the caller passes 10^(-top_db / 10), no kernel calls pow; ABS only asks that it is finite.  threshold: a uint64, read in ABS
+ *   mode, the frame-energy threshold in int16^2 units summed over the frame.  flags: 0 or 1.
+ *   FRAMES.  F = 1 + L / hop (integer division).  Frame f covers the samples m in [f * hop - fl / 2, f * hop + fl / 2) that lie in
+ *   [0, L): librosa.feature.rms(center=True, pad_mode="constant")'s framing.  Nothing at or behind L is read, interpreted or allowed
+ *   to influence a bit -- the grid holds other tracks there.
+ *   ENERGY.  E[c][f] = sum of y_c[m]^2 over the frame, an exact integer of at most 2^43.  M[f] = max over c of E[c][f] (librosa's
+ *   aggregate=np.max).  Emax = max over f of M[f].
+ *   THRESHOLD.  ABS: thr = threshold.  REL: thr = (uint64)floor((double)Emax * ratio) -- (double)Emax is exact, the product is
+ *   rounded once, the floor is exact: numpy float64 reproduces thr bit for bit.
+ *   ACTIVITY.  Frame f is active iff M[f] > thr, as integers.
+ *   RESULT.  first and last are the first and the last active frame, active their count.  No active frame: start = 0, count = 0.
+ *   Otherwise start = max(0, first * hop - margin), end = min(L, (last + 1) * hop + margin), count = end - start.  With margin 0
+ *   these are librosa.effects.trim's indices.
+ *   ONE DIVERGENCE.  A digitally silent track (Emax = 0) in REL mode trims to nothing: no M[f] is above 0.  librosa keeps it whole,
+ *   because power_to_db clamps both sides of its comparison to amin.
+ *   SCALE.  The energies are of the int16 samples IN FRONT OF scale[t]: a loudness gain, which is folded into the scale, does not
+ *   move an ABS threshold and changes no trim index.
+ *   RECORD.  opusgpu_wave_trim_stat per track: start, count, full = L, Emax, thr, frames = F, first, last (both -1 when nothing is
+ *   active), active.
+ *   FLAGS.  With flags = 1, one uint8 per frame (1 = active), the tracks packed back to back in track order, F[t] bytes each: what
+ *   librosa.effects.split makes its intervals from. */
+#define OPUSGPU_WAVE_TRIM_REL 0
+#define OPUSGPU_WAVE_TRIM_ABS 1
+typedef struct opusgpu_wave_trim_req { /* 64 bytes (ABI) */
+    double ratio;         /* REL: in (0, 1]; ABS: finite */
+    uint64_t threshold;   /* ABS */
+    int32_t enabled;      /* opusgpu_set_wave_trim: 0 is off; the stand-alone call does not read it */
+    int32_t mode;         /* OPUSGPU_WAVE_TRIM_* */
+    int32_t frame_length; /* a multiple of 16 in [16, 8192] */
+    int32_t hop;          /* a multiple of 8 in [8, frame_length] */
+    int32_t margin;       /* a multiple of 8, >= 0 */
+    int32_t flags;        /* 1: the activity flags are kept */
+    int32_t reserved[6];  /* 0 */
+} opusgpu_wave_trim_req;
+typedef struct opusgpu_wave_trim_stat { /* 64 bytes, one per track (ABI) */
+    int64_t start, count; /* the samples kept: [start, start + count) */
+    int64_t full;         /* L, the untrimmed length */
+    uint64_t emax, thr;
+    int32_t frames;       /* F */
+    int32_t first, last;  /* -1: no frame is active */
+    int32_t active;
+    int32_t reserved[2];  /* 0 */
+} opusgpu_wave_trim_stat;
+/* The request that holds for the whole-file calls that follow, as opusgpu_set_wave_batch does for its own; NULL or `enabled` 0 is
+ * off, the default, and every call is then byte for byte what it is above.  OPUSGPU_BAD_ARG, the request in force left as it was
+ * and the reason in opusgpu_last_error: a frame_length that is no multiple of 16 in [16, 8192]; a hop that is no multiple of 8 in
+ * [8, frame_length]; a margin that is negative or no multiple of 8; an unknown mode; a ratio that is not finite, or outside (0, 1]
+ * in REL mode; flags neither 0 nor 1; a reserved word that is not 0; a request turned on while the context holds no wave-batch
+ * request -- the packed grids are planned on the host and cannot shrink, only the dense tensor's rows can.  With both requests on,
+ * the calls that WAVE BATCHES names run this stage over their int16 scratch grid and hand the wave batch the trimmed tracks:
+ * statistics, cells, padding and mask follow the trimmed track; out_lengths[t] reports the trimmed count, the row's real length;
+ * track_lengths_out and status_out are what they were, and S is still held against the PLANNED, untrimmed length.  A call that
+ * finds this request on and the wave-batch request off is refused before any device work, with the reason.  The calls that ignore
+ * a wave-batch request ignore this one. */
+int opusgpu_set_wave_trim(opusgpu_ctx *ctx, const opusgpu_wave_trim_req *req);
+int opusgpu_ms_set_wave_trim(opusgpu_ms *ms, const opusgpu_wave_trim_req *req);
+/* The records of the last whole-file call that ran the stage: copies min(n, have) of them and returns `have`. */
+int opusgpu_last_wave_trim(const opusgpu_ctx *ctx, int n, opusgpu_wave_trim_stat *records);
+int opusgpu_ms_last_wave_trim(const opusgpu_ms *ms, int n, opusgpu_wave_trim_stat *records);
+/* FLAGS of that call, where its request asked for them: copies min(n_bytes, have) bytes and returns `have`, the sum of the records'
+ * `frames` (0 without flags). */
+int64_t opusgpu_last_wave_trim_flags(const opusgpu_ctx *ctx, int64_t n_bytes, uint8_t *flags);
+int64_t opusgpu_ms_last_wave_trim_flags(const opusgpu_ms *ms, int64_t n_bytes, uint8_t *flags);
+/* The stage alone over int16 tracks in device memory (k_wave_trim_energy, k_wave_trim_fold): `spans` is a HOST array of n_tracks
+ * opusgpu_wave_span records (their scale is not read); d_s16 interleaved int16 tracks of `channels` channels, 16-byte aligned, read
+ * in aligned 16-byte pieces up to the one that holds a track's last sample; stats_out n_tracks records on the HOST; flags_out the
+ * HOST bytes of FLAGS, the sum over the tracks of 1 + samples / hop, or NULL -- it is written only where req->flags is 1.  Uploads
+ * the spans and its tile table, launches on the context's stream (or `hip_stream`), copies the result back once, waits, and frees
+ * everything on every way out.  OPUSGPU_BAD_ARG before any device work, with the reason: what opusgpu_set_wave_trim refuses of the
+ * record, channels outside 1 - 8, a span that breaks a rule of WAVE BATCHES, samples * channels above 0x7fffffff, no stats_out. */
+int opusgpu_tracks_wave_trim_device(opusgpu_ctx *ctx, int n_tracks, const opusgpu_wave_span *spans, int channels,
+                                    const opusgpu_wave_trim_req *req, const void *d_s16, opusgpu_wave_trim_stat *stats_out,
+                                    uint8_t *flags_out, void *hip_stream);
+
+/* STFT BATCHES. The spectrograms of a TRACK STFT call as ONE dense tensor, padded to a common length and normalised per track: the
  * [B, 513, T] that VITS pads in its collate function, the complex [B, 257, T] of enhancement and separation models, the [B, 1025, T]
  * of music models, a spectrogram image in dB under its own maximum -- without a loop over tracks in the caller's code.  FEATURE
  * BATCHES, its record, its calls, its kernels and everything it refuses (widths above 128, an STFT call with a feature-batch

@@ -35,6 +35,9 @@ normalisation in torch (tools/mel_rate.py: compare_feature_batch).
 --rate R [--mono | --mix M] --wave-batch S[:NORM] [--packets-per-file P]: the fused call under a wave-batch request (include/opusgpu.h
 WAVE BATCHES; one dense padded float32 tensor and its mask, S 0: the longest planned track, NORM none | zmuv | peak) next to the packed
 float32 call followed by the gather into a padded tensor, the normalisation and the mask in torch (tools/wave_rate.py).
+--rate R ... --wave-batch S[:NORM] --wave-trim TOPDB[:FL:HOP]: that fused call with a trim request as well (include/opusgpu.h WAVE
+TRIM; TOPDB under the track's loudest frame, frames of FL every HOP, 2048 and 512 by default) next to the call without the trim and
+to the packed int16 call followed by the same trim, gather, normalisation and mask in torch (tools/wave_rate.py: compare_wave_trim).
 --packets-per-file P: files of P packets of 20 ms (in pages of at most 250) in place of the default 10, for --mel and --melspec: long
 tracks, whose tiles are full.
 --resample UP/DOWN [--mono | --mix M]: the fused ratio call (opusgpu_files_decode_ratio, include/opusgpu.h TRACK RATIOS) next to
@@ -97,6 +100,9 @@ ap.add_argument("--feature-batch", default=None, metavar="S[:NORM]",
 ap.add_argument("--wave-batch", default=None, metavar="S[:NORM]",
                 help="with --rate: the fused call with a wave-batch request (stride S, 0: the longest track; none, zmuv or peak) next to the "
                      "packed float32 call followed by padding, normalising and masking in torch (tools/wave_rate.py)")
+ap.add_argument("--wave-trim", default=None, metavar="TOPDB[:FL:HOP]",
+                help="with --wave-batch: the fused call with a trim request as well (include/opusgpu.h WAVE TRIM; frame 2048, hop 512) next to "
+                     "the call without it and to the packed int16 call followed by the same trim and collate in torch (tools/wave_rate.py)")
 ap.add_argument("--packets-per-file", type=int, default=10,
                 help="with --mel, --melspec, --fbank, --loudness or --wave-batch: packets of 20 ms per file")
 ap.add_argument("--loudness", nargs="?", const="measure", default=None, metavar="TARGET",
@@ -125,6 +131,8 @@ if args.feature_batch and not (args.mel or args.fbank):
     ap.error("--feature-batch goes with --mel or --fbank")
 if args.wave_batch and (not args.rate or args.loudness or (args.rate == 48000 and not (args.mono or args.mix))):
     ap.error("--wave-batch goes with --rate R, and at 48000 with --mono or --mix")
+if args.wave_trim and not args.wave_batch:
+    ap.error("--wave-trim goes with --wave-batch")
 if args.packets_per_file != 10 and not (args.mel or args.melspec or args.stft or args.fbank or args.loudness or args.cuts is not None or
                                         args.wave_batch):
     ap.error("--packets-per-file goes with --mel, --melspec, --stft, --fbank, --loudness, --cuts or --wave-batch")
@@ -235,6 +243,15 @@ if args.rate:
         if args.wave_batch:
             import wave_rate
             S, norm = wave_rate.wave_batch_arg(args.wave_batch)
+            set_batch = lambda wb: ctx._chk(ctx.lib.opusgpu_set_wave_batch(ctx.h, None if wb is None else wb.rec.ctypes.data), "opusgpu_set_wave_batch")
+            channels = 1 if args.mono else int(rec["out_channels"][0]) if rec is not None else 2
+            if args.wave_trim:
+                print(json.dumps(wave_rate.compare_wave_trim(
+                    torch, pkg, resampled, set_batch,
+                    lambda tr: ctx._chk(ctx.lib.opusgpu_set_wave_trim(ctx.h, None if tr is None else tr.ctypes.data), "opusgpu_set_wave_trim"),
+                    b, 1, 48000 // args.rate, channels, S, norm, wave_rate.wave_trim_arg(pkg, args.wave_trim), args.reps,
+                    f"stereo CELT-FB, {PAGES * PER_PAGE} packets per file, {name}")), flush=True)
+                continue
             print(json.dumps(wave_rate.compare_wave_batch(
                 torch, pkg, resampled,
                 lambda wb: ctx._chk(ctx.lib.opusgpu_set_wave_batch(ctx.h, None if wb is None else wb.rec.ctypes.data), "opusgpu_set_wave_batch"),

@@ -16,7 +16,8 @@ ms_rate.py's count per step).
 --rate R --mix mono | stereo: the same through the 5.1 default downmix table (opusgpu_ms_files_decode_mixed).
 --rate R [--mix M] --wave-batch S[:NORM] [--packets-per-file P]: the fused call under a wave-batch request (include/opusgpu.h WAVE
 BATCHES) next to the packed float32 call followed by padding, normalising and masking in torch (tools/wave_rate.py, as
-tools/files_rate.py --wave-batch).
+tools/files_rate.py --wave-batch).  With --wave-trim TOPDB[:FL:HOP] as well: the fused call under both requests (WAVE TRIM) next to
+the call without the trim and to the packed int16 call followed by the same trim and collate in torch, as tools/files_rate.py has it.
 --mel [--n-mels N]: the fused log-mel call (opusgpu_ms_files_decode_mel through the default mono downmix) next to float32 16 kHz mono
 tracks followed by torch.stft, the filterbank matmul and log10, and k_tracks_mel's share of the call (tools/mel_rate.py).
 --melspec tts | kaldi | clap | music: the fused mel-spectrogram call (opusgpu_ms_files_decode_melspec through the default mono downmix)
@@ -82,6 +83,9 @@ ap.add_argument("--loudness", nargs="?", const="measure", default=None, metavar=
 ap.add_argument("--wave-batch", default=None, metavar="S[:NORM]",
                 help="with --rate: the fused call with a wave-batch request (stride S, 0: the longest track; none, zmuv or peak) next to the "
                      "packed float32 call followed by padding, normalising and masking in torch (tools/wave_rate.py)")
+ap.add_argument("--wave-trim", default=None, metavar="TOPDB[:FL:HOP]",
+                help="with --wave-batch: the fused call with a trim request as well (include/opusgpu.h WAVE TRIM; frame 2048, hop 512) next to "
+                     "the call without it and to the packed int16 call followed by the same trim and collate in torch (tools/wave_rate.py)")
 ap.add_argument("--packets-per-file", type=int, default=10, help="with --loudness, --cuts or --wave-batch: packets of 20 ms per file, at most 80")
 ap.add_argument("--cuts", type=int, default=None, metavar="C", help="C random cuts per file next to the whole files (tools/cuts_rate.py)")
 ap.add_argument("--cut-seconds", type=float, default=0.5, metavar="S")
@@ -96,6 +100,8 @@ if args.loudness and (args.format or args.rate or args.mel or args.melspec or ar
     ap.error("--loudness goes alone")
 if args.wave_batch and not args.rate:
     ap.error("--wave-batch goes with --rate R")
+if args.wave_trim and not args.wave_batch:
+    ap.error("--wave-trim goes with --wave-batch")
 if args.packets_per_file != 10 and (not (args.loudness or args.cuts is not None or args.wave_batch) or not 1 <= args.packets_per_file <= 80):
     ap.error("--packets-per-file goes with --loudness, --cuts or --wave-batch and is at most 80: the files have one page")
 if args.melspec and (args.rate or args.format or args.resample or args.mel):
@@ -253,6 +259,15 @@ if args.rate:
     if args.wave_batch:
         import wave_rate
         stride, norm = wave_rate.wave_batch_arg(args.wave_batch)
+        if args.wave_trim:
+            print(json.dumps(wave_rate.compare_wave_trim(
+                torch, pkg, resampled,
+                lambda wb: ms._chk(ms.lib.opusgpu_ms_set_wave_batch(ms.h, None if wb is None else wb.rec.ctypes.data), "opusgpu_ms_set_wave_batch"),
+                lambda tr: ms._chk(ms.lib.opusgpu_ms_set_wave_trim(ms.h, None if tr is None else tr.ctypes.data), "opusgpu_ms_set_wave_trim"),
+                b, 1, 48000 // args.rate, int(rec["out_channels"][0]) if rec is not None else CH, stride, norm,
+                wave_rate.wave_trim_arg(pkg, args.wave_trim), args.reps, f"5.1 CELT-FB, {PACKETS} packets per file, in_order")))
+            ms.close()
+            raise SystemExit(0)
         print(json.dumps(wave_rate.compare_wave_batch(
             torch, pkg, resampled,
             lambda wb: ms._chk(ms.lib.opusgpu_ms_set_wave_batch(ms.h, None if wb is None else wb.rec.ctypes.data), "opusgpu_ms_set_wave_batch"),
