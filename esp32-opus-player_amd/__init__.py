@@ -48,7 +48,7 @@ EXPORTS = [
     "opusgpu_ms_files_decode_ratio",
     "opusgpu_spec_basis", "opusgpu_spec_filterbank", "opusgpu_spec_layout", "opusgpu_tracks_melspec_device", "opusgpu_files_decode_melspec",
     "opusgpu_ms_files_decode_melspec",
-    "opusgpu_stft_basis", "opusgpu_stft_tile", "opusgpu_stft_layout", "opusgpu_tracks_stft_device", "opusgpu_files_decode_stft",
+    "opusgpu_stft_basis", "opusgpu_stft_fft_tables", "opusgpu_stft_tile", "opusgpu_stft_layout", "opusgpu_tracks_stft_device", "opusgpu_files_decode_stft",
     "opusgpu_ms_files_decode_stft",
     "opusgpu_fbank_window", "opusgpu_fbank_filterbank", "opusgpu_fbank_dct", "opusgpu_fbank_layout", "opusgpu_tracks_fbank_device",
     "opusgpu_files_decode_fbank", "opusgpu_ms_files_decode_fbank",
@@ -168,6 +168,8 @@ SPEC_FRAMES = {"torch": 0, "whisper": 1}
 STFT_PARAMS_DTYPE = np.dtype([("sample_rate", "<i4"), ("n_fft", "<i4"), ("win_length", "<i4"), ("hop", "<i4"), ("power", "<i4"), ("log", "<i4"),
                               ("frames", "<i4"), ("layout", "<i4"), ("floor", "<f4"), ("reserved", "<i4", (7,))])
 STFT_COMPLEX = 0  # OPUSGPU_STFT_COMPLEX: power=None
+STFT_ALGO_DENSE, STFT_ALGO_FFT = 0, 1  # OPUSGPU_STFT_ALGO_*: reserved[1] of the record
+STFT_ALGOS = {"dense": STFT_ALGO_DENSE, "fft": STFT_ALGO_FFT}
 # opusgpu_fbank_params and its enums (include/opusgpu.h, TRACK KALDI FEATURES)
 FBANK_PARAMS_DTYPE = np.dtype([("sample_rate", "<i4"), ("frame_length", "<i4"), ("frame_shift", "<i4"), ("n_fft", "<i4"), ("n_mels", "<i4"),
                                ("n_ceps", "<i4"), ("window", "<i4"), ("snip_edges", "u1"), ("remove_dc", "u1"), ("power", "u1"), ("log", "u1"),
@@ -352,6 +354,7 @@ def load_lib():
     lib.opusgpu_files_decode_melspec.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.opusgpu_ms_files_decode_melspec.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.opusgpu_stft_basis.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    lib.opusgpu_stft_fft_tables.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
     lib.opusgpu_stft_tile.argtypes = [vp]
     lib.opusgpu_stft_layout.argtypes = [C.c_int, vp, C.c_int, C.c_int, vp, vp]
     lib.opusgpu_stft_layout.restype = C.c_int64
@@ -1118,12 +1121,13 @@ def _record_feature_args(batch, rec, layout, rate, resample, mono, mix, format, 
     return rec, mrec, scale, offsets, planes, total, out, how
 
 
-def stft_spec(sample_rate, n_fft, hop, win_length=None, power=2, log=None, floor=0.0, frames="torch", feature_layout="bands"):
+def stft_spec(sample_rate, n_fft, hop, win_length=None, power=2, log=None, floor=0.0, frames="torch", feature_layout="bands", algo="dense"):
     """An opusgpu_stft_params record (an STFT_PARAMS_DTYPE array of one; include/opusgpu.h TRACK STFT): the numbers that
     torchaudio's Spectrogram and torch.stft take.  win_length None is n_fft; power 2 (Re^2 + Im^2), 1 (its square root) or None: the
     complex STFT, with torch.stft's sign; log "log10", "ln" or None, over `floor`; frames "torch" (n // hop + 1) or "whisper"
-    (n // hop); feature_layout "bands" ([bins, frames]) or "frames" ([frames, bins]).  Raises ValueError for what the record's rules
-    refuse."""
+    (n // hop); feature_layout "bands" ([bins, frames]) or "frames" ([frames, bins]); algo "dense" (the DFT on the matrix cores,
+    n_fft up to 2048) or "fft" (n_fft a power of two in [64, 8192], any hop in [1, n_fft]).  Raises ValueError for what the record's
+    rules refuse."""
     import numbers
 
     def whole(name, v):
@@ -1132,13 +1136,21 @@ def stft_spec(sample_rate, n_fft, hop, win_length=None, power=2, log=None, floor
         return int(v)
     sample_rate, n_fft, hop = whole("sample_rate", sample_rate), whole("n_fft", n_fft), whole("hop", hop)
     win = n_fft if win_length is None else whole("win_length", win_length)
+    if not isinstance(algo, str) or algo not in STFT_ALGOS:
+        raise ValueError(f"algo must be one of {sorted(STFT_ALGOS)}, not {algo!r}")
     if not 1 <= sample_rate <= 1048576:
         raise ValueError(f"sample_rate must be in [1, 1048576], not {sample_rate}")
-    if not 64 <= n_fft <= 2048 or n_fft % 16:
+    if algo == "fft":
+        if not 64 <= n_fft <= 8192 or n_fft & (n_fft - 1):
+            raise ValueError(f"n_fft must be a power of two in [64, 8192] with algo='fft', not {n_fft}")
+    elif not 64 <= n_fft <= 2048 or n_fft % 16:
         raise ValueError(f"n_fft must be a multiple of 16 in [64, 2048], not {n_fft}")
     if not 16 <= win <= n_fft or win % 2:
         raise ValueError(f"win_length must be even and in [16, n_fft], not {win}")
-    if not 1 <= hop <= n_fft or 31 * hop + n_fft > 32768:
+    if algo == "fft":
+        if not 1 <= hop <= n_fft:
+            raise ValueError(f"hop must be in [1, n_fft] with algo='fft', not {hop}")
+    elif not 1 <= hop <= n_fft or 31 * hop + n_fft > 32768:
         raise ValueError(f"hop must be in [1, n_fft] with 31 * hop + n_fft <= 32768, not {hop}")
     for name, v, table in (("log", log, SPEC_LOGS), ("frames", frames, SPEC_FRAMES), ("feature_layout", feature_layout, MEL_LAYOUTS)):
         if not isinstance(v, (str, type(None))) or v not in table:
@@ -1151,6 +1163,7 @@ def stft_spec(sample_rate, n_fft, hop, win_length=None, power=2, log=None, floor
     rec["sample_rate"], rec["n_fft"], rec["win_length"], rec["hop"] = sample_rate, n_fft, win, hop
     rec["power"], rec["log"] = STFT_COMPLEX if power is None else int(power), SPEC_LOGS[log]
     rec["frames"], rec["layout"] = SPEC_FRAMES[frames], MEL_LAYOUTS[feature_layout]
+    rec["reserved"][0, 1] = STFT_ALGOS[algo]
     try:
         rec["floor"] = float(floor)
     except (TypeError, ValueError):
@@ -1175,8 +1188,17 @@ def stft_basis(rec):
     return tuple(a.reshape(int(rec["n_fft"][0]), -1) for a in tables)
 
 
+def stft_fft_tables(rec):
+    """opusgpu_stft_fft_tables: the tables of a stft_spec(algo="fft") record -> (window [n_fft], twiddle [n_fft / 2, 2]: cos and sin
+    of 2 pi j / n_fft), float32."""
+    rec = _stft_rec(rec)
+    window, twiddle = _tables("opusgpu_stft_fft_tables", C.c_float, (rec.ctypes.data,), 2, "opusgpu_stft_fft_tables refused the record")
+    return window, twiddle.reshape(-1, 2)
+
+
 def stft_tile(rec):
-    """opusgpu_stft_tile: the frames of a tile of k_tracks_stft for a stft_spec record, 128, 64 or 32."""
+    """opusgpu_stft_tile: the frames of a tile for a stft_spec record: of k_tracks_stft 128, 64 or 32, of k_tracks_fft (algo="fft")
+    the larger of 16 and 8192 / n_fft."""
     T = load_lib().opusgpu_stft_tile(_stft_rec(rec).ctypes.data)
     if T < 0:
         raise ValueError("opusgpu_stft_tile refused the record")
@@ -1907,6 +1929,9 @@ def files_request(batch, multistream=False, device=0, format=None, scale=None, o
         req = req._replace(feature_batch=fb, offsets=offsets, total=total, out=out, planes=np.full(batch.n_files, fb.stride, dtype=np.int64))
     if sdense:
         bins, c = int(req.params["n_fft"][0]) // 2 + 1, 2 if int(req.params["power"][0]) == STFT_COMPLEX else 1
+        if bins > STFT_BATCH_MAX_BINS:  # (only an algo="fft" record has that many)
+            raise ValueError(f"stft_stride=, stft_normalize= and stft_pad= hold spectrograms of 1 - {STFT_BATCH_MAX_BINS} bins, "
+                             f"this record has {bins}")
         sb = stft_batch_request(_planned_feature_frames(batch, req), bins, c, stft_stride, stft_normalize, stft_pad)
         offsets, total = stft_batch_layout(batch.n_files, bins, c, sb.stride)
         if out is not None:

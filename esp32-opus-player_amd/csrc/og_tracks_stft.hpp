@@ -2,7 +2,8 @@
 // STFT): the table per (n_fft, win_length), the kernel that turns packed int16 mono tracks into float32 spectrogram tracks, its host
 // side, and the whole-file call that ends in it.  Included at the end of og_api.hip behind og_tracks_melspec.hpp, whose tile rule it
 // takes, and og_tracks_mel.hpp, whose basis builder and packer, span record, run function and whole-file flow it shares, and in front
-// of og_ms_tracks.hpp, which holds the multistream twin of the whole-file call.
+// of og_ms_tracks.hpp, which holds the multistream twin of the whole-file call.  og_tracks_fft.hpp, included behind this header, holds
+// the second algorithm of the record (k_tracks_fft, OPUSGPU_STFT_ALGO_FFT): tracks_stft_run sends an FFT record there.
 #pragma once
 #include <map>
 #include <memory>
@@ -186,20 +187,30 @@ struct StftTables {
 
 static int stft_win(const opusgpu_stft_params &p) { return p.win_length ? p.win_length : p.n_fft; }
 
+// The record's algorithm is reserved[1]: OPUSGPU_STFT_ALGO_DENSE (k_tracks_stft, below) or OPUSGPU_STFT_ALGO_FFT (k_tracks_fft,
+// og_tracks_fft.hpp, which is included behind this header and holds everything the FFT records alone need).
+static bool stft_is_fft(const opusgpu_stft_params &p) { return p.reserved[1] == OPUSGPU_STFT_ALGO_FFT; }
+
 static bool stft_params_ok(const opusgpu_stft_params *p) {
     if (!p) return false;
     if (p->sample_rate < 1 || p->sample_rate > 1048576) return false;
-    if (p->n_fft < 64 || p->n_fft > 2048 || p->n_fft % 16) return false;
+    if (p->reserved[1] != OPUSGPU_STFT_ALGO_DENSE && p->reserved[1] != OPUSGPU_STFT_ALGO_FFT) return false;
+    if (stft_is_fft(*p)) {
+        if (p->n_fft < 64 || p->n_fft > 8192 || (p->n_fft & (p->n_fft - 1))) return false;
+        if (p->hop < 1 || p->hop > p->n_fft) return false;
+    } else {
+        if (p->n_fft < 64 || p->n_fft > 2048 || p->n_fft % 16) return false;
+        if (p->hop < 1 || p->hop > p->n_fft || 31 * p->hop + p->n_fft > MS_MAXW) return false;
+    }
     if (p->win_length && (p->win_length < 16 || p->win_length > p->n_fft || p->win_length % 2)) return false;
-    if (p->hop < 1 || p->hop > p->n_fft || 31 * p->hop + p->n_fft > MS_MAXW) return false;
     if (p->power != OPUSGPU_STFT_COMPLEX && p->power != 1 && p->power != 2) return false;
     if (p->log != OPUSGPU_SPEC_LOG_NONE && p->log != OPUSGPU_SPEC_LOG10 && p->log != OPUSGPU_SPEC_LN) return false;
     if (p->power == OPUSGPU_STFT_COMPLEX && p->log != OPUSGPU_SPEC_LOG_NONE) return false;
     if (p->frames != OPUSGPU_SPEC_FRAMES_TORCH && p->frames != OPUSGPU_SPEC_FRAMES_WHISPER) return false;
     if (p->layout != OPUSGPU_MEL_BANDS_MAJOR && p->layout != OPUSGPU_MEL_FRAMES_MAJOR) return false;
     if (!std::isfinite(p->floor) || p->floor < 0.f || (p->log != OPUSGPU_SPEC_LOG_NONE && !(p->floor > 0.f))) return false;
-    for (int32_t r : p->reserved)
-        if (r) return false;
+    for (int i = 0; i < 7; i++)
+        if (i != 1 && p->reserved[i]) return false;
     return true;
 }
 static_assert(sizeof(opusgpu_stft_params) == 64, "stft params layout");
@@ -230,7 +241,11 @@ static int64_t stft_frames(const opusgpu_stft_params &p, int64_t n) {
 static int stft_width(const opusgpu_stft_params &p) { return (p.n_fft / 2 + 1) * (p.power == OPUSGPU_STFT_COMPLEX ? 2 : 1); }
 // The tile in frames: spec_tile's rule, the largest of 128, 64, 32 whose window fits 65,536 bytes -- the launch's LDS is the window
 // alone, since the kernel stores from its accumulators.
+static int fft_tile(const opusgpu_stft_params &p); // og_tracks_fft.hpp
+static int tracks_fft_run(int device, hipStream_t s, int n_tracks, const opusgpu_mel_span *spans, const void *d_in,
+                          const opusgpu_stft_params *params, void *d_out, const TrackFail &hip_failed);
 static int stft_tile(const opusgpu_stft_params &p) {
+    if (stft_is_fft(p)) return fft_tile(p);
     for (int T = 128; T > 32; T >>= 1)
         if ((T - 1) * p.hop + p.n_fft <= MS_MAXW) return T;
     return 32;
@@ -241,6 +256,7 @@ static size_t stft_lds_bytes(const opusgpu_stft_params &p, int T) { return (((si
 static int tracks_stft_run(int device, hipStream_t s, int n_tracks, const opusgpu_mel_span *spans, const void *d_in,
                            const opusgpu_stft_params *params, void *d_out, const TrackFail &hip_failed) {
     if (!stft_params_ok(params)) return OPUSGPU_BAD_ARG;
+    if (stft_is_fft(*params)) return tracks_fft_run(device, s, n_tracks, spans, d_in, params, d_out, hip_failed);
     const int T = stft_tile(*params);
     const StftTables *tab = nullptr;
     return tracks_feature_run(
@@ -329,7 +345,7 @@ static int files_stft_run(const FilesOwner &own, int rate, int up, int down, int
 extern "C" {
 
 int opusgpu_stft_basis(const opusgpu_stft_params *p, const float **wc, const float **ws) {
-    if (!stft_params_ok(p)) return OPUSGPU_BAD_ARG;
+    if (!stft_params_ok(p) || p->n_fft > 2048) return OPUSGPU_BAD_ARG; // (above 2048 only the FFT runs, which multiplies no Wc / Ws)
     const StftTables &t = stft_tables(*p);
     if (wc) *wc = t.wc.data();
     if (ws) *ws = t.ws.data();

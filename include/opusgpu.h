@@ -1090,8 +1090,25 @@ int opusgpu_files_decode_fbank(opusgpu_ctx *ctx, const opusgpu_file_batch *batch
  *   roundup64(F(ceil(planned_48k[t] * up / down))) frames; feat_offset[t] the running sum of bins * c * plane[u], a multiple of 64
  *   floats.  OPUSGPU_MEL_BANDS_MAJOR (bins-major): cell (k, f) at feat_offset + (k * plane + f) * c.  OPUSGPU_MEL_FRAMES_MAJOR: at
  *   feat_offset + (f * bins + k) * c.  Padding is never written; a track cut short by a failed frame keeps its planned plane and
- *   reports its shorter F. */
+ *   reports its shorter F.
+ *   ALGORITHM.  reserved[1] of the record selects it.  OPUSGPU_STFT_ALGO_DENSE (0, what every record without the word is): the dense
+ *   DFT above on the matrix cores (k_tracks_stft), n_fft up to 2048 -- its table grows with n_fft^2.  OPUSGPU_STFT_ALGO_FFT (1): a
+ *   fast Fourier transform (k_tracks_fft), n_fft a power of two in [64, 8192]: 4096- and 8192-point spectrograms for source
+ *   separation and music models, and the sizes from 64 to 2048 for comparison.  Rules with OPUSGPU_STFT_ALGO_FFT: n_fft a power of
+ *   two in [64, 8192]; win_length even, in [16, n_fft], 0 means n_fft; hop in [1, n_fft] and nothing else (the kernel keeps no window
+ *   of the tile in LDS and forms hop * frame in 64 bits, so the dense kernel's 31 * hop + n_fft <= 32768 has no counterpart); power,
+ *   log, frames, layout, floor and sample_rate as above.  INPUT, FRAMES, WINDOW, WINDOW INDEX, SAMPLE, OUTPUT and LAYOUT hold word
+ *   for word (bins up to 4097); DFT is the same mathematical sum with w in double, Im with torch.stft's sign; SUMMATION ORDER is
+ *   outside the contract here too; the same call on the same input gives the same bits; an all-zero track is one bit pattern, the
+ *   floor's value or +0.0f in both halves of a pair.  FFT TABLES: the kernel multiplies a window, window[i] = (float)w[i], n_fft
+ *   floats, and one twiddle table, twiddle[2j], twiddle[2j + 1] = (float)cos(2 pi j / n_fft), (float)sin(2 pi j / n_fft) for j in
+ *   [0, n_fft / 2) -- no sine or cosine is computed on the device --, each entry computed in double and rounded once, at first use,
+ *   kept per (n_fft, win_length) for the life of the process, safe from any number of threads (opusgpu_stft_fft_tables).  The
+ *   tolerance is that of tests/test_gpu_tracks_fft.py: 8 x the error of a float32 radix-2 FFT in numpy against float64 (DESIGN.md
+ *   section 13p).  Any other value of reserved[1] is refused, as is n_fft 4096 without the word. */
 #define OPUSGPU_STFT_COMPLEX 0
+#define OPUSGPU_STFT_ALGO_DENSE 0
+#define OPUSGPU_STFT_ALGO_FFT 1
 typedef struct opusgpu_stft_params { /* 64 bytes (ABI) */
     int32_t sample_rate; /* Hz of the mono track the frames are cut from, 1 .. 1048576; the whole-file calls check it */
     int32_t n_fft;       /* a multiple of 16 in [64, 2048] */
@@ -1102,20 +1119,29 @@ typedef struct opusgpu_stft_params { /* 64 bytes (ABI) */
     int32_t frames;      /* OPUSGPU_SPEC_FRAMES_TORCH 0: F = n / hop + 1 (0 for n == 0); OPUSGPU_SPEC_FRAMES_WHISPER 1: F = n / hop */
     int32_t layout;      /* OPUSGPU_MEL_BANDS_MAJOR (bins-major) | OPUSGPU_MEL_FRAMES_MAJOR */
     float floor;         /* finite, >= 0; > 0 with a log; not applied to pairs */
-    int32_t reserved[7]; /* 0 */
+    int32_t reserved[7]; /* 0, but reserved[1]: the ALGORITHM, OPUSGPU_STFT_ALGO_DENSE 0 | OPUSGPU_STFT_ALGO_FFT 1, under which n_fft
+                            is a power of two in [64, 8192] and hop is in [1, n_fft] */
 } opusgpu_stft_params;
 /* The DFT basis of *p: sets *wc and *ws (either may be NULL) to Wc and Ws, [n_fft][n_fft / 2 + 1] floats each, valid for the life
- * of the process, and returns n_fft * (n_fft / 2 + 1); OPUSGPU_BAD_ARG for a record that breaks a rule above.  Host only. */
+ * of the process, and returns n_fft * (n_fft / 2 + 1); OPUSGPU_BAD_ARG for a record that breaks a rule above.  The same tables for
+ * either algorithm; OPUSGPU_BAD_ARG for n_fft above 2048, where the two tables would hold 2 x n_fft x (n_fft / 2 + 1) floats (268 MB
+ * at 8192) that no kernel multiplies: FFT records have opusgpu_stft_fft_tables.  Host only. */
 int opusgpu_stft_basis(const opusgpu_stft_params *p, const float **wc, const float **ws);
+/* FFT TABLES of an OPUSGPU_STFT_ALGO_FFT record: sets *window (n_fft floats) and *twiddle (n_fft / 2 pairs of cos, sin), either may
+ * be NULL, valid for the life of the process, and returns n_fft; OPUSGPU_BAD_ARG for an OPUSGPU_STFT_ALGO_DENSE record and for a
+ * record that breaks a rule.  Host only. */
+int opusgpu_stft_fft_tables(const opusgpu_stft_params *p, const float **window, const float **twiddle);
 /* The frames of a tile of k_tracks_stft for *p: the largest of 128, 64 and 32 whose window of (T - 1) hop + n_fft samples is at most
  * 32768 samples (65,536 bytes of LDS), TRACK SPECTROGRAMS' rule: the kernel stores from its accumulators and needs no store area.
- * OPUSGPU_BAD_ARG for a record that breaks a rule.  Host only. */
+ * For an OPUSGPU_STFT_ALGO_FFT record, the frames of a tile of k_tracks_fft: the larger of 16 and 8192 / n_fft, whatever the hop --
+ * 256 / min(256, n_fft / 8) frames are in flight in a workgroup, and a tile is four rounds of them up to n_fft 256, 16 frames from
+ * 512 up.  OPUSGPU_BAD_ARG for a record that breaks a rule.  Host only. */
 int opusgpu_stft_tile(const opusgpu_stft_params *p);
 /* LAYOUT above for n tracks of planned_48k_samples[i] samples at 48 kHz whose frames are cut at up / down of that rate (1 <= up <=
  * down <= 48000; not reduced, not held against sample_rate): writes feat_offsets[i] (may be NULL) and returns the total in floats.
  * OPUSGPU_BAD_ARG: a record that breaks a rule, such an up / down, a negative length.  Host only. */
 int64_t opusgpu_stft_layout(int n, const int64_t *planned_48k_samples, int up, int down, const opusgpu_stft_params *p, int64_t *feat_offsets);
-/* k_tracks_stft alone: opusgpu_tracks_melspec_device's contract and alignment rules -- d_in_mono packed int16 mono tracks, 16-byte
+/* k_tracks_stft alone (k_tracks_fft for an OPUSGPU_STFT_ALGO_FFT record): opusgpu_tracks_melspec_device's contract and alignment rules -- d_in_mono packed int16 mono tracks, 16-byte
  * aligned, read in aligned 16-byte pieces up to the one that holds a track's last sample; `spans` a HOST array of opusgpu_mel_span,
  * whose plane must be a multiple of 64 and >= F; d_out floats, 128-byte aligned -- with this section's record and width.
  * sample_rate is held against nothing.  A track without a frame writes nothing.  Uploads the records, its tile table and the

@@ -21,7 +21,8 @@ the log, and k_tracks_melspec's share of the call (tools/mel_rate.py: compare_sp
 with the request as asked, without a norm on the general and on the direct path, next to the packed call and the packed call followed by
 padding and normalising in torch; the stage alone beside k_feat_batch, and the peak device memory of both paths (tools/mel_rate.py:
 compare_stft_batch).
---stft tiny | enh | vits | wide | whisper_lin [--stft-layout bands | frames]: the fused linear / complex STFT call
+--stft tiny | enh | vits | wide | whisper_lin | fft_tiny | fft_enh | fft_vits | fft_wide | fft_sep | fft_big [--stft-layout bands | frames]
+[--stft-algo dense | fft]: the fused linear / complex STFT call
 (opusgpu_files_decode_stft, mono; include/opusgpu.h TRACK STFT) at that set's rate next to float32 mono tracks at the rate followed by
 torch.stft, abs / abs ** 2 / nothing, the floor and the log, k_tracks_stft's share of the call and the bytes it writes per second
 (tools/mel_rate.py: compare_stft).
@@ -83,9 +84,11 @@ ap.add_argument("--mel", action="store_true", help="compare the fused log-mel ca
 ap.add_argument("--n-mels", type=int, choices=[80, 128], default=80)
 ap.add_argument("--melspec", choices=["tts", "kaldi", "clap", "music"], default=None,
                 help="compare the fused mel-spectrogram call with float mono tracks at the set's rate + torch.stft (tools/mel_rate.py)")
-ap.add_argument("--stft", choices=["tiny", "enh", "vits", "wide", "whisper_lin"], default=None,
+ap.add_argument("--stft", choices=["tiny", "enh", "vits", "wide", "whisper_lin", "fft_tiny", "fft_enh", "fft_vits", "fft_wide", "fft_sep", "fft_big"], default=None,
                 help="compare the fused STFT call with float mono tracks at the set's rate + torch.stft (tools/mel_rate.py: compare_stft)")
 ap.add_argument("--stft-layout", choices=["bands", "frames"], default="bands", help="with --stft: the record's feature_layout")
+ap.add_argument("--stft-algo", choices=["dense", "fft"], default=None,
+                help="with --stft: the record's algorithm (stft_spec's algo=; default: the set's own, dense for the sets without fft_)")
 ap.add_argument("--stft-batch", default=None, metavar="S[:NORM]",
                 help="with --stft: the dense call with an STFT-batch request (stride S, 0: the longest track; none, whisper, refmax, cmn or cmvn), "
                      "on the general and the direct path, next to the packed call followed by padding and normalising in torch, and the stage "
@@ -127,6 +130,8 @@ if args.stft and (args.rate or args.format or args.resample or args.mel or args.
     ap.error("--stft goes alone (with --stft-layout, --n, --packets-per-file, --reps)")
 if (args.stft_batch or args.stft_batch_only) and not args.stft:
     ap.error("--stft-batch goes with --stft")
+if args.stft_algo and not args.stft:
+    ap.error("--stft-algo goes with --stft")
 if args.feature_batch and not (args.mel or args.fbank):
     ap.error("--feature-batch goes with --mel or --fbank")
 if args.wave_batch and (not args.rate or args.loudness or (args.rate == 48000 and not (args.mono or args.mix))):
@@ -371,8 +376,7 @@ if args.melspec:
 
 if args.stft:
     import mel_rate
-    kw, up, down = mel_rate.STFT_SETS[args.stft]
-    rec = pkg.stft_spec(feature_layout=args.stft_layout, **kw)
+    rec, up, down = mel_rate.stft_record(pkg, args.stft, args.stft_layout, args.stft_algo)
     rate = 48000 // down if up == 1 else 0
     b = pkg.FileBatch([r.tobytes() for r in files], channels=2, flags=pkg.PAGES_GROUP_BY_MODE, threads=args.threads)
     assert (b.info["status"] == 0).all() and b.n_steps == PAGES * PER_PAGE

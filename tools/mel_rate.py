@@ -264,7 +264,8 @@ def compare_stft(torch, pkg, decode_tracks, decode_stft, stft_alone, batch, rec,
         top = ref.abs().amax(dim=1 if frames_major else 0, keepdim=True).clamp(min=1e-30)  # the frame's largest
         worst = float(((got - ref).abs() / top).max())  # relative to the frame's largest cell
         assert worst < 1e-4, worst
-    out = {"stft": [int(rec[k][0]) for k in ("sample_rate", "n_fft", "win_length", "hop", "power", "log", "layout")], "files": n,
+    out = {"stft": [int(rec[k][0]) for k in ("sample_rate", "n_fft", "win_length", "hop", "power", "log", "layout")],
+           "algo": "fft" if int(rec["reserved"][0][1]) == pkg.STFT_ALGO_FFT else "dense", "files": n,
            "frames": int(frames.sum()), "reps": reps, "note": note, "tile": pkg.stft_tile(rec), "scratch_s16_bytes": int(total) * 2,
            "out_bytes": int(total_feat) * 4, "padded_batch_floats_of_b": n * longest,
            "worst_error_vs_torch": worst if fits else "not checked: no track long enough"}
@@ -642,7 +643,22 @@ STFT_SETS = {
     "vits": (dict(sample_rate=22050, n_fft=1024, hop=256, power=1), 147, 320),
     "wide": (dict(sample_rate=44100, n_fft=2048, hop=960, power=2, log="log10", floor=1e-10), 147, 160),
     "whisper_lin": (dict(sample_rate=16000, n_fft=400, hop=160, power=2, frames="whisper"), 1, 3),
+    # those of tests/test_tracks_fft.py: algo="fft" (the sets above take it from --stft-algo)
+    "fft_tiny": (dict(sample_rate=8000, n_fft=64, hop=24, win_length=48, power=2, log="ln", floor=1e-10, algo="fft"), 1, 6),
+    "fft_enh": (dict(sample_rate=16000, n_fft=512, hop=128, win_length=400, power=None, algo="fft"), 1, 3),
+    "fft_vits": (dict(sample_rate=22050, n_fft=1024, hop=256, power=1, algo="fft"), 147, 320),
+    "fft_wide": (dict(sample_rate=44100, n_fft=2048, hop=960, power=2, log="log10", floor=1e-10, algo="fft"), 147, 160),
+    "fft_sep": (dict(sample_rate=44100, n_fft=4096, hop=1024, power=None, algo="fft"), 147, 160),
+    "fft_big": (dict(sample_rate=48000, n_fft=8192, hop=1000, win_length=6000, power=2, log="log10", floor=1e-10, frames="whisper", algo="fft"), 1, 1),
 }
+
+
+def stft_record(pkg, name, layout, algo=None):
+    """The stft_spec record of --stft NAME --stft-layout LAYOUT [--stft-algo ALGO] -> (record, up, down)."""
+    kw, up, down = STFT_SETS[name]
+    if algo is not None:
+        kw = dict(kw, algo=algo)
+    return pkg.stft_spec(feature_layout=layout, **kw), up, down
 
 # the parameter sets of --melspec: (mel_spec arguments, up, down)
 SPEC_SETS = {

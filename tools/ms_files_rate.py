@@ -25,7 +25,8 @@ next to float32 mono tracks at the set's rate followed by torch.stft, the filter
 k_tracks_melspec's share of the call (tools/mel_rate.py: compare_spec).
 --stft SET --stft-batch S[:NORM]: the dense STFT call (include/opusgpu.h STFT BATCHES; opusgpu_ms_set_stft_batch) on both paths next to the
 packed call and the packed call followed by padding and normalising in torch (tools/mel_rate.py: compare_stft_batch).
---stft tiny | enh | vits | wide | whisper_lin [--stft-layout bands | frames]: the fused linear / complex STFT call
+--stft tiny | enh | vits | wide | whisper_lin | fft_tiny | fft_enh | fft_vits | fft_wide | fft_sep | fft_big [--stft-layout bands | frames]
+[--stft-algo dense | fft]: the fused linear / complex STFT call
 (opusgpu_ms_files_decode_stft through the default mono downmix; include/opusgpu.h TRACK STFT) next to float32 mono tracks at the set's
 rate followed by torch.stft, abs / abs ** 2 / nothing, the floor and the log, and k_tracks_stft's share of the call (tools/mel_rate.py:
 compare_stft).
@@ -70,9 +71,11 @@ ap.add_argument("--mel", action="store_true", help="compare the fused log-mel ca
 ap.add_argument("--n-mels", type=int, choices=[80, 128], default=80)
 ap.add_argument("--melspec", choices=["tts", "kaldi", "clap", "music"], default=None,
                 help="compare the fused mel-spectrogram call with float mono tracks at the set's rate + torch.stft (tools/mel_rate.py)")
-ap.add_argument("--stft", choices=["tiny", "enh", "vits", "wide", "whisper_lin"], default=None,
+ap.add_argument("--stft", choices=["tiny", "enh", "vits", "wide", "whisper_lin", "fft_tiny", "fft_enh", "fft_vits", "fft_wide", "fft_sep", "fft_big"], default=None,
                 help="compare the fused STFT call with float mono tracks at the set's rate + torch.stft (tools/mel_rate.py: compare_stft)")
 ap.add_argument("--stft-layout", choices=["bands", "frames"], default="bands", help="with --stft: the record's feature_layout")
+ap.add_argument("--stft-algo", choices=["dense", "fft"], default=None,
+                help="with --stft: the record's algorithm (stft_spec's algo=; default: the set's own, dense for the sets without fft_)")
 ap.add_argument("--stft-batch", default=None, metavar="S[:NORM]",
                 help="with --stft: the dense call with an STFT-batch request (stride S, 0: the longest track; none, whisper, refmax, cmn or cmvn) "
                      "next to the packed call followed by padding and normalising in torch (tools/mel_rate.py: compare_stft_batch)")
@@ -111,6 +114,8 @@ if args.stft and (args.rate or args.format or args.resample or args.mel or args.
     ap.error("--stft goes alone (with --stft-layout, --n, --reps)")
 if args.stft_batch and not args.stft:
     ap.error("--stft-batch goes with --stft")
+if args.stft_algo and not args.stft:
+    ap.error("--stft-algo goes with --stft")
 if args.mix and not (args.rate or args.resample):
     ap.error("--mix goes with --rate or --resample")
 if args.mel and (args.rate or args.format or args.resample):
@@ -369,8 +374,7 @@ if args.melspec:
 if args.stft:
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     import mel_rate
-    kw, up, down = mel_rate.STFT_SETS[args.stft]
-    srec = pkg.stft_spec(feature_layout=args.stft_layout, **kw)
+    srec, up, down = mel_rate.stft_record(pkg, args.stft, args.stft_layout, args.stft_algo)
     rate = 48000 // down if up == 1 else 0
     ms = pkg.MultistreamContext(0, n, *LAYOUT)
     mem = pkg.Context(0)
