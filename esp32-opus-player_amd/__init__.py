@@ -46,7 +46,7 @@ EXPORTS = [
     "opusgpu_ms_files_decode_mel",
     "opusgpu_resample_ratio_taps", "opusgpu_resample_ratio_layout", "opusgpu_tracks_resample_ratio_device", "opusgpu_files_decode_ratio",
     "opusgpu_ms_files_decode_ratio",
-    "opusgpu_spec_basis", "opusgpu_spec_filterbank", "opusgpu_spec_layout", "opusgpu_tracks_melspec_device", "opusgpu_files_decode_melspec",
+    "opusgpu_spec_basis", "opusgpu_spec_filterbank", "opusgpu_spec_fft_tables", "opusgpu_spec_tile", "opusgpu_spec_layout", "opusgpu_tracks_melspec_device", "opusgpu_files_decode_melspec",
     "opusgpu_ms_files_decode_melspec",
     "opusgpu_stft_basis", "opusgpu_stft_fft_tables", "opusgpu_stft_tile", "opusgpu_stft_layout", "opusgpu_tracks_stft_device", "opusgpu_files_decode_stft",
     "opusgpu_ms_files_decode_stft",
@@ -164,6 +164,8 @@ SPEC_SCALES = {"slaney": 0, "htk": 1}
 SPEC_NORMS = {"slaney": 0, None: 1, "none": 1}
 SPEC_LOGS = {None: 0, "none": 0, "log10": 1, "ln": 2}
 SPEC_FRAMES = {"torch": 0, "whisper": 1}
+SPEC_ALGO_DENSE, SPEC_ALGO_FFT = 0, 1  # OPUSGPU_SPEC_ALGO_*: reserved[1] of the record
+SPEC_ALGOS = {"dense": SPEC_ALGO_DENSE, "fft": SPEC_ALGO_FFT}
 # opusgpu_stft_params (include/opusgpu.h, TRACK STFT); log, frames and layout take TRACK SPECTROGRAMS' and TRACK FEATURES' values
 STFT_PARAMS_DTYPE = np.dtype([("sample_rate", "<i4"), ("n_fft", "<i4"), ("win_length", "<i4"), ("hop", "<i4"), ("power", "<i4"), ("log", "<i4"),
                               ("frames", "<i4"), ("layout", "<i4"), ("floor", "<f4"), ("reserved", "<i4", (7,))])
@@ -348,6 +350,8 @@ def load_lib():
     lib.opusgpu_ms_files_decode_mel.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.opusgpu_spec_basis.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
     lib.opusgpu_spec_filterbank.argtypes = [vp, C.POINTER(vp)]
+    lib.opusgpu_spec_fft_tables.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    lib.opusgpu_spec_tile.argtypes = [vp]
     lib.opusgpu_spec_layout.argtypes = [C.c_int, vp, C.c_int, C.c_int, vp, vp]
     lib.opusgpu_spec_layout.restype = C.c_int64
     lib.opusgpu_tracks_melspec_device.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
@@ -1003,11 +1007,12 @@ def track_feature_args(batch, features=None, n_mels=80, feature_layout="bands", 
 
 
 def mel_spec(sample_rate, n_fft, hop, win_length=None, n_mels=80, fmin=0.0, fmax=None, mel_scale="slaney", norm="slaney", power=2,
-             log="log10", floor=1e-10, frames="torch", feature_layout="bands"):
+             log="log10", floor=1e-10, frames="torch", feature_layout="bands", algo="dense"):
     """An opusgpu_spec_params record (a SPEC_PARAMS_DTYPE array of one; include/opusgpu.h TRACK SPECTROGRAMS): the numbers that
     torchaudio's MelSpectrogram and librosa's melspectrogram take.  win_length None is n_fft, fmax None is sample_rate / 2; mel_scale
     "slaney" or "htk"; norm "slaney" or None; power 1 or 2; log "log10", "ln" or None; frames "torch" (n // hop + 1) or "whisper"
-    (n // hop); feature_layout as for mel_params.  Raises ValueError for what the record's rules refuse."""
+    (n // hop); feature_layout as for mel_params; algo "dense" (the DFT on the matrix cores, n_fft up to 2048) or "fft" (n_fft a
+    power of two in [64, 8192], any hop in [1, n_fft]).  Raises ValueError for what the record's rules refuse."""
     import numbers
 
     def whole(name, v):
@@ -1016,13 +1021,21 @@ def mel_spec(sample_rate, n_fft, hop, win_length=None, n_mels=80, fmin=0.0, fmax
         return int(v)
     sample_rate, n_fft, hop, n_mels = whole("sample_rate", sample_rate), whole("n_fft", n_fft), whole("hop", hop), whole("n_mels", n_mels)
     win = n_fft if win_length is None else whole("win_length", win_length)
+    if not isinstance(algo, str) or algo not in SPEC_ALGOS:
+        raise ValueError(f"algo must be one of {sorted(SPEC_ALGOS)}, not {algo!r}")
     if not 1 <= sample_rate <= 1048576:
         raise ValueError(f"sample_rate must be in [1, 1048576], not {sample_rate}")
-    if not 64 <= n_fft <= 2048 or n_fft % 16:
+    if algo == "fft":
+        if not 64 <= n_fft <= 8192 or n_fft & (n_fft - 1):
+            raise ValueError(f"n_fft must be a power of two in [64, 8192] with algo='fft', not {n_fft}")
+    elif not 64 <= n_fft <= 2048 or n_fft % 16:
         raise ValueError(f"n_fft must be a multiple of 16 in [64, 2048], not {n_fft}")
     if not 16 <= win <= n_fft or win % 2:
         raise ValueError(f"win_length must be even and in [16, n_fft], not {win}")
-    if not 1 <= hop <= n_fft or 31 * hop + n_fft > 32768:
+    if algo == "fft":
+        if not 1 <= hop <= n_fft:
+            raise ValueError(f"hop must be in [1, n_fft] with algo='fft', not {hop}")
+    elif not 1 <= hop <= n_fft or 31 * hop + n_fft > 32768:
         raise ValueError(f"hop must be in [1, n_fft] with 31 * hop + n_fft <= 32768, not {hop}")
     if not 1 <= n_mels <= 128:
         raise ValueError(f"n_mels must be in [1, 128], not {n_mels}")
@@ -1036,6 +1049,7 @@ def mel_spec(sample_rate, n_fft, hop, win_length=None, n_mels=80, fmin=0.0, fmax
     rec["sample_rate"], rec["n_fft"], rec["win_length"], rec["hop"], rec["n_mels"] = sample_rate, n_fft, win, hop, n_mels
     rec["mel_scale"], rec["norm"], rec["power"], rec["log"] = SPEC_SCALES[mel_scale], SPEC_NORMS[norm], int(power), SPEC_LOGS[log]
     rec["frames"], rec["layout"] = SPEC_FRAMES[frames], MEL_LAYOUTS[feature_layout]
+    rec["reserved"][0, 1] = SPEC_ALGOS[algo]
     try:
         rec["fmin"], rec["fmax"], rec["floor"] = float(fmin), sample_rate / 2 if fmax is None else float(fmax), float(floor)
     except (TypeError, ValueError):
@@ -1055,7 +1069,8 @@ def _spec_rec(rec):
 
 
 def spec_basis(rec):
-    """opusgpu_spec_basis: the windowed DFT basis of a mel_spec record -> (Wc, Ws), float32 [n_fft, n_fft / 2 + 1] each."""
+    """opusgpu_spec_basis: the windowed DFT basis of a mel_spec record -> (Wc, Ws), float32 [n_fft, n_fft / 2 + 1] each.  Raises
+    ValueError for an algo="fft" record: there is no dense basis behind one (spec_fft_tables has its tables)."""
     rec = _spec_rec(rec)
     tables = _tables("opusgpu_spec_basis", C.c_float, (rec.ctypes.data,), 2, "opusgpu_spec_basis refused the record")
     return tuple(a.reshape(int(rec["n_fft"][0]), -1) for a in tables)
@@ -1066,6 +1081,23 @@ def spec_filterbank(rec):
     rec = _spec_rec(rec)
     bank = _tables("opusgpu_spec_filterbank", C.c_float, (rec.ctypes.data,), 1, "opusgpu_spec_filterbank refused the record")[0]
     return bank.reshape(int(rec["n_mels"][0]), -1)
+
+
+def spec_fft_tables(rec):
+    """opusgpu_spec_fft_tables: the tables of a mel_spec(algo="fft") record, which are stft_fft_tables' for the same n_fft and
+    win_length -> (window [n_fft], twiddle [n_fft / 2, 2]: cos and sin of 2 pi j / n_fft), float32."""
+    rec = _spec_rec(rec)
+    window, twiddle = _tables("opusgpu_spec_fft_tables", C.c_float, (rec.ctypes.data,), 2, "opusgpu_spec_fft_tables refused the record")
+    return window, twiddle.reshape(-1, 2)
+
+
+def spec_tile(rec):
+    """opusgpu_spec_tile: the frames of a tile for a mel_spec record: of k_tracks_melspec 128, 64 or 32, of k_tracks_melfft
+    (algo="fft") the larger of 32 and 8192 / n_fft."""
+    T = load_lib().opusgpu_spec_tile(_spec_rec(rec).ctypes.data)
+    if T < 0:
+        raise ValueError("opusgpu_spec_tile refused the record")
+    return int(T)
 
 
 def spec_frames(rec, samples):

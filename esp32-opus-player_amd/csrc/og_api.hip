@@ -1234,6 +1234,7 @@ static int grow(opusgpu_ctx *ctx, void **p, size_t *cap, size_t need) {
 #include "og_tracks_melspec.hpp"
 #include "og_tracks_stft.hpp"
 #include "og_tracks_fft.hpp"
+#include "og_tracks_melfft.hpp"
 #include "og_tracks_fbank.hpp"
 #include "og_feat_batch.hpp"
 #include "og_wave_batch.hpp"

@@ -34,6 +34,71 @@ struct FftArgs {
 
 __device__ __forceinline__ int fft_place(int p) { return p + (p >> 5); }
 
+// The steps that k_tracks_fft and k_tracks_melfft (og_tracks_melfft.hpp) share, for the P threads of one frame, t in [0, P).
+// Sample q of a track of n samples, counted from the track's first: reflected once, then 0; (float)y * scale in one multiply.
+__device__ __forceinline__ float fft_sample(const i16 *trk, long long n, float scale, long long q) {
+    if (q < 0)
+        q = -q;
+    else if (q >= n)
+        q = 2 * (n - 1) - q; // reflected once
+    const i16 y = q >= 0 && q < n ? trk[q] : (i16)0;
+    return __fmul_rn((float)y, scale);
+}
+// 1. LOAD: z[j] of the frame whose first sample is `base`, to place bitrev(j) of `buf`.
+__device__ __forceinline__ void fft_load(float2 *buf, const i16 *trk, long long n, float scale, const float *window, long long base, int t,
+                                         int P, int L) {
+    const int M = 1 << L;
+    for (int j = t; j < M; j += P) {
+        const float x0 = __fmul_rn(fft_sample(trk, n, scale, base + 2 * j), window[2 * j]);
+        const float x1 = __fmul_rn(fft_sample(trk, n, scale, base + 2 * j + 1), window[2 * j + 1]);
+        buf[fft_place((int)(__brev((unsigned)j) >> (32 - L)))] = make_float2(x0, x1);
+    }
+}
+// 2. PASSES over `buf`, in place, a barrier behind each: every thread of the workgroup calls this.
+__device__ __forceinline__ void fft_passes(float2 *buf, const float2 *twiddle, int t, int P, int L) {
+    const int M = 1 << L;
+    int s = 0;
+    if (L & 1) {
+        for (int u = t; u < M / 2; u += P) {
+            const float2 x0 = buf[fft_place(2 * u)], x1 = buf[fft_place(2 * u + 1)];
+            buf[fft_place(2 * u)] = make_float2(x0.x + x1.x, x0.y + x1.y);
+            buf[fft_place(2 * u + 1)] = make_float2(x0.x - x1.x, x0.y - x1.y);
+        }
+        s = 1;
+        __syncthreads();
+    }
+    for (; s < L; s += 2) {
+        const int h = 1 << s;
+        for (int u = t; u < M / 4; u += P) {
+            const int j = u & (h - 1), b = ((u >> s) << (s + 2)) + j;
+            const float2 w2 = twiddle[j << (L - s)], w4 = twiddle[j << (L - s - 1)]; // e^{-i a} = (cos a, -sin a)
+            const float2 x0 = buf[fft_place(b)], x1 = buf[fft_place(b + h)], x2 = buf[fft_place(b + 2 * h)], x3 = buf[fft_place(b + 3 * h)];
+            const float2 t1 = make_float2(x1.x * w2.x + x1.y * w2.y, x1.y * w2.x - x1.x * w2.y);
+            const float2 t3 = make_float2(x3.x * w2.x + x3.y * w2.y, x3.y * w2.x - x3.x * w2.y);
+            const float2 a0 = make_float2(x0.x + t1.x, x0.y + t1.y), a1 = make_float2(x0.x - t1.x, x0.y - t1.y);
+            const float2 a2 = make_float2(x2.x + t3.x, x2.y + t3.y), a3 = make_float2(x2.x - t3.x, x2.y - t3.y);
+            const float2 u2 = make_float2(a2.x * w4.x + a2.y * w4.y, a2.y * w4.x - a2.x * w4.y);
+            const float2 v3 = make_float2(a3.x * w4.x + a3.y * w4.y, a3.y * w4.x - a3.x * w4.y);
+            const float2 u3 = make_float2(v3.y, -v3.x); // times -i
+            buf[fft_place(b)] = make_float2(a0.x + u2.x, a0.y + u2.y);
+            buf[fft_place(b + 2 * h)] = make_float2(a0.x - u2.x, a0.y - u2.y);
+            buf[fft_place(b + h)] = make_float2(a1.x + u3.x, a1.y + u3.y);
+            buf[fft_place(b + 3 * h)] = make_float2(a1.x - u3.x, a1.y - u3.y);
+        }
+        __syncthreads();
+    }
+}
+// 3. SPLIT: X[k], k in [0, M], from Z[k] and Z[M - k] of the frame's buffer z.
+__device__ __forceinline__ void fft_bin(const float2 *z, const float2 *twiddle, int M, int k, float &re, float &im) {
+    const float2 zk = z[fft_place(k & (M - 1))], zm = z[fft_place((M - k) & (M - 1))];
+    const float er = 0.5f * (zk.x + zm.x), ei = 0.5f * (zk.y - zm.y);  // E = (Z[k] + conj Z[M - k]) / 2
+    const float dr = 0.5f * (zk.x - zm.x), di = 0.5f * (zk.y + zm.y);  // D = (Z[k] - conj Z[M - k]) / 2, O = -i D
+    const float2 w = k < M ? twiddle[k] : make_float2(-1.f, 0.f);
+    const float orr = di, oi = -dr;
+    re = er + (orr * w.x + oi * w.y);
+    im = ei + (oi * w.x - orr * w.y);
+}
+
 template <bool FM>
 __global__ void __launch_bounds__(256) k_tracks_fft(const MelTile *__restrict__ tiles, const MelSpan *__restrict__ spans,
                                                     const i16 *__restrict__ in, const float2 *__restrict__ twiddle,
@@ -59,14 +124,6 @@ __global__ void __launch_bounds__(256) k_tracks_fft(const MelTile *__restrict__ 
     const float floor = a.floor;
     float2 *const buf = fft_lds + slot * S;
 
-    auto sample = [&](long long q) {
-        if (q < 0)
-            q = -q;
-        else if (q >= n)
-            q = 2 * (n - 1) - q; // reflected once
-        const i16 y = q >= 0 && q < n ? trk[q] : (i16)0;
-        return __fmul_rn((float)y, scale);
-    };
     auto finish_store = [&](long long f, int k, float re, float im) {
         const long long cell = FM ? f * bins + k : k * plane + f;
         if (power == 0) {
@@ -83,62 +140,17 @@ __global__ void __launch_bounds__(256) k_tracks_fft(const MelTile *__restrict__ 
 
     for (int r0 = 0; r0 < nf; r0 += C) { // a round: frames r0 .. r0 + C - 1 of the tile, those that exist
         // 1. load
-        if (r0 + slot < nf) {
-            const long long base = (long long)H * (tl.first + r0 + slot) - N / 2;
-            for (int j = t; j < M; j += P) {
-                const float x0 = __fmul_rn(sample(base + 2 * j), window[2 * j]);
-                const float x1 = __fmul_rn(sample(base + 2 * j + 1), window[2 * j + 1]);
-                buf[fft_place((int)(__brev((unsigned)j) >> (32 - L)))] = make_float2(x0, x1);
-            }
-        }
+        if (r0 + slot < nf) fft_load(buf, trk, n, scale, window, (long long)H * (tl.first + r0 + slot) - N / 2, t, P, L);
         __syncthreads();
         // 2. passes (a slot without a frame runs them over what its buffer holds and stores nothing)
-        int s = 0;
-        if (L & 1) {
-            for (int u = t; u < M / 2; u += P) {
-                const float2 x0 = buf[fft_place(2 * u)], x1 = buf[fft_place(2 * u + 1)];
-                buf[fft_place(2 * u)] = make_float2(x0.x + x1.x, x0.y + x1.y);
-                buf[fft_place(2 * u + 1)] = make_float2(x0.x - x1.x, x0.y - x1.y);
-            }
-            s = 1;
-            __syncthreads();
-        }
-        for (; s < L; s += 2) {
-            const int h = 1 << s;
-            for (int u = t; u < M / 4; u += P) {
-                const int j = u & (h - 1), b = ((u >> s) << (s + 2)) + j;
-                const float2 w2 = twiddle[j << (L - s)], w4 = twiddle[j << (L - s - 1)]; // e^{-i a} = (cos a, -sin a)
-                const float2 x0 = buf[fft_place(b)], x1 = buf[fft_place(b + h)], x2 = buf[fft_place(b + 2 * h)], x3 = buf[fft_place(b + 3 * h)];
-                const float2 t1 = make_float2(x1.x * w2.x + x1.y * w2.y, x1.y * w2.x - x1.x * w2.y);
-                const float2 t3 = make_float2(x3.x * w2.x + x3.y * w2.y, x3.y * w2.x - x3.x * w2.y);
-                const float2 a0 = make_float2(x0.x + t1.x, x0.y + t1.y), a1 = make_float2(x0.x - t1.x, x0.y - t1.y);
-                const float2 a2 = make_float2(x2.x + t3.x, x2.y + t3.y), a3 = make_float2(x2.x - t3.x, x2.y - t3.y);
-                const float2 u2 = make_float2(a2.x * w4.x + a2.y * w4.y, a2.y * w4.x - a2.x * w4.y);
-                const float2 v3 = make_float2(a3.x * w4.x + a3.y * w4.y, a3.y * w4.x - a3.x * w4.y);
-                const float2 u3 = make_float2(v3.y, -v3.x); // times -i
-                buf[fft_place(b)] = make_float2(a0.x + u2.x, a0.y + u2.y);
-                buf[fft_place(b + 2 * h)] = make_float2(a0.x - u2.x, a0.y - u2.y);
-                buf[fft_place(b + h)] = make_float2(a1.x + u3.x, a1.y + u3.y);
-                buf[fft_place(b + 3 * h)] = make_float2(a1.x - u3.x, a1.y - u3.y);
-            }
-            __syncthreads();
-        }
+        fft_passes(buf, twiddle, t, P, L);
         // 3. split, finish, store
-        auto bin_of = [&](const float2 *z, int k, float &re, float &im) {
-            const float2 zk = z[fft_place(k & (M - 1))], zm = z[fft_place((M - k) & (M - 1))];
-            const float er = 0.5f * (zk.x + zm.x), ei = 0.5f * (zk.y - zm.y);  // E = (Z[k] + conj Z[M - k]) / 2
-            const float dr = 0.5f * (zk.x - zm.x), di = 0.5f * (zk.y + zm.y);  // D = (Z[k] - conj Z[M - k]) / 2, O = -i D
-            const float2 w = k < M ? twiddle[k] : make_float2(-1.f, 0.f);
-            const float orr = di, oi = -dr;
-            re = er + (orr * w.x + oi * w.y);
-            im = ei + (oi * w.x - orr * w.y);
-        };
         if (FM) {
             if (r0 + slot < nf) {
                 const long long f = (long long)tl.first + r0 + slot;
                 for (int k = t; k <= M; k += P) {
                     float re, im;
-                    bin_of(buf, k, re, im);
+                    fft_bin(buf, twiddle, M, k, re, im);
                     finish_store(f, k, re, im);
                 }
             }
@@ -147,7 +159,7 @@ __global__ void __launch_bounds__(256) k_tracks_fft(const MelTile *__restrict__ 
                 const int c = x & (C - 1), k = x >> cs;
                 if (r0 + c < nf) {
                     float re, im;
-                    bin_of(fft_lds + c * S, k, re, im);
+                    fft_bin(fft_lds + c * S, twiddle, M, k, re, im);
                     finish_store((long long)tl.first + r0 + c, k, re, im);
                 }
             }
@@ -164,17 +176,18 @@ struct FftTables {
     std::vector<float> twiddle; // [n_fft / 2][cos, sin] of 2 pi j / n_fft
 };
 
-// The tables of an FFT record that stft_params_ok has passed; safe from any number of threads.
-static const FftTables &fft_tables(const opusgpu_stft_params &p) {
+// The tables of an FFT record that stft_params_ok or spec_params_ok has passed, by its n_fft and window length (never 0 here); safe
+// from any number of threads.  TRACK SPECTROGRAMS' FFT records take theirs from this cache too (og_tracks_melfft.hpp).
+static const FftTables &fft_tables(int n_fft, int win) {
     static std::mutex mu;
     static std::map<std::pair<int, int>, std::unique_ptr<FftTables>> cache;
-    const std::pair<int, int> key(p.n_fft, stft_win(p));
+    const std::pair<int, int> key(n_fft, win);
     std::lock_guard<std::mutex> lock(mu);
     auto it = cache.find(key);
     if (it == cache.end()) {
         const double pi = 3.14159265358979323846;
         std::unique_ptr<FftTables> t(new FftTables);
-        const int n_fft = p.n_fft, win = stft_win(p), left = (n_fft - win) / 2;
+        const int left = (n_fft - win) / 2;
         t->n_fft = n_fft;
         t->window.assign((size_t)n_fft, 0.f);
         for (int i = left; i < left + win; i++) t->window[(size_t)i] = (float)(0.5 - 0.5 * std::cos(2.0 * pi * (i - left) / (double)win));
@@ -206,7 +219,7 @@ static int tracks_fft_run(int device, hipStream_t s, int n_tracks, const opusgpu
     return tracks_feature_run(
         device, s, n_tracks, spans, d_in, d_out, T, 0x7fffffff - T, [&](int64_t n) { return stft_frames(*params, n); },
         [&] {
-            tab = &fft_tables(*params);
+            tab = &fft_tables(params->n_fft, stft_win(*params));
             return FeatTables{&tab->twiddle, &tab->window};
         },
         [&](unsigned n_tiles, const MelTile *d_tiles, const MelSpan *d_spans, const float2 *d_twiddle, const float *d_window) {
@@ -231,7 +244,7 @@ extern "C" {
 
 int opusgpu_stft_fft_tables(const opusgpu_stft_params *p, const float **window, const float **twiddle) {
     if (!stft_params_ok(p) || !stft_is_fft(*p)) return OPUSGPU_BAD_ARG;
-    const FftTables &t = fft_tables(*p);
+    const FftTables &t = fft_tables(p->n_fft, stft_win(*p));
     if (window) *window = t.window.data();
     if (twiddle) *twiddle = t.twiddle.data();
     return t.n_fft;

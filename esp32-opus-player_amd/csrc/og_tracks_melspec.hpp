@@ -2,7 +2,8 @@
 // tables per parameter set, the kernel that turns packed int16 mono tracks into float32 feature tracks, its host side, and the
 // whole-file call that ends in it.  Included at the end of og_api.hip behind og_tracks_mel.hpp, whose table builders
 // and packers, span record, run function and whole-file flow it shares, and in front of og_ms_tracks.hpp, which holds the multistream
-// twin of the whole-file call.
+// twin of the whole-file call.  A record whose algorithm word is OPUSGPU_SPEC_ALGO_FFT passes the rules here and runs in
+// og_tracks_melfft.hpp (k_tracks_melfft), which is included behind og_tracks_fft.hpp and declared below.
 #pragma once
 #include <map>
 #include <memory>
@@ -226,11 +227,21 @@ typedef std::tuple<int, int, int, int, int, int, float, float> SpecKey; // sampl
 
 static int spec_win(const opusgpu_spec_params &p) { return p.win_length ? p.win_length : p.n_fft; }
 
+// The record's algorithm is reserved[1]: OPUSGPU_SPEC_ALGO_DENSE (k_tracks_melspec, above) or OPUSGPU_SPEC_ALGO_FFT (k_tracks_melfft,
+// og_tracks_melfft.hpp, which holds everything the FFT records alone need: they build no Wc / Ws).
+static bool spec_is_fft(const opusgpu_spec_params &p) { return p.reserved[1] == OPUSGPU_SPEC_ALGO_FFT; }
+
 static bool spec_params_ok(const opusgpu_spec_params *p) {
     if (!p) return false;
-    if (p->n_fft < 64 || p->n_fft > 2048 || p->n_fft % 16) return false;
+    if (p->reserved[0] || (p->reserved[1] != OPUSGPU_SPEC_ALGO_DENSE && p->reserved[1] != OPUSGPU_SPEC_ALGO_FFT)) return false;
+    if (spec_is_fft(*p)) {
+        if (p->n_fft < 64 || p->n_fft > 8192 || (p->n_fft & (p->n_fft - 1))) return false;
+        if (p->hop < 1 || p->hop > p->n_fft) return false;
+    } else {
+        if (p->n_fft < 64 || p->n_fft > 2048 || p->n_fft % 16) return false;
+        if (p->hop < 1 || p->hop > p->n_fft || 31 * p->hop + p->n_fft > MS_MAXW) return false;
+    }
     if (p->win_length && (p->win_length < 16 || p->win_length > p->n_fft || p->win_length % 2)) return false;
-    if (p->hop < 1 || p->hop > p->n_fft || 31 * p->hop + p->n_fft > MS_MAXW) return false;
     if (p->n_mels < 1 || p->n_mels > 128) return false;
     if (p->mel_scale != OPUSGPU_SPEC_SLANEY && p->mel_scale != OPUSGPU_SPEC_HTK) return false;
     if (p->norm != OPUSGPU_SPEC_NORM_SLANEY && p->norm != OPUSGPU_SPEC_NORM_NONE) return false;
@@ -241,8 +252,9 @@ static bool spec_params_ok(const opusgpu_spec_params *p) {
     if (p->sample_rate < 1 || p->sample_rate > 1048576) return false;
     if (!(p->fmin >= 0.f) || !(p->fmin < p->fmax) || !((double)p->fmax <= p->sample_rate / 2.0)) return false;
     if (!std::isfinite(p->floor) || p->floor < 0.f || (p->log != OPUSGPU_SPEC_LOG_NONE && !(p->floor > 0.f))) return false;
-    return !p->reserved[0] && !p->reserved[1];
+    return true;
 }
+static_assert(sizeof(opusgpu_spec_params) == 64, "spec params layout");
 
 static std::unique_ptr<SpecTables> spec_tables_make(const opusgpu_spec_params &p) {
     std::unique_ptr<SpecTables> t(new SpecTables);
@@ -263,7 +275,7 @@ static std::unique_ptr<SpecTables> spec_tables_make(const opusgpu_spec_params &p
     return t;
 }
 
-// The tables of a parameter set that spec_params_ok has passed; safe from any number of threads.
+// The tables of a dense parameter set that spec_params_ok has passed; safe from any number of threads.
 static const SpecTables &spec_tables(const opusgpu_spec_params &p) {
     static std::mutex mu;
     static std::map<SpecKey, std::unique_ptr<SpecTables>> cache;
@@ -278,8 +290,14 @@ static const SpecTables &spec_tables(const opusgpu_spec_params &p) {
 static int64_t spec_frames(const opusgpu_spec_params &p, int64_t n) {
     return p.frames == OPUSGPU_SPEC_FRAMES_WHISPER ? n / p.hop : n ? n / p.hop + 1 : 0;
 }
+// og_tracks_melfft.hpp: the tile, the filterbank and the run of an FFT record
+static int melfft_tile(const opusgpu_spec_params &p);
+static const std::vector<float> &melfft_bank(const opusgpu_spec_params &p);
+static int tracks_melfft_run(int device, hipStream_t s, int n_tracks, const opusgpu_mel_span *spans, const void *d_in,
+                             const opusgpu_spec_params *params, void *d_out, const TrackFail &hip_failed);
 // The tile in frames: the largest of 128, 64, 32 whose window fits the kernel's LDS (32 does: spec_params_ok).
 static int spec_tile(const opusgpu_spec_params &p) {
+    if (spec_is_fft(p)) return melfft_tile(p);
     for (int T = 128; T > 32; T >>= 1)
         if ((T - 1) * p.hop + p.n_fft <= MS_MAXW) return T;
     return 32;
@@ -295,6 +313,7 @@ static size_t spec_lds_bytes(const opusgpu_spec_params &p, int T) {
 static int tracks_melspec_run(int device, hipStream_t s, int n_tracks, const opusgpu_mel_span *spans, const void *d_in,
                               const opusgpu_spec_params *params, void *d_out, const TrackFail &hip_failed) {
     if (!spec_params_ok(params)) return OPUSGPU_BAD_ARG;
+    if (spec_is_fft(*params)) return tracks_melfft_run(device, s, n_tracks, spans, d_in, params, d_out, hip_failed);
     const int T = spec_tile(*params);
     const SpecTables *tab = nullptr;
     return tracks_feature_run(
@@ -342,7 +361,7 @@ static int files_melspec_run(const FilesOwner &own, int rate, int up, int down, 
 extern "C" {
 
 int opusgpu_spec_basis(const opusgpu_spec_params *p, const float **wc, const float **ws) {
-    if (!spec_params_ok(p)) return OPUSGPU_BAD_ARG;
+    if (!spec_params_ok(p) || spec_is_fft(*p)) return OPUSGPU_BAD_ARG; // (an FFT record multiplies no Wc / Ws and builds none)
     const SpecTables &t = spec_tables(*p);
     if (wc) *wc = t.wc.data();
     if (ws) *ws = t.ws.data();
@@ -351,10 +370,17 @@ int opusgpu_spec_basis(const opusgpu_spec_params *p, const float **wc, const flo
 
 int opusgpu_spec_filterbank(const opusgpu_spec_params *p, const float **b) {
     if (!spec_params_ok(p)) return OPUSGPU_BAD_ARG;
+    if (spec_is_fft(*p)) {
+        const std::vector<float> &bank = melfft_bank(*p);
+        if (b) *b = bank.data();
+        return (int)bank.size();
+    }
     const SpecTables &t = spec_tables(*p);
     if (b) *b = t.bank.data();
     return t.n_mels * t.bins;
 }
+
+int opusgpu_spec_tile(const opusgpu_spec_params *p) { return spec_params_ok(p) ? spec_tile(*p) : OPUSGPU_BAD_ARG; }
 
 int64_t opusgpu_spec_layout(int n, const int64_t *planned_48k_samples, int up, int down, const opusgpu_spec_params *p, int64_t *feat_offsets) {
     if (!spec_params_ok(p) || !spec_ratio_ok(up, down) || n < 0 || (n && !planned_48k_samples)) return OPUSGPU_BAD_ARG;

@@ -895,7 +895,28 @@ int opusgpu_files_decode_mel(opusgpu_ctx *ctx, const opusgpu_file_batch *batch, 
  *   track.
  *   LAYOUT.  TRACK FEATURES' grid with the new F: plane[t] = roundup64(F(ceil(planned_48k[t] * up / down))), up / down the track's
  *   rate over 48000 (1 / D for a rate of TRACK RATES); feat_offset[t] the running sum of n_mels * plane[u]; both layouts of TRACK
- *   FEATURES; padding is never written; a track cut short by a failed frame keeps its planned plane and reports its shorter F. */
+ *   FEATURES; padding is never written; a track cut short by a failed frame keeps its planned plane and reports its shorter F.
+ *   ALGORITHM.  reserved[1] of the record selects it.  OPUSGPU_SPEC_ALGO_DENSE (0, what every record without the word is): the dense
+ *   DFT above on the matrix cores (k_tracks_melspec), n_fft up to 2048 -- its table grows with n_fft^2.  OPUSGPU_SPEC_ALGO_FFT (1):
+ *   S[k] comes from a fast Fourier transform of the windowed frame (k_tracks_melfft: TRACK STFT's transform, its window and twiddle
+ *   tables, then S and a sparse band product in the same kernel), n_fft a power of two in [64, 8192]: 4096- and 8192-point mel
+ *   spectrograms for source separation and music models, and the sizes from 64 to 2048 without the dense table.  Rules with
+ *   OPUSGPU_SPEC_ALGO_FFT: n_fft a power of two in [64, 8192]; win_length even, in [16, n_fft], 0 means n_fft; hop in [1, n_fft] and
+ *   nothing else (the kernel keeps no window of the tile in LDS, so 31 * hop + n_fft <= 32768 has no counterpart); every other field
+ *   as above.  INPUT, FRAMES, WINDOW, WINDOW INDEX, SAMPLE, MEL, OUTPUT, FILTERBANK and LAYOUT hold word for word; DFT is the same
+ *   mathematical sum with w in double; SUMMATION ORDER is still not part of the contract.  What is: the tolerance of
+ *   tests/test_gpu_tracks_melfft.py (8 x the error of a float32 restatement -- a radix-2 FFT in numpy, a float32 S and band product
+ *   -- against float64, per parameter set); the same bits from the same call on the same input; one bit
+ *   pattern, the floor's value (its log with a log), in every cell of an all-zero track, +0.0f if the floor is 0, under a negative
+ *   scale too; a frame's cells depend only on the record, the scale and the n_fft samples the frame reads, not on where the frame
+ *   sits in its tile, track or batch; padding is never written, and a track without a frame writes nothing.  TABLES of an FFT
+ *   record: B, [n_mels][n_fft / 2 + 1], by the builder of the dense records -- for n_fft <= 2048 the dense record's B bit for bit --,
+ *   the runs of B that the kernel multiplies (per band from its first to its last non-zero float32 entry; a band without one gives
+ *   max(0, floor)), and TRACK STFT's FFT TABLES for the same n_fft and win_length, from the one cache (opusgpu_spec_fft_tables hands
+ *   out what opusgpu_stft_fft_tables does).  No Wc and no Ws are ever built for an FFT record.  Any other value of reserved[1] is
+ *   refused, as is n_fft 4096 without the word. */
+#define OPUSGPU_SPEC_ALGO_DENSE 0
+#define OPUSGPU_SPEC_ALGO_FFT 1
 #define OPUSGPU_SPEC_SLANEY 0
 #define OPUSGPU_SPEC_HTK 1
 #define OPUSGPU_SPEC_NORM_SLANEY 0
@@ -919,19 +940,29 @@ typedef struct opusgpu_spec_params { /* 64 bytes (ABI) */
     int32_t layout;      /* OPUSGPU_MEL_BANDS_MAJOR | OPUSGPU_MEL_FRAMES_MAJOR */
     float fmin, fmax;    /* Hz, 0 <= fmin < fmax <= sample_rate / 2 */
     float floor;         /* finite, >= 0; > 0 with a log */
-    int32_t reserved[2]; /* 0 */
+    int32_t reserved[2]; /* 0, but reserved[1]: the ALGORITHM, OPUSGPU_SPEC_ALGO_DENSE 0 | OPUSGPU_SPEC_ALGO_FFT 1, under which n_fft
+                            is a power of two in [64, 8192] and hop is in [1, n_fft] */
 } opusgpu_spec_params;
 /* The DFT basis of *p: sets *wc and *ws (either may be NULL) to Wc and Ws, [n_fft][n_fft / 2 + 1] floats each, valid for the life
- * of the process, and returns n_fft * (n_fft / 2 + 1); OPUSGPU_BAD_ARG for a record that breaks a rule above.  Host only. */
+ * of the process, and returns n_fft * (n_fft / 2 + 1); OPUSGPU_BAD_ARG for a record that breaks a rule above, and for every
+ * OPUSGPU_SPEC_ALGO_FFT record: there is no dense basis behind one.  Host only. */
 int opusgpu_spec_basis(const opusgpu_spec_params *p, const float **wc, const float **ws);
-/* The filterbank of *p: sets *b (may be NULL) to B, [n_mels][n_fft / 2 + 1] floats, and returns their count; OPUSGPU_BAD_ARG as
- * above.  Host only. */
+/* The filterbank of *p, either algorithm, every size: sets *b (may be NULL) to B, [n_mels][n_fft / 2 + 1] floats, and returns their
+ * count; OPUSGPU_BAD_ARG as above.  Host only. */
 int opusgpu_spec_filterbank(const opusgpu_spec_params *p, const float **b);
+/* FFT TABLES of an OPUSGPU_SPEC_ALGO_FFT record: opusgpu_stft_fft_tables' for the same n_fft and win_length, the very tables -- sets
+ * *window (n_fft floats) and *twiddle (n_fft / 2 pairs of cos, sin), either may be NULL, valid for the life of the process, and
+ * returns n_fft; OPUSGPU_BAD_ARG for an OPUSGPU_SPEC_ALGO_DENSE record and for a record that breaks a rule.  Host only. */
+int opusgpu_spec_fft_tables(const opusgpu_spec_params *p, const float **window, const float **twiddle);
+/* The frames of a tile for *p: of k_tracks_melspec the largest of 128, 64 and 32 whose window of (T - 1) hop + n_fft samples is at
+ * most 32768 samples; of k_tracks_melfft (an OPUSGPU_SPEC_ALGO_FFT record) the larger of 32 and 8192 / n_fft, whatever the hop.
+ * OPUSGPU_BAD_ARG for a record that breaks a rule.  Host only. */
+int opusgpu_spec_tile(const opusgpu_spec_params *p);
 /* LAYOUT above for n tracks of planned_48k_samples[i] samples at 48 kHz whose spectrograms are cut at up / down of that rate (1 <=
  * up <= down <= 48000; not reduced, not held against sample_rate): writes feat_offsets[i] (may be NULL) and returns the total in
  * floats.  OPUSGPU_BAD_ARG: a record that breaks a rule, such an up / down, a negative length.  Host only. */
 int64_t opusgpu_spec_layout(int n, const int64_t *planned_48k_samples, int up, int down, const opusgpu_spec_params *p, int64_t *feat_offsets);
-/* k_tracks_melspec alone: opusgpu_tracks_mel_device's contract and alignment rules -- d_in_mono packed int16 mono tracks, 16-byte
+/* k_tracks_melspec alone (k_tracks_melfft for an OPUSGPU_SPEC_ALGO_FFT record): opusgpu_tracks_mel_device's contract and alignment rules -- d_in_mono packed int16 mono tracks, 16-byte
  * aligned, read in aligned 16-byte pieces up to the one that holds a track's last sample; `spans` a HOST array of opusgpu_mel_span,
  * whose plane must be a multiple of 64 and >= F; d_out floats, 128-byte aligned -- with *p in place of the constants.  sample_rate
  * places the filterbank and is held against nothing.  A track without a frame writes nothing.  Uploads the records, its tile table

@@ -14,7 +14,7 @@ k_tracks_resample's row as well.
 --mono; `--mix mono` and `--mono` produce the same tracks, so their times show what the general staging costs.
 --mel [--n-mels N]: the fused log-mel call (opusgpu_files_decode_mel, mono) next to float32 16 kHz mono tracks followed by
 torch.stft, the filterbank matmul and log10, and k_tracks_mel's share of the call (tools/mel_rate.py).
---melspec tts | kaldi | clap | music: the fused mel-spectrogram call (opusgpu_files_decode_melspec, mono; include/opusgpu.h TRACK
+--melspec tts | kaldi | clap | music | sep | big [--melspec-algo dense | fft] [--melspec-layout bands | frames]: the fused mel-spectrogram call (opusgpu_files_decode_melspec, mono; include/opusgpu.h TRACK
 SPECTROGRAMS) at that set's rate next to float32 mono tracks at the rate followed by torch.stft, the filterbank matmul, the floor and
 the log, and k_tracks_melspec's share of the call (tools/mel_rate.py: compare_spec).
 --stft SET --stft-batch S[:NORM] [--stft-batch-only] [--pipe in_order | pipelined]: the dense STFT call (include/opusgpu.h STFT BATCHES)
@@ -82,11 +82,14 @@ ap.add_argument("--resample", default=None, metavar="UP/DOWN",
                 help="compare the fused ratio call with rate=24000 and with 48 kHz float tracks + a polyphase conv1d in torch (tools/ratio_rate.py)")
 ap.add_argument("--mel", action="store_true", help="compare the fused log-mel call with 16 kHz mono float tracks + torch.stft (tools/mel_rate.py)")
 ap.add_argument("--n-mels", type=int, choices=[80, 128], default=80)
-ap.add_argument("--melspec", choices=["tts", "kaldi", "clap", "music"], default=None,
+ap.add_argument("--melspec", choices=["tts", "kaldi", "clap", "music", "sep", "big"], default=None,
                 help="compare the fused mel-spectrogram call with float mono tracks at the set's rate + torch.stft (tools/mel_rate.py)")
 ap.add_argument("--stft", choices=["tiny", "enh", "vits", "wide", "whisper_lin", "fft_tiny", "fft_enh", "fft_vits", "fft_wide", "fft_sep", "fft_big"], default=None,
                 help="compare the fused STFT call with float mono tracks at the set's rate + torch.stft (tools/mel_rate.py: compare_stft)")
 ap.add_argument("--stft-layout", choices=["bands", "frames"], default="bands", help="with --stft: the record's feature_layout")
+ap.add_argument("--melspec-algo", choices=["dense", "fft"], default=None,
+                help="with --melspec: the record's algorithm (mel_spec's algo=; default: the set's own, dense but for sep and big, which are fft only)")
+ap.add_argument("--melspec-layout", choices=["bands", "frames"], default="bands", help="with --melspec: the record's feature_layout")
 ap.add_argument("--stft-algo", choices=["dense", "fft"], default=None,
                 help="with --stft: the record's algorithm (stft_spec's algo=; default: the set's own, dense for the sets without fft_)")
 ap.add_argument("--stft-batch", default=None, metavar="S[:NORM]",
@@ -94,7 +97,7 @@ ap.add_argument("--stft-batch", default=None, metavar="S[:NORM]",
                      "on the general and the direct path, next to the packed call followed by padding and normalising in torch, and the stage "
                      "alone beside k_feat_batch (tools/mel_rate.py: compare_stft_batch)")
 ap.add_argument("--stft-batch-only", action="store_true", help="with --stft-batch: skip compare_stft's legs")
-ap.add_argument("--pipe", choices=["both", "in_order", "pipelined"], default="both", help="with --stft: which step order to time")
+ap.add_argument("--pipe", choices=["both", "in_order", "pipelined"], default="both", help="with --stft or --melspec: which step order to time")
 ap.add_argument("--fbank", choices=["wenet", "mfcc", "mfcc8k", "wide"], default=None,
                 help="compare the fused Kaldi fbank / MFCC call with float mono tracks at the set's rate + unfold / rfft in torch (tools/mel_rate.py)")
 ap.add_argument("--feature-batch", default=None, metavar="S[:NORM]",
@@ -132,6 +135,10 @@ if (args.stft_batch or args.stft_batch_only) and not args.stft:
     ap.error("--stft-batch goes with --stft")
 if args.stft_algo and not args.stft:
     ap.error("--stft-algo goes with --stft")
+if (args.melspec_algo or args.melspec_layout != "bands") and not args.melspec:
+    ap.error("--melspec-algo and --melspec-layout go with --melspec")
+if args.melspec in ("sep", "big") and args.melspec_algo == "dense":
+    ap.error("--melspec sep and big have no dense leg: n_fft 4096 and 8192 are algo='fft' only")
 if args.feature_batch and not (args.mel or args.fbank):
     ap.error("--feature-batch goes with --mel or --fbank")
 if args.wave_batch and (not args.rate or args.loudness or (args.rate == 48000 and not (args.mono or args.mix))):
@@ -351,8 +358,7 @@ if args.fbank:
 
 if args.melspec:
     import mel_rate
-    kw, up, down = mel_rate.SPEC_SETS[args.melspec]
-    rec = pkg.mel_spec(**kw)
+    rec, up, down = mel_rate.spec_record(pkg, args.melspec, args.melspec_layout, args.melspec_algo)
     rate = 48000 // down if up == 1 else 0
     b = pkg.FileBatch([r.tobytes() for r in files], channels=2, flags=pkg.PAGES_GROUP_BY_MODE, threads=args.threads)
     assert (b.info["status"] == 0).all() and b.n_steps == PAGES * PER_PAGE
@@ -364,13 +370,15 @@ if args.melspec:
             return ctx._chk(ctx.lib.opusgpu_files_decode_resampled(ctx.h, b.h, rate, 1, fmt, None, d, oo, ol, ln, st), "opusgpu_files_decode_resampled")
         return ctx._chk(ctx.lib.opusgpu_files_decode_ratio(ctx.h, b.h, up, down, 1, None, fmt, None, d, oo, ol, ln, st), "opusgpu_files_decode_ratio")
     for name, pipe in (("in_order", 0), ("pipelined", 1)):
+        if args.pipe not in ("both", name):
+            continue
         ctx.set_pipeline(pipe)
         print(json.dumps(mel_rate.compare_spec(
             torch, pkg, tracks,
             lambda p, d, fo, fr, ln, st: ctx._chk(ctx.lib.opusgpu_files_decode_melspec(ctx.h, b.h, rate, 0 if rate else up, 0 if rate else down, 1,
                                                                                        None, p, None, d, fo, fr, ln, st), "opusgpu_files_decode_melspec"),
             lambda spans, d_in, r, d_out: ctx.tracks_melspec_device(spans, d_in, r, d_out), b, rec, up, down, args.reps,
-            f"{args.melspec}, {name}, {PAGES * PER_PAGE} packets per file")), flush=True)
+            f"{args.melspec}, {args.melspec_algo or 'set default'}, {args.melspec_layout}, {name}, {PAGES * PER_PAGE} packets per file")), flush=True)
     ctx.close()
     raise SystemExit(0)
 

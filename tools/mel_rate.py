@@ -167,7 +167,10 @@ def compare_spec(torch, pkg, decode_tracks, decode_spec, spec_alone, batch, rec,
     if fits:
         i = fits[0]
         F, o, p = int(frames[i]), int(feat_offs[i]), int(planes[i])
-        got = feat[o:o + n_mels * p].view(n_mels, p)[:, edge:F - edge].t()
+        if int(rec["layout"][0]) == pkg.MEL_FRAMES_MAJOR:
+            got = feat[o:o + n_mels * F].view(F, n_mels)[edge:F - edge]
+        else:
+            got = feat[o:o + n_mels * p].view(n_mels, p)[:, edge:F - edge].t()
         ref = want[i, edge:F - edge]
         d = (got - ref).abs()
         worst = float((d if log else d / ref.abs().clamp(min=1e-30)).max())
@@ -667,4 +670,16 @@ SPEC_SETS = {
                    floor=1.1920929e-7), 1, 3),
     "clap": (dict(sample_rate=48000, n_fft=1024, hop=480, n_mels=64, fmin=50.0, fmax=14000.0, mel_scale="htk", norm=None), 1, 1),
     "music": (dict(sample_rate=44100, n_fft=2048, hop=441, win_length=1102, n_mels=128), 147, 160),
+    # mf_sep and mf_big of tests/test_tracks_melfft.py: algo="fft" only, no dense record reaches these sizes
+    "sep": (dict(sample_rate=44100, n_fft=4096, hop=1024, n_mels=128, algo="fft"), 147, 160),
+    "big": (dict(sample_rate=48000, n_fft=8192, hop=1000, win_length=6000, n_mels=64, fmin=50.0, fmax=14000.0, mel_scale="htk", norm=None,
+                 frames="whisper", algo="fft"), 1, 1),
 }
+
+
+def spec_record(pkg, name, layout="bands", algo=None):
+    """The mel_spec record of --melspec NAME [--melspec-layout LAYOUT] [--melspec-algo ALGO] -> (record, up, down)."""
+    kw, up, down = SPEC_SETS[name]
+    if algo is not None:
+        kw = dict(kw, algo=algo)
+    return pkg.mel_spec(feature_layout=layout, **kw), up, down

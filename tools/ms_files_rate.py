@@ -20,7 +20,7 @@ tools/files_rate.py --wave-batch).  With --wave-trim TOPDB[:FL:HOP] as well: the
 the call without the trim and to the packed int16 call followed by the same trim and collate in torch, as tools/files_rate.py has it.
 --mel [--n-mels N]: the fused log-mel call (opusgpu_ms_files_decode_mel through the default mono downmix) next to float32 16 kHz mono
 tracks followed by torch.stft, the filterbank matmul and log10, and k_tracks_mel's share of the call (tools/mel_rate.py).
---melspec tts | kaldi | clap | music: the fused mel-spectrogram call (opusgpu_ms_files_decode_melspec through the default mono downmix)
+--melspec tts | kaldi | clap | music | sep | big [--melspec-algo dense | fft] [--melspec-layout bands | frames]: the fused mel-spectrogram call (opusgpu_ms_files_decode_melspec through the default mono downmix)
 next to float32 mono tracks at the set's rate followed by torch.stft, the filterbank matmul, the floor and the log, and
 k_tracks_melspec's share of the call (tools/mel_rate.py: compare_spec).
 --stft SET --stft-batch S[:NORM]: the dense STFT call (include/opusgpu.h STFT BATCHES; opusgpu_ms_set_stft_batch) on both paths next to the
@@ -69,11 +69,14 @@ ap.add_argument("--resample", default=None, metavar="UP/DOWN",
                 help="compare the fused ratio call with rate=24000 and with 48 kHz float tracks + a polyphase conv1d in torch (tools/ratio_rate.py)")
 ap.add_argument("--mel", action="store_true", help="compare the fused log-mel call with 16 kHz mono float tracks + torch.stft (tools/mel_rate.py)")
 ap.add_argument("--n-mels", type=int, choices=[80, 128], default=80)
-ap.add_argument("--melspec", choices=["tts", "kaldi", "clap", "music"], default=None,
+ap.add_argument("--melspec", choices=["tts", "kaldi", "clap", "music", "sep", "big"], default=None,
                 help="compare the fused mel-spectrogram call with float mono tracks at the set's rate + torch.stft (tools/mel_rate.py)")
 ap.add_argument("--stft", choices=["tiny", "enh", "vits", "wide", "whisper_lin", "fft_tiny", "fft_enh", "fft_vits", "fft_wide", "fft_sep", "fft_big"], default=None,
                 help="compare the fused STFT call with float mono tracks at the set's rate + torch.stft (tools/mel_rate.py: compare_stft)")
 ap.add_argument("--stft-layout", choices=["bands", "frames"], default="bands", help="with --stft: the record's feature_layout")
+ap.add_argument("--melspec-algo", choices=["dense", "fft"], default=None,
+                help="with --melspec: the record's algorithm (mel_spec's algo=; default: the set's own, dense but for sep and big, which are fft only)")
+ap.add_argument("--melspec-layout", choices=["bands", "frames"], default="bands", help="with --melspec: the record's feature_layout")
 ap.add_argument("--stft-algo", choices=["dense", "fft"], default=None,
                 help="with --stft: the record's algorithm (stft_spec's algo=; default: the set's own, dense for the sets without fft_)")
 ap.add_argument("--stft-batch", default=None, metavar="S[:NORM]",
@@ -116,6 +119,10 @@ if args.stft_batch and not args.stft:
     ap.error("--stft-batch goes with --stft")
 if args.stft_algo and not args.stft:
     ap.error("--stft-algo goes with --stft")
+if (args.melspec_algo or args.melspec_layout != "bands") and not args.melspec:
+    ap.error("--melspec-algo and --melspec-layout go with --melspec")
+if args.melspec in ("sep", "big") and args.melspec_algo == "dense":
+    ap.error("--melspec sep and big have no dense leg: n_fft 4096 and 8192 are algo='fft' only")
 if args.mix and not (args.rate or args.resample):
     ap.error("--mix goes with --rate or --resample")
 if args.mel and (args.rate or args.format or args.resample):
@@ -348,8 +355,7 @@ if args.fbank:
 if args.melspec:
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     import mel_rate
-    kw, up, down = mel_rate.SPEC_SETS[args.melspec]
-    srec = pkg.mel_spec(**kw)
+    srec, up, down = mel_rate.spec_record(pkg, args.melspec, args.melspec_layout, args.melspec_algo)
     rate = 48000 // down if up == 1 else 0
     ms = pkg.MultistreamContext(0, n, *LAYOUT)
     mem = pkg.Context(0)
