@@ -1062,23 +1062,58 @@ def mel_spec(sample_rate, n_fft, hop, win_length=None, n_mels=80, fmin=0.0, fmax
     return rec
 
 
-def _spec_rec(rec):
-    if getattr(rec, "dtype", None) != SPEC_PARAMS_DTYPE or np.size(rec) != 1:
-        raise ValueError("a spectrogram's parameters are a mel_spec() record")
+def _record(rec, dtype, what):
+    """A parameter record as the library takes it: one contiguous element of `dtype`; ValueError(what) for anything else."""
+    if getattr(rec, "dtype", None) != dtype or np.size(rec) != 1:
+        raise ValueError(what)
     return np.ascontiguousarray(rec).reshape(1)
+
+
+# (dtype, what) of the three records, as _record takes them
+_SPEC = (SPEC_PARAMS_DTYPE, "a spectrogram's parameters are a mel_spec() record")
+_STFT = (STFT_PARAMS_DTYPE, "an STFT's parameters are a stft_spec() record")
+_FBANK = (FBANK_PARAMS_DTYPE, "Kaldi features' parameters are a kaldi_fbank() or kaldi_mfcc() record")
+
+
+# The calls that mel_spec and stft_spec records share, keyed by the C symbol, for a checked record.
+def _record_basis(name, rec):
+    tables = _tables(name, C.c_float, (rec.ctypes.data,), 2, f"{name} refused the record")
+    return tuple(a.reshape(int(rec["n_fft"][0]), -1) for a in tables)
+
+
+def _record_fft_tables(name, rec):
+    window, twiddle = _tables(name, C.c_float, (rec.ctypes.data,), 2, f"{name} refused the record")
+    return window, twiddle.reshape(-1, 2)
+
+
+def _record_tile(name, rec):
+    T = getattr(load_lib(), name)(rec.ctypes.data)
+    if T < 0:
+        raise ValueError(f"{name} refused the record")
+    return int(T)
+
+
+def _centered_frames(rec, samples):
+    n, hop = np.asarray(samples, dtype=np.int64), int(rec["hop"][0])
+    return n // hop if int(rec["frames"][0]) == SPEC_FRAMES["whisper"] else np.where(n > 0, n // hop + 1, 0)
+
+
+def _record_layout(name, planned_48k_samples, up, down, rec, frames):
+    """opusgpu_spec_layout / opusgpu_stft_layout / opusgpu_fbank_layout for a checked record whose F is frames(rec, samples)."""
+    planned, offsets, total = _layout(name, planned_48k_samples, (int(up), int(down), rec.ctypes.data),
+                                      f"the record, the ratio {up!r}/{down!r} or a negative length")
+    return offsets, (frames(rec, -(-planned * int(up) // int(down))) + 63) // 64 * 64, total
 
 
 def spec_basis(rec):
     """opusgpu_spec_basis: the windowed DFT basis of a mel_spec record -> (Wc, Ws), float32 [n_fft, n_fft / 2 + 1] each.  Raises
     ValueError for an algo="fft" record: there is no dense basis behind one (spec_fft_tables has its tables)."""
-    rec = _spec_rec(rec)
-    tables = _tables("opusgpu_spec_basis", C.c_float, (rec.ctypes.data,), 2, "opusgpu_spec_basis refused the record")
-    return tuple(a.reshape(int(rec["n_fft"][0]), -1) for a in tables)
+    return _record_basis("opusgpu_spec_basis", _record(rec, *_SPEC))
 
 
 def spec_filterbank(rec):
     """opusgpu_spec_filterbank: the filterbank of a mel_spec record -> float32 [n_mels, n_fft / 2 + 1]."""
-    rec = _spec_rec(rec)
+    rec = _record(rec, *_SPEC)
     bank = _tables("opusgpu_spec_filterbank", C.c_float, (rec.ctypes.data,), 1, "opusgpu_spec_filterbank refused the record")[0]
     return bank.reshape(int(rec["n_mels"][0]), -1)
 
@@ -1086,34 +1121,24 @@ def spec_filterbank(rec):
 def spec_fft_tables(rec):
     """opusgpu_spec_fft_tables: the tables of a mel_spec(algo="fft") record, which are stft_fft_tables' for the same n_fft and
     win_length -> (window [n_fft], twiddle [n_fft / 2, 2]: cos and sin of 2 pi j / n_fft), float32."""
-    rec = _spec_rec(rec)
-    window, twiddle = _tables("opusgpu_spec_fft_tables", C.c_float, (rec.ctypes.data,), 2, "opusgpu_spec_fft_tables refused the record")
-    return window, twiddle.reshape(-1, 2)
+    return _record_fft_tables("opusgpu_spec_fft_tables", _record(rec, *_SPEC))
 
 
 def spec_tile(rec):
     """opusgpu_spec_tile: the frames of a tile for a mel_spec record: of k_tracks_melspec 128, 64 or 32, of k_tracks_melfft
     (algo="fft") the larger of 32 and 8192 / n_fft."""
-    T = load_lib().opusgpu_spec_tile(_spec_rec(rec).ctypes.data)
-    if T < 0:
-        raise ValueError("opusgpu_spec_tile refused the record")
-    return int(T)
+    return _record_tile("opusgpu_spec_tile", _record(rec, *_SPEC))
 
 
 def spec_frames(rec, samples):
     """F of TRACK SPECTROGRAMS for tracks of `samples` samples at the record's rate."""
-    rec = _spec_rec(rec)
-    n, hop = np.asarray(samples, dtype=np.int64), int(rec["hop"][0])
-    return n // hop if int(rec["frames"][0]) == SPEC_FRAMES["whisper"] else np.where(n > 0, n // hop + 1, 0)
+    return _centered_frames(_record(rec, *_SPEC), samples)
 
 
 def spec_layout(planned_48k_samples, up, down, rec):
     """opusgpu_spec_layout: the grid of the spectrograms of tracks at up / down of 48 kHz -> (feat_offsets [int64], planes [int64],
     total floats)."""
-    rec = _spec_rec(rec)
-    planned, offsets, total = _layout("opusgpu_spec_layout", planned_48k_samples, (int(up), int(down), rec.ctypes.data),
-                                      f"the record, the ratio {up!r}/{down!r} or a negative length")
-    return offsets, (spec_frames(rec, -(-planned * int(up) // int(down))) + 63) // 64 * 64, total
+    return _record_layout("opusgpu_spec_layout", planned_48k_samples, up, down, _record(rec, *_SPEC), _centered_frames)
 
 
 def track_spectrogram_args(batch, features, rate=None, resample=None, mono=False, mix=None, format=None, scale=None, out=None, device=0,
@@ -1124,7 +1149,7 @@ def track_spectrogram_args(batch, features, rate=None, resample=None, mono=False
     is taken as the one or the other.  Raises ValueError for a record that breaks a rule, both rate= and resample=, a rate or ratio
     that does not exist or is not the record's sample_rate, and for what track_feature_args refuses of format, mono, mix, scale and
     out."""
-    return _record_feature_args(batch, _spec_rec(features), spec_layout, rate, resample, mono, mix, format, scale, out, device, allow_mono)
+    return _record_feature_args(batch, _record(features, *_SPEC), spec_layout, rate, resample, mono, mix, format, scale, out, device, allow_mono)
 
 
 def _record_feature_args(batch, rec, layout, rate, resample, mono, mix, format, scale, out, device, allow_mono):
@@ -1206,64 +1231,46 @@ def stft_spec(sample_rate, n_fft, hop, win_length=None, power=2, log=None, floor
     return rec
 
 
-def _stft_rec(rec):
-    if getattr(rec, "dtype", None) != STFT_PARAMS_DTYPE or np.size(rec) != 1:
-        raise ValueError("an STFT's parameters are a stft_spec() record")
-    return np.ascontiguousarray(rec).reshape(1)
-
-
 def stft_basis(rec):
     """opusgpu_stft_basis: the windowed DFT basis of a stft_spec record -> (Wc, Ws), float32 [n_fft, n_fft / 2 + 1] each;
     Im = -(frame @ Ws)."""
-    rec = _stft_rec(rec)
-    tables = _tables("opusgpu_stft_basis", C.c_float, (rec.ctypes.data,), 2, "opusgpu_stft_basis refused the record")
-    return tuple(a.reshape(int(rec["n_fft"][0]), -1) for a in tables)
+    return _record_basis("opusgpu_stft_basis", _record(rec, *_STFT))
 
 
 def stft_fft_tables(rec):
     """opusgpu_stft_fft_tables: the tables of a stft_spec(algo="fft") record -> (window [n_fft], twiddle [n_fft / 2, 2]: cos and sin
     of 2 pi j / n_fft), float32."""
-    rec = _stft_rec(rec)
-    window, twiddle = _tables("opusgpu_stft_fft_tables", C.c_float, (rec.ctypes.data,), 2, "opusgpu_stft_fft_tables refused the record")
-    return window, twiddle.reshape(-1, 2)
+    return _record_fft_tables("opusgpu_stft_fft_tables", _record(rec, *_STFT))
 
 
 def stft_tile(rec):
     """opusgpu_stft_tile: the frames of a tile for a stft_spec record: of k_tracks_stft 128, 64 or 32, of k_tracks_fft (algo="fft")
     the larger of 16 and 8192 / n_fft."""
-    T = load_lib().opusgpu_stft_tile(_stft_rec(rec).ctypes.data)
-    if T < 0:
-        raise ValueError("opusgpu_stft_tile refused the record")
-    return int(T)
+    return _record_tile("opusgpu_stft_tile", _record(rec, *_STFT))
 
 
 def stft_width(rec):
     """The floats of one frame of a stft_spec record: n_fft / 2 + 1 bins, twice that for the complex STFT."""
-    rec = _stft_rec(rec)
+    rec = _record(rec, *_STFT)
     return (int(rec["n_fft"][0]) // 2 + 1) * (2 if int(rec["power"][0]) == STFT_COMPLEX else 1)
 
 
 def stft_frames(rec, samples):
     """F of TRACK STFT for tracks of `samples` samples at the record's rate."""
-    rec = _stft_rec(rec)
-    n, hop = np.asarray(samples, dtype=np.int64), int(rec["hop"][0])
-    return n // hop if int(rec["frames"][0]) == SPEC_FRAMES["whisper"] else np.where(n > 0, n // hop + 1, 0)
+    return _centered_frames(_record(rec, *_STFT), samples)
 
 
 def stft_layout(planned_48k_samples, up, down, rec):
     """opusgpu_stft_layout: the grid of the STFT spectrograms of tracks at up / down of 48 kHz -> (feat_offsets [int64], planes
     [int64], total floats)."""
-    rec = _stft_rec(rec)
-    planned, offsets, total = _layout("opusgpu_stft_layout", planned_48k_samples, (int(up), int(down), rec.ctypes.data),
-                                      f"the record, the ratio {up!r}/{down!r} or a negative length")
-    return offsets, (stft_frames(rec, -(-planned * int(up) // int(down))) + 63) // 64 * 64, total
+    return _record_layout("opusgpu_stft_layout", planned_48k_samples, up, down, _record(rec, *_STFT), _centered_frames)
 
 
 def track_stft_args(batch, features, rate=None, resample=None, mono=False, mix=None, format=None, scale=None, out=None, device=0,
                     allow_mono=True):
     """track_spectrogram_args for a stft_spec record as decode_files' features=: the same tuple, the same refusals, with
     stft_layout's grid (total and the out= size are in floats: a complex cell is two)."""
-    return _record_feature_args(batch, _stft_rec(features), stft_layout, rate, resample, mono, mix, format, scale, out, device, allow_mono)
+    return _record_feature_args(batch, _record(features, *_STFT), stft_layout, rate, resample, mono, mix, format, scale, out, device, allow_mono)
 
 
 def _kaldi_record(sample_rate, frame_length, frame_shift, num_mel_bins, low_freq, high_freq, preemphasis_coefficient, remove_dc_offset,
@@ -1367,34 +1374,28 @@ def kaldi_mfcc(sample_rate=16000, frame_length=25.0, frame_shift=10.0, num_mel_b
                          window_type, round_to_power_of_two, snip_edges, use_power, True, feature_layout, num_ceps, cepstral_lifter, rejected)
 
 
-def _fbank_rec(rec):
-    if getattr(rec, "dtype", None) != FBANK_PARAMS_DTYPE or np.size(rec) != 1:
-        raise ValueError("Kaldi features' parameters are a kaldi_fbank() or kaldi_mfcc() record")
-    return np.ascontiguousarray(rec).reshape(1)
-
-
 def fbank_width(rec):
     """The feature width of a kaldi_fbank / kaldi_mfcc record: n_ceps when it is > 0, else n_mels."""
-    rec = _fbank_rec(rec)
+    rec = _record(rec, *_FBANK)
     return int(rec["n_ceps"][0]) or int(rec["n_mels"][0])
 
 
 def fbank_window(rec):
     """opusgpu_fbank_window: the window of a kaldi_fbank / kaldi_mfcc record -> float32 [frame_length]."""
-    rec = _fbank_rec(rec)
+    rec = _record(rec, *_FBANK)
     return _tables("opusgpu_fbank_window", C.c_float, (rec.ctypes.data,), 1, "opusgpu_fbank_window refused the record")[0]
 
 
 def fbank_filterbank(rec):
     """opusgpu_fbank_filterbank: the filterbank of a kaldi_fbank / kaldi_mfcc record -> float32 [n_mels, n_fft / 2]."""
-    rec = _fbank_rec(rec)
+    rec = _record(rec, *_FBANK)
     bank = _tables("opusgpu_fbank_filterbank", C.c_float, (rec.ctypes.data,), 1, "opusgpu_fbank_filterbank refused the record")[0]
     return bank.reshape(int(rec["n_mels"][0]), -1)
 
 
 def fbank_dct(rec):
     """opusgpu_fbank_dct: the lifted DCT of a kaldi_mfcc record -> float32 [n_ceps, n_mels] ([0, n_mels] for a kaldi_fbank record)."""
-    rec = _fbank_rec(rec)
+    rec = _record(rec, *_FBANK)
     n = load_lib().opusgpu_fbank_dct(rec.ctypes.data, None)
     if n < 0:
         raise ValueError("opusgpu_fbank_dct refused the record")
@@ -1406,7 +1407,7 @@ def fbank_dct(rec):
 
 def fbank_frames(rec, samples):
     """F of TRACK KALDI FEATURES for tracks of `samples` samples at the record's rate."""
-    rec = _fbank_rec(rec)
+    rec = _record(rec, *_FBANK)
     n, L, H = np.asarray(samples, dtype=np.int64), int(rec["frame_length"][0]), int(rec["frame_shift"][0])
     if int(rec["snip_edges"][0]):
         return np.where(n < L, 0, 1 + (n - L) // H)
@@ -1416,10 +1417,7 @@ def fbank_frames(rec, samples):
 def fbank_layout(planned_48k_samples, up, down, rec):
     """opusgpu_fbank_layout: the grid of the Kaldi features of tracks at up / down of 48 kHz -> (feat_offsets [int64], planes [int64],
     total floats)."""
-    rec = _fbank_rec(rec)
-    planned, offsets, total = _layout("opusgpu_fbank_layout", planned_48k_samples, (int(up), int(down), rec.ctypes.data),
-                                      f"the record, the ratio {up!r}/{down!r} or a negative length")
-    return offsets, (fbank_frames(rec, -(-planned * int(up) // int(down))) + 63) // 64 * 64, total
+    return _record_layout("opusgpu_fbank_layout", planned_48k_samples, up, down, _record(rec, *_FBANK), fbank_frames)
 
 
 def track_kaldi_args(batch, features, rate=None, resample=None, mono=False, mix=None, format=None, scale=None, out=None, device=0,
@@ -1430,7 +1428,7 @@ def track_kaldi_args(batch, features, rate=None, resample=None, mono=False, mix=
     import numbers
     if isinstance(scale, numbers.Real) and not isinstance(scale, bool):
         scale = np.full(batch.n_files, scale, dtype=np.float32)
-    return _record_feature_args(batch, _fbank_rec(features), fbank_layout, rate, resample, mono, mix, format, scale, out, device, allow_mono)
+    return _record_feature_args(batch, _record(features, *_FBANK), fbank_layout, rate, resample, mono, mix, format, scale, out, device, allow_mono)
 
 
 def loudness_weights(channels):
@@ -2349,7 +2347,7 @@ class Context:
         """k_tracks_fbank alone (include/opusgpu.h TRACK KALDI FEATURES): spans a HOST array of MEL_SPAN_DTYPE, d_in packed int16 mono
         tracks at the record's rate, rec a kaldi_fbank / kaldi_mfcc record, d_out the float32 feature tracks.  Waits for the kernel."""
         spans = np.ascontiguousarray(spans, dtype=MEL_SPAN_DTYPE)
-        rec = _fbank_rec(rec)
+        rec = _record(rec, *_FBANK)
         self._chk(self.lib.opusgpu_tracks_fbank_device(self.h, spans.size, spans.ctypes.data, d_in, rec.ctypes.data, d_out, stream),
                   "opusgpu_tracks_fbank_device")
 
@@ -2404,7 +2402,7 @@ class Context:
         """k_tracks_melspec alone (include/opusgpu.h TRACK SPECTROGRAMS): spans a HOST array of MEL_SPAN_DTYPE, d_in packed int16 mono
         tracks at the record's rate, rec a mel_spec record, d_out the float32 feature tracks.  Waits for the kernel."""
         spans = np.ascontiguousarray(spans, dtype=MEL_SPAN_DTYPE)
-        rec = _spec_rec(rec)
+        rec = _record(rec, *_SPEC)
         self._chk(self.lib.opusgpu_tracks_melspec_device(self.h, spans.size, spans.ctypes.data, d_in, rec.ctypes.data, d_out, stream),
                   "opusgpu_tracks_melspec_device")
 
@@ -2413,7 +2411,7 @@ class Context:
         the record's rate, rec a stft_spec record, d_out the float32 spectrogram tracks (pairs for the complex STFT).  Waits for the
         kernel."""
         spans = np.ascontiguousarray(spans, dtype=MEL_SPAN_DTYPE)
-        rec = _stft_rec(rec)
+        rec = _record(rec, *_STFT)
         self._chk(self.lib.opusgpu_tracks_stft_device(self.h, spans.size, spans.ctypes.data, d_in, rec.ctypes.data, d_out, stream),
                   "opusgpu_tracks_stft_device")
 

@@ -1230,11 +1230,10 @@ static int grow(opusgpu_ctx *ctx, void **p, size_t *cap, size_t need) {
 #include "og_tracks_loudness.hpp"
 #include "og_tracks_resample.hpp"
 #include "og_tracks_resample_ratio.hpp"
+#include "og_feat.hpp"
 #include "og_tracks_mel.hpp"
-#include "og_tracks_melspec.hpp"
-#include "og_tracks_stft.hpp"
-#include "og_tracks_fft.hpp"
-#include "og_tracks_melfft.hpp"
+#include "og_tracks_stft.hpp"    // includes og_tracks_fft.hpp
+#include "og_tracks_melspec.hpp" // includes og_tracks_melfft.hpp
 #include "og_tracks_fbank.hpp"
 #include "og_feat_batch.hpp"
 #include "og_wave_batch.hpp"

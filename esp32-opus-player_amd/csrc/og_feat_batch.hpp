@@ -1,7 +1,7 @@
 // og_feat_batch.hpp -- feature batches (include/opusgpu.h, FEATURE BATCHES): the packed feature grid of TRACK FEATURES, TRACK
 // SPECTROGRAMS or TRACK KALDI FEATURES collated into one dense tensor of n * S * W floats, every track normalised by statistics of
 // its own real cells and padded to S frames.  Included by og_api.hip behind og_tracks_fbank.hpp; files_feature_run
-// (og_tracks_mel.hpp) calls feat_batch_run behind its feature kernel when the owner holds a request.  DESIGN.md section 13k.
+// (og_feat.hpp) calls feat_batch_run behind its feature kernel when the owner holds a request.  DESIGN.md section 13k.
 #pragma once
 
 // ---- kernels ------------------------------------------------------------------------------------------

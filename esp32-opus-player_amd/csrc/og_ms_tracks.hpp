@@ -1,7 +1,7 @@
 // og_ms_tracks.hpp -- whole multistream files (include/opusgpu.h, WHOLE FILES / MULTISTREAM): the kernel that maps channels and
 // assembles tracks in one pass, and what the driver of a planned batch (og_files_run.hpp) needs of an opusgpu_ms.  Included at the
 // end of og_api.hip behind og_ms.hpp (opusgpu_ms, ms_step_impl), og_tracks.hpp (TrackSeg, TrackState), og_tracks_resample.hpp,
-// og_tracks_resample_ratio.hpp, og_tracks_mel.hpp, og_tracks_melspec.hpp, og_tracks_stft.hpp and og_tracks_fbank.hpp.
+// og_tracks_resample_ratio.hpp, og_feat.hpp, og_tracks_mel.hpp, og_tracks_stft.hpp, og_tracks_melspec.hpp and og_tracks_fbank.hpp.
 #pragma once
 
 // ---- kernel -------------------------------------------------------------------------------------------

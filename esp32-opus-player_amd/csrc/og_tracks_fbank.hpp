@@ -1,19 +1,15 @@
 // og_tracks_fbank.hpp -- Kaldi's fbank and MFCC features of the mono track at any rate (include/opusgpu.h, TRACK KALDI FEATURES): the
 // tables per parameter set, the kernel that turns packed int16 mono tracks into float32 feature tracks, its host side, and the
-// whole-file call that ends in it.  Included at the end of og_api.hip behind og_tracks_melspec.hpp, whose tile and span records, run
-// function, filterbank packer, store step and whole-file flow it shares (og_tracks_mel.hpp holds most of them), and in front of
+// whole-file call that ends in it.  Included at the end of og_api.hip behind og_feat.hpp, whose window stage, tile and span
+// records, run function, filterbank packer, record rules and whole-file flow it shares, and in front of
 // og_ms_tracks.hpp, which holds the multistream twin of the whole-file call.
 #pragma once
-#include <map>
-#include <memory>
-#include <mutex>
-#include <tuple>
 
 // ---- kernel -------------------------------------------------------------------------------------------
 // k_tracks_fbank: k_tracks_melspec's shape -- one workgroup per entry of a tile table, a tile T = 128, 64 or 32 consecutive frames of
 // one track, 32 per wave, the window in LDS cut by phase, both products on v_mfma_f32_32x32x2_f32 -- with Kaldi's computation:
-//   1. STAGE.  The tile's window is W = (T - 1) H + L samples and starts at the first frame's s: H * first with snip_edges, H * first
-//      + H / 2 - L / 2 without.  The track comes through aligned 16-byte loads of the buffer, nothing read behind the piece that
+//   1. STAGE (og_feat.hpp: feat_stage_window).  The tile's window is W = (T - 1) H + L samples and starts at the first frame's s:
+//      H * first with snip_edges, H * first + H / 2 - L / 2 without.  The track comes through aligned 16-byte loads of the buffer, nothing read behind the piece that
 //      holds its last sample.  Without snip_edges the places in front of the track and behind it are filled by Kaldi's reflection
 //      repeated until it lies inside (q mod 2n, mirrored in the upper half), from LDS where the source is in the window, else from
 //      the track.  With snip_edges no frame that exists reads such a place; they are zeroed for the frames of a working wave that
@@ -32,7 +28,7 @@
 //   4. POWER, MEL.  As k_tracks_melspec, over N / 2 bins (no Nyquist bin): only the blocks of 32 bins some band weights are walked.
 //   5. FLOOR, LOG, MFCC.  max(mel, floor) and logf in the accumulators.  For MFCC they ARE the B operand of a third product, c[q][f] +=
 //      (lift D)[q][j] g[j][f], with the lifted DCT packed like a filterbank whose "bins" are the bands: fused, in registers, no LDS.
-//   6. STORE.  k_tracks_melspec's, with the feature width (n_ceps, else n_mels).
+//   6. STORE.  k_tracks_melspec's, with the feature width (n_ceps, else n_mels): a copy, as is step 4 (og_feat.hpp says why).
 // No float atomics, no sum whose order depends on the launch: the same input gives the same bits.
 struct FbArgs {
     i32 L, H, n_mels, n_ceps;
@@ -47,7 +43,7 @@ struct FbArgs {
 __global__ void __launch_bounds__(256) k_tracks_fbank(const MelTile *__restrict__ tiles, const MelSpan *__restrict__ spans,
                                                       const i16 *__restrict__ in, const float2 *__restrict__ basis,
                                                       const float *__restrict__ fb, FbArgs a, float *__restrict__ out) {
-    extern __shared__ __align__(16) i16 lds[]; // the window by phase, W places (fbank_lds_bytes); afterwards a store area of [32][MEL_STG] floats per wave
+    extern __shared__ __align__(16) i16 lds[]; // the window by phase, W places (feat_window_lds_bytes); afterwards a store area of [32][MEL_STG] floats per wave
     const int tid = (int)threadIdx.x, nthr = (int)blockDim.x, lane = tid & 63, wave = tid >> 6;
     const int T = nthr >> 1, L = a.L, H = a.H;
     const MelTile tl = tiles[blockIdx.x];
@@ -60,43 +56,11 @@ __global__ void __launch_bounds__(256) k_tracks_fbank(const MelTile *__restrict_
     const int waves_on = (nf + 31) >> 5;                       // waves that have a frame
     const int W = (T - 1) * H + L;                             // the tile's window, which fixes the places
     const int Wuse = (32 * waves_on - 1) * H + L;              // what the working waves read of it
-    const int Qm = W / H, Qr = W % H;                          // row `ph` begins at ph * Qm + min(ph, Qr)
-    auto place = [=](int p) {
-        const int ph = p % H;
-        return ph * Qm + (ph < Qr ? ph : Qr) + p / H;
-    };
+    const FeatPhase ph(W, H);
 
-    // 1. the window -> LDS
-    const i16 *const trk = in + sp.in_offset;
-    const long long base = (long long)H * tl.first + (a.snip ? 0 : H / 2 - L / 2); // its first sample, counted from the track's
-    const long long qa = base < 0 ? 0 : base;                  // the track's samples inside what is used of it: [qa, qb)
-    const long long qb = n < base + Wuse ? n : base + Wuse;
-    for (long long k = (qa >> 3) + tid; 8 * k < qb; k += nthr) {
-        const uint4 v = *reinterpret_cast<const uint4 *>(trk + 8 * k);
-        const u32 w32[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int h = 0; h < 8; h++) {
-            const long long q = 8 * k + h;
-            if (q >= qa && q < qb) lds[place((int)(q - base))] = (i16)(w32[h >> 1] >> (16 * (h & 1)));
-        }
-    }
-    __syncthreads();
-    {
-        const int lo_n = base < 0 ? (int)-base : 0;                     // places in front of the track
-        const int hi_0 = qb > qa ? (int)(qb - base) : lo_n;             // the first place behind it
-        for (int x = tid; x < lo_n + (Wuse - hi_0); x += nthr) {
-            const int p = x < lo_n ? x : hi_0 + (x - lo_n);
-            i16 s = 0;
-            if (!a.snip) { // Kaldi's reflection, repeated: period 2n, the upper half mirrored (n > 0: the tile has a frame)
-                long long r = (base + p) % (2 * n);
-                if (r < 0) r += 2 * n;
-                if (r >= n) r = 2 * n - 1 - r;
-                s = r >= qa && r < qb ? lds[place((int)(r - base))] : trk[r]; // places of the track: not written here
-            }
-            lds[place(p)] = s;
-        }
-    }
-    __syncthreads();
+    // 1. the window -> LDS: its first sample, counted from the track's, is the first frame's
+    feat_stage_window(lds, ph, in + sp.in_offset, n, (long long)H * tl.first + (a.snip ? 0 : H / 2 - L / 2), Wuse, tid, nthr,
+                      FeatEdgeKaldi{a.snip});
 
     // 2. to 5. 32 frames per wave
     const int fl = lane & 31, kh = lane >> 5;
@@ -108,15 +72,14 @@ __global__ void __launch_bounds__(256) k_tracks_fbank(const MelTile *__restrict_
     if (wave < waves_on) {
         if (a.n_blocks > 0) { // (no kept block: no band has a weight, and mel stays 0)
             const int f = wave * 32 + fl; // the lane's frame in the tile
-            auto at = [=](int ph, int col) { return ph * Qm + (ph < Qr ? ph : Qr) + col; };
             int Lm = 1, sum = 0;
             if (a.remove_dc) {
                 Lm = L;
                 const int i0 = kh ? L >> 1 : 0, i1 = kh ? L : L >> 1;
-                int ph = i0 % H, col = i0 / H + f;
+                int row = i0 % H, col = i0 / H + f;
                 for (int i = i0; i < i1; i++) {
-                    sum += lds[at(ph, col)];
-                    if (++ph >= H) ph = 0, col++;
+                    sum += lds[ph.at(row, col)];
+                    if (++row >= H) row = 0, col++;
                 }
                 sum += __shfl_xor(sum, 32);
             }
@@ -125,7 +88,7 @@ __global__ void __launch_bounds__(256) k_tracks_fbank(const MelTile *__restrict_
             // the lane's walk: upwards from tap i0, downwards from tap L - 1 - i0, whose predecessor L - 2 - i0 is the first it reads
             const int i0 = kh * a.ksr, lim = kh ? a.half - a.ksr : a.ksr; // (half - ksr <= ksr)
             const int ip = i0 ? i0 - 1 : 0, jc = L - 1 - i0, jn = jc - 1;  // tap 0 is its own predecessor
-            const float dpu0 = dval(lds[at(ip % H, ip / H + f)]), dcd0 = dval(lds[at(jc % H, jc / H + f)]);
+            const float dpu0 = dval(lds[ph.at(ip % H, ip / H + f)]), dcd0 = dval(lds[ph.at(jc % H, jc / H + f)]);
             const int pa0 = i0 % H, ca0 = i0 / H + f;
             const int pb0 = jn < 0 ? H - 1 : jn % H, cb0 = (jn < 0 ? -1 : jn / H) + f; // (jn = -1 for L = 2 alone, where it is never read)
             // the basis comes a k-step at a time, 512 bytes per wave: requested two groups of 4 k-steps ahead of its use, as in
@@ -149,7 +112,7 @@ __global__ void __launch_bounds__(256) k_tracks_fbank(const MelTile *__restrict_
 #pragma unroll
                     for (int j = 0; j < 4; j++, ks++) {
                         int xu = 0, xd = 0;
-                        if (ks < lim) xu = lds[at(pa, ca)], xd = lds[at(pb, cb)];
+                        if (ks < lim) xu = lds[ph.at(pa, ca)], xd = lds[ph.at(pb, cb)];
                         if (++pa >= H) pa = 0, ca++;
                         if (--pb < 0) pb = H - 1, cb--;
                         const float du = dval(xu), dd = dval(xd);
@@ -346,13 +309,7 @@ static std::unique_ptr<FbankTables> fbank_tables_make(const opusgpu_fbank_params
         }
     }
     // what the kernel loads
-    const int nblk = (bins + 31) / 32;
-    for (int nb = 0; nb < nblk; nb++) {
-        bool any = false;
-        for (int j = 0; j < n_mels && !any; j++)
-            for (int k = 32 * nb; k < 32 * nb + 32 && k < bins && !any; k++) any = t->bank[(size_t)j * bins + k] != 0.f;
-        if (any) t->blocks.push_back(nb);
-    }
+    t->blocks = feat_kept_blocks(t->bank, bins, n_mels);
     const int half = (L + 1) / 2, ksr = (half + 1) / 2, ks4 = (ksr + 3) / 4 * 4;
     t->half = half, t->ksr = ksr, t->ks4 = ks4;
     t->basis.assign(t->blocks.size() * ks4 * 64 * 2, 0.f);
@@ -385,14 +342,9 @@ static std::unique_ptr<FbankTables> fbank_tables_make(const opusgpu_fbank_params
 
 // The tables of a parameter set that fbank_params_ok has passed; safe from any number of threads.
 static const FbankTables &fbank_tables(const opusgpu_fbank_params &p) {
-    static std::mutex mu;
-    static std::map<FbankKey, std::unique_ptr<FbankTables>> cache;
     const FbankKey key(p.sample_rate, p.frame_length, fbank_n_fft(p), p.n_mels, p.n_ceps, p.window, p.low_freq, fbank_high(p),
                        p.n_ceps ? p.cepstral_lifter : 0.f);
-    std::lock_guard<std::mutex> lock(mu);
-    auto it = cache.find(key);
-    if (it == cache.end()) it = cache.emplace(key, fbank_tables_make(p)).first;
-    return *it->second;
+    return feat_cached<FbankKey, FbankTables>(key, [&] { return fbank_tables_make(p); });
 }
 
 // ---- host side ----------------------------------------------------------------------------------------
@@ -400,23 +352,12 @@ static int64_t fbank_frames(const opusgpu_fbank_params &p, int64_t n) {
     if (p.snip_edges) return n < p.frame_length ? 0 : 1 + (n - p.frame_length) / p.frame_shift;
     return (n + p.frame_shift / 2) / p.frame_shift;
 }
-// The tile in frames: the largest of 128, 64, 32 whose window fits the kernel's LDS (32 does: fbank_params_ok).
-static int fbank_tile(const opusgpu_fbank_params &p) {
-    for (int T = 128; T > 32; T >>= 1)
-        if ((int64_t)(T - 1) * p.frame_shift + p.frame_length <= MS_MAXW) return T;
-    return 32;
-}
-// A launch's LDS: the tile's window as int16, and no less than the waves' store areas; at most 65,536 bytes (fbank_tile).
-static size_t fbank_lds_bytes(const opusgpu_fbank_params &p, int T) {
-    const size_t window = ((size_t)(T - 1) * p.frame_shift + p.frame_length) * 2, store = (size_t)(T / 32) * 32 * MEL_STG * 4;
-    return ((window > store ? window : store) + 15) / 16 * 16;
-}
 
-// k_tracks_fbank over n tracks (og_tracks_mel.hpp: tracks_feature_run).
+// k_tracks_fbank over n tracks (og_feat.hpp: tracks_feature_run).
 static int tracks_fbank_run(int device, hipStream_t s, int n_tracks, const opusgpu_mel_span *spans, const void *d_in,
                             const opusgpu_fbank_params *params, void *d_out, const TrackFail &hip_failed) {
     if (!fbank_params_ok(params)) return OPUSGPU_BAD_ARG;
-    const int T = fbank_tile(*params);
+    const int T = feat_dense_tile(params->frame_shift, params->frame_length);
     const FbankTables *tab = nullptr;
     return tracks_feature_run(
         device, s, n_tracks, spans, d_in, d_out, T, 0x7fffffff - T, [&](int64_t n) { return fbank_frames(*params, n); },
@@ -431,33 +372,25 @@ static int tracks_fbank_run(int device, hipStream_t s, int n_tracks, const opusg
             a.power = params->power, a.log = params->log, a.snip = params->snip_edges, a.remove_dc = params->remove_dc;
             a.frames_major = params->layout == OPUSGPU_MEL_FRAMES_MAJOR, a.floor = params->floor, a.preemph = params->preemphasis;
             std::copy(std::begin(tab->mask), std::end(tab->mask), a.mask);
-            hipLaunchKernelGGL(k_tracks_fbank, dim3(n_tiles), dim3(2 * T), fbank_lds_bytes(*params, T), s, d_tiles, d_spans, (const i16 *)d_in,
-                               d_basis, d_fb, a, (float *)d_out);
+            hipLaunchKernelGGL(k_tracks_fbank, dim3(n_tiles), dim3(2 * T),
+                               feat_window_lds_bytes(params->frame_shift, params->frame_length, T, true), s, d_tiles, d_spans,
+                               (const i16 *)d_in, d_basis, d_fb, a, (float *)d_out);
         },
         hip_failed);
-}
-
-static int64_t fbank_plane(const opusgpu_fbank_params &p, int64_t planned_48k, int up, int down) {
-    return rs_round64(fbank_frames(p, (planned_48k * up + down - 1) / down));
 }
 
 // opusgpu_files_decode_fbank and its multistream twin (og_ms_tracks.hpp): files_feature_run at the record's rate.
 static int files_fbank_run(const FilesOwner &own, int rate, int up, int down, int mono, const opusgpu_mix_matrix *mix,
                            const opusgpu_fbank_params *params, const float *scale, void *d_out, int64_t *feat_offsets, int64_t *frames_out,
                            int64_t *track_lengths_out, int32_t *status_out) {
-    FeatFlow flow;
-    flow.sample_rate = fbank_params_ok(params) ? (int)params->sample_rate : 0;
-    flow.scratch_failed = "hipMalloc(fbank scratch)";
-    flow.plane = [=](int64_t planned, int u, int d) { return fbank_plane(*params, planned, u, d); };
-    flow.frames = [=](int64_t len) { return fbank_frames(*params, len); };
-    flow.layout = [=](int n, const int64_t *planned, int u, int d, int64_t *feat) {
-        return opusgpu_fbank_layout(n, planned, u, d, params, feat);
-    };
-    if (flow.sample_rate)
-        flow.width = params->n_ceps > 0 ? params->n_ceps : params->n_mels, flow.frames_major = params->layout == OPUSGPU_MEL_FRAMES_MAJOR;
-    flow.run = [&](int n, const opusgpu_mel_span *spans, const void *d_in, void *d_feat) {
-        return tracks_fbank_run(own.device, own.stream, n, spans, d_in, params, d_feat, own.hip_failed);
-    };
+    const bool ok = fbank_params_ok(params);
+    const FeatFlow flow = feat_record_flow(
+        ok, ok ? (int)params->sample_rate : 0, ok ? fbank_width(*params) : 0, ok && params->layout == OPUSGPU_MEL_FRAMES_MAJOR,
+        "hipMalloc(fbank scratch)", [=](int64_t len) { return fbank_frames(*params, len); },
+        [=](int n, const int64_t *planned, int u, int d, int64_t *feat) { return opusgpu_fbank_layout(n, planned, u, d, params, feat); },
+        [&own, params](int n, const opusgpu_mel_span *spans, const void *d_in, void *d_feat) {
+            return tracks_fbank_run(own.device, own.stream, n, spans, d_in, params, d_feat, own.hip_failed);
+        });
     return files_feature_run(own, rate, up, down, mono, mix, scale, d_out, feat_offsets, frames_out, track_lengths_out, status_out, flow);
 }
 
@@ -485,14 +418,8 @@ int opusgpu_fbank_dct(const opusgpu_fbank_params *p, const float **d) {
 }
 
 int64_t opusgpu_fbank_layout(int n, const int64_t *planned_48k_samples, int up, int down, const opusgpu_fbank_params *p, int64_t *feat_offsets) {
-    if (!fbank_params_ok(p) || !spec_ratio_ok(up, down) || n < 0 || (n && !planned_48k_samples)) return OPUSGPU_BAD_ARG;
-    int64_t at = 0;
-    for (int i = 0; i < n; i++) {
-        if (planned_48k_samples[i] < 0 || planned_48k_samples[i] > INT64_MAX / 65536) return OPUSGPU_BAD_ARG;
-        if (feat_offsets) feat_offsets[i] = at;
-        at += fbank_width(*p) * fbank_plane(*p, planned_48k_samples[i], up, down);
-    }
-    return at;
+    if (!fbank_params_ok(p)) return OPUSGPU_BAD_ARG;
+    return feat_grid_layout(n, planned_48k_samples, up, down, fbank_width(*p), [=](int64_t len) { return fbank_frames(*p, len); }, feat_offsets);
 }
 
 int opusgpu_tracks_fbank_device(opusgpu_ctx *ctx, int n_tracks, const opusgpu_mel_span *spans, const void *d_in_mono,

@@ -1,7 +1,7 @@
 // og_tracks_fft.hpp -- TRACK STFT by FFT (include/opusgpu.h, TRACK STFT, OPUSGPU_STFT_ALGO_FFT): the window and twiddle tables per
 // (n_fft, win_length), the kernel that turns packed int16 mono tracks into float32 spectrogram tracks for n_fft = 64 .. 8192, and its
-// host side.  Included in og_api.hip behind og_tracks_stft.hpp, which holds the record's rules, declares fft_tile and tracks_fft_run
-// and sends every FFT record here from tracks_stft_run: the whole-file calls, the layout and STFT BATCHES are that header's.
+// host side.  Included by og_tracks_stft.hpp behind the record's rules, which this header reads, and in front of tracks_stft_run, which
+// sends every FFT record here: the whole-file calls, the layout and STFT BATCHES are that header's.
 #pragma once
 
 // ---- kernel -------------------------------------------------------------------------------------------
@@ -179,12 +179,7 @@ struct FftTables {
 // The tables of an FFT record that stft_params_ok or spec_params_ok has passed, by its n_fft and window length (never 0 here); safe
 // from any number of threads.  TRACK SPECTROGRAMS' FFT records take theirs from this cache too (og_tracks_melfft.hpp).
 static const FftTables &fft_tables(int n_fft, int win) {
-    static std::mutex mu;
-    static std::map<std::pair<int, int>, std::unique_ptr<FftTables>> cache;
-    const std::pair<int, int> key(n_fft, win);
-    std::lock_guard<std::mutex> lock(mu);
-    auto it = cache.find(key);
-    if (it == cache.end()) {
+    return feat_cached<std::pair<int, int>, FftTables>({n_fft, win}, [&] {
         const double pi = 3.14159265358979323846;
         std::unique_ptr<FftTables> t(new FftTables);
         const int left = (n_fft - win) / 2;
@@ -196,9 +191,8 @@ static const FftTables &fft_tables(int n_fft, int win) {
             const double ang = 2.0 * pi * j / (double)n_fft;
             t->twiddle[2 * (size_t)j] = (float)std::cos(ang), t->twiddle[2 * (size_t)j + 1] = (float)std::sin(ang);
         }
-        it = cache.emplace(key, std::move(t)).first;
-    }
-    return *it->second;
+        return t;
+    });
 }
 
 // ---- host side ----------------------------------------------------------------------------------------
@@ -209,7 +203,7 @@ static size_t fft_lds_bytes(const opusgpu_stft_params &p) {
     return (size_t)(256 / P) * (size_t)(M + (M >> 5)) * sizeof(float2);
 }
 
-// k_tracks_fft over n tracks (og_tracks_mel.hpp: tracks_feature_run; the frames' bound is tracks_stft_run's).  hop needs no bound
+// k_tracks_fft over n tracks (og_feat.hpp: tracks_feature_run; the frames' bound is tracks_stft_run's).  hop needs no bound
 // beyond [1, n_fft]: the kernel keeps no window in LDS and forms hop * frame in 64 bits.
 static int tracks_fft_run(int device, hipStream_t s, int n_tracks, const opusgpu_mel_span *spans, const void *d_in,
                           const opusgpu_stft_params *params, void *d_out, const TrackFail &hip_failed) {

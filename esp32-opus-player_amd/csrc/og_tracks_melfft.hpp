@@ -1,9 +1,9 @@
 // og_tracks_melfft.hpp -- TRACK SPECTROGRAMS by FFT (include/opusgpu.h, TRACK SPECTROGRAMS, OPUSGPU_SPEC_ALGO_FFT): the tables of an
 // FFT record -- the filterbank, its sparse form, and the window and twiddles that TRACK STFT's FFT records use --, the kernel that
-// turns packed int16 mono tracks into float32 mel tracks for n_fft = 64 .. 8192, and its host side.  Included in og_api.hip behind
-// og_tracks_fft.hpp, whose load, passes and split it calls and whose table cache it shares; og_tracks_melspec.hpp holds the record's
-// rules, declares melfft_tile, melfft_bank and tracks_melfft_run and sends every FFT record here from tracks_melspec_run: the
-// whole-file calls, the layout and FEATURE BATCHES are that header's.
+// turns packed int16 mono tracks into float32 mel tracks for n_fft = 64 .. 8192, and its host side.  Included by
+// og_tracks_melspec.hpp behind the record's rules, which this header reads, and in front of tracks_melspec_run, which sends every FFT
+// record here; behind og_tracks_fft.hpp, whose load, passes and split it calls and whose table cache it shares.  The whole-file
+// calls, the layout and FEATURE BATCHES are og_tracks_melspec.hpp's.
 #pragma once
 
 // ---- kernel -------------------------------------------------------------------------------------------
@@ -158,13 +158,8 @@ struct MelFftTables {
 
 // The tables of an FFT record that spec_params_ok has passed; safe from any number of threads.
 static const MelFftTables &melfft_tables(const opusgpu_spec_params &p) {
-    static std::mutex mu;
-    static std::map<SpecKey, std::unique_ptr<MelFftTables>> cache;
-    const SpecKey key(p.sample_rate, p.n_fft, spec_win(p), p.n_mels, p.mel_scale, p.norm, p.fmin, p.fmax);
-    const FftTables &ft = fft_tables(p.n_fft, spec_win(p));
-    std::lock_guard<std::mutex> lock(mu);
-    auto it = cache.find(key);
-    if (it == cache.end()) {
+    const FftTables &ft = fft_tables(p.n_fft, spec_win(p)); // (taken in front of this cache's lock, not under it)
+    return feat_cached<SpecKey, MelFftTables>(spec_key(p), [&] {
         std::unique_ptr<MelFftTables> t(new MelFftTables);
         const int bins = p.n_fft / 2 + 1, n_mels = p.n_mels;
         mel_bank_make((double)p.sample_rate / p.n_fft, bins, n_mels, p.mel_scale == OPUSGPU_SPEC_HTK, p.norm == OPUSGPU_SPEC_NORM_SLANEY, p.fmin,
@@ -187,11 +182,9 @@ static const MelFftTables &melfft_tables(const opusgpu_spec_params &p) {
         t->bands_weights.resize(recs.size() + runs.size());
         std::memcpy(t->bands_weights.data(), recs.data(), recs.size() * sizeof(int32_t));
         std::copy(runs.begin(), runs.end(), t->bands_weights.begin() + (ptrdiff_t)recs.size());
-        it = cache.emplace(key, std::move(t)).first;
-    }
-    return *it->second;
+        return t;
+    });
 }
-static const std::vector<float> &melfft_bank(const opusgpu_spec_params &p) { return melfft_tables(p).bank; }
 
 // ---- host side ----------------------------------------------------------------------------------------
 // The tile in frames: the larger of 32 and 8192 / n_fft, a multiple of the store area's 32 frames and of the frames in flight.
@@ -205,7 +198,7 @@ static size_t melfft_lds_bytes(const opusgpu_spec_params &p) {
     return (size_t)melfft_in_flight(p) * (size_t)(M + (M >> 5)) * sizeof(float2) + (size_t)p.n_mels * MEL_STG * sizeof(float);
 }
 
-// k_tracks_melfft over n tracks (og_tracks_mel.hpp: tracks_feature_run; the frames' bound is tracks_melspec_run's).  The kernel's
+// k_tracks_melfft over n tracks (og_feat.hpp: tracks_feature_run; the frames' bound is tracks_melspec_run's).  The kernel's
 // four tables travel as tracks_feature_run's two: twiddles and window in the one, band records and weights in the other.
 static int tracks_melfft_run(int device, hipStream_t s, int n_tracks, const opusgpu_mel_span *spans, const void *d_in,
                              const opusgpu_spec_params *params, void *d_out, const TrackFail &hip_failed) {

@@ -1,28 +1,58 @@
 // og_tracks_melspec.hpp -- mel spectrograms of the mono track at any rate, n_fft and hop (include/opusgpu.h, TRACK SPECTROGRAMS): the
-// tables per parameter set, the kernel that turns packed int16 mono tracks into float32 feature tracks, its host side, and the
-// whole-file call that ends in it.  Included at the end of og_api.hip behind og_tracks_mel.hpp, whose table builders
-// and packers, span record, run function and whole-file flow it shares, and in front of og_ms_tracks.hpp, which holds the multistream
-// twin of the whole-file call.  A record whose algorithm word is OPUSGPU_SPEC_ALGO_FFT passes the rules here and runs in
-// og_tracks_melfft.hpp (k_tracks_melfft), which is included behind og_tracks_fft.hpp and declared below.
+// record's rules, the tables per parameter set, the dense kernel that turns packed int16 mono tracks into float32 feature tracks, its
+// host side, the dispatch on the record's algorithm word and the whole-file call that ends in it.  Included at the end of og_api.hip
+// behind og_feat.hpp, whose window stage, table builders and packers, record rules, span record, run function and whole-file
+// flow it shares, and behind og_tracks_stft.hpp (fft_tables), and in front of og_ms_tracks.hpp, which holds the
+// multistream twin of the whole-file call.  og_tracks_melfft.hpp, included below between the rules it reads and the dispatch that
+// sends it every FFT record, holds the second algorithm of the record (k_tracks_melfft, OPUSGPU_SPEC_ALGO_FFT).
 #pragma once
-#include <map>
-#include <memory>
-#include <mutex>
-#include <tuple>
+
+// ---- the record's rules -------------------------------------------------------------------------------
+typedef std::tuple<int, int, int, int, int, int, float, float> SpecKey; // sample_rate, n_fft, win, n_mels, mel_scale, norm, fmin, fmax
+
+static int spec_win(const opusgpu_spec_params &p) { return p.win_length ? p.win_length : p.n_fft; }
+static SpecKey spec_key(const opusgpu_spec_params &p) {
+    return SpecKey(p.sample_rate, p.n_fft, spec_win(p), p.n_mels, p.mel_scale, p.norm, p.fmin, p.fmax);
+}
+
+// The record's algorithm is reserved[1]: OPUSGPU_SPEC_ALGO_DENSE (k_tracks_melspec, below) or OPUSGPU_SPEC_ALGO_FFT (k_tracks_melfft,
+// og_tracks_melfft.hpp, which holds everything the FFT records alone need: they build no Wc / Ws).
+static bool spec_is_fft(const opusgpu_spec_params &p) { return p.reserved[1] == OPUSGPU_SPEC_ALGO_FFT; }
+
+static bool spec_params_ok(const opusgpu_spec_params *p) {
+    if (!p) return false;
+    if (p->reserved[0] || (p->reserved[1] != OPUSGPU_SPEC_ALGO_DENSE && p->reserved[1] != OPUSGPU_SPEC_ALGO_FFT)) return false;
+    if (!dft_shape_ok(p->n_fft, p->hop, p->win_length, spec_is_fft(*p))) return false;
+    if (p->n_mels < 1 || p->n_mels > 128) return false;
+    if (p->mel_scale != OPUSGPU_SPEC_SLANEY && p->mel_scale != OPUSGPU_SPEC_HTK) return false;
+    if (p->norm != OPUSGPU_SPEC_NORM_SLANEY && p->norm != OPUSGPU_SPEC_NORM_NONE) return false;
+    if (p->power != 1 && p->power != 2) return false;
+    if (p->log != OPUSGPU_SPEC_LOG_NONE && p->log != OPUSGPU_SPEC_LOG10 && p->log != OPUSGPU_SPEC_LN) return false;
+    if (p->frames != OPUSGPU_SPEC_FRAMES_TORCH && p->frames != OPUSGPU_SPEC_FRAMES_WHISPER) return false;
+    if (p->layout != OPUSGPU_MEL_BANDS_MAJOR && p->layout != OPUSGPU_MEL_FRAMES_MAJOR) return false;
+    if (p->sample_rate < 1 || p->sample_rate > 1048576) return false;
+    if (!(p->fmin >= 0.f) || !(p->fmin < p->fmax) || !((double)p->fmax <= p->sample_rate / 2.0)) return false;
+    if (!std::isfinite(p->floor) || p->floor < 0.f || (p->log != OPUSGPU_SPEC_LOG_NONE && !(p->floor > 0.f))) return false;
+    return true;
+}
+static_assert(sizeof(opusgpu_spec_params) == 64, "spec params layout");
+
+static int64_t spec_frames(const opusgpu_spec_params &p, int64_t n) {
+    return feat_frames_centered(p.frames == OPUSGPU_SPEC_FRAMES_WHISPER, p.hop, n);
+}
+
+#include "og_tracks_melfft.hpp" // k_tracks_melfft, melfft_tables, melfft_tile, tracks_melfft_run
 
 // ---- kernel -------------------------------------------------------------------------------------------
 // k_tracks_melspec: k_tracks_mel (og_tracks_mel.hpp, whose head comment says what the four steps are) with its constants as
 // arguments.  One workgroup per entry of a tile table built on the host, a tile being T = 128, 64 or 32 consecutive frames of one
 // track, 32 per wave: the workgroup has T / 32 waves.  What differs:
-//   1. STAGE.  The tile's window -- W = (T - 1) hop + n_fft samples, the first of them sample hop * first - n_fft / 2 of the track
-//      -- lies in LDS cut by phase: place p is at row p % hop, column p / hop, the rows packed without room between them (the first
-//      W % hop rows hold W / hop + 1 places, the others W / hop), so a window of 32,768 samples takes 65,536 bytes whatever the hop.
-//      Neither the hop nor the window's first sample need be a multiple of 8: the track comes through aligned 16-byte loads of the
-//      BUFFER, one piece per lane, and every sample of a piece finds its own place (a piece does not stay in one row).  Nothing is
-//      read behind the piece that holds the track's last sample.  The places in front of the track and behind it are then filled by
-//      the reflection rule from LDS -- or, where the reflected sample lies in front of the window (the last frame of F = n / hop + 1
-//      when hop divides n and that frame is its tile's first), from the track itself --, 0 outside the track.  Only the places that
-//      the tile's WORKING waves read are filled.
+//   1. STAGE (og_feat.hpp: feat_stage_window).  The tile's window -- W = (T - 1) hop + n_fft samples, the first of them sample hop *
+//      first - n_fft / 2 of the track -- lies in LDS cut by phase: place p is at row p % hop, column p / hop, the rows packed without
+//      room between them, so a window of 32,768 samples takes 65,536 bytes whatever the hop.  The places in front of the track and
+//      behind it are filled by the reflection rule from LDS -- or, where the reflected sample lies in front of the window (the last
+//      frame of F = n / hop + 1 when hop divides n and that frame is its tile's first), from the track itself --, 0 outside the
+//      track.  Only the places that the tile's WORKING waves read are filled.
 //   2. DFT.  The fold of k_tracks_mel: taps 1 .. n_fft / 2 of u_i = x_i + x_{n_fft - i} and v_i = x_i - x_{n_fft - i} (w[0] = 0 and
 //      w[i] = w[n_fft - i] for every window of the section), row n_fft / 2 halved for u and zero for v, n_fft / 4 k-steps of two
 //      taps.  A lane walks its two taps' (row, column) by additions: there is no division in the loop.  Only the blocks of 32 bins
@@ -32,9 +62,8 @@
 //      bands, those without a weight in the bin block skipped (4 mask bits per kept bin block, with the kernel's arguments).
 //   4. STORE.  max(mel, floor), its log10f or logf or neither, through LDS into the destination's order and out in aligned 16-byte
 //      pieces where a piece is whole and aligned (frames-major rows of an n_mels that is no multiple of 4 are not: element stores).
+//   Steps 3 and 4 are this kernel's own text and k_tracks_fbank's a copy of it: og_feat.hpp says why they are no shared functions.
 // No float atomics, no sum whose order depends on the launch: the same input gives the same bits.
-constexpr int MS_MAXW = 32768;      // samples of the largest window: 65,536 bytes of LDS, which a launch asks for by its own window
-constexpr int MS_MAXBLK = 33;       // blocks of 32 bins at n_fft 2048
 struct MsArgs {
     i32 n_fft, hop, n_mels;
     i32 n_blocks;                   // kept blocks of 32 bins
@@ -46,7 +75,7 @@ struct MsArgs {
 __global__ void __launch_bounds__(256) k_tracks_melspec(const MelTile *__restrict__ tiles, const MelSpan *__restrict__ spans,
                                                         const i16 *__restrict__ in, const float2 *__restrict__ basis,
                                                         const float *__restrict__ fb, MsArgs a, float *__restrict__ out) {
-    extern __shared__ __align__(16) i16 lds[]; // the window by phase, W places (spec_lds_bytes); afterwards a store area of [32][MEL_STG] floats per wave
+    extern __shared__ __align__(16) i16 lds[]; // the window by phase, W places (feat_window_lds_bytes); afterwards a store area of [32][MEL_STG] floats per wave
     const int tid = (int)threadIdx.x, nthr = (int)blockDim.x, lane = tid & 63, wave = tid >> 6;
     const int T = nthr >> 1, N = a.n_fft, H = a.hop;
     const MelTile tl = tiles[blockIdx.x];
@@ -59,40 +88,10 @@ __global__ void __launch_bounds__(256) k_tracks_melspec(const MelTile *__restric
     const int waves_on = (nf + 31) >> 5;                       // waves that have a frame
     const int W = (T - 1) * H + N;                             // the tile's window, which fixes the places
     const int Wuse = (32 * waves_on - 1) * H + N;              // what the working waves read of it
-    const int Qm = W / H, Qr = W % H;                          // row `ph` begins at ph * Qm + min(ph, Qr)
-    auto place = [=](int p) {
-        const int ph = p % H;
-        return ph * Qm + (ph < Qr ? ph : Qr) + p / H;
-    };
+    const FeatPhase ph(W, H);
 
-    // 1. the window -> LDS
-    const i16 *const trk = in + sp.in_offset;
-    const long long base = (long long)H * tl.first - N / 2;    // its first sample, counted from the track's
-    const long long qa = base < 0 ? 0 : base;                  // the track's samples inside what is used of it: [qa, qb)
-    const long long qb = n < base + Wuse ? n : base + Wuse;
-    for (long long k = (qa >> 3) + tid; 8 * k < qb; k += nthr) {
-        const uint4 v = *reinterpret_cast<const uint4 *>(trk + 8 * k);
-        const u32 w32[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int h = 0; h < 8; h++) {
-            const long long q = 8 * k + h;
-            if (q >= qa && q < qb) lds[place((int)(q - base))] = (i16)(w32[h >> 1] >> (16 * (h & 1)));
-        }
-    }
-    __syncthreads();
-    {
-        const int lo_n = base < 0 ? (int)-base : 0;                     // places in front of the track
-        const int hi_0 = n - base < Wuse ? (int)(n - base) : Wuse;      // the first place behind it
-        for (int x = tid; x < lo_n + (Wuse - hi_0); x += nthr) {
-            const int p = x < lo_n ? x : hi_0 + (x - lo_n);
-            const long long q = base + p;
-            const long long r = q < 0 ? -q : 2 * (n - 1) - q;           // reflected once
-            i16 s = 0;
-            if (r >= 0 && r < n) s = r >= qa && r < qb ? lds[place((int)(r - base))] : trk[r]; // places of the track: not written here
-            lds[place(p)] = s;
-        }
-    }
-    __syncthreads();
+    // 1. the window -> LDS: its first sample, counted from the track's, is hop * first - n_fft / 2
+    feat_stage_window(lds, ph, in + sp.in_offset, n, (long long)H * tl.first - N / 2, Wuse, tid, nthr, FeatEdgeTorch());
 
     // 2. and 3. 32 frames per wave: the kept bin blocks, then the bands
     const int fl = lane & 31, kh = lane >> 5;
@@ -109,6 +108,7 @@ __global__ void __launch_bounds__(256) k_tracks_melspec(const MelTile *__restric
         const int f = wave * 32 + fl;                    // the lane's frame in the tile
         const int pa0 = ia0 < 0 ? H - 1 - ((-ia0 - 1) % H) : ia0 % H, ca0 = ia0 < 0 ? -1 - (-ia0 - 1) / H : ia0 / H;
         const int pb0 = ib0 % H, cb0 = ib0 / H;
+        const int Qm = ph.Qm, Qr = ph.Qr;
         // the basis comes a k-step at a time, 512 bytes per wave, from L2 at best: requested two groups of 4 k-steps ahead of its
         // use (the table is one run over all kept blocks), or every k-step would wait out a load with nothing to hide it behind
         const int G = KS >> 2, GT = a.n_blocks * G;
@@ -132,8 +132,8 @@ __global__ void __launch_bounds__(256) k_tracks_melspec(const MelTile *__restric
                     if (pa >= H) pa -= H, ca++;
                     pb -= m2, cb -= d2;
                     if (pb < 0) pb += H, cb--;
-                    const float xa = __fmul_rn((float)lds[pa * Qm + (pa < Qr ? pa : Qr) + ca], scale);
-                    const float xb = __fmul_rn((float)lds[pb * Qm + (pb < Qr ? pb : Qr) + cb], scale);
+                    const float xa = __fmul_rn((float)lds[pa * Qm + (pa < Qr ? pa : Qr) + ca], scale); // (ph.at(pa, ca), written out:
+                    const float xb = __fmul_rn((float)lds[pb * Qm + (pb < Qr ? pb : Qr) + cb], scale); // the generated code stays what it was)
                     re = __builtin_amdgcn_mfma_f32_32x32x2f32(w0[j].x, xa + xb, re, 0, 0, 0);
                     im = __builtin_amdgcn_mfma_f32_32x32x2f32(w0[j].y, xa - xb, im, 0, 0, 0);
                 }
@@ -223,38 +223,6 @@ struct SpecTables {
     std::vector<float> fb;          // [kept block][4][16][64 lanes]: band 32 mm + (lane & 31), bin 32 nb + 8 (r >> 2) + 4 (lane >> 5) + (r & 3)
     u8 mask[MS_MAXBLK + 3] = {};
 };
-typedef std::tuple<int, int, int, int, int, int, float, float> SpecKey; // sample_rate, n_fft, win, n_mels, mel_scale, norm, fmin, fmax
-
-static int spec_win(const opusgpu_spec_params &p) { return p.win_length ? p.win_length : p.n_fft; }
-
-// The record's algorithm is reserved[1]: OPUSGPU_SPEC_ALGO_DENSE (k_tracks_melspec, above) or OPUSGPU_SPEC_ALGO_FFT (k_tracks_melfft,
-// og_tracks_melfft.hpp, which holds everything the FFT records alone need: they build no Wc / Ws).
-static bool spec_is_fft(const opusgpu_spec_params &p) { return p.reserved[1] == OPUSGPU_SPEC_ALGO_FFT; }
-
-static bool spec_params_ok(const opusgpu_spec_params *p) {
-    if (!p) return false;
-    if (p->reserved[0] || (p->reserved[1] != OPUSGPU_SPEC_ALGO_DENSE && p->reserved[1] != OPUSGPU_SPEC_ALGO_FFT)) return false;
-    if (spec_is_fft(*p)) {
-        if (p->n_fft < 64 || p->n_fft > 8192 || (p->n_fft & (p->n_fft - 1))) return false;
-        if (p->hop < 1 || p->hop > p->n_fft) return false;
-    } else {
-        if (p->n_fft < 64 || p->n_fft > 2048 || p->n_fft % 16) return false;
-        if (p->hop < 1 || p->hop > p->n_fft || 31 * p->hop + p->n_fft > MS_MAXW) return false;
-    }
-    if (p->win_length && (p->win_length < 16 || p->win_length > p->n_fft || p->win_length % 2)) return false;
-    if (p->n_mels < 1 || p->n_mels > 128) return false;
-    if (p->mel_scale != OPUSGPU_SPEC_SLANEY && p->mel_scale != OPUSGPU_SPEC_HTK) return false;
-    if (p->norm != OPUSGPU_SPEC_NORM_SLANEY && p->norm != OPUSGPU_SPEC_NORM_NONE) return false;
-    if (p->power != 1 && p->power != 2) return false;
-    if (p->log != OPUSGPU_SPEC_LOG_NONE && p->log != OPUSGPU_SPEC_LOG10 && p->log != OPUSGPU_SPEC_LN) return false;
-    if (p->frames != OPUSGPU_SPEC_FRAMES_TORCH && p->frames != OPUSGPU_SPEC_FRAMES_WHISPER) return false;
-    if (p->layout != OPUSGPU_MEL_BANDS_MAJOR && p->layout != OPUSGPU_MEL_FRAMES_MAJOR) return false;
-    if (p->sample_rate < 1 || p->sample_rate > 1048576) return false;
-    if (!(p->fmin >= 0.f) || !(p->fmin < p->fmax) || !((double)p->fmax <= p->sample_rate / 2.0)) return false;
-    if (!std::isfinite(p->floor) || p->floor < 0.f || (p->log != OPUSGPU_SPEC_LOG_NONE && !(p->floor > 0.f))) return false;
-    return true;
-}
-static_assert(sizeof(opusgpu_spec_params) == 64, "spec params layout");
 
 static std::unique_ptr<SpecTables> spec_tables_make(const opusgpu_spec_params &p) {
     std::unique_ptr<SpecTables> t(new SpecTables);
@@ -263,13 +231,7 @@ static std::unique_ptr<SpecTables> spec_tables_make(const opusgpu_spec_params &p
     mel_basis_make(N, spec_win(p), t->wc, t->ws);
     mel_bank_make((double)p.sample_rate / N, bins, n_mels, p.mel_scale == OPUSGPU_SPEC_HTK, p.norm == OPUSGPU_SPEC_NORM_SLANEY, p.fmin, p.fmax,
                   t->bank);
-    const int nblk = (bins + 31) / 32;
-    for (int nb = 0; nb < nblk; nb++) {
-        bool any = false;
-        for (int j = 0; j < n_mels && !any; j++)
-            for (int k = 32 * nb; k < 32 * nb + 32 && k < bins && !any; k++) any = t->bank[(size_t)j * bins + k] != 0.f;
-        if (any) t->blocks.push_back(nb);
-    }
+    t->blocks = feat_kept_blocks(t->bank, bins, n_mels);
     t->basis = feat_pack_basis(t->wc, t->ws, N, t->blocks);
     t->fb = feat_pack_fb(t->bank, bins, n_mels, t->blocks, 4, [&](int b, int mm) { t->mask[b] |= (u8)(1u << mm); });
     return t;
@@ -277,39 +239,15 @@ static std::unique_ptr<SpecTables> spec_tables_make(const opusgpu_spec_params &p
 
 // The tables of a dense parameter set that spec_params_ok has passed; safe from any number of threads.
 static const SpecTables &spec_tables(const opusgpu_spec_params &p) {
-    static std::mutex mu;
-    static std::map<SpecKey, std::unique_ptr<SpecTables>> cache;
-    const SpecKey key(p.sample_rate, p.n_fft, spec_win(p), p.n_mels, p.mel_scale, p.norm, p.fmin, p.fmax);
-    std::lock_guard<std::mutex> lock(mu);
-    auto it = cache.find(key);
-    if (it == cache.end()) it = cache.emplace(key, spec_tables_make(p)).first;
-    return *it->second;
+    return feat_cached<SpecKey, SpecTables>(spec_key(p), [&] { return spec_tables_make(p); });
 }
 
 // ---- host side ----------------------------------------------------------------------------------------
-static int64_t spec_frames(const opusgpu_spec_params &p, int64_t n) {
-    return p.frames == OPUSGPU_SPEC_FRAMES_WHISPER ? n / p.hop : n ? n / p.hop + 1 : 0;
-}
-// og_tracks_melfft.hpp: the tile, the filterbank and the run of an FFT record
-static int melfft_tile(const opusgpu_spec_params &p);
-static const std::vector<float> &melfft_bank(const opusgpu_spec_params &p);
-static int tracks_melfft_run(int device, hipStream_t s, int n_tracks, const opusgpu_mel_span *spans, const void *d_in,
-                             const opusgpu_spec_params *params, void *d_out, const TrackFail &hip_failed);
-// The tile in frames: the largest of 128, 64, 32 whose window fits the kernel's LDS (32 does: spec_params_ok).
-static int spec_tile(const opusgpu_spec_params &p) {
-    if (spec_is_fft(p)) return melfft_tile(p);
-    for (int T = 128; T > 32; T >>= 1)
-        if ((T - 1) * p.hop + p.n_fft <= MS_MAXW) return T;
-    return 32;
-}
+// The tile in frames: of a dense record feat_dense_tile's, of an FFT record melfft_tile's.
+static int spec_tile(const opusgpu_spec_params &p) { return spec_is_fft(p) ? melfft_tile(p) : feat_dense_tile(p.hop, p.n_fft); }
 
-// A launch's LDS: the tile's window as int16, and no less than the waves' store areas; at most 65,536 bytes (spec_tile).
-static size_t spec_lds_bytes(const opusgpu_spec_params &p, int T) {
-    const size_t window = ((size_t)(T - 1) * p.hop + p.n_fft) * 2, store = (size_t)(T / 32) * 32 * MEL_STG * 4;
-    return ((window > store ? window : store) + 15) / 16 * 16;
-}
-
-// k_tracks_melspec over n tracks (og_tracks_mel.hpp: tracks_feature_run, which also says why the frames' bound differs).
+// k_tracks_melspec, or for an FFT record k_tracks_melfft, over n tracks (og_feat.hpp: tracks_feature_run; og_tracks_mel.hpp says why
+// the frames' bound differs from tracks_mel_run's).
 static int tracks_melspec_run(int device, hipStream_t s, int n_tracks, const opusgpu_mel_span *spans, const void *d_in,
                               const opusgpu_spec_params *params, void *d_out, const TrackFail &hip_failed) {
     if (!spec_params_ok(params)) return OPUSGPU_BAD_ARG;
@@ -328,33 +266,24 @@ static int tracks_melspec_run(int device, hipStream_t s, int n_tracks, const opu
             a.power = params->power, a.log = params->log, a.whisper_frames = params->frames == OPUSGPU_SPEC_FRAMES_WHISPER;
             a.frames_major = params->layout == OPUSGPU_MEL_FRAMES_MAJOR, a.floor = params->floor;
             std::copy(std::begin(tab->mask), std::end(tab->mask), a.mask);
-            hipLaunchKernelGGL(k_tracks_melspec, dim3(n_tiles), dim3(2 * T), spec_lds_bytes(*params, T), s, d_tiles, d_spans, (const i16 *)d_in,
-                               d_basis, d_fb, a, (float *)d_out);
+            hipLaunchKernelGGL(k_tracks_melspec, dim3(n_tiles), dim3(2 * T), feat_window_lds_bytes(params->hop, params->n_fft, T, true), s,
+                               d_tiles, d_spans, (const i16 *)d_in, d_basis, d_fb, a, (float *)d_out);
         },
         hip_failed);
 }
-
-static int64_t spec_plane(const opusgpu_spec_params &p, int64_t planned_48k, int up, int down) {
-    return rs_round64(spec_frames(p, (planned_48k * up + down - 1) / down));
-}
-static bool spec_ratio_ok(int up, int down) { return up >= 1 && up <= down && down <= 48000; }
 
 // opusgpu_files_decode_melspec and its multistream twin (og_ms_tracks.hpp): files_feature_run at the record's rate.
 static int files_melspec_run(const FilesOwner &own, int rate, int up, int down, int mono, const opusgpu_mix_matrix *mix,
                              const opusgpu_spec_params *params, const float *scale, void *d_out, int64_t *feat_offsets, int64_t *frames_out,
                              int64_t *track_lengths_out, int32_t *status_out) {
-    FeatFlow flow;
-    flow.sample_rate = spec_params_ok(params) ? (int)params->sample_rate : 0;
-    flow.scratch_failed = "hipMalloc(spectrogram scratch)";
-    flow.plane = [=](int64_t planned, int u, int d) { return spec_plane(*params, planned, u, d); };
-    flow.frames = [=](int64_t len) { return spec_frames(*params, len); };
-    flow.layout = [=](int n, const int64_t *planned, int u, int d, int64_t *feat) {
-        return opusgpu_spec_layout(n, planned, u, d, params, feat);
-    };
-    if (flow.sample_rate) flow.width = params->n_mels, flow.frames_major = params->layout == OPUSGPU_MEL_FRAMES_MAJOR;
-    flow.run = [&](int n, const opusgpu_mel_span *spans, const void *d_in, void *d_feat) {
-        return tracks_melspec_run(own.device, own.stream, n, spans, d_in, params, d_feat, own.hip_failed);
-    };
+    const bool ok = spec_params_ok(params);
+    const FeatFlow flow = feat_record_flow(
+        ok, ok ? (int)params->sample_rate : 0, ok ? params->n_mels : 0, ok && params->layout == OPUSGPU_MEL_FRAMES_MAJOR,
+        "hipMalloc(spectrogram scratch)", [=](int64_t len) { return spec_frames(*params, len); },
+        [=](int n, const int64_t *planned, int u, int d, int64_t *feat) { return opusgpu_spec_layout(n, planned, u, d, params, feat); },
+        [&own, params](int n, const opusgpu_mel_span *spans, const void *d_in, void *d_feat) {
+            return tracks_melspec_run(own.device, own.stream, n, spans, d_in, params, d_feat, own.hip_failed);
+        });
     return files_feature_run(own, rate, up, down, mono, mix, scale, d_out, feat_offsets, frames_out, track_lengths_out, status_out, flow);
 }
 
@@ -371,7 +300,7 @@ int opusgpu_spec_basis(const opusgpu_spec_params *p, const float **wc, const flo
 int opusgpu_spec_filterbank(const opusgpu_spec_params *p, const float **b) {
     if (!spec_params_ok(p)) return OPUSGPU_BAD_ARG;
     if (spec_is_fft(*p)) {
-        const std::vector<float> &bank = melfft_bank(*p);
+        const std::vector<float> &bank = melfft_tables(*p).bank;
         if (b) *b = bank.data();
         return (int)bank.size();
     }
@@ -383,14 +312,8 @@ int opusgpu_spec_filterbank(const opusgpu_spec_params *p, const float **b) {
 int opusgpu_spec_tile(const opusgpu_spec_params *p) { return spec_params_ok(p) ? spec_tile(*p) : OPUSGPU_BAD_ARG; }
 
 int64_t opusgpu_spec_layout(int n, const int64_t *planned_48k_samples, int up, int down, const opusgpu_spec_params *p, int64_t *feat_offsets) {
-    if (!spec_params_ok(p) || !spec_ratio_ok(up, down) || n < 0 || (n && !planned_48k_samples)) return OPUSGPU_BAD_ARG;
-    int64_t at = 0;
-    for (int i = 0; i < n; i++) {
-        if (planned_48k_samples[i] < 0 || planned_48k_samples[i] > INT64_MAX / 65536) return OPUSGPU_BAD_ARG;
-        if (feat_offsets) feat_offsets[i] = at;
-        at += p->n_mels * spec_plane(*p, planned_48k_samples[i], up, down);
-    }
-    return at;
+    if (!spec_params_ok(p)) return OPUSGPU_BAD_ARG;
+    return feat_grid_layout(n, planned_48k_samples, up, down, p->n_mels, [=](int64_t len) { return spec_frames(*p, len); }, feat_offsets);
 }
 
 int opusgpu_tracks_melspec_device(opusgpu_ctx *ctx, int n_tracks, const opusgpu_mel_span *spans, const void *d_in_mono,

@@ -1,23 +1,51 @@
 // og_tracks_stft.hpp -- linear and complex STFT spectrograms of the mono track at any rate, n_fft and hop (include/opusgpu.h, TRACK
-// STFT): the table per (n_fft, win_length), the kernel that turns packed int16 mono tracks into float32 spectrogram tracks, its host
-// side, and the whole-file call that ends in it.  Included at the end of og_api.hip behind og_tracks_melspec.hpp, whose tile rule it
-// takes, and og_tracks_mel.hpp, whose basis builder and packer, span record, run function and whole-file flow it shares, and in front
-// of og_ms_tracks.hpp, which holds the multistream twin of the whole-file call.  og_tracks_fft.hpp, included behind this header, holds
-// the second algorithm of the record (k_tracks_fft, OPUSGPU_STFT_ALGO_FFT): tracks_stft_run sends an FFT record there.
+// STFT): the record's rules, the table per (n_fft, win_length), the dense kernel that turns packed int16 mono tracks into float32
+// spectrogram tracks, its host side, the dispatch on the record's algorithm word and the whole-file call that ends in it.  Included
+// at the end of og_api.hip behind og_feat.hpp, whose window stage, basis builder and packer, tile rule, span record, run function
+// and whole-file flow it shares, and in front of og_ms_tracks.hpp, which holds the multistream twin of the whole-file call.
+// og_tracks_fft.hpp, included below between the rules it reads and the dispatch that sends it every FFT record, holds the second
+// algorithm of the record (k_tracks_fft, OPUSGPU_STFT_ALGO_FFT).
 #pragma once
-#include <map>
-#include <memory>
-#include <mutex>
-#include <utility>
+
+// ---- the record's rules -------------------------------------------------------------------------------
+static int stft_win(const opusgpu_stft_params &p) { return p.win_length ? p.win_length : p.n_fft; }
+
+// The record's algorithm is reserved[1]: OPUSGPU_STFT_ALGO_DENSE (k_tracks_stft, below) or OPUSGPU_STFT_ALGO_FFT (k_tracks_fft,
+// og_tracks_fft.hpp, which holds everything the FFT records alone need).
+static bool stft_is_fft(const opusgpu_stft_params &p) { return p.reserved[1] == OPUSGPU_STFT_ALGO_FFT; }
+
+static bool stft_params_ok(const opusgpu_stft_params *p) {
+    if (!p) return false;
+    if (p->sample_rate < 1 || p->sample_rate > 1048576) return false;
+    if (p->reserved[1] != OPUSGPU_STFT_ALGO_DENSE && p->reserved[1] != OPUSGPU_STFT_ALGO_FFT) return false;
+    if (!dft_shape_ok(p->n_fft, p->hop, p->win_length, stft_is_fft(*p))) return false;
+    if (p->power != OPUSGPU_STFT_COMPLEX && p->power != 1 && p->power != 2) return false;
+    if (p->log != OPUSGPU_SPEC_LOG_NONE && p->log != OPUSGPU_SPEC_LOG10 && p->log != OPUSGPU_SPEC_LN) return false;
+    if (p->power == OPUSGPU_STFT_COMPLEX && p->log != OPUSGPU_SPEC_LOG_NONE) return false;
+    if (p->frames != OPUSGPU_SPEC_FRAMES_TORCH && p->frames != OPUSGPU_SPEC_FRAMES_WHISPER) return false;
+    if (p->layout != OPUSGPU_MEL_BANDS_MAJOR && p->layout != OPUSGPU_MEL_FRAMES_MAJOR) return false;
+    if (!std::isfinite(p->floor) || p->floor < 0.f || (p->log != OPUSGPU_SPEC_LOG_NONE && !(p->floor > 0.f))) return false;
+    for (int i = 0; i < 7; i++)
+        if (i != 1 && p->reserved[i]) return false;
+    return true;
+}
+static_assert(sizeof(opusgpu_stft_params) == 64, "stft params layout");
+
+static int64_t stft_frames(const opusgpu_stft_params &p, int64_t n) {
+    return feat_frames_centered(p.frames == OPUSGPU_SPEC_FRAMES_WHISPER, p.hop, n);
+}
+static int stft_width(const opusgpu_stft_params &p) { return (p.n_fft / 2 + 1) * (p.power == OPUSGPU_STFT_COMPLEX ? 2 : 1); }
+
+#include "og_tracks_fft.hpp" // k_tracks_fft, fft_tables, fft_tile, tracks_fft_run
 
 // ---- kernel -------------------------------------------------------------------------------------------
-// k_tracks_stft<FM>: steps 1 and 2 of k_tracks_melspec (og_tracks_melspec.hpp, whose head comment says what they are) -- copied, not
-// shared, so that kernel's generated code stays what it was -- over EVERY block of 32 bins, and a second half of its own.  One
+// k_tracks_stft<FM>: steps 1 and 2 of k_tracks_melspec (og_tracks_melspec.hpp, whose head comment says what they are; the stage is
+// og_feat.hpp's, the DFT loop a copy with this kernel's operands) over EVERY block of 32 bins, and a second half of its own.  One
 // workgroup of 256 threads per tile of 128, 64 or 32 frames; all four waves stage the window, then share out the tile's groups of
 // 32 frames that exist and, where those are fewer than four, the bin blocks (below): a dense DFT has blocks to spare.
 //   3. FINISH, STORE.  The accumulators of a bin block are finished (Re^2 + Im^2, its sqrtf, the floor, a log; or left as the pair)
 //      and stored straight from the registers after every block, while the window is still live in LDS: there is no store area, so
-//      the launch asks for the window alone and the tile rule is k_tracks_melspec's (spec_tile).  What makes that coalesce is the
+//      the launch asks for the window alone and the tile rule is k_tracks_melspec's (feat_dense_tile).  What makes that coalesce is the
 //      ORDER OF THE MFMA'S OPERANDS, which is the template argument.  Both operands are held the same way -- lane l has tap l >> 5 of
 //      bin or frame l & 31 -- so swapping them transposes the result at no cost:
 //        FM false (bins-major): A = basis, B = frames.  Register r of lane l is bin 8 (r >> 2) + 4 (l >> 5) + (r & 3) of the block,
@@ -43,7 +71,7 @@ template <bool FM>
 __global__ void __launch_bounds__(256) k_tracks_stft(const MelTile *__restrict__ tiles, const MelSpan *__restrict__ spans,
                                                      const i16 *__restrict__ in, const float2 *__restrict__ basis, StftArgs a,
                                                      float *__restrict__ out) {
-    extern __shared__ __align__(16) i16 lds[]; // the window by phase, W places (stft_lds_bytes)
+    extern __shared__ __align__(16) i16 lds[]; // the window by phase, W places (feat_window_lds_bytes)
     const int tid = (int)threadIdx.x, nthr = (int)blockDim.x, lane = tid & 63, wave = tid >> 6;
     const int T = a.tile, N = a.n_fft, H = a.hop;
     const MelTile tl = tiles[blockIdx.x];
@@ -56,40 +84,10 @@ __global__ void __launch_bounds__(256) k_tracks_stft(const MelTile *__restrict__
     const int waves_on = (nf + 31) >> 5;                       // waves that have a frame
     const int W = (T - 1) * H + N;                             // the tile's window, which fixes the places
     const int Wuse = (32 * waves_on - 1) * H + N;              // what the working waves read of it
-    const int Qm = W / H, Qr = W % H;                          // row `ph` begins at ph * Qm + min(ph, Qr)
-    auto place = [=](int p) {
-        const int ph = p % H;
-        return ph * Qm + (ph < Qr ? ph : Qr) + p / H;
-    };
+    const FeatPhase ph(W, H);
 
-    // 1. the window -> LDS
-    const i16 *const trk = in + sp.in_offset;
-    const long long base = (long long)H * tl.first - N / 2;    // its first sample, counted from the track's
-    const long long qa = base < 0 ? 0 : base;                  // the track's samples inside what is used of it: [qa, qb)
-    const long long qb = n < base + Wuse ? n : base + Wuse;
-    for (long long k = (qa >> 3) + tid; 8 * k < qb; k += nthr) {
-        const uint4 v = *reinterpret_cast<const uint4 *>(trk + 8 * k);
-        const u32 w32[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int h = 0; h < 8; h++) {
-            const long long q = 8 * k + h;
-            if (q >= qa && q < qb) lds[place((int)(q - base))] = (i16)(w32[h >> 1] >> (16 * (h & 1)));
-        }
-    }
-    __syncthreads();
-    {
-        const int lo_n = base < 0 ? (int)-base : 0;                     // places in front of the track
-        const int hi_0 = n - base < Wuse ? (int)(n - base) : Wuse;      // the first place behind it
-        for (int x = tid; x < lo_n + (Wuse - hi_0); x += nthr) {
-            const int p = x < lo_n ? x : hi_0 + (x - lo_n);
-            const long long q = base + p;
-            const long long r = q < 0 ? -q : 2 * (n - 1) - q;           // reflected once
-            i16 s = 0;
-            if (r >= 0 && r < n) s = r >= qa && r < qb ? lds[place((int)(r - base))] : trk[r]; // places of the track: not written here
-            lds[place(p)] = s;
-        }
-    }
-    __syncthreads();
+    // 1. the window -> LDS: its first sample, counted from the track's, is hop * first - n_fft / 2
+    feat_stage_window(lds, ph, in + sp.in_offset, n, (long long)H * tl.first - N / 2, Wuse, tid, nthr, FeatEdgeTorch());
     // The workgroup's four waves share out the tile's groups of 32 frames that exist AND the bin blocks: with 1, 2 or 3 - 4 groups
     // a wave takes every 4th, every 2nd or every block of its group.  A tile of 32 frames, and the one tile of a short track, so
     // keep all four SIMDs at work on one window.  (The last barrier is behind every wave: one without work leaves here.)
@@ -140,8 +138,8 @@ __global__ void __launch_bounds__(256) k_tracks_stft(const MelTile *__restrict__
                 if (pa >= H) pa -= H, ca++;
                 pb -= m2, cb -= d2;
                 if (pb < 0) pb += H, cb--;
-                const float xa = __fmul_rn((float)lds[pa * Qm + (pa < Qr ? pa : Qr) + ca], scale);
-                const float xb = __fmul_rn((float)lds[pb * Qm + (pb < Qr ? pb : Qr) + cb], scale);
+                const float xa = __fmul_rn((float)lds[ph.at(pa, ca)], scale);
+                const float xb = __fmul_rn((float)lds[ph.at(pb, cb)], scale);
                 if (FM) {
                     re = __builtin_amdgcn_mfma_f32_32x32x2f32(xa + xb, w0[j].x, re, 0, 0, 0);
                     im = __builtin_amdgcn_mfma_f32_32x32x2f32(xb - xa, w0[j].y, im, 0, 0, 0);
@@ -185,74 +183,26 @@ struct StftTables {
     std::vector<float> none;        // tracks_feature_run's second table: this kernel has no filterbank
 };
 
-static int stft_win(const opusgpu_stft_params &p) { return p.win_length ? p.win_length : p.n_fft; }
-
-// The record's algorithm is reserved[1]: OPUSGPU_STFT_ALGO_DENSE (k_tracks_stft, below) or OPUSGPU_STFT_ALGO_FFT (k_tracks_fft,
-// og_tracks_fft.hpp, which is included behind this header and holds everything the FFT records alone need).
-static bool stft_is_fft(const opusgpu_stft_params &p) { return p.reserved[1] == OPUSGPU_STFT_ALGO_FFT; }
-
-static bool stft_params_ok(const opusgpu_stft_params *p) {
-    if (!p) return false;
-    if (p->sample_rate < 1 || p->sample_rate > 1048576) return false;
-    if (p->reserved[1] != OPUSGPU_STFT_ALGO_DENSE && p->reserved[1] != OPUSGPU_STFT_ALGO_FFT) return false;
-    if (stft_is_fft(*p)) {
-        if (p->n_fft < 64 || p->n_fft > 8192 || (p->n_fft & (p->n_fft - 1))) return false;
-        if (p->hop < 1 || p->hop > p->n_fft) return false;
-    } else {
-        if (p->n_fft < 64 || p->n_fft > 2048 || p->n_fft % 16) return false;
-        if (p->hop < 1 || p->hop > p->n_fft || 31 * p->hop + p->n_fft > MS_MAXW) return false;
-    }
-    if (p->win_length && (p->win_length < 16 || p->win_length > p->n_fft || p->win_length % 2)) return false;
-    if (p->power != OPUSGPU_STFT_COMPLEX && p->power != 1 && p->power != 2) return false;
-    if (p->log != OPUSGPU_SPEC_LOG_NONE && p->log != OPUSGPU_SPEC_LOG10 && p->log != OPUSGPU_SPEC_LN) return false;
-    if (p->power == OPUSGPU_STFT_COMPLEX && p->log != OPUSGPU_SPEC_LOG_NONE) return false;
-    if (p->frames != OPUSGPU_SPEC_FRAMES_TORCH && p->frames != OPUSGPU_SPEC_FRAMES_WHISPER) return false;
-    if (p->layout != OPUSGPU_MEL_BANDS_MAJOR && p->layout != OPUSGPU_MEL_FRAMES_MAJOR) return false;
-    if (!std::isfinite(p->floor) || p->floor < 0.f || (p->log != OPUSGPU_SPEC_LOG_NONE && !(p->floor > 0.f))) return false;
-    for (int i = 0; i < 7; i++)
-        if (i != 1 && p->reserved[i]) return false;
-    return true;
-}
-static_assert(sizeof(opusgpu_stft_params) == 64, "stft params layout");
-
 // The tables of a parameter set that stft_params_ok has passed; safe from any number of threads.
 static const StftTables &stft_tables(const opusgpu_stft_params &p) {
-    static std::mutex mu;
-    static std::map<std::pair<int, int>, std::unique_ptr<StftTables>> cache;
-    const std::pair<int, int> key(p.n_fft, stft_win(p));
-    std::lock_guard<std::mutex> lock(mu);
-    auto it = cache.find(key);
-    if (it == cache.end()) {
+    return feat_cached<std::pair<int, int>, StftTables>({p.n_fft, stft_win(p)}, [&] {
         std::unique_ptr<StftTables> t(new StftTables);
         t->n_fft = p.n_fft, t->bins = p.n_fft / 2 + 1, t->n_blocks = (t->bins + 31) / 32;
         mel_basis_make(p.n_fft, stft_win(p), t->wc, t->ws);
         std::vector<int> all((size_t)t->n_blocks);
         for (int nb = 0; nb < t->n_blocks; nb++) all[(size_t)nb] = nb;
         t->basis = feat_pack_basis(t->wc, t->ws, p.n_fft, all);
-        it = cache.emplace(key, std::move(t)).first;
-    }
-    return *it->second;
+        return t;
+    });
 }
 
 // ---- host side ----------------------------------------------------------------------------------------
-static int64_t stft_frames(const opusgpu_stft_params &p, int64_t n) {
-    return p.frames == OPUSGPU_SPEC_FRAMES_WHISPER ? n / p.hop : n ? n / p.hop + 1 : 0;
-}
-static int stft_width(const opusgpu_stft_params &p) { return (p.n_fft / 2 + 1) * (p.power == OPUSGPU_STFT_COMPLEX ? 2 : 1); }
-// The tile in frames: spec_tile's rule, the largest of 128, 64, 32 whose window fits 65,536 bytes -- the launch's LDS is the window
-// alone, since the kernel stores from its accumulators.
-static int fft_tile(const opusgpu_stft_params &p); // og_tracks_fft.hpp
-static int tracks_fft_run(int device, hipStream_t s, int n_tracks, const opusgpu_mel_span *spans, const void *d_in,
-                          const opusgpu_stft_params *params, void *d_out, const TrackFail &hip_failed);
-static int stft_tile(const opusgpu_stft_params &p) {
-    if (stft_is_fft(p)) return fft_tile(p);
-    for (int T = 128; T > 32; T >>= 1)
-        if ((T - 1) * p.hop + p.n_fft <= MS_MAXW) return T;
-    return 32;
-}
-static size_t stft_lds_bytes(const opusgpu_stft_params &p, int T) { return (((size_t)(T - 1) * p.hop + p.n_fft) * 2 + 15) / 16 * 16; }
+// The tile in frames: of a dense record feat_dense_tile's -- the launch's LDS is the window alone, since the kernel stores from its
+// accumulators --, of an FFT record fft_tile's.
+static int stft_tile(const opusgpu_stft_params &p) { return stft_is_fft(p) ? fft_tile(p) : feat_dense_tile(p.hop, p.n_fft); }
 
-// k_tracks_stft over n tracks (og_tracks_mel.hpp: tracks_feature_run; the frames' bound is tracks_melspec_run's).
+// k_tracks_stft, or for an FFT record k_tracks_fft, over n tracks (og_feat.hpp: tracks_feature_run; the frames' bound is
+// tracks_melspec_run's).
 static int tracks_stft_run(int device, hipStream_t s, int n_tracks, const opusgpu_mel_span *spans, const void *d_in,
                            const opusgpu_stft_params *params, void *d_out, const TrackFail &hip_failed) {
     if (!stft_params_ok(params)) return OPUSGPU_BAD_ARG;
@@ -271,8 +221,8 @@ static int tracks_stft_run(int device, hipStream_t s, int n_tracks, const opusgp
             a.power = params->power, a.log = params->log, a.whisper_frames = params->frames == OPUSGPU_SPEC_FRAMES_WHISPER;
             a.floor = params->floor;
             auto go = [&](auto kern) {
-                hipLaunchKernelGGL(kern, dim3(n_tiles), dim3(256), stft_lds_bytes(*params, T), s, d_tiles, d_spans, (const i16 *)d_in,
-                                   d_basis, a, (float *)d_out);
+                hipLaunchKernelGGL(kern, dim3(n_tiles), dim3(256), feat_window_lds_bytes(params->hop, params->n_fft, T, false), s, d_tiles,
+                                   d_spans, (const i16 *)d_in, d_basis, a, (float *)d_out);
             };
             if (params->layout == OPUSGPU_MEL_FRAMES_MAJOR)
                 go(k_tracks_stft<true>);
@@ -280,10 +230,6 @@ static int tracks_stft_run(int device, hipStream_t s, int n_tracks, const opusgp
                 go(k_tracks_stft<false>);
         },
         hip_failed);
-}
-
-static int64_t stft_plane(const opusgpu_stft_params &p, int64_t planned_48k, int up, int down) {
-    return rs_round64(stft_frames(p, (planned_48k * up + down - 1) / down));
 }
 
 // STFT BATCHES (og_stft_batch.hpp, behind this header): the stage that turns a packed grid into the dense tensor, and the pad cells
@@ -306,18 +252,14 @@ static int files_stft_run(const FilesOwner &own, int rate, int up, int down, int
         if (own.refused) own.refused("feature batch: STFT spectrograms are not batched (widths of 1 - 128 only)");
         return OPUSGPU_BAD_ARG;
     }
-    FeatFlow flow;
-    flow.sample_rate = stft_params_ok(params) ? (int)params->sample_rate : 0;
-    flow.scratch_failed = "hipMalloc(stft scratch)";
-    flow.plane = [=](int64_t planned, int u, int d) { return stft_plane(*params, planned, u, d); };
-    flow.frames = [=](int64_t len) { return stft_frames(*params, len); };
-    flow.layout = [=](int n, const int64_t *planned, int u, int d, int64_t *feat) {
-        return opusgpu_stft_layout(n, planned, u, d, params, feat);
-    };
-    if (flow.sample_rate) flow.width = stft_width(*params), flow.frames_major = params->layout == OPUSGPU_MEL_FRAMES_MAJOR;
-    flow.run = [&](int n, const opusgpu_mel_span *spans, const void *d_in, void *d_feat) {
-        return tracks_stft_run(own.device, own.stream, n, spans, d_in, params, d_feat, own.hip_failed);
-    };
+    const bool ok = stft_params_ok(params);
+    FeatFlow flow = feat_record_flow(
+        ok, ok ? (int)params->sample_rate : 0, ok ? stft_width(*params) : 0, ok && params->layout == OPUSGPU_MEL_FRAMES_MAJOR,
+        "hipMalloc(stft scratch)", [=](int64_t len) { return stft_frames(*params, len); },
+        [=](int n, const int64_t *planned, int u, int d, int64_t *feat) { return opusgpu_stft_layout(n, planned, u, d, params, feat); },
+        [&own, params](int n, const opusgpu_mel_span *spans, const void *d_in, void *d_feat) {
+            return tracks_stft_run(own.device, own.stream, n, spans, d_in, params, d_feat, own.hip_failed);
+        });
     const StftBatchState *sb = own.sbatch && own.sbatch->req.enabled && flow.sample_rate ? own.sbatch : nullptr;
     FeatDense dense;
     if (sb) {
@@ -355,14 +297,8 @@ int opusgpu_stft_basis(const opusgpu_stft_params *p, const float **wc, const flo
 int opusgpu_stft_tile(const opusgpu_stft_params *p) { return stft_params_ok(p) ? stft_tile(*p) : OPUSGPU_BAD_ARG; }
 
 int64_t opusgpu_stft_layout(int n, const int64_t *planned_48k_samples, int up, int down, const opusgpu_stft_params *p, int64_t *feat_offsets) {
-    if (!stft_params_ok(p) || !spec_ratio_ok(up, down) || n < 0 || (n && !planned_48k_samples)) return OPUSGPU_BAD_ARG;
-    int64_t at = 0;
-    for (int i = 0; i < n; i++) {
-        if (planned_48k_samples[i] < 0 || planned_48k_samples[i] > INT64_MAX / 65536) return OPUSGPU_BAD_ARG;
-        if (feat_offsets) feat_offsets[i] = at;
-        at += stft_width(*p) * stft_plane(*p, planned_48k_samples[i], up, down);
-    }
-    return at;
+    if (!stft_params_ok(p)) return OPUSGPU_BAD_ARG;
+    return feat_grid_layout(n, planned_48k_samples, up, down, stft_width(*p), [=](int64_t len) { return stft_frames(*p, len); }, feat_offsets);
 }
 
 int opusgpu_tracks_stft_device(opusgpu_ctx *ctx, int n_tracks, const opusgpu_mel_span *spans, const void *d_in_mono,

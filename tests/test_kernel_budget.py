@@ -27,6 +27,14 @@ BUDGET = {
     "k_celt_post": (128, 0),
     "k_decode_rfc": (256, 1024),   # two waves per SIMD (launch bound; it spills)
     "k_stream_stall": (8, 0),      # OPUSGPU_STALL_STREAM (og_debug.hpp): a clock loop that writes no memory -- no scratch, no LDS either
+    # the feature kernels (og_feat.hpp and the og_tracks_* headers): the occupancy step each one's count sits under; no scratch.  A
+    # template's bound holds for every instantiation
+    "k_tracks_melspec": (256, 0),  # 252, of which 124 accumulators
+    "k_tracks_fbank": (256, 0),    # 232 / 100
+    "k_tracks_mel": (256, 0),      # <4>: 224 / 96, <3>: 200 / 88
+    "k_tracks_stft": (168, 0),     # <true>: 162 / 58; <false> is at 126 / 38, under the 128 step
+    "k_tracks_melfft": (64, 0),    # 62
+    "k_tracks_fft": (64, 0),       # <true>: 50, <false>: 45
 }
 
 
@@ -64,8 +72,9 @@ def test_kernels_keep_their_register_budgets():
     seen = {}
     for mangled, (vgpr, scratch, lds) in meta.items():
         for k in BUDGET:
-            if re.search(r"\d+" + k + r"(P|E|v|x|$)", mangled) or mangled == k:
-                seen[k] = (vgpr, scratch, lds)
+            if re.search(r"\d+" + k + r"(P|E|v|x|I|$)", mangled) or mangled == k:  # (I: a template's instantiations, each within the budget)
+                was = seen.get(k, (0, 0, 0))
+                seen[k] = (max(was[0], vgpr), max(was[1], scratch), max(was[2], lds))
     missing = [k for k in BUDGET if k not in seen]
     assert not missing, f"kernels not found in the library's code objects: {missing} (have {sorted(meta)[:6]}...)"
     over = {k: seen[k] for k in BUDGET if seen[k][0] > BUDGET[k][0] or seen[k][1] > BUDGET[k][1]}
